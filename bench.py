@@ -157,6 +157,43 @@ def parity_in_run(snap, kept, lane_hosts, levels, max_kp, log_bucket, bucket_lim
             **({"first_mismatch": bad} if bad else {})}
 
 
+DUMP_BYTES = 64_000_000                                   # --dump-outputs: bytes of array data in all, at most
+DUMP_SEED = 0x5eed                                        # the order in which pyramids enter a sample that must be cut
+
+
+def dump_outputs(path, kp, desc, counts, max_kp, match=None, budget=DUMP_BYTES):
+    """--dump-outputs: one step's outputs as float64 .npy files (every 32-bit word is exact in float64).
+      kp [B][max_kp], desc [B][max_kp][words], counts [B]: uint32 host arrays of the output set the step wrote;
+      match = (idx, dist, dist2) [B][max_kp] int32 of the matcher (--match) or None.
+    Written: counts.npy [B] (the reference's un-clamped counts, every pyramid), pyramids.npy [P] (the batch indices whose
+    keypoints follow), keypoints.npy [N] (the packed keypoint words of those pyramids in order, min(count, max_kp) each),
+    descriptors.npy [N][words], and with --match match_idx.npy / match_dist.npy / match_dist2.npy [N].  Slots past a
+    pyramid's count are never written: they hold no result.  P = B unless the arrays would exceed `budget` bytes; then the
+    pyramids are taken in a fixed seeded order while they fit and dumped in batch order."""
+    import numpy as np
+    B, words = len(counts), desc.shape[2]
+    n = np.minimum(counts.astype(np.int64), max_kp)
+    per_kp = 8 * (1 + words + (3 if match is not None else 0))
+    room = budget - 8 * 2 * B - 1024                        # counts.npy, pyramids.npy, the .npy headers
+    order = np.random.default_rng(DUMP_SEED).permutation(B)
+    take = np.sort(order[np.cumsum(n[order] * per_kp) <= room])
+    sel = [(b, int(n[b])) for b in take]
+    arrays = {"counts": counts, "pyramids": take,
+              "keypoints": np.concatenate([kp[b, :m] for b, m in sel] + [kp[:0, 0]]),
+              "descriptors": np.concatenate([desc[b, :m] for b, m in sel] + [desc[:0, 0]])}
+    if match is not None:
+        for name, a in zip(("match_idx", "match_dist", "match_dist2"), match):
+            arrays[name] = np.concatenate([a[b, :m] for b, m in sel] + [a[:0, 0]])
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = a.astype(np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    return {"dir": path, "arrays": {k: list(v.shape) for k, v in arrays.items()}, "bytes": total,
+            "pyramids": f"{len(take)} of {B}" + ("" if len(take) == B else f" (seeded sample, seed {DUMP_SEED:#x})")}
+
+
 # ---------------------------------------------------------------------------------------------------------
 # other_workloads: every other BASELINE configuration, briefly, inside the driver's one line
 # ---------------------------------------------------------------------------------------------------------
@@ -290,6 +327,10 @@ def build_parser():
     ap.add_argument("--log-bucket-size", type=int, default=0, help="fastExtract logBucketSize (README uses 4)")
     ap.add_argument("--bucket-limit", type=int, default=5, help="fastExtract bucketLimit (README uses 3)")
     ap.add_argument("--ablate", type=int, default=0, help="profiling only (results invalid): fused-kernel phase mask")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (rank 0) as float64 "
+                         "DIR/<name>.npy, at most 64 MB in all (see dump_outputs); the synthetic input then never depends on "
+                         "the host's core count, so that two builds can be compared output for output")
     # ---- supervision of the N>1 run ----
     ap.add_argument("--wall-cap", type=float, default=900.0,
                     help="wall-clock cap in seconds for the whole run incl. every fallback attempt (rc != 0 beyond it)")
@@ -652,8 +693,9 @@ def worker_main(args):
     nlane_in = 1 if args.shared_input else S
     gen_workers = args.gen_workers or max(1, min(16, int(effective_cores()[1]) // max(1, min(world, 8))))
     # (the generator takes ~60 ms per VGA pyramid and host thread: on a host with few usable cores per rank the input is
-    #  built from fewer different pyramids, each lane's batch tiling them — the bench must start within its attempt timeout)
-    if not args.distinct:
+    #  built from fewer different pyramids, each lane's batch tiling them — the bench must start within its attempt timeout;
+    #  not under --dump-outputs, whose outputs must come from the same input on every host)
+    if not args.distinct and not args.dump_outputs:
         px = w0 * h0 / (640.0 * 480.0)
         while nd > 16 and nd * nlane_in * 0.06 * px / gen_workers > 40.0:
             nd //= 2
@@ -895,6 +937,13 @@ def worker_main(args):
         torch.distributed.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the output set the LAST timed step wrote (its lane's; nothing has run since), before the pipelines run again
+        o = last_out[0]
+        dumped = dump_outputs(args.dump_outputs, *(t.cpu().numpy().view(np.uint32) for t in o), args.max_keypoints,
+                              match=[t.cpu().numpy() for t in m_out] if m_out is not None else None)
+        dumped["lane"] = (tick[0] - 1) % S
     # parity_in_run: what the timed steps left in the lanes' output sets (the set the lane's LAST timed step wrote), copied
     # now — before anything else touches the pipelines
     snap = None
@@ -1205,6 +1254,7 @@ def worker_main(args):
                 **({"pyramid_build": build_info} if build_info else {}),
                 **({"match_inside_step": match_info} if match_info else {}),
             },
+            **({"dump_outputs": dumped} if dumped else {}),
             "roofline": {
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": prof_source,

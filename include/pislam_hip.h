@@ -58,7 +58,8 @@ int pislam_ctx_set_stream(pislam_ctx *ctx, void *hip_stream);
  *                (device-pointer inputs must then be complete, or ordered by the caller, before a call); 0 = back to the null stream
  *   "sub_batches" fused batch path: 1 (default) one launch group; n <= 16: the batch is cut into n sub-batches whose overflow
  *                pass + gather/ORB kernels run on a context-owned second stream under the next sub-batch's strip kernel
- *                (fork / join by events inside the call; results and stream semantics unchanged, hipGraph-capturable;
+ *                (fork / join by events inside the call; results and stream semantics unchanged; a call captured into a
+ *                hipGraph runs its sub-batches in order on the context stream;
  *                measured slower than one launch group on MI355X — DESIGN.md); 0: by size ("sub_mb" MiB per sub-batch, 128)
  *   "pipeline"   0 auto, 1 staged (one launch group per reference call, HBM score map), 2 fused strips
  *   "dump_score" fused pipeline also materialises the score map (pislam_frontend_get_score_map)

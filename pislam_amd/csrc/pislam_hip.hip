@@ -164,7 +164,8 @@ struct pislam_ctx {
   bool timing_valid = false;
   // Sub-batch pipelining of the fused batch path (run_fused): the strip kernels of the sub-batches run back to
   // back on the context stream, the overflow pass + gather/ORB kernel of sub-batch i on `aux_stream` under the
-  // strip kernel of sub-batch i+1 (fork / join with events: one call, one context, capturable in a hipGraph).
+  // strip kernel of sub-batch i+1 (fork / join with events: one call, one context).  A call being captured into a
+  // hipGraph runs its sub-batches in order on the context stream instead (run_fused).
   static constexpr int MAX_SUB = 16;
   int opt_sub_batches = 1;             // 1 = one launch group (default), n = n sub-batches, 0 = by bytes per sub-batch
   int opt_sub_mb = 0;                  // auto rule: target MiB of pyramids per sub-batch (0 = default)
@@ -1670,7 +1671,16 @@ int run_fused(pislam_ctx *c, const pislam_frontend_params *p, const pf::FusedPar
     PCHK(prepare_ovf(c, nsub, ovf_stride));
     c->last_strips = (uint32_t)S * (uint32_t)batch;
   }
-  if (nsub > 1) PCHK(ensure_aux(c, nsub));
+  // A call that is being captured into a hipGraph does not fork: its sub-batches then run in order on the context stream, and
+  // the graph is one chain of nodes like every other captured call.  (A graph with a parallel branch from the fork crashed
+  // inside hipGraphLaunch when it was replayed; chains replay fine.)  Eager calls fork as before.
+  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+  if (nsub > 1 && hipStreamIsCapturing(c->stream, &capture) != hipSuccess) {
+    (void)hipGetLastError();                      // (the query's own error must not be reported by a later launch check)
+    capture = hipStreamCaptureStatusNone;
+  }
+  const bool fork = nsub > 1 && capture == hipStreamCaptureStatusNone;
+  if (fork) PCHK(ensure_aux(c, nsub));
   // HOOKS instantiations: score-map dump (debug / parity hook) and the profiling ablations
   const bool hooks = Fplan.dump_score || Fplan.ablate;
   using KernT = void (*)(const pf::FusedParams, const uint8_t *, size_t, uint32_t *, uint32_t *, uint8_t *, size_t,
@@ -1776,7 +1786,7 @@ int run_fused(pislam_ctx *c, const pislam_frontend_params *p, const pf::FusedPar
     }
   }
   const int base = batch / nsub, rem = batch % nsub;
-  hipStream_t M = c->stream, X = nsub > 1 ? c->aux_stream : c->stream;
+  hipStream_t M = c->stream, X = fork ? c->aux_stream : c->stream;
   for (int sub = 0; sub < nsub; sub++) {
     const int first = sub * base + std::min(sub, rem), n = base + (sub < rem ? 1 : 0);
     pf::FusedParams F = Fplan;
@@ -1830,9 +1840,11 @@ int run_fused(pislam_ctx *c, const pislam_frontend_params *p, const pf::FusedPar
     }
     PCHK(launch_ok(c, "k_fused_strips"));
     if (nsub > 1) {
-      // fork: the rest of this sub-batch runs on the aux stream, under the next sub-batch's strip kernel
-      HIPCHK(c, hipEventRecord(c->ev_sub[sub], M));
-      HIPCHK(c, hipStreamWaitEvent(X, c->ev_sub[sub], 0));
+      if (fork) {
+        // fork: the rest of this sub-batch runs on the aux stream, under the next sub-batch's strip kernel
+        HIPCHK(c, hipEventRecord(c->ev_sub[sub], M));
+        HIPCHK(c, hipStreamWaitEvent(X, c->ev_sub[sub], 0));
+      }
       if (sub == nsub - 1) {
         HIPCHK(c, hipEventRecord(c->ev[1], M));   // stage 0 = every sub-batch's strip kernel
         HIPCHK(c, hipEventRecord(c->ev[2], M));   // (stage 1, the overflow passes, runs on the aux stream)
@@ -1877,7 +1889,7 @@ int run_fused(pislam_ctx *c, const pislam_frontend_params *p, const pf::FusedPar
       PCHK(launch_ok(c, "k_gather_orb"));
     }
   }
-  if (nsub > 1) {                                   // join: the call is complete, in stream order, on the context stream
+  if (fork) {                                       // join: the call is complete, in stream order, on the context stream
     HIPCHK(c, hipEventRecord(c->ev_join, X));
     HIPCHK(c, hipStreamWaitEvent(M, c->ev_join, 0));
   }

@@ -53,3 +53,43 @@ def test_parity_in_run_accepts_the_oracle_and_rejects_every_kind_of_mismatch(orc
     out = bench.parity_in_run([_snap(res, 2048)], res, [host], levels, 2048, 0, 5, pins=len(res[0][0]) + 1)
     assert not out["ok"] and "pin" in out["first_mismatch"]
     assert not bench.parity_in_run([_snap(res, 2048)], [], [host], levels, 2048, 0, 5)["ok"]   # nothing compared is not a pass
+
+
+def test_dump_outputs_writes_the_stored_results_exactly_and_keeps_to_its_budget(tmp_path):
+    """bench.py --dump-outputs: float64 files whose words equal the uint32 outputs bit for bit (high bits included), only the
+    slots a pyramid's count covers (capacity clipping included), and past the byte budget a seeded sample of whole pyramids
+    that is the same on every call."""
+    import bench
+    rng = np.random.default_rng(3)
+    B, max_kp, words = 12, 64, 8
+    kp = rng.integers(0, 1 << 32, (B, max_kp), dtype=np.uint32)          # slots past the count hold garbage here
+    desc = rng.integers(0, 1 << 32, (B, max_kp, words), dtype=np.uint32)
+    counts = rng.integers(0, 90, B).astype(np.uint32)                      # some beyond max_kp: clipped storage
+    counts[3] = 0
+    match = [rng.integers(-1, 1 << 20, (B, max_kp)).astype(np.int32) for _ in range(3)]
+    n = np.minimum(counts, max_kp).astype(int)
+
+    def load(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+
+    info = bench.dump_outputs(str(tmp_path / "all"), kp, desc, counts, max_kp, match=match)
+    a = load(tmp_path / "all")
+    assert set(a) == {"counts", "pyramids", "keypoints", "descriptors", "match_idx", "match_dist", "match_dist2"}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert info["pyramids"] == f"{B} of {B}" and info["bytes"] == sum(v.nbytes for v in a.values())
+    assert (a["counts"] == counts).all() and (a["pyramids"] == np.arange(B)).all()
+    assert (a["keypoints"].astype(np.uint32) == np.concatenate([kp[b, :n[b]] for b in range(B)])).all()
+    assert (a["descriptors"].astype(np.uint32) == np.concatenate([desc[b, :n[b]] for b in range(B)])).all()
+    assert (a["match_dist2"] == np.concatenate([match[2][b, :n[b]] for b in range(B)])).all()
+
+    budget = 2 * 1024 + 8 * 9 * int(n.sum()) // 2                           # room for about half of the keypoints
+    picks = []
+    for d in ("half", "again"):
+        info = bench.dump_outputs(str(tmp_path / d), kp, desc, counts, max_kp, budget=budget)
+        h = load(tmp_path / d)
+        assert "match_idx" not in h and info["bytes"] <= budget and 0 < len(h["pyramids"]) < B
+        p = h["pyramids"].astype(int)
+        assert (np.diff(p) > 0).all() and (h["counts"] == counts).all()
+        assert (h["descriptors"].astype(np.uint32) == np.concatenate([desc[b, :n[b]] for b in p])).all()
+        picks.append(p)
+    assert (picks[0] == picks[1]).all()

@@ -117,15 +117,20 @@ def test_cpp_tool_batch_path_and_rccl_binding(tmp_path, demo_files, rccl, stream
 
 @pytest.mark.gpu
 def test_cpp_tool_two_processes_two_gpus(demo_files):
-    """One process per GPU from C++ (fork before HIP, id through a file, ncclCommInitRank, ncclAllGather):
-    needs two GPUs — RCCL refuses two ranks on one device."""
+    """One process per GPU from C++ (fork before HIP, id through a file, ncclCommInitRank, ncclAllGather).  The exchange
+    needs two GPUs: RCCL refuses two ranks on one device ("Duplicate GPU detected").  With one GPU the tool must refuse
+    the second rank itself: both ranks, forked before HIP, start their own HIP runtime, see the one device and exit 12
+    saying so (world 1 over RCCL is covered by --rccl-single)."""
     import torch
-    if torch.cuda.device_count() < 2:
-        pytest.skip("needs >= 2 GPUs (the gpurun box has one); world 1 over RCCL is covered by --rccl-single")
     exe = build_tool()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([exe, str(demo_files[0]), "--batch", "4", "--steps", "3", "--world", "2"], capture_output=True,
-                       text=True, timeout=600, env=env)
+    cmd = [exe, str(demo_files[0]), "--batch", "4", "--steps", "3", "--world", "2"]
+    if torch.cuda.device_count() < 2:
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 12, (r.stdout, r.stderr)
+        assert r.stderr.count("--world 2 needs 2 GPUs (one process per GPU), 1 visible") == 2, r.stderr
+        return
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, (r.stdout, r.stderr)
     assert f"{8 * 1754} features in 8 pyramids" in r.stdout and "2 ranks" in r.stdout
 
