@@ -363,6 +363,40 @@ int pislam_match_hamming_batch(pislam_ctx *ctx, int words, const uint32_t *query
                                const uint32_t *tcounts, size_t t_stride, int batch, int32_t *idx,
                                uint32_t *dist, uint32_t *dist2);
 
+/* Spatially windowed form for frame-to-frame tracking (DESIGN.md, section
+ * 5.5): pair b matches query i < nq_b = min(qcounts[b], q_stride) only against
+ * the train entries j < nt_b = min(tcounts[b], t_stride) near its position
+ * (a count of PISLAM_COUNT_INVALID counts as 0).  Positions are encodeFast
+ * words of the stacked pyramid (x = (k >> 12) & 0xfff, y = k & 0xfff; score
+ * bits ignored), keypoints [batch][stride] as pislam_orb_frontend_batch writes
+ * them; the level of a position is the level whose rectangle
+ * [col0, col0+width) x [row0, row0+height) holds it.  Train j is a candidate
+ * for query i when both have a level, the same level l, and
+ * |xq - xt| <= radius[l] and |yq - yt| <= radius[l] (a square window in that
+ * level's pixels).  Outputs as pislam_match_hamming_batch, restricted to the
+ * candidates: idx = the candidate with the smallest Hamming distance (ties:
+ * the smallest train index; -1 without candidates), dist = that distance
+ * (0xffffffff without candidates), dist2 = the smallest distance among the
+ * other candidates (0xffffffff with fewer than 2); idx indexes the caller's
+ * train array.  A query position in no level has no candidates.  Outputs are
+ * [batch][q_stride]; entries at and beyond nq_b are not written.
+ * words in {1,2,4,8}; 1 <= nlevels <= 16, level rectangles non-empty,
+ * disjoint, inside 12-bit coordinates; 0 <= radius[l] <= 4095;
+ * t_stride <= 65535.  Anything else: PISLAM_ERR_INVALID.  Device pointers
+ * only, except `levels` and `radius` (host arrays, read during the call).
+ * Asynchronous on the context stream.  The workspace lives in the context and
+ * grows on demand, which synchronises; after pislam_match_window_reserve of
+ * the same or a larger shape the call allocates nothing and never
+ * synchronises, so it can be captured into a hipGraph. */
+int pislam_match_window_reserve(pislam_ctx *ctx, int words, const pislam_level *levels, int nlevels,
+                                const int32_t *radius, size_t t_stride, int batch);
+int pislam_match_hamming_window_batch(pislam_ctx *ctx, int words,
+                                      const pislam_level *levels, int nlevels, const int32_t *radius,
+                                      const uint32_t *qkp, const uint32_t *qdesc, const uint32_t *qcounts,
+                                      size_t q_stride, const uint32_t *tkp, const uint32_t *tdesc,
+                                      const uint32_t *tcounts, size_t t_stride, int batch, int32_t *idx,
+                                      uint32_t *dist, uint32_t *dist2);
+
 /* ---- multi-GPU: one process per GPU, pyramids sharded, ONE collective ---- */
 
 /* The reference is a single-threaded per-frame loop without cross-frame state

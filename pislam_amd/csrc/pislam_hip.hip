@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <functional>
 #include <string>
 #include <vector>
@@ -105,6 +106,7 @@ struct pislam_ctx {
   // batch pipeline workspace
   DevBuf w_score, w_stage, w_stripcnt, w_work, w_prof, w_ovf, w_stagedesc;
   DevBuf w_ustage, w_ucount;         // bucket selection pass (pf::k_bucket_select): per-unit lists and counts
+  DevBuf w_win_off, w_win_meta, w_win_desc;   // windowed matcher: cell offsets, cell-sorted train entries (pm::k_window_index)
   // Host-built plan tables the kernels read instead of walking the plan (the bucket selection pass's unit table): one
   // device buffer per distinct CONTENT, never rewritten in place — a captured graph keeps reading the table
   // of the plan it was captured with whatever other shapes the context serves in between.  At most 16 are kept (the oldest
@@ -501,7 +503,8 @@ PISLAM_EXPORT int pislam_ctx_destroy(pislam_ctx *c) {
   (void)hipStreamSynchronize(c->stream);
   for (DevBuf *b : {&c->s_img, &c->s_out, &c->s_pts, &c->s_desc, &c->s_misc, &c->s_rots, &c->s_tmp, &c->w_cnt,
                     &c->w_off, &c->w_total, &c->w_cellkp, &c->w_score, &c->w_stage, &c->w_stripcnt, &c->w_work, &c->w_prof, &c->w_ovf,
-                    &c->w_stagedesc, &c->w_ustage, &c->w_ucount, &c->w_sync, &c->w_chain})
+                    &c->w_stagedesc, &c->w_ustage, &c->w_ucount, &c->w_sync, &c->w_chain, &c->w_win_off, &c->w_win_meta,
+                    &c->w_win_desc})
     b->release();
   for (auto *t : c->plan_tables) {
     t->dev.release();
@@ -2304,6 +2307,112 @@ PISLAM_EXPORT int pislam_match_hamming_batch(pislam_ctx *c, int words, const uin
   HIPCHK(c, hipSetDevice(c->device));
   return launch_match(c, words, query, qcounts, q_stride, 0, train, tcounts, t_stride, 0, batch, (uint32_t)q_stride,
                       idx, dist, dist2, q_stride);
+}
+
+// ---- spatially windowed matching ----------------------------------------------------
+
+namespace {
+
+// Checks the arguments every windowed call shares and lays out the per-pair cell grid (host only).  Cell side of
+// level l: max(1, radius[l]) * f with the smallest f >= 1 that keeps all levels' cells within pm::WIN_MAX_CELLS
+// (the LDS histogram of k_window_index).  Results do not depend on the side: the match applies the exact window test.
+int window_plan(pislam_ctx *c, int words, const pislam_level *lv, int nlevels, const int32_t *radius, size_t t_stride,
+                int batch, pm::WinPlan *P) {
+  if (words != 1 && words != 2 && words != 4 && words != 8) return fail(c, PISLAM_ERR_INVALID, "words must be 1, 2, 4 or 8");
+  if (nlevels < 1 || nlevels > pm::WIN_MAX_LEVELS) return fail(c, PISLAM_ERR_INVALID, "nlevels must be 1..16");
+  if (!lv || !radius) return fail(c, PISLAM_ERR_INVALID, "null levels / radius");
+  if (t_stride > 65535) return fail(c, PISLAM_ERR_INVALID, "at most 65535 train entries per pair");
+  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
+  for (int l = 0; l < nlevels; l++) {
+    const pislam_level &L = lv[l];
+    if (L.width < 1 || L.height < 1 || L.col0 < 0 || L.row0 < 0 || L.col0 + L.width > 4096 || L.row0 + L.height > 4096)
+      return fail(c, PISLAM_ERR_INVALID, "level rectangles must be non-empty and fit 12-bit coordinates");
+    if (radius[l] < 0 || radius[l] > 4095) return fail(c, PISLAM_ERR_INVALID, "radius must be 0..4095");
+    for (int k = 0; k < l; k++) {
+      const pislam_level &K = lv[k];
+      if (L.col0 < K.col0 + K.width && K.col0 < L.col0 + L.width && L.row0 < K.row0 + K.height && K.row0 < L.row0 + L.height)
+        return fail(c, PISLAM_ERR_INVALID, "level rectangles overlap");
+    }
+  }
+  auto side = [&](int l, long long f) { return (int)std::min<long long>(4096, std::max(1, radius[l]) * f); };
+  auto cells = [&](long long f) {
+    long long n = 0;
+    for (int l = 0; l < nlevels; l++) n += (long long)cdiv(lv[l].width, side(l, f)) * cdiv(lv[l].height, side(l, f));
+    return n;
+  };
+  // cells(f) ~ cells(1) / f^2: start just below that estimate; side 4096 leaves one cell per level, so this ends
+  long long f = std::max(1LL, (long long)std::sqrt((double)cells(1) / pm::WIN_MAX_CELLS));
+  while (cells(f) > pm::WIN_MAX_CELLS) f++;
+  *P = pm::WinPlan{};
+  int base = 0;
+  for (int l = 0; l < nlevels; l++) {
+    const int s = side(l, f), ncx = cdiv(lv[l].width, s);
+    P->lv[l] = pm::WinLevel{lv[l].col0, lv[l].row0, lv[l].width, lv[l].height, radius[l], s, ncx, base};
+    base += ncx * cdiv(lv[l].height, s);
+  }
+  P->nlevels = nlevels;
+  P->ncells = base;
+  return PISLAM_OK;
+}
+
+int window_workspace(pislam_ctx *c, const pm::WinPlan &P, int words, size_t t_stride, int batch) {
+  if (c->w_win_off.ensure(sizeof(uint32_t) * (size_t)(P.ncells + 1) * batch) != PISLAM_OK ||
+      c->w_win_meta.ensure(sizeof(uint2) * t_stride * batch) != PISLAM_OK ||
+      c->w_win_desc.ensure(sizeof(uint32_t) * words * t_stride * batch) != PISLAM_OK)
+    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(window matcher workspace)");
+  return PISLAM_OK;
+}
+
+}  // namespace
+
+PISLAM_EXPORT int pislam_match_window_reserve(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
+                                              const int32_t *radius, size_t t_stride, int batch) {
+  if (!c) return PISLAM_ERR_INVALID;
+  pm::WinPlan P;
+  PCHK(window_plan(c, words, levels, nlevels, radius, t_stride, batch, &P));
+  HIPCHK(c, hipSetDevice(c->device));
+  return window_workspace(c, P, words, t_stride, batch);
+}
+
+PISLAM_EXPORT int pislam_match_hamming_window_batch(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
+                                                    const int32_t *radius, const uint32_t *qkp, const uint32_t *qdesc,
+                                                    const uint32_t *qcounts, size_t q_stride, const uint32_t *tkp,
+                                                    const uint32_t *tdesc, const uint32_t *tcounts, size_t t_stride,
+                                                    int batch, int32_t *idx, uint32_t *dist, uint32_t *dist2) {
+  if (!c) return PISLAM_ERR_INVALID;
+  pm::WinPlan P;
+  PCHK(window_plan(c, words, levels, nlevels, radius, t_stride, batch, &P));
+  if (q_stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "q_stride too large");
+  if (batch == 0 || q_stride == 0) return PISLAM_OK;
+  for (const void *ptr : {(const void *)qkp, (const void *)qdesc, (const void *)qcounts, (const void *)tkp,
+                          (const void *)tdesc, (const void *)tcounts, (const void *)idx, (const void *)dist,
+                          (const void *)dist2}) {
+    if (!ptr) return fail(c, PISLAM_ERR_INVALID, "null pointer");
+    if (!is_device_ptr(ptr)) return fail(c, PISLAM_ERR_INVALID, "the window matcher takes device pointers only");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  PCHK(window_workspace(c, P, words, t_stride, batch));
+  uint32_t *off = c->w_win_off.as<uint32_t>(), *edesc = c->w_win_desc.as<uint32_t>();
+  uint2 *meta = c->w_win_meta.as<uint2>();
+  hipLaunchKernelGGL(pm::k_window_index, dim3((unsigned)batch), dim3(pm::WIN_INDEX_THREADS), 0, c->stream, P, words, tkp,
+                     tdesc, tcounts, t_stride, off, meta, edesc);
+  PCHK(launch_ok(c, "k_window_index"));
+  // query tiles per pair in flight: the counts live on the device, so the grid is sized for the capacity and aims at
+  // ~16 workgroups per CU over the batch; a workgroup loops over further tiles of its pair
+  const int tiles = cdiv((int)std::min<size_t>(q_stride, 0x7fffffff - pm::WIN_QPW), pm::WIN_QPW);
+  const int per_pair = batch > 1 ? std::max(1, std::min(tiles, cdiv(16 * std::max(1, c->num_cus), batch))) : std::min(tiles, 65535);
+  const dim3 grid((unsigned)per_pair, (unsigned)batch);
+#define PISLAM_MATCH_WINDOW(W)                                                                                  \
+  hipLaunchKernelGGL(pm::k_match_window<W>, grid, dim3(pm::WIN_THREADS), 0, c->stream, P, qkp, qdesc, qcounts, q_stride, \
+                     t_stride, off, meta, edesc, idx, dist, dist2)
+  switch (words) {
+    case 1: PISLAM_MATCH_WINDOW(1); break;
+    case 2: PISLAM_MATCH_WINDOW(2); break;
+    case 4: PISLAM_MATCH_WINDOW(4); break;
+    default: PISLAM_MATCH_WINDOW(8); break;            // (window_plan accepted only 1, 2, 4, 8)
+  }
+#undef PISLAM_MATCH_WINDOW
+  return launch_ok(c, "k_match_window");
 }
 
 // ---- batches in flight: a pipeline of contexts behind one object --------------------------------

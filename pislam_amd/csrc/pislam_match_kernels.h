@@ -235,4 +235,210 @@ __global__ __launch_bounds__(64 * MF_WAVES) void k_match_mfma(const uint32_t *__
   }
 }
 
+// ---------------------------------------------------------------------------
+// Spatially windowed matching (include/pislam_hip.h): query i of pair b sees only the train
+// entries on its own pyramid level whose position lies within radius[l] of its own (Chebyshev, level pixels), with
+// the outputs of k_match restricted to those candidates.  Two launches on the context stream:
+//   k_window_index   one workgroup per pair: every train position is decoded to its level and placed on that level's
+//                    grid of square cells (side chosen by the host from radius[l]); a counting sort in LDS (histogram
+//                    with LDS atomics, exclusive scan, scatter) writes the pair's cell offsets and a cell-sorted copy
+//                    of each entry (packed position, original index, descriptor dwords) to the workspace.
+//   k_match_window   WIN_LPQ lanes per query (the query descriptor in registers): the cell rows overlapping the window
+//                    are contiguous runs of entries; the lanes of a query take every WIN_LPQ-th entry of each run,
+//                    apply the exact window test, XOR-popcount and keep (best, second) on dist << 16 | index like
+//                    k_match, then merge through two xor-shuffles.
+// Positions outside every level are never indexed and find no candidates.  Scatter order inside a cell varies between
+// runs; the results do not: the packed key is unique per train index, so the minimum does not depend on visit order.
+// ---------------------------------------------------------------------------
+constexpr int WIN_MAX_LEVELS = 16;
+constexpr int WIN_MAX_CELLS = 16384;   // LDS histogram of k_window_index (64 KiB); the host coarsens cells to fit
+constexpr int WIN_INDEX_THREADS = 1024;
+constexpr int WIN_THREADS = 256;       // k_match_window workgroup
+constexpr int WIN_LPQ = 4;             // lanes per query
+constexpr int WIN_QPW = WIN_THREADS / WIN_LPQ;   // queries per workgroup pass
+
+struct WinLevel {
+  int32_t col0, row0, width, height;   // rectangle inside the stacked pyramid
+  int32_t radius, side;                // window radius, cell side (level pixels)
+  int32_t ncx, base;                   // cells per cell row, first cell of the level in the pair's cell table
+};
+struct WinPlan {                       // passed by value (kernel arguments: a captured graph keeps its own copy)
+  WinLevel lv[WIN_MAX_LEVELS];
+  int32_t nlevels, ncells;             // ncells: cells of all levels (<= WIN_MAX_CELLS)
+};
+
+// A count as the window matcher reads it: PISLAM_COUNT_INVALID (a pyramid the front end did not produce) is 0.
+__device__ __forceinline__ uint32_t win_count(uint32_t c, size_t stride) {
+  return c == 0xffffffffu ? 0u : (uint32_t)min((size_t)c, stride);
+}
+
+// The level whose rectangle holds (x, y): the loop is wave-uniform (kernel-argument loads), the fields of the level
+// found are picked by selects, so no per-lane indexing of the plan (which would go through scratch).
+struct WinHit {
+  int32_t col0, row0, width, height, radius, side, ncx, base;
+  bool found;
+};
+__device__ __forceinline__ WinHit win_level(const WinPlan &P, int32_t x, int32_t y) {
+  WinHit h{0, 0, 0, 0, 0, 1, 0, 0, false};
+  for (int l = 0; l < P.nlevels; l++) {
+    const WinLevel L = P.lv[l];
+    if ((uint32_t)(x - L.col0) < (uint32_t)L.width && (uint32_t)(y - L.row0) < (uint32_t)L.height) {
+      h = WinHit{L.col0, L.row0, L.width, L.height, L.radius, L.side, L.ncx, L.base, true};
+    }
+  }
+  return h;
+}
+
+// Cell of a packed position (x << 12 | y; score bits ignored), -1 outside every level.
+__device__ __forceinline__ int32_t win_cell(const WinPlan &P, uint32_t k) {
+  const int32_t x = (int32_t)((k >> 12) & 0xfffu), y = (int32_t)(k & 0xfffu);
+  const WinHit h = win_level(P, x, y);
+  if (!h.found) return -1;
+  return h.base + ((y - h.row0) / h.side) * h.ncx + (x - h.col0) / h.side;
+}
+
+// grid (batch), WIN_INDEX_THREADS threads.  t_stride in entries; cell_off [batch][ncells + 1],
+// ent_meta [batch][t_stride] = (x << 12 | y, original index), ent_desc [batch][t_stride][words].
+__global__ __launch_bounds__(WIN_INDEX_THREADS) void k_window_index(WinPlan P, int words, const uint32_t *__restrict__ tkp,
+                                                                    const uint32_t *__restrict__ tdesc,
+                                                                    const uint32_t *__restrict__ tcount, size_t t_stride,
+                                                                    uint32_t *__restrict__ cell_off, uint2 *__restrict__ ent_meta,
+                                                                    uint32_t *__restrict__ ent_desc) {
+  __shared__ uint32_t hist[WIN_MAX_CELLS];
+  __shared__ uint32_t wave_sum[WIN_INDEX_THREADS / 64];
+  const int b = blockIdx.x;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t nt = win_count(tcount[b], t_stride);
+  const int32_t nc = P.ncells;
+  const uint32_t *kp = tkp + (size_t)b * t_stride;
+  uint32_t *off = cell_off + (size_t)b * (nc + 1);
+  for (int32_t c = (int32_t)tid; c < nc; c += WIN_INDEX_THREADS) hist[c] = 0;
+  __syncthreads();
+  for (uint32_t j = tid; j < nt; j += WIN_INDEX_THREADS) {
+    const int32_t c = win_cell(P, kp[j]);
+    if (c >= 0) atomicAdd(&hist[c], 1u);
+  }
+  __syncthreads();
+  // exclusive scan: every thread sums a contiguous chunk, the chunk sums are scanned across the workgroup
+  const int32_t chunk = (nc + WIN_INDEX_THREADS - 1) / WIN_INDEX_THREADS;
+  const int32_t c0 = min((int32_t)tid * chunk, nc), c1 = min(c0 + chunk, nc);
+  uint32_t s = 0;
+  for (int32_t c = c0; c < c1; c++) s += hist[c];
+  uint32_t incl = s;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t v = __shfl_up(incl, d, 64);
+    if ((int)lane >= d) incl += v;
+  }
+  if (lane == 63) wave_sum[wave] = incl;
+  __syncthreads();
+  uint32_t run = incl - s;
+  for (uint32_t w = 0; w < wave; w++) run += wave_sum[w];
+  for (int32_t c = c0; c < c1; c++) {
+    const uint32_t v = hist[c];
+    hist[c] = run;
+    run += v;
+  }
+  if (tid == WIN_INDEX_THREADS - 1) off[nc] = run;     // entries indexed (the last chunk ends at the total)
+  __syncthreads();
+  for (int32_t c = (int32_t)tid; c < nc; c += WIN_INDEX_THREADS) off[c] = hist[c];
+  __syncthreads();
+  // scatter: hist[c] is the next free slot of cell c
+  const uint32_t *dp = tdesc + (size_t)b * t_stride * words;
+  uint2 *mp = ent_meta + (size_t)b * t_stride;
+  uint32_t *ep = ent_desc + (size_t)b * t_stride * words;
+  for (uint32_t j = tid; j < nt; j += WIN_INDEX_THREADS) {
+    const uint32_t k = kp[j];
+    const int32_t c = win_cell(P, k);
+    if (c < 0) continue;
+    const uint32_t slot = atomicAdd(&hist[c], 1u);
+    mp[slot] = make_uint2(k & 0xffffffu, j);
+    for (int w = 0; w < words; w++) ep[(size_t)slot * words + w] = dp[(size_t)j * words + w];
+  }
+}
+
+template <int WORDS>
+__device__ __forceinline__ uint32_t win_popc(const uint32_t (&qd)[WORDS], const uint32_t *__restrict__ e) {
+  uint32_t t[WORDS];
+  if constexpr (WORDS >= 4) {                           // entries are WORDS * 4 bytes apart from a 256-byte aligned base
+#pragma unroll
+    for (int k = 0; k < WORDS; k += 4) {
+      const uint4 v = *(const uint4 *)(e + k);
+      t[k] = v.x, t[k + 1] = v.y, t[k + 2] = v.z, t[k + 3] = v.w;
+    }
+  } else if constexpr (WORDS == 2) {
+    const uint2 v = *(const uint2 *)e;
+    t[0] = v.x, t[1] = v.y;
+  } else {
+    t[0] = e[0];
+  }
+  uint32_t d = 0;
+#pragma unroll
+  for (int k = 0; k < WORDS; k++) d += (uint32_t)__popc(qd[k] ^ t[k]);
+  return d;
+}
+
+// grid (query tiles, batch), WIN_THREADS threads; q_stride / t_stride in entries; outputs [batch][q_stride].
+template <int WORDS>
+__global__ __launch_bounds__(WIN_THREADS) void k_match_window(WinPlan P, const uint32_t *__restrict__ qkp,
+                                                              const uint32_t *__restrict__ qdesc,
+                                                              const uint32_t *__restrict__ qcount, size_t q_stride,
+                                                              size_t t_stride, const uint32_t *__restrict__ cell_off,
+                                                              const uint2 *__restrict__ ent_meta,
+                                                              const uint32_t *__restrict__ ent_desc,
+                                                              int32_t *__restrict__ idx, uint32_t *__restrict__ dist,
+                                                              uint32_t *__restrict__ dist2) {
+  const int b = blockIdx.y;
+  const uint32_t nq = win_count(qcount[b], q_stride);
+  const uint32_t sub = threadIdx.x % WIN_LPQ;
+  const uint32_t *off_b = cell_off + (size_t)b * (P.ncells + 1);
+  const uint2 *mp = ent_meta + (size_t)b * t_stride;
+  const uint32_t *ep = ent_desc + (size_t)b * t_stride * WORDS;
+  for (uint32_t q0 = blockIdx.x * (uint32_t)WIN_QPW; q0 < nq; q0 += gridDim.x * (uint32_t)WIN_QPW) {
+    const uint32_t i = q0 + threadIdx.x / WIN_LPQ;
+    uint32_t best = 0xffffffffu, second = 0xffffffffu;  // (keys are at most 256 << 16 | 65534: never the sentinel)
+    if (i < nq) {
+      const uint32_t k = qkp[(size_t)b * q_stride + i];
+      const int32_t x = (int32_t)((k >> 12) & 0xfffu), y = (int32_t)(k & 0xfffu);
+      const WinHit h = win_level(P, x, y);
+      if (h.found) {
+        uint32_t qd[WORDS];
+        const uint32_t *qp = qdesc + ((size_t)b * q_stride + i) * WORDS;
+#pragma unroll
+        for (int w = 0; w < WORDS; w++) qd[w] = qp[w];
+        const int32_t r = h.radius;
+        // the window clipped to the level: its train entries all lie inside the level's rectangle
+        const int32_t cx0 = (max(x - r, h.col0) - h.col0) / h.side, cx1 = (min(x + r, h.col0 + h.width - 1) - h.col0) / h.side;
+        const int32_t cy0 = (max(y - r, h.row0) - h.row0) / h.side, cy1 = (min(y + r, h.row0 + h.height - 1) - h.row0) / h.side;
+        const uint32_t *off = off_b + h.base;
+        for (int32_t cy = cy0; cy <= cy1; cy++) {
+          const uint32_t e1 = off[cy * h.ncx + cx1 + 1];
+          for (uint32_t e = off[cy * h.ncx + cx0] + sub; e < e1; e += WIN_LPQ) {
+            const uint2 m = mp[e];
+            const int32_t tx = (int32_t)(m.x >> 12), ty = (int32_t)(m.x & 0xfffu);
+            if (abs(tx - x) <= r && abs(ty - y) <= r) {
+              const uint32_t key = (win_popc<WORDS>(qd, ep + (size_t)e * WORDS) << 16) | m.y;
+              second = min(second, max(best, key));
+              best = min(best, key);
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 1; s < WIN_LPQ; s <<= 1) {              // merge the lanes of a query: they saw disjoint entries
+      const uint32_t ob = __shfl_xor(best, s, 64), os = __shfl_xor(second, s, 64);
+      second = min(min(second, os), max(best, ob));
+      best = min(best, ob);
+    }
+    if (sub == 0 && i < nq) {
+      const size_t o = (size_t)b * q_stride + i;
+      idx[o] = best == 0xffffffffu ? -1 : (int32_t)(best & 0xffffu);
+      dist[o] = best == 0xffffffffu ? 0xffffffffu : best >> 16;
+      dist2[o] = second == 0xffffffffu ? 0xffffffffu : second >> 16;
+    }
+  }
+}
+
+
 }  // namespace pm

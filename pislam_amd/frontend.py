@@ -208,6 +208,50 @@ def matchHammingBatch(qdesc, qcounts, tdesc, tcounts, idx=None, dist=None, dist2
     return idx, dist, dist2
 
 
+def _window_tables(levels, radius):
+    """levels [(w, h, row0[, col0])] and radius (int, or one per level) as the C arrays of the windowed matcher."""
+    lv = [Level(t[0], t[1], t[2], t[3] if len(t) > 3 else 0) for t in levels]
+    r = [int(radius)] * len(lv) if isinstance(radius, (int, np.integer)) else [int(v) for v in radius]
+    if len(r) != len(lv):
+        raise ValueError(f"radius: {len(r)} values for {len(lv)} levels")
+    n = max(1, len(lv))
+    return (Level * n)(*lv), len(lv), (ctypes.c_int32 * n)(*r)
+
+
+def reserveMatchWindow(levels, radius, t_stride: int, batch: int, *, words=8, ctx: Context | None = None):
+    """Sizes the context's windowed-matcher workspace (pislam_match_window_reserve): afterwards
+    matchHammingWindowBatch of the same or a smaller shape allocates nothing and can be captured into a hipGraph."""
+    ctx = ctx or default_context()
+    lv, n, r = _window_tables(levels, radius)
+    ctx.check(ctx.lib.pislam_match_window_reserve(ctx.h, words, lv, n, r, t_stride, batch), "pislam_match_window_reserve")
+
+
+def matchHammingWindowBatch(qkp, qdesc, qcounts, tkp, tdesc, tcounts, levels, radius, idx=None, dist=None, dist2=None, *,
+                            ctx: Context | None = None):
+    """Spatially windowed matcher on device-resident front-end outputs (torch tensors as OrbFrontend.alloc_outputs
+    makes them: keypoints [batch][max_kp], descriptors [batch][max_kp][words], counts [batch]): query i of pair b sees
+    only the train keypoints on its own level within `radius` (int, or one per level) in x and in y.  `levels` is
+    [(w, h, row0[, col0])].  Returns (idx, dist, dist2) int32 tensors [batch][max_kp] like matchHammingBatch
+    (pislam_match_hamming_window_batch); asynchronous on the ctx stream."""
+    import torch
+    ctx = ctx or default_context()
+    batch, qs, words = qdesc.shape
+    ts = tdesc.shape[1]
+    if tdesc.shape[2] != words:
+        raise ValueError("query and train descriptors differ in words")
+    lv, n, r = _window_tables(levels, radius)
+    if idx is None:
+        idx = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
+    if dist is None:
+        dist = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
+    if dist2 is None:
+        dist2 = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
+    ctx.check(ctx.lib.pislam_match_hamming_window_batch(ctx.h, words, lv, n, r, ptr(qkp), ptr(qdesc), ptr(qcounts), qs,
+                                                        ptr(tkp), ptr(tdesc), ptr(tcounts), ts, batch, ptr(idx), ptr(dist),
+                                                        ptr(dist2)), "pislam_match_hamming_window_batch")
+    return idx, dist, dist2
+
+
 # ---- Gaussian.h:48, Bilinear.h:42, Bilinear.h:165 -------------------------------------
 def gaussian5x5(width, height, img, out, *, ctx: Context | None = None):
     """pislam::gaussian5x5<vstep>(width, height, img, out); img may be out (in place)."""
