@@ -397,6 +397,49 @@ int pislam_match_hamming_window_batch(pislam_ctx *ctx, int words,
                                       const uint32_t *tcounts, size_t t_stride, int batch, int32_t *idx,
                                       uint32_t *dist, uint32_t *dist2);
 
+/* Scale-aware guided form: matching in level-0
+ * coordinates across pyramid levels, around an optional predicted position.
+ * Pairs, counts, keypoint words, descriptor and output layouts, and the level
+ * of a position are those of pislam_match_hamming_window_batch.  A position
+ * on level l with level-local u = x - col0, v = y - row0 maps to
+ * X = (u * s_l + 32768) >> 16, Y = (v * s_l + 32768) >> 16 (unsigned 32-bit
+ * arithmetic), s_l = scale_q16[l] = level-0 pixels per level-l pixel in Q16.
+ * Window centre (Xc, Yc): the query's own mapped position when qpred is NULL,
+ * else qpred[(b * q_stride + i) * 2 + {0, 1}] (device int32 level-0
+ * coordinates, clamped to [-2^20, 2^20]).  Train j on level lt is a candidate
+ * for query i on level lq when |lq - lt| <= level_span,
+ * |Xc - Xt| <= radius0[lq] and |Yc - Yt| <= radius0[lq] (the radius is in
+ * level-0 pixels and indexed by the query's level).  A query position in no
+ * level has no candidates, with or without a prediction.  Outputs as
+ * pislam_match_hamming_window_batch, restricted to these candidates (best on
+ * dist << 16 | j: ties go to the smallest train index; idx -1 and dist
+ * 0xffffffff without candidates; dist2 0xffffffff with fewer than 2); entries
+ * at and beyond nq_b are not written.  With level_span 0, every scale 65536,
+ * qpred NULL and radius0 = radius the outputs equal the windowed matcher's.
+ * words in {1,2,4,8}; 1 <= nlevels <= 16, level rectangles non-empty,
+ * disjoint, inside 12-bit coordinates; 0 <= radius0[l] <= 65535;
+ * 0 <= level_span <= nlevels - 1; 1 <= scale_q16[l] <= 2^20 and every level's
+ * mapped extent ((width - 1) * s_l + 32768) >> 16 (likewise height) <= 65535;
+ * t_stride <= 65535.  Anything else, or a host pointer where a device pointer
+ * is required: PISLAM_ERR_INVALID, before anything is launched or written.
+ * Device pointers only (qpred may be NULL), except `levels`, `scale_q16` and
+ * `radius0` (host arrays, read during the call: a captured graph keeps its own
+ * copy).  Asynchronous on the context stream; the workspace is the context's
+ * own (not the windowed matcher's) and grows on demand, which synchronises;
+ * after pislam_match_scaled_window_reserve of the same or a larger shape the
+ * call allocates nothing and never synchronises, so it can be captured into a
+ * hipGraph. */
+int pislam_match_scaled_window_reserve(pislam_ctx *ctx, int words, const pislam_level *levels, int nlevels,
+                                       const int32_t *scale_q16, const int32_t *radius0, int level_span,
+                                       size_t t_stride, int batch);
+int pislam_match_hamming_scaled_window_batch(pislam_ctx *ctx, int words,
+                                             const pislam_level *levels, int nlevels,
+                                             const int32_t *scale_q16, const int32_t *radius0, int level_span,
+                                             const uint32_t *qkp, const uint32_t *qdesc, const uint32_t *qcounts,
+                                             const int32_t *qpred, size_t q_stride,
+                                             const uint32_t *tkp, const uint32_t *tdesc, const uint32_t *tcounts,
+                                             size_t t_stride, int batch, int32_t *idx, uint32_t *dist, uint32_t *dist2);
+
 /* ---- multi-GPU: one process per GPU, pyramids sharded, ONE collective ---- */
 
 /* The reference is a single-threaded per-frame loop without cross-frame state

@@ -84,6 +84,11 @@ SYMBOLS = {
     "pislam_match_window_reserve": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32), _sz, _i]),
     "pislam_match_hamming_window_batch": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32), _vp, _vp,
                                                _vp, _sz, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp]),
+    "pislam_match_scaled_window_reserve": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),
+                                                ctypes.POINTER(ctypes.c_int32), _i, _sz, _i]),
+    "pislam_match_hamming_scaled_window_batch": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),
+                                                      ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _vp, _vp, _sz, _vp,
+                                                      _vp, _vp, _sz, _i, _vp, _vp, _vp]),
     "pislam_dist_shard": (_i, [_i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "pislam_dist_get_unique_id": (_i, [ctypes.c_char_p]),
     "pislam_dist_init": (_i, [_vp, ctypes.c_char_p, _i, _i]),

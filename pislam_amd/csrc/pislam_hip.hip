@@ -107,6 +107,7 @@ struct pislam_ctx {
   DevBuf w_score, w_stage, w_stripcnt, w_work, w_prof, w_ovf, w_stagedesc;
   DevBuf w_ustage, w_ucount;         // bucket selection pass (pf::k_bucket_select): per-unit lists and counts
   DevBuf w_win_off, w_win_meta, w_win_desc;   // windowed matcher: cell offsets, cell-sorted train entries (pm::k_window_index)
+  DevBuf w_sc_off, w_sc_meta, w_sc_desc;      // scaled window matcher: the same for pm::k_scaled_index (its own buffers)
   // Host-built plan tables the kernels read instead of walking the plan (the bucket selection pass's unit table): one
   // device buffer per distinct CONTENT, never rewritten in place — a captured graph keeps reading the table
   // of the plan it was captured with whatever other shapes the context serves in between.  At most 16 are kept (the oldest
@@ -504,7 +505,7 @@ PISLAM_EXPORT int pislam_ctx_destroy(pislam_ctx *c) {
   for (DevBuf *b : {&c->s_img, &c->s_out, &c->s_pts, &c->s_desc, &c->s_misc, &c->s_rots, &c->s_tmp, &c->w_cnt,
                     &c->w_off, &c->w_total, &c->w_cellkp, &c->w_score, &c->w_stage, &c->w_stripcnt, &c->w_work, &c->w_prof, &c->w_ovf,
                     &c->w_stagedesc, &c->w_ustage, &c->w_ucount, &c->w_sync, &c->w_chain, &c->w_win_off, &c->w_win_meta,
-                    &c->w_win_desc})
+                    &c->w_win_desc, &c->w_sc_off, &c->w_sc_meta, &c->w_sc_desc})
     b->release();
   for (auto *t : c->plan_tables) {
     t->dev.release();
@@ -2413,6 +2414,131 @@ PISLAM_EXPORT int pislam_match_hamming_window_batch(pislam_ctx *c, int words, co
   }
 #undef PISLAM_MATCH_WINDOW
   return launch_ok(c, "k_match_window");
+}
+
+// ---- scale-aware guided window matching ---------------------------------------------------
+
+namespace {
+
+// Checks the arguments every scaled-window call shares and lays out the per-pair cell grids (host only).  Level lt's
+// grid covers its mapped extent [0, ext_x] x [0, ext_y] in level-0 pixels with square cells of side m[lt] * f, where
+// m[lt] is the largest max(1, radius0[lq]) of the query levels lq that reach lt (|lq - lt| <= span) and f >= 1 is the
+// smallest factor that keeps all levels' cells within pm::WIN_MAX_CELLS.  Results do not depend on the side: the match
+// applies the exact window test.
+int scaled_plan(pislam_ctx *c, int words, const pislam_level *lv, int nlevels, const int32_t *scale_q16,
+                const int32_t *radius0, int level_span, size_t t_stride, int batch, pm::ScaledPlan *P) {
+  if (words != 1 && words != 2 && words != 4 && words != 8) return fail(c, PISLAM_ERR_INVALID, "words must be 1, 2, 4 or 8");
+  if (nlevels < 1 || nlevels > pm::WIN_MAX_LEVELS) return fail(c, PISLAM_ERR_INVALID, "nlevels must be 1..16");
+  if (!lv || !scale_q16 || !radius0) return fail(c, PISLAM_ERR_INVALID, "null levels / scale_q16 / radius0");
+  if (level_span < 0 || level_span > nlevels - 1) return fail(c, PISLAM_ERR_INVALID, "level_span must be 0..nlevels-1");
+  if (t_stride > 65535) return fail(c, PISLAM_ERR_INVALID, "at most 65535 train entries per pair");
+  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
+  int32_t ext_x[pm::WIN_MAX_LEVELS], ext_y[pm::WIN_MAX_LEVELS];
+  for (int l = 0; l < nlevels; l++) {
+    const pislam_level &L = lv[l];
+    if (L.width < 1 || L.height < 1 || L.col0 < 0 || L.row0 < 0 || L.col0 + L.width > 4096 || L.row0 + L.height > 4096)
+      return fail(c, PISLAM_ERR_INVALID, "level rectangles must be non-empty and fit 12-bit coordinates");
+    if (radius0[l] < 0 || radius0[l] > 65535) return fail(c, PISLAM_ERR_INVALID, "radius0 must be 0..65535");
+    if (scale_q16[l] < 1 || scale_q16[l] > (1 << 20)) return fail(c, PISLAM_ERR_INVALID, "scale_q16 must be 1..2^20");
+    const long long ex = ((long long)(L.width - 1) * scale_q16[l] + 32768) >> 16;
+    const long long ey = ((long long)(L.height - 1) * scale_q16[l] + 32768) >> 16;
+    if (ex > 65535 || ey > 65535) return fail(c, PISLAM_ERR_INVALID, "a level's mapped extent exceeds 65535");
+    ext_x[l] = (int32_t)ex, ext_y[l] = (int32_t)ey;
+    for (int k = 0; k < l; k++) {
+      const pislam_level &K = lv[k];
+      if (L.col0 < K.col0 + K.width && K.col0 < L.col0 + L.width && L.row0 < K.row0 + K.height && K.row0 < L.row0 + L.height)
+        return fail(c, PISLAM_ERR_INVALID, "level rectangles overlap");
+    }
+  }
+  long long m[pm::WIN_MAX_LEVELS];
+  for (int lt = 0; lt < nlevels; lt++) {
+    m[lt] = 1;
+    for (int lq = std::max(0, lt - level_span); lq <= std::min(nlevels - 1, lt + level_span); lq++)
+      m[lt] = std::max<long long>(m[lt], radius0[lq]);
+  }
+  auto side = [&](int l, long long f) { return (int)std::min<long long>(65536, m[l] * f); };
+  auto cells = [&](long long f) {
+    long long n = 0;
+    for (int l = 0; l < nlevels; l++) n += (long long)cdiv(ext_x[l] + 1, side(l, f)) * cdiv(ext_y[l] + 1, side(l, f));
+    return n;
+  };
+  // cells(f) ~ cells(1) / f^2: start just below that estimate; side 65536 leaves one cell per level, so this ends
+  long long f = std::max(1LL, (long long)std::sqrt((double)cells(1) / pm::WIN_MAX_CELLS));
+  while (cells(f) > pm::WIN_MAX_CELLS) f++;
+  *P = pm::ScaledPlan{};
+  int base = 0;
+  for (int l = 0; l < nlevels; l++) {
+    const int s = side(l, f), ncx = cdiv(ext_x[l] + 1, s);
+    P->lv[l] = pm::ScaledLevel{lv[l].col0, lv[l].row0, lv[l].width, lv[l].height, scale_q16[l], ext_x[l], ext_y[l],
+                               radius0[l], s, ncx, base};
+    base += ncx * cdiv(ext_y[l] + 1, s);
+  }
+  P->nlevels = nlevels;
+  P->ncells = base;
+  P->span = level_span;
+  return PISLAM_OK;
+}
+
+int scaled_workspace(pislam_ctx *c, const pm::ScaledPlan &P, int words, size_t t_stride, int batch) {
+  if (c->w_sc_off.ensure(sizeof(uint32_t) * (size_t)(P.ncells + 1) * batch) != PISLAM_OK ||
+      c->w_sc_meta.ensure(sizeof(uint2) * t_stride * batch) != PISLAM_OK ||
+      c->w_sc_desc.ensure(sizeof(uint32_t) * words * t_stride * batch) != PISLAM_OK)
+    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(scaled window matcher workspace)");
+  return PISLAM_OK;
+}
+
+}  // namespace
+
+PISLAM_EXPORT int pislam_match_scaled_window_reserve(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
+                                                     const int32_t *scale_q16, const int32_t *radius0, int level_span,
+                                                     size_t t_stride, int batch) {
+  if (!c) return PISLAM_ERR_INVALID;
+  pm::ScaledPlan P;
+  PCHK(scaled_plan(c, words, levels, nlevels, scale_q16, radius0, level_span, t_stride, batch, &P));
+  HIPCHK(c, hipSetDevice(c->device));
+  return scaled_workspace(c, P, words, t_stride, batch);
+}
+
+PISLAM_EXPORT int pislam_match_hamming_scaled_window_batch(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
+                                                           const int32_t *scale_q16, const int32_t *radius0, int level_span,
+                                                           const uint32_t *qkp, const uint32_t *qdesc, const uint32_t *qcounts,
+                                                           const int32_t *qpred, size_t q_stride, const uint32_t *tkp,
+                                                           const uint32_t *tdesc, const uint32_t *tcounts, size_t t_stride,
+                                                           int batch, int32_t *idx, uint32_t *dist, uint32_t *dist2) {
+  if (!c) return PISLAM_ERR_INVALID;
+  pm::ScaledPlan P;
+  PCHK(scaled_plan(c, words, levels, nlevels, scale_q16, radius0, level_span, t_stride, batch, &P));
+  if (q_stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "q_stride too large");
+  if (qpred && !is_device_ptr(qpred)) return fail(c, PISLAM_ERR_INVALID, "qpred must be a device pointer or null");
+  if (batch == 0 || q_stride == 0) return PISLAM_OK;
+  for (const void *ptr : {(const void *)qkp, (const void *)qdesc, (const void *)qcounts, (const void *)tkp,
+                          (const void *)tdesc, (const void *)tcounts, (const void *)idx, (const void *)dist,
+                          (const void *)dist2}) {
+    if (!ptr) return fail(c, PISLAM_ERR_INVALID, "null pointer");
+    if (!is_device_ptr(ptr)) return fail(c, PISLAM_ERR_INVALID, "the scaled window matcher takes device pointers only");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  PCHK(scaled_workspace(c, P, words, t_stride, batch));
+  uint32_t *off = c->w_sc_off.as<uint32_t>(), *edesc = c->w_sc_desc.as<uint32_t>();
+  uint2 *meta = c->w_sc_meta.as<uint2>();
+  hipLaunchKernelGGL(pm::k_scaled_index, dim3((unsigned)batch), dim3(pm::WIN_INDEX_THREADS), 0, c->stream, P, words, tkp,
+                     tdesc, tcounts, t_stride, off, meta, edesc);
+  PCHK(launch_ok(c, "k_scaled_index"));
+  // grid as pislam_match_hamming_window_batch: sized for the capacity, ~16 workgroups per CU over the batch
+  const int tiles = cdiv((int)std::min<size_t>(q_stride, 0x7fffffff - pm::WIN_QPW), pm::WIN_QPW);
+  const int per_pair = batch > 1 ? std::max(1, std::min(tiles, cdiv(16 * std::max(1, c->num_cus), batch))) : std::min(tiles, 65535);
+  const dim3 grid((unsigned)per_pair, (unsigned)batch);
+#define PISLAM_MATCH_SCALED(W)                                                                                           \
+  hipLaunchKernelGGL(pm::k_match_scaled<W>, grid, dim3(pm::WIN_THREADS), 0, c->stream, P, qkp, qdesc, qcounts, qpred,     \
+                     q_stride, t_stride, off, meta, edesc, idx, dist, dist2)
+  switch (words) {
+    case 1: PISLAM_MATCH_SCALED(1); break;
+    case 2: PISLAM_MATCH_SCALED(2); break;
+    case 4: PISLAM_MATCH_SCALED(4); break;
+    default: PISLAM_MATCH_SCALED(8); break;            // (scaled_plan accepted only 1, 2, 4, 8)
+  }
+#undef PISLAM_MATCH_SCALED
+  return launch_ok(c, "k_match_scaled");
 }
 
 // ---- batches in flight: a pipeline of contexts behind one object --------------------------------

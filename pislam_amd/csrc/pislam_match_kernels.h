@@ -440,5 +440,206 @@ __global__ __launch_bounds__(WIN_THREADS) void k_match_window(WinPlan P, const u
   }
 }
 
+// ---------------------------------------------------------------------------
+// Scale-aware guided window matching (include/pislam_hip.h): every position is mapped to level-0
+// coordinates through its level's Q16 scale, X = ((x - col0) * s + 32768) >> 16 (likewise Y); query i of level lq sees
+// the train entries of the levels within `span` of lq whose mapped position lies within radius0[lq] of the window
+// centre (the query's own mapped position, or a per-query prediction).  Same two-launch structure as the windowed
+// matcher, with its own plan and workspace:
+//   k_scaled_index   one workgroup per pair: each train entry goes to a cell of ITS level's grid of square cells in
+//                    level-0 pixels (so a cell run holds one level and the match needs no level test), by the same
+//                    counting sort as k_window_index; an entry keeps X << 16 | Y, its original index and its descriptor.
+//   k_match_scaled   WIN_LPQ lanes per query: a wave-uniform loop over the plan's levels (kernel-argument loads, no
+//                    per-lane indexing of the plan); a lane takes part in the levels within span of its own and walks
+//                    the cell rows of that level's grid overlapping the window clipped to the level's mapped extent.
+// ---------------------------------------------------------------------------
+struct ScaledLevel {
+  int32_t col0, row0, width, height;   // rectangle inside the stacked pyramid
+  int32_t scale;                       // level-0 pixels per level pixel, Q16 (1 .. 2^20)
+  int32_t ext_x, ext_y;                // largest mapped X / Y of the level (<= 65535)
+  int32_t radius;                      // radius0[l]: window radius of a query on this level (level-0 pixels)
+  int32_t side, ncx, base;             // grid of the level's train entries: cell side (level-0 pixels), cells per cell
+                                       // row, first cell of the level in the pair's cell table
+};
+struct ScaledPlan {                    // passed by value (kernel arguments: a captured graph keeps its own copy)
+  ScaledLevel lv[WIN_MAX_LEVELS];
+  int32_t nlevels, ncells, span;       // ncells: cells of all levels (<= WIN_MAX_CELLS); span: |lq - lt| <= span
+};
+
+// Level-0 coordinate of a level-local coordinate u (unsigned 32-bit: u <= 4095 and scale <= 2^20 cannot wrap).
+__device__ __forceinline__ int32_t sc_map(int32_t u, int32_t scale) {
+  return (int32_t)(((uint32_t)u * (uint32_t)scale + 32768u) >> 16);
+}
+
+// The level whose rectangle holds (x, y), its fields picked by selects in a wave-uniform loop (as win_level).
+struct ScaledHit {
+  int32_t level, col0, row0, scale, radius, side, ncx, base;   // level -1: in no level
+};
+__device__ __forceinline__ ScaledHit sc_level(const ScaledPlan &P, int32_t x, int32_t y) {
+  ScaledHit h{-1, 0, 0, 0, 0, 1, 0, 0};
+  for (int l = 0; l < P.nlevels; l++) {
+    const ScaledLevel L = P.lv[l];
+    if ((uint32_t)(x - L.col0) < (uint32_t)L.width && (uint32_t)(y - L.row0) < (uint32_t)L.height) {
+      h = ScaledHit{l, L.col0, L.row0, L.scale, L.radius, L.side, L.ncx, L.base};
+    }
+  }
+  return h;
+}
+
+// Cell of a packed position (x << 12 | y; score bits ignored) in its level's grid, -1 outside every level; *xy gets
+// the mapped X << 16 | Y.
+__device__ __forceinline__ int32_t sc_cell(const ScaledPlan &P, uint32_t k, uint32_t *xy) {
+  const int32_t x = (int32_t)((k >> 12) & 0xfffu), y = (int32_t)(k & 0xfffu);
+  const ScaledHit h = sc_level(P, x, y);
+  if (h.level < 0) return -1;
+  const int32_t X = sc_map(x - h.col0, h.scale), Y = sc_map(y - h.row0, h.scale);
+  *xy = (uint32_t)X << 16 | (uint32_t)Y;
+  return h.base + (Y / h.side) * h.ncx + X / h.side;
+}
+
+// grid (batch), WIN_INDEX_THREADS threads.  t_stride in entries; cell_off [batch][ncells + 1],
+// ent_meta [batch][t_stride] = (X << 16 | Y, original index), ent_desc [batch][t_stride][words].
+__global__ __launch_bounds__(WIN_INDEX_THREADS) void k_scaled_index(ScaledPlan P, int words, const uint32_t *__restrict__ tkp,
+                                                                    const uint32_t *__restrict__ tdesc,
+                                                                    const uint32_t *__restrict__ tcount, size_t t_stride,
+                                                                    uint32_t *__restrict__ cell_off, uint2 *__restrict__ ent_meta,
+                                                                    uint32_t *__restrict__ ent_desc) {
+  __shared__ uint32_t hist[WIN_MAX_CELLS];
+  __shared__ uint32_t wave_sum[WIN_INDEX_THREADS / 64];
+  const int b = blockIdx.x;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t nt = win_count(tcount[b], t_stride);
+  const int32_t nc = P.ncells;
+  const uint32_t *kp = tkp + (size_t)b * t_stride;
+  uint32_t *off = cell_off + (size_t)b * (nc + 1);
+  for (int32_t c = (int32_t)tid; c < nc; c += WIN_INDEX_THREADS) hist[c] = 0;
+  __syncthreads();
+  for (uint32_t j = tid; j < nt; j += WIN_INDEX_THREADS) {
+    uint32_t xy;
+    const int32_t c = sc_cell(P, kp[j], &xy);
+    if (c >= 0) atomicAdd(&hist[c], 1u);
+  }
+  __syncthreads();
+  // exclusive scan: every thread sums a contiguous chunk, the chunk sums are scanned across the workgroup
+  const int32_t chunk = (nc + WIN_INDEX_THREADS - 1) / WIN_INDEX_THREADS;
+  const int32_t c0 = min((int32_t)tid * chunk, nc), c1 = min(c0 + chunk, nc);
+  uint32_t s = 0;
+  for (int32_t c = c0; c < c1; c++) s += hist[c];
+  uint32_t incl = s;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t v = __shfl_up(incl, d, 64);
+    if ((int)lane >= d) incl += v;
+  }
+  if (lane == 63) wave_sum[wave] = incl;
+  __syncthreads();
+  uint32_t run = incl - s;
+  for (uint32_t w = 0; w < wave; w++) run += wave_sum[w];
+  for (int32_t c = c0; c < c1; c++) {
+    const uint32_t v = hist[c];
+    hist[c] = run;
+    run += v;
+  }
+  if (tid == WIN_INDEX_THREADS - 1) off[nc] = run;     // entries indexed (the last chunk ends at the total)
+  __syncthreads();
+  for (int32_t c = (int32_t)tid; c < nc; c += WIN_INDEX_THREADS) off[c] = hist[c];
+  __syncthreads();
+  // scatter: hist[c] is the next free slot of cell c
+  const uint32_t *dp = tdesc + (size_t)b * t_stride * words;
+  uint2 *mp = ent_meta + (size_t)b * t_stride;
+  uint32_t *ep = ent_desc + (size_t)b * t_stride * words;
+  for (uint32_t j = tid; j < nt; j += WIN_INDEX_THREADS) {
+    uint32_t xy;
+    const int32_t c = sc_cell(P, kp[j], &xy);
+    if (c < 0) continue;
+    const uint32_t slot = atomicAdd(&hist[c], 1u);
+    mp[slot] = make_uint2(xy, j);
+    for (int w = 0; w < words; w++) ep[(size_t)slot * words + w] = dp[(size_t)j * words + w];
+  }
+}
+
+constexpr int32_t SCALED_PRED_LIMIT = 1 << 20;   // predicted centres are clamped to [-2^20, 2^20]
+
+// grid (query tiles, batch), WIN_THREADS threads; q_stride / t_stride in entries; qpred [batch][q_stride][2] or null;
+// outputs [batch][q_stride].
+template <int WORDS>
+__global__ __launch_bounds__(WIN_THREADS) void k_match_scaled(ScaledPlan P, const uint32_t *__restrict__ qkp,
+                                                              const uint32_t *__restrict__ qdesc,
+                                                              const uint32_t *__restrict__ qcount,
+                                                              const int32_t *__restrict__ qpred, size_t q_stride,
+                                                              size_t t_stride, const uint32_t *__restrict__ cell_off,
+                                                              const uint2 *__restrict__ ent_meta,
+                                                              const uint32_t *__restrict__ ent_desc,
+                                                              int32_t *__restrict__ idx, uint32_t *__restrict__ dist,
+                                                              uint32_t *__restrict__ dist2) {
+  const int b = blockIdx.y;
+  const uint32_t nq = win_count(qcount[b], q_stride);
+  const uint32_t sub = threadIdx.x % WIN_LPQ;
+  const uint32_t *off_b = cell_off + (size_t)b * (P.ncells + 1);
+  const uint2 *mp = ent_meta + (size_t)b * t_stride;
+  const uint32_t *ep = ent_desc + (size_t)b * t_stride * WORDS;
+  for (uint32_t q0 = blockIdx.x * (uint32_t)WIN_QPW; q0 < nq; q0 += gridDim.x * (uint32_t)WIN_QPW) {
+    const uint32_t i = q0 + threadIdx.x / WIN_LPQ;
+    const size_t o = (size_t)b * q_stride + i;
+    uint32_t best = 0xffffffffu, second = 0xffffffffu;  // (keys are at most 256 << 16 | 65534: never the sentinel)
+    int32_t lq = -1, xc = 0, yc = 0, r = 0;             // lq -1: no candidates (past the count, or in no level)
+    uint32_t qd[WORDS];
+#pragma unroll
+    for (int w = 0; w < WORDS; w++) qd[w] = 0;
+    if (i < nq) {
+      const uint32_t k = qkp[o];
+      const int32_t x = (int32_t)((k >> 12) & 0xfffu), y = (int32_t)(k & 0xfffu);
+      const ScaledHit h = sc_level(P, x, y);
+      if (h.level >= 0) {
+        lq = h.level;
+        r = h.radius;
+        if (qpred) {
+          xc = min(max(qpred[o * 2], -SCALED_PRED_LIMIT), SCALED_PRED_LIMIT);
+          yc = min(max(qpred[o * 2 + 1], -SCALED_PRED_LIMIT), SCALED_PRED_LIMIT);
+        } else {
+          xc = sc_map(x - h.col0, h.scale);
+          yc = sc_map(y - h.row0, h.scale);
+        }
+        const uint32_t *qp = qdesc + o * WORDS;
+#pragma unroll
+        for (int w = 0; w < WORDS; w++) qd[w] = qp[w];
+      }
+    }
+    for (int l = 0; l < P.nlevels; l++) {               // wave-uniform: L comes from kernel-argument loads
+      if (lq < 0 || abs(l - lq) > P.span) continue;
+      const ScaledLevel L = P.lv[l];
+      // the window clipped to the level's mapped extent: its train entries all lie inside it
+      const int32_t x0 = max(xc - r, 0), x1 = min(xc + r, L.ext_x);
+      const int32_t y0 = max(yc - r, 0), y1 = min(yc + r, L.ext_y);
+      if (x0 > x1 || y0 > y1) continue;
+      const int32_t cx0 = x0 / L.side, cx1 = x1 / L.side, cy0 = y0 / L.side, cy1 = y1 / L.side;
+      const uint32_t *off = off_b + L.base;
+      for (int32_t cy = cy0; cy <= cy1; cy++) {
+        const uint32_t e1 = off[cy * L.ncx + cx1 + 1];
+        for (uint32_t e = off[cy * L.ncx + cx0] + sub; e < e1; e += WIN_LPQ) {
+          const uint2 m = mp[e];
+          const int32_t tx = (int32_t)(m.x >> 16), ty = (int32_t)(m.x & 0xffffu);
+          if (abs(tx - xc) <= r && abs(ty - yc) <= r) {
+            const uint32_t key = (win_popc<WORDS>(qd, ep + (size_t)e * WORDS) << 16) | m.y;
+            second = min(second, max(best, key));
+            best = min(best, key);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 1; s < WIN_LPQ; s <<= 1) {              // merge the lanes of a query: they saw disjoint entries
+      const uint32_t ob = __shfl_xor(best, s, 64), os = __shfl_xor(second, s, 64);
+      second = min(min(second, os), max(best, ob));
+      best = min(best, ob);
+    }
+    if (sub == 0 && i < nq) {
+      idx[o] = best == 0xffffffffu ? -1 : (int32_t)(best & 0xffffu);
+      dist[o] = best == 0xffffffffu ? 0xffffffffu : best >> 16;
+      dist2[o] = second == 0xffffffffu ? 0xffffffffu : second >> 16;
+    }
+  }
+}
+
 
 }  // namespace pm

@@ -252,6 +252,64 @@ def matchHammingWindowBatch(qkp, qdesc, qcounts, tkp, tdesc, tcounts, levels, ra
     return idx, dist, dist2
 
 
+def level_scales_q16(levels):
+    """Q16 level-0 pixels per level pixel of each level, from the level table alone: round(65536 * width_0 / width_l)
+    (halves round up), the scale_q16 of matchHammingScaledWindowBatch."""
+    w0 = int(levels[0][0])
+    return [(2 * 65536 * w0 + int(t[0])) // (2 * int(t[0])) for t in levels]
+
+
+def _scaled_tables(levels, scale_q16, radius0):
+    """levels, scale_q16 and radius0 (int, or one per level; scale_q16 None = level_scales_q16) as C arrays."""
+    lv, n, r = _window_tables(levels, radius0)
+    if scale_q16 is None:
+        scale_q16 = level_scales_q16(levels)
+    s = [int(scale_q16)] * n if isinstance(scale_q16, (int, np.integer)) else [int(v) for v in scale_q16]
+    if len(s) != n:
+        raise ValueError(f"scale_q16: {len(s)} values for {n} levels")
+    return lv, n, (ctypes.c_int32 * max(1, n))(*s), r
+
+
+def reserveMatchScaledWindow(levels, scale_q16, radius0, level_span: int, t_stride: int, batch: int, *, words=8,
+                             ctx: Context | None = None):
+    """Sizes the context's scaled-window workspace (pislam_match_scaled_window_reserve): afterwards
+    matchHammingScaledWindowBatch of the same or a smaller shape allocates nothing and can be captured into a hipGraph."""
+    ctx = ctx or default_context()
+    lv, n, s, r = _scaled_tables(levels, scale_q16, radius0)
+    ctx.check(ctx.lib.pislam_match_scaled_window_reserve(ctx.h, words, lv, n, s, r, level_span, t_stride, batch),
+              "pislam_match_scaled_window_reserve")
+
+
+def matchHammingScaledWindowBatch(qkp, qdesc, qcounts, tkp, tdesc, tcounts, levels, scale_q16, radius0, level_span=1,
+                                  qpred=None, idx=None, dist=None, dist2=None, *, ctx: Context | None = None):
+    """Scale-aware guided window matcher (pislam_match_hamming_scaled_window_batch) on device-resident front-end
+    outputs laid out as for matchHammingWindowBatch.  Positions map to level 0 through scale_q16 (Q16 level-0 pixels
+    per level pixel, int or one per level; None = level_scales_q16(levels)); query i on level lq sees the train
+    keypoints on levels lq - level_span .. lq + level_span within radius0[lq] (level-0 pixels, int or one per level)
+    of its window centre: its own mapped position, or qpred[b][i] = (X, Y) (int32 device tensor [batch][q_stride][2])
+    when given.  Returns (idx, dist, dist2) int32 tensors [batch][q_stride]; asynchronous on the ctx stream."""
+    import torch
+    ctx = ctx or default_context()
+    batch, qs, words = qdesc.shape
+    ts = tdesc.shape[1]
+    if tdesc.shape[2] != words:
+        raise ValueError("query and train descriptors differ in words")
+    if qpred is not None and (qpred.dtype != torch.int32 or tuple(qpred.shape) != (batch, qs, 2)):
+        raise ValueError("qpred must be an int32 tensor [batch][q_stride][2]")
+    lv, n, s, r = _scaled_tables(levels, scale_q16, radius0)
+    if idx is None:
+        idx = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
+    if dist is None:
+        dist = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
+    if dist2 is None:
+        dist2 = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
+    ctx.check(ctx.lib.pislam_match_hamming_scaled_window_batch(ctx.h, words, lv, n, s, r, int(level_span), ptr(qkp),
+                                                               ptr(qdesc), ptr(qcounts), ptr(qpred), qs, ptr(tkp),
+                                                               ptr(tdesc), ptr(tcounts), ts, batch, ptr(idx), ptr(dist),
+                                                               ptr(dist2)), "pislam_match_hamming_scaled_window_batch")
+    return idx, dist, dist2
+
+
 # ---- Gaussian.h:48, Bilinear.h:42, Bilinear.h:165 -------------------------------------
 def gaussian5x5(width, height, img, out, *, ctx: Context | None = None):
     """pislam::gaussian5x5<vstep>(width, height, img, out); img may be out (in place)."""
