@@ -440,6 +440,86 @@ int pislam_match_hamming_scaled_window_batch(pislam_ctx *ctx, int words,
                                              const uint32_t *tkp, const uint32_t *tdesc, const uint32_t *tcounts,
                                              size_t t_stride, int batch, int32_t *idx, uint32_t *dist, uint32_t *dist2);
 
+/* Rectified stereo matching: left <-> right
+ * correspondences of rectified stereo pairs with an SAD sub-pixel refinement,
+ * after ORB-SLAM2's Frame::ComputeStereoMatches, stated in integers.  Pair b
+ * is (left b, right b); the left list is the query, the right list the train.
+ * Pairs, counts, keypoint words, descriptor layouts, PISLAM_COUNT_INVALID as
+ * 0, the level of a position (the rectangle that holds it) and the Q16
+ * mapping X = (u * s_l + 32768) >> 16 (u = x - col0, v = y - row0
+ * level-local; likewise Y) are those of
+ * pislam_match_hamming_scaled_window_batch.  Both pyramids share `levels`.
+ *  1. Band search: right j on level lr is a candidate for left i on level ll
+ *     when |ll - lr| <= level_span, |Yl - Yr| <= row_radius0[lr] (level-0
+ *     pixels, indexed by the RIGHT level) and min_disp <= Xl - Xr <= max_disp
+ *     (signed).  idx[i] = the best candidate on dist << 16 | j (ties: the
+ *     smallest j; -1 without candidates), dist[i] = its Hamming distance
+ *     (0xffffffff without).  Both are written whether or not the match is
+ *     accepted below.
+ *  2. Steps 3-6 run only when dist[i] <= max_hamming (ORB-SLAM2: < 75 for
+ *     256-bit descriptors).
+ *  3. SAD refinement on level ll of both images, w = sad_radius,
+ *     L = search_radius.  The right centre column on level ll is
+ *     ur0 = floor((Xr * 65536 + floor(s_ll / 2)) / s_ll) (64-bit; the right
+ *     keypoint's own u when lr == ll and s >= 65536).  For inc in [-L, L]:
+ *     sad(inc) = sum over |dx|, |dy| <= w of
+ *       |(Lp(ul+dx, vl+dy) - Lp(ul, vl)) - (Rp(ur0+inc+dx, vl+dy) - Rp(ur0+inc, vl))|
+ *     where Lp / Rp are the bytes at
+ *     pyr + b * pyramid_stride + (row0 + v) * vstep + col0 + u (the right
+ *     patch uses the left row vl: the pair is rectified).  The match is
+ *     rejected when any pixel this would read, for any inc, lies outside level
+ *     ll's rectangle (a complete check; ORB-SLAM2's covers part of the range).
+ *     Otherwise ib = the inc of the smallest sad (ties: the smallest inc); the
+ *     match is rejected when ib = -L or ib = +L.
+ *  4. Sub-pixel fit: d1, d2, d3 = sad(ib-1), sad(ib), sad(ib+1),
+ *     num = d1 - d3, den = 2 (d1 + d3 - 2 d2) >= 0; delta_q8 = 0 if den == 0,
+ *     else floor((512 num + den) / (2 den)) (floor division, not C
+ *     truncation; |delta_q8| <= 128).
+ *  5. Disparity in level-0 pixels, Q8: dl_q8 = 256 (ul - ur0 - ib) - delta_q8,
+ *     disp_q8 = floor((dl_q8 * s_ll + 32768) / 65536) (signed 64-bit).  The
+ *     match is accepted iff 256 min_disp <= disp_q8 <= 256 max_disp; then
+ *     disp_q8 = max(disp_q8, 1) (callers may divide by it; ORB-SLAM2 clamps to
+ *     0.01 px) and sad[i] = sad(ib).
+ *  6. Median filter (median_filter = 1): m = pair b's accepted SADs sorted
+ *     ascending, element n / 2; every accepted match with 10 sad > 21 m
+ *     (sad > 1.5 * 1.4 * m) is rejected.  ORB-SLAM2 rejects with >=, which
+ *     with m = 0 (routine on clean or synthetic input) rejects everything; the
+ *     strict > keeps the zero-SAD matches.
+ *  7. A rejected match gets disp_q8 = -1 and sad = 0xffffffff.  nstereo[b]
+ *     (optional, device) = the matches accepted after the filter.  Entries at
+ *     and beyond the pair's left count are not written.
+ * Outputs idx, dist, disp_q8, sad are [batch][l_stride].
+ * Limits: words in {1,2,4,8}; 1 <= nlevels <= 16, level rectangles non-empty,
+ * disjoint, inside [0, rows) x [0, vstep) and 12-bit coordinates;
+ * 1 <= scale_q16[l] <= 2^20 and every mapped extent <= 65535 (as the scaled
+ * window matcher); 0 <= row_radius0[l] <= 65535;
+ * 0 <= level_span <= nlevels - 1; 0 <= min_disp <= max_disp <= 65535;
+ * max_hamming >= 0; 1 <= sad_radius <= 7; 1 <= search_radius <= 8;
+ * median_filter in {0, 1}; r_stride <= 65535.  Anything else, or a host
+ * pointer where a device pointer is required: PISLAM_ERR_INVALID, before
+ * anything is launched or written.  Device pointers only (nstereo may be
+ * NULL), except `levels`, `scale_q16`, `row_radius0` and `p` (host, read
+ * during the call: a captured graph keeps its own copy).  Asynchronous on the
+ * context stream, no host round trip; the workspace is the context's own (not
+ * either window matcher's) and grows on demand, which synchronises; after
+ * pislam_match_stereo_reserve of the same or a larger shape the call
+ * allocates nothing and never synchronises, so it can be captured into a
+ * hipGraph. */
+typedef struct pislam_stereo_params {
+  int32_t level_span, min_disp, max_disp, max_hamming, sad_radius, search_radius, median_filter;
+} pislam_stereo_params;
+int pislam_match_stereo_reserve(pislam_ctx *ctx, int words, const pislam_level *levels, int nlevels,
+                                const int32_t *scale_q16, const int32_t *row_radius0, const pislam_stereo_params *p,
+                                size_t r_stride, int batch);
+int pislam_match_stereo_batch(pislam_ctx *ctx, int words, const pislam_level *levels, int nlevels,
+                              const int32_t *scale_q16, const int32_t *row_radius0, const pislam_stereo_params *p,
+                              const uint8_t *left_pyr, const uint8_t *right_pyr, int vstep, int rows,
+                              size_t pyramid_stride,
+                              const uint32_t *lkp, const uint32_t *ldesc, const uint32_t *lcounts, size_t l_stride,
+                              const uint32_t *rkp, const uint32_t *rdesc, const uint32_t *rcounts, size_t r_stride,
+                              int batch, int32_t *idx, uint32_t *dist, int32_t *disp_q8, uint32_t *sad,
+                              uint32_t *nstereo);
+
 /* ---- multi-GPU: one process per GPU, pyramids sharded, ONE collective ---- */
 
 /* The reference is a single-threaded per-frame loop without cross-frame state

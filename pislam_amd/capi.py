@@ -30,6 +30,11 @@ class FrontendParams(ctypes.Structure):
         "log_bucket_size", "bucket_limit", "words", "max_keypoints")]
 
 
+class StereoParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "level_span", "min_disp", "max_disp", "max_hamming", "sad_radius", "search_radius", "median_filter")]
+
+
 # name -> (restype, argtypes); every symbol declared in include/pislam_hip.h
 SYMBOLS = {
     "pislam_abi_version": (_i, []),
@@ -89,6 +94,11 @@ SYMBOLS = {
     "pislam_match_hamming_scaled_window_batch": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),
                                                       ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _vp, _vp, _sz, _vp,
                                                       _vp, _vp, _sz, _i, _vp, _vp, _vp]),
+    "pislam_match_stereo_reserve": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),
+                                         ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(StereoParams), _sz, _i]),
+    "pislam_match_stereo_batch": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),
+                                       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(StereoParams), _vp, _vp, _i, _i,
+                                       _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
     "pislam_dist_shard": (_i, [_i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "pislam_dist_get_unique_id": (_i, [ctypes.c_char_p]),
     "pislam_dist_init": (_i, [_vp, ctypes.c_char_p, _i, _i]),

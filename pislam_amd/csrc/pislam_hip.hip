@@ -108,6 +108,7 @@ struct pislam_ctx {
   DevBuf w_ustage, w_ucount;         // bucket selection pass (pf::k_bucket_select): per-unit lists and counts
   DevBuf w_win_off, w_win_meta, w_win_desc;   // windowed matcher: cell offsets, cell-sorted train entries (pm::k_window_index)
   DevBuf w_sc_off, w_sc_meta, w_sc_desc;      // scaled window matcher: the same for pm::k_scaled_index (its own buffers)
+  DevBuf w_st_off, w_st_meta, w_st_desc;      // stereo matcher: pm::k_scaled_index of the right keypoints (its own buffers)
   // Host-built plan tables the kernels read instead of walking the plan (the bucket selection pass's unit table): one
   // device buffer per distinct CONTENT, never rewritten in place — a captured graph keeps reading the table
   // of the plan it was captured with whatever other shapes the context serves in between.  At most 16 are kept (the oldest
@@ -505,7 +506,8 @@ PISLAM_EXPORT int pislam_ctx_destroy(pislam_ctx *c) {
   for (DevBuf *b : {&c->s_img, &c->s_out, &c->s_pts, &c->s_desc, &c->s_misc, &c->s_rots, &c->s_tmp, &c->w_cnt,
                     &c->w_off, &c->w_total, &c->w_cellkp, &c->w_score, &c->w_stage, &c->w_stripcnt, &c->w_work, &c->w_prof, &c->w_ovf,
                     &c->w_stagedesc, &c->w_ustage, &c->w_ucount, &c->w_sync, &c->w_chain, &c->w_win_off, &c->w_win_meta,
-                    &c->w_win_desc, &c->w_sc_off, &c->w_sc_meta, &c->w_sc_desc})
+                    &c->w_win_desc, &c->w_sc_off, &c->w_sc_meta, &c->w_sc_desc, &c->w_st_off, &c->w_st_meta,
+                    &c->w_st_desc})
     b->release();
   for (auto *t : c->plan_tables) {
     t->dev.release();
@@ -2539,6 +2541,122 @@ PISLAM_EXPORT int pislam_match_hamming_scaled_window_batch(pislam_ctx *c, int wo
   }
 #undef PISLAM_MATCH_SCALED
   return launch_ok(c, "k_match_scaled");
+}
+
+// ---- rectified stereo matching ------------------------------------------------------------
+
+namespace {
+
+// Checks the arguments every stereo call shares and lays out the right keypoints' cell grids (host only): the scaled
+// window matcher's plan at span 0 with radius0 = row_radius0, so that level lr's cells are max(1, row_radius0[lr])
+// level-0 pixels (coarsened to fit pm::WIN_MAX_CELLS), then the level span of the band search.
+int stereo_plan(pislam_ctx *c, int words, const pislam_level *lv, int nlevels, const int32_t *scale_q16,
+                const int32_t *row_radius0, const pislam_stereo_params *p, size_t r_stride, int batch, pm::ScaledPlan *P) {
+  if (!p) return fail(c, PISLAM_ERR_INVALID, "null stereo parameters");
+  PCHK(scaled_plan(c, words, lv, nlevels, scale_q16, row_radius0, 0, r_stride, batch, P));
+  if (p->level_span < 0 || p->level_span > nlevels - 1) return fail(c, PISLAM_ERR_INVALID, "level_span must be 0..nlevels-1");
+  if (p->min_disp < 0 || p->min_disp > p->max_disp || p->max_disp > 65535)
+    return fail(c, PISLAM_ERR_INVALID, "need 0 <= min_disp <= max_disp <= 65535");
+  if (p->max_hamming < 0) return fail(c, PISLAM_ERR_INVALID, "max_hamming must be >= 0");
+  if (p->sad_radius < 1 || p->sad_radius > pm::ST_MAX_W) return fail(c, PISLAM_ERR_INVALID, "sad_radius must be 1..7");
+  if (p->search_radius < 1 || p->search_radius > pm::ST_MAX_L) return fail(c, PISLAM_ERR_INVALID, "search_radius must be 1..8");
+  if (p->median_filter != 0 && p->median_filter != 1) return fail(c, PISLAM_ERR_INVALID, "median_filter must be 0 or 1");
+  P->span = p->level_span;
+  return PISLAM_OK;
+}
+
+int stereo_workspace(pislam_ctx *c, const pm::ScaledPlan &P, int words, size_t r_stride, int batch) {
+  if (c->w_st_off.ensure(sizeof(uint32_t) * (size_t)(P.ncells + 1) * batch) != PISLAM_OK ||
+      c->w_st_meta.ensure(sizeof(uint2) * r_stride * batch) != PISLAM_OK ||
+      c->w_st_desc.ensure(sizeof(uint32_t) * words * r_stride * batch) != PISLAM_OK)
+    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(stereo matcher workspace)");
+  return PISLAM_OK;
+}
+
+}  // namespace
+
+PISLAM_EXPORT int pislam_match_stereo_reserve(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
+                                              const int32_t *scale_q16, const int32_t *row_radius0,
+                                              const pislam_stereo_params *p, size_t r_stride, int batch) {
+  if (!c) return PISLAM_ERR_INVALID;
+  pm::ScaledPlan P;
+  PCHK(stereo_plan(c, words, levels, nlevels, scale_q16, row_radius0, p, r_stride, batch, &P));
+  HIPCHK(c, hipSetDevice(c->device));
+  return stereo_workspace(c, P, words, r_stride, batch);
+}
+
+PISLAM_EXPORT int pislam_match_stereo_batch(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
+                                            const int32_t *scale_q16, const int32_t *row_radius0,
+                                            const pislam_stereo_params *p, const uint8_t *left_pyr,
+                                            const uint8_t *right_pyr, int vstep, int rows, size_t pyramid_stride,
+                                            const uint32_t *lkp, const uint32_t *ldesc, const uint32_t *lcounts,
+                                            size_t l_stride, const uint32_t *rkp, const uint32_t *rdesc,
+                                            const uint32_t *rcounts, size_t r_stride, int batch, int32_t *idx,
+                                            uint32_t *dist, int32_t *disp_q8, uint32_t *sad, uint32_t *nstereo) {
+  if (!c) return PISLAM_ERR_INVALID;
+  pm::ScaledPlan P;
+  PCHK(stereo_plan(c, words, levels, nlevels, scale_q16, row_radius0, p, r_stride, batch, &P));
+  if (vstep < 1 || rows < 1) return fail(c, PISLAM_ERR_INVALID, "vstep and rows must be positive");
+  for (int l = 0; l < nlevels; l++)
+    if (levels[l].col0 + levels[l].width > vstep || levels[l].row0 + levels[l].height > rows)
+      return fail(c, PISLAM_ERR_INVALID, "a level rectangle lies outside [0, rows) x [0, vstep)");
+  if (l_stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "l_stride too large");
+  if (nstereo && !is_device_ptr(nstereo)) return fail(c, PISLAM_ERR_INVALID, "nstereo must be a device pointer or null");
+  if (batch == 0 || (l_stride == 0 && !nstereo)) return PISLAM_OK;
+  for (const void *ptr : {(const void *)left_pyr, (const void *)right_pyr, (const void *)lkp, (const void *)ldesc,
+                          (const void *)lcounts, (const void *)rkp, (const void *)rdesc, (const void *)rcounts,
+                          (const void *)idx, (const void *)dist, (const void *)disp_q8, (const void *)sad}) {
+    if (!ptr) return fail(c, PISLAM_ERR_INVALID, "null pointer");
+    if (!is_device_ptr(ptr)) return fail(c, PISLAM_ERR_INVALID, "the stereo matcher takes device pointers only");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  PCHK(stereo_workspace(c, P, words, r_stride, batch));
+  uint32_t *off = c->w_st_off.as<uint32_t>(), *edesc = c->w_st_desc.as<uint32_t>();
+  uint2 *meta = c->w_st_meta.as<uint2>();
+  if (l_stride > 0) {
+    hipLaunchKernelGGL(pm::k_scaled_index, dim3((unsigned)batch), dim3(pm::WIN_INDEX_THREADS), 0, c->stream, P, words,
+                       rkp, rdesc, rcounts, r_stride, off, meta, edesc);
+    PCHK(launch_ok(c, "k_scaled_index"));
+    // grids as pislam_match_hamming_window_batch: sized for the capacity, ~16 workgroups per CU over the batch
+    const int tiles = cdiv((int)std::min<size_t>(l_stride, 0x7fffffff - pm::WIN_QPW), pm::WIN_QPW);
+    const int per_pair = batch > 1 ? std::max(1, std::min(tiles, cdiv(16 * std::max(1, c->num_cus), batch))) : std::min(tiles, 65535);
+#define PISLAM_MATCH_STEREO(W)                                                                                           \
+    hipLaunchKernelGGL(pm::k_match_stereo<W>, dim3((unsigned)per_pair, (unsigned)batch), dim3(pm::WIN_THREADS), 0,        \
+                       c->stream, P, p->min_disp, p->max_disp, lkp, ldesc, lcounts, l_stride, r_stride, off, meta, edesc, \
+                       idx, dist)
+    switch (words) {
+      case 1: PISLAM_MATCH_STEREO(1); break;
+      case 2: PISLAM_MATCH_STEREO(2); break;
+      case 4: PISLAM_MATCH_STEREO(4); break;
+      default: PISLAM_MATCH_STEREO(8); break;          // (stereo_plan accepted only 1, 2, 4, 8)
+    }
+#undef PISLAM_MATCH_STEREO
+    PCHK(launch_ok(c, "k_match_stereo"));
+    const int rtiles = cdiv((int)std::min<size_t>(l_stride, 0x7fffffff - pm::ST_QPW), pm::ST_QPW);
+    const int r_per_pair = batch > 1 ? std::max(1, std::min(rtiles, cdiv(16 * std::max(1, c->num_cus), batch)))
+                                     : std::min(rtiles, 65535);
+#define PISLAM_STEREO_REFINE(W)                                                                                          \
+    hipLaunchKernelGGL(pm::k_stereo_refine<W>, dim3((unsigned)r_per_pair, (unsigned)batch), dim3(pm::ST_THREADS), 0,      \
+                       c->stream, P, (uint32_t)p->max_hamming, p->search_radius, p->min_disp, p->max_disp, left_pyr,   \
+                       right_pyr, vstep, pyramid_stride, lkp, lcounts, l_stride, rkp, r_stride, idx, dist, disp_q8, sad)
+    switch (p->sad_radius) {
+      case 1: PISLAM_STEREO_REFINE(1); break;
+      case 2: PISLAM_STEREO_REFINE(2); break;
+      case 3: PISLAM_STEREO_REFINE(3); break;
+      case 4: PISLAM_STEREO_REFINE(4); break;
+      case 5: PISLAM_STEREO_REFINE(5); break;
+      case 6: PISLAM_STEREO_REFINE(6); break;
+      default: PISLAM_STEREO_REFINE(7); break;         // (stereo_plan accepted only 1..7)
+    }
+#undef PISLAM_STEREO_REFINE
+    PCHK(launch_ok(c, "k_stereo_refine"));
+  }
+  if (p->median_filter || nstereo) {
+    hipLaunchKernelGGL(pm::k_stereo_median, dim3((unsigned)batch), dim3(pm::ST_MEDIAN_THREADS), 0, c->stream,
+                       p->median_filter, lcounts, l_stride, disp_q8, sad, nstereo);
+    PCHK(launch_ok(c, "k_stereo_median"));
+  }
+  return PISLAM_OK;
 }
 
 // ---- batches in flight: a pipeline of contexts behind one object --------------------------------

@@ -642,4 +642,310 @@ __global__ __launch_bounds__(WIN_THREADS) void k_match_scaled(ScaledPlan P, cons
 }
 
 
+// ---------------------------------------------------------------------------
+// Rectified stereo matching (include/pislam_hip.h): left keypoint i (query) against the right
+// keypoints (train) of the same pair inside a row band, then an SAD refinement on the pyramid images, a parabola fit
+// and a per-pair median cut.  Four launches:
+//   k_scaled_index    the right keypoints, with a ScaledPlan whose radius is row_radius0 and whose cell side comes from
+//                     it (host: stereo_plan), unchanged from the scaled window matcher.
+//   k_match_stereo    WIN_LPQ lanes per left keypoint; a wave-uniform loop over the plan's levels; the cell rows the
+//                     band |Yl - Yr| <= row_radius0[lr] overlaps, columns Xl - max_disp .. Xl - min_disp, clipped to the
+//                     level's mapped extent; exact test, best on dist << 16 | j.  Writes idx / dist.
+//   k_stereo_refine   ST_LPQ lanes per left keypoint (one patch row each): the 2L + 1 SADs of the (2w+1)^2 patch, the
+//                     argmin, the parabola fit and the disparity.  w and L are kernel arguments, so the unrolled column
+//                     and offset loops are cut by uniform branches and the register arrays are only indexed by
+//                     compile-time constants.  Writes disp_q8 / sad.
+//   k_stereo_median   one workgroup per pair: the n/2-th accepted SAD by a two-pass LDS radix select (SADs are below
+//                     2^17: 8 high bits, then 9 low bits), the outlier cut and the count of accepted matches.
+// ---------------------------------------------------------------------------
+constexpr int ST_MAX_W = 7;            // sad_radius limit: patch rows / columns 2w + 1 <= 15
+constexpr int ST_MAX_L = 8;            // search_radius limit: 2L + 1 <= 17 offsets
+constexpr int ST_LPQ = 16;             // lanes per left keypoint in k_stereo_refine (>= 2 * ST_MAX_W + 1)
+constexpr int ST_THREADS = 256;
+constexpr int ST_QPW = ST_THREADS / ST_LPQ;
+constexpr int ST_MEDIAN_THREADS = 1024;
+
+// grid (query tiles, batch), WIN_THREADS threads; l_stride / r_stride in entries; outputs [batch][l_stride].
+template <int WORDS>
+__global__ __launch_bounds__(WIN_THREADS) void k_match_stereo(ScaledPlan P, int32_t min_disp, int32_t max_disp,
+                                                              const uint32_t *__restrict__ lkp,
+                                                              const uint32_t *__restrict__ ldesc,
+                                                              const uint32_t *__restrict__ lcount, size_t l_stride,
+                                                              size_t r_stride, const uint32_t *__restrict__ cell_off,
+                                                              const uint2 *__restrict__ ent_meta,
+                                                              const uint32_t *__restrict__ ent_desc,
+                                                              int32_t *__restrict__ idx, uint32_t *__restrict__ dist) {
+  const int b = blockIdx.y;
+  const uint32_t nq = win_count(lcount[b], l_stride);
+  const uint32_t sub = threadIdx.x % WIN_LPQ;
+  const uint32_t *off_b = cell_off + (size_t)b * (P.ncells + 1);
+  const uint2 *mp = ent_meta + (size_t)b * r_stride;
+  const uint32_t *ep = ent_desc + (size_t)b * r_stride * WORDS;
+  for (uint32_t q0 = blockIdx.x * (uint32_t)WIN_QPW; q0 < nq; q0 += gridDim.x * (uint32_t)WIN_QPW) {
+    const uint32_t i = q0 + threadIdx.x / WIN_LPQ;
+    const size_t o = (size_t)b * l_stride + i;
+    uint32_t best = 0xffffffffu;                        // (keys are at most 256 << 16 | 65534: never the sentinel)
+    int32_t lq = -1, xl = 0, yl = 0;                    // lq -1: no candidates (past the count, or in no level)
+    uint32_t qd[WORDS];
+#pragma unroll
+    for (int w = 0; w < WORDS; w++) qd[w] = 0;
+    if (i < nq) {
+      const uint32_t k = lkp[o];
+      const int32_t x = (int32_t)((k >> 12) & 0xfffu), y = (int32_t)(k & 0xfffu);
+      const ScaledHit h = sc_level(P, x, y);
+      if (h.level >= 0) {
+        lq = h.level;
+        xl = sc_map(x - h.col0, h.scale);
+        yl = sc_map(y - h.row0, h.scale);
+        const uint32_t *qp = ldesc + o * WORDS;
+#pragma unroll
+        for (int w = 0; w < WORDS; w++) qd[w] = qp[w];
+      }
+    }
+    for (int l = 0; l < P.nlevels; l++) {               // wave-uniform: L comes from kernel-argument loads
+      if (lq < 0 || abs(l - lq) > P.span) continue;
+      const ScaledLevel L = P.lv[l];
+      const int32_t r = L.radius;                       // row_radius0 of the RIGHT level
+      // the band clipped to the level's mapped extent: its right entries all lie inside it
+      const int32_t x0 = max(xl - max_disp, 0), x1 = min(xl - min_disp, L.ext_x);
+      const int32_t y0 = max(yl - r, 0), y1 = min(yl + r, L.ext_y);
+      if (x0 > x1 || y0 > y1) continue;
+      const int32_t cx0 = x0 / L.side, cx1 = x1 / L.side, cy0 = y0 / L.side, cy1 = y1 / L.side;
+      const uint32_t *off = off_b + L.base;
+      for (int32_t cy = cy0; cy <= cy1; cy++) {
+        const uint32_t e1 = off[cy * L.ncx + cx1 + 1];
+        for (uint32_t e = off[cy * L.ncx + cx0] + sub; e < e1; e += WIN_LPQ) {
+          const uint2 m = mp[e];
+          const int32_t dx = xl - (int32_t)(m.x >> 16), ty = (int32_t)(m.x & 0xffffu);
+          if (abs(ty - yl) <= r && dx >= min_disp && dx <= max_disp)
+            best = min(best, (win_popc<WORDS>(qd, ep + (size_t)e * WORDS) << 16) | m.y);
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 1; s < WIN_LPQ; s <<= 1) best = min(best, __shfl_xor(best, s, 64));
+    if (sub == 0 && i < nq) {
+      idx[o] = best == 0xffffffffu ? -1 : (int32_t)(best & 0xffffu);
+      dist[o] = best == 0xffffffffu ? 0xffffffffu : best >> 16;
+    }
+  }
+}
+
+// The levels whose rectangles hold the left position (x, y) and the right position (xr, yr): the left level's
+// rectangle and scale and the right position's mapped X, picked by selects in one wave-uniform loop.
+struct StereoHit {
+  int32_t col0, row0, width, height, scale, xr;
+};
+__device__ __forceinline__ StereoHit st_levels(const ScaledPlan &P, int32_t x, int32_t y, int32_t xr, int32_t yr) {
+  StereoHit h{0, 0, 0, 0, 65536, 0};
+  for (int l = 0; l < P.nlevels; l++) {
+    const ScaledLevel L = P.lv[l];
+    if ((uint32_t)(x - L.col0) < (uint32_t)L.width && (uint32_t)(y - L.row0) < (uint32_t)L.height)
+      h.col0 = L.col0, h.row0 = L.row0, h.width = L.width, h.height = L.height, h.scale = L.scale;
+    if ((uint32_t)(xr - L.col0) < (uint32_t)L.width && (uint32_t)(yr - L.row0) < (uint32_t)L.height)
+      h.xr = sc_map(xr - L.col0, L.scale);
+  }
+  return h;
+}
+
+// floor(a / b) for b > 0
+__device__ __forceinline__ int64_t st_floordiv(int64_t a, int64_t b) {
+  const int64_t q = a / b;
+  return (a % b != 0 && a < 0) ? q - 1 : q;
+}
+
+// grid (query tiles, batch), ST_THREADS threads; pyramids uint8 [batch] at pyramid_stride bytes, rows of vstep bytes.
+// Reads idx / dist of k_match_stereo and writes disp_q8 / sad for every left entry below the count.  W = sad_radius
+// (a template argument: the patch columns need no branches); L = search_radius.
+template <int W>
+__global__ __launch_bounds__(ST_THREADS) void k_stereo_refine(ScaledPlan P, uint32_t max_hamming, int32_t L, int32_t min_disp, int32_t max_disp,
+                                                              const uint8_t *__restrict__ lpyr,
+                                                              const uint8_t *__restrict__ rpyr, int32_t vstep,
+                                                              size_t pyramid_stride, const uint32_t *__restrict__ lkp,
+                                                              const uint32_t *__restrict__ lcount, size_t l_stride,
+                                                              const uint32_t *__restrict__ rkp, size_t r_stride,
+                                                              const int32_t *__restrict__ idx,
+                                                              const uint32_t *__restrict__ dist,
+                                                              int32_t *__restrict__ disp_q8, uint32_t *__restrict__ sad) {
+  constexpr int32_t w = W;
+  const int b = blockIdx.y;
+  const uint32_t nq = win_count(lcount[b], l_stride);
+  const int32_t sub = (int32_t)(threadIdx.x % ST_LPQ);
+  const uint8_t *lp = lpyr + (size_t)b * pyramid_stride, *rp = rpyr + (size_t)b * pyramid_stride;
+  for (uint32_t q0 = blockIdx.x * (uint32_t)ST_QPW; q0 < nq; q0 += gridDim.x * (uint32_t)ST_QPW) {
+    const uint32_t i = q0 + threadIdx.x / ST_LPQ;
+    const size_t o = (size_t)b * l_stride + i;
+    bool ok = false;
+    int32_t ul = 0, vl = 0, scale = 65536;
+    int64_t ur0 = 0;
+    const uint8_t *lrow = lp, *rrow = rp;               // level ll's row vl: column col0 + ul (left), col0 + ur0 (right)
+    if (i < nq && dist[o] <= max_hamming) {
+      const uint32_t kl = lkp[o], kr = rkp[(size_t)b * r_stride + (uint32_t)idx[o]];
+      // (a match has both positions in a level: k_match_stereo and k_scaled_index skip the others)
+      const StereoHit hl = st_levels(P, (int32_t)((kl >> 12) & 0xfffu), (int32_t)(kl & 0xfffu),
+                                     (int32_t)((kr >> 12) & 0xfffu), (int32_t)(kr & 0xfffu));
+      ul = (int32_t)((kl >> 12) & 0xfffu) - hl.col0;
+      vl = (int32_t)(kl & 0xfffu) - hl.row0;
+      scale = hl.scale;
+      ur0 = ((int64_t)hl.xr * 65536 + scale / 2) / scale;
+      // every pixel of every offset's patch inside level ll's rectangle
+      ok = ul - w >= 0 && ul + w < hl.width && vl - w >= 0 && vl + w < hl.height && ur0 - L - w >= 0 &&
+           ur0 + L + w < hl.width;
+      const size_t row = (size_t)(hl.row0 + vl) * vstep + hl.col0;
+      lrow = lp + row + ul;
+      rrow = rp + row + (ok ? ur0 : 0);
+    }
+    // this lane's patch row dy = sub - w (lanes past 2w + 1 add nothing)
+    uint32_t s[2 * ST_MAX_L + 1];
+#pragma unroll
+    for (int t = 0; t < 2 * ST_MAX_L + 1; t++) s[t] = 0;
+    if (ok && sub <= 2 * w) {
+      const int32_t dy = sub - w;
+      const int32_t cl = lrow[0];
+      const uint8_t *la = lrow + (ptrdiff_t)dy * vstep - w, *ra = rrow + (ptrdiff_t)dy * vstep - L - w;
+      // all ST_MAX_L offsets on either side, the reads clamped to the 2L + 1 in range (no branches on L: the offsets
+      // past L are computed from repeated pixels and never looked at)
+      // (the clamps are kept in vector registers: as scalars the compiler hoists all of them and spills)
+      uint32_t lim_r = 2 * (W + L), lim_c = 2 * L;
+      asm("" : "+v"(lim_r), "+v"(lim_c));
+      const uint8_t *ca = rrow - L;
+      int32_t a[2 * W + 1], rv[2 * W + 2 * ST_MAX_L + 1], cr[2 * ST_MAX_L + 1];
+#pragma unroll
+      for (int k = 0; k < 2 * W + 1; k++) a[k] = (int32_t)la[k] - cl;
+#pragma unroll
+      for (int k = 0; k < 2 * W + 2 * ST_MAX_L + 1; k++) rv[k] = ra[min((uint32_t)k, lim_r)];
+#pragma unroll
+      for (int t = 0; t < 2 * ST_MAX_L + 1; t++) cr[t] = ca[min((uint32_t)t, lim_c)];
+#pragma unroll
+      for (int t = 0; t < 2 * ST_MAX_L + 1; t++) {
+#pragma unroll
+        for (int k = 0; k < 2 * W + 1; k++) s[t] += (uint32_t)abs(a[k] - (rv[k + t] - cr[t]));
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 2 * ST_MAX_L + 1; t++) {
+#pragma unroll
+      for (int d = 1; d < ST_LPQ; d <<= 1) s[t] += __shfl_xor(s[t], d, 64);
+    }
+    if (sub == 0 && i < nq) {
+      int32_t out_disp = -1;
+      uint32_t out_sad = 0xffffffffu;
+      if (ok) {
+        // argmin (ties: the smallest offset), then its neighbours, by compile-time indexing only
+        uint32_t d2 = s[0];
+        int32_t tb = 0;
+#pragma unroll
+        for (int t = 1; t < 2 * ST_MAX_L + 1; t++)
+          if (s[t] < d2 && t <= 2 * L) d2 = s[t], tb = t;
+        if (tb != 0 && tb != 2 * L) {
+          uint32_t d1 = 0, d3 = 0;
+#pragma unroll
+          for (int t = 0; t < 2 * ST_MAX_L + 1; t++) {
+            if (t == tb - 1) d1 = s[t];
+            if (t == tb + 1) d3 = s[t];
+          }
+          const int64_t num = (int64_t)d1 - d3, den = 2 * ((int64_t)d1 + d3 - 2 * (int64_t)d2);
+          const int64_t delta = den == 0 ? 0 : st_floordiv(512 * num + den, 2 * den);
+          const int64_t dl = 256 * ((int64_t)ul - ur0 - (tb - L)) - delta;
+          const int64_t disp = (dl * scale + 32768) >> 16;        // arithmetic shift: floor
+          if (disp >= 256 * (int64_t)min_disp && disp <= 256 * (int64_t)max_disp) {
+            out_disp = (int32_t)max(disp, (int64_t)1);
+            out_sad = d2;
+          }
+        }
+      }
+      disp_q8[o] = out_disp;
+      sad[o] = out_sad;
+    }
+  }
+}
+
+// Wave 0 of the workgroup: the bin of hist[0 .. NB) that holds rank k (cumulative counts), and the rank inside it.
+template <int NB>
+__device__ __forceinline__ void st_select_bin(const uint32_t *hist, uint32_t k, uint32_t *bin, uint32_t *rank) {
+  constexpr int PER = NB / 64;
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t c[PER], sum = 0;
+#pragma unroll
+  for (int j = 0; j < PER; j++) sum += (c[j] = hist[lane * PER + j]);
+  uint32_t incl = sum;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t v = __shfl_up(incl, d, 64);
+    if ((int)lane >= d) incl += v;
+  }
+  uint32_t run = incl - sum;
+  // the one lane whose range [run, incl) holds k
+  if (k >= run && k < incl) {
+#pragma unroll
+    for (int j = 0; j < PER; j++) {
+      if (k >= run && k < run + c[j]) *bin = lane * PER + j, *rank = k - run;
+      run += c[j];
+    }
+  }
+}
+
+// grid (batch), ST_MEDIAN_THREADS threads.  median_filter 0: only counts (nstereo must then be non-null).
+__global__ __launch_bounds__(ST_MEDIAN_THREADS) void k_stereo_median(int32_t median_filter,
+                                                                     const uint32_t *__restrict__ lcount, size_t l_stride,
+                                                                     int32_t *__restrict__ disp_q8,
+                                                                     uint32_t *__restrict__ sad,
+                                                                     uint32_t *__restrict__ nstereo) {
+  __shared__ uint32_t hist[512];
+  __shared__ uint32_t sel[3];                            // accepted count, high bin, rank inside it / low bin
+  const int b = blockIdx.x;
+  const uint32_t tid = threadIdx.x;
+  const uint32_t nq = win_count(lcount[b], l_stride);
+  int32_t *dp = disp_q8 + (size_t)b * l_stride;
+  uint32_t *sp = sad + (size_t)b * l_stride;
+  for (uint32_t c = tid; c < 512; c += ST_MEDIAN_THREADS) hist[c] = 0;
+  if (tid == 0) sel[0] = 0;
+  __syncthreads();
+  uint32_t mine = 0;
+  for (uint32_t i = tid; i < nq; i += ST_MEDIAN_THREADS) {
+    const uint32_t v = sp[i];
+    if (v == 0xffffffffu) continue;
+    mine++;
+    if (median_filter) atomicAdd(&hist[v >> 9], 1u);   // SADs are at most 225 * 510 < 2^17: 256 high bins
+  }
+  if (mine) atomicAdd(&sel[0], mine);
+  __syncthreads();
+  const uint32_t n = sel[0];
+  if (!median_filter || n == 0) {
+    if (tid == 0 && nstereo) nstereo[b] = n;
+    return;
+  }
+  if (tid < 64) st_select_bin<256>(hist, n / 2, &sel[1], &sel[2]);
+  __syncthreads();
+  const uint32_t hi = sel[1], k = sel[2];
+  for (uint32_t c = tid; c < 512; c += ST_MEDIAN_THREADS) hist[c] = 0;
+  __syncthreads();
+  for (uint32_t i = tid; i < nq; i += ST_MEDIAN_THREADS) {
+    const uint32_t v = sp[i];
+    if (v != 0xffffffffu && (v >> 9) == hi) atomicAdd(&hist[v & 511u], 1u);
+  }
+  __syncthreads();
+  if (tid < 64) st_select_bin<512>(hist, k, &sel[2], &sel[1]);
+  __syncthreads();
+  const uint32_t m = hi << 9 | sel[2];
+  if (tid == 0) sel[0] = 0;
+  __syncthreads();
+  // outliers: 10 * sad > 21 * m (sad > 1.5 * 1.4 * m), kept: counted
+  uint32_t kept = 0;
+  for (uint32_t i = tid; i < nq; i += ST_MEDIAN_THREADS) {
+    const uint32_t v = sp[i];
+    if (v == 0xffffffffu) continue;
+    if (10u * v > 21u * m) {
+      dp[i] = -1;
+      sp[i] = 0xffffffffu;
+    } else {
+      kept++;
+    }
+  }
+  if (kept) atomicAdd(&sel[0], kept);
+  __syncthreads();
+  if (tid == 0 && nstereo) nstereo[b] = sel[0];
+}
+
+
 }  // namespace pm

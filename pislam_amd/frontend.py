@@ -17,7 +17,7 @@ import ctypes
 import numpy as np
 
 from . import capi
-from .capi import Context, FrontendParams, Level, ptr
+from .capi import Context, FrontendParams, Level, StereoParams, ptr
 
 _default_ctx: Context | None = None
 
@@ -308,6 +308,67 @@ def matchHammingScaledWindowBatch(qkp, qdesc, qcounts, tkp, tdesc, tcounts, leve
                                                                ptr(tdesc), ptr(tcounts), ts, batch, ptr(idx), ptr(dist),
                                                                ptr(dist2)), "pislam_match_hamming_scaled_window_batch")
     return idx, dist, dist2
+
+
+def _stereo_tables(levels, scale_q16, row_radius0, level_span, min_disp, max_disp, max_hamming, sad_radius,
+                   search_radius, median_filter):
+    """levels, scale_q16 (None = level_scales_q16), row_radius0 (int, or one per level) and the parameters as C."""
+    lv, n, s, r = _scaled_tables(levels, scale_q16, row_radius0)
+    p = StereoParams(int(level_span), int(min_disp), int(max_disp), int(max_hamming), int(sad_radius),
+                     int(search_radius), int(median_filter))
+    return lv, n, s, r, p
+
+
+def reserveMatchStereo(levels, scale_q16, row_radius0, r_stride: int, batch: int, *, min_disp, max_disp, max_hamming=74,
+                       level_span=1, sad_radius=5, search_radius=5, median_filter=True, words=8,
+                       ctx: Context | None = None):
+    """Sizes the context's stereo-matcher workspace (pislam_match_stereo_reserve): afterwards matchStereoBatch of the
+    same or a smaller shape allocates nothing and can be captured into a hipGraph."""
+    ctx = ctx or default_context()
+    lv, n, s, r, p = _stereo_tables(levels, scale_q16, row_radius0, level_span, min_disp, max_disp, max_hamming,
+                                    sad_radius, search_radius, median_filter)
+    ctx.check(ctx.lib.pislam_match_stereo_reserve(ctx.h, words, lv, n, s, r, ctypes.byref(p), r_stride, batch),
+              "pislam_match_stereo_reserve")
+
+
+def matchStereoBatch(lkp, ldesc, lcounts, rkp, rdesc, rcounts, left_pyr, right_pyr, levels, scale_q16, row_radius0, *,
+                     min_disp, max_disp, max_hamming=74, level_span=1, sad_radius=5, search_radius=5,
+                     median_filter=True, idx=None, dist=None, disp_q8=None, sad=None, nstereo=None,
+                     ctx: Context | None = None):
+    """Rectified stereo matcher (pislam_match_stereo_batch): left keypoint i of pair b against the right keypoints of
+    pair b inside the row band |Yl - Yr| <= row_radius0[lr] (level-0 pixels, int or one per level) with
+    min_disp <= Xl - Xr <= max_disp, on levels within level_span; then an SAD refinement of the matches with
+    dist <= max_hamming on the uint8 pyramids left_pyr / right_pyr ([batch][rows][vstep] device tensors of the same
+    shape and stride), a parabola fit and, with median_filter, a per-pair median cut.  Keypoints and descriptors are
+    laid out as for matchHammingWindowBatch; scale_q16 as matchHammingScaledWindowBatch (None = level_scales_q16).
+    Returns (idx, dist, disp_q8, sad, nstereo): int32 tensors [batch][l_stride] (disp_q8 in level-0 pixels, Q8; -1
+    and sad 0xffffffff for a rejected match) and nstereo [batch] (accepted matches); asynchronous on the ctx stream."""
+    import torch
+    ctx = ctx or default_context()
+    batch, ls, words = ldesc.shape
+    rs = rdesc.shape[1]
+    if rdesc.shape[2] != words:
+        raise ValueError("left and right descriptors differ in words")
+    if left_pyr.dim() != 3 or tuple(left_pyr.shape) != tuple(right_pyr.shape) or left_pyr.stride() != right_pyr.stride():
+        raise ValueError("left_pyr and right_pyr must be [batch][rows][vstep] tensors of the same shape and stride")
+    if left_pyr.dtype != torch.uint8 or right_pyr.dtype != torch.uint8 or left_pyr.stride(2) != 1:
+        raise ValueError("pyramids must be uint8 with contiguous rows")
+    rows, vstep = int(left_pyr.shape[1]), int(left_pyr.stride(1))
+    if int(left_pyr.shape[2]) > vstep:
+        raise ValueError("pyramid rows overlap")
+    lv, n, s, r, p = _stereo_tables(levels, scale_q16, row_radius0, level_span, min_disp, max_disp, max_hamming,
+                                    sad_radius, search_radius, median_filter)
+    out = []
+    for t in (idx, dist, disp_q8, sad):
+        out.append(torch.empty((batch, ls), dtype=torch.int32, device=ldesc.device) if t is None else t)
+    if nstereo is None:
+        nstereo = torch.empty((batch,), dtype=torch.int32, device=ldesc.device)
+    ctx.check(ctx.lib.pislam_match_stereo_batch(ctx.h, words, lv, n, s, r, ctypes.byref(p), ptr(left_pyr),
+                                                ptr(right_pyr), vstep, rows, int(left_pyr.stride(0)), ptr(lkp),
+                                                ptr(ldesc), ptr(lcounts), ls, ptr(rkp), ptr(rdesc), ptr(rcounts), rs,
+                                                batch, *[ptr(t) for t in out], ptr(nstereo)),
+              "pislam_match_stereo_batch")
+    return (*out, nstereo)
 
 
 # ---- Gaussian.h:48, Bilinear.h:42, Bilinear.h:165 -------------------------------------
