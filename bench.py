@@ -10,6 +10,11 @@ pyramids per GPU (BASELINE.json configs[1]); for N>1 each rank owns its own 256 
 scaling, configs[2]) and the step ends with the RCCL all-gather of the per-pyramid keypoint counts.
 Prints ONE JSON line on rank 0.
 
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints
+the line.  Everything else the benchmark measures or checks runs after the timed steps under --full: the CPU oracle
+baseline, parity_in_run against the oracle, one call at a time, one pyramid per call, the strip kernel alone, the
+roofline, the pyramid-build and matcher figures, and every other BASELINE configuration (other_workloads).
+
 Process structure for N > 1 (the run must not be lost to a hang): every torchrun rank is a SUPERVISOR that
 never touches the GPU.  The supervisors (a gloo group of their own) start one WORKER child per rank with a
 rendezvous port of its own, wait for it under a timeout, agree on the outcome, and on a failure or a hang kill
@@ -216,7 +221,7 @@ def other_workloads(args, timeout_s: float = 90.0):
     recs, ok = {}, True
     for name, extra in OTHER_WORKLOADS:
         cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.other_steps), "--warmup", "5", "--spin-s", "0.4",
-               "--no-cpu-baseline", "--no-one-pyramid", "--no-other-workloads", "--parity-pyramids", "8",
+               "--full", "--no-cpu-baseline", "--no-one-pyramid", "--no-other-workloads", "--parity-pyramids", "8",
                "--streams", str(args.streams), "--graph", str(args.graph)] + extra
         t0 = time.perf_counter()
         try:
@@ -271,6 +276,10 @@ def build_parser():
     ap.add_argument("--selftest-spawn", action="store_true",
                     help="testing only: exercise launch + supervision + rendezvous + count exchange with fake counts on "
                          "the CPU (no GPU work, value is null)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline: cpu_baseline, "
+                         "parity_in_run, one_batch_ms, one_pyramid_ms, the roofline, pyramid-build and matcher figures and "
+                         "other_workloads (the --no-* and --parity-pyramids options below choose among them)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of the 1-thread cpu_baseline leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--one-pyramid", action="store_true", help=argparse.SUPPRESS)      # (rounds 1-4: opt-in; now the default)
@@ -278,7 +287,7 @@ def build_parser():
                     help="skip one_pyramid_ms (ONE pyramid per call, the reference's frame-at-a-time use): profiled runs pass this "
                          "— its small launches would enter the kernel-trace averages and PMC medians of the batch kernels")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip other_workloads: by default the N=1 run of the headline workload ends with a SHORT run of every other "
+                    help="skip other_workloads: by default the N=1 --full run of the headline workload ends with a SHORT run of every other "
                          "configuration (the reference's demo photo, configs[3] on spec and at the dense shape count, configs[4], the "
                          "README bucket mode <4,3>) as child processes of this one — ms/step, strip-kernel time, keypoints per pyramid and "
                          "parity_in_run of each — so that the driver's ONE line carries a number for every BASELINE config")
@@ -296,7 +305,7 @@ def build_parser():
                          "demo-photo = the reference's own demo pyramid (tests/golden/demo_pyramid.npz: natural image content, "
                          "1754 keypoints) x batch, every lane its own copy")
     ap.add_argument("--parity-pyramids", type=int, default=32,
-                    help="parity_in_run: pyramids of lane 0 whose timed outputs (counts, keypoints, descriptors) are compared with "
+                    help="parity_in_run (--full): pyramids of lane 0 whose timed outputs (counts, keypoints, descriptors) are compared with "
                          "the oracle after the timed region (other lanes: 8 each); 0 = off.  A mismatch ends the run with rc 6")
     ap.add_argument("--pipeline", type=int, default=0, help="0 auto (fused), 1 staged, 2 fused")
     ap.add_argument("--strip-rows", type=int, default=0)
@@ -947,7 +956,7 @@ def worker_main(args):
     # parity_in_run: what the timed steps left in the lanes' output sets (the set the lane's LAST timed step wrote), copied
     # now — before anything else touches the pipelines
     snap = None
-    NP = max(0, args.parity_pyramids)
+    NP = max(0, args.parity_pyramids) if args.full else 0
     if NP:
         snap = []
         for li, P in enumerate(pipes):
@@ -957,16 +966,17 @@ def worker_main(args):
             snap.append((o[0][:n].cpu().numpy().view(np.uint32), o[1][:n].cpu().numpy().view(np.uint32).reshape(n, args.max_keypoints, -1),
                          o[2].cpu().numpy().view(np.uint32)))
     clock_ghz = None
-    try:
-        for _ in range(4):
-            spin_once()                                  # (the probe wave shares the GPU with the steps' kernels)
-        side = Context(device=local_rank)
-        side.set_option("own_stream", 2)
-        clock_ghz = side.shader_clock_ghz(200)
-        side.close()
-        torch.cuda.synchronize()
-    except Exception:                                    # noqa: BLE001
-        pass
+    if args.full:
+        try:
+            for _ in range(4):
+                spin_once()                              # (the probe wave shares the GPU with the steps' kernels)
+            side = Context(device=local_rank)
+            side.set_option("own_stream", 2)
+            clock_ghz = side.shader_clock_ghz(200)
+            side.close()
+            torch.cuda.synchronize()
+        except Exception:                                # noqa: BLE001
+            pass
     dt_rank = dt
     dts = [dt]
     coll_ok, coll = pdist.collectives_agree([P.xchg for P in pipes], world, dev)   # outside the timed region
@@ -984,146 +994,148 @@ def worker_main(args):
     def local_kp_fn(c_):
         return int(torch.clamp(c_.to(torch.int64), max=args.max_keypoints).sum().item())
 
-    # ---- one batch call at a time (the figure a caller without any stream choreography gets): a pipeline of depth 1
-    # (same library path, same graphs), and the stage times of eager calls on a plain context ----
-    ev = []
-    for _ in range(min(8, max(3, args.steps))):
-        with torch.cuda.stream(stream):
-            launches1(kp, desc, counts)
-        ev.append(fe1.last_timing())
-    ev_total_ms = float(np.mean([e[0] for e in ev]))
-    ev_stage_ms = [float(np.mean([e[1][i] for e in ev])) for i in range(3)]
-    one_ms = None
-    one_pyr_ms = one_pyr_lat_ms = one_pyr_path = None
-    try:
-        pl1 = capi.Pipeline(device=local_rank, depth=1)
-        pl1.set_option("graphs", 1 if use_graphs else 0)
-        for k_, v_ in lib_opts:
-            pl1.set_option(k_, v_)
-        pl1.reserve(fe.params, fe.levels, B)
-        c1 = pl1.lane(0)
-        s1 = torch.cuda.ExternalStream(pl1.stream_of(0), device=dev)
-        b1 = PyramidBuilder(w0, h0, ctx=c1) if builder is not None else None
-        o1 = fe.alloc_outputs(B, dev)
-        REPS = 30
-
-        def one_call():
-            if b1 is not None:
-                b1(d_frames, d_pyr, margins_clean=bool(args.margins_clean))
-            pl1.submit(fe.params, fe.levels, d_pyr, *o1)
-            if m_out is not None:
-                matchHammingBatch(o1[1], o1[2], t_desc, t_counts, *m_out, ctx=c1)
-
-        brackets = []
-        with torch.cuda.stream(s1):
-            for _ in range(4):                           # eager, captured, first replays
-                one_call()
-            for _ in range(3):                           # three brackets, the fastest counts (clock ramps, stragglers)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(s1)
-                for _ in range(REPS):
-                    one_call()
-                e1.record(s1)
-                brackets.append((e0, e1))
-        torch.cuda.synchronize()
-        one_ms = min(a.elapsed_time(b) for a, b in brackets) / REPS
-    except Exception as e:                               # noqa: BLE001
-        pl1 = None
-        print(f"[bench] one-call-at-a-time measurement failed: {e!r}", file=sys.stderr)
     lib_pipe = {"api": "pislam_pipeline_create / _submit / _wait (include/pislam_hip.h): the timed steps ARE submits to this object",
                 "depth": S, **pl.stats()}
-    # dominant kernel alone: REP back-to-back launches inside one hipEvent bracket (a single eager launch is
-    # bracketed together with ~10 us of command-processor latency)
-    strip_ms = None
-    if args.pipeline != 1:
-        REP = 16
-        ctx.set_option("repeat_strips", REP)
+    ev_total_ms = ev_stage_ms = one_ms = one_pyr_ms = one_pyr_lat_ms = one_pyr_path = strip_ms = build_info = match_info = None
+    if args.full:
+        # ---- one batch call at a time (the figure a caller without any stream choreography gets): a pipeline of depth 1
+        # (same library path, same graphs), and the stage times of eager calls on a plain context ----
+        ev = []
+        for _ in range(min(8, max(3, args.steps))):
+            with torch.cuda.stream(stream):
+                launches1(kp, desc, counts)
+            ev.append(fe1.last_timing())
+        ev_total_ms = float(np.mean([e[0] for e in ev]))
+        ev_stage_ms = [float(np.mean([e[1][i] for e in ev])) for i in range(3)]
+        one_ms = None
+        one_pyr_ms = one_pyr_lat_ms = one_pyr_path = None
         try:
-            rr = []
-            for _ in range(3):
-                fe1(d_pyr, kp, desc, counts)
-                rr.append(fe1.last_timing()[1][0] / REP)
-            strip_ms = float(np.mean(rr))
-        finally:
-            ctx.set_option("repeat_strips", 1)
-    build_info = None
-    if builder is not None:
-        # what PISLAM_BUILD_MARGINS_CLEAN leaves out of the step: the margin pass of a build into a dirty buffer
-        try:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            tm = []
-            for clean in (True, False):
-                with torch.cuda.stream(stream):
-                    e0.record(stream)
-                    for _ in range(10):
-                        builder1(d_frames, d_pyr, margins_clean=clean)
-                    e1.record(stream)
-                torch.cuda.synchronize()
-                tm.append(e0.elapsed_time(e1) / 10)
-            build_info = {"build_ms_margins_clean": tm[0], "build_ms_with_margin_pass": tm[1],
-                          "timed_step_uses": "margins_clean" if args.margins_clean else "margin pass every step"}
-        except Exception:                                # noqa: BLE001
-            pass
+            pl1 = capi.Pipeline(device=local_rank, depth=1)
+            pl1.set_option("graphs", 1 if use_graphs else 0)
+            for k_, v_ in lib_opts:
+                pl1.set_option(k_, v_)
+            pl1.reserve(fe.params, fe.levels, B)
+            c1 = pl1.lane(0)
+            s1 = torch.cuda.ExternalStream(pl1.stream_of(0), device=dev)
+            b1 = PyramidBuilder(w0, h0, ctx=c1) if builder is not None else None
+            o1 = fe.alloc_outputs(B, dev)
+            REPS = 30
 
-    match_info = None
-    if m_out is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(5):
-            matchHammingBatch(desc, counts, t_desc, t_counts, *m_out, ctx=ctx)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        cq = torch.clamp(counts.to(torch.int64), max=args.max_keypoints)
-        ct = torch.clamp(t_counts.to(torch.int64), max=args.max_keypoints)
-        pairs = int((cq * ct).sum().item())
-        mm = e0.elapsed_time(e1) / 5
-        match_info = {"ms": mm, "descriptor_pairs": pairs, "pairs_per_s": pairs / (mm * 1e-3),
-                      "matched_within_64_bits": int(((m_out[1] <= 64) & (torch.arange(args.max_keypoints, device=dev)[None, :]
-                                                                          < cq[:, None])).sum().item())}
+            def one_call():
+                if b1 is not None:
+                    b1(d_frames, d_pyr, margins_clean=bool(args.margins_clean))
+                pl1.submit(fe.params, fe.levels, d_pyr, *o1)
+                if m_out is not None:
+                    matchHammingBatch(o1[1], o1[2], t_desc, t_counts, *m_out, ctx=c1)
 
-    # (LAST of the measurements: its small, synchronised calls leave the GPU mostly idle — the strip-kernel bracket above
-    #  would otherwise be taken on clocks that have dropped; round 5's first profile showed 0.173 ms there against
-    #  0.161 ms in the kernel trace of the same kernel)
-    if pl1 is not None:
-        # ... and ONE pyramid per call on the same object (the reference's own use: a frame at a time)
-        if not args.no_one_pyramid and b1 is None and m_out is None:
+            brackets = []
+            with torch.cuda.stream(s1):
+                for _ in range(4):                           # eager, captured, first replays
+                    one_call()
+                for _ in range(3):                           # three brackets, the fastest counts (clock ramps, stragglers)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(s1)
+                    for _ in range(REPS):
+                        one_call()
+                    e1.record(s1)
+                    brackets.append((e0, e1))
+            torch.cuda.synchronize()
+            one_ms = min(a.elapsed_time(b) for a, b in brackets) / REPS
+        except Exception as e:                               # noqa: BLE001
+            pl1 = None
+            print(f"[bench] one-call-at-a-time measurement failed: {e!r}", file=sys.stderr)
+        # dominant kernel alone: REP back-to-back launches inside one hipEvent bracket (a single eager launch is
+        # bracketed together with ~10 us of command-processor latency)
+        strip_ms = None
+        if args.pipeline != 1:
+            REP = 16
+            ctx.set_option("repeat_strips", REP)
             try:
-                o_s = fe.alloc_outputs(1, dev)
-                d_one = d_pyr[:1]
-                brackets = []
-                with torch.cuda.stream(s1):
-                    for _ in range(4):
-                        pl1.submit(fe.params, fe.levels, d_one, *o_s)
-                    for _ in range(3):
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record(s1)
-                        for _ in range(200):
-                            pl1.submit(fe.params, fe.levels, d_one, *o_s)
-                        e1.record(s1)
-                        brackets.append((e0, e1))
-                torch.cuda.synchronize()
-                one_pyr_ms = min(a.elapsed_time(b) for a, b in brackets) / 200
-                if int(o_s[2].cpu()[0]) != int(o1[2].cpu()[0]):
-                    raise RuntimeError("a pyramid alone and as the first of its batch gave different keypoint counts")
-                # ... and the latency of ONE isolated call on an idle stream (events right around the submit, a synchronise
-                # between calls): 200 back-to-back submits above are paced by the host's ~30 us per pislam_pipeline_submit
-                # from Python, not by the GPU
-                lat = []
-                with torch.cuda.stream(s1):
-                    for _ in range(60):
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record(s1)
-                        pl1.submit(fe.params, fe.levels, d_one, *o_s)
-                        e1.record(s1)
-                        e1.synchronize()
-                        lat.append(e0.elapsed_time(e1))
-                one_pyr_lat_ms = float(np.median(lat[10:]))
-                one_pyr_path = "one launch (pf::k_frame)" if (fe.last_path_of(c1) & 4) else "three launches"
-            except Exception as e:                       # noqa: BLE001
-                one_pyr_ms = None
-                print(f"[bench] one-pyramid-per-call measurement failed: {e!r}", file=sys.stderr)
+                rr = []
+                for _ in range(3):
+                    fe1(d_pyr, kp, desc, counts)
+                    rr.append(fe1.last_timing()[1][0] / REP)
+                strip_ms = float(np.mean(rr))
+            finally:
+                ctx.set_option("repeat_strips", 1)
+        build_info = None
+        if builder is not None:
+            # what PISLAM_BUILD_MARGINS_CLEAN leaves out of the step: the margin pass of a build into a dirty buffer
+            try:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                tm = []
+                for clean in (True, False):
+                    with torch.cuda.stream(stream):
+                        e0.record(stream)
+                        for _ in range(10):
+                            builder1(d_frames, d_pyr, margins_clean=clean)
+                        e1.record(stream)
+                    torch.cuda.synchronize()
+                    tm.append(e0.elapsed_time(e1) / 10)
+                build_info = {"build_ms_margins_clean": tm[0], "build_ms_with_margin_pass": tm[1],
+                              "timed_step_uses": "margins_clean" if args.margins_clean else "margin pass every step"}
+            except Exception:                                # noqa: BLE001
+                pass
 
-        pl1.close()
+        match_info = None
+        if m_out is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(5):
+                matchHammingBatch(desc, counts, t_desc, t_counts, *m_out, ctx=ctx)
+            e1.record(stream)
+            torch.cuda.synchronize()
+            cq = torch.clamp(counts.to(torch.int64), max=args.max_keypoints)
+            ct = torch.clamp(t_counts.to(torch.int64), max=args.max_keypoints)
+            pairs = int((cq * ct).sum().item())
+            mm = e0.elapsed_time(e1) / 5
+            match_info = {"ms": mm, "descriptor_pairs": pairs, "pairs_per_s": pairs / (mm * 1e-3),
+                          "matched_within_64_bits": int(((m_out[1] <= 64) & (torch.arange(args.max_keypoints, device=dev)[None, :]
+                                                                              < cq[:, None])).sum().item())}
+
+        # (LAST of the measurements: its small, synchronised calls leave the GPU mostly idle — the strip-kernel bracket above
+        #  would otherwise be taken on clocks that have dropped; round 5's first profile showed 0.173 ms there against
+        #  0.161 ms in the kernel trace of the same kernel)
+        if pl1 is not None:
+            # ... and ONE pyramid per call on the same object (the reference's own use: a frame at a time)
+            if not args.no_one_pyramid and b1 is None and m_out is None:
+                try:
+                    o_s = fe.alloc_outputs(1, dev)
+                    d_one = d_pyr[:1]
+                    brackets = []
+                    with torch.cuda.stream(s1):
+                        for _ in range(4):
+                            pl1.submit(fe.params, fe.levels, d_one, *o_s)
+                        for _ in range(3):
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record(s1)
+                            for _ in range(200):
+                                pl1.submit(fe.params, fe.levels, d_one, *o_s)
+                            e1.record(s1)
+                            brackets.append((e0, e1))
+                    torch.cuda.synchronize()
+                    one_pyr_ms = min(a.elapsed_time(b) for a, b in brackets) / 200
+                    if int(o_s[2].cpu()[0]) != int(o1[2].cpu()[0]):
+                        raise RuntimeError("a pyramid alone and as the first of its batch gave different keypoint counts")
+                    # ... and the latency of ONE isolated call on an idle stream (events right around the submit, a synchronise
+                    # between calls): 200 back-to-back submits above are paced by the host's ~30 us per pislam_pipeline_submit
+                    # from Python, not by the GPU
+                    lat = []
+                    with torch.cuda.stream(s1):
+                        for _ in range(60):
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record(s1)
+                            pl1.submit(fe.params, fe.levels, d_one, *o_s)
+                            e1.record(s1)
+                            e1.synchronize()
+                            lat.append(e0.elapsed_time(e1))
+                    one_pyr_lat_ms = float(np.median(lat[10:]))
+                    one_pyr_path = "one launch (pf::k_frame)" if (fe.last_path_of(c1) & 4) else "three launches"
+                except Exception as e:                       # noqa: BLE001
+                    one_pyr_ms = None
+                    print(f"[bench] one-pyramid-per-call measurement failed: {e!r}", file=sys.stderr)
+
+            pl1.close()
     deferred, nstrips = fe1.last_stats()
     # counts are the reference's un-clamped totals; keypoints beyond the capacity are neither stored nor
     # described, so only min(count, max_keypoints) per pyramid is credited
@@ -1146,53 +1158,75 @@ def worker_main(args):
     parity_bad = False
     if rank == 0:
         fused = args.pipeline != 1
-        valid_px = sum(t[0] * t[1] for t in levels)
-        # algorithmic bytes of the DOMINANT KERNEL's launch: every valid pixel once + 36 B per
-        # keypoint + 4 B count — the strip kernel reads no frame and writes no pyramid, so the 720p-build
-        # workload's extra traffic (frame read + pyramid write) is priced with the whole step, never here
-        b_alg_launch = B * (valid_px + 4) + 36 * local_kp
-        b_alg_step = b_alg_launch + (B * (w0 * h0 + valid_px) if builder is not None else 0)
-        # dominant kernel: k_fused_strips (one launch per step covers the whole batch); for the staged
-        # pipeline there is no single dominant launch, so the whole step is priced instead
-        launch_ms = (strip_ms if strip_ms else ev_stage_ms[0]) if fused else ev_total_ms
-        achieved = b_alg_launch / (launch_ms * 1e-3) / 1e9
         step_ms = dt / args.steps * 1e3
-        bsfx = f"_buckets{args.log_bucket_size}{args.bucket_limit}" if args.log_bucket_size else ""
-        prof, prof_source = load_counters(args.workload, B, bsfx) if fused else (None, "null: staged pipeline")
-        prof3, prof3_source = load_counters(args.workload, B, bsfx + "_streams3") if fused else (None, "null: staged pipeline")
-        traffic = traffic_step = traffic_step3 = valu = lds_info = None
-        if prof3:
-            traffic_step3 = sum(k.get("hbm_bytes_per_launch", 0) * k.get("launches_per_step", 1) for k in prof3["kernels"].values()) or None
-        if prof:
-            ks = prof["kernels"]
-            dom = ks.get("k_fused_strips", {})
-            traffic = dom.get("hbm_bytes_per_launch")
-            traffic_step = sum(k.get("hbm_bytes_per_launch", 0) * k.get("launches_per_step", 1) for k in ks.values()) or None
-            if dom.get("SQ_LDS_IDX_ACTIVE") and dom.get("SQ_BUSY_CU_CYCLES"):
-                # the LDS of the dominant kernel: cycles its arrays were active over the CUs' busy cycles, and the share of
-                # those cycles that were bank-conflict replays (MI355X_MICROARCH.md, LDS section)
-                lds_info = {"busy_frac": dom["SQ_LDS_IDX_ACTIVE"] / dom["SQ_BUSY_CU_CYCLES"],
-                            "conflict_frac": dom.get("SQ_LDS_BANK_CONFLICT", 0.0) / dom["SQ_LDS_IDX_ACTIVE"],
-                            "lds_insts": dom.get("SQ_INSTS_LDS"), "wait_inst_lds": dom.get("SQ_WAIT_INST_LDS"),
-                            "per_phase": f"profiles/{PROFILE_TAG}_phase_ablation.txt", "source": prof_source}
-            if dom.get("SQ_INSTS_VALU") and clock_ghz:
-                nsimd = 4 * 256
-                insts = dom["SQ_INSTS_VALU"]
-                rate = insts / (launch_ms * 1e-3)                 # wave64 VALU instructions per second, chip-wide
-                valu = {"insts": insts, "salu_insts": dom.get("SQ_INSTS_SALU"),
-                        "issue_frac": insts * VALU_CYCLES_PER_WAVE_INST / (nsimd * clock_ghz * 1e9 * launch_ms * 1e-3),
-                        "issue_frac_of_sustained": rate / VALU_SUSTAINED_PER_S,
-                        "wave_insts_per_s": rate, "sustained_wave_insts_per_s": VALU_SUSTAINED_PER_S,
-                        "cycles_per_wave_inst_assumed": VALU_CYCLES_PER_WAVE_INST,
-                        "clock_ghz": clock_ghz,
-                        "note": "wave64 VALU instructions of one strip-kernel launch / launch_ms.  issue_frac prices an instruction "
-                                "at 4 cycles of its SIMD (1024 SIMDs x shader clock / 4): the rate tools/probes/valu_rate.hip "
-                                "MEASURED on this part for dependent-free 32-bit integer ops is 528-538 G wave-instructions/s "
-                                "chip-wide = 4.5 cycles — /opt/skills/guides/MI355X_MICROARCH.md quotes 2 cycles per wave64 op, which "
-                                "the probe does not reach for this instruction mix.  issue_frac_of_sustained = the rate over that "
-                                "measured 533 G/s: the share of the ACHIEVABLE integer issue rate this kernel uses — the binding "
-                                "resource.  Clock measured in this run (s_memtime vs s_memrealtime under the steps' load)",
-                        "source": prof_source}
+        roofline = None
+        if args.full:
+            valid_px = sum(t[0] * t[1] for t in levels)
+            # algorithmic bytes of the DOMINANT KERNEL's launch: every valid pixel once + 36 B per
+            # keypoint + 4 B count — the strip kernel reads no frame and writes no pyramid, so the 720p-build
+            # workload's extra traffic (frame read + pyramid write) is priced with the whole step, never here
+            b_alg_launch = B * (valid_px + 4) + 36 * local_kp
+            b_alg_step = b_alg_launch + (B * (w0 * h0 + valid_px) if builder is not None else 0)
+            # dominant kernel: k_fused_strips (one launch per step covers the whole batch); for the staged
+            # pipeline there is no single dominant launch, so the whole step is priced instead
+            launch_ms = (strip_ms if strip_ms else ev_stage_ms[0]) if fused else ev_total_ms
+            achieved = b_alg_launch / (launch_ms * 1e-3) / 1e9
+            bsfx = f"_buckets{args.log_bucket_size}{args.bucket_limit}" if args.log_bucket_size else ""
+            prof, prof_source = load_counters(args.workload, B, bsfx) if fused else (None, "null: staged pipeline")
+            prof3, prof3_source = load_counters(args.workload, B, bsfx + "_streams3") if fused else (None, "null: staged pipeline")
+            traffic = traffic_step = traffic_step3 = valu = lds_info = None
+            if prof3:
+                traffic_step3 = sum(k.get("hbm_bytes_per_launch", 0) * k.get("launches_per_step", 1) for k in prof3["kernels"].values()) or None
+            if prof:
+                ks = prof["kernels"]
+                dom = ks.get("k_fused_strips", {})
+                traffic = dom.get("hbm_bytes_per_launch")
+                traffic_step = sum(k.get("hbm_bytes_per_launch", 0) * k.get("launches_per_step", 1) for k in ks.values()) or None
+                if dom.get("SQ_LDS_IDX_ACTIVE") and dom.get("SQ_BUSY_CU_CYCLES"):
+                    # the LDS of the dominant kernel: cycles its arrays were active over the CUs' busy cycles, and the share of
+                    # those cycles that were bank-conflict replays
+                    lds_info = {"busy_frac": dom["SQ_LDS_IDX_ACTIVE"] / dom["SQ_BUSY_CU_CYCLES"],
+                                "conflict_frac": dom.get("SQ_LDS_BANK_CONFLICT", 0.0) / dom["SQ_LDS_IDX_ACTIVE"],
+                                "lds_insts": dom.get("SQ_INSTS_LDS"), "wait_inst_lds": dom.get("SQ_WAIT_INST_LDS"),
+                                "per_phase": f"profiles/{PROFILE_TAG}_phase_ablation.txt", "source": prof_source}
+                if dom.get("SQ_INSTS_VALU") and clock_ghz:
+                    nsimd = 4 * 256
+                    insts = dom["SQ_INSTS_VALU"]
+                    rate = insts / (launch_ms * 1e-3)                 # wave64 VALU instructions per second, chip-wide
+                    valu = {"insts": insts, "salu_insts": dom.get("SQ_INSTS_SALU"),
+                            "issue_frac": insts * VALU_CYCLES_PER_WAVE_INST / (nsimd * clock_ghz * 1e9 * launch_ms * 1e-3),
+                            "issue_frac_of_sustained": rate / VALU_SUSTAINED_PER_S,
+                            "wave_insts_per_s": rate, "sustained_wave_insts_per_s": VALU_SUSTAINED_PER_S,
+                            "cycles_per_wave_inst_assumed": VALU_CYCLES_PER_WAVE_INST,
+                            "clock_ghz": clock_ghz,
+                            "note": "wave64 VALU instructions of one strip-kernel launch / launch_ms.  issue_frac prices an instruction "
+                                    "at 4 cycles of its SIMD (1024 SIMDs x shader clock / 4): the rate tools/probes/valu_rate.hip "
+                                    "MEASURED on this part for dependent-free 32-bit integer ops is 528-538 G wave-instructions/s "
+                                    "chip-wide = 4.5 cycles — the 2 cycles per wave64 op often quoted for the part are not what "
+                                    "the probe reaches for this instruction mix.  issue_frac_of_sustained = the rate over that "
+                                    "measured 533 G/s: the share of the ACHIEVABLE integer issue rate this kernel uses — the binding "
+                                    "resource.  Clock measured in this run (s_memtime vs s_memrealtime under the steps' load)",
+                            "source": prof_source}
+            roofline = {
+                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": prof_source,
+                "traffic_whole_step": traffic_step,
+                "traffic_whole_step_3_lanes": traffic_step3, "traffic_3_lanes_source": prof3_source,
+                "kernel": "pf::k_fused_strips (hipEvents on the launch stream around 16 back-to-back launches, / 16, measured after "
+                          "the timed region with the other pipelines idle)" if fused
+                          else "whole staged step (all launches)",
+                "algorithmic_bytes_per_launch": b_alg_launch, "launch_ms": launch_ms,
+                "whole_step": {"algorithmic_bytes": b_alg_step, "ms": step_ms,
+                               "achieved": b_alg_step / (step_ms * 1e-3) / 1e9,
+                               "frac": b_alg_step / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                               "note": "per GPU, every kernel of a step over ms_per_step" +
+                                       (" (bytes incl. frame read + pyramid write of the build)" if builder is not None else "")},
+                "valu": valu,
+                "lds": lds_info,
+                "shader_clock_ghz": clock_ghz,
+                "step_gpu_ms": ev_total_ms,
+                "stage_ms": {"detect+score+nms": ev_stage_ms[0], "overflow pass" if fused else "extract": ev_stage_ms[1],
+                             "gather+orb" if fused else "orb": ev_stage_ms[2]}}
         cfg_idx = {"vga": 2 if world > 1 else 1, "1280x960": 3, "1280x960-dense": 3, "720p-build": 4, "demo-photo": 0}[args.workload]
         out = {
             "metric": METRIC,
@@ -1200,11 +1234,11 @@ def worker_main(args):
             "warmup": args.warmup, "ms_per_step": step_ms, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "u8",
             "data": "the reference's demo photo (fixture), replicated" if args.workload == "demo-photo" else "synthetic",
-            "one_batch_ms": one_ms,
-            "one_pyramid_ms": one_pyr_ms,
-            "one_pyramid_latency_ms": one_pyr_lat_ms,
-            "one_pyramid_path": one_pyr_path,
-            "one_batch_value": (local_kp / (one_ms * 1e-3)) if one_ms else None,
+            **({"one_batch_ms": one_ms,
+                "one_pyramid_ms": one_pyr_ms,
+                "one_pyramid_latency_ms": one_pyr_lat_ms,
+                "one_pyramid_path": one_pyr_path,
+                "one_batch_value": (local_kp / (one_ms * 1e-3)) if one_ms else None} if args.full else {}),
             "config": {
                 "workload": {"vga": f"batch={B} synthetic 640x480 pyramids per GPU, 8 levels x1.2 stacked (vstep=640, "
                                     "2210 rows)",
@@ -1255,31 +1289,11 @@ def worker_main(args):
                 **({"match_inside_step": match_info} if match_info else {}),
             },
             **({"dump_outputs": dumped} if dumped else {}),
-            "roofline": {
-                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": prof_source,
-                "traffic_whole_step": traffic_step,
-                "traffic_whole_step_3_lanes": traffic_step3, "traffic_3_lanes_source": prof3_source,
-                "kernel": "pf::k_fused_strips (hipEvents on the launch stream around 16 back-to-back launches, / 16, measured after "
-                          "the timed region with the other pipelines idle)" if fused
-                          else "whole staged step (all launches)",
-                "algorithmic_bytes_per_launch": b_alg_launch, "launch_ms": launch_ms,
-                "whole_step": {"algorithmic_bytes": b_alg_step, "ms": step_ms,
-                               "achieved": b_alg_step / (step_ms * 1e-3) / 1e9,
-                               "frac": b_alg_step / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                               "note": "per GPU, every kernel of a step over ms_per_step" +
-                                       (" (bytes incl. frame read + pyramid write of the build)" if builder is not None else "")},
-                "valu": valu,
-                "lds": lds_info,
-                "shader_clock_ghz": clock_ghz,
-                "step_gpu_ms": ev_total_ms,
-                "stage_ms": {"detect+score+nms": ev_stage_ms[0], "overflow pass" if fused else "extract": ev_stage_ms[1],
-                             "gather+orb" if fused else "orb": ev_stage_ms[2]},
-            },
+            **({"roofline": roofline} if roofline else {}),
         }
         kept = []
         lb, bl = args.log_bucket_size, args.bucket_limit
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(host, levels, budget_s=args.cpu_seconds, log_bucket=lb, bucket_limit=bl,
                                                keep=NP, kept=kept)
         if snap is not None and not args.ablate:
@@ -1294,9 +1308,9 @@ def worker_main(args):
             out["parity_in_run"] = parity_in_run(snap, kept_full, lane_hosts, levels, args.max_keypoints, lb, bl, pins=pins)
             parity_bad = not out["parity_in_run"]["ok"]
         # every other BASELINE configuration, briefly (children of this process; the headline above is complete by now)
-        # (only in the full default line: development / profiling runs pass --no-cpu-baseline and get none of it)
-        if (world == 1 and not args.no_other_workloads and not args.no_cpu_baseline and args.workload == "vga" and not args.ablate
-                and not args.log_bucket_size and not args.match and args.pipeline != 1 and not args.opt and B == 256):
+        # (only in the --full line of the headline workload: development / profiling runs pass --no-cpu-baseline and get none of it)
+        if (world == 1 and args.full and not args.no_other_workloads and not args.no_cpu_baseline and args.workload == "vga"
+                and not args.ablate and not args.log_bucket_size and not args.match and args.pipeline != 1 and not args.opt and B == 256):
             pl.synchronize()
             torch.cuda.synchronize()
             t_o = time.perf_counter()

@@ -1023,25 +1023,29 @@ def test_bench_step_with_the_c_abi_exchange_on_one_rank():
 
 
 def test_bench_dump_outputs_are_the_same_in_every_run(tmp_path):
-    """`bench.py --dump-outputs DIR`: the outputs of the last timed step as float64 .npy files, identical in two runs with the
-    same arguments (the input is seeded); their counts are the keypoints the line reports for that step's lane, the run's
-    own parity check passed on the same output set, and --steps is the number of timed steps the line reports."""
+    """`bench.py --dump-outputs DIR`: the outputs of the last timed step as float64 .npy files, identical in a plain run and a
+    --full run with the same arguments (the input is seeded); their counts are the keypoints the line reports for that
+    step's lane, the --full run's own parity check passed on the same output set, the plain line carries none of the
+    --full figures, and --steps is the number of timed steps the line reports."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     lines, dumps = [], []
-    for run in range(2):
+    for run, mode in enumerate(([], ["--full"])):
         d = tmp_path / f"run{run}"
         out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "1", "--batch", "16",
-                              "--no-cpu-baseline", "--spin-s", "0.1", "--dump-outputs", str(d)],
+                              "--no-cpu-baseline", "--spin-s", "0.1", "--dump-outputs", str(d)] + mode,
                              capture_output=True, text=True, timeout=300, cwd=root)
         assert out.returncode == 0, out.stderr[-2000:]
         lines.append(json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1]))
         dumps.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    plain, full = lines
+    assert full["parity_in_run"]["ok"] and full["roofline"]["launch_ms"] > 0 and full["one_batch_ms"] > 0
+    assert not {"parity_in_run", "roofline", "one_batch_ms", "cpu_baseline"} & set(plain)
     for r, a in zip(lines, dumps):
-        assert r["steps"] == 5 and r["ms_per_step"] > 0 and r["parity_in_run"]["ok"]
+        assert r["steps"] == 5 and r["ms_per_step"] > 0
         assert set(a) == {"counts", "pyramids", "keypoints", "descriptors"} and all(v.dtype == np.float64 for v in a.values())
         assert r["dump_outputs"]["pyramids"] == "16 of 16" and len(a["counts"]) == 16
         lane_kp = r["config"]["keypoints_per_step_by_lane"][r["dump_outputs"]["lane"]]

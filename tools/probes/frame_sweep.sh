@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 root=${GRAFT_REPO_ROOT:-/root/repo}
 run() {
   d=$root/gpurun_out/fsw_$$
-  rocprofv3 --kernel-trace --stats --output-format csv -d $d -o p -- python $root/bench.py --batch 1 --streams 1 --steps 400 --warmup 40 --no-cpu-baseline --no-one-pyramid --parity-pyramids 1 "$@" > $d.json 2>/dev/null
+  rocprofv3 --kernel-trace --stats --output-format csv -d $d -o p -- python $root/bench.py --batch 1 --streams 1 --steps 400 --warmup 40 --full --no-cpu-baseline --no-one-pyramid --parity-pyramids 1 "$@" > $d.json 2>/dev/null
   python - <<P
 import csv, json
 try:

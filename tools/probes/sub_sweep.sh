@@ -5,7 +5,7 @@ out=${1:-gpurun_out/sub_sweep}
 mkdir -p $out
 run() {  # label, args...
   local label=$1; shift
-  python bench.py --steps 40 --warmup 10 --no-cpu-baseline "$@" 2>/dev/null | python -c "
+  python bench.py --steps 40 --warmup 10 --full --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$label', 'ms/step %.4f' % d['ms_per_step'], 'value %.3e' % d['value'], 'strip_ms %.4f' % d['roofline']['launch_ms'], 'gpu_ms %.4f' % d['roofline']['step_gpu_ms'])
