@@ -106,9 +106,12 @@ struct pislam_ctx {
   // batch pipeline workspace
   DevBuf w_score, w_stage, w_stripcnt, w_work, w_prof, w_ovf, w_stagedesc;
   DevBuf w_ustage, w_ucount;         // bucket selection pass (pf::k_bucket_select): per-unit lists and counts
-  DevBuf w_win_off, w_win_meta, w_win_desc;   // windowed matcher: cell offsets, cell-sorted train entries (pm::k_window_index)
-  DevBuf w_sc_off, w_sc_meta, w_sc_desc;      // scaled window matcher: the same for pm::k_scaled_index (its own buffers)
-  DevBuf w_st_off, w_st_meta, w_st_desc;      // stereo matcher: pm::k_scaled_index of the right keypoints (its own buffers)
+  // Guided matchers: pm::k_scaled_index's cell offsets, cell-sorted train entries and their descriptors.  One set per
+  // matcher (windowed, scaled, stereo), so a graph captured for one is never invalidated by another's reserve.
+  struct CellIndex {
+    DevBuf off, meta, desc;
+  };
+  CellIndex w_win, w_sc, w_st;
   // Host-built plan tables the kernels read instead of walking the plan (the bucket selection pass's unit table): one
   // device buffer per distinct CONTENT, never rewritten in place — a captured graph keeps reading the table
   // of the plan it was captured with whatever other shapes the context serves in between.  At most 16 are kept (the oldest
@@ -505,10 +508,10 @@ PISLAM_EXPORT int pislam_ctx_destroy(pislam_ctx *c) {
   (void)hipStreamSynchronize(c->stream);
   for (DevBuf *b : {&c->s_img, &c->s_out, &c->s_pts, &c->s_desc, &c->s_misc, &c->s_rots, &c->s_tmp, &c->w_cnt,
                     &c->w_off, &c->w_total, &c->w_cellkp, &c->w_score, &c->w_stage, &c->w_stripcnt, &c->w_work, &c->w_prof, &c->w_ovf,
-                    &c->w_stagedesc, &c->w_ustage, &c->w_ucount, &c->w_sync, &c->w_chain, &c->w_win_off, &c->w_win_meta,
-                    &c->w_win_desc, &c->w_sc_off, &c->w_sc_meta, &c->w_sc_desc, &c->w_st_off, &c->w_st_meta,
-                    &c->w_st_desc})
+                    &c->w_stagedesc, &c->w_ustage, &c->w_ucount, &c->w_sync, &c->w_chain})
     b->release();
+  for (pislam_ctx::CellIndex *w : {&c->w_win, &c->w_sc, &c->w_st})
+    for (DevBuf *b : {&w->off, &w->meta, &w->desc}) b->release();
   for (auto *t : c->plan_tables) {
     t->dev.release();
     delete t;
@@ -2312,121 +2315,15 @@ PISLAM_EXPORT int pislam_match_hamming_batch(pislam_ctx *c, int words, const uin
                       idx, dist, dist2, q_stride);
 }
 
-// ---- spatially windowed matching ----------------------------------------------------
-
-namespace {
-
-// Checks the arguments every windowed call shares and lays out the per-pair cell grid (host only).  Cell side of
-// level l: max(1, radius[l]) * f with the smallest f >= 1 that keeps all levels' cells within pm::WIN_MAX_CELLS
-// (the LDS histogram of k_window_index).  Results do not depend on the side: the match applies the exact window test.
-int window_plan(pislam_ctx *c, int words, const pislam_level *lv, int nlevels, const int32_t *radius, size_t t_stride,
-                int batch, pm::WinPlan *P) {
-  if (words != 1 && words != 2 && words != 4 && words != 8) return fail(c, PISLAM_ERR_INVALID, "words must be 1, 2, 4 or 8");
-  if (nlevels < 1 || nlevels > pm::WIN_MAX_LEVELS) return fail(c, PISLAM_ERR_INVALID, "nlevels must be 1..16");
-  if (!lv || !radius) return fail(c, PISLAM_ERR_INVALID, "null levels / radius");
-  if (t_stride > 65535) return fail(c, PISLAM_ERR_INVALID, "at most 65535 train entries per pair");
-  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
-  for (int l = 0; l < nlevels; l++) {
-    const pislam_level &L = lv[l];
-    if (L.width < 1 || L.height < 1 || L.col0 < 0 || L.row0 < 0 || L.col0 + L.width > 4096 || L.row0 + L.height > 4096)
-      return fail(c, PISLAM_ERR_INVALID, "level rectangles must be non-empty and fit 12-bit coordinates");
-    if (radius[l] < 0 || radius[l] > 4095) return fail(c, PISLAM_ERR_INVALID, "radius must be 0..4095");
-    for (int k = 0; k < l; k++) {
-      const pislam_level &K = lv[k];
-      if (L.col0 < K.col0 + K.width && K.col0 < L.col0 + L.width && L.row0 < K.row0 + K.height && K.row0 < L.row0 + L.height)
-        return fail(c, PISLAM_ERR_INVALID, "level rectangles overlap");
-    }
-  }
-  auto side = [&](int l, long long f) { return (int)std::min<long long>(4096, std::max(1, radius[l]) * f); };
-  auto cells = [&](long long f) {
-    long long n = 0;
-    for (int l = 0; l < nlevels; l++) n += (long long)cdiv(lv[l].width, side(l, f)) * cdiv(lv[l].height, side(l, f));
-    return n;
-  };
-  // cells(f) ~ cells(1) / f^2: start just below that estimate; side 4096 leaves one cell per level, so this ends
-  long long f = std::max(1LL, (long long)std::sqrt((double)cells(1) / pm::WIN_MAX_CELLS));
-  while (cells(f) > pm::WIN_MAX_CELLS) f++;
-  *P = pm::WinPlan{};
-  int base = 0;
-  for (int l = 0; l < nlevels; l++) {
-    const int s = side(l, f), ncx = cdiv(lv[l].width, s);
-    P->lv[l] = pm::WinLevel{lv[l].col0, lv[l].row0, lv[l].width, lv[l].height, radius[l], s, ncx, base};
-    base += ncx * cdiv(lv[l].height, s);
-  }
-  P->nlevels = nlevels;
-  P->ncells = base;
-  return PISLAM_OK;
-}
-
-int window_workspace(pislam_ctx *c, const pm::WinPlan &P, int words, size_t t_stride, int batch) {
-  if (c->w_win_off.ensure(sizeof(uint32_t) * (size_t)(P.ncells + 1) * batch) != PISLAM_OK ||
-      c->w_win_meta.ensure(sizeof(uint2) * t_stride * batch) != PISLAM_OK ||
-      c->w_win_desc.ensure(sizeof(uint32_t) * words * t_stride * batch) != PISLAM_OK)
-    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(window matcher workspace)");
-  return PISLAM_OK;
-}
-
-}  // namespace
-
-PISLAM_EXPORT int pislam_match_window_reserve(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
-                                              const int32_t *radius, size_t t_stride, int batch) {
-  if (!c) return PISLAM_ERR_INVALID;
-  pm::WinPlan P;
-  PCHK(window_plan(c, words, levels, nlevels, radius, t_stride, batch, &P));
-  HIPCHK(c, hipSetDevice(c->device));
-  return window_workspace(c, P, words, t_stride, batch);
-}
-
-PISLAM_EXPORT int pislam_match_hamming_window_batch(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
-                                                    const int32_t *radius, const uint32_t *qkp, const uint32_t *qdesc,
-                                                    const uint32_t *qcounts, size_t q_stride, const uint32_t *tkp,
-                                                    const uint32_t *tdesc, const uint32_t *tcounts, size_t t_stride,
-                                                    int batch, int32_t *idx, uint32_t *dist, uint32_t *dist2) {
-  if (!c) return PISLAM_ERR_INVALID;
-  pm::WinPlan P;
-  PCHK(window_plan(c, words, levels, nlevels, radius, t_stride, batch, &P));
-  if (q_stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "q_stride too large");
-  if (batch == 0 || q_stride == 0) return PISLAM_OK;
-  for (const void *ptr : {(const void *)qkp, (const void *)qdesc, (const void *)qcounts, (const void *)tkp,
-                          (const void *)tdesc, (const void *)tcounts, (const void *)idx, (const void *)dist,
-                          (const void *)dist2}) {
-    if (!ptr) return fail(c, PISLAM_ERR_INVALID, "null pointer");
-    if (!is_device_ptr(ptr)) return fail(c, PISLAM_ERR_INVALID, "the window matcher takes device pointers only");
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  PCHK(window_workspace(c, P, words, t_stride, batch));
-  uint32_t *off = c->w_win_off.as<uint32_t>(), *edesc = c->w_win_desc.as<uint32_t>();
-  uint2 *meta = c->w_win_meta.as<uint2>();
-  hipLaunchKernelGGL(pm::k_window_index, dim3((unsigned)batch), dim3(pm::WIN_INDEX_THREADS), 0, c->stream, P, words, tkp,
-                     tdesc, tcounts, t_stride, off, meta, edesc);
-  PCHK(launch_ok(c, "k_window_index"));
-  // query tiles per pair in flight: the counts live on the device, so the grid is sized for the capacity and aims at
-  // ~16 workgroups per CU over the batch; a workgroup loops over further tiles of its pair
-  const int tiles = cdiv((int)std::min<size_t>(q_stride, 0x7fffffff - pm::WIN_QPW), pm::WIN_QPW);
-  const int per_pair = batch > 1 ? std::max(1, std::min(tiles, cdiv(16 * std::max(1, c->num_cus), batch))) : std::min(tiles, 65535);
-  const dim3 grid((unsigned)per_pair, (unsigned)batch);
-#define PISLAM_MATCH_WINDOW(W)                                                                                  \
-  hipLaunchKernelGGL(pm::k_match_window<W>, grid, dim3(pm::WIN_THREADS), 0, c->stream, P, qkp, qdesc, qcounts, q_stride, \
-                     t_stride, off, meta, edesc, idx, dist, dist2)
-  switch (words) {
-    case 1: PISLAM_MATCH_WINDOW(1); break;
-    case 2: PISLAM_MATCH_WINDOW(2); break;
-    case 4: PISLAM_MATCH_WINDOW(4); break;
-    default: PISLAM_MATCH_WINDOW(8); break;            // (window_plan accepted only 1, 2, 4, 8)
-  }
-#undef PISLAM_MATCH_WINDOW
-  return launch_ok(c, "k_match_window");
-}
-
-// ---- scale-aware guided window matching ---------------------------------------------------
+// ---- guided window matching: windowed, scale-aware ------------------------------------------
 
 namespace {
 
 // Checks the arguments every scaled-window call shares and lays out the per-pair cell grids (host only).  Level lt's
 // grid covers its mapped extent [0, ext_x] x [0, ext_y] in level-0 pixels with square cells of side m[lt] * f, where
 // m[lt] is the largest max(1, radius0[lq]) of the query levels lq that reach lt (|lq - lt| <= span) and f >= 1 is the
-// smallest factor that keeps all levels' cells within pm::WIN_MAX_CELLS.  Results do not depend on the side: the match
-// applies the exact window test.
+// smallest factor that keeps all levels' cells within pm::WIN_MAX_CELLS (the LDS histogram of k_scaled_index).  Results
+// do not depend on the side: the match applies the exact window test.
 int scaled_plan(pislam_ctx *c, int words, const pislam_level *lv, int nlevels, const int32_t *scale_q16,
                 const int32_t *radius0, int level_span, size_t t_stride, int batch, pm::ScaledPlan *P) {
   if (words != 1 && words != 2 && words != 4 && words != 8) return fail(c, PISLAM_ERR_INVALID, "words must be 1, 2, 4 or 8");
@@ -2481,15 +2378,100 @@ int scaled_plan(pislam_ctx *c, int words, const pislam_level *lv, int nlevels, c
   return PISLAM_OK;
 }
 
-int scaled_workspace(pislam_ctx *c, const pm::ScaledPlan &P, int words, size_t t_stride, int batch) {
-  if (c->w_sc_off.ensure(sizeof(uint32_t) * (size_t)(P.ncells + 1) * batch) != PISLAM_OK ||
-      c->w_sc_meta.ensure(sizeof(uint2) * t_stride * batch) != PISLAM_OK ||
-      c->w_sc_desc.ensure(sizeof(uint32_t) * words * t_stride * batch) != PISLAM_OK)
-    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(scaled window matcher workspace)");
+// The windowed matcher's plan: the scaled plan with unit scales (mapped = level-local coordinates), span 0 and
+// radius0 = radius, so level l's cells are max(1, radius[l]) * f level pixels over its rectangle.
+int window_plan(pislam_ctx *c, int words, const pislam_level *lv, int nlevels, const int32_t *radius, size_t t_stride,
+                int batch, pm::ScaledPlan *P) {
+  if (!lv || !radius) return fail(c, PISLAM_ERR_INVALID, "null levels / radius");
+  for (int l = 0; l < std::min(nlevels, pm::WIN_MAX_LEVELS); l++)
+    if (radius[l] < 0 || radius[l] > 4095) return fail(c, PISLAM_ERR_INVALID, "radius must be 0..4095");
+  int32_t unit[pm::WIN_MAX_LEVELS];
+  std::fill(unit, unit + pm::WIN_MAX_LEVELS, 65536);
+  return scaled_plan(c, words, lv, nlevels, unit, radius, 0, t_stride, batch, P);
+}
+
+int cell_workspace(pislam_ctx *c, pislam_ctx::CellIndex &w, const pm::ScaledPlan &P, int words, size_t t_stride,
+                   int batch, const char *what) {
+  if (w.off.ensure(sizeof(uint32_t) * (size_t)(P.ncells + 1) * batch) != PISLAM_OK ||
+      w.meta.ensure(sizeof(uint2) * t_stride * batch) != PISLAM_OK ||
+      w.desc.ensure(sizeof(uint32_t) * words * t_stride * batch) != PISLAM_OK)
+    return fail(c, PISLAM_ERR_NOMEM, what);
   return PISLAM_OK;
 }
 
+// The guided matchers take device pointers only: fails with `what` at the first host pointer.
+int device_ptrs(pislam_ctx *c, std::initializer_list<const void *> ptrs, const char *what) {
+  for (const void *ptr : ptrs) {
+    if (!ptr) return fail(c, PISLAM_ERR_INVALID, "null pointer");
+    if (!is_device_ptr(ptr)) return fail(c, PISLAM_ERR_INVALID, what);
+  }
+  return PISLAM_OK;
+}
+
+// Query tiles per pair in flight for `qpw` queries per workgroup pass: the counts live on the device, so the grid is sized
+// for the capacity and aims at ~16 workgroups per CU over the batch; a workgroup loops over further tiles of its pair.
+dim3 query_grid(const pislam_ctx *c, size_t q_stride, int qpw, int batch) {
+  const int tiles = cdiv((int)std::min<size_t>(q_stride, 0x7fffffff - qpw), qpw);
+  const int per_pair = batch > 1 ? std::max(1, std::min(tiles, cdiv(16 * std::max(1, c->num_cus), batch))) : std::min(tiles, 65535);
+  return dim3((unsigned)per_pair, (unsigned)batch);
+}
+
+// Index + match of the windowed and the scaled call (arguments checked, workspace w reserved).
+int launch_guided(pislam_ctx *c, const pislam_ctx::CellIndex &w, const pm::ScaledPlan &P, int words, const uint32_t *qkp,
+                  const uint32_t *qdesc, const uint32_t *qcounts, const int32_t *qpred, size_t q_stride,
+                  const uint32_t *tkp, const uint32_t *tdesc, const uint32_t *tcounts, size_t t_stride, int batch,
+                  int32_t *idx, uint32_t *dist, uint32_t *dist2) {
+  uint32_t *off = w.off.as<uint32_t>(), *edesc = w.desc.as<uint32_t>();
+  uint2 *meta = w.meta.as<uint2>();
+  hipLaunchKernelGGL(pm::k_scaled_index, dim3((unsigned)batch), dim3(pm::WIN_INDEX_THREADS), 0, c->stream, P, words, tkp,
+                     tdesc, tcounts, t_stride, off, meta, edesc);
+  PCHK(launch_ok(c, "k_scaled_index"));
+  const dim3 grid = query_grid(c, q_stride, pm::WIN_QPW, batch);
+#define PISLAM_MATCH_SCALED(W)                                                                                           \
+  if (P.span == 0)                                                                                                       \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pm::k_match_scaled<W, true>), grid, dim3(pm::WIN_THREADS), 0, c->stream, P, qkp,  \
+                       qdesc, qcounts, qpred, q_stride, t_stride, off, meta, edesc, idx, dist, dist2);                   \
+  else                                                                                                                   \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pm::k_match_scaled<W, false>), grid, dim3(pm::WIN_THREADS), 0, c->stream, P, qkp, \
+                       qdesc, qcounts, qpred, q_stride, t_stride, off, meta, edesc, idx, dist, dist2)
+  switch (words) {
+    case 1: PISLAM_MATCH_SCALED(1); break;
+    case 2: PISLAM_MATCH_SCALED(2); break;
+    case 4: PISLAM_MATCH_SCALED(4); break;
+    default: PISLAM_MATCH_SCALED(8); break;            // (scaled_plan accepted only 1, 2, 4, 8)
+  }
+#undef PISLAM_MATCH_SCALED
+  return launch_ok(c, "k_match_scaled");
+}
+
 }  // namespace
+
+PISLAM_EXPORT int pislam_match_window_reserve(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
+                                              const int32_t *radius, size_t t_stride, int batch) {
+  if (!c) return PISLAM_ERR_INVALID;
+  pm::ScaledPlan P;
+  PCHK(window_plan(c, words, levels, nlevels, radius, t_stride, batch, &P));
+  HIPCHK(c, hipSetDevice(c->device));
+  return cell_workspace(c, c->w_win, P, words, t_stride, batch, "hipMalloc(window matcher workspace)");
+}
+
+PISLAM_EXPORT int pislam_match_hamming_window_batch(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
+                                                    const int32_t *radius, const uint32_t *qkp, const uint32_t *qdesc,
+                                                    const uint32_t *qcounts, size_t q_stride, const uint32_t *tkp,
+                                                    const uint32_t *tdesc, const uint32_t *tcounts, size_t t_stride,
+                                                    int batch, int32_t *idx, uint32_t *dist, uint32_t *dist2) {
+  if (!c) return PISLAM_ERR_INVALID;
+  pm::ScaledPlan P;
+  PCHK(window_plan(c, words, levels, nlevels, radius, t_stride, batch, &P));
+  if (q_stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "q_stride too large");
+  if (batch == 0 || q_stride == 0) return PISLAM_OK;
+  PCHK(device_ptrs(c, {qkp, qdesc, qcounts, tkp, tdesc, tcounts, idx, dist, dist2},
+                   "the window matcher takes device pointers only"));
+  HIPCHK(c, hipSetDevice(c->device));
+  PCHK(cell_workspace(c, c->w_win, P, words, t_stride, batch, "hipMalloc(window matcher workspace)"));
+  return launch_guided(c, c->w_win, P, words, qkp, qdesc, qcounts, nullptr, q_stride, tkp, tdesc, tcounts, t_stride, batch,
+                       idx, dist, dist2);
+}
 
 PISLAM_EXPORT int pislam_match_scaled_window_reserve(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
                                                      const int32_t *scale_q16, const int32_t *radius0, int level_span,
@@ -2498,7 +2480,7 @@ PISLAM_EXPORT int pislam_match_scaled_window_reserve(pislam_ctx *c, int words, c
   pm::ScaledPlan P;
   PCHK(scaled_plan(c, words, levels, nlevels, scale_q16, radius0, level_span, t_stride, batch, &P));
   HIPCHK(c, hipSetDevice(c->device));
-  return scaled_workspace(c, P, words, t_stride, batch);
+  return cell_workspace(c, c->w_sc, P, words, t_stride, batch, "hipMalloc(scaled window matcher workspace)");
 }
 
 PISLAM_EXPORT int pislam_match_hamming_scaled_window_batch(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
@@ -2513,34 +2495,12 @@ PISLAM_EXPORT int pislam_match_hamming_scaled_window_batch(pislam_ctx *c, int wo
   if (q_stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "q_stride too large");
   if (qpred && !is_device_ptr(qpred)) return fail(c, PISLAM_ERR_INVALID, "qpred must be a device pointer or null");
   if (batch == 0 || q_stride == 0) return PISLAM_OK;
-  for (const void *ptr : {(const void *)qkp, (const void *)qdesc, (const void *)qcounts, (const void *)tkp,
-                          (const void *)tdesc, (const void *)tcounts, (const void *)idx, (const void *)dist,
-                          (const void *)dist2}) {
-    if (!ptr) return fail(c, PISLAM_ERR_INVALID, "null pointer");
-    if (!is_device_ptr(ptr)) return fail(c, PISLAM_ERR_INVALID, "the scaled window matcher takes device pointers only");
-  }
+  PCHK(device_ptrs(c, {qkp, qdesc, qcounts, tkp, tdesc, tcounts, idx, dist, dist2},
+                   "the scaled window matcher takes device pointers only"));
   HIPCHK(c, hipSetDevice(c->device));
-  PCHK(scaled_workspace(c, P, words, t_stride, batch));
-  uint32_t *off = c->w_sc_off.as<uint32_t>(), *edesc = c->w_sc_desc.as<uint32_t>();
-  uint2 *meta = c->w_sc_meta.as<uint2>();
-  hipLaunchKernelGGL(pm::k_scaled_index, dim3((unsigned)batch), dim3(pm::WIN_INDEX_THREADS), 0, c->stream, P, words, tkp,
-                     tdesc, tcounts, t_stride, off, meta, edesc);
-  PCHK(launch_ok(c, "k_scaled_index"));
-  // grid as pislam_match_hamming_window_batch: sized for the capacity, ~16 workgroups per CU over the batch
-  const int tiles = cdiv((int)std::min<size_t>(q_stride, 0x7fffffff - pm::WIN_QPW), pm::WIN_QPW);
-  const int per_pair = batch > 1 ? std::max(1, std::min(tiles, cdiv(16 * std::max(1, c->num_cus), batch))) : std::min(tiles, 65535);
-  const dim3 grid((unsigned)per_pair, (unsigned)batch);
-#define PISLAM_MATCH_SCALED(W)                                                                                           \
-  hipLaunchKernelGGL(pm::k_match_scaled<W>, grid, dim3(pm::WIN_THREADS), 0, c->stream, P, qkp, qdesc, qcounts, qpred,     \
-                     q_stride, t_stride, off, meta, edesc, idx, dist, dist2)
-  switch (words) {
-    case 1: PISLAM_MATCH_SCALED(1); break;
-    case 2: PISLAM_MATCH_SCALED(2); break;
-    case 4: PISLAM_MATCH_SCALED(4); break;
-    default: PISLAM_MATCH_SCALED(8); break;            // (scaled_plan accepted only 1, 2, 4, 8)
-  }
-#undef PISLAM_MATCH_SCALED
-  return launch_ok(c, "k_match_scaled");
+  PCHK(cell_workspace(c, c->w_sc, P, words, t_stride, batch, "hipMalloc(scaled window matcher workspace)"));
+  return launch_guided(c, c->w_sc, P, words, qkp, qdesc, qcounts, qpred, q_stride, tkp, tdesc, tcounts, t_stride, batch,
+                       idx, dist, dist2);
 }
 
 // ---- rectified stereo matching ------------------------------------------------------------
@@ -2565,14 +2525,6 @@ int stereo_plan(pislam_ctx *c, int words, const pislam_level *lv, int nlevels, c
   return PISLAM_OK;
 }
 
-int stereo_workspace(pislam_ctx *c, const pm::ScaledPlan &P, int words, size_t r_stride, int batch) {
-  if (c->w_st_off.ensure(sizeof(uint32_t) * (size_t)(P.ncells + 1) * batch) != PISLAM_OK ||
-      c->w_st_meta.ensure(sizeof(uint2) * r_stride * batch) != PISLAM_OK ||
-      c->w_st_desc.ensure(sizeof(uint32_t) * words * r_stride * batch) != PISLAM_OK)
-    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(stereo matcher workspace)");
-  return PISLAM_OK;
-}
-
 }  // namespace
 
 PISLAM_EXPORT int pislam_match_stereo_reserve(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
@@ -2582,7 +2534,7 @@ PISLAM_EXPORT int pislam_match_stereo_reserve(pislam_ctx *c, int words, const pi
   pm::ScaledPlan P;
   PCHK(stereo_plan(c, words, levels, nlevels, scale_q16, row_radius0, p, r_stride, batch, &P));
   HIPCHK(c, hipSetDevice(c->device));
-  return stereo_workspace(c, P, words, r_stride, batch);
+  return cell_workspace(c, c->w_st, P, words, r_stride, batch, "hipMalloc(stereo matcher workspace)");
 }
 
 PISLAM_EXPORT int pislam_match_stereo_batch(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
@@ -2603,27 +2555,20 @@ PISLAM_EXPORT int pislam_match_stereo_batch(pislam_ctx *c, int words, const pisl
   if (l_stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "l_stride too large");
   if (nstereo && !is_device_ptr(nstereo)) return fail(c, PISLAM_ERR_INVALID, "nstereo must be a device pointer or null");
   if (batch == 0 || (l_stride == 0 && !nstereo)) return PISLAM_OK;
-  for (const void *ptr : {(const void *)left_pyr, (const void *)right_pyr, (const void *)lkp, (const void *)ldesc,
-                          (const void *)lcounts, (const void *)rkp, (const void *)rdesc, (const void *)rcounts,
-                          (const void *)idx, (const void *)dist, (const void *)disp_q8, (const void *)sad}) {
-    if (!ptr) return fail(c, PISLAM_ERR_INVALID, "null pointer");
-    if (!is_device_ptr(ptr)) return fail(c, PISLAM_ERR_INVALID, "the stereo matcher takes device pointers only");
-  }
+  PCHK(device_ptrs(c, {left_pyr, right_pyr, lkp, ldesc, lcounts, rkp, rdesc, rcounts, idx, dist, disp_q8, sad},
+                   "the stereo matcher takes device pointers only"));
   HIPCHK(c, hipSetDevice(c->device));
-  PCHK(stereo_workspace(c, P, words, r_stride, batch));
-  uint32_t *off = c->w_st_off.as<uint32_t>(), *edesc = c->w_st_desc.as<uint32_t>();
-  uint2 *meta = c->w_st_meta.as<uint2>();
+  PCHK(cell_workspace(c, c->w_st, P, words, r_stride, batch, "hipMalloc(stereo matcher workspace)"));
+  uint32_t *off = c->w_st.off.as<uint32_t>(), *edesc = c->w_st.desc.as<uint32_t>();
+  uint2 *meta = c->w_st.meta.as<uint2>();
   if (l_stride > 0) {
     hipLaunchKernelGGL(pm::k_scaled_index, dim3((unsigned)batch), dim3(pm::WIN_INDEX_THREADS), 0, c->stream, P, words,
                        rkp, rdesc, rcounts, r_stride, off, meta, edesc);
     PCHK(launch_ok(c, "k_scaled_index"));
-    // grids as pislam_match_hamming_window_batch: sized for the capacity, ~16 workgroups per CU over the batch
-    const int tiles = cdiv((int)std::min<size_t>(l_stride, 0x7fffffff - pm::WIN_QPW), pm::WIN_QPW);
-    const int per_pair = batch > 1 ? std::max(1, std::min(tiles, cdiv(16 * std::max(1, c->num_cus), batch))) : std::min(tiles, 65535);
+    const dim3 grid = query_grid(c, l_stride, pm::WIN_QPW, batch);
 #define PISLAM_MATCH_STEREO(W)                                                                                           \
-    hipLaunchKernelGGL(pm::k_match_stereo<W>, dim3((unsigned)per_pair, (unsigned)batch), dim3(pm::WIN_THREADS), 0,        \
-                       c->stream, P, p->min_disp, p->max_disp, lkp, ldesc, lcounts, l_stride, r_stride, off, meta, edesc, \
-                       idx, dist)
+    hipLaunchKernelGGL(pm::k_match_stereo<W>, grid, dim3(pm::WIN_THREADS), 0, c->stream, P, p->min_disp, p->max_disp,    \
+                       lkp, ldesc, lcounts, l_stride, r_stride, off, meta, edesc, idx, dist)
     switch (words) {
       case 1: PISLAM_MATCH_STEREO(1); break;
       case 2: PISLAM_MATCH_STEREO(2); break;
@@ -2632,13 +2577,11 @@ PISLAM_EXPORT int pislam_match_stereo_batch(pislam_ctx *c, int words, const pisl
     }
 #undef PISLAM_MATCH_STEREO
     PCHK(launch_ok(c, "k_match_stereo"));
-    const int rtiles = cdiv((int)std::min<size_t>(l_stride, 0x7fffffff - pm::ST_QPW), pm::ST_QPW);
-    const int r_per_pair = batch > 1 ? std::max(1, std::min(rtiles, cdiv(16 * std::max(1, c->num_cus), batch)))
-                                     : std::min(rtiles, 65535);
+    const dim3 rgrid = query_grid(c, l_stride, pm::ST_QPW, batch);
 #define PISLAM_STEREO_REFINE(W)                                                                                          \
-    hipLaunchKernelGGL(pm::k_stereo_refine<W>, dim3((unsigned)r_per_pair, (unsigned)batch), dim3(pm::ST_THREADS), 0,      \
-                       c->stream, P, (uint32_t)p->max_hamming, p->search_radius, p->min_disp, p->max_disp, left_pyr,   \
-                       right_pyr, vstep, pyramid_stride, lkp, lcounts, l_stride, rkp, r_stride, idx, dist, disp_q8, sad)
+    hipLaunchKernelGGL(pm::k_stereo_refine<W>, rgrid, dim3(pm::ST_THREADS), 0, c->stream, P, (uint32_t)p->max_hamming,    \
+                       p->search_radius, p->min_disp, p->max_disp, left_pyr, right_pyr, vstep, pyramid_stride, lkp,      \
+                       lcounts, l_stride, rkp, r_stride, idx, dist, disp_q8, sad)
     switch (p->sad_radius) {
       case 1: PISLAM_STEREO_REFINE(1); break;
       case 2: PISLAM_STEREO_REFINE(2); break;

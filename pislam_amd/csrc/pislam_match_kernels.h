@@ -236,224 +236,32 @@ __global__ __launch_bounds__(64 * MF_WAVES) void k_match_mfma(const uint32_t *__
 }
 
 // ---------------------------------------------------------------------------
-// Spatially windowed matching (include/pislam_hip.h): query i of pair b sees only the train
-// entries on its own pyramid level whose position lies within radius[l] of its own (Chebyshev, level pixels), with
-// the outputs of k_match restricted to those candidates.  Two launches on the context stream:
-//   k_window_index   one workgroup per pair: every train position is decoded to its level and placed on that level's
-//                    grid of square cells (side chosen by the host from radius[l]); a counting sort in LDS (histogram
-//                    with LDS atomics, exclusive scan, scatter) writes the pair's cell offsets and a cell-sorted copy
-//                    of each entry (packed position, original index, descriptor dwords) to the workspace.
-//   k_match_window   WIN_LPQ lanes per query (the query descriptor in registers): the cell rows overlapping the window
-//                    are contiguous runs of entries; the lanes of a query take every WIN_LPQ-th entry of each run,
-//                    apply the exact window test, XOR-popcount and keep (best, second) on dist << 16 | index like
-//                    k_match, then merge through two xor-shuffles.
+// Guided window matching (include/pislam_hip.h): every position is mapped to level-0 coordinates
+// through its level's Q16 scale, X = ((x - col0) * s + 32768) >> 16 (likewise Y); query i of level lq sees the train
+// entries of the levels within `span` of lq whose mapped position lies within radius0[lq] of the window centre (the
+// query's own mapped position, or a per-query prediction), with the outputs of k_match restricted to those candidates.
+// The windowed matcher is the case of unit scales (65536: X = x - col0) and span 0.  Two launches on the context stream:
+//   k_scaled_index   one workgroup per pair: each train entry goes to a cell of ITS level's grid of square cells in
+//                    level-0 pixels (side chosen by the host), so a cell run holds one level and the match needs no level
+//                    test; a counting sort in LDS (histogram with LDS atomics, exclusive scan, scatter) writes the pair's
+//                    cell offsets and a cell-sorted copy of each entry (X << 16 | Y, original index, descriptor dwords).
+//   k_match_scaled   WIN_LPQ lanes per query (the query descriptor in registers): the cell rows overlapping the window
+//                    clipped to a level's mapped extent are contiguous runs of entries; the lanes of a query take every
+//                    WIN_LPQ-th entry of each run, apply the exact window test, XOR-popcount and keep (best, second) on
+//                    dist << 16 | index like k_match, then merge through two xor-shuffles.  At span 0 (ONE_LEVEL) a lane
+//                    walks its own level with that level's fields picked per lane; otherwise a wave-uniform loop over the
+//                    plan's levels (kernel-argument loads, no per-lane indexing of the plan) walks the levels within span.
 // Positions outside every level are never indexed and find no candidates.  Scatter order inside a cell varies between
 // runs; the results do not: the packed key is unique per train index, so the minimum does not depend on visit order.
 // ---------------------------------------------------------------------------
 constexpr int WIN_MAX_LEVELS = 16;
-constexpr int WIN_MAX_CELLS = 16384;   // LDS histogram of k_window_index (64 KiB); the host coarsens cells to fit
+constexpr int WIN_MAX_CELLS = 16384;   // LDS histogram of k_scaled_index (64 KiB); the host coarsens cells to fit
 constexpr int WIN_INDEX_THREADS = 1024;
-constexpr int WIN_THREADS = 256;       // k_match_window workgroup
+constexpr int WIN_THREADS = 256;       // k_match_scaled / k_match_stereo workgroup
 constexpr int WIN_LPQ = 4;             // lanes per query
 constexpr int WIN_QPW = WIN_THREADS / WIN_LPQ;   // queries per workgroup pass
 
-struct WinLevel {
-  int32_t col0, row0, width, height;   // rectangle inside the stacked pyramid
-  int32_t radius, side;                // window radius, cell side (level pixels)
-  int32_t ncx, base;                   // cells per cell row, first cell of the level in the pair's cell table
-};
-struct WinPlan {                       // passed by value (kernel arguments: a captured graph keeps its own copy)
-  WinLevel lv[WIN_MAX_LEVELS];
-  int32_t nlevels, ncells;             // ncells: cells of all levels (<= WIN_MAX_CELLS)
-};
-
-// A count as the window matcher reads it: PISLAM_COUNT_INVALID (a pyramid the front end did not produce) is 0.
-__device__ __forceinline__ uint32_t win_count(uint32_t c, size_t stride) {
-  return c == 0xffffffffu ? 0u : (uint32_t)min((size_t)c, stride);
-}
-
-// The level whose rectangle holds (x, y): the loop is wave-uniform (kernel-argument loads), the fields of the level
-// found are picked by selects, so no per-lane indexing of the plan (which would go through scratch).
-struct WinHit {
-  int32_t col0, row0, width, height, radius, side, ncx, base;
-  bool found;
-};
-__device__ __forceinline__ WinHit win_level(const WinPlan &P, int32_t x, int32_t y) {
-  WinHit h{0, 0, 0, 0, 0, 1, 0, 0, false};
-  for (int l = 0; l < P.nlevels; l++) {
-    const WinLevel L = P.lv[l];
-    if ((uint32_t)(x - L.col0) < (uint32_t)L.width && (uint32_t)(y - L.row0) < (uint32_t)L.height) {
-      h = WinHit{L.col0, L.row0, L.width, L.height, L.radius, L.side, L.ncx, L.base, true};
-    }
-  }
-  return h;
-}
-
-// Cell of a packed position (x << 12 | y; score bits ignored), -1 outside every level.
-__device__ __forceinline__ int32_t win_cell(const WinPlan &P, uint32_t k) {
-  const int32_t x = (int32_t)((k >> 12) & 0xfffu), y = (int32_t)(k & 0xfffu);
-  const WinHit h = win_level(P, x, y);
-  if (!h.found) return -1;
-  return h.base + ((y - h.row0) / h.side) * h.ncx + (x - h.col0) / h.side;
-}
-
-// grid (batch), WIN_INDEX_THREADS threads.  t_stride in entries; cell_off [batch][ncells + 1],
-// ent_meta [batch][t_stride] = (x << 12 | y, original index), ent_desc [batch][t_stride][words].
-__global__ __launch_bounds__(WIN_INDEX_THREADS) void k_window_index(WinPlan P, int words, const uint32_t *__restrict__ tkp,
-                                                                    const uint32_t *__restrict__ tdesc,
-                                                                    const uint32_t *__restrict__ tcount, size_t t_stride,
-                                                                    uint32_t *__restrict__ cell_off, uint2 *__restrict__ ent_meta,
-                                                                    uint32_t *__restrict__ ent_desc) {
-  __shared__ uint32_t hist[WIN_MAX_CELLS];
-  __shared__ uint32_t wave_sum[WIN_INDEX_THREADS / 64];
-  const int b = blockIdx.x;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const uint32_t nt = win_count(tcount[b], t_stride);
-  const int32_t nc = P.ncells;
-  const uint32_t *kp = tkp + (size_t)b * t_stride;
-  uint32_t *off = cell_off + (size_t)b * (nc + 1);
-  for (int32_t c = (int32_t)tid; c < nc; c += WIN_INDEX_THREADS) hist[c] = 0;
-  __syncthreads();
-  for (uint32_t j = tid; j < nt; j += WIN_INDEX_THREADS) {
-    const int32_t c = win_cell(P, kp[j]);
-    if (c >= 0) atomicAdd(&hist[c], 1u);
-  }
-  __syncthreads();
-  // exclusive scan: every thread sums a contiguous chunk, the chunk sums are scanned across the workgroup
-  const int32_t chunk = (nc + WIN_INDEX_THREADS - 1) / WIN_INDEX_THREADS;
-  const int32_t c0 = min((int32_t)tid * chunk, nc), c1 = min(c0 + chunk, nc);
-  uint32_t s = 0;
-  for (int32_t c = c0; c < c1; c++) s += hist[c];
-  uint32_t incl = s;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t v = __shfl_up(incl, d, 64);
-    if ((int)lane >= d) incl += v;
-  }
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  uint32_t run = incl - s;
-  for (uint32_t w = 0; w < wave; w++) run += wave_sum[w];
-  for (int32_t c = c0; c < c1; c++) {
-    const uint32_t v = hist[c];
-    hist[c] = run;
-    run += v;
-  }
-  if (tid == WIN_INDEX_THREADS - 1) off[nc] = run;     // entries indexed (the last chunk ends at the total)
-  __syncthreads();
-  for (int32_t c = (int32_t)tid; c < nc; c += WIN_INDEX_THREADS) off[c] = hist[c];
-  __syncthreads();
-  // scatter: hist[c] is the next free slot of cell c
-  const uint32_t *dp = tdesc + (size_t)b * t_stride * words;
-  uint2 *mp = ent_meta + (size_t)b * t_stride;
-  uint32_t *ep = ent_desc + (size_t)b * t_stride * words;
-  for (uint32_t j = tid; j < nt; j += WIN_INDEX_THREADS) {
-    const uint32_t k = kp[j];
-    const int32_t c = win_cell(P, k);
-    if (c < 0) continue;
-    const uint32_t slot = atomicAdd(&hist[c], 1u);
-    mp[slot] = make_uint2(k & 0xffffffu, j);
-    for (int w = 0; w < words; w++) ep[(size_t)slot * words + w] = dp[(size_t)j * words + w];
-  }
-}
-
-template <int WORDS>
-__device__ __forceinline__ uint32_t win_popc(const uint32_t (&qd)[WORDS], const uint32_t *__restrict__ e) {
-  uint32_t t[WORDS];
-  if constexpr (WORDS >= 4) {                           // entries are WORDS * 4 bytes apart from a 256-byte aligned base
-#pragma unroll
-    for (int k = 0; k < WORDS; k += 4) {
-      const uint4 v = *(const uint4 *)(e + k);
-      t[k] = v.x, t[k + 1] = v.y, t[k + 2] = v.z, t[k + 3] = v.w;
-    }
-  } else if constexpr (WORDS == 2) {
-    const uint2 v = *(const uint2 *)e;
-    t[0] = v.x, t[1] = v.y;
-  } else {
-    t[0] = e[0];
-  }
-  uint32_t d = 0;
-#pragma unroll
-  for (int k = 0; k < WORDS; k++) d += (uint32_t)__popc(qd[k] ^ t[k]);
-  return d;
-}
-
-// grid (query tiles, batch), WIN_THREADS threads; q_stride / t_stride in entries; outputs [batch][q_stride].
-template <int WORDS>
-__global__ __launch_bounds__(WIN_THREADS) void k_match_window(WinPlan P, const uint32_t *__restrict__ qkp,
-                                                              const uint32_t *__restrict__ qdesc,
-                                                              const uint32_t *__restrict__ qcount, size_t q_stride,
-                                                              size_t t_stride, const uint32_t *__restrict__ cell_off,
-                                                              const uint2 *__restrict__ ent_meta,
-                                                              const uint32_t *__restrict__ ent_desc,
-                                                              int32_t *__restrict__ idx, uint32_t *__restrict__ dist,
-                                                              uint32_t *__restrict__ dist2) {
-  const int b = blockIdx.y;
-  const uint32_t nq = win_count(qcount[b], q_stride);
-  const uint32_t sub = threadIdx.x % WIN_LPQ;
-  const uint32_t *off_b = cell_off + (size_t)b * (P.ncells + 1);
-  const uint2 *mp = ent_meta + (size_t)b * t_stride;
-  const uint32_t *ep = ent_desc + (size_t)b * t_stride * WORDS;
-  for (uint32_t q0 = blockIdx.x * (uint32_t)WIN_QPW; q0 < nq; q0 += gridDim.x * (uint32_t)WIN_QPW) {
-    const uint32_t i = q0 + threadIdx.x / WIN_LPQ;
-    uint32_t best = 0xffffffffu, second = 0xffffffffu;  // (keys are at most 256 << 16 | 65534: never the sentinel)
-    if (i < nq) {
-      const uint32_t k = qkp[(size_t)b * q_stride + i];
-      const int32_t x = (int32_t)((k >> 12) & 0xfffu), y = (int32_t)(k & 0xfffu);
-      const WinHit h = win_level(P, x, y);
-      if (h.found) {
-        uint32_t qd[WORDS];
-        const uint32_t *qp = qdesc + ((size_t)b * q_stride + i) * WORDS;
-#pragma unroll
-        for (int w = 0; w < WORDS; w++) qd[w] = qp[w];
-        const int32_t r = h.radius;
-        // the window clipped to the level: its train entries all lie inside the level's rectangle
-        const int32_t cx0 = (max(x - r, h.col0) - h.col0) / h.side, cx1 = (min(x + r, h.col0 + h.width - 1) - h.col0) / h.side;
-        const int32_t cy0 = (max(y - r, h.row0) - h.row0) / h.side, cy1 = (min(y + r, h.row0 + h.height - 1) - h.row0) / h.side;
-        const uint32_t *off = off_b + h.base;
-        for (int32_t cy = cy0; cy <= cy1; cy++) {
-          const uint32_t e1 = off[cy * h.ncx + cx1 + 1];
-          for (uint32_t e = off[cy * h.ncx + cx0] + sub; e < e1; e += WIN_LPQ) {
-            const uint2 m = mp[e];
-            const int32_t tx = (int32_t)(m.x >> 12), ty = (int32_t)(m.x & 0xfffu);
-            if (abs(tx - x) <= r && abs(ty - y) <= r) {
-              const uint32_t key = (win_popc<WORDS>(qd, ep + (size_t)e * WORDS) << 16) | m.y;
-              second = min(second, max(best, key));
-              best = min(best, key);
-            }
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int s = 1; s < WIN_LPQ; s <<= 1) {              // merge the lanes of a query: they saw disjoint entries
-      const uint32_t ob = __shfl_xor(best, s, 64), os = __shfl_xor(second, s, 64);
-      second = min(min(second, os), max(best, ob));
-      best = min(best, ob);
-    }
-    if (sub == 0 && i < nq) {
-      const size_t o = (size_t)b * q_stride + i;
-      idx[o] = best == 0xffffffffu ? -1 : (int32_t)(best & 0xffffu);
-      dist[o] = best == 0xffffffffu ? 0xffffffffu : best >> 16;
-      dist2[o] = second == 0xffffffffu ? 0xffffffffu : second >> 16;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Scale-aware guided window matching (include/pislam_hip.h): every position is mapped to level-0
-// coordinates through its level's Q16 scale, X = ((x - col0) * s + 32768) >> 16 (likewise Y); query i of level lq sees
-// the train entries of the levels within `span` of lq whose mapped position lies within radius0[lq] of the window
-// centre (the query's own mapped position, or a per-query prediction).  Same two-launch structure as the windowed
-// matcher, with its own plan and workspace:
-//   k_scaled_index   one workgroup per pair: each train entry goes to a cell of ITS level's grid of square cells in
-//                    level-0 pixels (so a cell run holds one level and the match needs no level test), by the same
-//                    counting sort as k_window_index; an entry keeps X << 16 | Y, its original index and its descriptor.
-//   k_match_scaled   WIN_LPQ lanes per query: a wave-uniform loop over the plan's levels (kernel-argument loads, no
-//                    per-lane indexing of the plan); a lane takes part in the levels within span of its own and walks
-//                    the cell rows of that level's grid overlapping the window clipped to the level's mapped extent.
-// ---------------------------------------------------------------------------
-struct ScaledLevel {
+struct alignas(16) ScaledLevel {      // (16-byte aligned: the level search fetches the rectangle with one scalar load)
   int32_t col0, row0, width, height;   // rectangle inside the stacked pyramid
   int32_t scale;                       // level-0 pixels per level pixel, Q16 (1 .. 2^20)
   int32_t ext_x, ext_y;                // largest mapped X / Y of the level (<= 65535)
@@ -466,21 +274,28 @@ struct ScaledPlan {                    // passed by value (kernel arguments: a c
   int32_t nlevels, ncells, span;       // ncells: cells of all levels (<= WIN_MAX_CELLS); span: |lq - lt| <= span
 };
 
+// A count as the window matchers read it: PISLAM_COUNT_INVALID (a pyramid the front end did not produce) is 0.
+__device__ __forceinline__ uint32_t win_count(uint32_t c, size_t stride) {
+  return c == 0xffffffffu ? 0u : (uint32_t)min((size_t)c, stride);
+}
+
 // Level-0 coordinate of a level-local coordinate u (unsigned 32-bit: u <= 4095 and scale <= 2^20 cannot wrap).
 __device__ __forceinline__ int32_t sc_map(int32_t u, int32_t scale) {
   return (int32_t)(((uint32_t)u * (uint32_t)scale + 32768u) >> 16);
 }
 
-// The level whose rectangle holds (x, y), its fields picked by selects in a wave-uniform loop (as win_level).
+// The level whose rectangle holds (x, y): the loop is wave-uniform (kernel-argument loads), the fields of the level
+// found are picked by selects, so no per-lane indexing of the plan (which would go through scratch).  The two range
+// tests are combined with `&`: a short-circuit `&&` splits them into two branches with a scalar-load wait each.
 struct ScaledHit {
-  int32_t level, col0, row0, scale, radius, side, ncx, base;   // level -1: in no level
+  int32_t level, col0, row0, scale, ext_x, ext_y, radius, side, ncx, base;   // level -1: in no level
 };
 __device__ __forceinline__ ScaledHit sc_level(const ScaledPlan &P, int32_t x, int32_t y) {
-  ScaledHit h{-1, 0, 0, 0, 0, 1, 0, 0};
+  ScaledHit h{-1, 0, 0, 0, 0, 0, 0, 1, 0, 0};
   for (int l = 0; l < P.nlevels; l++) {
     const ScaledLevel L = P.lv[l];
-    if ((uint32_t)(x - L.col0) < (uint32_t)L.width && (uint32_t)(y - L.row0) < (uint32_t)L.height) {
-      h = ScaledHit{l, L.col0, L.row0, L.scale, L.radius, L.side, L.ncx, L.base};
+    if (((uint32_t)(x - L.col0) < (uint32_t)L.width) & ((uint32_t)(y - L.row0) < (uint32_t)L.height)) {
+      h = ScaledHit{l, L.col0, L.row0, L.scale, L.ext_x, L.ext_y, L.radius, L.side, L.ncx, L.base};
     }
   }
   return h;
@@ -558,11 +373,50 @@ __global__ __launch_bounds__(WIN_INDEX_THREADS) void k_scaled_index(ScaledPlan P
   }
 }
 
+template <int WORDS>
+__device__ __forceinline__ uint32_t win_popc(const uint32_t (&qd)[WORDS], const uint32_t *__restrict__ e) {
+  uint32_t t[WORDS];
+  if constexpr (WORDS >= 4) {                           // entries are WORDS * 4 bytes apart from a 256-byte aligned base
+#pragma unroll
+    for (int k = 0; k < WORDS; k += 4) {
+      const uint4 v = *(const uint4 *)(e + k);
+      t[k] = v.x, t[k + 1] = v.y, t[k + 2] = v.z, t[k + 3] = v.w;
+    }
+  } else if constexpr (WORDS == 2) {
+    const uint2 v = *(const uint2 *)e;
+    t[0] = v.x, t[1] = v.y;
+  } else {
+    t[0] = e[0];
+  }
+  uint32_t d = 0;
+#pragma unroll
+  for (int k = 0; k < WORDS; k++) d += (uint32_t)__popc(qd[k] ^ t[k]);
+  return d;
+}
+
+// Clip-and-walk over one level's grid (L: a ScaledLevel, or a ScaledHit's fields of it): the window [x0, x1] x [y0, y1]
+// clipped to the level's mapped extent [0, ext_x] x [0, ext_y] (its train entries all lie inside it), the cell rows
+// that overlap it, and in each row's run of entries every WIN_LPQ-th one from lane `sub` on: visit(e, ent_meta[e]).
+template <class Level, class Visit>
+__device__ __forceinline__ void win_walk(const Level &L, const uint32_t *__restrict__ off_b,
+                                         const uint2 *__restrict__ mp, uint32_t sub, int32_t x0, int32_t x1, int32_t y0,
+                                         int32_t y1, Visit &&visit) {
+  x0 = max(x0, 0), x1 = min(x1, L.ext_x);
+  y0 = max(y0, 0), y1 = min(y1, L.ext_y);
+  if (x0 > x1 || y0 > y1) return;
+  const int32_t cx0 = x0 / L.side, cx1 = x1 / L.side, cy0 = y0 / L.side, cy1 = y1 / L.side;
+  const uint32_t *off = off_b + L.base;
+  for (int32_t cy = cy0; cy <= cy1; cy++) {
+    const uint32_t e1 = off[cy * L.ncx + cx1 + 1];
+    for (uint32_t e = off[cy * L.ncx + cx0] + sub; e < e1; e += WIN_LPQ) visit(e, mp[e]);
+  }
+}
+
 constexpr int32_t SCALED_PRED_LIMIT = 1 << 20;   // predicted centres are clamped to [-2^20, 2^20]
 
 // grid (query tiles, batch), WIN_THREADS threads; q_stride / t_stride in entries; qpred [batch][q_stride][2] or null;
-// outputs [batch][q_stride].
-template <int WORDS>
+// outputs [batch][q_stride].  ONE_LEVEL: the plan's span is 0.
+template <int WORDS, bool ONE_LEVEL>
 __global__ __launch_bounds__(WIN_THREADS) void k_match_scaled(ScaledPlan P, const uint32_t *__restrict__ qkp,
                                                               const uint32_t *__restrict__ qdesc,
                                                               const uint32_t *__restrict__ qcount,
@@ -582,17 +436,16 @@ __global__ __launch_bounds__(WIN_THREADS) void k_match_scaled(ScaledPlan P, cons
     const uint32_t i = q0 + threadIdx.x / WIN_LPQ;
     const size_t o = (size_t)b * q_stride + i;
     uint32_t best = 0xffffffffu, second = 0xffffffffu;  // (keys are at most 256 << 16 | 65534: never the sentinel)
-    int32_t lq = -1, xc = 0, yc = 0, r = 0;             // lq -1: no candidates (past the count, or in no level)
+    ScaledHit h{-1, 0, 0, 0, 0, 0, 0, 1, 0, 0};         // level -1: no candidates (past the count, or in no level)
+    int32_t xc = 0, yc = 0;
     uint32_t qd[WORDS];
 #pragma unroll
     for (int w = 0; w < WORDS; w++) qd[w] = 0;
     if (i < nq) {
       const uint32_t k = qkp[o];
       const int32_t x = (int32_t)((k >> 12) & 0xfffu), y = (int32_t)(k & 0xfffu);
-      const ScaledHit h = sc_level(P, x, y);
+      h = sc_level(P, x, y);
       if (h.level >= 0) {
-        lq = h.level;
-        r = h.radius;
         if (qpred) {
           xc = min(max(qpred[o * 2], -SCALED_PRED_LIMIT), SCALED_PRED_LIMIT);
           yc = min(max(qpred[o * 2 + 1], -SCALED_PRED_LIMIT), SCALED_PRED_LIMIT);
@@ -605,26 +458,21 @@ __global__ __launch_bounds__(WIN_THREADS) void k_match_scaled(ScaledPlan P, cons
         for (int w = 0; w < WORDS; w++) qd[w] = qp[w];
       }
     }
-    for (int l = 0; l < P.nlevels; l++) {               // wave-uniform: L comes from kernel-argument loads
-      if (lq < 0 || abs(l - lq) > P.span) continue;
-      const ScaledLevel L = P.lv[l];
-      // the window clipped to the level's mapped extent: its train entries all lie inside it
-      const int32_t x0 = max(xc - r, 0), x1 = min(xc + r, L.ext_x);
-      const int32_t y0 = max(yc - r, 0), y1 = min(yc + r, L.ext_y);
-      if (x0 > x1 || y0 > y1) continue;
-      const int32_t cx0 = x0 / L.side, cx1 = x1 / L.side, cy0 = y0 / L.side, cy1 = y1 / L.side;
-      const uint32_t *off = off_b + L.base;
-      for (int32_t cy = cy0; cy <= cy1; cy++) {
-        const uint32_t e1 = off[cy * L.ncx + cx1 + 1];
-        for (uint32_t e = off[cy * L.ncx + cx0] + sub; e < e1; e += WIN_LPQ) {
-          const uint2 m = mp[e];
-          const int32_t tx = (int32_t)(m.x >> 16), ty = (int32_t)(m.x & 0xffffu);
-          if (abs(tx - xc) <= r && abs(ty - yc) <= r) {
-            const uint32_t key = (win_popc<WORDS>(qd, ep + (size_t)e * WORDS) << 16) | m.y;
-            second = min(second, max(best, key));
-            best = min(best, key);
-          }
-        }
+    const int32_t r = h.radius;
+    auto visit = [&](uint32_t e, uint2 m) {
+      const int32_t tx = (int32_t)(m.x >> 16), ty = (int32_t)(m.x & 0xffffu);
+      if (abs(tx - xc) <= r && abs(ty - yc) <= r) {
+        const uint32_t key = (win_popc<WORDS>(qd, ep + (size_t)e * WORDS) << 16) | m.y;
+        second = min(second, max(best, key));
+        best = min(best, key);
+      }
+    };
+    if constexpr (ONE_LEVEL) {
+      if (h.level >= 0) win_walk(h, off_b, mp, sub, xc - r, xc + r, yc - r, yc + r, visit);
+    } else {
+      for (int l = 0; l < P.nlevels; l++) {             // wave-uniform: the level's fields are kernel-argument loads
+        if (h.level < 0 || abs(l - h.level) > P.span) continue;
+        win_walk(P.lv[l], off_b, mp, sub, xc - r, xc + r, yc - r, yc + r, visit);
       }
     }
 #pragma unroll
@@ -650,7 +498,7 @@ __global__ __launch_bounds__(WIN_THREADS) void k_match_scaled(ScaledPlan P, cons
 //                     it (host: stereo_plan), unchanged from the scaled window matcher.
 //   k_match_stereo    WIN_LPQ lanes per left keypoint; a wave-uniform loop over the plan's levels; the cell rows the
 //                     band |Yl - Yr| <= row_radius0[lr] overlaps, columns Xl - max_disp .. Xl - min_disp, clipped to the
-//                     level's mapped extent; exact test, best on dist << 16 | j.  Writes idx / dist.
+//                     level's mapped extent (win_walk); exact test, best on dist << 16 | j.  Writes idx / dist.
 //   k_stereo_refine   ST_LPQ lanes per left keypoint (one patch row each): the 2L + 1 SADs of the (2w+1)^2 patch, the
 //                     argmin, the parabola fit and the disparity.  w and L are kernel arguments, so the unrolled column
 //                     and offset loops are cut by uniform branches and the register arrays are only indexed by
@@ -702,25 +550,14 @@ __global__ __launch_bounds__(WIN_THREADS) void k_match_stereo(ScaledPlan P, int3
         for (int w = 0; w < WORDS; w++) qd[w] = qp[w];
       }
     }
-    for (int l = 0; l < P.nlevels; l++) {               // wave-uniform: L comes from kernel-argument loads
+    for (int l = 0; l < P.nlevels; l++) {               // wave-uniform: the level's fields are kernel-argument loads
       if (lq < 0 || abs(l - lq) > P.span) continue;
-      const ScaledLevel L = P.lv[l];
-      const int32_t r = L.radius;                       // row_radius0 of the RIGHT level
-      // the band clipped to the level's mapped extent: its right entries all lie inside it
-      const int32_t x0 = max(xl - max_disp, 0), x1 = min(xl - min_disp, L.ext_x);
-      const int32_t y0 = max(yl - r, 0), y1 = min(yl + r, L.ext_y);
-      if (x0 > x1 || y0 > y1) continue;
-      const int32_t cx0 = x0 / L.side, cx1 = x1 / L.side, cy0 = y0 / L.side, cy1 = y1 / L.side;
-      const uint32_t *off = off_b + L.base;
-      for (int32_t cy = cy0; cy <= cy1; cy++) {
-        const uint32_t e1 = off[cy * L.ncx + cx1 + 1];
-        for (uint32_t e = off[cy * L.ncx + cx0] + sub; e < e1; e += WIN_LPQ) {
-          const uint2 m = mp[e];
-          const int32_t dx = xl - (int32_t)(m.x >> 16), ty = (int32_t)(m.x & 0xffffu);
-          if (abs(ty - yl) <= r && dx >= min_disp && dx <= max_disp)
-            best = min(best, (win_popc<WORDS>(qd, ep + (size_t)e * WORDS) << 16) | m.y);
-        }
-      }
+      const int32_t r = P.lv[l].radius;                 // row_radius0 of the RIGHT level
+      win_walk(P.lv[l], off_b, mp, sub, xl - max_disp, xl - min_disp, yl - r, yl + r, [&](uint32_t e, uint2 m) {
+        const int32_t dx = xl - (int32_t)(m.x >> 16), ty = (int32_t)(m.x & 0xffffu);
+        if (abs(ty - yl) <= r && dx >= min_disp && dx <= max_disp)
+          best = min(best, (win_popc<WORDS>(qd, ep + (size_t)e * WORDS) << 16) | m.y);
+      });
     }
 #pragma unroll
     for (int s = 1; s < WIN_LPQ; s <<= 1) best = min(best, __shfl_xor(best, s, 64));
