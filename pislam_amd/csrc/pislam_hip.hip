@@ -1472,7 +1472,6 @@ int choose_sub_batches(const pislam_ctx *c, const pislam_frontend_params *p, int
   }
   return std::max(1, std::min(std::min(n, batch), (int)pislam_ctx::MAX_SUB));
 }
-inline int sub_max(int batch, int nsub) { return batch / nsub + (batch % nsub ? 1 : 0); }
 
 // Overflow lists: one per sub-batch ([0] count, [1] count of the previous step, [2..] entries), `stride` dwords
 // apart.  A new layout (or a new allocation) starts from an all-zero buffer: a stale entry must never be read
@@ -1502,8 +1501,7 @@ int ensure_aux(pislam_ctx *c, int nsub) {
 
 // The bucket selection pass (pf::k_bucket_select) and the UNIT plan the gather runs on when the strips run as without buckets
 // (build_fused_plan_rows): one "strip" per (level, cell row), `buckets x limit` slots each, lists final (lbs != 0, no tiles:
-// the gather concatenates).  Shared by run_fused and pislam_frontend_reserve (which sizes w_ustage / w_ucount from it, so that
-// the first bucket-mode call after a reserve allocates nothing and can be captured into a hipGraph).
+// the gather concatenates).  Part of the call's plan (plan_frontend).
 int build_select_plan(pislam_ctx *c, const pislam_frontend_params *p, const pf::FusedParams &Fplan, pf::SelectPlan *Qp,
                       pf::FusedParams *Up) {
   pf::SelectPlan &Q = *Qp;
@@ -1564,9 +1562,8 @@ int build_select_plan(pislam_ctx *c, const pislam_frontend_params *p, const pf::
 }
 
 // The device copy of a host-built plan table: found by content, or created (hipMalloc + upload in stream order — never
-// inside a capture: the first occurrence of a call runs eagerly, and pislam_frontend_reserve builds the tables).
-int plan_table(pislam_ctx *c, std::vector<uint32_t> &&t, const uint32_t **out) {
-  if (t.empty()) t.push_back(0u);
+// inside a capture: the first occurrence of a call runs eagerly, and reserve_frontend uploads the tables).
+int plan_table(pislam_ctx *c, const std::vector<uint32_t> &t, const uint32_t **out) {
   for (size_t i = 0; i < c->plan_tables.size(); i++)
     if (c->plan_tables[i]->host == t) {
       std::rotate(c->plan_tables.begin() + i, c->plan_tables.begin() + i + 1, c->plan_tables.end());   // most recently used last, the others keep their order
@@ -1581,7 +1578,7 @@ int plan_table(pislam_ctx *c, std::vector<uint32_t> &&t, const uint32_t **out) {
     c->table_uploads++;
   }
   pislam_ctx::PlanTable *pt = new pislam_ctx::PlanTable();
-  pt->host = std::move(t);
+  pt->host = t;
   if (pt->dev.ensure(sizeof(uint32_t) * pt->host.size()) != PISLAM_OK) {
     delete pt;
     return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(plan table)");
@@ -1593,8 +1590,8 @@ int plan_table(pislam_ctx *c, std::vector<uint32_t> &&t, const uint32_t **out) {
 }
 
 // The unit table of the bucket selection pass (pf::k_bucket_select reads one record per unit instead of walking the plan):
-// built on the host from the strip plan and the selection plan; its device copy comes from plan_table().
-int ensure_unit_table(pislam_ctx *c, const pislam_frontend_params *p, const pf::FusedParams &F, const pf::SelectPlan &Q) {
+// built on the host from the strip plan and the selection plan (never empty); its device copy comes from plan_table().
+std::vector<uint32_t> unit_table(const pislam_frontend_params *p, const pf::FusedParams &F, const pf::SelectPlan &Q) {
   std::vector<uint32_t> t((size_t)Q.units_per_pyr * pf::SEL_REC, 0u);
   const int B = p->border, lbs = p->log_bucket_size, bs = 1 << lbs;
   for (int l = 0; l < Q.nlevels; l++)
@@ -1618,7 +1615,7 @@ int ensure_unit_table(pislam_ctx *c, const pislam_frontend_params *p, const pf::
       r[4] = (uint32_t)(Q.row0[l] + B);
       r[5] = (uint32_t)(Q.col0[l] + B);
     }
-  return plan_table(c, std::move(t), &c->cur_utab);
+  return t;
 }
 
 // The one-launch path (pf::k_frame) takes batches of up to FRAME_MAX_BATCH pyramids: three launch floors are most of such
@@ -1628,7 +1625,6 @@ int ensure_unit_table(pislam_ctx *c, const pislam_frontend_params *p, const pf::
 constexpr int FRAME_MAX_BATCH = 8;                                  // what option "frame" can be raised to
 constexpr int FRAME_DEFAULT_BATCH = 2;                              // measured: one launch wins for 1 and 2 pyramids per call
 inline int frame_max_batch(const pislam_ctx *c) { return c->opt_frame <= 0 ? 0 : c->opt_frame == 1 ? FRAME_DEFAULT_BATCH : std::min(c->opt_frame, FRAME_MAX_BATCH); }
-inline int frame_chunks(int batch) { return std::min(64, std::max(16, 128 / std::max(1, batch))); }   // ORB workgroups per pyramid
 static_assert(FRAME_MAX_BATCH <= pf::FRAME_SYNC_PYR, "k_frame's hand-over counters");
 int ensure_frame_sync(pislam_ctx *c) {
   bool grew = false;
@@ -1637,105 +1633,65 @@ int ensure_frame_sync(pislam_ctx *c) {
   if (grew) HIPCHK(c, hipMemsetAsync(c->w_sync.p, 0, c->w_sync.cap, c->stream));   // (the kernel re-arms them itself)
   return ensure_fault_flag(c);
 }
-// `Fplan`: the strip plan, built for the largest sub-batch (sub_max pyramids).
-int run_fused(pislam_ctx *c, const pislam_frontend_params *p, const pf::FusedParams &Fplan, size_t lds, size_t lds_alias,
-              const uint8_t *pyramids, size_t stride, int batch, int nsub, uint32_t *kp, uint32_t *desc, uint32_t *counts) {
-  const int S = Fplan.strips_per_pyr;
-  const int submax = sub_max(batch, nsub);
-  // Buckets with the strips run as without (build_fused_plan_rows): the selection pass and the UNIT plan the gather runs on —
-  // one "strip" per (level, cell row), `buckets x limit` slots each, lists final (lbs != 0, no tiles: the gather concatenates).
-  const bool sel = p->log_bucket_size != 0 && Fplan.lbs == 0;
-  pf::SelectPlan Q;
-  pf::FusedParams U;
-  memset(&Q, 0, sizeof(Q));
-  memset(&U, 0, sizeof(U));
-  if (sel) {
-    PCHK(build_select_plan(c, p, Fplan, &Q, &U));
-    if (c->w_ustage.ensure(sizeof(uint32_t) * (size_t)Q.uslots_per_pyr * batch) != PISLAM_OK ||
-        c->w_ucount.ensure(sizeof(uint32_t) * (size_t)Q.units_per_pyr * batch) != PISLAM_OK)
-      return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(bucket selection staging)");
-    PCHK(ensure_unit_table(c, p, Fplan, Q));
+// What a front-end batch call decides from the shape and the options (plan_frontend, host only): reserve_frontend sizes the
+// workspace from it and run_fused launches from it: after a reserve the call allocates nothing and can be captured into a hipGraph.
+struct FrontendPlan {
+  bool fused = false;                 // false: the staged pipeline (option "pipeline" 1, or no strip plan for the shape)
+  int nsub = 1, submax = 0;           // sub-batches, pyramids in the largest one
+  pf::FusedParams F{};                // the strip plan, built for submax pyramids (strips_per_pyr == 0: nothing to extract)
+  size_t lds = 0, lds_alias = 0, klds = 0;   // strip kernel LDS bytes: plain layout, ALIAS layout, the layout it runs with
+  bool sel = false;                   // the bucket selection pass: build_select_plan's two plans, the unit table
+  pf::SelectPlan Q{};
+  pf::FusedParams U{};
+  std::vector<uint32_t> utab;
+  size_t sel_lds = 0, glds = 0;       // LDS bytes of k_bucket_select and of k_gather
+  bool alias = false;                 // ALIAS layout: one overflow list of ovf_stride dwords per sub-batch
+  size_t ovf_stride = 0, sdesc_per_pyr = 0;
+  bool generic_orb = false;           // k_gather + per-keypoint k_orb instead of k_gather_orb
+  bool frame = false;                 // the one-launch path (pf::k_frame), as far as the shape and the options decide
+  int nch = 0, fch = 0;               // ORB workgroups per pyramid of k_gather_orb and of k_frame
+  size_t per_max = 0, olds = 0, fper = 0, flds = 0;   // keypoints per workgroup and LDS bytes of the two
+};
+
+// The plan of a batch call (parameters checked).  Fails only where build_select_plan does, with `fused` and F already set.
+int plan_frontend(pislam_ctx *c, const pislam_frontend_params *p, const pislam_level *lv, int batch, FrontendPlan *P) {
+  P->nsub = choose_sub_batches(c, p, batch);
+  P->submax = batch / P->nsub + (batch % P->nsub ? 1 : 0);
+  P->fused = c->opt_pipeline != 1 && build_fused_plan(c, p, lv, P->submax, &P->F, &P->lds, &P->lds_alias);
+  const pf::FusedParams &F = P->F;
+  const int S = F.strips_per_pyr, nsub = P->nsub, submax = P->submax;
+  if (!P->fused || S == 0) return PISLAM_OK;
+  P->sel = p->log_bucket_size != 0 && F.lbs == 0;
+  if (P->sel) {
+    PCHK(build_select_plan(c, p, F, &P->Q, &P->U));
+    P->utab = unit_table(p, F, P->Q);
+    P->sel_lds = sizeof(uint32_t) * pf::SEL_WAVES * (64 + 2 * (size_t)P->Q.nb_max);
   }
-  c->last_path = PISLAM_PATH_FUSED | (sel ? PISLAM_PATH_BUCKET_SELECT : 0u) | (Fplan.lbs != 0 ? PISLAM_PATH_BUCKETS_IN_STRIPS : 0u);
-  const int Sg = sel ? Q.units_per_pyr : S;            // "strips" of the plan the gather runs on
+  const int Sg = P->sel ? P->Q.units_per_pyr : S;   // "strips" of the plan the gather runs on
   // descriptor staging: QS_SHARED slots of `words` dwords per strip (ALIAS strips hold at most QS_SHARED survivors)
   // (only strips that describe their own keypoints write there: option "orb_in_strip")
-  const size_t sdesc_per_pyr = Fplan.orb_in_strip ? (size_t)S * pf::QS_SHARED * (size_t)p->words : 0;
-  // (+ 64 dwords: pf::k_bucket_select requests the first 64 slots of a strip's list whatever its count)
-  if (c->w_stage.ensure(sizeof(uint32_t) * ((size_t)Fplan.slots_per_pyr * batch + 64)) != PISLAM_OK ||
-      c->w_stripcnt.ensure(sizeof(uint32_t) * (size_t)S * batch) != PISLAM_OK ||
-      c->w_stagedesc.ensure(sizeof(uint32_t) * sdesc_per_pyr * batch) != PISLAM_OK)
-    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(fused staging)");
-  // 16-byte loads need 16-byte aligned rows
-  bool vec = ((uintptr_t)pyramids % 16 == 0) && (stride % 16 == 0) && (p->vstep % 16 == 0);
-  for (int l = 0; l < Fplan.nlevels; l++) vec = vec && (Fplan.lv[l].col0 % 16 == 0);
-  uint8_t *dump = Fplan.dump_score ? c->w_score.as<uint8_t>() : nullptr;
-  const size_t dump_stride = (size_t)p->rows * p->vstep;
+  P->sdesc_per_pyr = F.orb_in_strip ? (size_t)S * pf::QS_SHARED * (size_t)p->words : 0;
   // ALIAS layout (score tile laid over the dead image rows, 26 KB instead of 39 KB of LDS per workgroup
   // at VGA): the default.  Its overflow list (strips with overflowing queues) is drained by
   // k_fused_overflow right after; the gather kernel empties the list for the next step.
-  const bool alias = c->opt_alias && submax <= 65535 && S <= 65535;
-  const size_t ovf_stride = 2 + (size_t)S * submax;
-  if (alias) {
-    PCHK(prepare_ovf(c, nsub, ovf_stride));
-    c->last_strips = (uint32_t)S * (uint32_t)batch;
-  }
-  // A call that is being captured into a hipGraph does not fork: its sub-batches then run in order on the context stream, and
-  // the graph is one chain of nodes like every other captured call.  (A graph with a parallel branch from the fork crashed
-  // inside hipGraphLaunch when it was replayed; chains replay fine.)  Eager calls fork as before.
-  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-  if (nsub > 1 && hipStreamIsCapturing(c->stream, &capture) != hipSuccess) {
-    (void)hipGetLastError();                      // (the query's own error must not be reported by a later launch check)
-    capture = hipStreamCaptureStatusNone;
-  }
-  const bool fork = nsub > 1 && capture == hipStreamCaptureStatusNone;
-  if (fork) PCHK(ensure_aux(c, nsub));
-  // HOOKS instantiations: score-map dump (debug / parity hook) and the profiling ablations
-  const bool hooks = Fplan.dump_score || Fplan.ablate;
-  using KernT = void (*)(const pf::FusedParams, const uint8_t *, size_t, uint32_t *, uint32_t *, uint8_t *, size_t,
-                         unsigned long long *, uint32_t *, uint32_t *);
-  static const KernT kerns[8] = {
-      pf::k_fused_strips<false, false, false>, pf::k_fused_strips<false, false, true>,
-      pf::k_fused_strips<false, true, false>,  pf::k_fused_strips<false, true, true>,
-      pf::k_fused_strips<true, false, false>,  pf::k_fused_strips<true, false, true>,
-      pf::k_fused_strips<true, true, false>,   pf::k_fused_strips<true, true, true>};
-  // strips describing their own keypoints (option "orb_in_strip"): separate instantiations of the aligned ALIAS kernels
-  static const KernT kerns_orb[2] = {pf::k_fused_strips<true, false, true, true>, pf::k_fused_strips<true, true, true, true>};
-  // the default mode's kernels (aligned ALIAS layout, no buckets, gather+ORB describes): compiled without the bucket code
-  static const KernT kerns_nb[2] = {pf::k_fused_strips<true, false, true, false, false>,
-                                    pf::k_fused_strips<true, true, true, false, false>};
-  const KernT kern = (Fplan.orb_in_strip && vec && alias) ? kerns_orb[hooks ? 1 : 0]
-                     : (vec && alias && Fplan.lbs == 0)   ? kerns_nb[hooks ? 1 : 0]
-                                                          : kerns[(vec ? 4 : 0) | (hooks ? 2 : 0) | (alias ? 1 : 0)];
-  const size_t klds = alias ? lds_alias : lds;
-  if (klds > 150 * 1024) return fail(c, PISLAM_ERR_INVALID, "level too wide for the strip kernel's LDS tiles");
-  if (klds > 64 * 1024)
-    HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)klds));
-  using OvfT = void (*)(const pf::FusedParams, const uint8_t *, size_t, uint32_t *, uint32_t *, uint8_t *, size_t,
-                        const uint32_t *);
-  static const OvfT okerns[4] = {pf::k_fused_overflow<false, false>, pf::k_fused_overflow<false, true>,
-                                 pf::k_fused_overflow<true, false>, pf::k_fused_overflow<true, true>};
-  const OvfT okern = okerns[(vec ? 2 : 0) | (hooks ? 1 : 0)];
-  if (alias && lds > 64 * 1024)
-    HIPCHK(c, hipFuncSetAttribute((const void *)okern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  P->alias = c->opt_alias && submax <= 65535 && S <= 65535;
+  P->ovf_stride = 2 + (size_t)S * submax;
+  P->klds = P->alias ? P->lds_alias : P->lds;
   // k_gather_orb's 48-byte row windows assume a row-independent byte shift (vstep % 16 == 0) and
   // 32-bit byte offsets inside a pyramid; other layouts take the generic gather + per-keypoint ORB kernels.
-  const bool generic_orb = p->vstep % 16 != 0 || (size_t)p->rows * p->vstep > 0x7fffffffu;
+  P->generic_orb = p->vstep % 16 != 0 || (size_t)p->rows * p->vstep > 0x7fffffffu;
+  P->glds = sizeof(uint32_t) * (Sg + 1);
   // gather + orbCompute in one launch: (chunks, pyramids) workgroups
   // Workgroups per pyramid: one per ~70 k classified pixels (keypoint counts are not known to the host; ~70-100
   // keypoints per workgroup measured best: VGA, 981 keypoints: 14 = 21 chunks > 7, 28; 1280x960, 4389 keypoints: 42-49
   // chunks 0.36 ms against 0.41 ms with 14), at least 16 for small batches, and such that the grid is a whole number
   // of "waves" of resident workgroups (7 per CU: 64 VGPRs, 13.5 KB LDS) — batch 256: 14 chunks = 2 x 1792 workgroups
   // measured 0.079 ms against 0.085 ms with 16 (2.3 waves: the last one 30 % full).
-  int nch = 0;
-  size_t per_max = 0, olds = 0;
-  // (the profiling instantiation exists for the gather's per-phase counters: option "ablate" bits 20..23, pf::orb_describe)
-  const auto gkern = (Fplan.ablate >> 20) & 15 ? pf::k_gather_orb<true> : pf::k_gather_orb<false>;
-  if (!generic_orb) {
+  if (!P->generic_orb) {
     long px = 0;
-    for (int l = 0; l < Fplan.nlevels; l++) px += (long)(Fplan.lv[l].ex1 - Fplan.lv[l].ex0) * Fplan.lv[l].nstrips * Fplan.lv[l].R;
+    for (int l = 0; l < F.nlevels; l++) px += (long)(F.lv[l].ex1 - F.lv[l].ex0) * F.lv[l].nstrips * F.lv[l].R;
     const int by_px = (int)(px / 70000);
-    nch = std::min(64, submax >= 128 ? std::max(8, by_px) : std::max(by_px, std::max(16, 4096 / submax)));
+    int nch = std::min(64, submax >= 128 ? std::max(8, by_px) : std::max(by_px, std::max(16, 4096 / submax)));
     if (nsub == 1) {
       const long slots = 7L * std::max(1, c->num_cus);
       long best = nch, bestd = 1L << 40;
@@ -1754,61 +1710,164 @@ int run_fused(pislam_ctx *c, const pislam_frontend_params *p, const pf::FusedPar
       // resident workgroups mean nothing there — one workgroup per ~70 k pixels
       nch = std::min(64, std::max(8, by_px));
     }
-    if (c->opt_orb_chunks > 0) nch = c->opt_orb_chunks;
-    per_max = ((size_t)p->max_keypoints + nch - 1) / nch;
-    olds = pf::orb_lds_bytes(Sg, per_max);
-    if (olds > 150 * 1024) return fail(c, PISLAM_ERR_INVALID, "max_keypoints too large for the fused ORB kernel");
-    if (olds > 64 * 1024)
-      HIPCHK(c, hipFuncSetAttribute((const void *)gkern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)olds));
+    P->nch = c->opt_orb_chunks > 0 ? c->opt_orb_chunks : nch;
+    P->per_max = ((size_t)p->max_keypoints + P->nch - 1) / P->nch;
+    P->olds = pf::orb_lds_bytes(Sg, P->per_max);
+  }
+  // The one-launch path.  Occupancy gate: the gather + ORB workgroups WAIT inside the grid.  With `lanes_in_flight` such
+  // launches on the device at most lanes x batch x fch of them are resident, an eighth per XCD; they must stay a small
+  // fraction (a quarter) of the workgroups an XCD holds with this launch's LDS footprint (96 VGPRs: five 4-wave workgroups
+  // per CU at most), so that strip workgroups always find a slot.
+  if (P->alias && !P->sel && F.lbs == 0 && !F.dump_score && !F.ablate && !P->generic_orb && nsub == 1 && !F.orb_in_strip &&
+      c->opt_repeat_strips <= 1 && batch <= frame_max_batch(c)) {
+    P->fch = c->opt_orb_chunks > 0 ? std::min(c->opt_orb_chunks, 128) : std::min(64, std::max(16, 128 / batch));
+    P->fper = ((size_t)p->max_keypoints + P->fch - 1) / P->fch;
+    P->flds = std::max(std::max(P->lds_alias, P->lds), pf::orb_lds_bytes(S, P->fper));
+    const long wg_per_cu = std::max<long>(1, std::min<long>(5, (long)(160 * 1024) / (long)std::max<size_t>(P->flds, 1)));
+    const long slots_per_xcd = wg_per_cu * std::max(1, c->num_cus / 8);
+    const long waiting_per_xcd = ((long)std::max(1, c->lanes_in_flight) * batch * P->fch + 7) / 8;
+    P->frame = P->flds <= 150 * 1024 && 4 * waiting_per_xcd <= slots_per_xcd;
+  }
+  return PISLAM_OK;
+}
+
+// The workspace of plan P: the only place the front end's buffers are allocated (option "ablate" 8192's profiling aside).
+int reserve_frontend(pislam_ctx *c, const pislam_frontend_params *p, const pislam_level *lv, const FrontendPlan &P, int batch) {
+  const size_t pyr_bytes = (size_t)p->rows * p->vstep;
+  bool grew = false;
+  if (c->w_score.ensure(pyr_bytes * batch, &grew) != PISLAM_OK)
+    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(score map)");
+  const bool same_shape = !grew && c->last_batch >= batch && c->last_params.vstep == p->vstep &&
+                          c->last_params.rows == p->rows && c->last_params.nlevels == p->nlevels &&
+                          c->last_params.border == p->border && (int)c->last_levels.size() == p->nlevels &&
+                          memcmp(c->last_levels.data(), lv, sizeof(pislam_level) * p->nlevels) == 0;
+  if (!same_shape) {
+    // Fast.h:42-44: `out` must start as zeros; afterwards the regions fastDetect rewrites are the
+    // only ones that ever change, so the zeroing is needed once per shape.
+    HIPCHK(c, hipMemsetAsync(c->w_score.p, 0, pyr_bytes * batch, c->stream));
+    c->last_params = *p;
+    c->last_levels.assign(lv, lv + p->nlevels);
+    c->last_batch = batch;
+  }
+  size_t maxn = 1;
+  for (int l = 0; l < p->nlevels; l++) {
+    const int ny = lv[l].height - 2 * p->border, nx = lv[l].width - 2 * p->border;
+    if (ny <= 0 || nx <= 0) continue;
+    const int bs = 1 << p->log_bucket_size;
+    maxn = std::max<size_t>(maxn, p->log_bucket_size == 0 ? (size_t)cdiv(ny, 2) : (size_t)((nx - 1) / bs + 1) * ((ny - 1) / bs + 1));
+  }
+  if (c->w_cnt.ensure(sizeof(uint32_t) * maxn * batch) != PISLAM_OK ||
+      c->w_off.ensure(sizeof(uint32_t) * maxn * batch) != PISLAM_OK ||
+      (p->log_bucket_size &&
+       c->w_cellkp.ensure(sizeof(uint32_t) * maxn * batch * p->bucket_limit) != PISLAM_OK))
+    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(extract scratch)");
+  if (!P.fused || P.F.strips_per_pyr == 0) return PISLAM_OK;
+  // (+ 64 dwords: pf::k_bucket_select requests the first 64 slots of a strip's list whatever its count)
+  if (c->w_stage.ensure(sizeof(uint32_t) * ((size_t)P.F.slots_per_pyr * batch + 64)) != PISLAM_OK ||
+      c->w_stripcnt.ensure(sizeof(uint32_t) * (size_t)P.F.strips_per_pyr * batch) != PISLAM_OK ||
+      c->w_stagedesc.ensure(sizeof(uint32_t) * P.sdesc_per_pyr * batch) != PISLAM_OK)
+    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(fused staging)");
+  if (P.alias) PCHK(prepare_ovf(c, P.nsub, P.ovf_stride));
+  if (P.nsub > 1) PCHK(ensure_aux(c, P.nsub));
+  if (batch <= frame_max_batch(c)) PCHK(ensure_frame_sync(c));
+  if (P.sel) {
+    if (c->w_ustage.ensure(sizeof(uint32_t) * (size_t)P.Q.uslots_per_pyr * batch) != PISLAM_OK ||
+        c->w_ucount.ensure(sizeof(uint32_t) * (size_t)P.Q.units_per_pyr * batch) != PISLAM_OK)
+      return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(bucket selection staging)");
+    PCHK(plan_table(c, P.utab, &c->cur_utab));
+  }
+  return PISLAM_OK;
+}
+
+// Launches plan P (strips_per_pyr > 0, workspace reserved by reserve_frontend) with the call's pointers.
+int run_fused(pislam_ctx *c, const pislam_frontend_params *p, const FrontendPlan &P, const uint8_t *pyramids, size_t stride,
+              int batch, uint32_t *kp, uint32_t *desc, uint32_t *counts) {
+  const int S = P.F.strips_per_pyr, nsub = P.nsub;
+  const bool sel = P.sel, alias = P.alias;
+  c->last_path = PISLAM_PATH_FUSED | (sel ? PISLAM_PATH_BUCKET_SELECT : 0u) | (P.F.lbs != 0 ? PISLAM_PATH_BUCKETS_IN_STRIPS : 0u);
+  // 16-byte loads need 16-byte aligned rows
+  bool vec = ((uintptr_t)pyramids % 16 == 0) && (stride % 16 == 0) && (p->vstep % 16 == 0);
+  for (int l = 0; l < P.F.nlevels; l++) vec = vec && (P.F.lv[l].col0 % 16 == 0);
+  uint8_t *dump = P.F.dump_score ? c->w_score.as<uint8_t>() : nullptr;
+  const size_t dump_stride = (size_t)p->rows * p->vstep;
+  if (alias) c->last_strips = (uint32_t)S * (uint32_t)batch;
+  // A call that is being captured into a hipGraph does not fork: its sub-batches then run in order on the context stream, and
+  // the graph is one chain of nodes like every other captured call.  (A graph with a parallel branch from the fork crashed
+  // inside hipGraphLaunch when it was replayed; chains replay fine.)  Eager calls fork as before.
+  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+  if (nsub > 1 && hipStreamIsCapturing(c->stream, &capture) != hipSuccess) {
+    (void)hipGetLastError();                      // (the query's own error must not be reported by a later launch check)
+    capture = hipStreamCaptureStatusNone;
+  }
+  const bool fork = nsub > 1 && capture == hipStreamCaptureStatusNone;
+  // HOOKS instantiations: score-map dump (debug / parity hook) and the profiling ablations
+  const bool hooks = P.F.dump_score || P.F.ablate;
+  using KernT = void (*)(const pf::FusedParams, const uint8_t *, size_t, uint32_t *, uint32_t *, uint8_t *, size_t,
+                         unsigned long long *, uint32_t *, uint32_t *);
+  static const KernT kerns[8] = {
+      pf::k_fused_strips<false, false, false>, pf::k_fused_strips<false, false, true>,
+      pf::k_fused_strips<false, true, false>,  pf::k_fused_strips<false, true, true>,
+      pf::k_fused_strips<true, false, false>,  pf::k_fused_strips<true, false, true>,
+      pf::k_fused_strips<true, true, false>,   pf::k_fused_strips<true, true, true>};
+  // strips describing their own keypoints (option "orb_in_strip"): separate instantiations of the aligned ALIAS kernels
+  static const KernT kerns_orb[2] = {pf::k_fused_strips<true, false, true, true>, pf::k_fused_strips<true, true, true, true>};
+  // the default mode's kernels (aligned ALIAS layout, no buckets, gather+ORB describes): compiled without the bucket code
+  static const KernT kerns_nb[2] = {pf::k_fused_strips<true, false, true, false, false>,
+                                    pf::k_fused_strips<true, true, true, false, false>};
+  const KernT kern = (P.F.orb_in_strip && vec && alias) ? kerns_orb[hooks ? 1 : 0]
+                     : (vec && alias && P.F.lbs == 0)   ? kerns_nb[hooks ? 1 : 0]
+                                                          : kerns[(vec ? 4 : 0) | (hooks ? 2 : 0) | (alias ? 1 : 0)];
+  if (P.klds > 150 * 1024) return fail(c, PISLAM_ERR_INVALID, "level too wide for the strip kernel's LDS tiles");
+  if (P.klds > 64 * 1024)
+    HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.klds));
+  using OvfT = void (*)(const pf::FusedParams, const uint8_t *, size_t, uint32_t *, uint32_t *, uint8_t *, size_t,
+                        const uint32_t *);
+  static const OvfT okerns[4] = {pf::k_fused_overflow<false, false>, pf::k_fused_overflow<false, true>,
+                                 pf::k_fused_overflow<true, false>, pf::k_fused_overflow<true, true>};
+  const OvfT okern = okerns[(vec ? 2 : 0) | (hooks ? 1 : 0)];
+  if (alias && P.lds > 64 * 1024)
+    HIPCHK(c, hipFuncSetAttribute((const void *)okern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds));
+  // (the profiling instantiation exists for the gather's per-phase counters: option "ablate" bits 20..23, pf::orb_describe)
+  const auto gkern = (P.F.ablate >> 20) & 15 ? pf::k_gather_orb<true> : pf::k_gather_orb<false>;
+  if (!P.generic_orb) {
+    if (P.olds > 150 * 1024) return fail(c, PISLAM_ERR_INVALID, "max_keypoints too large for the fused ORB kernel");
+    if (P.olds > 64 * 1024)
+      HIPCHK(c, hipFuncSetAttribute((const void *)gkern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.olds));
   }
 
   // ---- small batches: strips -> (overflowed strips redone in place) -> gather + ORB as ONE launch ----
   if (c->frame_disabled) c->last_path |= PISLAM_PATH_FRAME_TIMED_OUT;
-  if (alias && vec && !sel && Fplan.lbs == 0 && !hooks && !generic_orb && nsub == 1 && !Fplan.orb_in_strip &&
-      c->opt_repeat_strips <= 1 && batch <= frame_max_batch(c) && !c->frame_disabled) {
-    const int fch = c->opt_orb_chunks > 0 ? std::min(c->opt_orb_chunks, 128) : frame_chunks(batch);
-    const size_t fper = ((size_t)p->max_keypoints + fch - 1) / fch;
-    const size_t flds = std::max(std::max(lds_alias, lds), pf::orb_lds_bytes(S, fper));
-    // Occupancy gate: the gather + ORB workgroups WAIT inside the grid.  With `lanes_in_flight` such launches on the device
-    // at most lanes x batch x fch of them are resident, an eighth per XCD; they must stay a small fraction (a quarter) of
-    // the workgroups an XCD holds with this launch's LDS footprint (96 VGPRs: five 4-wave workgroups per CU at most), so
-    // that strip workgroups always find a slot.
-    const long wg_per_cu = std::max<long>(1, std::min<long>(5, (long)(160 * 1024) / (long)std::max<size_t>(flds, 1)));
-    const long slots_per_xcd = wg_per_cu * std::max(1, c->num_cus / 8);
-    const long waiting_per_xcd = ((long)std::max(1, c->lanes_in_flight) * batch * fch + 7) / 8;
-    if (flds <= 150 * 1024 && 4 * waiting_per_xcd <= slots_per_xcd) {
-      PCHK(ensure_frame_sync(c));
-      if (flds > 64 * 1024)
-        HIPCHK(c, hipFuncSetAttribute((const void *)pf::k_frame, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
-      pf::FusedParams F = Fplan;
-      F.batch = batch;
-      const unsigned grid = (unsigned)(batch * F.runs_per_pyr + batch * fch);
-      hipLaunchKernelGGL(pf::k_frame, dim3(grid), dim3(pf::NT), flds, c->stream, F, pyramids, stride, c->w_stage.as<uint32_t>(),
-                         c->w_stripcnt.as<uint32_t>(), kp, (size_t)p->max_keypoints, (uint32_t)p->max_keypoints, counts, desc,
-                         (size_t)p->max_keypoints * p->words, p->words, (uint32_t)fper, fch, c->w_sync.as<uint32_t>(),
-                         c->w_ovf.as<uint32_t>(), c->frame_flag_dev, (uint32_t)c->opt_frame_test);
-      PCHK(launch_ok(c, "k_frame"));
-      c->last_path = PISLAM_PATH_FUSED | PISLAM_PATH_ONE_LAUNCH;
-      HIPCHK(c, hipEventRecord(c->ev[1], c->stream));   // (one launch: the stage split of last_timing is all in stage 0)
-      HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-      return PISLAM_OK;
-    }
+  if (P.frame && vec && !c->frame_disabled) {
+    if (P.flds > 64 * 1024)
+      HIPCHK(c, hipFuncSetAttribute((const void *)pf::k_frame, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.flds));
+    pf::FusedParams F = P.F;
+    F.batch = batch;
+    const unsigned grid = (unsigned)(batch * F.runs_per_pyr + batch * P.fch);
+    hipLaunchKernelGGL(pf::k_frame, dim3(grid), dim3(pf::NT), P.flds, c->stream, F, pyramids, stride, c->w_stage.as<uint32_t>(),
+                       c->w_stripcnt.as<uint32_t>(), kp, (size_t)p->max_keypoints, (uint32_t)p->max_keypoints, counts, desc,
+                       (size_t)p->max_keypoints * p->words, p->words, (uint32_t)P.fper, P.fch, c->w_sync.as<uint32_t>(),
+                       c->w_ovf.as<uint32_t>(), c->frame_flag_dev, (uint32_t)c->opt_frame_test);
+    PCHK(launch_ok(c, "k_frame"));
+    c->last_path = PISLAM_PATH_FUSED | PISLAM_PATH_ONE_LAUNCH;
+    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));   // (one launch: the stage split of last_timing is all in stage 0)
+    HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
+    return PISLAM_OK;
   }
   const int base = batch / nsub, rem = batch % nsub;
   hipStream_t M = c->stream, X = fork ? c->aux_stream : c->stream;
   for (int sub = 0; sub < nsub; sub++) {
     const int first = sub * base + std::min(sub, rem), n = base + (sub < rem ? 1 : 0);
-    pf::FusedParams F = Fplan;
+    pf::FusedParams F = P.F;
     F.batch = n;
     const uint8_t *s_pyr = pyramids + (size_t)first * stride;
     uint32_t *s_stage = c->w_stage.as<uint32_t>() + (size_t)first * F.slots_per_pyr;
     uint32_t *s_cnt = c->w_stripcnt.as<uint32_t>() + (size_t)first * S;
-    uint32_t *s_sdesc = c->w_stagedesc.as<uint32_t>() + (size_t)first * sdesc_per_pyr;
+    uint32_t *s_sdesc = c->w_stagedesc.as<uint32_t>() + (size_t)first * P.sdesc_per_pyr;
     uint8_t *s_dump = dump ? dump + (size_t)first * dump_stride : nullptr;
     uint32_t *s_kp = kp + (size_t)first * p->max_keypoints;
     uint32_t *s_desc = desc + (size_t)first * p->max_keypoints * p->words;
     uint32_t *s_counts = counts + first;
-    uint32_t *ovf = alias ? c->w_ovf.as<uint32_t>() + (size_t)sub * ovf_stride : nullptr;
+    uint32_t *ovf = alias ? c->w_ovf.as<uint32_t>() + (size_t)sub * P.ovf_stride : nullptr;
     const dim3 grid((unsigned)(cdiv(n, 8) * F.runs_per_pyr * 8));
     unsigned long long *prof = nullptr;
     const size_t prof_n = (size_t)grid.x * 8;
@@ -1822,7 +1881,7 @@ int run_fused(pislam_ctx *c, const pislam_frontend_params *p, const pf::FusedPar
     //  around a single eager launch; every launch rewrites the same outputs)
     for (int rep = 0; rep < std::max(1, c->opt_repeat_strips); rep++) {
       if (rep && ovf) HIPCHK(c, hipMemsetAsync(ovf, 0, sizeof(uint32_t), M));   // the last launch's list counts
-      hipLaunchKernelGGL(kern, grid, dim3(pf::NT), klds, M, F, s_pyr, stride, s_stage, s_cnt, s_dump, dump_stride, prof, ovf,
+      hipLaunchKernelGGL(kern, grid, dim3(pf::NT), P.klds, M, F, s_pyr, stride, s_stage, s_cnt, s_dump, dump_stride, prof, ovf,
                          s_sdesc);
     }
     if (prof) {
@@ -1862,7 +1921,7 @@ int run_fused(pislam_ctx *c, const pislam_frontend_params *p, const pf::FusedPar
       HIPCHK(c, hipEventRecord(c->ev[1], M));     // stage 0 = the strip kernel alone
     }
     if (alias) {
-      hipLaunchKernelGGL(okern, dim3((unsigned)std::max(8, c->num_cus / 2)), dim3(pf::NT), lds, X, F, s_pyr, stride, s_stage,
+      hipLaunchKernelGGL(okern, dim3((unsigned)std::max(8, c->num_cus / 2)), dim3(pf::NT), P.lds, X, F, s_pyr, stride, s_stage,
                          s_cnt, s_dump, dump_stride, (const uint32_t *)ovf);
       PCHK(launch_ok(c, "k_fused_overflow"));
     }
@@ -1871,20 +1930,19 @@ int run_fused(pislam_ctx *c, const pislam_frontend_params *p, const pf::FusedPar
     pf::FusedParams G = F;
     const uint32_t *g_stage = s_stage, *g_cnt = s_cnt;
     if (sel) {
-      uint32_t *u_stage = c->w_ustage.as<uint32_t>() + (size_t)first * Q.uslots_per_pyr;
-      uint32_t *u_cnt = c->w_ucount.as<uint32_t>() + (size_t)first * Q.units_per_pyr;
-      const size_t sel_lds = sizeof(uint32_t) * pf::SEL_WAVES * (64 + 2 * (size_t)Q.nb_max);
-      hipLaunchKernelGGL(pf::k_bucket_select, dim3(cdiv(Q.units_per_pyr, pf::SEL_WAVES), n), dim3(64 * pf::SEL_WAVES), sel_lds, X, F, Q,
+      uint32_t *u_stage = c->w_ustage.as<uint32_t>() + (size_t)first * P.Q.uslots_per_pyr;
+      uint32_t *u_cnt = c->w_ucount.as<uint32_t>() + (size_t)first * P.Q.units_per_pyr;
+      hipLaunchKernelGGL(pf::k_bucket_select, dim3(cdiv(P.Q.units_per_pyr, pf::SEL_WAVES), n), dim3(64 * pf::SEL_WAVES), P.sel_lds, X, F, P.Q,
                          (const uint32_t *)s_stage, (const uint32_t *)s_cnt, u_stage, u_cnt, c->cur_utab);
       PCHK(launch_ok(c, "k_bucket_select"));
-      G = U;
+      G = P.U;
       G.batch = n;
       g_stage = u_stage;
       g_cnt = u_cnt;
     }
-    if (generic_orb) {
+    if (P.generic_orb) {
       c->last_path |= PISLAM_PATH_GENERIC_ORB;
-      hipLaunchKernelGGL(pf::k_gather, dim3(n), dim3(256), sizeof(uint32_t) * (Sg + 1), X, G, g_stage, g_cnt, s_kp,
+      hipLaunchKernelGGL(pf::k_gather, dim3(n), dim3(256), P.glds, X, G, g_stage, g_cnt, s_kp,
                          (size_t)p->max_keypoints, (uint32_t)p->max_keypoints, s_counts, ovf);
       PCHK(launch_ok(c, "k_gather"));
       hipLaunchKernelGGL(pk::k_orb<0>, dim3(cdiv(p->max_keypoints, 4), 1, n), dim3(256), 0, X, s_pyr, p->vstep, stride,
@@ -1892,9 +1950,9 @@ int run_fused(pislam_ctx *c, const pislam_frontend_params *p, const pf::FusedPar
                          (size_t)p->max_keypoints * p->words, (int32_t *)nullptr, (const uint8_t *)nullptr);
       PCHK(launch_ok(c, "k_orb<batch>"));
     } else {
-      hipLaunchKernelGGL(gkern, dim3(nch, n), dim3(256), olds, X, G, s_pyr, stride, g_stage, g_cnt,
+      hipLaunchKernelGGL(gkern, dim3(P.nch, n), dim3(256), P.olds, X, G, s_pyr, stride, g_stage, g_cnt,
                          (const uint32_t *)s_sdesc, s_kp, (size_t)p->max_keypoints, (uint32_t)p->max_keypoints, s_counts,
-                         s_desc, (size_t)p->max_keypoints * p->words, p->words, (uint32_t)per_max, ovf);
+                         s_desc, (size_t)p->max_keypoints * p->words, p->words, (uint32_t)P.per_max, ovf);
       PCHK(launch_ok(c, "k_gather_orb"));
     }
   }
@@ -1905,14 +1963,55 @@ int run_fused(pislam_ctx *c, const pislam_frontend_params *p, const pf::FusedPar
   return PISLAM_OK;
 }
 
+// The staged pipeline: a launch group per level (FAST, Harris, ordered extraction), then per-keypoint ORB over the batch.
+int run_staged(pislam_ctx *c, const pislam_frontend_params *p, const pislam_level *lv, const uint8_t *pyramids, size_t stride,
+               int batch, uint32_t *kp, uint32_t *desc, uint32_t *counts) {
+  const size_t pyr_bytes = (size_t)p->rows * p->vstep;
+  uint8_t *score = c->w_score.as<uint8_t>();
+  HIPCHK(c, hipMemsetAsync(counts, 0, sizeof(uint32_t) * batch, c->stream));
+  // The score map workspace is laid out with stride pyr_bytes; the image with `stride`.  The stage
+  // kernels take one stride for both, so when they differ fall back to per-pyramid launches.
+  const bool same = stride == pyr_bytes;
+  for (int l = 0; l < p->nlevels; l++) {
+    const size_t off = (size_t)lv[l].row0 * p->vstep + lv[l].col0;
+    if (same) {
+      PCHK(launch_detect(c, pyramids + off, score + off, p->vstep, pyr_bytes, batch, p->border,
+                         lv[l].width, lv[l].height, p->fast_threshold));
+      PCHK(launch_harris(c, pyramids + off, score + off, p->vstep, pyr_bytes, batch, p->border,
+                         lv[l].width, lv[l].height, p->harris_threshold));
+    } else {
+      for (int b = 0; b < batch; b++) {
+        PCHK(launch_detect(c, pyramids + b * stride + off, score + b * pyr_bytes + off, p->vstep, 0, 1,
+                           p->border, lv[l].width, lv[l].height, p->fast_threshold));
+        PCHK(launch_harris(c, pyramids + b * stride + off, score + b * pyr_bytes + off, p->vstep, 0, 1,
+                           p->border, lv[l].width, lv[l].height, p->harris_threshold));
+      }
+    }
+  }
+  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
+  for (int l = 0; l < p->nlevels; l++) {
+    const size_t off = (size_t)lv[l].row0 * p->vstep + lv[l].col0;
+    const uint32_t add_xy = ((uint32_t)lv[l].col0 << 12) | (uint32_t)lv[l].row0;   // README.md:78
+    PCHK(launch_extract(c, score + off, p->vstep, pyr_bytes, batch, p->border, p->log_bucket_size,
+                        p->bucket_limit, lv[l].width, lv[l].height, kp, (size_t)p->max_keypoints,
+                        (uint32_t)p->max_keypoints, add_xy, counts));
+  }
+  HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
+  hipLaunchKernelGGL(pk::k_orb<0>, dim3(cdiv(p->max_keypoints, 4), 1, batch), dim3(256), 0, c->stream,
+                     pyramids, p->vstep, stride, kp, (size_t)p->max_keypoints, counts, 0u,
+                     (uint32_t)p->max_keypoints, p->words, desc, (size_t)p->max_keypoints * p->words,
+                     (int32_t *)nullptr, (const uint8_t *)nullptr);
+  return launch_ok(c, "k_orb<batch>");
+}
+
 }  // namespace
 
-// Host-only: build the strip plan (and the bucket selection plan) for these parameters exactly as a batch call would —
-// no device, no allocation, no launch — and check its invariants.  For the sanitizer runs of the host code (tests/
-// test_sanitizers.py runs thousands of random level tables through it in a library built with -fsanitize=address,undefined)
-// and for tools that want to know what a call will launch.  options: "key=value,key=value" (pislam_ctx_set_option keys).
-// summary: [0] plan entries, [1] strips per pyramid, [2] runs per pyramid, [3] staging slots per pyramid, [4] run length,
-// [5] LDS bytes (plain layout), [6] LDS bytes (aliased layout), [7] units of the selection pass (0: none).
+// Host-only: plan a batch call for these parameters with the call's own planner (plan_frontend: no device, no allocation,
+// no launch) and check the invariants of its strip plan and bucket selection plan.  For the sanitizer runs of the host code
+// (tests/test_sanitizers.py runs thousands of random level tables through it in a library built with -fsanitize=address,
+// undefined) and for tools that want to know what a call will launch.  options: "key=value,key=value" (pislam_ctx_set_option
+// keys).  summary: [0] plan entries, [1] strips per pyramid, [2] runs per pyramid, [3] staging slots per pyramid, [4] run
+// length, [5] LDS bytes (plain layout), [6] LDS bytes (aliased layout), [7] units of the selection pass (0: none).
 PISLAM_EXPORT int pislam_debug_build_plan(const pislam_frontend_params *p, const pislam_level *lv, int batch, int num_cus,
                                           int lanes_in_flight, const char *options, uint32_t summary[8], char *err, size_t err_cap) {
   pislam_ctx c;                                       // (never touches a device: plain members only)
@@ -1940,15 +2039,15 @@ PISLAM_EXPORT int pislam_debug_build_plan(const pislam_frontend_params *p, const
     if (rc != PISLAM_OK) return say(rc);
     q += len + (e ? 1 : 0);
   }
-  int rc = check_params(&c, p, lv, batch);
+  const int rc = check_params(&c, p, lv, batch);
   if (rc != PISLAM_OK) return say(rc);
-  pf::FusedParams F;
-  size_t lds = 0, lds_alias = 0;
-  const int nsub = choose_sub_batches(&c, p, batch);
-  if (c.opt_pipeline == 1 || !build_fused_plan(&c, p, lv, sub_max(batch, nsub), &F, &lds, &lds_alias)) {
+  FrontendPlan P;
+  const int plan_rc = plan_frontend(&c, p, lv, batch, &P);
+  if (!P.fused) {
     c.err = "no strip plan for these parameters (the staged pipeline takes the call)";
     return say(PISLAM_ERR_INVALID);
   }
+  const pf::FusedParams &F = P.F;
   // ---- invariants the kernels rely on ----
   auto bad = [&](const char *what) {
     c.err = std::string("plan invariant violated: ") + what;
@@ -1987,19 +2086,17 @@ PISLAM_EXPORT int pislam_debug_build_plan(const pislam_frontend_params *p, const
     for (int v : seen)
       if (v != 1) return bad("order is not a permutation of the runs");
   }
-  if (lds_alias > 160 * 1024) return bad("aliased LDS size");
+  if (P.lds_alias > 160 * 1024) return bad("aliased LDS size");
   summary[0] = (uint32_t)F.nlevels;
   summary[1] = (uint32_t)F.strips_per_pyr;
   summary[2] = (uint32_t)F.runs_per_pyr;
   summary[3] = (uint32_t)F.slots_per_pyr;
   summary[4] = (uint32_t)F.run_len;
-  summary[5] = (uint32_t)lds;
-  summary[6] = (uint32_t)lds_alias;
-  if (p->log_bucket_size != 0 && F.lbs == 0 && strips > 0) {
-    pf::SelectPlan Q;
-    pf::FusedParams U;
-    rc = build_select_plan(&c, p, F, &Q, &U);
-    if (rc != PISLAM_OK) return say(rc);
+  summary[5] = (uint32_t)P.lds;
+  summary[6] = (uint32_t)P.lds_alias;
+  if (plan_rc != PISLAM_OK) return say(plan_rc);   // (a refusal of the selection plan: reported after the strip plan checks)
+  if (P.sel) {
+    const pf::SelectPlan &Q = P.Q;
     int units = 0, uslots = 0;
     for (int l = 0; l < Q.nlevels; l++) {
       if (Q.unit0[l] != units || Q.uslot0[l] != uslots) return bad("selection plan prefix sums");
@@ -2018,65 +2115,9 @@ PISLAM_EXPORT int pislam_frontend_reserve(pislam_ctx *c, const pislam_frontend_p
                                           const pislam_level *lv, int batch) {
   PCHK(check_params(c, p, lv, batch));
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t pyr_bytes = (size_t)p->rows * p->vstep;
-  bool grew = false;
-  if (c->w_score.ensure(pyr_bytes * batch, &grew) != PISLAM_OK)
-    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(score map)");
-  const bool same_shape = !grew && c->last_batch >= batch && c->last_params.vstep == p->vstep &&
-                          c->last_params.rows == p->rows && c->last_params.nlevels == p->nlevels &&
-                          c->last_params.border == p->border && (int)c->last_levels.size() == p->nlevels &&
-                          memcmp(c->last_levels.data(), lv, sizeof(pislam_level) * p->nlevels) == 0;
-  if (!same_shape) {
-    // Fast.h:42-44: `out` must start as zeros; afterwards the regions fastDetect rewrites are the
-    // only ones that ever change, so the zeroing is needed once per shape.
-    HIPCHK(c, hipMemsetAsync(c->w_score.p, 0, pyr_bytes * batch, c->stream));
-    c->last_params = *p;
-    c->last_levels.assign(lv, lv + p->nlevels);
-    c->last_batch = batch;
-  }
-  size_t maxn = 1;
-  for (int l = 0; l < p->nlevels; l++) {
-    const int ny = lv[l].height - 2 * p->border, nx = lv[l].width - 2 * p->border;
-    if (ny <= 0 || nx <= 0) continue;
-    if (p->log_bucket_size == 0) maxn = std::max<size_t>(maxn, cdiv(ny, 2));
-    else {
-      const int bs = 1 << p->log_bucket_size;
-      maxn = std::max<size_t>(maxn, (size_t)((nx - 1) / bs + 1) * ((ny - 1) / bs + 1));
-    }
-  }
-  if (c->w_cnt.ensure(sizeof(uint32_t) * maxn * batch) != PISLAM_OK ||
-      c->w_off.ensure(sizeof(uint32_t) * maxn * batch) != PISLAM_OK ||
-      (p->log_bucket_size &&
-       c->w_cellkp.ensure(sizeof(uint32_t) * maxn * batch * p->bucket_limit) != PISLAM_OK))
-    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(extract scratch)");
-  // fused pipeline: strip staging, strip counts, overflow list (so that the batch call itself allocates
-  // nothing — it can then be captured into a hipGraph)
-  if (c->opt_pipeline != 1) {
-    pf::FusedParams F;
-    size_t lds = 0, lds_alias = 0;
-    const int nsub = choose_sub_batches(c, p, batch), submax = sub_max(batch, nsub);
-    if (build_fused_plan(c, p, lv, submax, &F, &lds, &lds_alias) && F.strips_per_pyr > 0) {
-      if (c->w_stage.ensure(sizeof(uint32_t) * ((size_t)F.slots_per_pyr * batch + 64)) != PISLAM_OK ||
-          c->w_stripcnt.ensure(sizeof(uint32_t) * (size_t)F.strips_per_pyr * batch) != PISLAM_OK ||
-          (F.orb_in_strip &&
-           c->w_stagedesc.ensure(sizeof(uint32_t) * (size_t)F.strips_per_pyr * batch * pf::QS_SHARED * (size_t)p->words) != PISLAM_OK))
-        return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(fused staging)");
-      if (c->opt_alias && submax <= 65535 && F.strips_per_pyr <= 65535)
-        PCHK(prepare_ovf(c, nsub, 2 + (size_t)F.strips_per_pyr * submax));
-      if (nsub > 1) PCHK(ensure_aux(c, nsub));
-      if (batch <= frame_max_batch(c)) PCHK(ensure_frame_sync(c));
-      if (p->log_bucket_size != 0 && F.lbs == 0) {   // the selection pass's staging (run_fused allocates nothing after this)
-        pf::SelectPlan Q;
-        pf::FusedParams U;
-        PCHK(build_select_plan(c, p, F, &Q, &U));
-        if (c->w_ustage.ensure(sizeof(uint32_t) * (size_t)Q.uslots_per_pyr * batch) != PISLAM_OK ||
-            c->w_ucount.ensure(sizeof(uint32_t) * (size_t)Q.units_per_pyr * batch) != PISLAM_OK)
-          return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(bucket selection staging)");
-        PCHK(ensure_unit_table(c, p, F, Q));
-      }
-    }
-  }
-  return PISLAM_OK;
+  FrontendPlan P;
+  PCHK(plan_frontend(c, p, lv, batch, &P));
+  return reserve_frontend(c, p, lv, P, batch);
 }
 
 PISLAM_EXPORT int pislam_orb_frontend_batch(pislam_ctx *c, const pislam_frontend_params *p,
@@ -2084,72 +2125,30 @@ PISLAM_EXPORT int pislam_orb_frontend_batch(pislam_ctx *c, const pislam_frontend
                                             size_t stride, int batch, uint32_t *kp, uint32_t *desc,
                                             uint32_t *counts) {
   PCHK(check_params(c, p, lv, batch));
+  HIPCHK(c, hipSetDevice(c->device));
   PCHK(check_frame_poison(c));
   if (!pyramids || !kp || !desc || !counts) return fail(c, PISLAM_ERR_INVALID, "null pointer");
   if (stride < (size_t)p->rows * p->vstep) return fail(c, PISLAM_ERR_INVALID, "pyramid_stride too small");
   if (!is_device_ptr(pyramids) || !is_device_ptr(kp) || !is_device_ptr(desc) || !is_device_ptr(counts))
     return fail(c, PISLAM_ERR_INVALID, "the batch path takes device pointers only");
-  PCHK(pislam_frontend_reserve(c, p, lv, batch));
-  const size_t pyr_bytes = (size_t)p->rows * p->vstep;
-  uint8_t *score = c->w_score.as<uint8_t>();
-  c->last_stride = pyr_bytes;
-  pf::FusedParams F;
-  size_t lds = 0;
-  size_t lds_alias = 0;
-  const int nsub = choose_sub_batches(c, p, batch);
-  bool fused = c->opt_pipeline != 1 && build_fused_plan(c, p, lv, sub_max(batch, nsub), &F, &lds, &lds_alias);
-  if (c->opt_pipeline >= 2 && !fused)
+  FrontendPlan P;
+  PCHK(plan_frontend(c, p, lv, batch, &P));
+  if (c->opt_pipeline >= 2 && !P.fused)
     return fail(c, PISLAM_ERR_INVALID, "fused pipeline unavailable for these parameters (bucket size / LDS size)");
-  c->last_pipeline = fused ? 2 : 1;
-  c->last_path = fused ? PISLAM_PATH_FUSED : PISLAM_PATH_STAGED;
+  PCHK(reserve_frontend(c, p, lv, P, batch));
+  c->last_stride = (size_t)p->rows * p->vstep;
+  c->last_pipeline = P.fused ? 2 : 1;
+  c->last_path = P.fused ? PISLAM_PATH_FUSED : PISLAM_PATH_STAGED;
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  if (fused && F.strips_per_pyr == 0) {            // every level is smaller than 2 x border: nothing to extract
+  if (P.fused && P.F.strips_per_pyr == 0) {          // every level is smaller than 2 x border: nothing to extract
     HIPCHK(c, hipMemsetAsync(counts, 0, sizeof(uint32_t) * batch, c->stream));
     for (int i = 1; i < 4; i++) HIPCHK(c, hipEventRecord(c->ev[i], c->stream));
     c->timing_valid = true;
     c->last_strips = 0;
     return PISLAM_OK;
   }
-  if (fused) {
-    PCHK(run_fused(c, p, F, lds, lds_alias, pyramids, stride, batch, nsub, kp, desc, counts));
-  } else {
-  HIPCHK(c, hipMemsetAsync(counts, 0, sizeof(uint32_t) * batch, c->stream));
-  // The score map workspace is laid out with stride pyr_bytes; the image with `stride`.  The stage
-  // kernels take one stride for both, so when they differ fall back to per-pyramid launches.
-  const bool same = stride == pyr_bytes;
-  for (int l = 0; l < p->nlevels; l++) {
-    const size_t off = (size_t)lv[l].row0 * p->vstep + lv[l].col0;
-    if (same) {
-      PCHK(launch_detect(c, pyramids + off, score + off, p->vstep, pyr_bytes, batch, p->border,
-                         lv[l].width, lv[l].height, p->fast_threshold));
-      PCHK(launch_harris(c, pyramids + off, score + off, p->vstep, pyr_bytes, batch, p->border,
-                         lv[l].width, lv[l].height, p->harris_threshold));
-    } else {
-      for (int b = 0; b < batch; b++) {
-        PCHK(launch_detect(c, pyramids + b * stride + off, score + b * pyr_bytes + off, p->vstep, 0, 1,
-                           p->border, lv[l].width, lv[l].height, p->fast_threshold));
-        PCHK(launch_harris(c, pyramids + b * stride + off, score + b * pyr_bytes + off, p->vstep, 0, 1,
-                           p->border, lv[l].width, lv[l].height, p->harris_threshold));
-      }
-    }
-  }
-  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-  for (int l = 0; l < p->nlevels; l++) {
-    const size_t off = (size_t)lv[l].row0 * p->vstep + lv[l].col0;
-    const uint32_t add_xy = ((uint32_t)lv[l].col0 << 12) | (uint32_t)lv[l].row0;   // README.md:78
-    PCHK(launch_extract(c, score + off, p->vstep, pyr_bytes, batch, p->border, p->log_bucket_size,
-                        p->bucket_limit, lv[l].width, lv[l].height, kp, (size_t)p->max_keypoints,
-                        (uint32_t)p->max_keypoints, add_xy, counts));
-  }
-  HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-  }
-  if (!fused) {
-    hipLaunchKernelGGL(pk::k_orb<0>, dim3(cdiv(p->max_keypoints, 4), 1, batch), dim3(256), 0, c->stream,
-                       pyramids, p->vstep, stride, kp, (size_t)p->max_keypoints, counts, 0u,
-                       (uint32_t)p->max_keypoints, p->words, desc, (size_t)p->max_keypoints * p->words,
-                       (int32_t *)nullptr, (const uint8_t *)nullptr);
-    PCHK(launch_ok(c, "k_orb<batch>"));
-  }
+  PCHK(P.fused ? run_fused(c, p, P, pyramids, stride, batch, kp, desc, counts)
+               : run_staged(c, p, lv, pyramids, stride, batch, kp, desc, counts));
   HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
   c->timing_valid = true;
   return PISLAM_OK;

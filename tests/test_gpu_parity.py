@@ -880,6 +880,57 @@ def test_first_bucket_mode_call_after_reserve_is_capturable(gpu_ctx, orc):
         assert c[b] == len(okp) and (kk[b, :len(okp)] == okp).all() and (dd[b, :len(okp)] == odesc).all(), b
 
 
+def test_first_call_of_every_fused_path_after_reserve_is_capturable(gpu_ctx, orc):
+    """pislam_frontend_reserve and the batch call size the workspace from one plan, so after a reserve the first call of ANY
+    configuration allocates nothing.  For every path whose workspace differs (three launches, one launch, buckets in the
+    strips, orb_in_strip, alias 0, two sub-batches, generic ORB): a fresh context runs one call of another shape (module
+    load), sets the options, reserves, captures its first call of that configuration, replays it and matches the oracle."""
+    import torch
+    from pislam_amd import synth
+    from pislam_amd.capi import Context
+    from pislam_amd.frontend import OrbFrontend as FE
+    levels, small = synth.level_table(), synth.level_table(320, 240, 4)
+    rows = synth.pyramid_rows(levels)
+    dev = torch.device("cuda:0")
+    side = torch.cuda.Stream(dev)
+    d_small = torch.from_numpy(synth.make_batch(0, 3, w0=320, h0=240, nlevels=4, levels=small)).to(dev)
+    cases = [  # name, batch, options, (log_bucket_size, bucket_limit), vstep, path
+        ("three launches", 4, {}, (0, 5), 640, FE.PATH_FUSED),
+        ("one launch", 1, {}, (0, 5), 640, FE.PATH_FUSED | FE.PATH_ONE_LAUNCH),
+        ("buckets in strips", 3, {"bucket_select": 0}, (4, 3), 640, FE.PATH_FUSED | FE.PATH_BUCKETS_IN_STRIPS),
+        ("orb_in_strip", 3, {"orb_in_strip": 1}, (0, 5), 640, FE.PATH_FUSED),
+        ("alias 0", 3, {"alias": 0}, (0, 5), 640, FE.PATH_FUSED),
+        ("sub_batches 2", 4, {"sub_batches": 2}, (0, 5), 640, FE.PATH_FUSED),
+        ("generic ORB", 3, {}, (0, 5), 648, FE.PATH_FUSED | FE.PATH_GENERIC_ORB),
+    ]
+    for i, (name, batch, options, (lbs, limit), vstep, path) in enumerate(cases):
+        pyr = synth.make_batch(70 + 8 * i, batch, vstep=vstep, levels=levels)
+        d_pyr = torch.from_numpy(pyr).to(dev)
+        with torch.cuda.stream(side):
+            ctx = Context(device=0, stream=side.cuda_stream)
+            fe0 = FE(small, vstep=320, rows=synth.pyramid_rows(small), max_keypoints=2048, ctx=ctx)
+            fe0(d_small, *fe0.alloc_outputs(3, dev))
+            for k, v in options.items():
+                ctx.set_option(k, v)
+            fe = FE(levels, vstep=vstep, rows=rows, max_keypoints=4096, ctx=ctx, log_bucket_size=lbs, bucket_limit=limit)
+            fe.reserve(batch)
+            kp, desc, counts = fe.alloc_outputs(batch, dev)
+            side.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side):
+                fe(d_pyr, kp, desc, counts)             # the first call of this configuration on the context
+            g.replay()
+            side.synchronize()
+        assert fe.last_path() == path, (name, fe.last_path())
+        c = counts.cpu().numpy().view(np.uint32)
+        kk, dd = kp.cpu().numpy().view(np.uint32), desc.cpu().numpy().view(np.uint32)
+        for b in range(batch):
+            okp, odesc, _ = orc.pyramid(pyr[b], levels, log_bucket=lbs, bucket_limit=limit)
+            assert c[b] == len(okp) and (kk[b, :len(okp)] == okp).all() and (dd[b, :len(okp)] == odesc).all(), (name, b)
+        del g
+        ctx.close()
+
+
 def test_dense_input_takes_the_overflow_pass_and_stays_exact(gpu_ctx, orc, frame):
     """Level 0: isolated bright dots on the lattice spanned by (4, 0) and (2, 1) — no lattice point lies on another's
     FAST ring, so every dot is a corner: one pixel in four, more than the fast path's on-chip corner queue (at most 4096
