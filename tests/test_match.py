@@ -89,6 +89,35 @@ def test_gpu_matcher_structured_bits(gpu_ctx, orc, match_kernel):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("words", [1, 8])
+def test_gpu_matcher_at_the_largest_16_bit_train_index(gpu_ctx, orc, match_kernel, words):
+    """nt = 65535, the largest train count the matcher takes: best matches and ties planted at train indices above
+    65000, the last one (65534) included."""
+    from pislam_amd import frontend
+    rng = np.random.default_rng(65535 + words)
+    nt, nq = 65535, 300
+    t = rng.integers(0, 2**32, size=(nt, words), dtype=np.uint64).astype(np.uint32)
+    q = rng.integers(0, 2**32, size=(nq, words), dtype=np.uint64).astype(np.uint32)
+    flip = lambda bits: np.array([bits] + [0] * (words - 1), np.uint32)     # bits of word 0
+    t[65533] = t[65001]                        # a tie above 65000: the smaller index wins
+    q[0] = t[65534]                            # exact match at the last index
+    q[1] = t[65534] ^ flip(1)                  # distance 1 to the last index
+    q[2] = t[65533]                            # exact tie 65001 / 65533
+    q[3] = t[65002] ^ flip(3)                  # distance 2 to 65002 and 3 ...
+    t[65527] = t[65002] ^ flip(4)              # ... to 65527: second best
+    q[299] = t[65534]
+    got = frontend.matchHamming(q, t, ctx=gpu_ctx)
+    exp = orc.match_hamming(q, t)
+    for g, e in zip(got, exp):
+        assert (g == e).all()
+    idx, dist, dist2 = got
+    assert idx[0] == 65534 and dist[0] == 0 and idx[1] == 65534 and dist[1] == 1
+    assert idx[2] == 65001 and dist[2] == 0 and dist2[2] == 0
+    assert idx[3] == 65002 and dist[3] == 2 and dist2[3] == 3
+    assert idx[299] == 65534 and dist[299] == 0
+
+
+@pytest.mark.gpu
 def test_gpu_matcher_rejects_bad_arguments(gpu_ctx):
     from pislam_amd.capi import PislamError
     from pislam_amd import frontend
