@@ -520,6 +520,96 @@ int pislam_match_stereo_batch(pislam_ctx *ctx, int words, const pislam_level *le
                               int batch, int32_t *idx, uint32_t *dist, int32_t *disp_q8, uint32_t *sad,
                               uint32_t *nstereo);
 
+/* ---- bag of words: quantisation, vector, word-guided matching ----------- */
+
+/* Matching without a position (relocalisation, loop closure, key frames
+ * without a pose), after DBoW2 / ORB-SLAM's SearchByBoW, stated in integers
+ * (DESIGN.md, section 5.5).  The reference ships neither a vocabulary nor a
+ * matcher: the semantics are this library's own.
+ *
+ * The vocabulary is a rooted tree of `nnodes` cluster centres given by HOST
+ * arrays: node_desc [nnodes][words], first_child [nnodes], child_count
+ * [nnodes].  Node 0 is the root (its descriptor is ignored); the children of
+ * node n are the nodes first_child[n] .. first_child[n] + child_count[n] - 1;
+ * child_count[n] == 0 makes n a leaf (its first_child is ignored).
+ * Refused with PISLAM_ERR_INVALID: words not in {1,2,4,8}; nnodes outside
+ * 2 .. 2^24; a child_count outside 0 .. 32; the root a leaf; a child range that
+ * leaves [1, nnodes), that does not lie strictly after its parent
+ * (first_child[n] > n) or that overlaps another node's range; a node other
+ * than the root that is nobody's child; a leaf deeper than 16 (root = depth
+ * 0); group_depth outside 0 .. 16.
+ *   Word id:  the leaves numbered 0 .. nwords - 1 in ascending node index.
+ *   Group id: every node at depth group_depth and every leaf shallower than
+ *             that, numbered 0 .. ngroups - 1 in ascending node index; the group
+ *             of a word is the one of these nodes on its path.  (group_depth 0:
+ *             one group, the root; a group_depth at or below the deepest leaf:
+ *             groups = words.  ORB-SLAM's levelsup = 4 on its 10-ary, 6-level
+ *             vocabulary is group_depth 2: 100 groups.)
+ * pislam_vocab_create validates, repacks and uploads on the context's device
+ * and stream and synchronises; the host arrays are not referenced afterwards.
+ * A vocabulary is immutable and may be used by any context of the same device;
+ * destroy it after the work that uses it has completed.  pislam_vocab_nwords /
+ * _ngroups: the counts (PISLAM_ERR_INVALID for NULL). */
+typedef struct pislam_vocab pislam_vocab;
+int pislam_vocab_create(pislam_ctx *ctx, int words, int nnodes, const uint32_t *node_desc,
+                        const int32_t *first_child, const int32_t *child_count, int group_depth,
+                        pislam_vocab **vocab);
+int pislam_vocab_destroy(pislam_vocab *vocab);
+int pislam_vocab_nwords(const pislam_vocab *vocab);
+int pislam_vocab_ngroups(const pislam_vocab *vocab);
+
+/* Quantisation.  For pyramid b and every i < n_b = min(counts[b], stride)
+ * (PISLAM_COUNT_INVALID counts as 0): start at the root; at an inner node n go
+ * to the child c that minimises
+ *   hamming(desc[b][i], node_desc[c]) << 8 | (c - first_child[n])
+ * (ties: the smallest child index); stop at a leaf.  word[b][i] = the leaf's
+ * word id, group[b][i] = its group id, wdist[b][i] = the Hamming distance to
+ * the leaf's descriptor; group and wdist may each be NULL.  Layouts
+ * [batch][stride]; desc [batch][stride][words] with the vocabulary's words, as
+ * pislam_orb_frontend_batch writes it.  Entries at and beyond n_b are not
+ * written.  Device pointers only; a host pointer, a NULL desc / counts / word or
+ * a vocabulary of another device: PISLAM_ERR_INVALID before anything is
+ * launched or written.  Asynchronous on the context stream; no workspace, so
+ * the call can be captured into a hipGraph as it is. */
+int pislam_bow_transform_batch(pislam_ctx *ctx, const pislam_vocab *vocab, const uint32_t *desc,
+                               const uint32_t *counts, size_t stride, int batch,
+                               uint32_t *word, uint32_t *group, uint32_t *wdist);
+
+/* The bag-of-words vector.  bow_word[b][0 .. bow_n[b]) = the distinct values
+ * of word[b][0 .. n_b) in ascending order, bow_tf[b][k] = how often
+ * bow_word[b][k] occurs, bow_n[b] = their number; slots at and beyond bow_n[b]
+ * are not written.  Layouts [batch][stride], bow_n [batch]; stride <= 16384
+ * (one workgroup sorts a pyramid's words in LDS), more is refused.  Any uint32
+ * is a word here.  Weights (idf), normalisation and scores are the caller's.
+ * Device pointers only; asynchronous on the context stream; no workspace. */
+int pislam_bow_vector_batch(pislam_ctx *ctx, const uint32_t *word, const uint32_t *counts, size_t stride, int batch,
+                            uint32_t *bow_word, uint32_t *bow_tf, uint32_t *bow_n);
+
+/* Word-guided matching.  Pairs, counts, descriptor and output layouts as
+ * pislam_match_hamming_window_batch; qgroup [batch][q_stride] and tgroup
+ * [batch][t_stride] are group ids as pislam_bow_transform_batch writes them.
+ * Train j is a candidate for query i of the same pair iff
+ * qgroup[b][i] == tgroup[b][j] and both are below ngroups; an id at or above
+ * ngroups has no candidates and is not indexed.  Outputs as
+ * pislam_match_hamming_window_batch, restricted to these candidates (best on
+ * dist << 16 | j: ties go to the smallest train index; idx -1 and dist
+ * 0xffffffff without candidates; dist2 0xffffffff with fewer than 2); entries
+ * at and beyond nq_b are not written.  With ngroups 1 and every group 0 the
+ * outputs equal pislam_match_hamming_batch's.
+ * words in {1,2,4,8}; 1 <= ngroups <= 16384; t_stride <= 65535.  Anything
+ * else, or a host pointer where a device pointer is required:
+ * PISLAM_ERR_INVALID, before anything is launched or written.  Device
+ * pointers only.  Asynchronous on the context stream; the workspace is the
+ * context's own (no other matcher's) and grows on demand, which synchronises;
+ * after pislam_match_bow_reserve of the same or a larger shape the call
+ * allocates nothing and never synchronises, so it can be captured into a
+ * hipGraph. */
+int pislam_match_bow_reserve(pislam_ctx *ctx, int words, int ngroups, size_t t_stride, int batch);
+int pislam_match_hamming_bow_batch(pislam_ctx *ctx, int words, int ngroups,
+                                   const uint32_t *qdesc, const uint32_t *qgroup, const uint32_t *qcounts, size_t q_stride,
+                                   const uint32_t *tdesc, const uint32_t *tgroup, const uint32_t *tcounts, size_t t_stride,
+                                   int batch, int32_t *idx, uint32_t *dist, uint32_t *dist2);
+
 /* ---- multi-GPU: one process per GPU, pyramids sharded, ONE collective ---- */
 
 /* The reference is a single-threaded per-frame loop without cross-frame state

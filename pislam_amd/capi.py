@@ -99,6 +99,14 @@ SYMBOLS = {
     "pislam_match_stereo_batch": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),
                                        ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(StereoParams), _vp, _vp, _i, _i,
                                        _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pislam_vocab_create": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, ctypes.POINTER(_vp)]),
+    "pislam_vocab_destroy": (_i, [_vp]),
+    "pislam_vocab_nwords": (_i, [_vp]),
+    "pislam_vocab_ngroups": (_i, [_vp]),
+    "pislam_bow_transform_batch": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp]),
+    "pislam_bow_vector_batch": (_i, [_vp, _vp, _vp, _sz, _i, _vp, _vp, _vp]),
+    "pislam_match_bow_reserve": (_i, [_vp, _i, _i, _sz, _i]),
+    "pislam_match_hamming_bow_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp]),
     "pislam_dist_shard": (_i, [_i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "pislam_dist_get_unique_id": (_i, [ctypes.c_char_p]),
     "pislam_dist_init": (_i, [_vp, ctypes.c_char_p, _i, _i]),

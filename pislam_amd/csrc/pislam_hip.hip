@@ -53,6 +53,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 
 #include "pislam_prep_kernels.h"
 #include "pislam_match_kernels.h"
+#include "pislam_bow_kernels.h"
 
 #define PISLAM_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -112,6 +113,7 @@ struct pislam_ctx {
     DevBuf off, meta, desc;
   };
   CellIndex w_win, w_sc, w_st;
+  CellIndex w_bow;                   // word-guided matcher (pb::k_bow_index): group offsets, group-sorted indices (meta), descriptors
   // Host-built plan tables the kernels read instead of walking the plan (the bucket selection pass's unit table): one
   // device buffer per distinct CONTENT, never rewritten in place — a captured graph keeps reading the table
   // of the plan it was captured with whatever other shapes the context serves in between.  At most 16 are kept (the oldest
@@ -510,7 +512,7 @@ PISLAM_EXPORT int pislam_ctx_destroy(pislam_ctx *c) {
                     &c->w_off, &c->w_total, &c->w_cellkp, &c->w_score, &c->w_stage, &c->w_stripcnt, &c->w_work, &c->w_prof, &c->w_ovf,
                     &c->w_stagedesc, &c->w_ustage, &c->w_ucount, &c->w_sync, &c->w_chain})
     b->release();
-  for (pislam_ctx::CellIndex *w : {&c->w_win, &c->w_sc, &c->w_st})
+  for (pislam_ctx::CellIndex *w : {&c->w_win, &c->w_sc, &c->w_st, &c->w_bow})
     for (DevBuf *b : {&w->off, &w->meta, &w->desc}) b->release();
   for (auto *t : c->plan_tables) {
     t->dev.release();
@@ -2599,6 +2601,194 @@ PISLAM_EXPORT int pislam_match_stereo_batch(pislam_ctx *c, int words, const pisl
     PCHK(launch_ok(c, "k_stereo_median"));
   }
   return PISLAM_OK;
+}
+
+// ---- bag of words: vocabulary tree, quantisation, vector, word-guided matching ---------------
+
+struct pislam_vocab {
+  int device = 0;
+  int words = 0, nnodes = 0, nwords = 0, ngroups = 0;
+  DevBuf desc, meta;   // pb::k_bow_descend's node records: descriptors [nnodes][words], (first | word, count | group << 8) [nnodes]
+};
+
+PISLAM_EXPORT int pislam_vocab_create(pislam_ctx *c, int words, int nnodes, const uint32_t *node_desc,
+                                      const int32_t *first_child, const int32_t *child_count, int group_depth,
+                                      pislam_vocab **vocab) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!vocab) return fail(c, PISLAM_ERR_INVALID, "null vocabulary pointer");
+  *vocab = nullptr;
+  if (words != 1 && words != 2 && words != 4 && words != 8) return fail(c, PISLAM_ERR_INVALID, "words must be 1, 2, 4 or 8");
+  if (nnodes < 2 || nnodes > (1 << 24)) return fail(c, PISLAM_ERR_INVALID, "nnodes must be 2..2^24");
+  if (group_depth < 0 || group_depth > pb::BOW_MAX_DEPTH) return fail(c, PISLAM_ERR_INVALID, "group_depth must be 0..16");
+  if (!node_desc || !first_child || !child_count) return fail(c, PISLAM_ERR_INVALID, "null node_desc / first_child / child_count");
+  // children lie strictly after their parent, so one ascending pass sees a parent before its children
+  std::vector<int32_t> parent((size_t)nnodes, -1);
+  for (int n = 0; n < nnodes; n++) {
+    const int64_t cc = child_count[n], fc = first_child[n];
+    if (cc < 0 || cc > pb::BOW_MAX_CHILDREN) return fail(c, PISLAM_ERR_INVALID, "child_count must be 0..32");
+    if (cc == 0) continue;
+    if (fc <= n || fc < 1 || fc + cc > nnodes)
+      return fail(c, PISLAM_ERR_INVALID, "a child range must lie after its parent and inside [1, nnodes)");
+    for (int64_t k = fc; k < fc + cc; k++) {
+      if (parent[(size_t)k] >= 0) return fail(c, PISLAM_ERR_INVALID, "child ranges overlap");
+      parent[(size_t)k] = n;
+    }
+  }
+  if (child_count[0] == 0) return fail(c, PISLAM_ERR_INVALID, "the root must not be a leaf");
+  for (int n = 1; n < nnodes; n++)
+    if (parent[(size_t)n] < 0) return fail(c, PISLAM_ERR_INVALID, "a node other than the root is nobody's child");
+  std::vector<uint8_t> depth((size_t)nnodes, 0);
+  std::vector<uint2> meta((size_t)nnodes);
+  std::vector<uint32_t> grp((size_t)nnodes, 0);       // group id of the nodes at and below the group nodes
+  int nwords = 0, ngroups = 0;
+  for (int n = 0; n < nnodes; n++) {
+    const int d = n ? depth[(size_t)parent[(size_t)n]] + 1 : 0;
+    if (d > pb::BOW_MAX_DEPTH) return fail(c, PISLAM_ERR_INVALID, "the tree is deeper than 16");
+    depth[(size_t)n] = (uint8_t)d;
+    const bool leaf = child_count[n] == 0;
+    if (d == group_depth || (leaf && d < group_depth))
+      grp[(size_t)n] = (uint32_t)ngroups++;
+    else if (d > group_depth)
+      grp[(size_t)n] = grp[(size_t)parent[(size_t)n]];
+    meta[(size_t)n] = leaf ? make_uint2((uint32_t)nwords++, grp[(size_t)n] << 8)
+                           : make_uint2((uint32_t)first_child[n], (uint32_t)child_count[n]);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  pislam_vocab *v = new pislam_vocab();
+  v->device = c->device;
+  v->words = words, v->nnodes = nnodes, v->nwords = nwords, v->ngroups = ngroups;
+  const size_t dbytes = sizeof(uint32_t) * (size_t)words * nnodes, mbytes = sizeof(uint2) * (size_t)nnodes;
+  if (v->desc.ensure(dbytes) != PISLAM_OK || v->meta.ensure(mbytes) != PISLAM_OK) {
+    v->desc.release(), v->meta.release();
+    delete v;
+    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(vocabulary)");
+  }
+  hipError_t e = hipMemcpyAsync(v->desc.p, node_desc, dbytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(v->meta.p, meta.data(), mbytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (the host arrays may go away after the call)
+  if (e != hipSuccess) {
+    v->desc.release(), v->meta.release();
+    delete v;
+    return fail(c, PISLAM_ERR_HIP, "vocabulary upload", e);
+  }
+  *vocab = v;
+  return PISLAM_OK;
+}
+
+PISLAM_EXPORT int pislam_vocab_destroy(pislam_vocab *v) {
+  if (!v) return PISLAM_ERR_INVALID;
+  (void)hipSetDevice(v->device);
+  v->desc.release(), v->meta.release();
+  delete v;
+  return PISLAM_OK;
+}
+
+PISLAM_EXPORT int pislam_vocab_nwords(const pislam_vocab *v) { return v ? v->nwords : PISLAM_ERR_INVALID; }
+PISLAM_EXPORT int pislam_vocab_ngroups(const pislam_vocab *v) { return v ? v->ngroups : PISLAM_ERR_INVALID; }
+
+PISLAM_EXPORT int pislam_bow_transform_batch(pislam_ctx *c, const pislam_vocab *v, const uint32_t *desc,
+                                             const uint32_t *counts, size_t stride, int batch, uint32_t *word,
+                                             uint32_t *group, uint32_t *wdist) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!v) return fail(c, PISLAM_ERR_INVALID, "null vocabulary");
+  if (v->device != c->device) return fail(c, PISLAM_ERR_INVALID, "the vocabulary lives on another device");
+  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
+  if (stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "stride too large");
+  if (group && !is_device_ptr(group)) return fail(c, PISLAM_ERR_INVALID, "group must be a device pointer or null");
+  if (wdist && !is_device_ptr(wdist)) return fail(c, PISLAM_ERR_INVALID, "wdist must be a device pointer or null");
+  if (batch == 0 || stride == 0) return PISLAM_OK;
+  PCHK(device_ptrs(c, {desc, counts, word}, "the bag-of-words transform takes device pointers only"));
+  HIPCHK(c, hipSetDevice(c->device));
+  const dim3 grid = query_grid(c, stride, pb::BOW_DPW, batch);
+  const uint32_t *nd = v->desc.as<uint32_t>();
+  const uint2 *nm = v->meta.as<uint2>();
+#define PISLAM_BOW_DESCEND(W)                                                                                            \
+  hipLaunchKernelGGL(pb::k_bow_descend<W>, grid, dim3(pb::BOW_THREADS), 0, c->stream, nd, nm, desc, counts, stride, word, \
+                     group, wdist)
+  switch (v->words) {
+    case 1: PISLAM_BOW_DESCEND(1); break;
+    case 2: PISLAM_BOW_DESCEND(2); break;
+    case 4: PISLAM_BOW_DESCEND(4); break;
+    default: PISLAM_BOW_DESCEND(8); break;             // (pislam_vocab_create accepted only 1, 2, 4, 8)
+  }
+#undef PISLAM_BOW_DESCEND
+  return launch_ok(c, "k_bow_descend");
+}
+
+PISLAM_EXPORT int pislam_bow_vector_batch(pislam_ctx *c, const uint32_t *word, const uint32_t *counts, size_t stride,
+                                          int batch, uint32_t *bow_word, uint32_t *bow_tf, uint32_t *bow_n) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
+  if (stride > (size_t)pb::BOW_VEC_MAX) return fail(c, PISLAM_ERR_INVALID, "stride must be at most 16384");
+  if (batch == 0) return PISLAM_OK;
+  if (stride == 0) {                                    // no slot to read or write but the numbers
+    PCHK(device_ptrs(c, {counts, bow_n}, "the bag-of-words vector takes device pointers only"));
+  } else {
+    PCHK(device_ptrs(c, {word, counts, bow_word, bow_tf, bow_n}, "the bag-of-words vector takes device pointers only"));
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipLaunchKernelGGL(pb::k_bow_vector, dim3((unsigned)batch), dim3(pb::BOW_VEC_THREADS), 0, c->stream, word, counts, stride,
+                     bow_word, bow_tf, bow_n);
+  return launch_ok(c, "k_bow_vector");
+}
+
+namespace {
+
+int bow_match_args(pislam_ctx *c, int words, int ngroups, size_t t_stride, int batch) {
+  if (words != 1 && words != 2 && words != 4 && words != 8) return fail(c, PISLAM_ERR_INVALID, "words must be 1, 2, 4 or 8");
+  if (ngroups < 1 || ngroups > pb::BOW_MAX_GROUPS) return fail(c, PISLAM_ERR_INVALID, "ngroups must be 1..16384");
+  if (t_stride > 65535) return fail(c, PISLAM_ERR_INVALID, "at most 65535 train entries per pair");
+  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
+  return PISLAM_OK;
+}
+
+int bow_workspace(pislam_ctx *c, int words, int ngroups, size_t t_stride, int batch) {
+  pislam_ctx::CellIndex &w = c->w_bow;
+  if (w.off.ensure(sizeof(uint32_t) * (size_t)(ngroups + 1) * batch) != PISLAM_OK ||
+      w.meta.ensure(sizeof(uint32_t) * t_stride * batch) != PISLAM_OK ||
+      w.desc.ensure(sizeof(uint32_t) * words * t_stride * batch) != PISLAM_OK)
+    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(word-guided matcher workspace)");
+  return PISLAM_OK;
+}
+
+}  // namespace
+
+PISLAM_EXPORT int pislam_match_bow_reserve(pislam_ctx *c, int words, int ngroups, size_t t_stride, int batch) {
+  if (!c) return PISLAM_ERR_INVALID;
+  PCHK(bow_match_args(c, words, ngroups, t_stride, batch));
+  HIPCHK(c, hipSetDevice(c->device));
+  return bow_workspace(c, words, ngroups, t_stride, batch);
+}
+
+PISLAM_EXPORT int pislam_match_hamming_bow_batch(pislam_ctx *c, int words, int ngroups, const uint32_t *qdesc,
+                                                 const uint32_t *qgroup, const uint32_t *qcounts, size_t q_stride,
+                                                 const uint32_t *tdesc, const uint32_t *tgroup, const uint32_t *tcounts,
+                                                 size_t t_stride, int batch, int32_t *idx, uint32_t *dist,
+                                                 uint32_t *dist2) {
+  if (!c) return PISLAM_ERR_INVALID;
+  PCHK(bow_match_args(c, words, ngroups, t_stride, batch));
+  if (q_stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "q_stride too large");
+  if (batch == 0 || q_stride == 0) return PISLAM_OK;
+  PCHK(device_ptrs(c, {qdesc, qgroup, qcounts, tdesc, tgroup, tcounts, idx, dist, dist2},
+                   "the word-guided matcher takes device pointers only"));
+  HIPCHK(c, hipSetDevice(c->device));
+  PCHK(bow_workspace(c, words, ngroups, t_stride, batch));
+  uint32_t *off = c->w_bow.off.as<uint32_t>(), *eidx = c->w_bow.meta.as<uint32_t>(), *edesc = c->w_bow.desc.as<uint32_t>();
+  hipLaunchKernelGGL(pb::k_bow_index, dim3((unsigned)batch), dim3(pm::WIN_INDEX_THREADS), 0, c->stream, (uint32_t)ngroups,
+                     words, tgroup, tdesc, tcounts, t_stride, off, eidx, edesc);
+  PCHK(launch_ok(c, "k_bow_index"));
+  const dim3 grid = query_grid(c, q_stride, pm::WIN_QPW, batch);
+#define PISLAM_MATCH_BOW(W)                                                                                              \
+  hipLaunchKernelGGL(pb::k_match_bow<W>, grid, dim3(pm::WIN_THREADS), 0, c->stream, (uint32_t)ngroups, qdesc, qgroup,    \
+                     qcounts, q_stride, t_stride, off, eidx, edesc, idx, dist, dist2)
+  switch (words) {
+    case 1: PISLAM_MATCH_BOW(1); break;
+    case 2: PISLAM_MATCH_BOW(2); break;
+    case 4: PISLAM_MATCH_BOW(4); break;
+    default: PISLAM_MATCH_BOW(8); break;               // (bow_match_args accepted only 1, 2, 4, 8)
+  }
+#undef PISLAM_MATCH_BOW
+  return launch_ok(c, "k_match_bow");
 }
 
 // ---- batches in flight: a pipeline of contexts behind one object --------------------------------

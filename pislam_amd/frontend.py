@@ -371,6 +371,145 @@ def matchStereoBatch(lkp, ldesc, lcounts, rkp, rdesc, rcounts, left_pyr, right_p
     return (*out, nstereo)
 
 
+# ---- bag of words: vocabulary tree, quantisation, vector, word-guided matching ----------
+class Vocabulary:
+    """pislam_vocab: a rooted tree of cluster centres from host arrays — node_desc uint32 [nnodes][words] (node 0 is
+    the root, its descriptor is ignored), first_child and child_count int [nnodes] (children are contiguous;
+    child_count 0 = leaf).  Words are the leaves in ascending node index; groups are the nodes at depth `group_depth`
+    plus the leaves shallower than that (include/pislam_hip.h).  Shapes are checked here, the tree by the library."""
+
+    def __init__(self, node_desc, first_child, child_count, group_depth: int, *, ctx: Context | None = None):
+        node_desc = np.ascontiguousarray(node_desc, np.uint32)
+        if node_desc.ndim != 2:
+            raise ValueError("node_desc must be [nnodes][words]")
+        nnodes, words = node_desc.shape
+        if words not in (1, 2, 4, 8):
+            raise ValueError("words must be 1, 2, 4 or 8")
+        first_child = np.ascontiguousarray(first_child, np.int32)
+        child_count = np.ascontiguousarray(child_count, np.int32)
+        if first_child.shape != (nnodes,) or child_count.shape != (nnodes,):
+            raise ValueError(f"first_child and child_count must have one entry per node ({nnodes})")
+        self.h = None
+        self.ctx = ctx or default_context()
+        self.words, self.nnodes, self.group_depth = int(words), int(nnodes), int(group_depth)
+        h = ctypes.c_void_p()
+        self.ctx.check(self.ctx.lib.pislam_vocab_create(self.ctx.h, self.words, self.nnodes, ptr(node_desc),
+                                                        ptr(first_child), ptr(child_count), self.group_depth,
+                                                        ctypes.byref(h)), "pislam_vocab_create")
+        self.h = h
+        self.nwords = int(self.ctx.lib.pislam_vocab_nwords(h))
+        self.ngroups = int(self.ctx.lib.pislam_vocab_ngroups(h))
+
+    @staticmethod
+    def kary_tables(k: int, depth: int):
+        """(first_child, child_count) of the complete k-ary tree with leaves at `depth` in breadth-first order."""
+        if not 1 <= k <= 32 or not 1 <= depth <= 16:
+            raise ValueError("need 1 <= k <= 32 and 1 <= depth <= 16")
+        level = [k ** d for d in range(depth + 1)]
+        nnodes, inner = sum(level), sum(level[:-1])
+        if nnodes > 1 << 24:
+            raise ValueError("more than 2^24 nodes")
+        n = np.arange(nnodes, dtype=np.int64)
+        first = np.where(n < inner, n * k + 1, 0).astype(np.int32)
+        count = np.where(n < inner, k, 0).astype(np.int32)
+        return first, count
+
+    @classmethod
+    def from_kary(cls, node_desc, k: int, depth: int, group_depth: int = 2, *, ctx: Context | None = None):
+        """A complete k-ary tree of `depth` levels below the root, nodes in breadth-first order (node n's children are
+        n * k + 1 .. n * k + k): node_desc [(k^(depth+1) - 1) / (k - 1)][words]."""
+        first, count = cls.kary_tables(k, depth)
+        node_desc = np.asarray(node_desc)
+        if node_desc.ndim != 2 or node_desc.shape[0] != len(first):
+            raise ValueError(f"a {k}-ary tree of depth {depth} has {len(first)} nodes")
+        return cls(node_desc, first, count, group_depth, ctx=ctx)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.pislam_vocab_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bowTransformBatch(vocab: Vocabulary, desc, counts, word=None, group=None, wdist=None, *, want_group=True,
+                      want_wdist=True, ctx: Context | None = None):
+    """Drops every descriptor of device-resident front-end outputs (desc [batch][max_kp][words], counts [batch]) down
+    the vocabulary tree (pislam_bow_transform_batch).  Returns (word, group, wdist) int32 tensors [batch][max_kp]: the
+    leaf's word id, its group id and the Hamming distance to the leaf; group / wdist are None when not wanted
+    (want_group / want_wdist False and no tensor given).  Asynchronous on the ctx stream."""
+    import torch
+    ctx = ctx or default_context()
+    batch, stride, words = desc.shape
+    if words != vocab.words:
+        raise ValueError(f"descriptors have {words} words, the vocabulary {vocab.words}")
+    new = lambda: torch.empty((batch, stride), dtype=torch.int32, device=desc.device)
+    if word is None:
+        word = new()
+    if group is None and want_group:
+        group = new()
+    if wdist is None and want_wdist:
+        wdist = new()
+    ctx.check(ctx.lib.pislam_bow_transform_batch(ctx.h, vocab.h, ptr(desc), ptr(counts), stride, batch, ptr(word),
+                                                 ptr(group), ptr(wdist)), "pislam_bow_transform_batch")
+    return word, group, wdist
+
+
+def bowVectorBatch(word, counts, bow_word=None, bow_tf=None, bow_n=None, *, ctx: Context | None = None):
+    """Bag-of-words vectors of word [batch][stride] (pislam_bow_vector_batch, stride <= 16384): returns (bow_word,
+    bow_tf int32 [batch][stride], bow_n int32 [batch]) — pyramid b's distinct words in ascending order, how often each
+    occurs, and their number; slots at and beyond bow_n[b] are not written.  Asynchronous on the ctx stream."""
+    import torch
+    ctx = ctx or default_context()
+    batch, stride = word.shape
+    if bow_word is None:
+        bow_word = torch.empty((batch, stride), dtype=torch.int32, device=word.device)
+    if bow_tf is None:
+        bow_tf = torch.empty((batch, stride), dtype=torch.int32, device=word.device)
+    if bow_n is None:
+        bow_n = torch.empty((batch,), dtype=torch.int32, device=word.device)
+    ctx.check(ctx.lib.pislam_bow_vector_batch(ctx.h, ptr(word), ptr(counts), stride, batch, ptr(bow_word), ptr(bow_tf),
+                                              ptr(bow_n)), "pislam_bow_vector_batch")
+    return bow_word, bow_tf, bow_n
+
+
+def reserveMatchBow(ngroups: int, t_stride: int, batch: int, *, words=8, ctx: Context | None = None):
+    """Sizes the context's word-guided matcher workspace (pislam_match_bow_reserve): afterwards matchHammingBowBatch of
+    the same or a smaller shape allocates nothing and can be captured into a hipGraph."""
+    ctx = ctx or default_context()
+    ctx.check(ctx.lib.pislam_match_bow_reserve(ctx.h, words, int(ngroups), t_stride, batch), "pislam_match_bow_reserve")
+
+
+def matchHammingBowBatch(qdesc, qgroup, qcounts, tdesc, tgroup, tcounts, ngroups: int, idx=None, dist=None, dist2=None,
+                         *, ctx: Context | None = None):
+    """Word-guided matcher (pislam_match_hamming_bow_batch) on device-resident front-end outputs and the group ids
+    bowTransformBatch wrote for them ([batch][max_kp]): query i of pair b sees the train descriptors of the same
+    group; ids at or above ngroups match nothing.  Returns (idx, dist, dist2) int32 tensors [batch][q_stride] like
+    matchHammingBatch; asynchronous on the ctx stream."""
+    import torch
+    ctx = ctx or default_context()
+    batch, qs, words = qdesc.shape
+    ts = tdesc.shape[1]
+    if tdesc.shape[2] != words:
+        raise ValueError("query and train descriptors differ in words")
+    if tuple(qgroup.shape) != (batch, qs) or tuple(tgroup.shape) != (tdesc.shape[0], ts):
+        raise ValueError("qgroup / tgroup must be [batch][stride] like the descriptors")
+    if idx is None:
+        idx = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
+    if dist is None:
+        dist = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
+    if dist2 is None:
+        dist2 = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
+    ctx.check(ctx.lib.pislam_match_hamming_bow_batch(ctx.h, words, int(ngroups), ptr(qdesc), ptr(qgroup), ptr(qcounts),
+                                                     qs, ptr(tdesc), ptr(tgroup), ptr(tcounts), ts, batch, ptr(idx),
+                                                     ptr(dist), ptr(dist2)), "pislam_match_hamming_bow_batch")
+    return idx, dist, dist2
+
+
 # ---- Gaussian.h:48, Bilinear.h:42, Bilinear.h:165 -------------------------------------
 def gaussian5x5(width, height, img, out, *, ctx: Context | None = None):
     """pislam::gaussian5x5<vstep>(width, height, img, out); img may be out (in place)."""
