@@ -610,6 +610,103 @@ int pislam_match_hamming_bow_batch(pislam_ctx *ctx, int words, int ngroups,
                                    const uint32_t *tdesc, const uint32_t *tgroup, const uint32_t *tcounts, size_t t_stride,
                                    int batch, int32_t *idx, uint32_t *dist, uint32_t *dist2);
 
+/* ---- bag of words: integer weights and the key-frame database ------------ */
+
+/* Place recognition (relocalisation, loop detection), after DBoW2's
+ * Database::query and ORB-SLAM's KeyFrameDatabase::Detect*Candidates, stated
+ * in integers: the step between
+ * pislam_bow_vector_batch and pislam_match_hamming_bow_batch.  The reference
+ * ships nothing of the kind: the semantics are this library's own.
+ *
+ * Weights.  Inputs are what pislam_bow_vector_batch wrote ([batch][stride],
+ * n_b = bow_n[b] clamped to stride, PISLAM_COUNT_INVALID counts as 0;
+ * stride <= 16384).  idf is a DEVICE array [nwords] of the caller's
+ * fixed-point idf (any scale; a value above 65535 counts as 65535); NULL means
+ * 1 for every word.  With a_k = bow_tf[b][k] * idf[bow_word[b][k]] (0 for a word
+ * >= nwords) and A = the sum of a_k over k < n_b, in 64 bits:
+ *   bow_weight[b][k] = A == 0 ? 0 : (a_k << 24) / A      (floor; Q24)
+ * so the weights of a frame sum to at most 2^24.  (The tf of a vector sum to at
+ * most 16384, so a_k and A stay below 2^30; for other inputs the arithmetic is
+ * modulo 2^64.)  Slots at and beyond n_b are not written.  Device pointers
+ * only; asynchronous on the context stream; no workspace. */
+int pislam_bow_weight_batch(pislam_ctx *ctx, const uint32_t *bow_word, const uint32_t *bow_tf, const uint32_t *bow_n,
+                            size_t stride, int batch, const uint32_t *idf, uint32_t nwords, uint32_t *bow_weight);
+
+/* The database holds up to `capacity` key frames (1 .. 2^20) of at most
+ * `stride` entries (word, weight) each (1 .. 16384) over the words
+ * 0 .. nwords - 1 (1 .. 2^24); capacity * stride <= 2^31.  All device memory
+ * (20 bytes per entry of capacity * stride, 12 per word, 5 per key frame) is
+ * allocated by pislam_bowdb_create on the context's device
+ * (PISLAM_ERR_NOMEM when it cannot be had); nothing allocates later.  It may be
+ * used by any context of that device, by one stream at a time.
+ *   add     Frame b of the call becomes key frame id = size + b; ids are never
+ *           reused; *first_id (HOST, may be NULL) = the first.  Inputs as the
+ *           vector and weight calls write them; the add's stride may differ from
+ *           the database's: a bow_n[b] above the database's stride is clamped to
+ *           it (the first entries are kept).  An entry with a word >= nwords is
+ *           stored but not indexed.  Entries need not be sorted.  The id count
+ *           is host state: an add that would pass `capacity`, or any bad
+ *           argument, returns PISLAM_ERR_INVALID before anything is launched
+ *           and leaves the database as it was.  The inverted file (CSR over the
+ *           words) is rebuilt by every add.
+ *   remove  marks ids (HOST array) dead.  An unknown, already dead or repeated
+ *           id: PISLAM_ERR_INVALID, nothing changed.  A dead key frame never
+ *           appears in a result and does not count towards max_common.
+ *   clear   empties the database and restarts ids at 0.
+ *   size    ids handed out so far (removed ones included).
+ * add, remove and clear are asynchronous on the context stream and ordered
+ * against queries on it; they change host state and are not meant to be
+ * captured into a hipGraph.  The number of key frames and the liveness flags
+ * the QUERY reads live in device memory: a captured query replays against the
+ * database as it is at replay time.  Destroy a database after the work that
+ * uses it has completed. */
+typedef struct pislam_bowdb pislam_bowdb;
+int pislam_bowdb_create(pislam_ctx *ctx, uint32_t nwords, size_t stride, int capacity, pislam_bowdb **db);
+int pislam_bowdb_destroy(pislam_bowdb *db);
+int pislam_bowdb_size(const pislam_bowdb *db);
+int pislam_bowdb_add_batch(pislam_ctx *ctx, pislam_bowdb *db, const uint32_t *bow_word, const uint32_t *bow_weight,
+                           const uint32_t *bow_n, size_t stride, int batch, int32_t *first_id);
+int pislam_bowdb_remove(pislam_ctx *ctx, pislam_bowdb *db, const int32_t *ids, int n);
+int pislam_bowdb_clear(pislam_ctx *ctx, pislam_bowdb *db);
+
+/* The query.  For query b (entries i < n_b of q_word / q_weight [batch][stride],
+ * n_b = q_n[b] clamped to stride, stride <= 16384) and every key frame k, over
+ * the words < nwords that both hold (query entry i, entry j of k):
+ *   common[b][k] = the number of such words                         (<= 16384)
+ *   score[b][k]  = the sum over them of min(q_weight[b][i], weight_k[j])  (<= 2^24)
+ * score / 2^24 is DBoW2's L1 score 1 - 0.5 * |v/|v| - w/|w||_1 of the two tf-idf
+ * vectors with every weight floored to Q24.
+ *   eligible   k is alive and k < id_limit[b] (id_limit: DEVICE [batch] or NULL
+ *              = every key frame; a limit <= 0: none).
+ *   max_common[b] = the largest common[b][k] over eligible k (0 without one).
+ *   candidate  k is eligible, common >= 1 and
+ *              common * 100 >= min_common_pct * max_common[b]  (0 .. 100).
+ *   top_id[b][0 .. topk) = the candidates by descending score, ties to the
+ *              smaller id; top_score / top_common their values; with fewer than
+ *              topk candidates the rest of the row is -1 / 0 / 0.  Every row is
+ *              written in full.  topk 1 .. 64; layouts [batch][topk],
+ *              max_common [batch].
+ * These results are defined for frames, on both sides, whose words are
+ * distinct and whose weights sum to at most 2^24: what the vector and weight
+ * calls write.  For other inputs the VALUES are unspecified, but every access
+ * stays in bounds and top_id holds -1 or an eligible id.
+ * Device pointers only; batch 0 .. 65535; anything else, a NULL or host pointer
+ * where a device pointer is required, or a database of another device:
+ * PISLAM_ERR_INVALID before anything is launched or written.  Asynchronous on
+ * the context stream.  The workspace is the context's own (no matcher's) and
+ * grows on demand, which synchronises; after pislam_bowdb_query_reserve of the
+ * same or a larger shape the call allocates nothing and can be captured into a
+ * hipGraph together with the transform, vector, weight and guided match calls.
+ * Workspace bytes (each term rounded up to 256), C = capacity rounded up to
+ * even, S = ceil(capacity / 8192):
+ *   batch * (6 * C + 4)  +  (S > 1 ? 12 * batch * S * topk : 0)
+ * PISLAM_ERR_NOMEM when it cannot be had (the context's workspace is then
+ * empty; a later, smaller call allocates again). */
+int pislam_bowdb_query_reserve(pislam_ctx *ctx, const pislam_bowdb *db, int batch, int topk);
+int pislam_bowdb_query_batch(pislam_ctx *ctx, const pislam_bowdb *db, const uint32_t *q_word, const uint32_t *q_weight,
+                             const uint32_t *q_n, size_t stride, int batch, const int32_t *id_limit, int min_common_pct,
+                             int topk, int32_t *top_id, uint32_t *top_score, uint32_t *top_common, uint32_t *max_common);
+
 /* ---- multi-GPU: one process per GPU, pyramids sharded, ONE collective ---- */
 
 /* The reference is a single-threaded per-frame loop without cross-frame state

@@ -107,6 +107,15 @@ SYMBOLS = {
     "pislam_bow_vector_batch": (_i, [_vp, _vp, _vp, _sz, _i, _vp, _vp, _vp]),
     "pislam_match_bow_reserve": (_i, [_vp, _i, _i, _sz, _i]),
     "pislam_match_hamming_bow_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp]),
+    "pislam_bow_weight_batch": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, ctypes.c_uint32, _vp]),
+    "pislam_bowdb_create": (_i, [_vp, ctypes.c_uint32, _sz, _i, ctypes.POINTER(_vp)]),
+    "pislam_bowdb_destroy": (_i, [_vp]),
+    "pislam_bowdb_size": (_i, [_vp]),
+    "pislam_bowdb_add_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, ctypes.POINTER(ctypes.c_int32)]),
+    "pislam_bowdb_remove": (_i, [_vp, _vp, _vp, _i]),
+    "pislam_bowdb_clear": (_i, [_vp, _vp]),
+    "pislam_bowdb_query_reserve": (_i, [_vp, _vp, _i, _i]),
+    "pislam_bowdb_query_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "pislam_dist_shard": (_i, [_i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "pislam_dist_get_unique_id": (_i, [ctypes.c_char_p]),
     "pislam_dist_init": (_i, [_vp, ctypes.c_char_p, _i, _i]),

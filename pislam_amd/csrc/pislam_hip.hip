@@ -54,6 +54,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_prep_kernels.h"
 #include "pislam_match_kernels.h"
 #include "pislam_bow_kernels.h"
+#include "pislam_bowdb_kernels.h"
 
 #define PISLAM_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -114,6 +115,7 @@ struct pislam_ctx {
   };
   CellIndex w_win, w_sc, w_st;
   CellIndex w_bow;                   // word-guided matcher (pb::k_bow_index): group offsets, group-sorted indices (meta), descriptors
+  DevBuf w_db;                       // key-frame database query (pd::k_db_accumulate .. k_db_merge): accumulator planes, maxima, partial lists
   // Host-built plan tables the kernels read instead of walking the plan (the bucket selection pass's unit table): one
   // device buffer per distinct CONTENT, never rewritten in place — a captured graph keeps reading the table
   // of the plan it was captured with whatever other shapes the context serves in between.  At most 16 are kept (the oldest
@@ -514,6 +516,7 @@ PISLAM_EXPORT int pislam_ctx_destroy(pislam_ctx *c) {
     b->release();
   for (pislam_ctx::CellIndex *w : {&c->w_win, &c->w_sc, &c->w_st, &c->w_bow})
     for (DevBuf *b : {&w->off, &w->meta, &w->desc}) b->release();
+  c->w_db.release();
   for (auto *t : c->plan_tables) {
     t->dev.release();
     delete t;
@@ -2789,6 +2792,242 @@ PISLAM_EXPORT int pislam_match_hamming_bow_batch(pislam_ctx *c, int words, int n
   }
 #undef PISLAM_MATCH_BOW
   return launch_ok(c, "k_match_bow");
+}
+
+// ---- bag of words: integer weights and the key-frame database -----------------------------
+
+PISLAM_EXPORT int pislam_bow_weight_batch(pislam_ctx *c, const uint32_t *bow_word, const uint32_t *bow_tf,
+                                          const uint32_t *bow_n, size_t stride, int batch, const uint32_t *idf,
+                                          uint32_t nwords, uint32_t *bow_weight) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
+  if (stride > (size_t)pd::DB_MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be at most 16384");
+  if (idf && !is_device_ptr(idf)) return fail(c, PISLAM_ERR_INVALID, "idf must be a device pointer or null");
+  if (batch == 0 || stride == 0) return PISLAM_OK;
+  PCHK(device_ptrs(c, {bow_word, bow_tf, bow_n, bow_weight}, "the bag-of-words weights take device pointers only"));
+  HIPCHK(c, hipSetDevice(c->device));
+  hipLaunchKernelGGL(pd::k_bow_weight, dim3((unsigned)batch), dim3(pd::DB_THREADS), 0, c->stream, bow_word, bow_tf, bow_n,
+                     stride, idf, nwords, bow_weight);
+  return launch_ok(c, "k_bow_weight");
+}
+
+struct pislam_bowdb {
+  int device = 0;
+  uint32_t nwords = 0;
+  size_t stride = 0;
+  int capacity = 0;
+  int size = 0;                      // ids handed out (host state: an add is refused before anything is launched)
+  std::vector<uint8_t> alive;        // host mirror of d_alive (pislam_bowdb_remove validates on it)
+  // forward store [capacity][stride], entries per key frame, liveness, the number of key frames as the query reads it
+  DevBuf fwd_word, fwd_weight, fwd_n, d_alive, d_size;
+  // inverted file: entries per word, CSR offsets [nwords + 1], scatter cursors, chunk sums of the scan, postings (id, weight)
+  DevBuf cnt, off, cursor, bsum, post;
+  void release() {
+    for (DevBuf *b : {&fwd_word, &fwd_weight, &fwd_n, &d_alive, &d_size, &cnt, &off, &cursor, &bsum, &post}) b->release();
+  }
+};
+
+namespace {
+
+// Launch shape and workspace layout of a query of `batch` vectors for `topk` results against a database of `capacity`.
+struct DbQueryPlan {
+  uint32_t cap_pad, slice, nslices, nsel;
+  size_t lds, o_score, o_common, o_gmax, o_pkey, o_pcom, bytes;
+};
+
+DbQueryPlan db_query_plan(int capacity, int batch, int topk) {
+  DbQueryPlan P{};
+  const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  P.cap_pad = ((uint32_t)capacity + 1u) & ~1u;
+  P.nslices = (uint32_t)cdiv(capacity, pd::DB_ACC_MAX_SLICE);
+  P.slice = ((uint32_t)cdiv(capacity, (int)P.nslices) + 1u) & ~1u;
+  P.nsel = (uint32_t)cdiv(capacity, pd::DB_SEL_SLICE);
+  P.lds = (size_t)P.slice * 6;
+  const size_t cells = (size_t)batch * P.cap_pad, part = P.nsel > 1 ? (size_t)batch * P.nsel * topk : 0;
+  P.o_score = 0;
+  P.o_common = up(P.o_score + 4 * cells);
+  P.o_gmax = up(P.o_common + 2 * cells);
+  P.o_pkey = up(P.o_gmax + 4 * (size_t)batch);
+  P.o_pcom = up(P.o_pkey + 8 * part);
+  P.bytes = up(P.o_pcom + 4 * part);
+  return P;
+}
+
+int db_query_args(pislam_ctx *c, const pislam_bowdb *db, int batch, int topk) {
+  if (!db) return fail(c, PISLAM_ERR_INVALID, "null database");
+  if (db->device != c->device) return fail(c, PISLAM_ERR_INVALID, "the database lives on another device");
+  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
+  if (topk < 1 || topk > pd::DB_MAX_TOPK) return fail(c, PISLAM_ERR_INVALID, "topk must be 1..64");
+  return PISLAM_OK;
+}
+
+int db_query_workspace(pislam_ctx *c, const DbQueryPlan &P) {
+  if (c->w_db.ensure(P.bytes) != PISLAM_OK) return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(database query workspace)");
+  if (P.lds > 64 * 1024)
+    HIPCHK(c, hipFuncSetAttribute((const void *)pd::k_db_accumulate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds));
+  return PISLAM_OK;
+}
+
+}  // namespace
+
+PISLAM_EXPORT int pislam_bowdb_create(pislam_ctx *c, uint32_t nwords, size_t stride, int capacity, pislam_bowdb **out) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!out) return fail(c, PISLAM_ERR_INVALID, "null database pointer");
+  *out = nullptr;
+  if (nwords < 1 || nwords > (1u << 24)) return fail(c, PISLAM_ERR_INVALID, "nwords must be 1..2^24");
+  if (stride < 1 || stride > (size_t)pd::DB_MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
+  if (capacity < 1 || capacity > pd::DB_MAX_CAPACITY) return fail(c, PISLAM_ERR_INVALID, "capacity must be 1..2^20");
+  const size_t entries = stride * (size_t)capacity;
+  if (entries > ((size_t)1 << 31)) return fail(c, PISLAM_ERR_NOMEM, "more than 2^31 entries (capacity * stride)");
+  HIPCHK(c, hipSetDevice(c->device));
+  pislam_bowdb *db = new pislam_bowdb();
+  db->device = c->device;
+  db->nwords = nwords, db->stride = stride, db->capacity = capacity;
+  db->alive.assign((size_t)capacity, 0);
+  const size_t nchunks = (size_t)cdiv((int)nwords, pd::DB_SCAN_CHUNK);
+  const bool ok = db->fwd_word.ensure(4 * entries) == PISLAM_OK && db->fwd_weight.ensure(4 * entries) == PISLAM_OK &&
+                  db->post.ensure(8 * entries) == PISLAM_OK && db->fwd_n.ensure(4 * (size_t)capacity) == PISLAM_OK &&
+                  db->d_alive.ensure((size_t)capacity) == PISLAM_OK && db->d_size.ensure(4) == PISLAM_OK &&
+                  db->cnt.ensure(4 * (size_t)nwords) == PISLAM_OK && db->off.ensure(4 * ((size_t)nwords + 1)) == PISLAM_OK &&
+                  db->cursor.ensure(4 * (size_t)nwords) == PISLAM_OK && db->bsum.ensure(4 * nchunks) == PISLAM_OK;
+  if (!ok) {
+    db->release();
+    delete db;
+    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(key-frame database)");
+  }
+  hipError_t e = hipMemsetAsync(db->cnt.p, 0, 4 * (size_t)nwords, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(db->d_alive.p, 0, (size_t)capacity, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(db->d_size.p, 0, 4, c->stream);
+  if (e != hipSuccess) {
+    db->release();
+    delete db;
+    return fail(c, PISLAM_ERR_HIP, "database initialisation", e);
+  }
+  *out = db;
+  return PISLAM_OK;
+}
+
+PISLAM_EXPORT int pislam_bowdb_destroy(pislam_bowdb *db) {
+  if (!db) return PISLAM_ERR_INVALID;
+  (void)hipSetDevice(db->device);
+  db->release();
+  delete db;
+  return PISLAM_OK;
+}
+
+PISLAM_EXPORT int pislam_bowdb_size(const pislam_bowdb *db) { return db ? db->size : PISLAM_ERR_INVALID; }
+
+PISLAM_EXPORT int pislam_bowdb_add_batch(pislam_ctx *c, pislam_bowdb *db, const uint32_t *bow_word,
+                                         const uint32_t *bow_weight, const uint32_t *bow_n, size_t stride, int batch,
+                                         int32_t *first_id) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!db) return fail(c, PISLAM_ERR_INVALID, "null database");
+  if (db->device != c->device) return fail(c, PISLAM_ERR_INVALID, "the database lives on another device");
+  if (batch < 0 || batch > db->capacity - db->size) return fail(c, PISLAM_ERR_INVALID, "the add would pass the database's capacity");
+  if (stride > (size_t)pd::DB_MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be at most 16384");
+  if (batch > 0) PCHK(device_ptrs(c, {bow_word, bow_weight, bow_n}, "the key-frame database takes device pointers only"));
+  if (first_id) *first_id = db->size;
+  if (batch == 0) return PISLAM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint32_t first = (uint32_t)db->size, dbs = (uint32_t)db->stride, nw = db->nwords;
+  uint32_t *cnt = db->cnt.as<uint32_t>(), *off = db->off.as<uint32_t>(), *cursor = db->cursor.as<uint32_t>();
+  uint32_t *bsum = db->bsum.as<uint32_t>();
+  hipLaunchKernelGGL(pd::k_db_store, dim3((unsigned)batch), dim3(pd::DB_STORE_THREADS), 0, c->stream, first, dbs, nw,
+                     bow_word, bow_weight, bow_n, stride, db->fwd_word.as<uint32_t>(), db->fwd_weight.as<uint32_t>(),
+                     db->fwd_n.as<uint32_t>(), db->d_alive.as<uint8_t>(), cnt, db->d_size.as<uint32_t>());
+  PCHK(launch_ok(c, "k_db_store"));
+  // the ids are handed out now: the forward store holds them whatever happens to the launches below
+  for (int b = 0; b < batch; b++) db->alive[(size_t)first + b] = 1;
+  db->size += batch;
+  const unsigned nchunks = (unsigned)cdiv((int)nw, pd::DB_SCAN_CHUNK);
+  hipLaunchKernelGGL(pd::k_db_scan_chunks, dim3(nchunks), dim3(pd::DB_THREADS), 0, c->stream, cnt, nw, bsum);
+  PCHK(launch_ok(c, "k_db_scan_chunks"));
+  hipLaunchKernelGGL(pd::k_db_scan_sums, dim3(1), dim3(pd::DB_THREADS), 0, c->stream, nchunks, nw, bsum, off);
+  PCHK(launch_ok(c, "k_db_scan_sums"));
+  hipLaunchKernelGGL(pd::k_db_scan_offsets, dim3(nchunks), dim3(pd::DB_THREADS), 0, c->stream, cnt, nw, bsum, off, cursor);
+  PCHK(launch_ok(c, "k_db_scan_offsets"));
+  hipLaunchKernelGGL(pd::k_db_scatter, dim3((unsigned)db->size), dim3(pd::DB_STORE_THREADS), 0, c->stream, dbs, nw,
+                     db->fwd_word.as<uint32_t>(), db->fwd_weight.as<uint32_t>(), db->fwd_n.as<uint32_t>(), cursor,
+                     db->post.as<uint2>());
+  return launch_ok(c, "k_db_scatter");
+}
+
+PISLAM_EXPORT int pislam_bowdb_remove(pislam_ctx *c, pislam_bowdb *db, const int32_t *ids, int n) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!db) return fail(c, PISLAM_ERR_INVALID, "null database");
+  if (db->device != c->device) return fail(c, PISLAM_ERR_INVALID, "the database lives on another device");
+  if (n < 0 || (n > 0 && !ids)) return fail(c, PISLAM_ERR_INVALID, "null ids");
+  for (int k = 0; k < n; k++) {                         // validate first: nothing changes on an error
+    bool bad = ids[k] < 0 || ids[k] >= db->size || !db->alive[(size_t)ids[k]];
+    for (int j = 0; j < k && !bad; j++) bad = ids[j] == ids[k];
+    if (bad) return fail(c, PISLAM_ERR_INVALID, "unknown, removed or repeated key-frame id");
+  }
+  if (n == 0) return PISLAM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  // (the postings of a removed key frame stay in the inverted file until pislam_bowdb_clear: the query reads the flag)
+  for (int k = 0; k < n; k++) {
+    HIPCHK(c, hipMemsetAsync(db->d_alive.as<uint8_t>() + ids[k], 0, 1, c->stream));
+    db->alive[(size_t)ids[k]] = 0;
+  }
+  return PISLAM_OK;
+}
+
+PISLAM_EXPORT int pislam_bowdb_clear(pislam_ctx *c, pislam_bowdb *db) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!db) return fail(c, PISLAM_ERR_INVALID, "null database");
+  if (db->device != c->device) return fail(c, PISLAM_ERR_INVALID, "the database lives on another device");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemsetAsync(db->d_size.p, 0, 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(db->cnt.p, 0, 4 * (size_t)db->nwords, c->stream));
+  HIPCHK(c, hipMemsetAsync(db->d_alive.p, 0, (size_t)db->capacity, c->stream));
+  std::fill(db->alive.begin(), db->alive.end(), 0);
+  db->size = 0;
+  return PISLAM_OK;
+}
+
+PISLAM_EXPORT int pislam_bowdb_query_reserve(pislam_ctx *c, const pislam_bowdb *db, int batch, int topk) {
+  if (!c) return PISLAM_ERR_INVALID;
+  PCHK(db_query_args(c, db, batch, topk));
+  HIPCHK(c, hipSetDevice(c->device));
+  return db_query_workspace(c, db_query_plan(db->capacity, batch, topk));
+}
+
+PISLAM_EXPORT int pislam_bowdb_query_batch(pislam_ctx *c, const pislam_bowdb *db, const uint32_t *q_word,
+                                           const uint32_t *q_weight, const uint32_t *q_n, size_t stride, int batch,
+                                           const int32_t *id_limit, int min_common_pct, int topk, int32_t *top_id,
+                                           uint32_t *top_score, uint32_t *top_common, uint32_t *max_common) {
+  if (!c) return PISLAM_ERR_INVALID;
+  PCHK(db_query_args(c, db, batch, topk));
+  if (stride > (size_t)pd::DB_MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be at most 16384");
+  if (min_common_pct < 0 || min_common_pct > 100) return fail(c, PISLAM_ERR_INVALID, "min_common_pct must be 0..100");
+  if (id_limit && !is_device_ptr(id_limit)) return fail(c, PISLAM_ERR_INVALID, "id_limit must be a device pointer or null");
+  if (batch == 0) return PISLAM_OK;
+  PCHK(device_ptrs(c, {q_word, q_weight, q_n, top_id, top_score, top_common, max_common},
+                   "the database query takes device pointers only"));
+  HIPCHK(c, hipSetDevice(c->device));
+  const DbQueryPlan P = db_query_plan(db->capacity, batch, topk);
+  PCHK(db_query_workspace(c, P));
+  uint8_t *ws = c->w_db.as<uint8_t>();
+  uint32_t *acc_score = (uint32_t *)(ws + P.o_score), *acc_common = (uint32_t *)(ws + P.o_common);
+  uint32_t *gmax = (uint32_t *)(ws + P.o_gmax), *pcom = (uint32_t *)(ws + P.o_pcom);
+  uint64_t *pkey = (uint64_t *)(ws + P.o_pkey);
+  const uint32_t *dsize = db->d_size.as<uint32_t>();
+  const uint8_t *alive = db->d_alive.as<uint8_t>();
+  HIPCHK(c, hipMemsetAsync(gmax, 0, 4 * (size_t)batch, c->stream));
+  hipLaunchKernelGGL(pd::k_db_accumulate, dim3(P.nslices, (unsigned)batch), dim3(pd::DB_THREADS), P.lds, c->stream, db->nwords,
+                     P.cap_pad, P.slice, dsize, alive, db->off.as<uint32_t>(), db->post.as<uint2>(), q_word, q_weight, q_n,
+                     stride, id_limit, acc_score, acc_common, gmax);
+  PCHK(launch_ok(c, "k_db_accumulate"));
+  hipLaunchKernelGGL(pd::k_db_select, dim3(P.nsel, (unsigned)batch), dim3(pd::DB_THREADS), 0, c->stream, P.cap_pad, dsize,
+                     alive, id_limit, (uint32_t)min_common_pct, topk, acc_score, (const uint16_t *)acc_common, gmax, pkey, pcom,
+                     top_id, top_score, top_common, max_common);
+  PCHK(launch_ok(c, "k_db_select"));
+  if (P.nsel > 1) {
+    hipLaunchKernelGGL(pd::k_db_merge, dim3((unsigned)batch), dim3(pd::DB_THREADS), 0, c->stream, P.nsel, topk, pkey, pcom,
+                       gmax, top_id, top_score, top_common, max_common);
+    PCHK(launch_ok(c, "k_db_merge"));
+  }
+  return PISLAM_OK;
 }
 
 // ---- batches in flight: a pipeline of contexts behind one object --------------------------------

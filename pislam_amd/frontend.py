@@ -510,6 +510,151 @@ def matchHammingBowBatch(qdesc, qgroup, qcounts, tdesc, tgroup, tcounts, ngroups
     return idx, dist, dist2
 
 
+# ---- bag of words: integer weights and the key-frame database ----------
+BOW_MAX_STRIDE = 16384       # entries of a bag-of-words vector (pislam_bow_vector_batch)
+
+
+def _check_bow_rows(what, word, other, n):
+    """[batch][stride] word / weight tensors and their [batch] counts: returns (batch, stride)."""
+    if word.ndim != 2:
+        raise ValueError(f"{what}: words must be [batch][stride]")
+    batch, stride = (int(v) for v in word.shape)
+    if stride > BOW_MAX_STRIDE:
+        raise ValueError(f"{what}: stride must be at most {BOW_MAX_STRIDE}")
+    if tuple(other.shape) != (batch, stride):
+        raise ValueError(f"{what}: words and weights must have the same [batch][stride] shape")
+    if tuple(n.shape) != (batch,):
+        raise ValueError(f"{what}: one count per frame ({batch})")
+    return batch, stride
+
+
+def bowWeightBatch(bow_word, bow_tf, bow_n, idf=None, nwords: int | None = None, bow_weight=None, *,
+                   ctx: Context | None = None):
+    """Q24 integer tf-idf weights of bag-of-words vectors (pislam_bow_weight_batch): bow_weight[b][k] =
+    (tf * idf << 24) / (the frame's sum of tf * idf), floored; idf is a device int32 tensor [nwords] (values above
+    65535 count as 65535) or None (= 1 for every word, then `nwords` must be given).  Returns bow_weight int32
+    [batch][stride]; slots at and beyond bow_n[b] are not written.  Asynchronous on the ctx stream."""
+    batch, stride = _check_bow_rows("bowWeightBatch", bow_word, bow_tf, bow_n)
+    if idf is not None:
+        if idf.ndim != 1:
+            raise ValueError("bowWeightBatch: idf must be [nwords]")
+        if nwords is None:
+            nwords = int(idf.shape[0])
+        elif int(nwords) > int(idf.shape[0]):
+            raise ValueError("bowWeightBatch: nwords exceeds the idf table")
+    elif nwords is None:
+        raise ValueError("bowWeightBatch: nwords is needed without an idf table")
+    if not 1 <= int(nwords) <= 1 << 24:
+        raise ValueError("bowWeightBatch: nwords must be 1..2^24")
+    if bow_weight is not None and tuple(bow_weight.shape) != (batch, stride):
+        raise ValueError("bowWeightBatch: bow_weight must be [batch][stride] like the words")
+    import torch
+    ctx = ctx or default_context()
+    if bow_weight is None:
+        bow_weight = torch.empty((batch, stride), dtype=torch.int32, device=bow_word.device)
+    ctx.check(ctx.lib.pislam_bow_weight_batch(ctx.h, ptr(bow_word), ptr(bow_tf), ptr(bow_n), stride, batch, ptr(idf),
+                                              int(nwords), ptr(bow_weight)), "pislam_bow_weight_batch")
+    return bow_weight
+
+
+class BowDatabase:
+    """pislam_bowdb: up to `capacity` key frames of at most `stride` (word, weight) entries over `nwords` words, with an
+    inverted file on the device.  add() takes what bowVectorBatch / bowWeightBatch wrote and returns the first new id;
+    query() returns, per query vector, the `topk` key frames with the largest integer L1 score among those that share
+    at least min_common_pct % of the best key frame's common words (include/pislam_hip.h).  Shapes and ranges are checked
+    here, before the library is touched."""
+
+    def __init__(self, nwords: int, stride: int, capacity: int, *, ctx: Context | None = None):
+        self.h = None
+        nwords, stride, capacity = int(nwords), int(stride), int(capacity)
+        if not 1 <= nwords <= 1 << 24:
+            raise ValueError("nwords must be 1..2^24")
+        if not 1 <= stride <= BOW_MAX_STRIDE:
+            raise ValueError(f"stride must be 1..{BOW_MAX_STRIDE}")
+        if not 1 <= capacity <= 1 << 20:
+            raise ValueError("capacity must be 1..2^20")
+        if stride * capacity > 1 << 31:
+            raise ValueError("capacity * stride must be at most 2^31")
+        self.nwords, self.stride, self.capacity = nwords, stride, capacity
+        self.ctx = ctx or default_context()
+        h = ctypes.c_void_p()
+        self.ctx.check(self.ctx.lib.pislam_bowdb_create(self.ctx.h, nwords, stride, capacity, ctypes.byref(h)),
+                       "pislam_bowdb_create")
+        self.h = h
+
+    @property
+    def size(self) -> int:
+        """Ids handed out so far (removed ones included)."""
+        return int(self.ctx.lib.pislam_bowdb_size(self.h))
+
+    def add(self, bow_word, bow_weight, bow_n) -> int:
+        """Adds the frames of [batch][stride] device tensors as key frames size .. size + batch - 1; returns the first id."""
+        batch, stride = _check_bow_rows("BowDatabase.add", bow_word, bow_weight, bow_n)
+        first = ctypes.c_int32(-1)
+        self.ctx.check(self.ctx.lib.pislam_bowdb_add_batch(self.ctx.h, self.h, ptr(bow_word), ptr(bow_weight), ptr(bow_n),
+                                                           stride, batch, ctypes.byref(first)), "pislam_bowdb_add_batch")
+        return int(first.value)
+
+    def remove(self, ids):
+        ids = np.ascontiguousarray(np.atleast_1d(np.asarray(ids)), np.int32)
+        if ids.ndim != 1:
+            raise ValueError("BowDatabase.remove: ids must be a list of key-frame ids")
+        self.ctx.check(self.ctx.lib.pislam_bowdb_remove(self.ctx.h, self.h, ptr(ids), len(ids)), "pislam_bowdb_remove")
+
+    def clear(self):
+        self.ctx.check(self.ctx.lib.pislam_bowdb_clear(self.ctx.h, self.h), "pislam_bowdb_clear")
+
+    def reserve_query(self, batch: int, topk: int):
+        """Sizes the context's query workspace: afterwards query() of the same or a smaller shape allocates nothing and
+        can be captured into a hipGraph."""
+        if not 0 <= int(batch) <= 65535:
+            raise ValueError("batch must be 0..65535")
+        if not 1 <= int(topk) <= 64:
+            raise ValueError("topk must be 1..64")
+        self.ctx.check(self.ctx.lib.pislam_bowdb_query_reserve(self.ctx.h, self.h, int(batch), int(topk)),
+                       "pislam_bowdb_query_reserve")
+
+    def query(self, q_word, q_weight, q_n, topk: int = 16, min_common_pct: int = 80, id_limit=None, top_id=None,
+              top_score=None, top_common=None, max_common=None):
+        """Returns (top_id, top_score, top_common int32 [batch][topk], max_common int32 [batch]); rows with fewer than
+        topk candidates end in -1 / 0 / 0.  id_limit: device int32 [batch] (key frames at or above it are not eligible)
+        or None.  Asynchronous on the ctx stream."""
+        batch, stride = _check_bow_rows("BowDatabase.query", q_word, q_weight, q_n)
+        topk, min_common_pct = int(topk), int(min_common_pct)
+        if not 1 <= topk <= 64:
+            raise ValueError("topk must be 1..64")
+        if not 0 <= min_common_pct <= 100:
+            raise ValueError("min_common_pct must be 0..100")
+        if id_limit is not None and tuple(id_limit.shape) != (batch,):
+            raise ValueError(f"BowDatabase.query: one id_limit per query ({batch})")
+        for t, shape in ((top_id, (batch, topk)), (top_score, (batch, topk)), (top_common, (batch, topk)),
+                         (max_common, (batch,))):
+            if t is not None and tuple(t.shape) != shape:
+                raise ValueError("BowDatabase.query: outputs must be [batch][topk] and max_common [batch]")
+        import torch
+        new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=q_word.device)
+        top_id = new(batch, topk) if top_id is None else top_id
+        top_score = new(batch, topk) if top_score is None else top_score
+        top_common = new(batch, topk) if top_common is None else top_common
+        max_common = new(batch) if max_common is None else max_common
+        self.ctx.check(self.ctx.lib.pislam_bowdb_query_batch(self.ctx.h, self.h, ptr(q_word), ptr(q_weight), ptr(q_n), stride,
+                                                             batch, ptr(id_limit), min_common_pct, topk, ptr(top_id),
+                                                             ptr(top_score), ptr(top_common), ptr(max_common)),
+                       "pislam_bowdb_query_batch")
+        return top_id, top_score, top_common, max_common
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.pislam_bowdb_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ---- Gaussian.h:48, Bilinear.h:42, Bilinear.h:165 -------------------------------------
 def gaussian5x5(width, height, img, out, *, ctx: Context | None = None):
     """pislam::gaussian5x5<vstep>(width, height, img, out); img may be out (in place)."""
