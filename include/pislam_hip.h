@@ -610,6 +610,102 @@ int pislam_match_hamming_bow_batch(pislam_ctx *ctx, int words, int ngroups,
                                    const uint32_t *tdesc, const uint32_t *tgroup, const uint32_t *tcounts, size_t t_stride,
                                    int batch, int32_t *idx, uint32_t *dist, uint32_t *dist2);
 
+/* ---- after the match: angle bins and match selection --------------------- */
+
+/* The rotation bin of every keypoint of a batch of pyramids (DESIGN.md,
+ * section 5.5): what pislam_orb_frontend_batch computes for each keypoint
+ * inside its descriptor pass and does not hand out.  The call covers pyramid b
+ * (pyramids + b * pyramid_stride, uint8 [rows][vstep]) and every
+ * i < n_b = min(counts[b], stride); PISLAM_COUNT_INVALID counts as 0.
+ * angles[b][i] = the rotation bin, 0 .. 29 (12 degrees each), that orbCompute
+ * uses for the position keypoints[b][i] (x = (k >> 12) & 0xfff, y = k & 0xfff;
+ * score bits ignored) on pyramid b: the moments of Orb.h:80-308 over the
+ * radius-15 circular patch, then the bin of Orb.h:310-387 — the same bits the
+ * descriptor pass rotates its pattern by.  A position whose patch would leave
+ * the buffer (x < 15, x > vstep - 16, y < 15 or y > rows - 16) gets 0xff; no
+ * byte is read for it.  Entries at and beyond n_b are not written.
+ * Layouts: keypoints uint32 [batch][stride] as pislam_orb_frontend_batch writes
+ * them, angles uint8 [batch][stride].  Device pointers only: a host or NULL
+ * pointer, batch < 0, vstep < 31, rows < 31 or stride >= 2^31:
+ * PISLAM_ERR_INVALID, before anything is launched or written.  batch == 0 is a
+ * no-op that returns PISLAM_OK.  Asynchronous on the context stream; no
+ * workspace, so the call can be captured into a hipGraph as it is. */
+int pislam_orb_angles_batch(pislam_ctx *ctx, const uint8_t *pyramids, int vstep, int rows, size_t pyramid_stride,
+                            const uint32_t *keypoints, const uint32_t *counts, size_t stride, int batch,
+                            uint8_t *angles);
+
+/* Match selection: the four integer steps ORB-SLAM
+ * runs after every search (SearchByBoW, SearchForInitialization,
+ * SearchByProjection) — distance threshold, nearest-neighbour ratio,
+ * one-to-one claim of a train descriptor, rotation-consistency histogram
+ * (HISTO_LENGTH = 30, ComputeThreeMaxima, the 10 % rule) — and the compaction
+ * of the survivors into pair lists, on the device.  The reference ships
+ * nothing of the kind: the semantics are this library's own.
+ *
+ * Inputs.  idx, dist, dist2 are [batch][q_stride] as any matcher of this
+ * library writes them; dist2 may be NULL (the stereo matcher has none),
+ * ratio_den must then be 0.  back_idx is [batch][t_stride] or NULL: the idx of
+ * the reverse match, train -> query (the caller runs any matcher with the roles
+ * swapped).  qangle [batch][q_stride] and tangle [batch][t_stride] are uint8
+ * as pislam_orb_angles_batch writes them; both must be non-NULL if and only if
+ * rot_keep > 0.  nq_b / nt_b = qcounts[b] / tcounts[b] clamped to the strides;
+ * PISLAM_COUNT_INVALID counts as 0.
+ *
+ * Steps.  Each query i < nq_b takes the FIRST test it fails; status[b][i]
+ * records which.  With j = idx[b][i]:
+ *  1. no match: j < 0 or j >= nt_b.
+ *  2. distance: dist > max_dist.
+ *  3. ratio: ratio_den > 0, dist2 != 0xffffffff and
+ *     dist * ratio_den >= dist2 * ratio_num (64-bit).  A query without a second
+ *     candidate (dist2 == 0xffffffff) passes.
+ *  4. cross-check: back_idx != NULL and back_idx[b][j] != i.
+ *  5. uniqueness: unique == 1 and another query that passed tests 1-4 has the
+ *     same j with a smaller key dist << 32 | i: the smallest distance wins, ties
+ *     go to the smallest query index.
+ *  6. rotation: rot_keep > 0.  A survivor of tests 1-5 with qangle[i] >= 30 or
+ *     tangle[j] >= 30 fails and is not counted.  Every other survivor counts
+ *     into h[(qangle[i] - tangle[j] + 30) % 30].  The 30 bins are ranked by
+ *     descending count, ties to the smaller bin; `top` is rank 0.  Bin k is kept
+ *     iff rank(k) < rot_keep, h[k] >= 1 and 100 * h[k] >= rot_min_pct * h[top].
+ *     A survivor whose bin is not kept fails.
+ * Queries that fail nothing are selected: status 0.
+ *
+ * Outputs.  sel_q[b][0 .. nsel[b]) = the selected queries in ascending order,
+ * sel_t their j, nsel[b] their number; sel_q / sel_t are [batch][q_stride] and
+ * slots at and beyond nsel[b] are not written.  status (uint8
+ * [batch][q_stride], optional) = 0 or the number of the failed test; entries at
+ * and beyond nq_b are not written.  rot_hist (uint32 [batch][30], optional) = h
+ * before pruning; every row is written in full, all zero when rot_keep == 0.
+ * ORB-SLAM's settings are {50, 6..9, 10, 1, 3, 10}.  With {256, 0, 0, 0, 0, 0}
+ * and back_idx NULL the selection is every query with a valid idx.
+ *
+ * Limits: t_stride <= 65535; 1 <= q_stride <= 2^22; 0 <= batch <= 65535; the
+ * parameter ranges below.  Anything else, a host or NULL pointer where a device
+ * pointer is required, or a violated NULL rule (dist2 against ratio_den, the
+ * angles against rot_keep): PISLAM_ERR_INVALID, before anything is launched or
+ * written.  `p` is a host struct, read during the call.  Asynchronous on the
+ * context stream, no host round trip and no workspace: the call can be
+ * captured into a hipGraph as it is, and no reserve function exists because
+ * none is needed.  One workgroup selects a pair.  Its uniqueness table covers
+ * 16384 train indices at a time: with nt_b <= 16384 it is filled once per call;
+ * a larger nt_b is walked in 2 .. 4 chunks, and the compaction then fills a
+ * chunk again for each block of 1024 queries that refers to it (slower, same
+ * results). */
+typedef struct pislam_select_params {
+  int32_t max_dist;             /* keep dist <= max_dist; 0 .. 256                                             */
+  int32_t ratio_num, ratio_den; /* keep dist * ratio_den < dist2 * ratio_num; ratio_den 0 = off;
+                                   otherwise 1 <= ratio_num <= ratio_den <= 65535                              */
+  int32_t unique;               /* 0 / 1: a train index is given to one query only                             */
+  int32_t rot_keep;             /* 0 = no rotation check; 1 .. 30 = histogram bins kept (ORB-SLAM: 3)          */
+  int32_t rot_min_pct;          /* 0 .. 100: a kept bin holds at least this share of the top bin (ORB-SLAM: 10) */
+} pislam_select_params;
+int pislam_match_select_batch(pislam_ctx *ctx, const pislam_select_params *p,
+                              const int32_t *idx, const uint32_t *dist, const uint32_t *dist2,
+                              const uint32_t *qcounts, size_t q_stride,
+                              const uint32_t *tcounts, size_t t_stride,
+                              const int32_t *back_idx, const uint8_t *qangle, const uint8_t *tangle, int batch,
+                              int32_t *sel_q, int32_t *sel_t, uint32_t *nsel, uint8_t *status, uint32_t *rot_hist);
+
 /* ---- bag of words: integer weights and the key-frame database ------------ */
 
 /* Place recognition (relocalisation, loop detection), after DBoW2's

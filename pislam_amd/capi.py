@@ -35,6 +35,11 @@ class StereoParams(ctypes.Structure):
         "level_span", "min_disp", "max_disp", "max_hamming", "sad_radius", "search_radius", "median_filter")]
 
 
+class SelectParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "max_dist", "ratio_num", "ratio_den", "unique", "rot_keep", "rot_min_pct")]
+
+
 # name -> (restype, argtypes); every symbol declared in include/pislam_hip.h
 SYMBOLS = {
     "pislam_abi_version": (_i, []),
@@ -107,6 +112,9 @@ SYMBOLS = {
     "pislam_bow_vector_batch": (_i, [_vp, _vp, _vp, _sz, _i, _vp, _vp, _vp]),
     "pislam_match_bow_reserve": (_i, [_vp, _i, _i, _sz, _i]),
     "pislam_match_hamming_bow_batch": (_i, [_vp, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp]),
+    "pislam_orb_angles_batch": (_i, [_vp, _vp, _i, _i, _sz, _vp, _vp, _sz, _i, _vp]),
+    "pislam_match_select_batch": (_i, [_vp, ctypes.POINTER(SelectParams), _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp,
+                                       _i, _vp, _vp, _vp, _vp, _vp]),
     "pislam_bow_weight_batch": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, ctypes.c_uint32, _vp]),
     "pislam_bowdb_create": (_i, [_vp, ctypes.c_uint32, _sz, _i, ctypes.POINTER(_vp)]),
     "pislam_bowdb_destroy": (_i, [_vp]),

@@ -55,6 +55,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_match_kernels.h"
 #include "pislam_bow_kernels.h"
 #include "pislam_bowdb_kernels.h"
+#include "pislam_select_kernels.h"
 
 #define PISLAM_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -499,6 +500,11 @@ PISLAM_EXPORT int pislam_ctx_create(int device, pislam_ctx **out) {
     }
   }
 #undef CREATE_CHK
+  // pislam_match_select_batch is capturable from its first call: its kernel's LDS (a 64 KB table and a little more) is
+  // allowed here, not in the call.  (Should this fail, that call's launch reports it.)
+  if (hipFuncSetAttribute((const void *)ps::k_match_select, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)ps::SEL_LDS_BYTES) != hipSuccess)
+    (void)hipGetLastError();
   *out = c;
   return PISLAM_OK;
 }
@@ -2792,6 +2798,67 @@ PISLAM_EXPORT int pislam_match_hamming_bow_batch(pislam_ctx *c, int words, int n
   }
 #undef PISLAM_MATCH_BOW
   return launch_ok(c, "k_match_bow");
+}
+
+// ---- after the match: batched angle bins and match selection ------------------------------
+
+PISLAM_EXPORT int pislam_orb_angles_batch(pislam_ctx *c, const uint8_t *pyramids, int vstep, int rows,
+                                          size_t pyramid_stride, const uint32_t *keypoints, const uint32_t *counts,
+                                          size_t stride, int batch, uint8_t *angles) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
+  if (vstep < 31 || rows < 31) return fail(c, PISLAM_ERR_INVALID, "vstep and rows must hold a 31 x 31 patch");
+  if (stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "stride too large");
+  if (batch == 0) return PISLAM_OK;
+  PCHK(device_ptrs(c, {pyramids, keypoints, counts, angles}, "the batched angle call takes device pointers only"));
+  if (stride == 0) return PISLAM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  for (int b0 = 0; b0 < batch; b0 += 65535) {                // (grid.y)
+    const int nb = std::min(batch - b0, 65535);
+    const dim3 grid = query_grid(c, stride, 4, nb);
+    hipLaunchKernelGGL(pk::k_orb_angles, grid, dim3(256), 0, c->stream, pyramids + (size_t)b0 * pyramid_stride, vstep, rows,
+                       pyramid_stride, keypoints + (size_t)b0 * stride, counts + b0, stride, angles + (size_t)b0 * stride);
+    PCHK(launch_ok(c, "k_orb_angles"));
+  }
+  return PISLAM_OK;
+}
+
+PISLAM_EXPORT int pislam_match_select_batch(pislam_ctx *c, const pislam_select_params *p, const int32_t *idx,
+                                            const uint32_t *dist, const uint32_t *dist2, const uint32_t *qcounts,
+                                            size_t q_stride, const uint32_t *tcounts, size_t t_stride,
+                                            const int32_t *back_idx, const uint8_t *qangle, const uint8_t *tangle,
+                                            int batch, int32_t *sel_q, int32_t *sel_t, uint32_t *nsel, uint8_t *status,
+                                            uint32_t *rot_hist) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
+  if (p->max_dist < 0 || p->max_dist > 256) return fail(c, PISLAM_ERR_INVALID, "max_dist must be 0..256");
+  if (p->ratio_den != 0 && !(1 <= p->ratio_num && p->ratio_num <= p->ratio_den && p->ratio_den <= 65535))
+    return fail(c, PISLAM_ERR_INVALID, "the ratio must be off (ratio_den 0) or 1 <= ratio_num <= ratio_den <= 65535");
+  if (p->unique != 0 && p->unique != 1) return fail(c, PISLAM_ERR_INVALID, "unique must be 0 or 1");
+  if (p->rot_keep < 0 || p->rot_keep > ps::SEL_BINS) return fail(c, PISLAM_ERR_INVALID, "rot_keep must be 0..30");
+  if (p->rot_min_pct < 0 || p->rot_min_pct > 100) return fail(c, PISLAM_ERR_INVALID, "rot_min_pct must be 0..100");
+  if (t_stride > 65535) return fail(c, PISLAM_ERR_INVALID, "at most 65535 train entries per pair");
+  if (q_stride < 1 || q_stride > ((size_t)1 << 22)) return fail(c, PISLAM_ERR_INVALID, "q_stride must be 1..2^22");
+  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
+  if (!dist2 && p->ratio_den != 0) return fail(c, PISLAM_ERR_INVALID, "a ratio test needs dist2");
+  if ((p->rot_keep > 0) != (qangle != nullptr) || (p->rot_keep > 0) != (tangle != nullptr))
+    return fail(c, PISLAM_ERR_INVALID, "qangle and tangle go with rot_keep > 0, and only with it");
+  const char *what = "the match selection takes device pointers only";
+  PCHK(device_ptrs(c, {idx, dist, qcounts, tcounts, sel_q, sel_t, nsel}, what));
+  for (const void *opt : {(const void *)dist2, (const void *)back_idx, (const void *)qangle, (const void *)tangle,
+                          (const void *)status, (const void *)rot_hist})
+    if (opt && !is_device_ptr(opt)) return fail(c, PISLAM_ERR_INVALID, what);
+  if (batch == 0) return PISLAM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  ps::SelArgs A;
+  A.max_dist = p->max_dist, A.ratio_num = (uint32_t)p->ratio_num, A.ratio_den = (uint32_t)p->ratio_den;
+  A.unique = p->unique, A.rot_keep = p->rot_keep, A.rot_min_pct = p->rot_min_pct;
+  A.idx = idx, A.dist = dist, A.dist2 = p->ratio_den ? dist2 : nullptr;
+  A.qcounts = qcounts, A.tcounts = tcounts, A.back_idx = back_idx, A.qangle = qangle, A.tangle = tangle;
+  A.q_stride = q_stride, A.t_stride = t_stride;
+  A.sel_q = sel_q, A.sel_t = sel_t, A.nsel = nsel, A.status = status, A.rot_hist = rot_hist;
+  hipLaunchKernelGGL(ps::k_match_select, dim3((unsigned)batch), dim3(ps::SEL_THREADS), ps::SEL_LDS_BYTES, c->stream, A);
+  return launch_ok(c, "k_match_select");
 }
 
 // ---- bag of words: integer weights and the key-frame database -----------------------------

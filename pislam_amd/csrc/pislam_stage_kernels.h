@@ -309,4 +309,44 @@ __global__ void k_angles(const int32_t *__restrict__ xys, int nslots, uint8_t *_
   ang[i] = (uint8_t)angle_bin_fast(xys[8 * g + s], xys[8 * g + 4 + s], ::g_vrecpe_tab.v);
 }
 
+// pislam_orb_angles_batch: the rotation bin orbCompute uses (k_orb's moments and angle, Orb.h:80-387) for every
+// keypoint of a batch of pyramids, without the descriptor.  One wave per keypoint, lanes as in k_orb; the workgroups
+// of a pyramid (blockIdx.x of gridDim.x, pyramid blockIdx.y) stride over its keypoints.  A position whose patch would
+// leave the rows x vstep buffer gets 0xff and reads nothing.
+__global__ __launch_bounds__(256) void k_orb_angles(
+    const uint8_t *__restrict__ img, int vstep, int rows, size_t pyr_stride, const uint32_t *__restrict__ pts,
+    const uint32_t *__restrict__ counts, size_t pts_stride, uint8_t *__restrict__ ang) {
+  const int b = blockIdx.y;
+  uint32_t n = counts[b];
+  n = n == 0xffffffffu ? 0u : (n < pts_stride ? n : (uint32_t)pts_stride);   // PISLAM_COUNT_INVALID counts as 0
+  const uint8_t *im = img + (size_t)b * pyr_stride;
+  const int lane = lane_id();
+  const int dx = (lane & 31) - 15, adx = dx < 0 ? -dx : dx;
+  for (uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += gridDim.x * 4) {
+    const uint32_t p = pts[(size_t)b * pts_stride + i];
+    const int x = decode_x(p), y = decode_y(p);
+    uint32_t rot = 0xff;
+    if (x >= 15 && x <= vstep - 16 && y >= 15 && y <= rows - 16) {           // wave-uniform
+      const uint8_t *c = im + (ptrdiff_t)y * vstep + x;
+      int m10 = 0, m01 = 0;
+#pragma unroll 4
+      for (int j = 0; j < 16; j++) {
+        const int dy = -15 + (lane >> 5) + 2 * j;
+        if (dy <= 15) {
+          const int ady = dy < 0 ? -dy : dy;
+          if (adx <= patch_umax(ady)) {
+            const int v = c[dy * vstep + dx];
+            m10 += dx * v;
+            m01 += dy * v;
+          }
+        }
+      }
+      m10 = wave_sum(m10);
+      m01 = wave_sum(m01);
+      rot = angle_bin_fast(m10, m01, ::g_vrecpe_tab.v);
+    }
+    if (lane == 0) ang[(size_t)b * pts_stride + i] = (uint8_t)rot;
+  }
+}
+
 }  // namespace pk

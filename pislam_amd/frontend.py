@@ -17,7 +17,7 @@ import ctypes
 import numpy as np
 
 from . import capi
-from .capi import Context, FrontendParams, Level, StereoParams, ptr
+from .capi import Context, FrontendParams, Level, SelectParams, StereoParams, ptr
 
 _default_ctx: Context | None = None
 
@@ -510,6 +510,77 @@ def matchHammingBowBatch(qdesc, qgroup, qcounts, tdesc, tgroup, tcounts, ngroups
     return idx, dist, dist2
 
 
+# ---- after the match: angle bins and match selection ---------------------
+def orbAnglesBatch(pyramids, kp, counts, angles=None, *, ctx: Context | None = None):
+    """Rotation bins of device-resident front-end keypoints (pislam_orb_angles_batch): pyramids uint8
+    [batch][rows][vstep], kp [batch][stride], counts [batch].  Returns angles uint8 [batch][stride]: the bin 0..29
+    orbCompute uses for each keypoint, 0xff where the patch would leave the buffer; entries at and beyond a pyramid's
+    count are not written.  Asynchronous on the ctx stream."""
+    import torch
+    ctx = ctx or default_context()
+    batch, rows, vstep = (int(v) for v in pyramids.shape)
+    stride = int(kp.shape[1])
+    if int(kp.shape[0]) != batch:
+        raise ValueError("pyramids and keypoints differ in batch")
+    if angles is None:
+        angles = torch.empty((batch, stride), dtype=torch.uint8, device=kp.device)
+    ctx.check(ctx.lib.pislam_orb_angles_batch(ctx.h, ptr(pyramids), vstep, rows, int(pyramids.stride(0)) if batch else 0,
+                                              ptr(kp), ptr(counts), stride, batch, ptr(angles)),
+              "pislam_orb_angles_batch")
+    return angles
+
+
+def selectMatchesBatch(idx, dist, dist2, qcounts, tcounts, *, max_dist=50, ratio=(8, 10), unique=True, rot_keep=3,
+                       rot_min_pct=10, back_idx=None, qangle=None, tangle=None, want_status=False, want_hist=False,
+                       t_stride: int | None = None, sel_q=None, sel_t=None, nsel=None, status=None, rot_hist=None,
+                       ctx: Context | None = None):
+    """Match selection on the device (pislam_match_select_batch) over the (idx, dist, dist2) [batch][q_stride] of any
+    matcher: distance threshold, ratio test (ratio = (num, den), None = off; dist2 may be None then), cross-check against
+    back_idx [batch][t_stride], one-to-one claim, and ORB-SLAM's rotation histogram over qangle / tangle (orbAnglesBatch;
+    rot_keep is forced to 0 when no angles are given).  Returns (sel_q, sel_t, nsel[, status][, rot_hist]): pair b's
+    selected queries in ascending order and their train indices in the first nsel[b] slots of int32 [batch][q_stride]
+    (the other slots are not written), status uint8 [batch][q_stride] (0 or the number of the failed test), rot_hist
+    int32 [batch][30].  t_stride is taken from tangle or back_idx; without either it may be given (default 65535: the
+    train counts are then not clamped).  Asynchronous on the ctx stream; no workspace."""
+    import torch
+    ctx = ctx or default_context()
+    batch, qs = (int(v) for v in idx.shape)
+    if qangle is None or tangle is None:
+        if qangle is not None or tangle is not None:
+            raise ValueError("qangle and tangle go together")
+        rot_keep = 0
+    for a in (tangle, back_idx):
+        if a is not None:
+            if t_stride is not None and int(a.shape[1]) != t_stride:
+                raise ValueError("t_stride, tangle and back_idx disagree")
+            t_stride = int(a.shape[1])
+    if t_stride is None:
+        t_stride = 65535
+    num, den = (0, 0) if ratio is None else (int(ratio[0]), int(ratio[1]))
+    p = SelectParams(int(max_dist), num, den, 1 if unique else 0, int(rot_keep), int(rot_min_pct))
+    dev = idx.device
+    if sel_q is None:
+        sel_q = torch.empty((batch, qs), dtype=torch.int32, device=dev)
+    if sel_t is None:
+        sel_t = torch.empty((batch, qs), dtype=torch.int32, device=dev)
+    if nsel is None:
+        nsel = torch.empty((batch,), dtype=torch.int32, device=dev)
+    if status is None and want_status:
+        status = torch.empty((batch, qs), dtype=torch.uint8, device=dev)
+    if rot_hist is None and want_hist:
+        rot_hist = torch.empty((batch, 30), dtype=torch.int32, device=dev)
+    ctx.check(ctx.lib.pislam_match_select_batch(ctx.h, ctypes.byref(p), ptr(idx), ptr(dist), ptr(dist2), ptr(qcounts), qs,
+                                                ptr(tcounts), t_stride, ptr(back_idx), ptr(qangle), ptr(tangle), batch,
+                                                ptr(sel_q), ptr(sel_t), ptr(nsel), ptr(status), ptr(rot_hist)),
+              "pislam_match_select_batch")
+    out = (sel_q, sel_t, nsel)
+    if status is not None:
+        out += (status,)
+    if rot_hist is not None:
+        out += (rot_hist,)
+    return out
+
+
 # ---- bag of words: integer weights and the key-frame database ----------
 BOW_MAX_STRIDE = 16384       # entries of a bag-of-words vector (pislam_bow_vector_batch)
 
@@ -751,6 +822,10 @@ class OrbFrontend:
         c.check(c.lib.pislam_orb_frontend_batch(c.h, ctypes.byref(self.params), self.levels, ptr(pyramids),
                                                 stride, batch, ptr(kp), ptr(desc), ptr(counts)),
                 "pislam_orb_frontend_batch")
+
+    def angles(self, pyramids, kp, counts, angles=None):
+        """The rotation bin of every keypoint this front end wrote (orbAnglesBatch on this context)."""
+        return orbAnglesBatch(pyramids, kp, counts, angles, ctx=self.ctx)
 
     def score_map(self, b: int) -> np.ndarray:
         c = self.ctx
