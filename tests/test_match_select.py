@@ -5,7 +5,7 @@ The semantics are the library's own (include/pislam_hip.h).  `ref_select` states
 one boolean mask per test applied in order, a minimum of dist << 32 | i per train index for the claim, a bincount and
 a sort by (-count, bin) for the histogram.  The CPU tests check that reference on hand-built cases and on the demo
 photograph against its 180 degree rotation; the GPU tests compare the library with it bit for bit, outputs pre-filled
-with a sentinel."""
+with a sentinel.  The block, chunk, index and batch limits are in test_after_match_limits.py."""
 import ctypes
 
 import numpy as np

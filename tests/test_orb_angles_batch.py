@@ -2,7 +2,8 @@
 for every keypoint of a batch of pyramids.
 
 The expectation is the oracle's: `orc.atan2_bins(orc.orb_centroids(img, kp))` — the reference's own moments and bin.
-The GPU tests pre-fill the output with the sentinel byte and compare bit for bit."""
+The GPU tests pre-fill the output with the sentinel byte and compare bit for bit.  The grid, launch, coordinate and
+address limits are in test_after_match_limits.py."""
 import os
 import re
 
