@@ -9,10 +9,10 @@
 //                   level costs one dependent load latency, not two.  No LDS, no branches around the loads.
 //   k_bow_vector    one workgroup per pyramid: bitonic sort of the words in LDS, run heads flagged and scanned, the
 //                   distinct words and their run lengths written in ascending order.
-//   k_bow_index     one workgroup per pair: pm::k_scaled_index's counting sort with the train entry's group id as the cell
-//                   (ids at or above ngroups are not indexed).
+//   k_bow_index     one workgroup per pair: pm::lds_counting_sort (the sort of pm::k_scaled_index) with the train entry's
+//                   group id as the bin (ids at or above ngroups are not indexed).
 //   k_match_bow     pm::WIN_LPQ lanes per query walking the one run of its group, (best, second) on dist << 16 | index
-//                   as the window matchers keep them.
+//                   kept, merged and stored by the functions the window matchers use.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(BOW_VEC_THREADS) void k_bow_vector(const uint32_t *
   __shared__ uint16_t start[BOW_VEC_MAX];                // first sorted position of the run with a given rank
   __shared__ uint32_t wave_sum[BOW_VEC_THREADS / 64];
   const int b = blockIdx.x;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t tid = threadIdx.x;
   const uint32_t n = pm::win_count(count[b], stride);
   if (n == 0) {
     if (tid == 0) bow_n[b] = 0;
@@ -129,20 +129,8 @@ __global__ __launch_bounds__(BOW_VEC_THREADS) void k_bow_vector(const uint32_t *
   const uint32_t i0 = min(tid * chunk, n), i1 = min(i0 + chunk, n);
   uint32_t s = 0;
   for (uint32_t i = i0; i < i1; i++) s += (i == 0 || key[i] != key[i - 1]) ? 1u : 0u;
-  uint32_t incl = s;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t v = __shfl_up(incl, d, 64);
-    if ((int)lane >= d) incl += v;
-  }
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  uint32_t rank = incl - s, total = 0;
-  for (uint32_t w = 0; w < BOW_VEC_THREADS / 64; w++) {
-    const uint32_t v = wave_sum[w];
-    if (w < wave) rank += v;
-    total += v;
-  }
+  uint32_t total;
+  uint32_t rank = pm::block_scan<BOW_VEC_THREADS>(s, wave_sum, &total);
   uint32_t *ow = bow_word + (size_t)b * stride, *ot = bow_tf + (size_t)b * stride;
   for (uint32_t i = i0; i < i1; i++) {
     if (i == 0 || key[i] != key[i - 1]) {
@@ -157,9 +145,9 @@ __global__ __launch_bounds__(BOW_VEC_THREADS) void k_bow_vector(const uint32_t *
 }
 
 // grid (batch), pm::WIN_INDEX_THREADS threads.  tgroup [batch][t_stride]; grp_off [batch][ngroups + 1],
-// ent_idx [batch][t_stride] = original index, ent_desc [batch][t_stride][words], both sorted by group.  The counting sort
-// of pm::k_scaled_index (kept apart from it so that kernel stays as it is): histogram with LDS atomics, exclusive scan,
-// scatter.  Scatter order inside a group varies between runs; the match results do not (the key is unique per index).
+// ent_idx [batch][t_stride] = original index, ent_desc [batch][t_stride][words], both sorted by group:
+// pm::lds_counting_sort with the group id as the bin, as pm::k_scaled_index runs it with the cell.  Scatter order inside
+// a group varies between runs; the match results do not (the key is unique per index).
 __global__ __launch_bounds__(pm::WIN_INDEX_THREADS) void k_bow_index(uint32_t ngroups, int words,
                                                                      const uint32_t *__restrict__ tgroup,
                                                                      const uint32_t *__restrict__ tdesc,
@@ -167,54 +155,23 @@ __global__ __launch_bounds__(pm::WIN_INDEX_THREADS) void k_bow_index(uint32_t ng
                                                                      uint32_t *__restrict__ grp_off,
                                                                      uint32_t *__restrict__ ent_idx,
                                                                      uint32_t *__restrict__ ent_desc) {
-  constexpr uint32_t T = pm::WIN_INDEX_THREADS;
   __shared__ uint32_t hist[BOW_MAX_GROUPS];
-  __shared__ uint32_t wave_sum[T / 64];
+  __shared__ uint32_t wave_sum[pm::WIN_INDEX_THREADS / 64];
   const int b = blockIdx.x;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const uint32_t nt = pm::win_count(tcount[b], t_stride);
   const uint32_t *gp = tgroup + (size_t)b * t_stride;
-  uint32_t *off = grp_off + (size_t)b * (ngroups + 1);
-  for (uint32_t c = tid; c < ngroups; c += T) hist[c] = 0;
-  __syncthreads();
-  for (uint32_t j = tid; j < nt; j += T) {
-    const uint32_t g = gp[j];
-    if (g < ngroups) atomicAdd(&hist[g], 1u);
-  }
-  __syncthreads();
-  const uint32_t chunk = (ngroups + T - 1) / T;
-  const uint32_t c0 = min(tid * chunk, ngroups), c1 = min(c0 + chunk, ngroups);
-  uint32_t s = 0;
-  for (uint32_t c = c0; c < c1; c++) s += hist[c];
-  uint32_t incl = s;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t v = __shfl_up(incl, d, 64);
-    if ((int)lane >= d) incl += v;
-  }
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  uint32_t run = incl - s;
-  for (uint32_t w = 0; w < wave; w++) run += wave_sum[w];
-  for (uint32_t c = c0; c < c1; c++) {
-    const uint32_t v = hist[c];
-    hist[c] = run;
-    run += v;
-  }
-  if (tid == T - 1) off[ngroups] = run;                  // entries indexed (the last chunk ends at the total)
-  __syncthreads();
-  for (uint32_t c = tid; c < ngroups; c += T) off[c] = hist[c];
-  __syncthreads();
   const uint32_t *dp = tdesc + (size_t)b * t_stride * words;
   uint32_t *ip = ent_idx + (size_t)b * t_stride;
   uint32_t *ep = ent_desc + (size_t)b * t_stride * words;
-  for (uint32_t j = tid; j < nt; j += T) {
-    const uint32_t g = gp[j];
-    if (g >= ngroups) continue;
-    const uint32_t slot = atomicAdd(&hist[g], 1u);       // hist[g] is the next free slot of group g
-    ip[slot] = j;
-    for (int w = 0; w < words; w++) ep[(size_t)slot * words + w] = dp[(size_t)j * words + w];
-  }
+  pm::lds_counting_sort<pm::WIN_INDEX_THREADS>(
+      ngroups, pm::win_count(tcount[b], t_stride), hist, wave_sum, grp_off + (size_t)b * (ngroups + 1),
+      [&](uint32_t j) {
+        const uint32_t g = gp[j];
+        return g < ngroups ? (int32_t)g : -1;
+      },
+      [&](uint32_t slot, uint32_t j) {
+        ip[slot] = j;
+        for (int w = 0; w < words; w++) ep[(size_t)slot * words + w] = dp[(size_t)j * words + w];
+      });
 }
 
 // grid (query tiles, batch), pm::WIN_THREADS threads; q_stride / t_stride in entries; outputs [batch][q_stride].
@@ -236,36 +193,22 @@ __global__ __launch_bounds__(pm::WIN_THREADS) void k_match_bow(uint32_t ngroups,
   for (uint32_t q0 = blockIdx.x * (uint32_t)pm::WIN_QPW; q0 < nq; q0 += gridDim.x * (uint32_t)pm::WIN_QPW) {
     const uint32_t i = q0 + threadIdx.x / pm::WIN_LPQ;
     const size_t o = (size_t)b * q_stride + i;
-    uint32_t best = 0xffffffffu, second = 0xffffffffu;  // (keys are at most 256 << 16 | 65534: never the sentinel)
+    uint32_t best = 0xffffffffu, second = 0xffffffffu;
     uint32_t e = 0, e1 = 0;                             // the run of the query's group (empty: past the count, no group)
-    uint32_t qd[WORDS];
-#pragma unroll
-    for (int w = 0; w < WORDS; w++) qd[w] = 0;
+    const uint32_t *qp = nullptr;
     if (i < nq) {
       const uint32_t g = qgroup[o];
       if (g < ngroups) {
         e = off[g] + sub, e1 = off[g + 1];
-        const uint32_t *qp = qdesc + o * WORDS;
-#pragma unroll
-        for (int w = 0; w < WORDS; w++) qd[w] = qp[w];
+        qp = qdesc + o * WORDS;
       }
     }
-    for (; e < e1; e += pm::WIN_LPQ) {
-      const uint32_t key = (pm::win_popc<WORDS>(qd, ep + (size_t)e * WORDS) << 16) | ip[e];
-      second = min(second, max(best, key));
-      best = min(best, key);
-    }
-#pragma unroll
-    for (int s = 1; s < pm::WIN_LPQ; s <<= 1) {          // merge the lanes of a query: they saw disjoint entries
-      const uint32_t ob = __shfl_xor(best, s, 64), os = __shfl_xor(second, s, 64);
-      second = min(min(second, os), max(best, ob));
-      best = min(best, ob);
-    }
-    if (sub == 0 && i < nq) {
-      idx[o] = best == 0xffffffffu ? -1 : (int32_t)(best & 0xffffu);
-      dist[o] = best == 0xffffffffu ? 0xffffffffu : best >> 16;
-      dist2[o] = second == 0xffffffffu ? 0xffffffffu : second >> 16;
-    }
+    uint32_t qd[WORDS];
+    pm::load_query<WORDS>(qd, qp);
+    for (; e < e1; e += pm::WIN_LPQ)
+      pm::pair_push(best, second, (pm::win_popc<WORDS>(qd, ep + (size_t)e * WORDS) << 16) | ip[e]);
+    pm::pair_merge_lanes<pm::WIN_LPQ>(best, second);
+    if (sub == 0 && i < nq) pm::store_match(o, best, second, idx, dist, dist2);
   }
 }
 

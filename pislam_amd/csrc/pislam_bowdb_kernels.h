@@ -6,8 +6,8 @@
 //   k_bow_weight      one workgroup per frame: A = sum tf * idf in 64 bits, then (a_k << 24) / A per entry.
 //   k_db_store        one workgroup per added frame: the entries go to the forward store, the words' counts (global
 //                     memory, integer atomics) grow by the new entries.
-//   k_db_scan_*       exclusive scan of the counts into the CSR offsets: chunk sums, one workgroup over the chunk sums,
-//                     offsets and scatter cursors per chunk.
+//   k_db_scan_*       exclusive scan of the counts into the CSR offsets (pm::block_scan in each): chunk sums, one
+//                     workgroup over the chunk sums, offsets and scatter cursors per chunk.
 //   k_db_scatter      one workgroup per stored frame: every entry takes the next free slot of its word.  Posting order
 //                     inside a word varies between runs; no result does.
 //   k_db_accumulate   one workgroup per (slice of ids, query).  The (score, common) cells of the slice live in LDS: a
@@ -46,28 +46,6 @@ constexpr int DB_SEL_SLICE = DB_THREADS * DB_SEL_R;   // 8192 ids; 2^20 / 8192 *
 __device__ __forceinline__ uint64_t db_shfl_xor64(uint64_t v, int s) {
   const uint32_t lo = __shfl_xor((uint32_t)v, s, 64), hi = __shfl_xor((uint32_t)(v >> 32), s, 64);
   return ((uint64_t)hi << 32) | lo;
-}
-
-// Exclusive scan of one value per thread over the DB_THREADS threads of the workgroup; *total = the sum.
-__device__ __forceinline__ uint32_t db_block_scan(uint32_t v, uint32_t *wave_sum /* LDS [DB_WAVES] */, uint32_t *total) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(incl, d, 64);
-    if ((int)lane >= d) incl += o;
-  }
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  uint32_t run = incl - v, tot = 0;
-  for (uint32_t w = 0; w < (uint32_t)DB_WAVES; w++) {
-    const uint32_t x = wave_sum[w];
-    if (w < wave) run += x;
-    tot += x;
-  }
-  *total = tot;
-  __syncthreads();                                       // (wave_sum may be written again)
-  return run;
 }
 
 // grid (batch), DB_THREADS threads.  Layouts [batch][stride]; idf [nwords] or null (= 1 for every word).
@@ -138,7 +116,7 @@ __global__ __launch_bounds__(DB_THREADS) void k_db_scan_chunks(const uint32_t *_
   __shared__ uint32_t wave_sum[DB_WAVES];
   const uint32_t i0 = blockIdx.x * (uint32_t)DB_SCAN_CHUNK + threadIdx.x * (uint32_t)DB_SCAN_PER_THREAD;
   uint32_t total;
-  (void)db_block_scan(db_chunk_sum(cnt, nwords, i0), wave_sum, &total);
+  (void)pm::block_scan<DB_THREADS>(db_chunk_sum(cnt, nwords, i0), wave_sum, &total);
   if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 
@@ -147,7 +125,7 @@ __global__ __launch_bounds__(DB_THREADS) void k_db_scan_sums(uint32_t nchunks, u
                                                              uint32_t *__restrict__ word_off) {
   __shared__ uint32_t wave_sum[DB_WAVES];
   uint32_t total;
-  const uint32_t run = db_block_scan(threadIdx.x < nchunks ? bsum[threadIdx.x] : 0u, wave_sum, &total);
+  const uint32_t run = pm::block_scan<DB_THREADS>(threadIdx.x < nchunks ? bsum[threadIdx.x] : 0u, wave_sum, &total);
   if (threadIdx.x < nchunks) bsum[threadIdx.x] = run;
   if (threadIdx.x == 0) word_off[nwords] = total;
 }
@@ -160,7 +138,7 @@ __global__ __launch_bounds__(DB_THREADS) void k_db_scan_offsets(const uint32_t *
   __shared__ uint32_t wave_sum[DB_WAVES];
   const uint32_t i0 = blockIdx.x * (uint32_t)DB_SCAN_CHUNK + threadIdx.x * (uint32_t)DB_SCAN_PER_THREAD;
   uint32_t total;
-  uint32_t run = db_block_scan(db_chunk_sum(cnt, nwords, i0), wave_sum, &total) + bsum[blockIdx.x];
+  uint32_t run = pm::block_scan<DB_THREADS>(db_chunk_sum(cnt, nwords, i0), wave_sum, &total) + bsum[blockIdx.x];
   for (int k = 0; k < DB_SCAN_PER_THREAD; k++) {
     const uint32_t i = i0 + k;
     if (i >= nwords) break;

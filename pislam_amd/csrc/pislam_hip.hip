@@ -12,6 +12,7 @@
 #include <cmath>
 #include <functional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pislam_hip.h"
@@ -2240,9 +2241,50 @@ PISLAM_EXPORT int pislam_debug_shader_clock(pislam_ctx *c, int micros, double *g
 
 namespace {
 
+// Argument checks the matchers, the bag-of-words calls and the key-frame database share.
+int check_words(pislam_ctx *c, int words) {
+  if (words != 1 && words != 2 && words != 4 && words != 8) return fail(c, PISLAM_ERR_INVALID, "words must be 1, 2, 4 or 8");
+  return PISLAM_OK;
+}
+int check_batch(pislam_ctx *c, int batch) {                                   // (a batch is the grid's y or x extent)
+  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
+  return PISLAM_OK;
+}
+int check_train_stride(pislam_ctx *c, size_t t_stride, const char *what) {   // (the match keys hold a 16-bit train index)
+  if (t_stride > 65535) return fail(c, PISLAM_ERR_INVALID, what);
+  return PISLAM_OK;
+}
+
+// f(std::integral_constant<int, W>{}) for W = words, which check_words accepted.
+template <class F>
+void with_words(int words, F &&f) {
+  switch (words) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+  }
+}
+
+// The same for sad_radius, which stereo_plan accepted (1..pm::ST_MAX_W).
+template <class F>
+void with_sad_radius(int sad_radius, F &&f) {
+  switch (sad_radius) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    default: f(std::integral_constant<int, 7>{}); break;
+  }
+}
+
 int launch_match(pislam_ctx *c, int words, const uint32_t *q, const uint32_t *qc, size_t q_stride, uint32_t nq,
                  const uint32_t *t, const uint32_t *tc, size_t t_stride, uint32_t nt, int batch, uint32_t max_q,
                  int32_t *idx, uint32_t *dist, uint32_t *dist2, size_t out_stride) {
+  PCHK(check_words(c, words));
+  const uint32_t cap_q = (uint32_t)std::min<size_t>(q_stride, 0xffffffffu), cap_t = (uint32_t)std::min<size_t>(t_stride, 65535);
   if (c->opt_match_mfma) {
     // matrix-core path (v_mfma_i32_32x32x32_i8): 4 waves x 32 queries per workgroup pass
     // query blocks per pair in flight: the batch API only knows the capacity (the counts live on the device), and a
@@ -2250,33 +2292,19 @@ int launch_match(pislam_ctx *c, int words, const uint32_t *q, const uint32_t *qc
     // 0.27 ms against 0.09 ms with 8), so the grid aims at ~8 workgroups per CU and the workgroups loop
     const int per_pair = batch > 1 ? std::max(1, std::min(cdiv((int)max_q, pm::MF_Q), cdiv(8 * std::max(1, c->num_cus), batch))) : 65535;
     const dim3 mgrid((unsigned)std::min(cdiv((int)max_q, pm::MF_Q), per_pair), (unsigned)batch);
-#define PISLAM_MATCH_MFMA(W)                                                                                  \
-  hipLaunchKernelGGL(pm::k_match_mfma<W>, mgrid, dim3(64 * pm::MF_WAVES), 0, c->stream, q, qc, q_stride * W, nq, t, tc, \
-                     t_stride * W, nt, (uint32_t)std::min<size_t>(q_stride, 0xffffffffu),                   \
-                     (uint32_t)std::min<size_t>(t_stride, 65535), idx, dist, dist2, out_stride)
-    switch (words) {
-      case 1: PISLAM_MATCH_MFMA(1); break;
-      case 2: PISLAM_MATCH_MFMA(2); break;
-      case 4: PISLAM_MATCH_MFMA(4); break;
-      case 8: PISLAM_MATCH_MFMA(8); break;
-      default: return fail(c, PISLAM_ERR_INVALID, "words must be 1, 2, 4 or 8");
-    }
-#undef PISLAM_MATCH_MFMA
+    with_words(words, [&](auto w) {
+      constexpr int W = decltype(w)::value;
+      hipLaunchKernelGGL(pm::k_match_mfma<W>, mgrid, dim3(64 * pm::MF_WAVES), 0, c->stream, q, qc, q_stride * W, nq, t, tc,
+                         t_stride * W, nt, cap_q, cap_t, idx, dist, dist2, out_stride);
+    });
     return launch_ok(c, "k_match_mfma");
   }
   const dim3 grid((unsigned)std::min(cdiv((int)max_q, pm::QPW), batch > 1 ? pm::MAX_GRID_X : 65535), (unsigned)batch);
-#define PISLAM_MATCH(W)                                                                                       \
-  hipLaunchKernelGGL(pm::k_match<W>, grid, dim3(pm::QPW * pm::SPLIT), 0, c->stream, q, qc, q_stride * W, nq, t, tc, t_stride * W, \
-                     nt, (uint32_t)std::min<size_t>(q_stride, 0xffffffffu), (uint32_t)std::min<size_t>(t_stride, 65535), \
-                     idx, dist, dist2, out_stride)
-  switch (words) {
-    case 1: PISLAM_MATCH(1); break;
-    case 2: PISLAM_MATCH(2); break;
-    case 4: PISLAM_MATCH(4); break;
-    case 8: PISLAM_MATCH(8); break;
-    default: return fail(c, PISLAM_ERR_INVALID, "words must be 1, 2, 4 or 8");
-  }
-#undef PISLAM_MATCH
+  with_words(words, [&](auto w) {
+    constexpr int W = decltype(w)::value;
+    hipLaunchKernelGGL(pm::k_match<W>, grid, dim3(pm::QPW * pm::SPLIT), 0, c->stream, q, qc, q_stride * W, nq, t, tc,
+                       t_stride * W, nt, cap_q, cap_t, idx, dist, dist2, out_stride);
+  });
   return launch_ok(c, "k_match");
 }
 
@@ -2286,7 +2314,7 @@ PISLAM_EXPORT int pislam_match_hamming(pislam_ctx *c, int words, const uint32_t 
                                        const uint32_t *train, size_t nt, int32_t *idx, uint32_t *dist,
                                        uint32_t *dist2) {
   if (!c) return PISLAM_ERR_INVALID;
-  if (words != 1 && words != 2 && words != 4 && words != 8) return fail(c, PISLAM_ERR_INVALID, "words must be 1, 2, 4 or 8");
+  PCHK(check_words(c, words));
   if (nt > 65535) return fail(c, PISLAM_ERR_INVALID, "at most 65535 train descriptors");
   if (nq > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "too many query descriptors");
   if (nq == 0) return PISLAM_OK;
@@ -2312,8 +2340,8 @@ PISLAM_EXPORT int pislam_match_hamming_batch(pislam_ctx *c, int words, const uin
                                              const uint32_t *tcounts, size_t t_stride, int batch, int32_t *idx,
                                              uint32_t *dist, uint32_t *dist2) {
   if (!c) return PISLAM_ERR_INVALID;
-  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
-  if (t_stride > 65535) return fail(c, PISLAM_ERR_INVALID, "at most 65535 train descriptors per pair");
+  PCHK(check_batch(c, batch));
+  PCHK(check_train_stride(c, t_stride, "at most 65535 train descriptors per pair"));
   if (q_stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "q_stride too large");
   if (batch == 0 || q_stride == 0) return PISLAM_OK;
   if (!query || !train || !qcounts || !tcounts || !idx || !dist || !dist2) return fail(c, PISLAM_ERR_INVALID, "null pointer");
@@ -2336,12 +2364,12 @@ namespace {
 // do not depend on the side: the match applies the exact window test.
 int scaled_plan(pislam_ctx *c, int words, const pislam_level *lv, int nlevels, const int32_t *scale_q16,
                 const int32_t *radius0, int level_span, size_t t_stride, int batch, pm::ScaledPlan *P) {
-  if (words != 1 && words != 2 && words != 4 && words != 8) return fail(c, PISLAM_ERR_INVALID, "words must be 1, 2, 4 or 8");
+  PCHK(check_words(c, words));
   if (nlevels < 1 || nlevels > pm::WIN_MAX_LEVELS) return fail(c, PISLAM_ERR_INVALID, "nlevels must be 1..16");
   if (!lv || !scale_q16 || !radius0) return fail(c, PISLAM_ERR_INVALID, "null levels / scale_q16 / radius0");
   if (level_span < 0 || level_span > nlevels - 1) return fail(c, PISLAM_ERR_INVALID, "level_span must be 0..nlevels-1");
-  if (t_stride > 65535) return fail(c, PISLAM_ERR_INVALID, "at most 65535 train entries per pair");
-  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
+  PCHK(check_train_stride(c, t_stride, "at most 65535 train entries per pair"));
+  PCHK(check_batch(c, batch));
   int32_t ext_x[pm::WIN_MAX_LEVELS], ext_y[pm::WIN_MAX_LEVELS];
   for (int l = 0; l < nlevels; l++) {
     const pislam_level &L = lv[l];
@@ -2400,10 +2428,12 @@ int window_plan(pislam_ctx *c, int words, const pislam_level *lv, int nlevels, c
   return scaled_plan(c, words, lv, nlevels, unit, radius, 0, t_stride, batch, P);
 }
 
-int cell_workspace(pislam_ctx *c, pislam_ctx::CellIndex &w, const pm::ScaledPlan &P, int words, size_t t_stride,
-                   int batch, const char *what) {
-  if (w.off.ensure(sizeof(uint32_t) * (size_t)(P.ncells + 1) * batch) != PISLAM_OK ||
-      w.meta.ensure(sizeof(uint2) * t_stride * batch) != PISLAM_OK ||
+// The workspace of an index kernel (pm::lds_counting_sort): noffsets offsets per pair, and per train entry meta_bytes of
+// metadata and the descriptor.
+int index_workspace(pislam_ctx *c, pislam_ctx::CellIndex &w, size_t noffsets, size_t meta_bytes, int words, size_t t_stride,
+                    int batch, const char *what) {
+  if (w.off.ensure(sizeof(uint32_t) * noffsets * batch) != PISLAM_OK ||
+      w.meta.ensure(meta_bytes * t_stride * batch) != PISLAM_OK ||
       w.desc.ensure(sizeof(uint32_t) * words * t_stride * batch) != PISLAM_OK)
     return fail(c, PISLAM_ERR_NOMEM, what);
   return PISLAM_OK;
@@ -2426,31 +2456,32 @@ dim3 query_grid(const pislam_ctx *c, size_t q_stride, int qpw, int batch) {
   return dim3((unsigned)per_pair, (unsigned)batch);
 }
 
+// pm::k_scaled_index of the train entries into workspace w (arguments checked, w reserved).
+int launch_scaled_index(pislam_ctx *c, const pislam_ctx::CellIndex &w, const pm::ScaledPlan &P, int words,
+                        const uint32_t *kp, const uint32_t *desc, const uint32_t *counts, size_t stride, int batch) {
+  hipLaunchKernelGGL(pm::k_scaled_index, dim3((unsigned)batch), dim3(pm::WIN_INDEX_THREADS), 0, c->stream, P, words, kp,
+                     desc, counts, stride, w.off.as<uint32_t>(), w.meta.as<uint2>(), w.desc.as<uint32_t>());
+  return launch_ok(c, "k_scaled_index");
+}
+
 // Index + match of the windowed and the scaled call (arguments checked, workspace w reserved).
 int launch_guided(pislam_ctx *c, const pislam_ctx::CellIndex &w, const pm::ScaledPlan &P, int words, const uint32_t *qkp,
                   const uint32_t *qdesc, const uint32_t *qcounts, const int32_t *qpred, size_t q_stride,
                   const uint32_t *tkp, const uint32_t *tdesc, const uint32_t *tcounts, size_t t_stride, int batch,
                   int32_t *idx, uint32_t *dist, uint32_t *dist2) {
-  uint32_t *off = w.off.as<uint32_t>(), *edesc = w.desc.as<uint32_t>();
-  uint2 *meta = w.meta.as<uint2>();
-  hipLaunchKernelGGL(pm::k_scaled_index, dim3((unsigned)batch), dim3(pm::WIN_INDEX_THREADS), 0, c->stream, P, words, tkp,
-                     tdesc, tcounts, t_stride, off, meta, edesc);
-  PCHK(launch_ok(c, "k_scaled_index"));
+  PCHK(launch_scaled_index(c, w, P, words, tkp, tdesc, tcounts, t_stride, batch));
   const dim3 grid = query_grid(c, q_stride, pm::WIN_QPW, batch);
-#define PISLAM_MATCH_SCALED(W)                                                                                           \
-  if (P.span == 0)                                                                                                       \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(pm::k_match_scaled<W, true>), grid, dim3(pm::WIN_THREADS), 0, c->stream, P, qkp,  \
-                       qdesc, qcounts, qpred, q_stride, t_stride, off, meta, edesc, idx, dist, dist2);                   \
-  else                                                                                                                   \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(pm::k_match_scaled<W, false>), grid, dim3(pm::WIN_THREADS), 0, c->stream, P, qkp, \
-                       qdesc, qcounts, qpred, q_stride, t_stride, off, meta, edesc, idx, dist, dist2)
-  switch (words) {
-    case 1: PISLAM_MATCH_SCALED(1); break;
-    case 2: PISLAM_MATCH_SCALED(2); break;
-    case 4: PISLAM_MATCH_SCALED(4); break;
-    default: PISLAM_MATCH_SCALED(8); break;            // (scaled_plan accepted only 1, 2, 4, 8)
-  }
-#undef PISLAM_MATCH_SCALED
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(pm::WIN_THREADS), 0, c->stream, P, qkp, qdesc, qcounts, qpred, q_stride, t_stride,
+                       w.off.as<uint32_t>(), w.meta.as<uint2>(), w.desc.as<uint32_t>(), idx, dist, dist2);
+  };
+  with_words(words, [&](auto wd) {
+    constexpr int W = decltype(wd)::value;
+    if (P.span == 0)
+      launch(pm::k_match_scaled<W, true>);
+    else
+      launch(pm::k_match_scaled<W, false>);
+  });
   return launch_ok(c, "k_match_scaled");
 }
 
@@ -2462,7 +2493,8 @@ PISLAM_EXPORT int pislam_match_window_reserve(pislam_ctx *c, int words, const pi
   pm::ScaledPlan P;
   PCHK(window_plan(c, words, levels, nlevels, radius, t_stride, batch, &P));
   HIPCHK(c, hipSetDevice(c->device));
-  return cell_workspace(c, c->w_win, P, words, t_stride, batch, "hipMalloc(window matcher workspace)");
+  return index_workspace(c, c->w_win, (size_t)P.ncells + 1, sizeof(uint2), words, t_stride, batch,
+                         "hipMalloc(window matcher workspace)");
 }
 
 PISLAM_EXPORT int pislam_match_hamming_window_batch(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
@@ -2478,7 +2510,8 @@ PISLAM_EXPORT int pislam_match_hamming_window_batch(pislam_ctx *c, int words, co
   PCHK(device_ptrs(c, {qkp, qdesc, qcounts, tkp, tdesc, tcounts, idx, dist, dist2},
                    "the window matcher takes device pointers only"));
   HIPCHK(c, hipSetDevice(c->device));
-  PCHK(cell_workspace(c, c->w_win, P, words, t_stride, batch, "hipMalloc(window matcher workspace)"));
+  PCHK(index_workspace(c, c->w_win, (size_t)P.ncells + 1, sizeof(uint2), words, t_stride, batch,
+                       "hipMalloc(window matcher workspace)"));
   return launch_guided(c, c->w_win, P, words, qkp, qdesc, qcounts, nullptr, q_stride, tkp, tdesc, tcounts, t_stride, batch,
                        idx, dist, dist2);
 }
@@ -2490,7 +2523,8 @@ PISLAM_EXPORT int pislam_match_scaled_window_reserve(pislam_ctx *c, int words, c
   pm::ScaledPlan P;
   PCHK(scaled_plan(c, words, levels, nlevels, scale_q16, radius0, level_span, t_stride, batch, &P));
   HIPCHK(c, hipSetDevice(c->device));
-  return cell_workspace(c, c->w_sc, P, words, t_stride, batch, "hipMalloc(scaled window matcher workspace)");
+  return index_workspace(c, c->w_sc, (size_t)P.ncells + 1, sizeof(uint2), words, t_stride, batch,
+                         "hipMalloc(scaled window matcher workspace)");
 }
 
 PISLAM_EXPORT int pislam_match_hamming_scaled_window_batch(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
@@ -2508,7 +2542,8 @@ PISLAM_EXPORT int pislam_match_hamming_scaled_window_batch(pislam_ctx *c, int wo
   PCHK(device_ptrs(c, {qkp, qdesc, qcounts, tkp, tdesc, tcounts, idx, dist, dist2},
                    "the scaled window matcher takes device pointers only"));
   HIPCHK(c, hipSetDevice(c->device));
-  PCHK(cell_workspace(c, c->w_sc, P, words, t_stride, batch, "hipMalloc(scaled window matcher workspace)"));
+  PCHK(index_workspace(c, c->w_sc, (size_t)P.ncells + 1, sizeof(uint2), words, t_stride, batch,
+                       "hipMalloc(scaled window matcher workspace)"));
   return launch_guided(c, c->w_sc, P, words, qkp, qdesc, qcounts, qpred, q_stride, tkp, tdesc, tcounts, t_stride, batch,
                        idx, dist, dist2);
 }
@@ -2544,7 +2579,8 @@ PISLAM_EXPORT int pislam_match_stereo_reserve(pislam_ctx *c, int words, const pi
   pm::ScaledPlan P;
   PCHK(stereo_plan(c, words, levels, nlevels, scale_q16, row_radius0, p, r_stride, batch, &P));
   HIPCHK(c, hipSetDevice(c->device));
-  return cell_workspace(c, c->w_st, P, words, r_stride, batch, "hipMalloc(stereo matcher workspace)");
+  return index_workspace(c, c->w_st, (size_t)P.ncells + 1, sizeof(uint2), words, r_stride, batch,
+                         "hipMalloc(stereo matcher workspace)");
 }
 
 PISLAM_EXPORT int pislam_match_stereo_batch(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
@@ -2568,40 +2604,24 @@ PISLAM_EXPORT int pislam_match_stereo_batch(pislam_ctx *c, int words, const pisl
   PCHK(device_ptrs(c, {left_pyr, right_pyr, lkp, ldesc, lcounts, rkp, rdesc, rcounts, idx, dist, disp_q8, sad},
                    "the stereo matcher takes device pointers only"));
   HIPCHK(c, hipSetDevice(c->device));
-  PCHK(cell_workspace(c, c->w_st, P, words, r_stride, batch, "hipMalloc(stereo matcher workspace)"));
-  uint32_t *off = c->w_st.off.as<uint32_t>(), *edesc = c->w_st.desc.as<uint32_t>();
-  uint2 *meta = c->w_st.meta.as<uint2>();
+  PCHK(index_workspace(c, c->w_st, (size_t)P.ncells + 1, sizeof(uint2), words, r_stride, batch,
+                       "hipMalloc(stereo matcher workspace)"));
   if (l_stride > 0) {
-    hipLaunchKernelGGL(pm::k_scaled_index, dim3((unsigned)batch), dim3(pm::WIN_INDEX_THREADS), 0, c->stream, P, words,
-                       rkp, rdesc, rcounts, r_stride, off, meta, edesc);
-    PCHK(launch_ok(c, "k_scaled_index"));
+    const pislam_ctx::CellIndex &w = c->w_st;
+    PCHK(launch_scaled_index(c, w, P, words, rkp, rdesc, rcounts, r_stride, batch));
     const dim3 grid = query_grid(c, l_stride, pm::WIN_QPW, batch);
-#define PISLAM_MATCH_STEREO(W)                                                                                           \
-    hipLaunchKernelGGL(pm::k_match_stereo<W>, grid, dim3(pm::WIN_THREADS), 0, c->stream, P, p->min_disp, p->max_disp,    \
-                       lkp, ldesc, lcounts, l_stride, r_stride, off, meta, edesc, idx, dist)
-    switch (words) {
-      case 1: PISLAM_MATCH_STEREO(1); break;
-      case 2: PISLAM_MATCH_STEREO(2); break;
-      case 4: PISLAM_MATCH_STEREO(4); break;
-      default: PISLAM_MATCH_STEREO(8); break;          // (stereo_plan accepted only 1, 2, 4, 8)
-    }
-#undef PISLAM_MATCH_STEREO
+    with_words(words, [&](auto wd) {
+      hipLaunchKernelGGL(pm::k_match_stereo<decltype(wd)::value>, grid, dim3(pm::WIN_THREADS), 0, c->stream, P, p->min_disp,
+                         p->max_disp, lkp, ldesc, lcounts, l_stride, r_stride, w.off.as<uint32_t>(), w.meta.as<uint2>(),
+                         w.desc.as<uint32_t>(), idx, dist);
+    });
     PCHK(launch_ok(c, "k_match_stereo"));
     const dim3 rgrid = query_grid(c, l_stride, pm::ST_QPW, batch);
-#define PISLAM_STEREO_REFINE(W)                                                                                          \
-    hipLaunchKernelGGL(pm::k_stereo_refine<W>, rgrid, dim3(pm::ST_THREADS), 0, c->stream, P, (uint32_t)p->max_hamming,    \
-                       p->search_radius, p->min_disp, p->max_disp, left_pyr, right_pyr, vstep, pyramid_stride, lkp,      \
-                       lcounts, l_stride, rkp, r_stride, idx, dist, disp_q8, sad)
-    switch (p->sad_radius) {
-      case 1: PISLAM_STEREO_REFINE(1); break;
-      case 2: PISLAM_STEREO_REFINE(2); break;
-      case 3: PISLAM_STEREO_REFINE(3); break;
-      case 4: PISLAM_STEREO_REFINE(4); break;
-      case 5: PISLAM_STEREO_REFINE(5); break;
-      case 6: PISLAM_STEREO_REFINE(6); break;
-      default: PISLAM_STEREO_REFINE(7); break;         // (stereo_plan accepted only 1..7)
-    }
-#undef PISLAM_STEREO_REFINE
+    with_sad_radius(p->sad_radius, [&](auto r) {
+      hipLaunchKernelGGL(pm::k_stereo_refine<decltype(r)::value>, rgrid, dim3(pm::ST_THREADS), 0, c->stream, P,
+                         (uint32_t)p->max_hamming, p->search_radius, p->min_disp, p->max_disp, left_pyr, right_pyr, vstep,
+                         pyramid_stride, lkp, lcounts, l_stride, rkp, r_stride, idx, dist, disp_q8, sad);
+    });
     PCHK(launch_ok(c, "k_stereo_refine"));
   }
   if (p->median_filter || nstereo) {
@@ -2626,7 +2646,7 @@ PISLAM_EXPORT int pislam_vocab_create(pislam_ctx *c, int words, int nnodes, cons
   if (!c) return PISLAM_ERR_INVALID;
   if (!vocab) return fail(c, PISLAM_ERR_INVALID, "null vocabulary pointer");
   *vocab = nullptr;
-  if (words != 1 && words != 2 && words != 4 && words != 8) return fail(c, PISLAM_ERR_INVALID, "words must be 1, 2, 4 or 8");
+  PCHK(check_words(c, words));
   if (nnodes < 2 || nnodes > (1 << 24)) return fail(c, PISLAM_ERR_INVALID, "nnodes must be 2..2^24");
   if (group_depth < 0 || group_depth > pb::BOW_MAX_DEPTH) return fail(c, PISLAM_ERR_INVALID, "group_depth must be 0..16");
   if (!node_desc || !first_child || !child_count) return fail(c, PISLAM_ERR_INVALID, "null node_desc / first_child / child_count");
@@ -2701,7 +2721,7 @@ PISLAM_EXPORT int pislam_bow_transform_batch(pislam_ctx *c, const pislam_vocab *
   if (!c) return PISLAM_ERR_INVALID;
   if (!v) return fail(c, PISLAM_ERR_INVALID, "null vocabulary");
   if (v->device != c->device) return fail(c, PISLAM_ERR_INVALID, "the vocabulary lives on another device");
-  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
+  PCHK(check_batch(c, batch));
   if (stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "stride too large");
   if (group && !is_device_ptr(group)) return fail(c, PISLAM_ERR_INVALID, "group must be a device pointer or null");
   if (wdist && !is_device_ptr(wdist)) return fail(c, PISLAM_ERR_INVALID, "wdist must be a device pointer or null");
@@ -2711,23 +2731,17 @@ PISLAM_EXPORT int pislam_bow_transform_batch(pislam_ctx *c, const pislam_vocab *
   const dim3 grid = query_grid(c, stride, pb::BOW_DPW, batch);
   const uint32_t *nd = v->desc.as<uint32_t>();
   const uint2 *nm = v->meta.as<uint2>();
-#define PISLAM_BOW_DESCEND(W)                                                                                            \
-  hipLaunchKernelGGL(pb::k_bow_descend<W>, grid, dim3(pb::BOW_THREADS), 0, c->stream, nd, nm, desc, counts, stride, word, \
-                     group, wdist)
-  switch (v->words) {
-    case 1: PISLAM_BOW_DESCEND(1); break;
-    case 2: PISLAM_BOW_DESCEND(2); break;
-    case 4: PISLAM_BOW_DESCEND(4); break;
-    default: PISLAM_BOW_DESCEND(8); break;             // (pislam_vocab_create accepted only 1, 2, 4, 8)
-  }
-#undef PISLAM_BOW_DESCEND
+  with_words(v->words, [&](auto w) {
+    hipLaunchKernelGGL(pb::k_bow_descend<decltype(w)::value>, grid, dim3(pb::BOW_THREADS), 0, c->stream, nd, nm, desc, counts,
+                       stride, word, group, wdist);
+  });
   return launch_ok(c, "k_bow_descend");
 }
 
 PISLAM_EXPORT int pislam_bow_vector_batch(pislam_ctx *c, const uint32_t *word, const uint32_t *counts, size_t stride,
                                           int batch, uint32_t *bow_word, uint32_t *bow_tf, uint32_t *bow_n) {
   if (!c) return PISLAM_ERR_INVALID;
-  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
+  PCHK(check_batch(c, batch));
   if (stride > (size_t)pb::BOW_VEC_MAX) return fail(c, PISLAM_ERR_INVALID, "stride must be at most 16384");
   if (batch == 0) return PISLAM_OK;
   if (stride == 0) {                                    // no slot to read or write but the numbers
@@ -2744,20 +2758,10 @@ PISLAM_EXPORT int pislam_bow_vector_batch(pislam_ctx *c, const uint32_t *word, c
 namespace {
 
 int bow_match_args(pislam_ctx *c, int words, int ngroups, size_t t_stride, int batch) {
-  if (words != 1 && words != 2 && words != 4 && words != 8) return fail(c, PISLAM_ERR_INVALID, "words must be 1, 2, 4 or 8");
+  PCHK(check_words(c, words));
   if (ngroups < 1 || ngroups > pb::BOW_MAX_GROUPS) return fail(c, PISLAM_ERR_INVALID, "ngroups must be 1..16384");
-  if (t_stride > 65535) return fail(c, PISLAM_ERR_INVALID, "at most 65535 train entries per pair");
-  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
-  return PISLAM_OK;
-}
-
-int bow_workspace(pislam_ctx *c, int words, int ngroups, size_t t_stride, int batch) {
-  pislam_ctx::CellIndex &w = c->w_bow;
-  if (w.off.ensure(sizeof(uint32_t) * (size_t)(ngroups + 1) * batch) != PISLAM_OK ||
-      w.meta.ensure(sizeof(uint32_t) * t_stride * batch) != PISLAM_OK ||
-      w.desc.ensure(sizeof(uint32_t) * words * t_stride * batch) != PISLAM_OK)
-    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(word-guided matcher workspace)");
-  return PISLAM_OK;
+  PCHK(check_train_stride(c, t_stride, "at most 65535 train entries per pair"));
+  return check_batch(c, batch);
 }
 
 }  // namespace
@@ -2766,7 +2770,8 @@ PISLAM_EXPORT int pislam_match_bow_reserve(pislam_ctx *c, int words, int ngroups
   if (!c) return PISLAM_ERR_INVALID;
   PCHK(bow_match_args(c, words, ngroups, t_stride, batch));
   HIPCHK(c, hipSetDevice(c->device));
-  return bow_workspace(c, words, ngroups, t_stride, batch);
+  return index_workspace(c, c->w_bow, (size_t)ngroups + 1, sizeof(uint32_t), words, t_stride, batch,
+                         "hipMalloc(word-guided matcher workspace)");
 }
 
 PISLAM_EXPORT int pislam_match_hamming_bow_batch(pislam_ctx *c, int words, int ngroups, const uint32_t *qdesc,
@@ -2781,22 +2786,17 @@ PISLAM_EXPORT int pislam_match_hamming_bow_batch(pislam_ctx *c, int words, int n
   PCHK(device_ptrs(c, {qdesc, qgroup, qcounts, tdesc, tgroup, tcounts, idx, dist, dist2},
                    "the word-guided matcher takes device pointers only"));
   HIPCHK(c, hipSetDevice(c->device));
-  PCHK(bow_workspace(c, words, ngroups, t_stride, batch));
+  PCHK(index_workspace(c, c->w_bow, (size_t)ngroups + 1, sizeof(uint32_t), words, t_stride, batch,
+                       "hipMalloc(word-guided matcher workspace)"));
   uint32_t *off = c->w_bow.off.as<uint32_t>(), *eidx = c->w_bow.meta.as<uint32_t>(), *edesc = c->w_bow.desc.as<uint32_t>();
   hipLaunchKernelGGL(pb::k_bow_index, dim3((unsigned)batch), dim3(pm::WIN_INDEX_THREADS), 0, c->stream, (uint32_t)ngroups,
                      words, tgroup, tdesc, tcounts, t_stride, off, eidx, edesc);
   PCHK(launch_ok(c, "k_bow_index"));
   const dim3 grid = query_grid(c, q_stride, pm::WIN_QPW, batch);
-#define PISLAM_MATCH_BOW(W)                                                                                              \
-  hipLaunchKernelGGL(pb::k_match_bow<W>, grid, dim3(pm::WIN_THREADS), 0, c->stream, (uint32_t)ngroups, qdesc, qgroup,    \
-                     qcounts, q_stride, t_stride, off, eidx, edesc, idx, dist, dist2)
-  switch (words) {
-    case 1: PISLAM_MATCH_BOW(1); break;
-    case 2: PISLAM_MATCH_BOW(2); break;
-    case 4: PISLAM_MATCH_BOW(4); break;
-    default: PISLAM_MATCH_BOW(8); break;               // (bow_match_args accepted only 1, 2, 4, 8)
-  }
-#undef PISLAM_MATCH_BOW
+  with_words(words, [&](auto w) {
+    hipLaunchKernelGGL(pb::k_match_bow<decltype(w)::value>, grid, dim3(pm::WIN_THREADS), 0, c->stream, (uint32_t)ngroups, qdesc,
+                       qgroup, qcounts, q_stride, t_stride, off, eidx, edesc, idx, dist, dist2);
+  });
   return launch_ok(c, "k_match_bow");
 }
 
@@ -2837,9 +2837,9 @@ PISLAM_EXPORT int pislam_match_select_batch(pislam_ctx *c, const pislam_select_p
   if (p->unique != 0 && p->unique != 1) return fail(c, PISLAM_ERR_INVALID, "unique must be 0 or 1");
   if (p->rot_keep < 0 || p->rot_keep > ps::SEL_BINS) return fail(c, PISLAM_ERR_INVALID, "rot_keep must be 0..30");
   if (p->rot_min_pct < 0 || p->rot_min_pct > 100) return fail(c, PISLAM_ERR_INVALID, "rot_min_pct must be 0..100");
-  if (t_stride > 65535) return fail(c, PISLAM_ERR_INVALID, "at most 65535 train entries per pair");
+  PCHK(check_train_stride(c, t_stride, "at most 65535 train entries per pair"));
   if (q_stride < 1 || q_stride > ((size_t)1 << 22)) return fail(c, PISLAM_ERR_INVALID, "q_stride must be 1..2^22");
-  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
+  PCHK(check_batch(c, batch));
   if (!dist2 && p->ratio_den != 0) return fail(c, PISLAM_ERR_INVALID, "a ratio test needs dist2");
   if ((p->rot_keep > 0) != (qangle != nullptr) || (p->rot_keep > 0) != (tangle != nullptr))
     return fail(c, PISLAM_ERR_INVALID, "qangle and tangle go with rot_keep > 0, and only with it");
@@ -2867,7 +2867,7 @@ PISLAM_EXPORT int pislam_bow_weight_batch(pislam_ctx *c, const uint32_t *bow_wor
                                           const uint32_t *bow_n, size_t stride, int batch, const uint32_t *idf,
                                           uint32_t nwords, uint32_t *bow_weight) {
   if (!c) return PISLAM_ERR_INVALID;
-  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
+  PCHK(check_batch(c, batch));
   if (stride > (size_t)pd::DB_MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be at most 16384");
   if (idf && !is_device_ptr(idf)) return fail(c, PISLAM_ERR_INVALID, "idf must be a device pointer or null");
   if (batch == 0 || stride == 0) return PISLAM_OK;
@@ -2923,7 +2923,7 @@ DbQueryPlan db_query_plan(int capacity, int batch, int topk) {
 int db_query_args(pislam_ctx *c, const pislam_bowdb *db, int batch, int topk) {
   if (!db) return fail(c, PISLAM_ERR_INVALID, "null database");
   if (db->device != c->device) return fail(c, PISLAM_ERR_INVALID, "the database lives on another device");
-  if (batch < 0 || batch > 65535) return fail(c, PISLAM_ERR_INVALID, "batch must be 0..65535");
+  PCHK(check_batch(c, batch));
   if (topk < 1 || topk > pd::DB_MAX_TOPK) return fail(c, PISLAM_ERR_INVALID, "topk must be 1..64");
   return PISLAM_OK;
 }

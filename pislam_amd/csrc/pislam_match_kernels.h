@@ -18,6 +18,118 @@ namespace pm {
 
 constexpr int MAX_WORDS = 16;
 
+// ---------------------------------------------------------------------------
+// Pieces the matchers, the bag-of-words kernels (pislam_bow_kernels.h) and the key-frame database
+// (pislam_bowdb_kernels.h) share: the workgroup scan, the LDS counting sort of the two index kernels, and the
+// (best, second) bookkeeping of the match kernels.
+// ---------------------------------------------------------------------------
+
+// Exclusive scan of one value per thread over the THREADS threads of the workgroup: returns the sum over the threads
+// below this one, *total = the sum over all.  wave_sum: LDS [THREADS / 64].  The one barrier lies between writing and
+// reading wave_sum; a caller that writes wave_sum again afterwards puts its own barrier in between.
+template <int THREADS>
+__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t *wave_sum, uint32_t *total) {
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t incl = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t o = __shfl_up(incl, d, 64);
+    if ((int)lane >= d) incl += o;
+  }
+  if (lane == 63) wave_sum[wave] = incl;
+  __syncthreads();
+  uint32_t run = incl - v, tot = 0;
+  for (uint32_t w = 0; w < (uint32_t)(THREADS / 64); w++) {
+    const uint32_t x = wave_sum[w];
+    if (w < wave) run += x;
+    tot += x;
+  }
+  *total = tot;
+  return run;
+}
+
+// Counting sort of entries 0 .. n - 1 into nbins bins by one workgroup of THREADS threads: histogram with LDS atomics,
+// exclusive scan (every thread sums a contiguous chunk of bins, block_scan over the chunk sums), then the scatter.
+// hist: LDS [>= nbins], wave_sum: LDS [THREADS / 64], off: the pair's offset row in global memory, off[c] = first slot
+// of bin c and off[nbins] = entries indexed.  bin_of(j) is the bin of entry j, negative for an entry that is not
+// indexed; it is evaluated in the count pass and again in the scatter pass, where place(slot, j) follows it at once in
+// the same thread (so place may use what bin_of left behind).  Slot order inside a bin varies between runs.
+template <int THREADS, class BinOf, class Place>
+__device__ __forceinline__ void lds_counting_sort(uint32_t nbins, uint32_t n, uint32_t *hist, uint32_t *wave_sum,
+                                                  uint32_t *__restrict__ off, BinOf &&bin_of, Place &&place) {
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t c = tid; c < nbins; c += THREADS) hist[c] = 0;
+  __syncthreads();
+  for (uint32_t j = tid; j < n; j += THREADS) {
+    const int32_t c = bin_of(j);
+    if (c >= 0) atomicAdd(&hist[c], 1u);
+  }
+  __syncthreads();
+  const uint32_t chunk = (nbins + THREADS - 1) / THREADS;
+  const uint32_t c0 = min(tid * chunk, nbins), c1 = min(c0 + chunk, nbins);
+  uint32_t s = 0, total;
+  for (uint32_t c = c0; c < c1; c++) s += hist[c];
+  uint32_t run = block_scan<THREADS>(s, wave_sum, &total);
+  for (uint32_t c = c0; c < c1; c++) {
+    const uint32_t v = hist[c];
+    hist[c] = run;
+    run += v;
+  }
+  if (tid == 0) off[nbins] = total;
+  __syncthreads();
+  for (uint32_t c = tid; c < nbins; c += THREADS) off[c] = hist[c];
+  __syncthreads();
+  for (uint32_t j = tid; j < n; j += THREADS) {
+    const int32_t c = bin_of(j);
+    if (c >= 0) place(atomicAdd(&hist[c], 1u), j);       // hist[c] is the next free slot of bin c
+  }
+}
+
+// The two smallest of the keys dist << 16 | index seen so far, 0xffffffff for "none" (keys are at most
+// 256 << 16 | 65534: never the sentinel).  Keys are unique per train index, so neither depends on the visit order.
+__device__ __forceinline__ void pair_push(uint32_t &best, uint32_t &second, uint32_t key) {
+  second = min(second, max(best, key));
+  best = min(best, key);
+}
+
+// Merges the pair (ob, os) of a disjoint set of entries into (best, second).
+__device__ __forceinline__ void pair_merge(uint32_t &best, uint32_t &second, uint32_t ob, uint32_t os) {
+  second = min(min(second, os), max(best, ob));
+  best = min(best, ob);
+}
+
+// Merges the pairs of the LPQ adjacent lanes of a query (they saw disjoint entries): every one of them gets the result.
+template <int LPQ>
+__device__ __forceinline__ void pair_merge_lanes(uint32_t &best, uint32_t &second) {
+#pragma unroll
+  for (int s = 1; s < LPQ; s <<= 1) {
+    const uint32_t ob = __shfl_xor(best, s, 64), os = __shfl_xor(second, s, 64);
+    pair_merge(best, second, ob, os);
+  }
+}
+
+// Output slot o of a guided matcher: "none" becomes index -1 and distance 0xffffffff.
+__device__ __forceinline__ void store_match(size_t o, uint32_t best, int32_t *__restrict__ idx, uint32_t *__restrict__ dist) {
+  idx[o] = best == 0xffffffffu ? -1 : (int32_t)(best & 0xffffu);
+  dist[o] = best == 0xffffffffu ? 0xffffffffu : best >> 16;
+}
+__device__ __forceinline__ void store_match(size_t o, uint32_t best, uint32_t second, int32_t *__restrict__ idx,
+                                            uint32_t *__restrict__ dist, uint32_t *__restrict__ dist2) {
+  store_match(o, best, idx, dist);
+  dist2[o] = second == 0xffffffffu ? 0xffffffffu : second >> 16;
+}
+
+// The query descriptor of a lane: the WORDS dwords at p, zeros for a lane without a query (p null).
+template <int WORDS>
+__device__ __forceinline__ void load_query(uint32_t (&qd)[WORDS], const uint32_t *__restrict__ p) {
+#pragma unroll
+  for (int w = 0; w < WORDS; w++) qd[w] = 0;
+  if (p) {
+#pragma unroll
+    for (int w = 0; w < WORDS; w++) qd[w] = p[w];
+  }
+}
+
 constexpr int QPW = 64;                // queries per workgroup pass (one per lane; the waves split the train set)
 constexpr int SPLIT = 8;               // waves per workgroup = interleaved slices of the train set
 constexpr int MAX_GRID_X = 16;         // query tiles per pair in flight; a workgroup loops over further tiles
@@ -62,31 +174,22 @@ __global__ __launch_bounds__(QPW *SPLIT) void k_match(const uint32_t *__restrict
         d0 += (uint32_t)__popc(qd[k] ^ t0[k]);
         d1 += (uint32_t)__popc(qd[k] ^ t1[k]);
       }
-      const uint32_t k0 = (d0 << 16) | j, k1 = (d1 << 16) | (j + SPLIT);
-      second = min(second, max(best, k0));
-      best = min(best, k0);
-      second = min(second, max(best, k1));
-      best = min(best, k1);
+      pair_push(best, second, (d0 << 16) | j);
+      pair_push(best, second, (d1 << 16) | (j + SPLIT));
     }
     if (j < nt) {
       const uint32_t *t0 = tp + (size_t)j * WORDS;
       uint32_t d0 = 0;
 #pragma unroll
       for (int k = 0; k < WORDS; k++) d0 += (uint32_t)__popc(qd[k] ^ t0[k]);
-      const uint32_t k0 = (d0 << 16) | j;
-      second = min(second, max(best, k0));
-      best = min(best, k0);
+      pair_push(best, second, (d0 << 16) | j);
     }
     sh_best[wave][lane] = best;
     sh_second[wave][lane] = second;
     __syncthreads();
     if (wave == 0 && i < nq) {
 #pragma unroll
-      for (int w = 1; w < SPLIT; w++) {                  // merge sorted pairs: keys are unique per train index
-        const uint32_t ob = sh_best[w][lane], os = sh_second[w][lane];
-        second = min(min(second, os), max(best, ob));
-        best = min(best, ob);
-      }
+      for (int w = 1; w < SPLIT; w++) pair_merge(best, second, sh_best[w][lane], sh_second[w][lane]);
       const size_t o = (size_t)b * out_stride + i;
       idx[o] = nt ? (int32_t)(best & 0xffffu) : -1;
       dist[o] = nt ? best >> 16 : 0xffffffffu;
@@ -243,12 +346,12 @@ __global__ __launch_bounds__(64 * MF_WAVES) void k_match_mfma(const uint32_t *__
 // The windowed matcher is the case of unit scales (65536: X = x - col0) and span 0.  Two launches on the context stream:
 //   k_scaled_index   one workgroup per pair: each train entry goes to a cell of ITS level's grid of square cells in
 //                    level-0 pixels (side chosen by the host), so a cell run holds one level and the match needs no level
-//                    test; a counting sort in LDS (histogram with LDS atomics, exclusive scan, scatter) writes the pair's
-//                    cell offsets and a cell-sorted copy of each entry (X << 16 | Y, original index, descriptor dwords).
+//                    test; lds_counting_sort with the cell as the bin writes the pair's cell offsets and a cell-sorted
+//                    copy of each entry (X << 16 | Y, original index, descriptor dwords).
 //   k_match_scaled   WIN_LPQ lanes per query (the query descriptor in registers): the cell rows overlapping the window
 //                    clipped to a level's mapped extent are contiguous runs of entries; the lanes of a query take every
 //                    WIN_LPQ-th entry of each run, apply the exact window test, XOR-popcount and keep (best, second) on
-//                    dist << 16 | index like k_match, then merge through two xor-shuffles.  At span 0 (ONE_LEVEL) a lane
+//                    dist << 16 | index like k_match (pair_push), then merge through two xor-shuffles.  At span 0 (ONE_LEVEL) a lane
 //                    walks its own level with that level's fields picked per lane; otherwise a wave-uniform loop over the
 //                    plan's levels (kernel-argument loads, no per-lane indexing of the plan) walks the levels within span.
 // Positions outside every level are never indexed and find no candidates.  Scatter order inside a cell varies between
@@ -322,55 +425,18 @@ __global__ __launch_bounds__(WIN_INDEX_THREADS) void k_scaled_index(ScaledPlan P
   __shared__ uint32_t hist[WIN_MAX_CELLS];
   __shared__ uint32_t wave_sum[WIN_INDEX_THREADS / 64];
   const int b = blockIdx.x;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const uint32_t nt = win_count(tcount[b], t_stride);
-  const int32_t nc = P.ncells;
   const uint32_t *kp = tkp + (size_t)b * t_stride;
-  uint32_t *off = cell_off + (size_t)b * (nc + 1);
-  for (int32_t c = (int32_t)tid; c < nc; c += WIN_INDEX_THREADS) hist[c] = 0;
-  __syncthreads();
-  for (uint32_t j = tid; j < nt; j += WIN_INDEX_THREADS) {
-    uint32_t xy;
-    const int32_t c = sc_cell(P, kp[j], &xy);
-    if (c >= 0) atomicAdd(&hist[c], 1u);
-  }
-  __syncthreads();
-  // exclusive scan: every thread sums a contiguous chunk, the chunk sums are scanned across the workgroup
-  const int32_t chunk = (nc + WIN_INDEX_THREADS - 1) / WIN_INDEX_THREADS;
-  const int32_t c0 = min((int32_t)tid * chunk, nc), c1 = min(c0 + chunk, nc);
-  uint32_t s = 0;
-  for (int32_t c = c0; c < c1; c++) s += hist[c];
-  uint32_t incl = s;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t v = __shfl_up(incl, d, 64);
-    if ((int)lane >= d) incl += v;
-  }
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  uint32_t run = incl - s;
-  for (uint32_t w = 0; w < wave; w++) run += wave_sum[w];
-  for (int32_t c = c0; c < c1; c++) {
-    const uint32_t v = hist[c];
-    hist[c] = run;
-    run += v;
-  }
-  if (tid == WIN_INDEX_THREADS - 1) off[nc] = run;     // entries indexed (the last chunk ends at the total)
-  __syncthreads();
-  for (int32_t c = (int32_t)tid; c < nc; c += WIN_INDEX_THREADS) off[c] = hist[c];
-  __syncthreads();
-  // scatter: hist[c] is the next free slot of cell c
   const uint32_t *dp = tdesc + (size_t)b * t_stride * words;
   uint2 *mp = ent_meta + (size_t)b * t_stride;
   uint32_t *ep = ent_desc + (size_t)b * t_stride * words;
-  for (uint32_t j = tid; j < nt; j += WIN_INDEX_THREADS) {
-    uint32_t xy;
-    const int32_t c = sc_cell(P, kp[j], &xy);
-    if (c < 0) continue;
-    const uint32_t slot = atomicAdd(&hist[c], 1u);
-    mp[slot] = make_uint2(xy, j);
-    for (int w = 0; w < words; w++) ep[(size_t)slot * words + w] = dp[(size_t)j * words + w];
-  }
+  uint32_t xy = 0;                                       // mapped position of the entry bin_of saw last
+  lds_counting_sort<WIN_INDEX_THREADS>(
+      (uint32_t)P.ncells, win_count(tcount[b], t_stride), hist, wave_sum, cell_off + (size_t)b * (P.ncells + 1),
+      [&](uint32_t j) { return sc_cell(P, kp[j], &xy); },
+      [&](uint32_t slot, uint32_t j) {
+        mp[slot] = make_uint2(xy, j);
+        for (int w = 0; w < words; w++) ep[(size_t)slot * words + w] = dp[(size_t)j * words + w];
+      });
 }
 
 template <int WORDS>
@@ -435,12 +501,10 @@ __global__ __launch_bounds__(WIN_THREADS) void k_match_scaled(ScaledPlan P, cons
   for (uint32_t q0 = blockIdx.x * (uint32_t)WIN_QPW; q0 < nq; q0 += gridDim.x * (uint32_t)WIN_QPW) {
     const uint32_t i = q0 + threadIdx.x / WIN_LPQ;
     const size_t o = (size_t)b * q_stride + i;
-    uint32_t best = 0xffffffffu, second = 0xffffffffu;  // (keys are at most 256 << 16 | 65534: never the sentinel)
+    uint32_t best = 0xffffffffu, second = 0xffffffffu;
     ScaledHit h{-1, 0, 0, 0, 0, 0, 0, 1, 0, 0};         // level -1: no candidates (past the count, or in no level)
     int32_t xc = 0, yc = 0;
-    uint32_t qd[WORDS];
-#pragma unroll
-    for (int w = 0; w < WORDS; w++) qd[w] = 0;
+    const uint32_t *qp = nullptr;
     if (i < nq) {
       const uint32_t k = qkp[o];
       const int32_t x = (int32_t)((k >> 12) & 0xfffu), y = (int32_t)(k & 0xfffu);
@@ -453,19 +517,16 @@ __global__ __launch_bounds__(WIN_THREADS) void k_match_scaled(ScaledPlan P, cons
           xc = sc_map(x - h.col0, h.scale);
           yc = sc_map(y - h.row0, h.scale);
         }
-        const uint32_t *qp = qdesc + o * WORDS;
-#pragma unroll
-        for (int w = 0; w < WORDS; w++) qd[w] = qp[w];
+        qp = qdesc + o * WORDS;
       }
     }
+    uint32_t qd[WORDS];
+    load_query<WORDS>(qd, qp);
     const int32_t r = h.radius;
     auto visit = [&](uint32_t e, uint2 m) {
       const int32_t tx = (int32_t)(m.x >> 16), ty = (int32_t)(m.x & 0xffffu);
-      if (abs(tx - xc) <= r && abs(ty - yc) <= r) {
-        const uint32_t key = (win_popc<WORDS>(qd, ep + (size_t)e * WORDS) << 16) | m.y;
-        second = min(second, max(best, key));
-        best = min(best, key);
-      }
+      if (abs(tx - xc) <= r && abs(ty - yc) <= r)
+        pair_push(best, second, (win_popc<WORDS>(qd, ep + (size_t)e * WORDS) << 16) | m.y);
     };
     if constexpr (ONE_LEVEL) {
       if (h.level >= 0) win_walk(h, off_b, mp, sub, xc - r, xc + r, yc - r, yc + r, visit);
@@ -475,20 +536,10 @@ __global__ __launch_bounds__(WIN_THREADS) void k_match_scaled(ScaledPlan P, cons
         win_walk(P.lv[l], off_b, mp, sub, xc - r, xc + r, yc - r, yc + r, visit);
       }
     }
-#pragma unroll
-    for (int s = 1; s < WIN_LPQ; s <<= 1) {              // merge the lanes of a query: they saw disjoint entries
-      const uint32_t ob = __shfl_xor(best, s, 64), os = __shfl_xor(second, s, 64);
-      second = min(min(second, os), max(best, ob));
-      best = min(best, ob);
-    }
-    if (sub == 0 && i < nq) {
-      idx[o] = best == 0xffffffffu ? -1 : (int32_t)(best & 0xffffu);
-      dist[o] = best == 0xffffffffu ? 0xffffffffu : best >> 16;
-      dist2[o] = second == 0xffffffffu ? 0xffffffffu : second >> 16;
-    }
+    pair_merge_lanes<WIN_LPQ>(best, second);
+    if (sub == 0 && i < nq) store_match(o, best, second, idx, dist, dist2);
   }
 }
-
 
 // ---------------------------------------------------------------------------
 // Rectified stereo matching (include/pislam_hip.h): left keypoint i (query) against the right
@@ -532,11 +583,9 @@ __global__ __launch_bounds__(WIN_THREADS) void k_match_stereo(ScaledPlan P, int3
   for (uint32_t q0 = blockIdx.x * (uint32_t)WIN_QPW; q0 < nq; q0 += gridDim.x * (uint32_t)WIN_QPW) {
     const uint32_t i = q0 + threadIdx.x / WIN_LPQ;
     const size_t o = (size_t)b * l_stride + i;
-    uint32_t best = 0xffffffffu;                        // (keys are at most 256 << 16 | 65534: never the sentinel)
+    uint32_t best = 0xffffffffu;
     int32_t lq = -1, xl = 0, yl = 0;                    // lq -1: no candidates (past the count, or in no level)
-    uint32_t qd[WORDS];
-#pragma unroll
-    for (int w = 0; w < WORDS; w++) qd[w] = 0;
+    const uint32_t *qp = nullptr;
     if (i < nq) {
       const uint32_t k = lkp[o];
       const int32_t x = (int32_t)((k >> 12) & 0xfffu), y = (int32_t)(k & 0xfffu);
@@ -545,11 +594,11 @@ __global__ __launch_bounds__(WIN_THREADS) void k_match_stereo(ScaledPlan P, int3
         lq = h.level;
         xl = sc_map(x - h.col0, h.scale);
         yl = sc_map(y - h.row0, h.scale);
-        const uint32_t *qp = ldesc + o * WORDS;
-#pragma unroll
-        for (int w = 0; w < WORDS; w++) qd[w] = qp[w];
+        qp = ldesc + o * WORDS;
       }
     }
+    uint32_t qd[WORDS];
+    load_query<WORDS>(qd, qp);
     for (int l = 0; l < P.nlevels; l++) {               // wave-uniform: the level's fields are kernel-argument loads
       if (lq < 0 || abs(l - lq) > P.span) continue;
       const int32_t r = P.lv[l].radius;                 // row_radius0 of the RIGHT level
@@ -561,10 +610,7 @@ __global__ __launch_bounds__(WIN_THREADS) void k_match_stereo(ScaledPlan P, int3
     }
 #pragma unroll
     for (int s = 1; s < WIN_LPQ; s <<= 1) best = min(best, __shfl_xor(best, s, 64));
-    if (sub == 0 && i < nq) {
-      idx[o] = best == 0xffffffffu ? -1 : (int32_t)(best & 0xffffu);
-      dist[o] = best == 0xffffffffu ? 0xffffffffu : best >> 16;
-    }
+    if (sub == 0 && i < nq) store_match(o, best, idx, dist);
   }
 }
 

@@ -544,6 +544,23 @@ def test_gpu_vector_hand_made_words(gpu_ctx):
         run_vector(gpu_ctx, word, np.array([10], np.uint32))
 
 
+@pytest.mark.gpu
+def test_gpu_vector_scan_at_chunk_sizes(gpu_ctx):
+    """The run-head scan with one word, with chunks of 2 of which most are empty (1025 words, all distinct and all
+    equal) and with full chunks of 16 (16384 distinct words)."""
+    rng = np.random.default_rng(1025)
+    S = 16384
+    word = np.zeros((4, S), np.uint32)
+    word[0] = 7
+    word[1] = rng.permutation(S).astype(np.uint32) * 5 + 2
+    word[2] = 99
+    word[3] = rng.permutation(S).astype(np.uint32) * 3
+    counts = np.array([1, 1025, 1025, S], np.uint32)
+    got = run_vector(gpu_ctx, word, counts)
+    check_vector(got, word, counts)
+    assert list(got[2]) == [1, 1025, 1, S]
+
+
 # ---- GPU: word-guided matcher ------------------------------------------------------------------------------------------
 def run_bow_match(ctx, ngroups, qd, qg, qc, td, tg, tc, fill=SENTINEL):
     import torch
@@ -646,6 +663,31 @@ def test_gpu_bow_match_random_groups(gpu_ctx, words, ngroups):
         got = run_bow_match(gpu_ctx, ngroups, qd, qg, qc, td, tg, tc, fill=fill)
         check_bow_match(got, ngroups, qd, qg, qc, td, tg, tc, fill=fill)
     assert (got[0][5, :1500].view(np.int32) >= 0).any() and (got[0][5, :1500].view(np.int32) == -1).any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ngroups", [1, 1025, 16384])
+def test_gpu_bow_index_sort_bin_counts(gpu_ctx, ngroups):
+    """The index kernel's counting sort with a single bin, with chunks of 2 of which most are empty and at the
+    histogram's limit; three pairs with different counts (so each pair's offset row is its own): no train entry under
+    live queries, every train entry in the last group, and train groups of which a third are at or above ngroups."""
+    rng = np.random.default_rng([3, ngroups])
+    words, qs, ts = 2, 200, 300
+    qc = np.array([200, 150, 180], np.uint32)
+    tc = np.array([0, 257, 300], np.uint32)
+    td = np.stack([random_descriptors(rng, ts, words) for _ in range(3)])
+    qd = np.stack([td[b, rng.integers(0, ts, qs)] for b in range(3)])
+    tg = rng.integers(0, ngroups, (3, ts)).astype(np.uint32)
+    tg[1] = ngroups - 1
+    above = rng.choice(np.array([ngroups, ngroups + 7, 0x80000000, 0xFFFFFFFF], np.uint32), ts)
+    tg[2] = np.where(np.arange(ts) % 3 == 0, above, tg[2])
+    qg = np.stack([tg[b, rng.integers(0, ts, qs)] for b in range(3)])       # (a third of pair 2's are not groups)
+    qg[1, ::4] = rng.integers(0, ngroups, len(qg[1, ::4]))
+    got = run_bow_match(gpu_ctx, ngroups, qd, qg, qc, td, tg, tc)
+    check_bow_match(got, ngroups, qd, qg, qc, td, tg, tc)
+    gi = got[0].view(np.int32)
+    assert (gi[0, :200] == -1).all()
+    assert (gi[1, :150] >= 0).any() and (gi[2, :180] >= 0).any() and (gi[2, :180] == -1).any()
 
 
 @pytest.mark.gpu

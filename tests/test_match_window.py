@@ -349,6 +349,57 @@ def test_gpu_window_invalid_counts_and_untouched_slots(gpu_ctx):
         assert (gi[2, :100].view(np.int32) >= 0).any()
 
 
+def plan_cells(levels, radius):
+    """(cells, f) of the windowed matcher's index by the rule the library states above its scaled_plan: level l has
+    square cells of side max(1, radius[l]) * f over its rectangle, f >= 1 the smallest factor that keeps the cells of
+    all levels within the 16384 bins of the index kernel's histogram."""
+    rad = [radius] * len(levels) if np.isscalar(radius) else list(radius)
+    f = 1
+    while True:
+        sides = [min(65536, max(1, int(r)) * f) for r in rad]
+        n = sum(-(-_lv(t)[0] // s) * -(-_lv(t)[1] // s) for t, s in zip(levels, sides))
+        if n <= 16384:
+            return n, f
+        f += 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size,radius,ncells,f", [((8, 8), 4095, 1, 1),            # a single bin
+                                                  ((33, 32), 1, 1056, 1),          # chunks of 2, most threads' chunk empty
+                                                  ((128, 128), 1, 16384, 1),       # the histogram's limit
+                                                  ((129, 128), 1, 65 * 64, 2)])    # coarsened
+def test_gpu_window_index_sort_bin_counts(gpu_ctx, size, radius, ncells, f):
+    """The index kernel's counting sort at its bin-count edges, three pairs with different counts (so each pair's offset
+    row is its own): no train entry under live queries, every train entry in one cell (the last), and a third of the
+    train positions in no level."""
+    w, h = size
+    levels = [(w, h, 0, 0)]
+    assert plan_cells(levels, radius) == (ncells, f)
+    rng = np.random.default_rng([w, h, radius])
+    words, qs, ts = 2, 200, 300
+    qc = np.array([200, 150, 180], np.uint32)
+    tc = np.array([0, 257, 300], np.uint32)
+    tkp = np.zeros((3, ts), np.uint32)
+    tkp[0] = pack(rng.integers(0, w, ts), rng.integers(0, h, ts))            # (past the count: never read)
+    tkp[1] = pack(np.full(ts, w - 1), np.full(ts, h - 1))
+    outside = np.arange(ts) % 3 == 0
+    tkp[2] = pack(np.where(outside, rng.integers(w, w + 40, ts), rng.integers(0, w, ts)), rng.integers(0, h, ts))
+    td = np.stack([random_descriptors(rng, ts, words) for _ in range(3)])
+    # queries: a train position moved by -1 .. 1 (clipped into the level), or anywhere up to 2 px outside the level
+    src = np.stack([tkp[b, rng.integers(0, max(1, int(tc[b])), qs)] for b in range(3)]).astype(np.int64)
+    nx = np.clip(((src >> 12) & 0xFFF) + rng.integers(-1, 2, (3, qs)), 0, w - 1)
+    ny = np.clip((src & 0xFFF) + rng.integers(-1, 2, (3, qs)), 0, h - 1)
+    anywhere = pack(rng.integers(0, w + 2, (3, qs)), rng.integers(0, h + 2, (3, qs)))
+    qkp = np.where(rng.random((3, qs)) < 0.6, pack(nx, ny), anywhere).astype(np.uint32)
+    qkp[:, :5] = pack(np.full(5, w), np.arange(5))                           # in no level
+    qd = np.stack([td[b, rng.integers(0, ts, qs)] for b in range(3)])
+    got = run_window(gpu_ctx, levels, radius, qkp, qd, qc, tkp, td, tc)
+    check_against_reference(got, levels, radius, qkp, qd, qc, tkp, td, tc)
+    gi = got[0].view(np.int32)
+    assert (gi[0, :200] == -1).all()
+    assert (gi[1, :150] >= 0).any() and (gi[2, :180] >= 0).any() and (gi[2, :180] == -1).any()
+
+
 @pytest.mark.gpu
 def test_gpu_window_rejects_bad_arguments(gpu_ctx):
     import torch
