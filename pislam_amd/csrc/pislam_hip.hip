@@ -575,67 +575,64 @@ int use_own_stream(pislam_ctx *c, int mode) {
 }
 }  // namespace
 
+namespace {
+// The options that are one int member of the context: accepted range [lo, hi] with the message of a value outside it
+// (no message: every value is accepted), then what is stored (no normaliser: the value itself).
+struct OptionDef {
+  const char *key;
+  int pislam_ctx::*member;
+  int lo, hi;
+  const char *range_error;
+  int (*stored)(int);
+};
+int as_flag(int v) { return v != 0; }
+int at_least_0(int v) { return std::max(0, v); }
+const OptionDef OPTIONS[] = {
+    {"pipeline", &pislam_ctx::opt_pipeline, 0, 2, "pipeline must be 0 (auto), 1 (staged) or 2 (fused)", nullptr},
+    {"dump_score", &pislam_ctx::opt_dump_score, 0, 0, nullptr, as_flag},
+    {"repeat_strips", &pislam_ctx::opt_repeat_strips, 1, 64, "repeat_strips must be 1..64", nullptr},
+    {"alias", &pislam_ctx::opt_alias, 0, 0, nullptr, as_flag},
+    {"run_len", &pislam_ctx::opt_run_len, 0, 64, "run_len must be 0 (default) .. 64", nullptr},
+    {"lds_pad", &pislam_ctx::opt_lds_pad, 0, 0, nullptr, at_least_0},
+    {"wgs_per_cu", &pislam_ctx::opt_wgs_per_cu, 0, 8, "wgs_per_cu must be 0..8", nullptr},
+    {"match_mfma", &pislam_ctx::opt_match_mfma, 0, 0, nullptr, as_flag},
+    {"run_order", &pislam_ctx::opt_run_order, 0, 0, nullptr, as_flag},
+    {"strip_px", &pislam_ctx::opt_strip_px, 0, 0, nullptr, [](int v) { return std::max(4096, v); }},
+    {"strip_rows_max", &pislam_ctx::opt_strip_rows_max, 0, 0, nullptr, [](int v) { return v <= 0 ? 0 : std::max(16, std::min(64, v & ~1)); }},
+    // 0: never one launch; 1 (default): batches of 1 or 2 pyramids; n = 2..8: batches of up to n
+    {"frame", &pislam_ctx::opt_frame, 0, 8, "frame must be 0..8", nullptr},
+    // test hook of the one-launch path's bounded wait (see pf::k_frame `test`)
+    {"frame_test", &pislam_ctx::opt_frame_test, 0, 0, nullptr, nullptr},
+    // pyramid build: 1 = levels 1.. in ONE launch (pp::k_bilinear_chain), 0 (default) one launch per level
+    {"build_chain", &pislam_ctx::opt_build_chain, 0, 0, nullptr, as_flag},
+    {"orb_in_strip", &pislam_ctx::opt_orb_in_strip, 0, 0, nullptr, as_flag},
+    {"bucket_select", &pislam_ctx::opt_bucket_select, 0, 0, nullptr, as_flag},
+    {"dist_rccl_single", &pislam_ctx::opt_dist_rccl_single, 0, 0, nullptr, as_flag},
+    {"bucket_round_up", &pislam_ctx::opt_bucket_round_up, 0, 0, nullptr, as_flag},
+    {"orb_chunks", &pislam_ctx::opt_orb_chunks, 0, 1024, "orb_chunks must be 0..1024", nullptr},
+    {"sub_batches", &pislam_ctx::opt_sub_batches, 0, pislam_ctx::MAX_SUB, "sub_batches must be 0 (auto) .. 16", nullptr},
+    {"sub_mb", &pislam_ctx::opt_sub_mb, 0, 0, nullptr, at_least_0},
+    {"ablate", &pislam_ctx::opt_ablate, 0, 0, nullptr, nullptr},
+};
+}  // namespace
+
 PISLAM_EXPORT int pislam_ctx_set_option(pislam_ctx *c, const char *key, int value) {
   if (!c || !key) return PISLAM_ERR_INVALID;
-  if (!strcmp(key, "pipeline")) {
-    if (value < 0 || value > 2) return fail(c, PISLAM_ERR_INVALID, "pipeline must be 0 (auto), 1 (staged) or 2 (fused)");
-    c->opt_pipeline = value;
-  } else if (!strcmp(key, "own_stream")) {
+  for (const OptionDef &o : OPTIONS) {
+    if (strcmp(key, o.key)) continue;
+    if (o.range_error && (value < o.lo || value > o.hi)) return fail(c, PISLAM_ERR_INVALID, o.range_error);
+    c->*o.member = o.stored ? o.stored(value) : value;
+    return PISLAM_OK;
+  }
+  // the options with a side effect, or a range that is no interval
+  if (!strcmp(key, "own_stream")) {
     if (value < 0 || value > 2) return fail(c, PISLAM_ERR_INVALID, "own_stream must be 0, 1 (default flags) or 2 (non-blocking)");
     return use_own_stream(c, value);
-  } else if (!strcmp(key, "dump_score")) {
-    c->opt_dump_score = value != 0;
-  } else if (!strcmp(key, "repeat_strips")) {
-    if (value < 1 || value > 64) return fail(c, PISLAM_ERR_INVALID, "repeat_strips must be 1..64");
-    c->opt_repeat_strips = value;
-  } else if (!strcmp(key, "alias")) {
-    c->opt_alias = value != 0;
-  } else if (!strcmp(key, "run_len")) {
-    if (value < 0 || value > 64) return fail(c, PISLAM_ERR_INVALID, "run_len must be 0 (default) .. 64");
-    c->opt_run_len = value;
-  } else if (!strcmp(key, "lds_pad")) {
-    c->opt_lds_pad = value < 0 ? 0 : value;
-  } else if (!strcmp(key, "wgs_per_cu")) {
-    if (value < 0 || value > 8) return fail(c, PISLAM_ERR_INVALID, "wgs_per_cu must be 0..8");
-    c->opt_wgs_per_cu = value;
-  } else if (!strcmp(key, "match_mfma")) {
-    c->opt_match_mfma = value != 0;
-  } else if (!strcmp(key, "run_order")) {
-    c->opt_run_order = value != 0;
-  } else if (!strcmp(key, "strip_px")) {
-    c->opt_strip_px = std::max(4096, value);
-  } else if (!strcmp(key, "strip_rows_max")) {
-    c->opt_strip_rows_max = value <= 0 ? 0 : std::max(16, std::min(64, value & ~1));
   } else if (!strcmp(key, "tile_cols")) {
     if (value > 0 && value < 64) return fail(c, PISLAM_ERR_INVALID, "tile_cols must be 0 (default), < 0 (never) or >= 64");
     c->opt_tile_cols = value;
-  } else if (!strcmp(key, "frame")) {   // 0: never one launch; 1 (default): batches of 1 or 2 pyramids; n = 2..8: batches of up to n
-    if (value < 0 || value > 8) return fail(c, PISLAM_ERR_INVALID, "frame must be 0..8");
-    c->opt_frame = value;
-  } else if (!strcmp(key, "frame_test")) {   // test hook of the one-launch path's bounded wait (see pf::k_frame `test`)
-    c->opt_frame_test = value;
   } else if (!strcmp(key, "frame_rearm")) {  // 1: take the one-launch paths again after a reported timeout (tests)
     if (value) c->frame_disabled = c->chain_disabled = false;
-  } else if (!strcmp(key, "build_chain")) {  // pyramid build: 1 = levels 1.. in ONE launch (pp::k_bilinear_chain), 0 (default) one launch per level
-    c->opt_build_chain = value != 0;
-  } else if (!strcmp(key, "orb_in_strip")) {
-    c->opt_orb_in_strip = value != 0;
-  } else if (!strcmp(key, "bucket_select")) {
-    c->opt_bucket_select = value != 0;
-  } else if (!strcmp(key, "dist_rccl_single")) {
-    c->opt_dist_rccl_single = value != 0;
-  } else if (!strcmp(key, "bucket_round_up")) {
-    c->opt_bucket_round_up = value != 0;
-  } else if (!strcmp(key, "orb_chunks")) {
-    if (value < 0 || value > 1024) return fail(c, PISLAM_ERR_INVALID, "orb_chunks must be 0..1024");
-    c->opt_orb_chunks = value;
-  } else if (!strcmp(key, "sub_batches")) {
-    if (value < 0 || value > pislam_ctx::MAX_SUB) return fail(c, PISLAM_ERR_INVALID, "sub_batches must be 0 (auto) .. 16");
-    c->opt_sub_batches = value;
-  } else if (!strcmp(key, "sub_mb")) {
-    c->opt_sub_mb = std::max(0, value);
-  } else if (!strcmp(key, "ablate")) {
-    c->opt_ablate = value;
   } else if (!strcmp(key, "strip_rows")) {
     if (value < 0 || value > 64 || (value & 1)) return fail(c, PISLAM_ERR_INVALID, "strip_rows must be even, 0..64");
     c->opt_strip_rows = value;
@@ -1163,8 +1160,227 @@ int check_params(pislam_ctx *c, const pislam_frontend_params *p, const pislam_le
 
 namespace {
 
-// Strip plan of the fused pipeline.  Strip height per level: aim at ~8k pixels per workgroup,
-// even, 16..32 rows (override: option "strip_rows").
+// ---- the strip plan of the fused pipeline (build_fused_plan) ----
+// LDS figures every step of the plan, the launcher and the plan's invariant checks share.
+constexpr long CU_LDS = 160 * 1024;          // LDS of a CU: `wgs` resident workgroups have CU_LDS / wgs bytes each
+constexpr size_t LDS_CAP = 150 * 1024;       // most dynamic LDS a launch may ask for
+constexpr size_t LDS_OPT_IN = 64 * 1024;     // more than this: the kernel's hipFuncAttributeMaxDynamicSharedMemorySize is raised first
+// Queue bytes of a strip workgroup: the per-wave queues, plus the shared queues the two layouts differ in — ALIAS keeps one
+// corner queue (QH_SHARED entries at least: FusedLevel::qh), the plain layout the corner queue and the NMS candidates'.
+constexpr long WAVE_QUEUE_BYTES = (long)pf::WAVES * pf::QCAP * 4;
+constexpr long QUEUE_BYTES_ALIAS = WAVE_QUEUE_BYTES + pf::QH_SHARED * 4;
+constexpr long QUEUE_BYTES_PLAIN = WAVE_QUEUE_BYTES + pf::SHARED_Q * 4;
+// What a workgroup's dynamic LDS may take for `wgs` of them to stay resident on a CU.
+// (margin of 1280 B: static LDS + allocation granule — with 512 B the kernel measurably lost its 5th workgroup)
+inline long residency_budget(int wgs) { return CU_LDS / wgs - 1280; }
+// Residency target of the heuristic: 5 workgroups per CU.  (A search over 5 / 4 / 3 per CU with a cost model
+// "pixels * (R + 4) / R / measured throughput at that residency" was tried for the 1280-wide levels of BASELINE
+// config 4 — 12-row strips at 4 per CU instead of 16 rows at 3 — and measured no better: 1.24 vs 1.21 ms at
+// batch 256; forcing 5 per CU with 8-row strips and no halo carry gave 1.16 ms.  Option "wgs_per_cu" overrides.)
+inline int alias_wgs(const pislam_ctx *c) { return c->opt_wgs_per_cu > 0 ? c->opt_wgs_per_cu : 5; }
+// Strips a resident slot (5 per CU) works through in a launch of `batch` pyramids.
+inline double strips_per_slot(const pislam_ctx *c, int strips, int batch) {
+  return (double)strips * batch / (5.0 * std::max(1, c->num_cus));
+}
+
+inline int classified_end(int border, int nx) { return border + 16 * cdiv(nx, 16); }   // FusedLevel::xend for nx columns inside the border
+inline int score_pitch(int xend) { return (xend + 4 + 15) & ~15; }                     // FusedLevel::pitch
+// LDS pitch of an image tile row that stages columns [xbase, xend + 8), xbase = (border - 4) & ~15: a multiple of 16 bytes.
+// (An ODD number of 16-byte vectors — consecutive rows 4 banks apart instead of column x of every row in one bank at VGA
+// level 0's 640 bytes — was measured in round 4: bit-exact, the strip kernel within 0.5 % either way: the per-candidate
+// reads' bank conflicts, 45 % of its LDS cycles, come from the candidates' random columns, not from the row pitch.)
+inline int tile_pitch(int border, int xend) { return (xend - border + ((border - 4) & 15) + 4 + 8 + 15) & ~15; }
+
+// Step 1, plan entries: a level, or the x-tiles of a wide level (pf::FusedLevel: w, h, row0, col0, ex0, ex1, xscore, gfirst,
+// gn).  A level with more than `tile_max` classified columns is cut into tiles of T block-origin columns (T a multiple of
+// 32: tiles start on bucket boundaries for every fused bucket size); tile t > 0 starts HALO = 32 columns to the left of its
+// first block origin, so that, seen as a level of its own with the same border B, it classifies and scores the columns its
+// boundary blocks' NMS reads, and every tile but the last ends 2 columns past its last owned block origin.
+// False: more entries than a plan holds.
+bool plan_entries(const pislam_ctx *c, const pislam_frontend_params *p, const pislam_level *lv, pf::FusedParams *F) {
+  const int B = p->border, HALO = 32;
+  const int tile_max = c->opt_tile_cols > 0 ? c->opt_tile_cols : (c->opt_tile_cols < 0 ? 1 << 30 : 704);
+  int n = 0;
+  for (int l = 0; l < p->nlevels; l++) {
+    const int w = lv[l].width, nx = w - 2 * B, ny = lv[l].height - 2 * B;
+    int nt = 1;
+    // tiles of ~448 owned columns: with the 32-column halo a tile row is two full 256-pixel prefilter steps,
+    // and its strips reach the full 28 rows at 5 workgroups per CU (1280x960 batch 256: 0.94 ms with three
+    // 416-column tiles at level 0 against 1.01 ms with two of 624)
+    if (nx > 0 && ny > 0 && 16 * cdiv(nx, 16) > tile_max)
+      nt = std::max(2, tile_max >= 640 ? (nx + 224) / 448 : cdiv(nx, std::max(64, tile_max)));
+    const int T = nt > 1 ? (cdiv(nx, nt) + 31) & ~31 : 0;
+    nt = nt > 1 ? cdiv(nx, T) : 1;
+    if (n + nt > pf::MAX_LEVELS) {
+      memset(F->lv, 0, sizeof(F->lv));                 // (a refused plan holds no entries, not the first few)
+      return false;
+    }
+    const int g0 = n;
+    for (int t = 0; t < nt; t++) {
+      pf::FusedLevel &L = F->lv[n++];
+      const int o = t == 0 ? 0 : t * T - HALO;                           // level column of the entry's origin
+      const int E = nt == 1 ? w - B : std::min(B + (t + 1) * T, w - B);  // one past the last owned block origin (level x)
+      L.w = t == nt - 1 ? w - o : E - o + 2 + B;
+      L.h = lv[l].height;
+      L.row0 = lv[l].row0;
+      L.col0 = lv[l].col0 + o;
+      L.ex0 = t == 0 ? B : B + HALO;
+      L.ex1 = E - o;
+      L.xscore = (w - B) - o;
+      L.gfirst = g0;
+      L.gn = nt;
+    }
+  }
+  F->nlevels = n;
+  return true;
+}
+
+// The widest entry of entry e's level: all tiles of a level must cut the same strips, so its strip height comes from this one.
+int widest_tile(const pf::FusedParams &F, int e) {
+  int w = 0;
+  for (int t = F.lv[e].gfirst; t < F.lv[e].gfirst + F.lv[e].gn; t++) w = std::max(w, F.lv[t].w);
+  return w;
+}
+
+// Step 2, the strip height of a level whose widest entry has w columns (rows_max: build_fused_plan's cap).  Four rules, in
+// this precedence: option "strip_rows"; the ALIAS layout's residency rule; the generic 8k-pixel rule; and, where the strips
+// select per bucket themselves (lbs != 0), rounding to whole bucket rows on top of whichever rule gave the height.
+int strip_height(const pislam_ctx *c, const pislam_frontend_params *p, int lbs, int w, int rows_max) {
+  const int xend = classified_end(p->border, w - 2 * p->border), tpitch = tile_pitch(p->border, xend);
+  const int wgs = alias_wgs(c);
+  int R = c->opt_strip_rows;
+  if (R == 0 && c->opt_alias) {
+    // ALIAS layout under a residency target of `wgs` workgroups per CU: ~16k pixels per strip, 16..rows_max rows, capped so
+    // that queues + tile + the minimum shared queue fit CU_LDS / wgs where 16 rows allow it (VGA at 5 per CU: 24 rows at
+    // level 0, 28 below; measured 0.293 ms vs 0.311 ms with 16-row strips).
+    const int rcap = (int)((CU_LDS / wgs - QUEUE_BYTES_ALIAS) / tpitch - 10) & ~1;
+    if (wgs == 5 || rcap >= 10)                        // (else: an explicit residency request falls back to the generic rule)
+      R = std::max(16, std::min(std::min(rows_max, std::max(16, (c->opt_strip_px / w) & ~1)), rcap));
+  }
+  if (R == 0) {
+    R = (8192 / w) & ~1;                               // ~8k pixels per strip ...
+    R = std::min(32, std::max(16, R));
+    if (c->opt_wgs_per_cu > 0) {                       // ... capped so that tiles + queues fit CU_LDS / wgs_per_cu
+      const long budget = CU_LDS / c->opt_wgs_per_cu, pitch = score_pitch(xend);
+      if (budget > QUEUE_BYTES_PLAIN + 13 * pitch)
+        R = std::max(8, std::min(R, (int)(((budget - QUEUE_BYTES_PLAIN) / pitch - 13) / 2) & ~1));
+    }
+  }
+  if (lbs) {                                           // (selection inside the strips:) strips hold whole bucket rows
+    const int bs = 1 << lbs;
+    if (c->opt_strip_rows == 0 && c->opt_alias) {
+      // heuristic height: round UP to whole bucket rows (16-px buckets: 32-row strips — measured 0.315 ms
+      // vs 0.371 ms with 16-row strips) where that still fits the residency budget, DOWN on the levels where it
+      // does not: the launch has ONE LDS size, a single level over the budget costs every level its fifth workgroup
+      const int up = std::min(std::max(bs, 32), ((R + bs - 1) / bs) * bs), down = std::max(bs, (R / bs) * bs);
+      const long need = QUEUE_BYTES_ALIAS + (long)(up + 10) * tpitch;
+      R = (c->opt_bucket_round_up || need <= residency_budget(wgs)) ? up : down;
+    } else
+      R = std::max(bs, (R / bs) * bs);
+  }
+  return R;
+}
+
+// Step 3, the LDS of an entry whose R, nbx and xend are set: pitches, the reciprocals the kernel divides by them with, and
+// what a workgroup of this entry needs in the plain layout (tbytes) and in the ALIAS layout (apad, qh at `wgs` per CU),
+// raising the launch's *lds and *lds_alias to it.
+void level_lds(int border, int wgs, pf::FusedLevel &L, size_t *lds, size_t *lds_alias) {
+  const int R = L.R;
+  L.pitch = score_pitch(L.xend);
+  L.tpitch = tile_pitch(border, L.xend);
+  L.vpr_recip = (uint32_t)(((1ull << 32) + (L.tpitch / 16) - 1) / (L.tpitch / 16));
+  L.tp_recip = (uint32_t)(((1ull << 32) + L.tpitch - 1) / L.tpitch);
+  // scan fallbacks reuse the image tile: row buffers of R/2 x nbx dwords, or per-cell results (<= one
+  // dword per block) + per-cell counts (<= a quarter of that: a cell holds >= 2x2 blocks)
+  L.tbytes = std::max((R + 10) * L.tpitch, (((R / 2) * L.nbx * 5 + 64) + 15) & ~15);
+  *lds = std::max(*lds, (size_t)L.tbytes + (size_t)(R + 3) * L.pitch + (size_t)QUEUE_BYTES_PLAIN);
+  // ALIAS layout: the score tile (R+3 rows) is laid over [NMS scratch end, image row R): pad the
+  // per-wave queue area when that span is too short (levels wider than ~680 columns)
+  // ... and the ORB phase's 8 patches + vrecpe table are laid over the same span (strip_body phase E)
+  const long need = std::max((long)pf::NMS_SCRATCH * 4 + (long)(R + 3) * L.pitch,
+                             (long)pf::NMS_SCRATCH * 4 + (long)pf::WAVES * 2 * pf::ORB_PATCH_BYTES + 256);
+  const long have = WAVE_QUEUE_BYTES + (long)R * L.tpitch;
+  L.apad = need > have ? (int)((need - have + 15) & ~15L) : 0;
+  // one shared queue in this layout: at least QH_SHARED entries, and whatever LDS the level's tile
+  // leaves under the residency budget (narrow levels of a textured photo are the dense ones)
+  const long fixed = WAVE_QUEUE_BYTES + L.apad + (long)(R + 10) * L.tpitch;
+  const long spare = (residency_budget(wgs) - fixed) / 4;
+  L.qh = (int)std::min<long>(4096, std::max<long>(pf::QH_SHARED, spare & ~3L));
+  *lds_alias = std::max(*lds_alias, (size_t)fixed + (size_t)L.qh * 4);
+}
+
+// Step 4, the run length.  Runs: a workgroup walks run_len consecutive strips of a level (halo carried in LDS).  Longer runs
+// save the duplicated halo work but leave fewer, longer workgroups for the dispatcher to balance over the 5 resident
+// slots per CU.  Measured (strip kernel, ms): VGA batch 256 (15 strips per slot): 0.236 / 0.231 / 0.233 / 0.243 /
+// 0.242 / 0.235 / 0.231 / 0.229 / 0.229 / 0.243 for run_len 1 / 2 / 3 / 4 / 5 / 6 / 8 / 10 / 12 / 16 — the carry is
+// worth ~3 % at best and the curve is dispatch-quantisation noise; 720p batch 64 (10 strips per slot): 0.208 /
+// 0.207 / 0.216 / 0.227 / 0.238 for 1..5; 1280x960 batch 256 (54 per slot): 1.029 / 1.018 / 1.012 / 1.044 / 1.053 /
+// 1.010 for 4 / 5 / 6 / 7 / 8..10 / 12, batch 64: 0.278 / 0.307 / 0.376 for 2 / 3 / 8; VGA batch 32, 64: 1 is best.
+// Rule: ~6.5 workgroups per resident slot, at most 8 strips per run.  (List-scheduling and processor-sharing
+// simulations of one XCD were tried as a predictor: neither tracks the measured 2-3 % structure.)
+// With the runs of a pyramid launched longest first (order_runs) the curve flattens: VGA batch 256
+// 0.232 / 0.222 / 0.220 / 0.224 / 0.222 / 0.233 for run_len 1 / 2 / 3 / 4 / 6 / 8; 1280x960 batch 256 0.920 / 0.898 /
+// 0.899 / 0.889 / 0.889 for 2 / 4 / 6 / 8 / 12; 720p batch 64 0.191 / 0.191 / 0.197 / 0.206 for 1 / 2 / 3 / 4.
+int run_length(const pislam_ctx *c, const pf::FusedParams &F, int strips, int batch) {
+  if (c->opt_run_len > 0) return c->opt_run_len;
+  // Round 5 (strips of a run follow each other without a barrier): one call at a time the rule stands (VGA batch 256: strip
+  // kernel 0.164 / 0.166 / 0.171 ms for run_len 2 / 3 / 4), but as a LANE of a pipeline — other batches' kernels fill the
+  // tail of the launch — longer runs win: whole step 0.2233 / 0.2208 / 0.2203 ms for 2 / 3 / 4 (720p batch 64: 0.2974 /
+  // 0.2954 for 2 / 3; demo photo x 256: 0.3242 / 0.3208 for 2 / 4).  Lanes aim at ~3.25 workgroups per slot.
+  const double per_wg = c->lanes_in_flight > 1 ? 3.25 : 6.5;
+  const int by_slot = std::max(1, std::min(8, (int)(strips_per_slot(c, strips, batch) / per_wg + 0.5)));
+  if (c->lanes_in_flight <= 1) return by_slot;
+  // Round 6, lanes only: the LONGEST runs that still leave the launch 0.6 workgroups per resident slot (5 per CU) — whole
+  // levels per workgroup where the batch is large enough.  Re-swept after the pretest change, pipelined step in ms for
+  // run_len default (the rule above) / 12 / 16 / 24 / 32 / 64: VGA batch 256 0.2117 / 0.2087 / 0.2062 / 0.2072 / 0.2063 / 0.2068
+  // (8 whole-level runs per pyramid = 1.6 per slot); demo photo 0.3169 / 0.3153 / 0.3153 / 0.3144 / 0.3143 / 0.3140; 1280x960
+  // 0.6692 / 0.6674 / 0.6628 / 0.6637 / 0.6517 / 0.6531; 720p build batch 64 0.2865 / 0.2759 / 0.2671 / 0.2581 / 0.2589 / 0.2590
+  // (15 runs per pyramid = 0.75 per slot); bucket mode 0.2334 / 0.2293 / 0.2285 / 0.2281 / 0.2287 / 0.2277 — and where the
+  // launch gets too few workgroups it turns: VGA batch 64 0.0646 / 0.0631 (0.6 per slot) / 0.0681 (0.5) / 0.0720; batch 16
+  // 0.0208 / 0.0425.  The strip kernel ALONE is slower with long runs (0.156 -> 0.159-0.162 ms: a longer tail); on a lane
+  // another batch's kernels run in that tail, and a long run stages its halo once and prefetches every strip but the first.
+  const long want = (long)(0.6 * 5.0 * std::max(1, c->num_cus));
+  int longest = 1;
+  for (int l = 0; l < F.nlevels; l++) longest = std::max(longest, F.lv[l].nstrips);
+  longest = std::min(longest, 64);                     // (option range; k_frame keeps a 64-bit mask of a run's strips)
+  for (int rl = longest; rl > by_slot; rl--) {
+    long r = 0;
+    for (int l = 0; l < F.nlevels; l++) r += cdiv(F.lv[l].nstrips, rl);
+    if (r * batch >= want && r <= pf::MAX_ORDER) return rl;
+  }
+  return by_slot;
+}
+
+// Step 5, the launch order of a pyramid's runs: estimated cost (pixels + a fixed share per strip), longest first — the
+// longest-processing-time-first rule of list scheduling: workgroups are dispatched in blockIdx order to the
+// 5 resident slots per CU, so the short runs of the small levels fill the tail of the launch.  Entry order
+// (level by level) interleaves short last-runs of big levels with long runs of the next level: VGA batch 256
+// 0.232 -> 0.222 ms, 1280x960 batch 256 0.927 -> 0.895 ms.  Plans with more runs than order[] holds keep entry order.
+void order_runs(const pislam_ctx *c, pf::FusedParams *F) {
+  F->order_n = 0;
+  if (F->runs_per_pyr <= 0 || F->runs_per_pyr > pf::MAX_ORDER || !c->opt_run_order) return;
+  struct RunCost {
+    double cost;
+    int entry, run;
+  };
+  std::vector<RunCost> rc;
+  for (int l = 0; l < F->nlevels; l++) {
+    const pf::FusedLevel &L = F->lv[l];
+    const int ny = L.h - 2 * F->border;
+    for (int r = 0; r < L.nruns; r++) {
+      double cst = 0;
+      for (int sidx = r * F->run_len; sidx < std::min((r + 1) * F->run_len, L.nstrips); sidx++)
+        cst += 1.6 * L.w * std::min(L.R, ny - sidx * L.R) + 6000.0;
+      rc.push_back({cst, l, r});
+    }
+  }
+  std::stable_sort(rc.begin(), rc.end(), [](const RunCost &a, const RunCost &b) { return a.cost > b.cost; });
+  for (size_t i = 0; i < rc.size(); i++) F->order[i] = ((uint32_t)rc[i].entry << 16) | (uint32_t)rc[i].run;
+  F->order_n = (int)rc.size();
+}
+
+// The strip plan for heuristic strip heights of at most rows_max rows: the five steps above.  False: no strip plan for
+// these parameters (the staged pipeline takes the call).
 bool build_fused_plan_rows(const pislam_ctx *c, const pislam_frontend_params *p, const pislam_level *lv,
                            int batch, int rows_max, pf::FusedParams *F, size_t *lds_bytes, size_t *lds_alias_bytes) {
   if (p->nlevels > pf::MAX_LEVELS) return false;
@@ -1194,251 +1410,42 @@ bool build_fused_plan_rows(const pislam_ctx *c, const pislam_frontend_params *p,
   // fused bucket mode inside the strips: cells of 4..32 px (they must fit a strip and the per-wave scratch)
   if (F->lbs != 0 && (p->log_bucket_size < 2 || p->log_bucket_size > 5)) return false;
   F->ablate = c->opt_ablate;
+  if (!plan_entries(c, p, lv, F)) return false;
   int strips = 0, slots = 0, runs = 0;
   size_t lds = 0, lds_alias = 0;
-  // ALIAS layout, heuristic strip height for a level under a residency target of `wgs` workgroups per CU:
-  // ~16k pixels per strip, 16..28 rows, capped so that queues + tile + the minimum shared queue fit
-  // 160 KiB / wgs where 16 rows allow it (VGA at 5 per CU: 24 rows at level 0, 28 below; measured 0.293 ms
-  // vs 0.311 ms with 16-row strips).
-  // LDS pitch of an image tile row that stages columns [xbase, xend + 8): a multiple of 16 bytes.  (An ODD number of
-  // 16-byte vectors — consecutive rows 4 banks apart instead of column x of every row in one bank at VGA level 0's 640
-  // bytes — was measured in round 4: bit-exact, the strip kernel within 0.5 % either way: the per-candidate reads'
-  // bank conflicts, 45 % of its LDS cycles, come from the candidates' random columns, not from the row pitch.)
-  auto tile_pitch = [&](int xend_l) -> int {
-    return (xend_l - p->border + ((p->border - 4) & 15) + 4 + 8 + 15) & ~15;
-  };
-  auto alias_rows = [&](int xend_l, int w, int wgs) -> int {
-    const int tpitch_l = tile_pitch(xend_l);
-    const long budget = 160 * 1024 / wgs - (long)(pf::WAVES * pf::QCAP + pf::QH_SHARED) * 4;
-    const int rcap = (int)(budget / tpitch_l - 10) & ~1;
-    if (wgs != 5 && rcap < 10) return 0;              // (an explicit residency request falls back to the generic rule)
-    return std::max(16, std::min(std::min(rows_max, std::max(16, (c->opt_strip_px / w) & ~1)), rcap));
-  };
-  // Residency target of the heuristic: 5 workgroups per CU.  (A search over 5 / 4 / 3 per CU with a cost model
-  // "pixels * (R + 4) / R / measured throughput at that residency" was tried for the 1280-wide levels of BASELINE
-  // config 4 — 12-row strips at 4 per CU instead of 16 rows at 3 — and measured no better: 1.24 vs 1.21 ms at
-  // batch 256; forcing 5 per CU with 8-row strips and no halo carry gave 1.16 ms.  Option "wgs_per_cu" overrides.)
-  const int alias_wgs = c->opt_wgs_per_cu > 0 ? c->opt_wgs_per_cu : 5;
-  // Plan entries: a level, or the x-tiles of a wide level (pf::FusedLevel).  A level with more than `tile_max`
-  // classified columns is cut into tiles of T block-origin columns (T a multiple of 32: tiles start on
-  // bucket boundaries for every fused bucket size); tile t > 0 starts HALO = 32 columns to the left of its
-  // first block origin, so that, seen as a level of its own with the same border B, it classifies and scores
-  // the columns its boundary blocks' NMS reads, and every tile but the last ends 2 columns past its last
-  // owned block origin.
-  struct Entry {
-    int w, h, row0, col0, ex0, ex1, xscore, gfirst, gn, wmax;
-  };
-  std::vector<Entry> entries;
-  {
-    const int B = p->border, HALO = 32;
-    const int tile_max = c->opt_tile_cols > 0 ? c->opt_tile_cols : (c->opt_tile_cols < 0 ? 1 << 30 : 704);
-    for (int l = 0; l < p->nlevels; l++) {
-      const int w = lv[l].width, nx = w - 2 * B, ny = lv[l].height - 2 * B;
-      int nt = 1;
-      // tiles of ~448 owned columns: with the 32-column halo a tile row is two full 256-pixel prefilter steps,
-      // and its strips reach the full 28 rows at 5 workgroups per CU (1280x960 batch 256: 0.94 ms with three
-      // 416-column tiles at level 0 against 1.01 ms with two of 624)
-      if (nx > 0 && ny > 0 && 16 * cdiv(nx, 16) > tile_max)
-        nt = std::max(2, tile_max >= 640 ? (nx + 224) / 448 : cdiv(nx, std::max(64, tile_max)));
-      const int T = nt > 1 ? (cdiv(nx, nt) + 31) & ~31 : 0;
-      nt = nt > 1 ? cdiv(nx, T) : 1;
-      const int g0 = (int)entries.size();
-      int wmax = 0;
-      for (int t = 0; t < nt; t++) {
-        Entry e;
-        if (nt == 1) {
-          e = {w, lv[l].height, lv[l].row0, lv[l].col0, B, w - B, w - B, g0, 1, w};
-        } else {
-          const int o = t == 0 ? 0 : t * T - HALO;                 // level column of the entry's origin
-          const int E = std::min(B + (t + 1) * T, w - B);           // one past the last owned block origin (level x)
-          e.w = t == nt - 1 ? w - o : E - o + 2 + B;
-          e.h = lv[l].height;
-          e.row0 = lv[l].row0;
-          e.col0 = lv[l].col0 + o;
-          e.ex0 = t == 0 ? B : B + HALO;
-          e.ex1 = E - o;
-          e.xscore = (w - B) - o;
-          e.gfirst = g0;
-          e.gn = nt;
-        }
-        wmax = std::max(wmax, e.w);
-        entries.push_back(e);
-      }
-      for (int t = 0; t < nt; t++) entries[g0 + t].wmax = wmax;
-    }
-    if ((int)entries.size() > pf::MAX_LEVELS) return false;
-  }
-  F->nlevels = (int)entries.size();
   for (int l = 0; l < F->nlevels; l++) {
     pf::FusedLevel &L = F->lv[l];
-    const Entry &en = entries[l];
-    L.w = en.w;
-    L.h = en.h;
-    L.row0 = en.row0;
-    L.col0 = en.col0;
-    L.ex0 = en.ex0;
-    L.ex1 = en.ex1;
-    L.xscore = en.xscore;
-    L.gfirst = en.gfirst;
-    L.gn = en.gn;
     const int nx = L.w - 2 * p->border, ny = L.h - 2 * p->border;
     L.strip0 = strips;
     L.slot0 = slots;
     if (nx <= 0 || ny <= 0) {   // nothing to extract on this level (Fast.h loops do not run)
-      L.R = 16;
-      L.nstrips = 0;
-      L.nbx = 0;
+      L.R = 16;                 // (nstrips and nbx stay 0)
       L.xend = p->border;
       L.pitch = 16;
       continue;
     }
-    // (the strip height comes from the widest tile of the level: all its tiles must cut the same strips)
-    const int nx_r = en.wmax - 2 * p->border;
-    const int xend_l = p->border + 16 * cdiv(nx_r, 16), pitch_l = (xend_l + 4 + 15) & ~15;
-    const size_t qbytes = (pf::WAVES * pf::QCAP + pf::SHARED_Q) * sizeof(uint32_t);
-    int R = c->opt_strip_rows;
-    if (R == 0 && c->opt_alias) R = alias_rows(xend_l, en.wmax, alias_wgs);
-    if (R == 0) {
-      R = (8192 / en.wmax) & ~1;         // ~8k pixels per strip ...
-      R = std::min(32, std::max(16, R));
-      if (c->opt_wgs_per_cu > 0) {       // ... capped so that tiles + queues fit 160 KiB / wgs_per_cu
-        const size_t budget = (size_t)(160 * 1024) / (size_t)c->opt_wgs_per_cu;
-        if (budget > qbytes + 13 * (size_t)pitch_l) {
-          const int rcap = (int)(((budget - qbytes) / pitch_l - 13) / 2) & ~1;
-          R = std::max(8, std::min(R, rcap));
-        }
-      }
-    }
-    if (F->lbs) {                        // (selection inside the strips:) strips hold whole bucket rows
-      const int bs = 1 << p->log_bucket_size;
-      if (c->opt_strip_rows == 0 && c->opt_alias) {
-        // heuristic height: round UP to whole bucket rows (16-px buckets: 32-row strips — measured 0.315 ms
-        // vs 0.371 ms with 16-row strips) where that still fits the residency budget, DOWN on the levels where it
-        // does not: the launch has ONE LDS size, a single level over the budget costs every level its fifth workgroup
-        const int up = std::min(std::max(bs, 32), ((R + bs - 1) / bs) * bs), down = std::max(bs, (R / bs) * bs);
-        const int tp = tile_pitch(xend_l);
-        const long need = (long)(pf::WAVES * pf::QCAP + pf::QH_SHARED) * 4 + (long)(up + 10) * tp;
-        R = (c->opt_bucket_round_up || need <= 160 * 1024 / alias_wgs - 1280) ? up : down;
-      } else
-        R = std::max(bs, (R / bs) * bs);
-    }
-    L.R = R;
-    L.nstrips = cdiv(ny, R);
+    L.R = strip_height(c, p, F->lbs, widest_tile(*F, l), rows_max);
+    L.nstrips = cdiv(ny, L.R);
     L.nbx = (nx + 1) / 2;
-    L.xend = p->border + 16 * cdiv(nx, 16);
-    L.pitch = (L.xend + 4 + 15) & ~15;
-    {
-      // staged columns [xbase, xbase+tpitch) with xbase = (border-4) & ~15 must reach column xend+8
-      L.tpitch = tile_pitch(L.xend);
-    }
-    L.vpr_recip = (uint32_t)(((1ull << 32) + (L.tpitch / 16) - 1) / (L.tpitch / 16));
-    L.tp_recip = (uint32_t)(((1ull << 32) + L.tpitch - 1) / L.tpitch);
+    L.xend = classified_end(p->border, nx);
+    level_lds(p->border, alias_wgs(c), L, &lds, &lds_alias);
     strips += L.nstrips;
-    slots += L.nstrips * (R / 2) * L.nbx;
-    // scan fallbacks reuse the image tile: row buffers of R/2 x nbx dwords, or per-cell results (<= one
-    // dword per block) + per-cell counts (<= a quarter of that: a cell holds >= 2x2 blocks)
-    L.tbytes = std::max((R + 10) * L.tpitch, (((R / 2) * L.nbx * 5 + 64) + 15) & ~15);
-    lds = std::max(lds, (size_t)L.tbytes + (size_t)(R + 3) * L.pitch +
-                            (pf::WAVES * pf::QCAP + pf::SHARED_Q) * sizeof(uint32_t));
-    {
-      // ALIAS layout: the score tile (R+3 rows) is laid over [NMS scratch end, image row R): pad the
-      // per-wave queue area when that span is too short (levels wider than ~680 columns)
-      // ... and the ORB phase's 8 patches + vrecpe table are laid over the same span (strip_body phase E)
-      const long need = std::max((long)pf::NMS_SCRATCH * 4 + (long)(R + 3) * L.pitch,
-                                 (long)pf::NMS_SCRATCH * 4 + (long)pf::WAVES * 2 * pf::ORB_PATCH_BYTES + 256);
-      const long have = (long)pf::WAVES * pf::QCAP * 4 + (long)R * L.tpitch;
-      L.apad = need > have ? (int)((need - have + 15) & ~15L) : 0;
-      // one shared queue in this layout: at least QH_SHARED entries, and whatever LDS the level's tile
-      // leaves under the 5-workgroups-per-CU budget (narrow levels of a textured photo are the dense ones)
-      const long fixed = (long)pf::WAVES * pf::QCAP * 4 + L.apad + (long)(R + 10) * L.tpitch;
-      // (margin of 1280 B: static LDS + allocation granule — with 512 B the kernel measurably lost its 5th workgroup)
-      const long spare = (160 * 1024 / alias_wgs - 1280 - fixed) / 4;
-      L.qh = (int)std::min<long>(4096, std::max<long>(pf::QH_SHARED, spare & ~3L));
-      lds_alias = std::max(lds_alias, (size_t)fixed + (size_t)L.qh * 4);
-    }
+    slots += L.nstrips * (L.R / 2) * L.nbx;
   }
-  // Runs: a workgroup walks run_len consecutive strips of a level (halo carried in LDS).  Longer runs save the
-  // duplicated halo work but leave fewer, longer workgroups for the dispatcher to balance over the 5 resident
-  // slots per CU.  Measured (strip kernel, ms): VGA batch 256 (15 strips per slot): 0.236 / 0.231 / 0.233 / 0.243 /
-  // 0.242 / 0.235 / 0.231 / 0.229 / 0.229 / 0.243 for run_len 1 / 2 / 3 / 4 / 5 / 6 / 8 / 10 / 12 / 16 — the carry is
-  // worth ~3 % at best and the curve is dispatch-quantisation noise; 720p batch 64 (10 strips per slot): 0.208 /
-  // 0.207 / 0.216 / 0.227 / 0.238 for 1..5; 1280x960 batch 256 (54 per slot): 1.029 / 1.018 / 1.012 / 1.044 / 1.053 /
-  // 1.010 for 4 / 5 / 6 / 7 / 8..10 / 12, batch 64: 0.278 / 0.307 / 0.376 for 2 / 3 / 8; VGA batch 32, 64: 1 is best.
-  // Rule: ~6.5 workgroups per resident slot, at most 8 strips per run.  (List-scheduling and processor-sharing
-  // simulations of one XCD were tried as a predictor: neither tracks the measured 2-3 % structure.)
-  // With the runs of a pyramid launched longest first (order[], below) the curve flattens: VGA batch 256
-  // 0.232 / 0.222 / 0.220 / 0.224 / 0.222 / 0.233 for run_len 1 / 2 / 3 / 4 / 6 / 8; 1280x960 batch 256 0.920 / 0.898 /
-  // 0.899 / 0.889 / 0.889 for 2 / 4 / 6 / 8 / 12; 720p batch 64 0.191 / 0.191 / 0.197 / 0.206 for 1 / 2 / 3 / 4.
-  {
-    // Round 5 (strips of a run follow each other without a barrier): one call at a time the rule stands (VGA batch 256: strip
-    // kernel 0.164 / 0.166 / 0.171 ms for run_len 2 / 3 / 4), but as a LANE of a pipeline — other batches' kernels fill the
-    // tail of the launch — longer runs win: whole step 0.2233 / 0.2208 / 0.2203 ms for 2 / 3 / 4 (720p batch 64: 0.2974 /
-    // 0.2954 for 2 / 3; demo photo x 256: 0.3242 / 0.3208 for 2 / 4).  Lanes aim at ~3.25 workgroups per slot.
-    const double per_slot = (double)strips * batch / (5.0 * std::max(1, c->num_cus));
-    const double per_wg = c->lanes_in_flight > 1 ? 3.25 : 6.5;
-    F->run_len = c->opt_run_len > 0 ? c->opt_run_len : std::max(1, std::min(8, (int)(per_slot / per_wg + 0.5)));
-    // Round 6, lanes only: the LONGEST runs that still leave the launch 0.6 workgroups per resident slot (5 per CU) — whole
-    // levels per workgroup where the batch is large enough.  Re-swept after the pretest change, pipelined step in ms for
-    // run_len default (the rule above) / 12 / 16 / 24 / 32 / 64: VGA batch 256 0.2117 / 0.2087 / 0.2062 / 0.2072 / 0.2063 / 0.2068
-    // (8 whole-level runs per pyramid = 1.6 per slot); demo photo 0.3169 / 0.3153 / 0.3153 / 0.3144 / 0.3143 / 0.3140; 1280x960
-    // 0.6692 / 0.6674 / 0.6628 / 0.6637 / 0.6517 / 0.6531; 720p build batch 64 0.2865 / 0.2759 / 0.2671 / 0.2581 / 0.2589 / 0.2590
-    // (15 runs per pyramid = 0.75 per slot); bucket mode 0.2334 / 0.2293 / 0.2285 / 0.2281 / 0.2287 / 0.2277 — and where the
-    // launch gets too few workgroups it turns: VGA batch 64 0.0646 / 0.0631 (0.6 per slot) / 0.0681 (0.5) / 0.0720; batch 16
-    // 0.0208 / 0.0425.  The strip kernel ALONE is slower with long runs (0.156 -> 0.159-0.162 ms: a longer tail); on a lane
-    // another batch's kernels run in that tail, and a long run stages its halo once and prefetches every strip but the first.
-    if (c->opt_run_len <= 0 && c->lanes_in_flight > 1) {
-      const long want = (long)(0.6 * 5.0 * std::max(1, c->num_cus));
-      int longest = 1;
-      for (int l = 0; l < F->nlevels; l++) longest = std::max(longest, F->lv[l].nstrips);
-      longest = std::min(longest, 64);                 // (option range; k_frame keeps a 64-bit mask of a run's strips)
-      for (int rl = longest; rl > F->run_len; rl--) {
-        long r = 0;
-        for (int l = 0; l < F->nlevels; l++) r += cdiv(F->lv[l].nstrips, rl);
-        if (r * batch >= want && r <= pf::MAX_ORDER) {
-          F->run_len = rl;
-          break;
-        }
-      }
-    }
-  }
+  F->run_len = run_length(c, *F, strips, batch);
   for (int l = 0; l < F->nlevels; l++) {
     F->lv[l].run0 = runs;
     F->lv[l].nruns = cdiv(F->lv[l].nstrips, F->run_len);
     runs += F->lv[l].nruns;
   }
-  // Launch order of a pyramid's runs: estimated cost (pixels + a fixed share per strip), longest first — the
-  // longest-processing-time-first rule of list scheduling: workgroups are dispatched in blockIdx order to the
-  // 5 resident slots per CU, so the short runs of the small levels fill the tail of the launch.  Entry order
-  // (level by level) interleaves short last-runs of big levels with long runs of the next level: VGA batch 256
-  // 0.232 -> 0.222 ms, 1280x960 batch 256 0.927 -> 0.895 ms.
-  F->order_n = 0;
-  if (runs > 0 && runs <= pf::MAX_ORDER && c->opt_run_order) {
-    struct RunCost {
-      double cost;
-      int entry, run;
-    };
-    std::vector<RunCost> rc;
-    for (int l = 0; l < F->nlevels; l++) {
-      const pf::FusedLevel &L = F->lv[l];
-      const int ny = L.h - 2 * p->border;
-      for (int r = 0; r < L.nruns; r++) {
-        double cst = 0;
-        for (int sidx = r * F->run_len; sidx < std::min((r + 1) * F->run_len, L.nstrips); sidx++)
-          cst += 1.6 * L.w * std::min(L.R, ny - sidx * L.R) + 6000.0;
-        rc.push_back({cst, l, r});
-      }
-    }
-    std::stable_sort(rc.begin(), rc.end(), [](const RunCost &a, const RunCost &b) { return a.cost > b.cost; });
-    for (size_t i = 0; i < rc.size(); i++) F->order[i] = ((uint32_t)rc[i].entry << 16) | (uint32_t)rc[i].run;
-    F->order_n = (int)rc.size();
-  }
   F->strips_per_pyr = strips;
   F->runs_per_pyr = runs;
   F->slots_per_pyr = slots;
+  order_runs(c, F);
   *lds_bytes = lds;
   *lds_alias_bytes = lds_alias + (size_t)c->opt_lds_pad;   // profiling: opt_lds_pad lowers the residency artificially
   if ((size_t)p->rows * p->vstep > 0x7fffffffu) return false;   // 32-bit byte offsets inside a pyramid
-  return lds <= 150 * 1024;       // (strips == 0: no level holds a classifiable pixel — the caller writes zero counts)
+  return lds <= LDS_CAP;          // (strips == 0: no level holds a classifiable pixel — the caller writes zero counts)
 }
 
 // Cap of the heuristic strip height.  Every strip pays a fixed share (set-up, barriers, the halo carried through
@@ -1453,8 +1460,7 @@ bool build_fused_plan(const pislam_ctx *c, const pislam_frontend_params *p, cons
   if (c->opt_strip_rows_max > 0)
     return build_fused_plan_rows(c, p, lv, batch, c->opt_strip_rows_max, F, lds_bytes, lds_alias_bytes);
   if (!build_fused_plan_rows(c, p, lv, batch, 28, F, lds_bytes, lds_alias_bytes)) return false;
-  const double per_slot = (double)F->strips_per_pyr * batch / (5.0 * std::max(1, c->num_cus));
-  if (per_slot < 12.0) return true;
+  if (strips_per_slot(c, F->strips_per_pyr, batch) < 12.0) return true;
   pf::FusedParams tall;
   size_t l0 = 0, l1 = 0;
   if (build_fused_plan_rows(c, p, lv, batch, 56, &tall, &l0, &l1)) {
@@ -1512,7 +1518,7 @@ int ensure_aux(pislam_ctx *c, int nsub) {
 }
 
 // The bucket selection pass (pf::k_bucket_select) and the UNIT plan the gather runs on when the strips run as without buckets
-// (build_fused_plan_rows): one "strip" per (level, cell row), `buckets x limit` slots each, lists final (lbs != 0, no tiles:
+// (build_fused_plan): one "strip" per (level, cell row), `buckets x limit` slots each, lists final (lbs != 0, no tiles:
 // the gather concatenates).  Part of the call's plan (plan_frontend).
 int build_select_plan(pislam_ctx *c, const pislam_frontend_params *p, const pf::FusedParams &Fplan, pf::SelectPlan *Qp,
                       pf::FusedParams *Up) {
@@ -1735,12 +1741,67 @@ int plan_frontend(pislam_ctx *c, const pislam_frontend_params *p, const pislam_l
     P->fch = c->opt_orb_chunks > 0 ? std::min(c->opt_orb_chunks, 128) : std::min(64, std::max(16, 128 / batch));
     P->fper = ((size_t)p->max_keypoints + P->fch - 1) / P->fch;
     P->flds = std::max(std::max(P->lds_alias, P->lds), pf::orb_lds_bytes(S, P->fper));
-    const long wg_per_cu = std::max<long>(1, std::min<long>(5, (long)(160 * 1024) / (long)std::max<size_t>(P->flds, 1)));
+    const long wg_per_cu = std::max<long>(1, std::min<long>(5, CU_LDS / (long)std::max<size_t>(P->flds, 1)));
     const long slots_per_xcd = wg_per_cu * std::max(1, c->num_cus / 8);
     const long waiting_per_xcd = ((long)std::max(1, c->lanes_in_flight) * batch * P->fch + 7) / 8;
-    P->frame = P->flds <= 150 * 1024 && 4 * waiting_per_xcd <= slots_per_xcd;
+    P->frame = P->flds <= LDS_CAP && 4 * waiting_per_xcd <= slots_per_xcd;
   }
   return PISLAM_OK;
+}
+
+// The invariants of a plan the kernels rely on (pislam_debug_build_plan checks every plan it builds): what is violated, or
+// nullptr.  The strip plan first; the selection plan's are a second function because plan_frontend may have refused it.
+const char *strip_plan_violation(const FrontendPlan &P, const pislam_frontend_params *p) {
+  const pf::FusedParams &F = P.F;
+  if (F.nlevels < 1 || F.nlevels > pf::MAX_LEVELS) return "entries";
+  int strips = 0, slots = 0, runs = 0;
+  for (int l = 0; l < F.nlevels; l++) {
+    const pf::FusedLevel &L = F.lv[l];
+    if (L.strip0 != strips || L.slot0 != slots || L.run0 != runs) return "prefix sums";
+    if (L.nstrips < 0 || (L.nstrips > 0 && (L.R < 2 || (L.R & 1)))) return "strip height";
+    if (L.nstrips > 0) {
+      if (L.col0 < 0 || L.row0 < 0 || L.col0 + L.w > p->vstep || L.row0 + L.h > p->rows) return "entry outside the pyramid";
+      if (L.tpitch % 16 || L.pitch % 16 || L.tpitch <= 0) return "pitch";
+      if ((L.R + 10) * L.tpitch > (int)LDS_CAP) return "tile larger than the LDS";
+      if (L.gfirst < 0 || L.gfirst > l || L.gn < 1 || L.gfirst + L.gn > F.nlevels) return "tile group";
+      if (L.ex0 < p->border || L.ex1 > L.w || L.ex0 > L.ex1) return "owned columns";
+      if (cdiv(L.nstrips, F.run_len) != L.nruns) return "runs";
+      if ((uint64_t)L.vpr_recip * (uint64_t)(L.tpitch / 16) < (1ull << 32)) return "vpr_recip";
+      if ((uint64_t)L.tp_recip * (uint64_t)L.tpitch < (1ull << 32)) return "tp_recip";
+      if (L.qh < pf::QH_SHARED) return "corner queue";
+    }
+    strips += L.nstrips;
+    slots += L.nstrips * (L.R / 2) * L.nbx;
+    runs += L.nruns;
+  }
+  if (strips != F.strips_per_pyr || slots != F.slots_per_pyr || runs != F.runs_per_pyr) return "totals";
+  if (F.order_n) {
+    if (F.order_n != runs || runs > pf::MAX_ORDER) return "order size";
+    std::vector<int> seen((size_t)runs, 0);
+    for (int i = 0; i < F.order_n; i++) {
+      const int e = (int)(F.order[i] >> 16), r = (int)(F.order[i] & 0xffff);
+      if (e >= F.nlevels || r >= F.lv[e].nruns) return "order entry";
+      seen[(size_t)(F.lv[e].run0 + r)]++;
+    }
+    for (int v : seen)
+      if (v != 1) return "order is not a permutation of the runs";
+  }
+  if (P.lds_alias > (size_t)CU_LDS) return "aliased LDS size";
+  return nullptr;
+}
+
+const char *select_plan_violation(const FrontendPlan &P, const pislam_frontend_params *p) {
+  const pf::SelectPlan &Q = P.Q;
+  int units = 0, uslots = 0;
+  for (int l = 0; l < Q.nlevels; l++) {
+    if (Q.unit0[l] != units || Q.uslot0[l] != uslots) return "selection plan prefix sums";
+    if (Q.g0[l] < 0 || Q.g0[l] + Q.gn[l] > P.F.nlevels) return "selection plan entries";
+    if (Q.cap[l] / p->bucket_limit > pf::SEL_NB) return "more buckets than the selection pass holds";
+    units += Q.nunits[l];
+    uslots += Q.nunits[l] * Q.cap[l];
+  }
+  if (units != Q.units_per_pyr || uslots != Q.uslots_per_pyr) return "selection plan totals";
+  return nullptr;
 }
 
 // The workspace of plan P: the only place the front end's buffers are allocated (option "ablate" 8192's profiling aside).
@@ -1791,18 +1852,201 @@ int reserve_frontend(pislam_ctx *c, const pislam_frontend_params *p, const pisla
   return PISLAM_OK;
 }
 
+// A kernel that asks for more dynamic LDS than LDS_OPT_IN has its limit raised first.
+#define RAISE_LDS_LIMIT(c, kern, bytes)                                                                                \
+  do {                                                                                                                 \
+    if ((bytes) > LDS_OPT_IN)                                                                                          \
+      HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));      \
+  } while (0)
+
+using StripKernT = void (*)(const pf::FusedParams, const uint8_t *, size_t, uint32_t *, uint32_t *, uint8_t *, size_t,
+                            unsigned long long *, uint32_t *, uint32_t *);
+using OvfKernT = void (*)(const pf::FusedParams, const uint8_t *, size_t, uint32_t *, uint32_t *, uint8_t *, size_t, const uint32_t *);
+
+// The kernels a fused call runs.  vec: 16-byte aligned rows; hooks: score-map dump (debug / parity hook) or a profiling ablation.
+StripKernT strip_kernel(bool vec, bool alias, bool hooks, bool orb_in_strip, int lbs) {
+  static const StripKernT kerns[8] = {
+      pf::k_fused_strips<false, false, false>, pf::k_fused_strips<false, false, true>,
+      pf::k_fused_strips<false, true, false>,  pf::k_fused_strips<false, true, true>,
+      pf::k_fused_strips<true, false, false>,  pf::k_fused_strips<true, false, true>,
+      pf::k_fused_strips<true, true, false>,   pf::k_fused_strips<true, true, true>};
+  // strips describing their own keypoints (option "orb_in_strip"): separate instantiations of the aligned ALIAS kernels
+  static const StripKernT kerns_orb[2] = {pf::k_fused_strips<true, false, true, true>, pf::k_fused_strips<true, true, true, true>};
+  // the default mode's kernels (aligned ALIAS layout, no buckets, gather+ORB describes): compiled without the bucket code
+  static const StripKernT kerns_nb[2] = {pf::k_fused_strips<true, false, true, false, false>,
+                                         pf::k_fused_strips<true, true, true, false, false>};
+  return (orb_in_strip && vec && alias) ? kerns_orb[hooks ? 1 : 0]
+         : (vec && alias && lbs == 0)   ? kerns_nb[hooks ? 1 : 0]
+                                        : kerns[(vec ? 4 : 0) | (hooks ? 2 : 0) | (alias ? 1 : 0)];
+}
+OvfKernT overflow_kernel(bool vec, bool hooks) {
+  static const OvfKernT okerns[4] = {pf::k_fused_overflow<false, false>, pf::k_fused_overflow<false, true>,
+                                     pf::k_fused_overflow<true, false>, pf::k_fused_overflow<true, true>};
+  return okerns[(vec ? 2 : 0) | (hooks ? 1 : 0)];
+}
+// (the profiling instantiation exists for the gather's per-phase counters: option "ablate" bits 20..23, pf::orb_describe)
+auto gather_orb_kernel(int ablate) { return (ablate >> 20) & 15 ? pf::k_gather_orb<true> : pf::k_gather_orb<false>; }
+
+// Per-keypoint ORB over n pyramids (pk::k_orb<0>, blockIdx.z = pyramid): the staged pipeline's last launch, and the fused
+// pipeline's where k_gather_orb does not take the layout.
+int launch_orb_batch(pislam_ctx *c, hipStream_t stream, const pislam_frontend_params *p, const uint8_t *pyramids, size_t stride,
+                     int n, const uint32_t *kp, const uint32_t *counts, uint32_t *desc) {
+  hipLaunchKernelGGL(pk::k_orb<0>, dim3(cdiv(p->max_keypoints, 4), 1, n), dim3(256), 0, stream, pyramids, p->vstep, stride, kp,
+                     (size_t)p->max_keypoints, counts, 0u, (uint32_t)p->max_keypoints, p->words, desc,
+                     (size_t)p->max_keypoints * p->words, (int32_t *)nullptr, (const uint8_t *)nullptr);
+  return launch_ok(c, "k_orb<batch>");
+}
+
+// Profiling hook (option "ablate" 8192): the strip kernel's per-phase workgroup cycles, 8 counters per workgroup -> stderr.
+int report_strip_profile(pislam_ctx *c, const unsigned long long *prof, size_t prof_n, hipStream_t M, double ns, unsigned workgroups) {
+  std::vector<unsigned long long> hv(prof_n);
+  HIPCHK(c, hipMemcpyAsync(hv.data(), prof, prof_n * sizeof(unsigned long long), hipMemcpyDeviceToHost, M));
+  HIPCHK(c, hipStreamSynchronize(M));
+  double h[8] = {0};
+  unsigned long long why[3] = {0, 0, 0};
+  for (size_t i = 0; i < prof_n; i++) {
+    if ((i & 7) == 5) {
+      why[0] += hv[i] & 0xfffff;
+      why[1] += (hv[i] >> 20) & 0xfffff;
+      why[2] += hv[i] >> 40;
+    } else {
+      h[i & 7] += (double)hv[i];
+    }
+  }
+  fprintf(stderr, "[pislam prof] deferred strips by reason: corner queue %llu, score queue %llu, survivor buffer %llu\n",
+          why[0], why[1], why[2]);
+  fprintf(stderr, "[pislam prof] cycles/strip: stage %.0f classify %.0f harris %.0f nms %.0f emit %.0f "
+                  "(strips %.0f, carried %.0f, workgroups %u, lifetime %.0f/strip)\n",
+          h[0] / ns, h[1] / ns, h[2] / ns, h[3] / ns, h[4] / ns, ns, h[6], workgroups, h[7] / ns);
+  return PISLAM_OK;
+}
+
+// What the launches of one fused call share: the call's arguments, the kernels chosen for it and its two streams.
+struct FusedCall {
+  const pislam_frontend_params *p;
+  const FrontendPlan &P;
+  const uint8_t *pyramids;
+  size_t stride;
+  int batch;
+  uint32_t *kp, *desc, *counts;
+  StripKernT kern;
+  OvfKernT okern;
+  decltype(gather_orb_kernel(0)) gkern;
+  bool fork;          // sub-batches fork: an eager call with more than one
+  hipStream_t M, X;   // the context stream (strips), and where the rest of a sub-batch runs: M, or the aux stream of a fork
+};
+
+// ---- small batches: strips -> (overflowed strips redone in place) -> gather + ORB as ONE launch ----
+int launch_frame(pislam_ctx *c, const FusedCall &k) {
+  const pislam_frontend_params *p = k.p;
+  const FrontendPlan &P = k.P;
+  RAISE_LDS_LIMIT(c, pf::k_frame, P.flds);
+  pf::FusedParams F = P.F;
+  F.batch = k.batch;
+  const unsigned grid = (unsigned)(k.batch * F.runs_per_pyr + k.batch * P.fch);
+  hipLaunchKernelGGL(pf::k_frame, dim3(grid), dim3(pf::NT), P.flds, c->stream, F, k.pyramids, k.stride, c->w_stage.as<uint32_t>(),
+                     c->w_stripcnt.as<uint32_t>(), k.kp, (size_t)p->max_keypoints, (uint32_t)p->max_keypoints, k.counts, k.desc,
+                     (size_t)p->max_keypoints * p->words, p->words, (uint32_t)P.fper, P.fch, c->w_sync.as<uint32_t>(),
+                     c->w_ovf.as<uint32_t>(), c->frame_flag_dev, (uint32_t)c->opt_frame_test);
+  PCHK(launch_ok(c, "k_frame"));
+  c->last_path = PISLAM_PATH_FUSED | PISLAM_PATH_ONE_LAUNCH;
+  HIPCHK(c, hipEventRecord(c->ev[1], c->stream));   // (one launch: the stage split of last_timing is all in stage 0)
+  HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
+  return PISLAM_OK;
+}
+
+// Sub-batch `sub` of the call (the whole call where nsub == 1): strips on M; overflow pass, bucket selection and gather + ORB on X.
+int launch_sub_batch(pislam_ctx *c, const FusedCall &k, int sub) {
+  const pislam_frontend_params *p = k.p;
+  const FrontendPlan &P = k.P;
+  const int S = P.F.strips_per_pyr, nsub = P.nsub, base = k.batch / nsub, rem = k.batch % nsub;
+  const int first = sub * base + std::min(sub, rem), n = base + (sub < rem ? 1 : 0);
+  const hipStream_t M = k.M, X = k.X;
+  pf::FusedParams F = P.F;
+  F.batch = n;
+  const size_t dump_stride = (size_t)p->rows * p->vstep;
+  const uint8_t *s_pyr = k.pyramids + (size_t)first * k.stride;
+  uint32_t *s_stage = c->w_stage.as<uint32_t>() + (size_t)first * F.slots_per_pyr;
+  uint32_t *s_cnt = c->w_stripcnt.as<uint32_t>() + (size_t)first * S;
+  uint32_t *s_sdesc = c->w_stagedesc.as<uint32_t>() + (size_t)first * P.sdesc_per_pyr;
+  uint8_t *s_dump = F.dump_score ? c->w_score.as<uint8_t>() + (size_t)first * dump_stride : nullptr;
+  uint32_t *s_kp = k.kp + (size_t)first * p->max_keypoints;
+  uint32_t *s_desc = k.desc + (size_t)first * p->max_keypoints * p->words;
+  uint32_t *s_counts = k.counts + first;
+  uint32_t *ovf = P.alias ? c->w_ovf.as<uint32_t>() + (size_t)sub * P.ovf_stride : nullptr;
+  const dim3 grid((unsigned)(cdiv(n, 8) * F.runs_per_pyr * 8));
+  unsigned long long *prof = nullptr;
+  const size_t prof_n = (size_t)grid.x * 8;
+  if (F.ablate & 8192) {                         // profiling hook: per-phase workgroup cycles -> stderr
+    if (c->w_prof.ensure(prof_n * sizeof(unsigned long long)) != PISLAM_OK) return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(prof)");
+    prof = c->w_prof.as<unsigned long long>();
+    HIPCHK(c, hipMemsetAsync(prof, 0, prof_n * sizeof(unsigned long long), M));
+  }
+  // (profiling option "repeat_strips": the strip kernel launched n times back to back inside the stage-0
+  //  event bracket, so that the per-launch duration is not inflated by the command-processor latency
+  //  around a single eager launch; every launch rewrites the same outputs)
+  for (int rep = 0; rep < std::max(1, c->opt_repeat_strips); rep++) {
+    if (rep && ovf) HIPCHK(c, hipMemsetAsync(ovf, 0, sizeof(uint32_t), M));   // the last launch's list counts
+    hipLaunchKernelGGL(k.kern, grid, dim3(pf::NT), P.klds, M, F, s_pyr, k.stride, s_stage, s_cnt, s_dump, dump_stride, prof, ovf,
+                       s_sdesc);
+  }
+  if (prof) PCHK(report_strip_profile(c, prof, prof_n, M, (double)S * n, grid.x));
+  PCHK(launch_ok(c, "k_fused_strips"));
+  if (nsub > 1) {
+    if (k.fork) {
+      // fork: the rest of this sub-batch runs on the aux stream, under the next sub-batch's strip kernel
+      HIPCHK(c, hipEventRecord(c->ev_sub[sub], M));
+      HIPCHK(c, hipStreamWaitEvent(X, c->ev_sub[sub], 0));
+    }
+    if (sub == nsub - 1) {
+      HIPCHK(c, hipEventRecord(c->ev[1], M));   // stage 0 = every sub-batch's strip kernel
+      HIPCHK(c, hipEventRecord(c->ev[2], M));   // (stage 1, the overflow passes, runs on the aux stream)
+    }
+  } else {
+    HIPCHK(c, hipEventRecord(c->ev[1], M));     // stage 0 = the strip kernel alone
+  }
+  if (P.alias) {
+    hipLaunchKernelGGL(k.okern, dim3((unsigned)std::max(8, c->num_cus / 2)), dim3(pf::NT), P.lds, X, F, s_pyr, k.stride, s_stage,
+                       s_cnt, s_dump, dump_stride, (const uint32_t *)ovf);
+    PCHK(launch_ok(c, "k_fused_overflow"));
+  }
+  if (nsub == 1) HIPCHK(c, hipEventRecord(c->ev[2], M));   // stage 1 = the overflow pass (normally empty)
+  // the plan, lists and counts the gather runs on: the strips' own, or the units of the bucket selection pass
+  pf::FusedParams G = F;
+  const uint32_t *g_stage = s_stage, *g_cnt = s_cnt;
+  if (P.sel) {
+    uint32_t *u_stage = c->w_ustage.as<uint32_t>() + (size_t)first * P.Q.uslots_per_pyr;
+    uint32_t *u_cnt = c->w_ucount.as<uint32_t>() + (size_t)first * P.Q.units_per_pyr;
+    hipLaunchKernelGGL(pf::k_bucket_select, dim3(cdiv(P.Q.units_per_pyr, pf::SEL_WAVES), n), dim3(64 * pf::SEL_WAVES), P.sel_lds, X, F, P.Q,
+                       (const uint32_t *)s_stage, (const uint32_t *)s_cnt, u_stage, u_cnt, c->cur_utab);
+    PCHK(launch_ok(c, "k_bucket_select"));
+    G = P.U;
+    G.batch = n;
+    g_stage = u_stage;
+    g_cnt = u_cnt;
+  }
+  if (P.generic_orb) {
+    c->last_path |= PISLAM_PATH_GENERIC_ORB;
+    hipLaunchKernelGGL(pf::k_gather, dim3(n), dim3(256), P.glds, X, G, g_stage, g_cnt, s_kp,
+                       (size_t)p->max_keypoints, (uint32_t)p->max_keypoints, s_counts, ovf);
+    PCHK(launch_ok(c, "k_gather"));
+    return launch_orb_batch(c, X, p, s_pyr, k.stride, n, s_kp, s_counts, s_desc);
+  }
+  hipLaunchKernelGGL(k.gkern, dim3(P.nch, n), dim3(256), P.olds, X, G, s_pyr, k.stride, g_stage, g_cnt,
+                     (const uint32_t *)s_sdesc, s_kp, (size_t)p->max_keypoints, (uint32_t)p->max_keypoints, s_counts,
+                     s_desc, (size_t)p->max_keypoints * p->words, p->words, (uint32_t)P.per_max, ovf);
+  return launch_ok(c, "k_gather_orb");
+}
+
 // Launches plan P (strips_per_pyr > 0, workspace reserved by reserve_frontend) with the call's pointers.
 int run_fused(pislam_ctx *c, const pislam_frontend_params *p, const FrontendPlan &P, const uint8_t *pyramids, size_t stride,
               int batch, uint32_t *kp, uint32_t *desc, uint32_t *counts) {
-  const int S = P.F.strips_per_pyr, nsub = P.nsub;
-  const bool sel = P.sel, alias = P.alias;
-  c->last_path = PISLAM_PATH_FUSED | (sel ? PISLAM_PATH_BUCKET_SELECT : 0u) | (P.F.lbs != 0 ? PISLAM_PATH_BUCKETS_IN_STRIPS : 0u);
+  const int nsub = P.nsub;
+  c->last_path = PISLAM_PATH_FUSED | (P.sel ? PISLAM_PATH_BUCKET_SELECT : 0u) | (P.F.lbs != 0 ? PISLAM_PATH_BUCKETS_IN_STRIPS : 0u);
   // 16-byte loads need 16-byte aligned rows
   bool vec = ((uintptr_t)pyramids % 16 == 0) && (stride % 16 == 0) && (p->vstep % 16 == 0);
   for (int l = 0; l < P.F.nlevels; l++) vec = vec && (P.F.lv[l].col0 % 16 == 0);
-  uint8_t *dump = P.F.dump_score ? c->w_score.as<uint8_t>() : nullptr;
-  const size_t dump_stride = (size_t)p->rows * p->vstep;
-  if (alias) c->last_strips = (uint32_t)S * (uint32_t)batch;
+  if (P.alias) c->last_strips = (uint32_t)P.F.strips_per_pyr * (uint32_t)batch;
   // A call that is being captured into a hipGraph does not fork: its sub-batches then run in order on the context stream, and
   // the graph is one chain of nodes like every other captured call.  (A graph with a parallel branch from the fork crashed
   // inside hipGraphLaunch when it was replayed; chains replay fine.)  Eager calls fork as before.
@@ -1812,165 +2056,24 @@ int run_fused(pislam_ctx *c, const pislam_frontend_params *p, const FrontendPlan
     capture = hipStreamCaptureStatusNone;
   }
   const bool fork = nsub > 1 && capture == hipStreamCaptureStatusNone;
-  // HOOKS instantiations: score-map dump (debug / parity hook) and the profiling ablations
   const bool hooks = P.F.dump_score || P.F.ablate;
-  using KernT = void (*)(const pf::FusedParams, const uint8_t *, size_t, uint32_t *, uint32_t *, uint8_t *, size_t,
-                         unsigned long long *, uint32_t *, uint32_t *);
-  static const KernT kerns[8] = {
-      pf::k_fused_strips<false, false, false>, pf::k_fused_strips<false, false, true>,
-      pf::k_fused_strips<false, true, false>,  pf::k_fused_strips<false, true, true>,
-      pf::k_fused_strips<true, false, false>,  pf::k_fused_strips<true, false, true>,
-      pf::k_fused_strips<true, true, false>,   pf::k_fused_strips<true, true, true>};
-  // strips describing their own keypoints (option "orb_in_strip"): separate instantiations of the aligned ALIAS kernels
-  static const KernT kerns_orb[2] = {pf::k_fused_strips<true, false, true, true>, pf::k_fused_strips<true, true, true, true>};
-  // the default mode's kernels (aligned ALIAS layout, no buckets, gather+ORB describes): compiled without the bucket code
-  static const KernT kerns_nb[2] = {pf::k_fused_strips<true, false, true, false, false>,
-                                    pf::k_fused_strips<true, true, true, false, false>};
-  const KernT kern = (P.F.orb_in_strip && vec && alias) ? kerns_orb[hooks ? 1 : 0]
-                     : (vec && alias && P.F.lbs == 0)   ? kerns_nb[hooks ? 1 : 0]
-                                                          : kerns[(vec ? 4 : 0) | (hooks ? 2 : 0) | (alias ? 1 : 0)];
-  if (P.klds > 150 * 1024) return fail(c, PISLAM_ERR_INVALID, "level too wide for the strip kernel's LDS tiles");
-  if (P.klds > 64 * 1024)
-    HIPCHK(c, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.klds));
-  using OvfT = void (*)(const pf::FusedParams, const uint8_t *, size_t, uint32_t *, uint32_t *, uint8_t *, size_t,
-                        const uint32_t *);
-  static const OvfT okerns[4] = {pf::k_fused_overflow<false, false>, pf::k_fused_overflow<false, true>,
-                                 pf::k_fused_overflow<true, false>, pf::k_fused_overflow<true, true>};
-  const OvfT okern = okerns[(vec ? 2 : 0) | (hooks ? 1 : 0)];
-  if (alias && P.lds > 64 * 1024)
-    HIPCHK(c, hipFuncSetAttribute((const void *)okern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds));
-  // (the profiling instantiation exists for the gather's per-phase counters: option "ablate" bits 20..23, pf::orb_describe)
-  const auto gkern = (P.F.ablate >> 20) & 15 ? pf::k_gather_orb<true> : pf::k_gather_orb<false>;
+  const StripKernT kern = strip_kernel(vec, P.alias, hooks, P.F.orb_in_strip, P.F.lbs);
+  if (P.klds > LDS_CAP) return fail(c, PISLAM_ERR_INVALID, "level too wide for the strip kernel's LDS tiles");
+  RAISE_LDS_LIMIT(c, kern, P.klds);
+  const OvfKernT okern = overflow_kernel(vec, hooks);
+  if (P.alias) RAISE_LDS_LIMIT(c, okern, P.lds);
+  const auto gkern = gather_orb_kernel(P.F.ablate);
   if (!P.generic_orb) {
-    if (P.olds > 150 * 1024) return fail(c, PISLAM_ERR_INVALID, "max_keypoints too large for the fused ORB kernel");
-    if (P.olds > 64 * 1024)
-      HIPCHK(c, hipFuncSetAttribute((const void *)gkern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.olds));
+    if (P.olds > LDS_CAP) return fail(c, PISLAM_ERR_INVALID, "max_keypoints too large for the fused ORB kernel");
+    RAISE_LDS_LIMIT(c, gkern, P.olds);
   }
-
-  // ---- small batches: strips -> (overflowed strips redone in place) -> gather + ORB as ONE launch ----
+  const FusedCall k{p, P, pyramids, stride, batch, kp, desc, counts, kern, okern, gkern, fork, c->stream, fork ? c->aux_stream : c->stream};
   if (c->frame_disabled) c->last_path |= PISLAM_PATH_FRAME_TIMED_OUT;
-  if (P.frame && vec && !c->frame_disabled) {
-    if (P.flds > 64 * 1024)
-      HIPCHK(c, hipFuncSetAttribute((const void *)pf::k_frame, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.flds));
-    pf::FusedParams F = P.F;
-    F.batch = batch;
-    const unsigned grid = (unsigned)(batch * F.runs_per_pyr + batch * P.fch);
-    hipLaunchKernelGGL(pf::k_frame, dim3(grid), dim3(pf::NT), P.flds, c->stream, F, pyramids, stride, c->w_stage.as<uint32_t>(),
-                       c->w_stripcnt.as<uint32_t>(), kp, (size_t)p->max_keypoints, (uint32_t)p->max_keypoints, counts, desc,
-                       (size_t)p->max_keypoints * p->words, p->words, (uint32_t)P.fper, P.fch, c->w_sync.as<uint32_t>(),
-                       c->w_ovf.as<uint32_t>(), c->frame_flag_dev, (uint32_t)c->opt_frame_test);
-    PCHK(launch_ok(c, "k_frame"));
-    c->last_path = PISLAM_PATH_FUSED | PISLAM_PATH_ONE_LAUNCH;
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));   // (one launch: the stage split of last_timing is all in stage 0)
-    HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-    return PISLAM_OK;
-  }
-  const int base = batch / nsub, rem = batch % nsub;
-  hipStream_t M = c->stream, X = fork ? c->aux_stream : c->stream;
-  for (int sub = 0; sub < nsub; sub++) {
-    const int first = sub * base + std::min(sub, rem), n = base + (sub < rem ? 1 : 0);
-    pf::FusedParams F = P.F;
-    F.batch = n;
-    const uint8_t *s_pyr = pyramids + (size_t)first * stride;
-    uint32_t *s_stage = c->w_stage.as<uint32_t>() + (size_t)first * F.slots_per_pyr;
-    uint32_t *s_cnt = c->w_stripcnt.as<uint32_t>() + (size_t)first * S;
-    uint32_t *s_sdesc = c->w_stagedesc.as<uint32_t>() + (size_t)first * P.sdesc_per_pyr;
-    uint8_t *s_dump = dump ? dump + (size_t)first * dump_stride : nullptr;
-    uint32_t *s_kp = kp + (size_t)first * p->max_keypoints;
-    uint32_t *s_desc = desc + (size_t)first * p->max_keypoints * p->words;
-    uint32_t *s_counts = counts + first;
-    uint32_t *ovf = alias ? c->w_ovf.as<uint32_t>() + (size_t)sub * P.ovf_stride : nullptr;
-    const dim3 grid((unsigned)(cdiv(n, 8) * F.runs_per_pyr * 8));
-    unsigned long long *prof = nullptr;
-    const size_t prof_n = (size_t)grid.x * 8;
-    if (F.ablate & 8192) {                         // profiling hook: per-phase workgroup cycles -> stderr
-      if (c->w_prof.ensure(prof_n * sizeof(unsigned long long)) != PISLAM_OK) return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(prof)");
-      prof = c->w_prof.as<unsigned long long>();
-      HIPCHK(c, hipMemsetAsync(prof, 0, prof_n * sizeof(unsigned long long), M));
-    }
-    // (profiling option "repeat_strips": the strip kernel launched n times back to back inside the stage-0
-    //  event bracket, so that the per-launch duration is not inflated by the command-processor latency
-    //  around a single eager launch; every launch rewrites the same outputs)
-    for (int rep = 0; rep < std::max(1, c->opt_repeat_strips); rep++) {
-      if (rep && ovf) HIPCHK(c, hipMemsetAsync(ovf, 0, sizeof(uint32_t), M));   // the last launch's list counts
-      hipLaunchKernelGGL(kern, grid, dim3(pf::NT), P.klds, M, F, s_pyr, stride, s_stage, s_cnt, s_dump, dump_stride, prof, ovf,
-                         s_sdesc);
-    }
-    if (prof) {
-      std::vector<unsigned long long> hv(prof_n);
-      HIPCHK(c, hipMemcpyAsync(hv.data(), prof, prof_n * sizeof(unsigned long long), hipMemcpyDeviceToHost, M));
-      HIPCHK(c, hipStreamSynchronize(M));
-      double h[8] = {0};
-      unsigned long long why[3] = {0, 0, 0};
-      for (size_t i = 0; i < prof_n; i++) {
-        if ((i & 7) == 5) {
-          why[0] += hv[i] & 0xfffff;
-          why[1] += (hv[i] >> 20) & 0xfffff;
-          why[2] += hv[i] >> 40;
-        } else {
-          h[i & 7] += (double)hv[i];
-        }
-      }
-      fprintf(stderr, "[pislam prof] deferred strips by reason: corner queue %llu, score queue %llu, survivor buffer %llu\n",
-              why[0], why[1], why[2]);
-      const double ns = (double)S * n;
-      fprintf(stderr, "[pislam prof] cycles/strip: stage %.0f classify %.0f harris %.0f nms %.0f emit %.0f "
-                      "(strips %.0f, carried %.0f, workgroups %u, lifetime %.0f/strip)\n",
-              h[0] / ns, h[1] / ns, h[2] / ns, h[3] / ns, h[4] / ns, ns, h[6], grid.x, h[7] / ns);
-    }
-    PCHK(launch_ok(c, "k_fused_strips"));
-    if (nsub > 1) {
-      if (fork) {
-        // fork: the rest of this sub-batch runs on the aux stream, under the next sub-batch's strip kernel
-        HIPCHK(c, hipEventRecord(c->ev_sub[sub], M));
-        HIPCHK(c, hipStreamWaitEvent(X, c->ev_sub[sub], 0));
-      }
-      if (sub == nsub - 1) {
-        HIPCHK(c, hipEventRecord(c->ev[1], M));   // stage 0 = every sub-batch's strip kernel
-        HIPCHK(c, hipEventRecord(c->ev[2], M));   // (stage 1, the overflow passes, runs on the aux stream)
-      }
-    } else {
-      HIPCHK(c, hipEventRecord(c->ev[1], M));     // stage 0 = the strip kernel alone
-    }
-    if (alias) {
-      hipLaunchKernelGGL(okern, dim3((unsigned)std::max(8, c->num_cus / 2)), dim3(pf::NT), P.lds, X, F, s_pyr, stride, s_stage,
-                         s_cnt, s_dump, dump_stride, (const uint32_t *)ovf);
-      PCHK(launch_ok(c, "k_fused_overflow"));
-    }
-    if (nsub == 1) HIPCHK(c, hipEventRecord(c->ev[2], M));   // stage 1 = the overflow pass (normally empty)
-    // the plan, lists and counts the gather runs on: the strips' own, or the units of the bucket selection pass
-    pf::FusedParams G = F;
-    const uint32_t *g_stage = s_stage, *g_cnt = s_cnt;
-    if (sel) {
-      uint32_t *u_stage = c->w_ustage.as<uint32_t>() + (size_t)first * P.Q.uslots_per_pyr;
-      uint32_t *u_cnt = c->w_ucount.as<uint32_t>() + (size_t)first * P.Q.units_per_pyr;
-      hipLaunchKernelGGL(pf::k_bucket_select, dim3(cdiv(P.Q.units_per_pyr, pf::SEL_WAVES), n), dim3(64 * pf::SEL_WAVES), P.sel_lds, X, F, P.Q,
-                         (const uint32_t *)s_stage, (const uint32_t *)s_cnt, u_stage, u_cnt, c->cur_utab);
-      PCHK(launch_ok(c, "k_bucket_select"));
-      G = P.U;
-      G.batch = n;
-      g_stage = u_stage;
-      g_cnt = u_cnt;
-    }
-    if (P.generic_orb) {
-      c->last_path |= PISLAM_PATH_GENERIC_ORB;
-      hipLaunchKernelGGL(pf::k_gather, dim3(n), dim3(256), P.glds, X, G, g_stage, g_cnt, s_kp,
-                         (size_t)p->max_keypoints, (uint32_t)p->max_keypoints, s_counts, ovf);
-      PCHK(launch_ok(c, "k_gather"));
-      hipLaunchKernelGGL(pk::k_orb<0>, dim3(cdiv(p->max_keypoints, 4), 1, n), dim3(256), 0, X, s_pyr, p->vstep, stride,
-                         s_kp, (size_t)p->max_keypoints, s_counts, 0u, (uint32_t)p->max_keypoints, p->words, s_desc,
-                         (size_t)p->max_keypoints * p->words, (int32_t *)nullptr, (const uint8_t *)nullptr);
-      PCHK(launch_ok(c, "k_orb<batch>"));
-    } else {
-      hipLaunchKernelGGL(gkern, dim3(P.nch, n), dim3(256), P.olds, X, G, s_pyr, stride, g_stage, g_cnt,
-                         (const uint32_t *)s_sdesc, s_kp, (size_t)p->max_keypoints, (uint32_t)p->max_keypoints, s_counts,
-                         s_desc, (size_t)p->max_keypoints * p->words, p->words, (uint32_t)P.per_max, ovf);
-      PCHK(launch_ok(c, "k_gather_orb"));
-    }
-  }
+  if (P.frame && vec && !c->frame_disabled) return launch_frame(c, k);
+  for (int sub = 0; sub < nsub; sub++) PCHK(launch_sub_batch(c, k, sub));
   if (fork) {                                       // join: the call is complete, in stream order, on the context stream
-    HIPCHK(c, hipEventRecord(c->ev_join, X));
-    HIPCHK(c, hipStreamWaitEvent(M, c->ev_join, 0));
+    HIPCHK(c, hipEventRecord(c->ev_join, k.X));
+    HIPCHK(c, hipStreamWaitEvent(k.M, c->ev_join, 0));
   }
   return PISLAM_OK;
 }
@@ -2009,27 +2112,27 @@ int run_staged(pislam_ctx *c, const pislam_frontend_params *p, const pislam_leve
                         (uint32_t)p->max_keypoints, add_xy, counts));
   }
   HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-  hipLaunchKernelGGL(pk::k_orb<0>, dim3(cdiv(p->max_keypoints, 4), 1, batch), dim3(256), 0, c->stream,
-                     pyramids, p->vstep, stride, kp, (size_t)p->max_keypoints, counts, 0u,
-                     (uint32_t)p->max_keypoints, p->words, desc, (size_t)p->max_keypoints * p->words,
-                     (int32_t *)nullptr, (const uint8_t *)nullptr);
-  return launch_ok(c, "k_orb<batch>");
+  return launch_orb_batch(c, c->stream, p, pyramids, stride, batch, kp, counts, desc);
 }
 
 }  // namespace
 
 // Host-only: plan a batch call for these parameters with the call's own planner (plan_frontend: no device, no allocation,
-// no launch) and check the invariants of its strip plan and bucket selection plan.  For the sanitizer runs of the host code
-// (tests/test_sanitizers.py runs thousands of random level tables through it in a library built with -fsanitize=address,
-// undefined) and for tools that want to know what a call will launch.  options: "key=value,key=value" (pislam_ctx_set_option
-// keys).  summary: [0] plan entries, [1] strips per pyramid, [2] runs per pyramid, [3] staging slots per pyramid, [4] run
-// length, [5] LDS bytes (plain layout), [6] LDS bytes (aliased layout), [7] units of the selection pass (0: none).
+// no launch) and check the invariants of its strip plan and bucket selection plan (strip_plan_violation, select_plan_violation).
+// For the sanitizer runs of the host code (tests/test_sanitizers.py runs thousands of random level tables through it in a library built
+// with -fsanitize=address,undefined) and for tools that want to know what a call will launch.  options: "key=value,key=value"
+// (pislam_ctx_set_option keys).  summary: [0] plan entries, [1] strips per pyramid, [2] runs per pyramid, [3] staging slots per pyramid,
+// [4] run length, [5] LDS bytes (plain layout), [6] LDS bytes (aliased layout), [7] units of the selection pass (0: none).
 PISLAM_EXPORT int pislam_debug_build_plan(const pislam_frontend_params *p, const pislam_level *lv, int batch, int num_cus,
                                           int lanes_in_flight, const char *options, uint32_t summary[8], char *err, size_t err_cap) {
   pislam_ctx c;                                       // (never touches a device: plain members only)
   auto say = [&](int rc) {
     if (err && err_cap) snprintf(err, err_cap, "%s", c.err.c_str());
     return rc;
+  };
+  auto bad = [&](const char *what) {
+    c.err = std::string("plan invariant violated: ") + what;
+    return say(PISLAM_ERR_HIP);
   };
   c.num_cus = num_cus > 0 ? num_cus : 256;
   c.lanes_in_flight = lanes_in_flight > 0 ? lanes_in_flight : 1;
@@ -2059,66 +2162,15 @@ PISLAM_EXPORT int pislam_debug_build_plan(const pislam_frontend_params *p, const
     c.err = "no strip plan for these parameters (the staged pipeline takes the call)";
     return say(PISLAM_ERR_INVALID);
   }
-  const pf::FusedParams &F = P.F;
-  // ---- invariants the kernels rely on ----
-  auto bad = [&](const char *what) {
-    c.err = std::string("plan invariant violated: ") + what;
-    return say(PISLAM_ERR_HIP);
-  };
-  if (F.nlevels < 1 || F.nlevels > pf::MAX_LEVELS) return bad("entries");
-  int strips = 0, slots = 0, runs = 0;
-  for (int l = 0; l < F.nlevels; l++) {
-    const pf::FusedLevel &L = F.lv[l];
-    if (L.strip0 != strips || L.slot0 != slots || L.run0 != runs) return bad("prefix sums");
-    if (L.nstrips < 0 || (L.nstrips > 0 && (L.R < 2 || (L.R & 1)))) return bad("strip height");
-    if (L.nstrips > 0) {
-      if (L.col0 < 0 || L.row0 < 0 || L.col0 + L.w > p->vstep || L.row0 + L.h > p->rows) return bad("entry outside the pyramid");
-      if (L.tpitch % 16 || L.pitch % 16 || L.tpitch <= 0) return bad("pitch");
-      if ((L.R + 10) * L.tpitch > 150 * 1024) return bad("tile larger than the LDS");
-      if (L.gfirst < 0 || L.gfirst > l || L.gn < 1 || L.gfirst + L.gn > F.nlevels) return bad("tile group");
-      if (L.ex0 < p->border || L.ex1 > L.w || L.ex0 > L.ex1) return bad("owned columns");
-      if (cdiv(L.nstrips, F.run_len) != L.nruns) return bad("runs");
-      if ((uint64_t)L.vpr_recip * (uint64_t)(L.tpitch / 16) < (1ull << 32)) return bad("vpr_recip");
-      if ((uint64_t)L.tp_recip * (uint64_t)L.tpitch < (1ull << 32)) return bad("tp_recip");
-      if (L.qh < pf::QH_SHARED) return bad("corner queue");
-    }
-    strips += L.nstrips;
-    slots += L.nstrips * (L.R / 2) * L.nbx;
-    runs += L.nruns;
-  }
-  if (strips != F.strips_per_pyr || slots != F.slots_per_pyr || runs != F.runs_per_pyr) return bad("totals");
-  if (F.order_n) {
-    if (F.order_n != runs || runs > pf::MAX_ORDER) return bad("order size");
-    std::vector<int> seen((size_t)runs, 0);
-    for (int i = 0; i < F.order_n; i++) {
-      const int e = (int)(F.order[i] >> 16), r = (int)(F.order[i] & 0xffff);
-      if (e >= F.nlevels || r >= F.lv[e].nruns) return bad("order entry");
-      seen[(size_t)(F.lv[e].run0 + r)]++;
-    }
-    for (int v : seen)
-      if (v != 1) return bad("order is not a permutation of the runs");
-  }
-  if (P.lds_alias > 160 * 1024) return bad("aliased LDS size");
-  summary[0] = (uint32_t)F.nlevels;
-  summary[1] = (uint32_t)F.strips_per_pyr;
-  summary[2] = (uint32_t)F.runs_per_pyr;
-  summary[3] = (uint32_t)F.slots_per_pyr;
-  summary[4] = (uint32_t)F.run_len;
-  summary[5] = (uint32_t)P.lds;
-  summary[6] = (uint32_t)P.lds_alias;
+  if (const char *what = strip_plan_violation(P, p)) return bad(what);
+  const uint32_t strip_summary[7] = {(uint32_t)P.F.nlevels,       (uint32_t)P.F.strips_per_pyr, (uint32_t)P.F.runs_per_pyr,
+                                     (uint32_t)P.F.slots_per_pyr, (uint32_t)P.F.run_len,        (uint32_t)P.lds,
+                                     (uint32_t)P.lds_alias};
+  memcpy(summary, strip_summary, sizeof(strip_summary));
   if (plan_rc != PISLAM_OK) return say(plan_rc);   // (a refusal of the selection plan: reported after the strip plan checks)
   if (P.sel) {
-    const pf::SelectPlan &Q = P.Q;
-    int units = 0, uslots = 0;
-    for (int l = 0; l < Q.nlevels; l++) {
-      if (Q.unit0[l] != units || Q.uslot0[l] != uslots) return bad("selection plan prefix sums");
-      if (Q.g0[l] < 0 || Q.g0[l] + Q.gn[l] > F.nlevels) return bad("selection plan entries");
-      if (Q.cap[l] / p->bucket_limit > pf::SEL_NB) return bad("more buckets than the selection pass holds");
-      units += Q.nunits[l];
-      uslots += Q.nunits[l] * Q.cap[l];
-    }
-    if (units != Q.units_per_pyr || uslots != Q.uslots_per_pyr) return bad("selection plan totals");
-    summary[7] = (uint32_t)Q.units_per_pyr;
+    if (const char *what = select_plan_violation(P, p)) return bad(what);
+    summary[7] = (uint32_t)P.Q.units_per_pyr;
   }
   return PISLAM_OK;
 }
@@ -2930,8 +2982,7 @@ int db_query_args(pislam_ctx *c, const pislam_bowdb *db, int batch, int topk) {
 
 int db_query_workspace(pislam_ctx *c, const DbQueryPlan &P) {
   if (c->w_db.ensure(P.bytes) != PISLAM_OK) return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(database query workspace)");
-  if (P.lds > 64 * 1024)
-    HIPCHK(c, hipFuncSetAttribute((const void *)pd::k_db_accumulate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds));
+  RAISE_LDS_LIMIT(c, pd::k_db_accumulate, P.lds);
   return PISLAM_OK;
 }
 

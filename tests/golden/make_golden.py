@@ -9,6 +9,9 @@
   synth_small.npz    : a 3-level 160x120 synthetic pyramid + oracle outputs (regression fixture
                        for the generator and the oracle; small enough for pure-Python checks).
   brief_table_ref.npy: written by oracle/gen_brief_pattern.py (probe of the compiled Brief.h).
+  plan_summaries.json: what pislam_debug_build_plan answers for the seeded cases of tests/plan_fuzz.py and for every option
+                       at the edges of its range (`make_golden.py plans`: recorded from the library that is loaded, which
+                       must be the one whose planner is the reference for tests/test_plan_golden.py).
 """
 import hashlib
 import os
@@ -51,7 +54,32 @@ def stages(img, levels):
                 centroids=cen, angles=ang, desc=desc)
 
 
+PLAN_SEEDS = (0, 1000)
+
+
+def plan_summaries():
+    import json
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import plan_fuzz
+    from pislam_amd import capi
+    lib = capi.load(rebuild_if_stale=False)
+    seeds = range(PLAN_SEEDS[0], PLAN_SEEDS[0] + PLAN_SEEDS[1])
+    cases = [plan_fuzz.run_case(lib, s) for s in seeds]
+    # the conditions tests/test_plan_golden.py states about its inputs
+    assert 4 * sum(rc == 0 for rc, _, _ in cases) >= len(cases)
+    assert sum(s[7] > 0 for _, s, _ in cases) >= 20
+    assert sum(s[0] > len(plan_fuzz.case(sd)[0]) for sd, (_, s, _) in zip(seeds, cases)) >= 20
+    options = {k: [plan_fuzz.run_option(lib, k, v) for v in plan_fuzz.OPTION_VALUES] for k in plan_fuzz.OPTION_KEYS}
+    with open(os.path.join(HERE, "plan_summaries.json"), "w") as f:
+        json.dump(dict(seeds=list(PLAN_SEEDS), cases=cases, option_values=list(plan_fuzz.OPTION_VALUES),
+                       options=options), f, separators=(",", ":"))
+        f.write("\n")
+    print("plan_summaries.json ok:", len(cases), "cases,", len(options), "options")
+
+
 def main():
+    if sys.argv[1:] == ["plans"]:
+        return plan_summaries()
     from PIL import Image
     img = np.ascontiguousarray(np.array(Image.open("/root/reference/demo/input.png")))
     levels = synth.level_table()

@@ -59,26 +59,53 @@ def case(seed):
     return levels, par, opts, batch, cus, lanes
 
 
+def build_plan(lib, levels, par, batch, cus, lanes, options):
+    """One call of pislam_debug_build_plan: (return code, summary[0..7], error string)."""
+    P = capi.FrontendParams(*[par[k] for k in ("vstep", "rows", "nlevels", "border", "fast_threshold", "harris_threshold",
+                                               "log_bucket_size", "bucket_limit", "words", "max_keypoints")])
+    L = (capi.Level * len(levels))(*[capi.Level(*t) for t in levels])
+    summary = (ctypes.c_uint32 * 8)()
+    err = ctypes.create_string_buffer(256)
+    rc = lib.pislam_debug_build_plan(ctypes.byref(P), L, batch, cus, lanes, options.encode(), ctypes.byref(summary), err, 256)
+    return rc, list(summary), err.value.decode()
+
+
+def run_case(lib, seed):
+    levels, par, opts, batch, cus, lanes = case(seed)
+    return build_plan(lib, levels, par, batch, cus, lanes, ",".join(f"{k}={v}" for k, v in opts.items()))
+
+
+# Every key of pislam_ctx_set_option, and the values that straddle its range checks (tests/test_plan_golden.py passes each
+# pair alone in the options string, on the VGA level table of tests/test_abi.py at batch 256).
+OPTION_KEYS = ("pipeline", "own_stream", "dump_score", "repeat_strips", "alias", "run_len", "lds_pad", "wgs_per_cu", "match_mfma",
+               "run_order", "strip_px", "strip_rows_max", "tile_cols", "frame", "frame_test", "frame_rearm", "build_chain",
+               "orb_in_strip", "bucket_select", "dist_rccl_single", "bucket_round_up", "orb_chunks", "sub_batches", "sub_mb",
+               "ablate", "strip_rows", "no_such_option")
+OPTION_VALUES = (-1, 0, 1, 5, 64, 65, 100000)
+
+
+def run_option(lib, key, value):
+    from pislam_amd import synth
+    levels = [(w, h, r0, 0) for w, h, r0 in synth.level_table()]
+    par = dict(vstep=640, rows=2210, nlevels=8, border=16, fast_threshold=20, harris_threshold=1 << 15, log_bucket_size=4,
+               bucket_limit=3, words=8, max_keypoints=4096)
+    return build_plan(lib, levels, par, 256, 256, 1, f"{key}={value}")
+
+
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
     first = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     lib = capi.load(rebuild_if_stale=False)
     ok = refused = 0
     for seed in range(first, first + n):
-        levels, par, opts, batch, cus, lanes = case(seed)
-        P = capi.FrontendParams(*[par[k] for k in ("vstep", "rows", "nlevels", "border", "fast_threshold", "harris_threshold",
-                                                   "log_bucket_size", "bucket_limit", "words", "max_keypoints")])
-        L = (capi.Level * len(levels))(*[capi.Level(*t) for t in levels])
-        summary = (ctypes.c_uint32 * 8)()
-        err = ctypes.create_string_buffer(256)
-        o = ",".join(f"{k}={v}" for k, v in opts.items()).encode()
-        rc = lib.pislam_debug_build_plan(ctypes.byref(P), L, batch, cus, lanes, o, ctypes.byref(summary), err, 256)
+        rc, _, err = run_case(lib, seed)
         if rc == 0:
             ok += 1
         elif rc == -1:                                # PISLAM_ERR_INVALID: refused parameters, or the staged pipeline takes the call
             refused += 1
         else:
-            print(f"seed {seed}: rc {rc}: {err.value.decode()}\n  levels {levels}\n  params {par}\n  options {opts} batch {batch} "
+            levels, par, opts, batch, cus, lanes = case(seed)
+            print(f"seed {seed}: rc {rc}: {err}\n  levels {levels}\n  params {par}\n  options {opts} batch {batch} "
                   f"cus {cus} lanes {lanes}")
             return 1
     print(f"{ok} plans, {refused} refused, 0 violations ({n} cases from seed {first}; library {capi.library_path()})")

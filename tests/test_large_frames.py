@@ -42,7 +42,7 @@ def rows_of(levels):
 
 
 def x_tiles(w, border=16):
-    """Plan entries of one level (build_fused_plan_rows): more than 704 classified columns are cut into tiles of about
+    """Plan entries of one level (plan_entries): more than 704 classified columns are cut into tiles of about
     448 owned columns, T a multiple of 32."""
     nx = w - 2 * border
     if 16 * -(-nx // 16) <= 704:
