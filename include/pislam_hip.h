@@ -78,6 +78,7 @@ int pislam_ctx_set_stream(pislam_ctx *ctx, void *hip_stream);
  *                batches of up to n, 0 never (always strip kernel -> overflow pass -> gather + ORB); not with buckets
  *   "wgs_per_cu", "strip_px", "strip_rows_max", "lds_pad", "bucket_round_up", "repeat_strips", "ablate"  profiling only (ablate != 0 gives INVALID results by design)
  *   "match_mfma" 1 (default) pislam_match_hamming* run on the int8 matrix cores, 0 the VALU popcount kernel (same results)
+ *   "warp_direct" 1 every tile of pislam_warp_batch takes its taps from global memory, 0 (default) tiles whose source box fits are staged in LDS
  *   "dist_rccl_single" test hook: pislam_dist_init(world = 1) still creates a 1-rank RCCL communicator */
 int pislam_ctx_set_option(pislam_ctx *ctx, const char *key, int value);
 int pislam_ctx_synchronize(pislam_ctx *ctx);
@@ -173,6 +174,62 @@ int pislam_bilinear7_8(pislam_ctx *ctx, int vstep, int width, int height, const 
                        uint8_t *out);
 int pislam_bilinear13_16(pislam_ctx *ctx, int vstep, int width, int height, const uint8_t *img,
                          uint8_t *out);
+
+/* Lens undistortion and stereo rectification as a fixed-point mesh warp: the step in front
+ * of pislam_pyramid_build_batch.  The matchers, pislam_match_stereo_batch in particular, assume undistorted
+ * (rectified) pinhole images.  The reference ships nothing of the kind: the semantics are this library's own.
+ *
+ * An immutable warp object holds a coarse grid of source coordinates the caller computes from a calibration;
+ * pislam_warp_batch resamples `batch` device-resident 8-bit frames through it, bilinearly, into `batch` output
+ * frames.
+ *
+ * Mesh layout.  C = 1 << log_cell, 0 <= log_cell <= 6.  mesh_w = ((width - 1) >> log_cell) + 2, mesh_h likewise
+ * (pislam_warp_mesh_dims; no context needed).  mesh_x and mesh_y are HOST int32 [mesh_h][mesh_w]; node (j, i) is the
+ * source position of output pixel (i * C, j * C) in Q8: 256 is one source pixel, pixel centres lie at integers.
+ * With log_cell == 0 the mesh is dense; its last node column and row carry weight 0, must still be supplied and
+ * are ignored.
+ *
+ * Source coordinate of output pixel (x, y).  i = x >> log_cell, fx = x & (C - 1), j = y >> log_cell,
+ * fy = y & (C - 1).  Per axis, with m the mesh:
+ *   a    = (m[j][i]   * (C - fx) + m[j][i+1]   * fx + (C >> 1)) >> log_cell
+ *   b    = (m[j+1][i] * (C - fx) + m[j+1][i+1] * fx + (C >> 1)) >> log_cell
+ *   s_q8 = (a * (C - fy) + b * fy + (C >> 1)) >> log_cell
+ * in signed 32-bit arithmetic; every >> is an arithmetic shift (floor).  Nothing overflows within the node range
+ * below.
+ *
+ * Sampling.  s5 = (s_q8 + 4) >> 3, x0 = s5x >> 5, ax = s5x & 31, likewise y0 and ay (a position of -0.5 px is
+ * x0 = -1, ax = 16).  S(u, v) = the source byte at src + b * src_stride + v * src_vstep + u when 0 <= u < src_width
+ * and 0 <= v < src_height, otherwise `border`.
+ *   out = ((32-ax)*(32-ay)*S(x0,y0) + ax*(32-ay)*S(x0+1,y0) + (32-ax)*ay*S(x0,y0+1) + ax*ay*S(x0+1,y0+1) + 512) >> 10
+ * written to dst + b * dst_stride + y * dst_vstep + x.  Only the width x height bytes of each output frame are
+ * written.  No source byte outside the src_width x src_height rectangle of a frame is read, row padding included.
+ *
+ * Limits: 1 <= width, height <= 4096 (outputs stay inside the 12-bit keypoint coordinates);
+ * 1 <= src_width, src_height <= 16384; every node in [-2^23, 2^23); 0 <= border <= 255; src_vstep >= src_width and
+ * dst_vstep >= width; batch >= 0 (batch == 0 is a no-op that returns PISLAM_OK); src and dst are device pointers
+ * whose byte ranges do not overlap; the warp belongs to the context's device.  Anything else: PISLAM_ERR_INVALID,
+ * before anything is launched or written.  Offsets use size_t arithmetic throughout: strides may push a batch past
+ * 4 GiB.
+ *
+ * Lifetime and streams.  pislam_warp_create validates, plans, uploads on the context's device and stream and
+ * synchronises, as pislam_vocab_create does; the host arrays are not referenced afterwards.  A warp is immutable and
+ * may be used by any context of its device; destroy it after the work that uses it has completed.
+ * pislam_warp_batch is asynchronous on the context stream, has no workspace and no host round trip, and can be
+ * captured into a hipGraph as it is.
+ *
+ * The output is cut into tiles of 64 x 32 pixels, one workgroup each.  A tile whose source bounding box (from the
+ * minimum and maximum of its nodes) fits the workgroup's LDS is staged there; any other tile takes its taps from
+ * global memory (direct).  Option "warp_direct" 1 sends every tile down the direct path (0, the default: by the
+ * plan; other values are refused); the results are the same.  pislam_warp_info: info[0] tiles, [1] tiles staged,
+ * [2] tiles direct (as planned, whatever the option says), [3] LDS bytes per workgroup. */
+typedef struct pislam_warp pislam_warp;
+int pislam_warp_create(pislam_ctx *ctx, int width, int height, int src_width, int src_height, int log_cell,
+                       const int32_t *mesh_x, const int32_t *mesh_y, int border, pislam_warp **warp);
+int pislam_warp_destroy(pislam_warp *warp);
+int pislam_warp_mesh_dims(int width, int height, int log_cell, int32_t *mesh_w, int32_t *mesh_h);
+int pislam_warp_info(const pislam_warp *warp, int32_t info[4]);
+int pislam_warp_batch(pislam_ctx *ctx, const pislam_warp *warp, const uint8_t *src, int src_vstep, size_t src_stride,
+                      uint8_t *dst, int dst_vstep, size_t dst_stride, int batch);
 
 /* ---- the measured path: a batch of stacked pyramids, device resident --- */
 

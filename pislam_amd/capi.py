@@ -62,6 +62,11 @@ SYMBOLS = {
     "pislam_gaussian5x5": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "pislam_bilinear7_8": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "pislam_bilinear13_16": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "pislam_warp_create": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, ctypes.POINTER(_vp)]),
+    "pislam_warp_destroy": (_i, [_vp]),
+    "pislam_warp_mesh_dims": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "pislam_warp_info": (_i, [_vp, ctypes.POINTER(ctypes.c_int32 * 4)]),
+    "pislam_warp_batch": (_i, [_vp, _vp, _vp, _i, _sz, _vp, _i, _sz, _i]),
     "pislam_pyramid_layout": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_int32), _i, ctypes.POINTER(Level),
                                    ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "pislam_pyramid_build_batch": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(Level), _vp, _i, _sz,

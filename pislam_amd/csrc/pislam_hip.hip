@@ -57,6 +57,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_bow_kernels.h"
 #include "pislam_bowdb_kernels.h"
 #include "pislam_select_kernels.h"
+#include "pislam_warp_kernels.h"
 
 #define PISLAM_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -165,6 +166,7 @@ struct pislam_ctx {
   int opt_frame = 1;         // fused pipeline: small batches run as ONE launch (pf::k_frame): 1 = batches of 1 or 2 pyramids, n = up to n (<= 8), 0 = never
   int opt_orb_in_strip = 0;  // fused pipeline: 1 = strips describe their own keypoints (measured slower: DESIGN.md §8), 0 = k_gather_orb describes all
   int opt_match_mfma = 1;         // matcher on the matrix cores (0: the VALU popcount kernel)
+  int opt_warp_direct = 0;        // mesh warp: 1 = every tile takes the direct path (taps from global memory), 0 = by the tile plan
   int opt_dist_rccl_single = 0;   // test hook: pislam_dist_init(world = 1) still creates a (1-rank) RCCL communicator
   int last_pipeline = 0;
   unsigned last_path = 0;    // PISLAM_PATH_* of the last batch call
@@ -596,6 +598,7 @@ const OptionDef OPTIONS[] = {
     {"lds_pad", &pislam_ctx::opt_lds_pad, 0, 0, nullptr, at_least_0},
     {"wgs_per_cu", &pislam_ctx::opt_wgs_per_cu, 0, 8, "wgs_per_cu must be 0..8", nullptr},
     {"match_mfma", &pislam_ctx::opt_match_mfma, 0, 0, nullptr, as_flag},
+    {"warp_direct", &pislam_ctx::opt_warp_direct, 0, 1, "warp_direct must be 0 or 1", nullptr},
     {"run_order", &pislam_ctx::opt_run_order, 0, 0, nullptr, as_flag},
     {"strip_px", &pislam_ctx::opt_strip_px, 0, 0, nullptr, [](int v) { return std::max(4096, v); }},
     {"strip_rows_max", &pislam_ctx::opt_strip_rows_max, 0, 0, nullptr, [](int v) { return v <= 0 ? 0 : std::max(16, std::min(64, v & ~1)); }},
@@ -2850,6 +2853,95 @@ PISLAM_EXPORT int pislam_match_hamming_bow_batch(pislam_ctx *c, int words, int n
                        qgroup, qcounts, q_stride, t_stride, off, eidx, edesc, idx, dist, dist2);
   });
   return launch_ok(c, "k_match_bow");
+}
+
+// ---- image preparation: lens undistortion and stereo rectification as a mesh warp ----------
+
+struct pislam_warp {
+  int device = 0;
+  int width = 0, height = 0, src_width = 0, src_height = 0, log_cell = 0, border = 0;
+  int32_t mesh_w = 0, mesh_h = 0;
+  int tiles_x = 0, ntiles = 0, staged = 0, direct = 0;
+  DevBuf mesh, tiles;   // pw::k_warp's tables: mesh_x then mesh_y int32 [mesh_h][mesh_w], pw::Tile [ntiles]
+};
+
+PISLAM_EXPORT int pislam_warp_mesh_dims(int width, int height, int log_cell, int32_t *mesh_w, int32_t *mesh_h) {
+  return pw::mesh_dims(width, height, log_cell, mesh_w, mesh_h) ? PISLAM_OK : PISLAM_ERR_INVALID;
+}
+
+PISLAM_EXPORT int pislam_warp_create(pislam_ctx *c, int width, int height, int src_width, int src_height, int log_cell,
+                                     const int32_t *mesh_x, const int32_t *mesh_y, int border, pislam_warp **warp) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!warp) return fail(c, PISLAM_ERR_INVALID, "null warp pointer");
+  *warp = nullptr;
+  if (const char *bad = pw::check_create(width, height, src_width, src_height, log_cell, mesh_x, mesh_y, border))
+    return fail(c, PISLAM_ERR_INVALID, bad);
+  const pw::Plan plan = pw::make_plan(width, height, src_width, src_height, log_cell, mesh_x, mesh_y);
+  HIPCHK(c, hipSetDevice(c->device));
+  pislam_warp *w = new pislam_warp();
+  w->device = c->device;
+  w->width = width, w->height = height, w->src_width = src_width, w->src_height = src_height;
+  w->log_cell = log_cell, w->border = border;
+  pw::mesh_dims(width, height, log_cell, &w->mesh_w, &w->mesh_h);
+  w->tiles_x = plan.tiles_x, w->ntiles = (int)plan.tiles.size(), w->staged = plan.staged, w->direct = plan.direct;
+  const size_t nbytes = sizeof(int32_t) * (size_t)w->mesh_w * w->mesh_h, tbytes = sizeof(pw::Tile) * plan.tiles.size();
+  if (w->mesh.ensure(2 * nbytes) != PISLAM_OK || w->tiles.ensure(tbytes) != PISLAM_OK) {
+    w->mesh.release(), w->tiles.release();
+    delete w;
+    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(warp)");
+  }
+  hipError_t e = hipMemcpyAsync(w->mesh.p, mesh_x, nbytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(w->mesh.as<uint8_t>() + nbytes, mesh_y, nbytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(w->tiles.p, plan.tiles.data(), tbytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (the host arrays and the plan may go away after the call)
+  if (e != hipSuccess) {
+    w->mesh.release(), w->tiles.release();
+    delete w;
+    return fail(c, PISLAM_ERR_HIP, "warp upload", e);
+  }
+  *warp = w;
+  return PISLAM_OK;
+}
+
+PISLAM_EXPORT int pislam_warp_destroy(pislam_warp *w) {
+  if (!w) return PISLAM_ERR_INVALID;
+  (void)hipSetDevice(w->device);
+  w->mesh.release(), w->tiles.release();
+  delete w;
+  return PISLAM_OK;
+}
+
+PISLAM_EXPORT int pislam_warp_info(const pislam_warp *w, int32_t info[4]) {
+  if (!w || !info) return PISLAM_ERR_INVALID;
+  info[0] = w->ntiles, info[1] = w->staged, info[2] = w->direct, info[3] = pw::LDS_BYTES;
+  return PISLAM_OK;
+}
+
+PISLAM_EXPORT int pislam_warp_batch(pislam_ctx *c, const pislam_warp *w, const uint8_t *src, int src_vstep,
+                                    size_t src_stride, uint8_t *dst, int dst_vstep, size_t dst_stride, int batch) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!w) return fail(c, PISLAM_ERR_INVALID, "null warp");
+  if (w->device != c->device) return fail(c, PISLAM_ERR_INVALID, "the warp lives on another device");
+  if (const char *bad = pw::check_batch(w->width, w->height, w->src_width, w->src_height, src, src_vstep, src_stride, dst,
+                                        dst_vstep, dst_stride, batch))
+    return fail(c, PISLAM_ERR_INVALID, bad);
+  if (batch == 0) return PISLAM_OK;
+  PCHK(device_ptrs(c, {src, dst}, "the mesh warp takes device pointers only"));
+  HIPCHK(c, hipSetDevice(c->device));
+  pw::WarpArgs a{};
+  a.tiles = w->tiles.as<pw::Tile>();
+  a.mesh_x = w->mesh.as<int32_t>(), a.mesh_y = a.mesh_x + (size_t)w->mesh_w * w->mesh_h;
+  a.mesh_w = w->mesh_w, a.log_cell = w->log_cell, a.width = w->width, a.height = w->height;
+  a.src_width = w->src_width, a.src_height = w->src_height, a.border = w->border, a.tiles_x = w->tiles_x;
+  a.direct = c->opt_warp_direct;
+  a.src_vstep = src_vstep, a.src_stride = src_stride, a.dst_vstep = dst_vstep, a.dst_stride = dst_stride;
+  for (int b0 = 0; b0 < batch; b0 += 65535) {                // (grid.y)
+    const int nb = std::min(batch - b0, 65535);
+    a.src = src + (size_t)b0 * src_stride, a.dst = dst + (size_t)b0 * dst_stride;
+    hipLaunchKernelGGL(pw::k_warp, dim3((unsigned)w->ntiles, (unsigned)nb), dim3(pw::THREADS), 0, c->stream, a);
+    PCHK(launch_ok(c, "k_warp"));
+  }
+  return PISLAM_OK;
 }
 
 // ---- after the match: batched angle bins and match selection ------------------------------

@@ -746,6 +746,88 @@ def bilinear13_16(width, height, img, out, *, ctx: Context | None = None):
               "pislam_bilinear13_16")
 
 
+# ---- lens undistortion / stereo rectification: the mesh warp in front of the pyramid build ---------
+def warpMeshDims(width: int, height: int, log_cell: int):
+    """(mesh_w, mesh_h) of a warp mesh (pislam_warp_mesh_dims): ((width - 1) >> log_cell) + 2, likewise the height."""
+    mw, mh = ctypes.c_int32(0), ctypes.c_int32(0)
+    rc = capi.load().pislam_warp_mesh_dims(int(width), int(height), int(log_cell), ctypes.byref(mw), ctypes.byref(mh))
+    if rc != 0:
+        raise capi.PislamError(f"pislam_warp_mesh_dims failed ({rc}): need 1 <= width, height <= 4096, 0 <= log_cell <= 6")
+    return mw.value, mh.value
+
+
+class Warp:
+    """pislam_warp: an immutable mesh of Q8 source coordinates (mesh_x, mesh_y int32 [mesh_h][mesh_w], host; node
+    (j, i) = where output pixel (i << log_cell, j << log_cell) comes from, 256 = one source pixel) through which
+    batches of device-resident frames uint8 [batch][src_height][src_width] are resampled bilinearly into frames
+    [batch][height][width] (include/pislam_hip.h).  Source pixels outside the frame read as `border`.  Shapes are
+    checked here, values by the library."""
+
+    def __init__(self, mesh_x, mesh_y, width: int, height: int, src_width: int, src_height: int, log_cell: int,
+                 border: int = 0, ctx: Context | None = None):
+        self.h = None
+        self.ctx = ctx or default_context()
+        mesh_x = np.ascontiguousarray(mesh_x, np.int32)
+        mesh_y = np.ascontiguousarray(mesh_y, np.int32)
+        mw, mh = warpMeshDims(width, height, log_cell)
+        if mesh_x.shape != (mh, mw) or mesh_y.shape != (mh, mw):
+            raise ValueError(f"mesh_x and mesh_y must be [{mh}][{mw}] for a {width} x {height} output at log_cell {log_cell}")
+        self.width, self.height, self.src_width, self.src_height = int(width), int(height), int(src_width), int(src_height)
+        self.log_cell, self.border = int(log_cell), int(border)
+        h = ctypes.c_void_p()
+        self.ctx.check(self.ctx.lib.pislam_warp_create(self.ctx.h, self.width, self.height, self.src_width, self.src_height,
+                                                       self.log_cell, ptr(mesh_x), ptr(mesh_y), self.border,
+                                                       ctypes.byref(h)), "pislam_warp_create")
+        self.h = h
+
+    @classmethod
+    def from_calibration(cls, K, dist, size, *, R=None, P=None, src_size=None, log_cell: int = 3, border: int = 0,
+                         ctx: Context | None = None):
+        """The warp that undistorts (and, with R and P, rectifies) a camera: rectify.rectify_mesh after OpenCV's
+        initUndistortRectifyMap.  size = (width, height) of the output, src_size of the camera frames (default: size).
+        log_cell 3 keeps the interpolated coordinate within 0.03 px of the model for a EuRoC-like lens."""
+        from . import rectify
+        mx, my = rectify.rectify_mesh(K, dist, R, P, size, log_cell)
+        sw, sh = src_size if src_size is not None else size
+        return cls(mx, my, size[0], size[1], sw, sh, log_cell, border, ctx)
+
+    def info(self) -> dict:
+        v = (ctypes.c_int32 * 4)()
+        self.ctx.check(self.ctx.lib.pislam_warp_info(self.h, ctypes.byref(v)), "pislam_warp_info")
+        return {"tiles": int(v[0]), "staged": int(v[1]), "direct": int(v[2]), "lds_bytes": int(v[3])}
+
+    def __call__(self, frames, out=None, *, ctx: Context | None = None):
+        """frames: uint8 device tensor [batch][src_height][>= src_width] (a view with padded rows or frames is fine as
+        long as bytes of a row are adjacent); out: likewise [batch][height][>= width], allocated when None.
+        Asynchronous on the stream of `ctx` (default: the warp's context); returns out."""
+        import torch
+        c = ctx or self.ctx
+        if frames.dtype != torch.uint8 or frames.dim() != 3 or frames.shape[1] != self.src_height \
+                or frames.shape[2] < self.src_width or (frames.shape[2] > 1 and frames.stride(2) != 1):
+            raise ValueError(f"frames must be uint8 [batch][{self.src_height}][>= {self.src_width}] with adjacent row bytes")
+        batch = int(frames.shape[0])
+        if out is None:
+            out = torch.empty((batch, self.height, self.width), dtype=torch.uint8, device=frames.device)
+        if out.dtype != torch.uint8 or out.dim() != 3 or out.shape[0] != batch or out.shape[1] != self.height \
+                or out.shape[2] < self.width or (out.shape[2] > 1 and out.stride(2) != 1):
+            raise ValueError(f"out must be uint8 [{batch}][{self.height}][>= {self.width}] with adjacent row bytes")
+        c.check(c.lib.pislam_warp_batch(c.h, self.h, frames.data_ptr(), int(frames.stride(1)), int(frames.stride(0)),
+                                        out.data_ptr(), int(out.stride(1)), int(out.stride(0)), batch),
+                "pislam_warp_batch")
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.pislam_warp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ---- on-GPU pyramid build (BASELINE config 5) ------------------------------------------
 DEFAULT_CHAIN = (2, 1, 2, 2, 1, 2, 2)     # 13/16, 7/8, 13/16, ... : (13/16)^2 * 7/8 = 0.578 ~ 1.2^-3 (SURVEY 8f-1)
 
