@@ -79,6 +79,8 @@ int pislam_ctx_set_stream(pislam_ctx *ctx, void *hip_stream);
  *   "wgs_per_cu", "strip_px", "strip_rows_max", "lds_pad", "bucket_round_up", "repeat_strips", "ablate"  profiling only (ablate != 0 gives INVALID results by design)
  *   "match_mfma" 1 (default) pislam_match_hamming* run on the int8 matrix cores, 0 the VALU popcount kernel (same results)
  *   "warp_direct" 1 every tile of pislam_warp_batch takes its taps from global memory, 0 (default) tiles whose source box fits are staged in LDS
+ *   "clahe_combine" 1 (default) pislam_clahe_luts_batch adds equal bytes of a lane's dword to the LDS histogram in one atomic, 0 one atomic per pixel (same results)
+ *   "clahe_lut_global" 1 pislam_clahe_apply_batch reads its four tables from global memory per pixel, 0 (default) stages them in LDS (same results)
  *   "dist_rccl_single" test hook: pislam_dist_init(world = 1) still creates a 1-rank RCCL communicator */
 int pislam_ctx_set_option(pislam_ctx *ctx, const char *key, int value);
 int pislam_ctx_synchronize(pislam_ctx *ctx);
@@ -230,6 +232,73 @@ int pislam_warp_mesh_dims(int width, int height, int log_cell, int32_t *mesh_w, 
 int pislam_warp_info(const pislam_warp *warp, int32_t info[4]);
 int pislam_warp_batch(pislam_ctx *ctx, const pislam_warp *warp, const uint8_t *src, int src_vstep, size_t src_stride,
                       uint8_t *dst, int dst_vstep, size_t dst_stride, int batch);
+
+/* Contrast-limited adaptive histogram equalisation (CLAHE): the step between
+ * pislam_warp_batch and pislam_pyramid_build_batch for dim, hazy or unevenly lit frames (fast_threshold and
+ * harris_threshold are absolute grey-level numbers).  The reference ships nothing of the kind: the semantics are this
+ * library's own, after OpenCV's CLAHE but stated in integers from end to end.  This comment is the contract.
+ *
+ * Buffers.  Frame b is at src + b * src_stride, uint8 [height][src_vstep]; dst is laid out likewise.  luts is a device
+ * buffer the caller supplies, uint8 [batch][tiles_y][tiles_x][256], pislam_clahe_lut_size(p) bytes per frame.
+ * pislam_clahe_luts_batch computes the tables, pislam_clahe_apply_batch blends given tables into dst, and
+ * pislam_clahe_batch is the first followed by the second on the context stream: its luts is both the scratch space
+ * and an output the caller may inspect.  The caller owns luts, so there is no context workspace and no reserve call:
+ * every call is asynchronous on the context stream, has no host round trip and can be captured into a hipGraph as
+ * it is.
+ *
+ * With W = width, H = height, tw = ceil(W / tiles_x), th = ceil(H / tiles_y), area = tw * th:
+ *
+ * Extended frame.  E(x, y) = src[r(y, H)][r(x, W)] for 0 <= x < tw * tiles_x, 0 <= y < th * tiles_y, with r(i, n) = i
+ * if i < n and 2 * (n - 1) - i otherwise (reflect-101; tiles_x <= W and tiles_y <= H keep r >= 0).  No byte outside
+ * the W x H rectangle of a frame is read, row padding included.
+ *
+ * Histogram of tile (tx, ty).  h[v] = the number of pixels of E with value v in [tx * tw, (tx + 1) * tw) x
+ * [ty * th, (ty + 1) * th); it sums to area.
+ *
+ * Clip (only if clip_q8 > 0).  clip = max((clip_q8 * area) >> 16, 1), computed in 64 bits.
+ * excess = sum over v of max(h[v] - clip, 0); then h[v] = min(h[v], clip).  q = excess / 256, res = excess % 256.
+ * Every bin gets + q.  If res > 0: step = 256 / res (floor; at least 1), and bin v gets + 1 iff v % step == 0 and
+ * v / step < res.  (OpenCV's residual loop in closed form.  Bins may exceed clip afterwards, as in OpenCV.)
+ *
+ * Table.  lut[v] = min(255, (255 * cdf[v] + (area >> 1)) / area), cdf the inclusive prefix sum of h, floor division.
+ *
+ * Blend, for output pixel (x, y) with v = src[y][x] and L[ty][tx] the table of tile (tx, ty):
+ *   fx = 2 * x - tw, tx1 = floor(fx / (2 * tw)) (-1 for fx < 0), wx2 = fx - 2 * tw * tx1 (0 <= wx2 < 2 * tw),
+ *   wx1 = 2 * tw - wx2, tx2 = tx1 + 1; then tx1 = max(tx1, 0), tx2 = min(tx2, tiles_x - 1): the clamp does not change
+ *   the weights.  Likewise fy, ty1, ty2, wy1, wy2 with th.
+ *   S = wy1 * (wx1 * L[ty1][tx1][v] + wx2 * L[ty1][tx2][v]) + wy2 * (wx1 * L[ty2][tx1][v] + wx2 * L[ty2][tx2][v])
+ *   D = 4 * tw * th, out = (S + (D >> 1)) / D, floor division.
+ * Only the W x H bytes of each output frame are written.  pislam_clahe_apply_batch takes any table bytes, monotone
+ * or not.
+ *
+ * Differences from OpenCV (by construction; OpenCV was not run against this): OpenCV rounds the table and the blend
+ * in float (cvRound), this statement rounds half up in exact integers; OpenCV pads both axes whenever either does
+ * not divide evenly, this statement pads each axis on its own.  The tile grid, the clip formula, the single-pass
+ * redistribution and the x / tw - 0.5 tile coordinate follow OpenCV (ORB-SLAM3's createCLAHE(3.0, Size(8, 8)) is
+ * tiles 8 x 8, clip_q8 768).
+ *
+ * Limits: 1 <= width, height <= 4096; 1 <= tiles_x <= min(32, width), 1 <= tiles_y <= min(32, height);
+ * area <= 2^20 (so S + D / 2 < 2^32 and 255 * cdf < 2^28; a 4096 x 4096 frame needs at least 4 x 4 tiles);
+ * 0 <= clip_q8 <= 65535; src_vstep >= width, dst_vstep >= width; batch >= 0 with no upper limit (batch == 0 is a
+ * no-op that returns PISLAM_OK after the checks of p, batch and the steps; the data pointers are not looked at then
+ * and may be NULL).  Offsets use size_t arithmetic throughout: strides may carry a batch past 4 GiB.  dst may be
+ * exactly src (same pointer, same vstep, same stride: in place); any other overlap of the byte ranges of src, dst and
+ * luts is refused.  src, dst and luts are device pointers; p is a host struct read during the call.  Any violation:
+ * PISLAM_ERR_INVALID, before anything is launched or written.  pislam_clahe_lut_size needs no context and returns
+ * 0 for an invalid p. */
+typedef struct pislam_clahe_params {
+  int32_t width, height;     /* frame size in pixels */
+  int32_t tiles_x, tiles_y;  /* tile grid (OpenCV's tileGridSize; ORB-SLAM3: 8, 8) */
+  int32_t clip_q8;           /* clip limit in Q8 (OpenCV's clipLimit * 256; ORB-SLAM3: 768); 0 = no clipping */
+} pislam_clahe_params;
+size_t pislam_clahe_lut_size(const pislam_clahe_params *p);
+int pislam_clahe_luts_batch(pislam_ctx *ctx, const pislam_clahe_params *p, const uint8_t *src, int src_vstep,
+                            size_t src_stride, int batch, uint8_t *luts);
+int pislam_clahe_apply_batch(pislam_ctx *ctx, const pislam_clahe_params *p, const uint8_t *src, int src_vstep,
+                             size_t src_stride, const uint8_t *luts, uint8_t *dst, int dst_vstep, size_t dst_stride,
+                             int batch);
+int pislam_clahe_batch(pislam_ctx *ctx, const pislam_clahe_params *p, const uint8_t *src, int src_vstep,
+                       size_t src_stride, uint8_t *dst, int dst_vstep, size_t dst_stride, int batch, uint8_t *luts);
 
 /* ---- the measured path: a batch of stacked pyramids, device resident --- */
 

@@ -40,6 +40,10 @@ class SelectParams(ctypes.Structure):
         "max_dist", "ratio_num", "ratio_den", "unique", "rot_keep", "rot_min_pct")]
 
 
+class ClaheParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "tiles_x", "tiles_y", "clip_q8")]
+
+
 # name -> (restype, argtypes); every symbol declared in include/pislam_hip.h
 SYMBOLS = {
     "pislam_abi_version": (_i, []),
@@ -67,6 +71,10 @@ SYMBOLS = {
     "pislam_warp_mesh_dims": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "pislam_warp_info": (_i, [_vp, ctypes.POINTER(ctypes.c_int32 * 4)]),
     "pislam_warp_batch": (_i, [_vp, _vp, _vp, _i, _sz, _vp, _i, _sz, _i]),
+    "pislam_clahe_lut_size": (_sz, [ctypes.POINTER(ClaheParams)]),
+    "pislam_clahe_luts_batch": (_i, [_vp, ctypes.POINTER(ClaheParams), _vp, _i, _sz, _i, _vp]),
+    "pislam_clahe_apply_batch": (_i, [_vp, ctypes.POINTER(ClaheParams), _vp, _i, _sz, _vp, _vp, _i, _sz, _i]),
+    "pislam_clahe_batch": (_i, [_vp, ctypes.POINTER(ClaheParams), _vp, _i, _sz, _vp, _i, _sz, _i, _vp]),
     "pislam_pyramid_layout": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_int32), _i, ctypes.POINTER(Level),
                                    ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "pislam_pyramid_build_batch": (_i, [_vp, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(Level), _vp, _i, _sz,

@@ -58,6 +58,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_bowdb_kernels.h"
 #include "pislam_select_kernels.h"
 #include "pislam_warp_kernels.h"
+#include "pislam_clahe_kernels.h"
 
 #define PISLAM_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -167,6 +168,8 @@ struct pislam_ctx {
   int opt_orb_in_strip = 0;  // fused pipeline: 1 = strips describe their own keypoints (measured slower: DESIGN.md §8), 0 = k_gather_orb describes all
   int opt_match_mfma = 1;         // matcher on the matrix cores (0: the VALU popcount kernel)
   int opt_warp_direct = 0;        // mesh warp: 1 = every tile takes the direct path (taps from global memory), 0 = by the tile plan
+  int opt_clahe_combine = 1;      // CLAHE table kernel: 1 = equal bytes of a lane's dword share one LDS atomic, 0 = one atomic per pixel
+  int opt_clahe_lut_global = 0;   // CLAHE apply kernel: 1 = the four tables are read from global memory per pixel, 0 = staged in LDS
   int opt_dist_rccl_single = 0;   // test hook: pislam_dist_init(world = 1) still creates a (1-rank) RCCL communicator
   int last_pipeline = 0;
   unsigned last_path = 0;    // PISLAM_PATH_* of the last batch call
@@ -599,6 +602,8 @@ const OptionDef OPTIONS[] = {
     {"wgs_per_cu", &pislam_ctx::opt_wgs_per_cu, 0, 8, "wgs_per_cu must be 0..8", nullptr},
     {"match_mfma", &pislam_ctx::opt_match_mfma, 0, 0, nullptr, as_flag},
     {"warp_direct", &pislam_ctx::opt_warp_direct, 0, 1, "warp_direct must be 0 or 1", nullptr},
+    {"clahe_combine", &pislam_ctx::opt_clahe_combine, 0, 1, "clahe_combine must be 0 or 1", nullptr},
+    {"clahe_lut_global", &pislam_ctx::opt_clahe_lut_global, 0, 1, "clahe_lut_global must be 0 or 1", nullptr},
     {"run_order", &pislam_ctx::opt_run_order, 0, 0, nullptr, as_flag},
     {"strip_px", &pislam_ctx::opt_strip_px, 0, 0, nullptr, [](int v) { return std::max(4096, v); }},
     {"strip_rows_max", &pislam_ctx::opt_strip_rows_max, 0, 0, nullptr, [](int v) { return v <= 0 ? 0 : std::max(16, std::min(64, v & ~1)); }},
@@ -2942,6 +2947,89 @@ PISLAM_EXPORT int pislam_warp_batch(pislam_ctx *c, const pislam_warp *w, const u
     PCHK(launch_ok(c, "k_warp"));
   }
   return PISLAM_OK;
+}
+
+// ---- image preparation: contrast-limited adaptive histogram equalisation -------------------
+
+namespace {
+
+const char *clahe_check_params(const pislam_clahe_params *p) {
+  if (!p) return "null params";
+  return pc::check_params(p->width, p->height, p->tiles_x, p->tiles_y, p->clip_q8);
+}
+
+// The checked arguments of one of the three calls, as kernel arguments for the whole batch.
+int clahe_args(pislam_ctx *c, const pislam_clahe_params *p, const uint8_t *src, int src_vstep, size_t src_stride,
+               uint8_t *dst, int dst_vstep, size_t dst_stride, uint8_t *luts, int batch, bool use_src, bool use_dst,
+               pc::Args *a) {
+  if (const char *bad = clahe_check_params(p)) return fail(c, PISLAM_ERR_INVALID, bad);
+  if (const char *bad = pc::check_call(p->width, p->height, pislam_clahe_lut_size(p), src, src_vstep, src_stride, dst,
+                                       dst_vstep, dst_stride, luts, batch, use_src, use_dst))
+    return fail(c, PISLAM_ERR_INVALID, bad);
+  if (batch == 0) return PISLAM_OK;
+  if (use_src && !is_device_ptr(src)) return fail(c, PISLAM_ERR_INVALID, "CLAHE takes device pointers only");
+  if (use_dst && !is_device_ptr(dst)) return fail(c, PISLAM_ERR_INVALID, "CLAHE takes device pointers only");
+  if (!is_device_ptr(luts)) return fail(c, PISLAM_ERR_INVALID, "CLAHE takes device pointers only");
+  *a = pc::geometry(p->width, p->height, p->tiles_x, p->tiles_y, p->clip_q8);
+  a->src = src, a->src_vstep = src_vstep, a->src_stride = src_stride;
+  a->dst = dst, a->dst_vstep = dst_vstep, a->dst_stride = dst_stride;
+  a->luts = luts;
+  return PISLAM_OK;
+}
+
+// One launch per 65535 frames (grid.y); `apply` chooses the kernel.
+int clahe_launch(pislam_ctx *c, pc::Args a, int batch, bool apply) {
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t ntiles = (size_t)a.tiles_x * a.tiles_y;
+  const unsigned gx = apply ? (unsigned)(a.cells_x * a.cells_y * a.chunks) : (unsigned)ntiles;
+  const uint8_t *src = a.src;
+  uint8_t *dst = a.dst, *luts = a.luts;
+  for (int b0 = 0; b0 < batch; b0 += 65535) {
+    const dim3 grid(gx, (unsigned)std::min(batch - b0, 65535)), block(pc::THREADS);
+    a.src = src + (size_t)b0 * a.src_stride, a.luts = luts + (size_t)b0 * ntiles * 256;
+    if (apply) a.dst = dst + (size_t)b0 * a.dst_stride;
+    if (!apply && c->opt_clahe_combine) hipLaunchKernelGGL(pc::k_clahe_luts<true>, grid, block, 0, c->stream, a);
+    else if (!apply) hipLaunchKernelGGL(pc::k_clahe_luts<false>, grid, block, 0, c->stream, a);
+    else if (c->opt_clahe_lut_global) hipLaunchKernelGGL(pc::k_clahe_apply<false>, grid, block, 0, c->stream, a);
+    else hipLaunchKernelGGL(pc::k_clahe_apply<true>, grid, block, 0, c->stream, a);
+    PCHK(launch_ok(c, apply ? "k_clahe_apply" : "k_clahe_luts"));
+  }
+  return PISLAM_OK;
+}
+
+}  // namespace
+
+PISLAM_EXPORT size_t pislam_clahe_lut_size(const pislam_clahe_params *p) {
+  return clahe_check_params(p) ? 0 : (size_t)p->tiles_x * (size_t)p->tiles_y * 256;
+}
+
+PISLAM_EXPORT int pislam_clahe_luts_batch(pislam_ctx *c, const pislam_clahe_params *p, const uint8_t *src, int src_vstep,
+                                          size_t src_stride, int batch, uint8_t *luts) {
+  if (!c) return PISLAM_ERR_INVALID;
+  pc::Args a{};
+  PCHK(clahe_args(c, p, src, src_vstep, src_stride, nullptr, 0, 0, luts, batch, true, false, &a));
+  return batch ? clahe_launch(c, a, batch, false) : PISLAM_OK;
+}
+
+PISLAM_EXPORT int pislam_clahe_apply_batch(pislam_ctx *c, const pislam_clahe_params *p, const uint8_t *src, int src_vstep,
+                                           size_t src_stride, const uint8_t *luts, uint8_t *dst, int dst_vstep,
+                                           size_t dst_stride, int batch) {
+  if (!c) return PISLAM_ERR_INVALID;
+  pc::Args a{};
+  PCHK(clahe_args(c, p, src, src_vstep, src_stride, dst, dst_vstep, dst_stride, const_cast<uint8_t *>(luts), batch, true,
+                  true, &a));
+  return batch ? clahe_launch(c, a, batch, true) : PISLAM_OK;
+}
+
+PISLAM_EXPORT int pislam_clahe_batch(pislam_ctx *c, const pislam_clahe_params *p, const uint8_t *src, int src_vstep,
+                                     size_t src_stride, uint8_t *dst, int dst_vstep, size_t dst_stride, int batch,
+                                     uint8_t *luts) {
+  if (!c) return PISLAM_ERR_INVALID;
+  pc::Args a{};
+  PCHK(clahe_args(c, p, src, src_vstep, src_stride, dst, dst_vstep, dst_stride, luts, batch, true, true, &a));
+  if (batch == 0) return PISLAM_OK;
+  PCHK(clahe_launch(c, a, batch, false));
+  return clahe_launch(c, a, batch, true);
 }
 
 // ---- after the match: batched angle bins and match selection ------------------------------

@@ -17,7 +17,7 @@ import ctypes
 import numpy as np
 
 from . import capi
-from .capi import Context, FrontendParams, Level, SelectParams, StereoParams, ptr
+from .capi import ClaheParams, Context, FrontendParams, Level, SelectParams, StereoParams, ptr
 
 _default_ctx: Context | None = None
 
@@ -826,6 +826,84 @@ class Warp:
             self.close()
         except Exception:
             pass
+
+
+# ---- contrast-limited adaptive histogram equalisation: between the warp and the pyramid build ------
+class Clahe:
+    """pislam_clahe_*: CLAHE of batches of device-resident frames uint8 [batch][height][width], after OpenCV's
+    createCLAHE(clip_q8 / 256, tiles) but stated in integers (include/pislam_hip.h).  The defaults are ORB-SLAM3's
+    (8 x 8 tiles, clip limit 3.0).  The tables are a caller-visible device tensor uint8
+    [batch][tiles_y][tiles_x][256]; there is no workspace, so every call can be captured into a graph.  Shapes are
+    checked here, values by the library."""
+
+    def __init__(self, width: int, height: int, tiles=(8, 8), clip_q8: int = 768, ctx: Context | None = None):
+        self.ctx = ctx or default_context()
+        self.width, self.height, self.tiles, self.clip_q8 = int(width), int(height), (int(tiles[0]), int(tiles[1])), int(clip_q8)
+        self.params = ClaheParams(self.width, self.height, self.tiles[0], self.tiles[1], self.clip_q8)
+        self.lut_size = int(self.ctx.lib.pislam_clahe_lut_size(ctypes.byref(self.params)))
+        if self.lut_size == 0:
+            raise capi.PislamError("pislam_clahe_lut_size: need 1 <= width, height <= 4096, 1 <= tiles <= min(32, size) per axis, "
+                                   "a tile of at most 2^20 pixels and 0 <= clip_q8 <= 65535")
+        self.last_luts = None
+
+    def _frames(self, t, name, batch=None):
+        import torch
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[1] != self.height or t.shape[2] < self.width \
+                or (t.shape[2] > 1 and t.stride(2) != 1) or (batch is not None and t.shape[0] != batch):
+            raise ValueError(f"{name} must be uint8 [{'batch' if batch is None else batch}][{self.height}][>= {self.width}] "
+                             "with adjacent row bytes")
+        return int(t.shape[0])
+
+    def _luts(self, luts, batch, device):
+        import torch
+        shape = (batch, self.tiles[1], self.tiles[0], 256)
+        if luts is None:
+            return torch.empty(shape, dtype=torch.uint8, device=device)
+        if luts.dtype != torch.uint8 or tuple(luts.shape) != shape or not luts.is_contiguous():
+            raise ValueError(f"luts must be a contiguous uint8 tensor {list(shape)}")
+        return luts
+
+    def luts(self, frames, out=None, *, ctx: Context | None = None):
+        """The tables of `frames` (pislam_clahe_luts_batch): uint8 [batch][tiles_y][tiles_x][256], allocated when
+        `out` is None.  Asynchronous on the stream of `ctx` (default: this object's context)."""
+        c = ctx or self.ctx
+        batch = self._frames(frames, "frames")
+        out = self._luts(out, batch, frames.device)
+        c.check(c.lib.pislam_clahe_luts_batch(c.h, ctypes.byref(self.params), frames.data_ptr(), int(frames.stride(1)),
+                                              int(frames.stride(0)), batch, out.data_ptr()), "pislam_clahe_luts_batch")
+        return out
+
+    def apply(self, frames, luts, out=None, *, ctx: Context | None = None):
+        """Blends the given tables into `out` (pislam_clahe_apply_batch; allocated when None, may be `frames` itself)."""
+        import torch
+        c = ctx or self.ctx
+        batch = self._frames(frames, "frames")
+        luts = self._luts(luts, batch, frames.device)
+        if out is None:
+            out = torch.empty((batch, self.height, self.width), dtype=torch.uint8, device=frames.device)
+        self._frames(out, "out", batch)
+        c.check(c.lib.pislam_clahe_apply_batch(c.h, ctypes.byref(self.params), frames.data_ptr(), int(frames.stride(1)),
+                                               int(frames.stride(0)), luts.data_ptr(), out.data_ptr(), int(out.stride(1)),
+                                               int(out.stride(0)), batch), "pislam_clahe_apply_batch")
+        return out
+
+    def __call__(self, frames, out=None, luts=None, *, ctx: Context | None = None):
+        """frames: uint8 device tensor [batch][height][>= width] (a view with padded rows or frames is fine as long as
+        bytes of a row are adjacent); out: likewise, allocated when None, may be `frames` itself (in place); luts:
+        the table tensor, allocated when None and kept as `last_luts` either way.  pislam_clahe_batch: tables, then
+        blend, asynchronous on the stream of `ctx` (default: this object's context); returns out."""
+        import torch
+        c = ctx or self.ctx
+        batch = self._frames(frames, "frames")
+        luts = self._luts(luts, batch, frames.device)
+        if out is None:
+            out = torch.empty((batch, self.height, self.width), dtype=torch.uint8, device=frames.device)
+        self._frames(out, "out", batch)
+        c.check(c.lib.pislam_clahe_batch(c.h, ctypes.byref(self.params), frames.data_ptr(), int(frames.stride(1)),
+                                         int(frames.stride(0)), out.data_ptr(), int(out.stride(1)), int(out.stride(0)), batch,
+                                         luts.data_ptr()), "pislam_clahe_batch")
+        self.last_luts = luts
+        return out
 
 
 # ---- on-GPU pyramid build (BASELINE config 5) ------------------------------------------
