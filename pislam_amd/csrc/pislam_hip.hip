@@ -856,15 +856,12 @@ PISLAM_EXPORT int pislam_harris_score_points(pislam_ctx *c, int vstep, const uin
 
 
 namespace {
-// launch bilinear N/M for `batch` images; fast 4-block kernel when everything is 16-byte aligned
+// launch bilinear N/M for `batch` images; quad: the fast 4-block kernel (pp::quad_kernel_applies)
 template <int N, int M>
 int launch_bilinear(pislam_ctx *c, const uint8_t *src, uint8_t *dst, int vstep_src, int vstep_dst, size_t stride_src,
-                    size_t stride_dst, int batch, int width, int height) {
+                    size_t stride_dst, int batch, int width, int height, bool quad) {
   const int nbx = cdiv(width, N), nby = cdiv(height, N);
-  const bool fast = ((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 4 == 0) && vstep_src % 16 == 0 && vstep_dst % 4 == 0 &&
-                    stride_src % 16 == 0 && stride_dst % 4 == 0 &&
-                    (ptrdiff_t)cdiv(nbx, 4) * 4 * N <= vstep_src;      // the last group's 16-byte loads stay in the row
-  if (fast)
+  if (quad)
     hipLaunchKernelGGL((pp::k_bilinear4<N, M>), dim3(cdiv(cdiv(nbx, 4) * nby * M, 256), 1, batch), dim3(256), 0,
                        c->stream, src, dst, vstep_src, vstep_dst, stride_src, stride_dst, width, height);
   else
@@ -883,14 +880,13 @@ int prep_common(pislam_ctx *c, int kind, int vstep, int width, int height, const
   if (!c) return PISLAM_ERR_INVALID;
   if (!img || !out) return fail(c, PISLAM_ERR_INVALID, "null image");
   if (vstep <= 0 || width <= 0 || height <= 0) return fail(c, PISLAM_ERR_INVALID, "bad vstep/width/height");
-  const int N = kind == 0 ? 1 : (kind == 1 ? 8 : 16);
-  const int wpad = (width + N - 1) / N * N, hpad = (height + N - 1) / N * N;   // Bilinear.h:32,155 padding
+  const pp::Reduction r = kind == 0 ? pp::Reduction{1, 1} : pp::reduction(kind);
+  const int wpad = r.padded(width), hpad = r.padded(height);
   if (wpad > vstep) return fail(c, PISLAM_ERR_INVALID, "width (padded to the block size) exceeds vstep");
   if (kind == 0 && (width < 3 || height < 3)) return fail(c, PISLAM_ERR_INVALID, "gaussian5x5 needs at least 3x3");
   HIPCHK(c, hipSetDevice(c->device));
   const size_t in_bytes = (size_t)hpad * vstep;
-  const int M = kind == 1 ? 7 : 13;
-  const size_t out_rows = kind == 0 ? (size_t)height : (size_t)(hpad / N) * M;
+  const size_t out_rows = (size_t)r.written(height);
   const size_t out_bytes = out_rows * vstep;
   Staged si, so;
   PCHK(stage_in(c, c->s_img, img, in_bytes, &si));
@@ -914,10 +910,11 @@ int prep_common(pislam_ctx *c, int kind, int vstep, int width, int height, const
     hipLaunchKernelGGL(pp::k_gaussian5x5, grid, dim3(256), 0, c->stream, d_src, d_dst, vstep, vstep, (size_t)0,
                        (size_t)0, width, height);
     PCHK(launch_ok(c, "k_gaussian5x5"));
-  } else if (kind == 1) {
-    PCHK((launch_bilinear<8, 7>(c, d_src, d_dst, vstep, vstep, 0, 0, 1, width, height)));
   } else {
-    PCHK((launch_bilinear<16, 13>(c, d_src, d_dst, vstep, vstep, 0, 0, 1, width, height)));
+    const bool quad = pp::quad_kernel_applies((unsigned)((uintptr_t)d_src % 16), (unsigned)((uintptr_t)d_dst % 16), vstep, vstep, 0, 0,
+                                              r.blocks(width), r.N);
+    if (kind == 1) PCHK((launch_bilinear<8, 7>(c, d_src, d_dst, vstep, vstep, 0, 0, 1, width, height, quad)));
+    else PCHK((launch_bilinear<16, 13>(c, d_src, d_dst, vstep, vstep, 0, 0, 1, width, height, quad)));
   }
   if (so.host) {
     PCHK(stage_out(c, so, out, out_bytes));   // rows the kernels can have written
@@ -949,194 +946,110 @@ PISLAM_EXPORT int pislam_bilinear13_16(pislam_ctx *c, int vstep, int width, int 
 // ---------------------------------------------------------------------------
 PISLAM_EXPORT int pislam_pyramid_layout(int width, int height, int nlevels, const int32_t *steps, int vstep_min,
                                         pislam_level *levels, int32_t *vstep, int32_t *rows) {
-  if (width <= 0 || height <= 0 || nlevels < 1 || nlevels > 16 || !levels || (nlevels > 1 && !steps))
-    return PISLAM_ERR_INVALID;
-  int w = width, h = height, row = 0, maxcols = width;
-  for (int l = 0; l < nlevels; l++) {
-    int written = 0;                       // rows the reduction INTO this level writes (whole 7x7 / 13x13 blocks)
-    if (l > 0) {
-      if (steps[l - 1] == 1) {
-        written = (h + 7) / 8 * 7;
-        maxcols = std::max(maxcols, (w + 7) / 8 * 7);
-        w = w * 7 / 8;                     // Bilinear.h:34-35: round down
-        h = h * 7 / 8;
-      } else if (steps[l - 1] == 2) {
-        written = (h + 15) / 16 * 13;
-        maxcols = std::max(maxcols, (w + 15) / 16 * 13);
-        w = w * 13 / 16;                   // Bilinear.h:157-158
-        h = h * 13 / 16;
-      } else {
-        return PISLAM_ERR_INVALID;
-      }
-    }
-    if (w < 3 || h < 3) return PISLAM_ERR_INVALID;
-    levels[l].width = w;
-    levels[l].height = h;
-    levels[l].row0 = row;
-    levels[l].col0 = 0;
-    // the slot holds the padding rows the next reduction reads (Bilinear.h:32,155) and every row the
-    // reduction into this level writes
-    row += std::max((h + 15) / 16 * 16, written);
+  return pp::layout(width, height, nlevels, steps, vstep_min, levels, vstep, rows);
+}
+
+// The steps of pislam_pyramid_build_batch, in launch order.  What each launches is decided by pp::make_build_plan.
+namespace {
+// Padding bytes are read by the bilinear steps (block padding) and by FAST's right-edge columns: they are
+// defined as zero.  Every build rewrites the same rectangle of each level's slot and zeroes the margins
+// around it that those consumers read (pp::k_zero_margins) — on EVERY call: a caller may have scribbled over
+// the buffer, or the allocator may hand out a recycled address — unless the caller vouches for them
+// (PISLAM_BUILD_MARGINS_CLEAN: a buffer this function filled before with the same layout and nobody wrote
+// to since; the margin pass costs ~20 us per 64 720p frames).  Bytes beyond the margins are nobody's input
+// and are left untouched (zero-initialise the buffer once if they must be defined).
+int build_margins(pislam_ctx *c, const pp::ZeroPlan &Z, int batch, uint8_t *pyramids, size_t pyramid_stride, bool check) {
+  if (check) {
+    // debug: verify the caller's promise instead of trusting it (synchronises; a dirty margin is an error)
+    if (c->w_total.ensure(sizeof(uint32_t)) != PISLAM_OK) return fail(c, PISLAM_ERR_NOMEM, "hipMalloc");
+    HIPCHK(c, hipMemsetAsync(c->w_total.p, 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(pp::k_zero_margins<true>, dim3(2 * Z.nlevels, batch), dim3(256), 0, c->stream, Z, pyramids,
+                       pyramid_stride, c->w_total.as<unsigned int>());
+    PCHK(launch_ok(c, "k_zero_margins<check>"));
+    uint32_t nz = 0;
+    HIPCHK(c, hipMemcpyAsync(&nz, c->w_total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    PCHK(sync(c));
+    if (nz) return fail(c, PISLAM_ERR_INVALID, "PISLAM_BUILD_MARGINS_CLEAN was passed but the margins hold non-zero bytes");
+    return PISLAM_OK;
   }
-  if (vstep) *vstep = std::max(vstep_min, (maxcols + 15) / 16 * 16);
-  if (rows) *rows = row;
+  hipLaunchKernelGGL(pp::k_zero_margins<false>, dim3(2 * Z.nlevels, batch), dim3(256), 0, c->stream, Z, pyramids,
+                     pyramid_stride, (unsigned int *)nullptr);
+  return launch_ok(c, "k_zero_margins");
+}
+
+// level 0 = gaussian5x5 of the frame, or the frame itself
+int build_level0(pislam_ctx *c, const pislam_level &lv, const uint8_t *frames, int frame_vstep, size_t frame_stride, int batch,
+                 uint8_t *pyramids, int vstep, size_t pyramid_stride, bool blur) {
+  const int w0 = lv.width, h0 = lv.height;
+  uint8_t *dst = pyramids + (size_t)lv.row0 * vstep;
+  if (blur) {
+    hipLaunchKernelGGL(pp::k_gaussian5x5, dim3(cdiv(w0, pp::G_TW), cdiv(h0, pp::G_TH), batch), dim3(256), 0, c->stream,
+                       frames, dst, frame_vstep, vstep, frame_stride, pyramid_stride, w0, h0);
+    return launch_ok(c, "k_gaussian5x5");
+  }
+  for (int b = 0; b < batch; b++)
+    HIPCHK(c, hipMemcpy2DAsync(dst + b * pyramid_stride, vstep, frames + b * frame_stride, frame_vstep, w0, h0,
+                               hipMemcpyDeviceToDevice, c->stream));
   return PISLAM_OK;
 }
+
+// (Fusing two chained reductions per launch — a 128-tile of level k maps onto whole blocks of 13/16 then 7/8,
+//  level k+1 kept in LDS — was built and measured: 184 vs 167 us per 64 frames, 667 vs 584 us per 256.  The
+//  64-frame pyramid set fits the 256 MiB Infinity Cache, so the re-read the fusion saves never reaches HBM,
+//  and the LDS round trips cost more than k_bilinear4's register-only path.)
+// (The small levels in ONE launch — one 1024-thread workgroup per pyramid walking levels 3 .. 7 through k_bilinear4's
+//  work items, a device-scope fence + barrier between levels — was built in round 4, bit-exact, and measured: the step of
+//  64 720p frames 0.375 -> 0.53 ms from level 3 on, 0.59 ms from level 2 on: 64 workgroups with a handful of dependent
+//  load -> compute -> store round trips each are far slower than five launches that fill the chip, launch floors included.)
+// Round 6: ALL reductions as one launch with a row-band hand-over between the levels (pp::k_bilinear_chain) — the same
+// work items as the per-level launches, every workgroup starting as soon as the source rows it reads are complete.
+int build_reductions(pislam_ctx *c, const pp::BuildPlan &P, int nlevels, int batch, uint8_t *pyramids, int vstep,
+                     size_t pyramid_stride) {
+  if (P.chain) {
+    bool grew = false;
+    if (c->w_chain.ensure(sizeof(uint32_t) * P.chain_words, &grew) != PISLAM_OK) return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(build chain counters)");
+    if (grew || c->chain_words != P.chain_words) {
+      // (a different layout puts [done, fault] elsewhere: start from zeros — stream order puts this behind any launch in flight)
+      HIPCHK(c, hipMemsetAsync(c->w_chain.p, 0, c->w_chain.cap, c->stream));
+      if (!grew && c->chain_words != 0) c->ovf_layouts++;   // (a captured build holds the old layout: workspace_generation)
+      c->chain_words = P.chain_words;
+    }
+    PCHK(ensure_fault_flag(c));
+    hipLaunchKernelGGL(pp::k_bilinear_chain, dim3(P.chain_grid), dim3(256), 0, c->stream, P.C, pyramids, pyramid_stride,
+                       c->w_chain.as<uint32_t>(), c->frame_flag_dev + 1, (uint32_t)c->opt_frame_test);
+    return launch_ok(c, "k_bilinear_chain");
+  }
+  for (int l = 0; l + 1 < nlevels; l++) {
+    const pp::ReductionPlan &R = P.red[l];
+    const uint8_t *src = pyramids + R.src_ofs;
+    uint8_t *dst = pyramids + R.dst_ofs;
+    if (R.step == 1)
+      PCHK((launch_bilinear<8, 7>(c, src, dst, vstep, vstep, pyramid_stride, pyramid_stride, batch, R.width, R.height, R.quad)));
+    else
+      PCHK((launch_bilinear<16, 13>(c, src, dst, vstep, vstep, pyramid_stride, pyramid_stride, batch, R.width, R.height, R.quad)));
+  }
+  return PISLAM_OK;
+}
+}  // namespace
 
 PISLAM_EXPORT int pislam_pyramid_build_batch(pislam_ctx *c, int nlevels, const int32_t *steps,
                                              const pislam_level *levels, const uint8_t *frames, int frame_vstep,
                                              size_t frame_stride, int batch, uint8_t *pyramids, int vstep,
                                              int rows, size_t pyramid_stride, int flags) {
-  const bool blur = (flags & PISLAM_BUILD_BLUR) != 0;
   if (!c) return PISLAM_ERR_INVALID;
-  // (ABI 1 took `blur` = any non-zero value here: unknown bits are refused, not silently read as flags)
-  if (flags & ~(PISLAM_BUILD_BLUR | PISLAM_BUILD_MARGINS_CLEAN | PISLAM_BUILD_CHECK_MARGINS))
-    return fail(c, PISLAM_ERR_INVALID, "unknown PISLAM_BUILD_* flag bits");
-  if (!levels || !frames || !pyramids || batch <= 0 || nlevels < 1 || nlevels > 16 || (nlevels > 1 && !steps))
-    return fail(c, PISLAM_ERR_INVALID, "bad argument");
-  if (!is_device_ptr(frames) || !is_device_ptr(pyramids))
-    return fail(c, PISLAM_ERR_INVALID, "the pyramid builder takes device pointers only");
-  PCHK(check_frame_poison(c));
-  for (int l = 0; l < nlevels; l++) {
-    const int pad = l + 1 < nlevels ? (steps[l] == 1 ? 8 : 16) : 1;
-    const int wp = (levels[l].width + pad - 1) / pad * pad, hp = (levels[l].height + pad - 1) / pad * pad;
-    if (levels[l].col0 != 0 || wp > vstep || levels[l].row0 + hp > rows || pyramid_stride < (size_t)rows * vstep)
-      return fail(c, PISLAM_ERR_INVALID, "level (with its bilinear padding) does not fit the pyramid buffer");
-  }
-  for (int l = 0; l + 1 < nlevels; l++) {           // whole output blocks must land inside the next level's slot
-    const int N = steps[l] == 1 ? 8 : 16, M = steps[l] == 1 ? 7 : 13;
-    const int oh = (levels[l].height + N - 1) / N * M, ow = (levels[l].width + N - 1) / N * M;
-    const int slot_end = l + 2 < nlevels ? levels[l + 2].row0 : rows;
-    if (ow > vstep || levels[l + 1].row0 + oh > slot_end)
-      return fail(c, PISLAM_ERR_INVALID, "a reduction's output blocks overrun the next level's slot (use pislam_pyramid_layout)");
-  }
-  if (levels[0].width > frame_vstep || frame_stride < (size_t)levels[0].height * frame_vstep)
-    return fail(c, PISLAM_ERR_INVALID, "frame buffer too small");
+  if (const char *bad = pp::check_build_call(nlevels, steps, levels, frames, pyramids, batch, flags))
+    return fail(c, PISLAM_ERR_INVALID, bad);
+  if (!is_device_ptr(frames) || !is_device_ptr(pyramids)) return fail(c, PISLAM_ERR_INVALID, pp::HOST_POINTERS);
   HIPCHK(c, hipSetDevice(c->device));
-  // Padding bytes are read by the bilinear steps (block padding) and by FAST's right-edge columns: they are
-  // defined as zero.  Every build rewrites the same rectangle of each level's slot and zeroes the margins
-  // around it that those consumers read (pp::k_zero_margins) — on EVERY call: a caller may have scribbled over
-  // the buffer, or the allocator may hand out a recycled address — unless the caller vouches for them
-  // (PISLAM_BUILD_MARGINS_CLEAN: a buffer this function filled before with the same layout and nobody wrote
-  // to since; the margin pass costs ~20 us per 64 720p frames).  Bytes beyond the margins are nobody's input
-  // and are left untouched (zero-initialise the buffer once if they must be defined).
-  const bool clean = (flags & PISLAM_BUILD_MARGINS_CLEAN) != 0, check = (flags & PISLAM_BUILD_CHECK_MARGINS) != 0;
-  if (!clean || check) {
-    pp::ZeroPlan Z;
-    memset(&Z, 0, sizeof(Z));
-    Z.nlevels = nlevels;
-    Z.vstep = vstep;
-    for (int l = 0; l < nlevels; l++) {
-      Z.row0[l] = levels[l].row0;
-      Z.slot_rows[l] = (l + 1 < nlevels ? levels[l + 1].row0 : rows) - levels[l].row0;
-      if (l == 0) {
-        Z.ww[l] = levels[0].width;
-        Z.wh[l] = levels[0].height;
-      } else {
-        const int N = steps[l - 1] == 1 ? 8 : 16, M = steps[l - 1] == 1 ? 7 : 13;
-        Z.ww[l] = (levels[l - 1].width + N - 1) / N * M;
-        Z.wh[l] = (levels[l - 1].height + N - 1) / N * M;
-      }
-    }
-    if (clean) {
-      // debug: verify the caller's promise instead of trusting it (synchronises; a dirty margin is an error)
-      if (c->w_total.ensure(sizeof(uint32_t)) != PISLAM_OK) return fail(c, PISLAM_ERR_NOMEM, "hipMalloc");
-      HIPCHK(c, hipMemsetAsync(c->w_total.p, 0, sizeof(uint32_t), c->stream));
-      hipLaunchKernelGGL(pp::k_zero_margins<true>, dim3(2 * nlevels, batch), dim3(256), 0, c->stream, Z, pyramids,
-                         pyramid_stride, c->w_total.as<unsigned int>());
-      PCHK(launch_ok(c, "k_zero_margins<check>"));
-      uint32_t nz = 0;
-      HIPCHK(c, hipMemcpyAsync(&nz, c->w_total.p, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-      PCHK(sync(c));
-      if (nz) return fail(c, PISLAM_ERR_INVALID, "PISLAM_BUILD_MARGINS_CLEAN was passed but the margins hold non-zero bytes");
-    } else {
-      hipLaunchKernelGGL(pp::k_zero_margins<false>, dim3(2 * nlevels, batch), dim3(256), 0, c->stream, Z, pyramids,
-                         pyramid_stride, (unsigned int *)nullptr);
-      PCHK(launch_ok(c, "k_zero_margins"));
-    }
-  }
-  const int w0 = levels[0].width, h0 = levels[0].height;
-  if (blur) {
-    hipLaunchKernelGGL(pp::k_gaussian5x5, dim3(cdiv(w0, pp::G_TW), cdiv(h0, pp::G_TH), batch), dim3(256), 0, c->stream,
-                       frames, pyramids + (size_t)levels[0].row0 * vstep, frame_vstep, vstep, frame_stride,
-                       pyramid_stride, w0, h0);
-    PCHK(launch_ok(c, "k_gaussian5x5"));
-  } else {
-    HIPCHK(c, hipMemcpy2DAsync(pyramids + (size_t)levels[0].row0 * vstep, vstep, frames, frame_vstep, w0, h0,
-                               hipMemcpyDeviceToDevice, c->stream));
-    for (int b = 1; b < batch; b++)
-      HIPCHK(c, hipMemcpy2DAsync(pyramids + b * pyramid_stride + (size_t)levels[0].row0 * vstep, vstep,
-                                 frames + b * frame_stride, frame_vstep, w0, h0, hipMemcpyDeviceToDevice, c->stream));
-  }
-  // (Fusing two chained reductions per launch — a 128-tile of level k maps onto whole blocks of 13/16 then 7/8,
-  //  level k+1 kept in LDS — was built and measured: 184 vs 167 us per 64 frames, 667 vs 584 us per 256.  The
-  //  64-frame pyramid set fits the 256 MiB Infinity Cache, so the re-read the fusion saves never reaches HBM,
-  //  and the LDS round trips cost more than k_bilinear4's register-only path.)
-  // (The small levels in ONE launch — one 1024-thread workgroup per pyramid walking levels 3 .. 7 through k_bilinear4's
-  //  work items, a device-scope fence + barrier between levels — was built in round 4, bit-exact, and measured: the step of
-  //  64 720p frames 0.375 -> 0.53 ms from level 3 on, 0.59 ms from level 2 on: 64 workgroups with a handful of dependent
-  //  load -> compute -> store round trips each are far slower than five launches that fill the chip, launch floors included.)
-  // Round 6: ALL reductions as one launch with a row-band hand-over between the levels (pp::k_bilinear_chain) — the same
-  // work items as the per-level launches, every workgroup starting as soon as the source rows it reads are complete.
-  bool chain = c->opt_build_chain && !c->chain_disabled && nlevels >= 3;
-  pp::ChainPlan C;
-  memset(&C, 0, sizeof(C));
-  if (chain) {
-    chain = (uintptr_t)pyramids % 16 == 0 && vstep % 16 == 0 && pyramid_stride % 16 == 0;   // k_bilinear4's fast path, every level
-    C.nlevels = nlevels;
-    C.vstep = vstep;
-    C.batch = batch;
-    C.groups = cdiv(batch, 8);
-    long wg = 0;
-    int bands = 0;
-    for (int l = 1; l < nlevels && chain; l++) {
-      const int N = steps[l - 1] == 1 ? 8 : 16, M = steps[l - 1] == 1 ? 7 : 13;
-      const int sw = levels[l - 1].width, sh = levels[l - 1].height;
-      const int nbx = cdiv(sw, N), nby = cdiv(sh, N);
-      if ((ptrdiff_t)cdiv(nbx, 4) * 4 * N > vstep) chain = false;      // the last group's 16-byte loads must stay in the row
-      C.kind[l] = steps[l - 1];
-      C.row0[l] = levels[l].row0;
-      C.sw[l] = sw;
-      C.sh[l] = sh;
-      C.nq[l] = cdiv(nbx, 4);
-      C.oh[l] = nby * M;
-      C.wpf[l] = cdiv(C.nq[l] * C.oh[l], 256);
-      C.wg0[l] = (int)wg;
-      wg += 8L * C.wpf[l] * C.groups;                 // (frame = 8 g + b % 8: one XCD per frame, see the kernel)
-      C.band0[l] = bands;
-      bands += cdiv(C.oh[l], pp::CH_BAND);
-    }
-    C.row0[0] = levels[0].row0;
-    C.bands_per_frame = bands;
-    C.wg0[nlevels] = (int)wg;
-    if (wg > 0x3fffffffL) chain = false;
-    if (chain) {
-      const size_t words = pp::chain_words((size_t)batch, (size_t)bands, (size_t)C.groups);
-      bool grew = false;
-      if (c->w_chain.ensure(sizeof(uint32_t) * words, &grew) != PISLAM_OK) return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(build chain counters)");
-      if (grew || c->chain_words != words) {
-        // (a different layout puts [done, fault] elsewhere: start from zeros — stream order puts this behind any launch in flight)
-        HIPCHK(c, hipMemsetAsync(c->w_chain.p, 0, c->w_chain.cap, c->stream));
-        if (!grew && c->chain_words != 0) c->ovf_layouts++;   // (a captured build holds the old layout: workspace_generation)
-        c->chain_words = words;
-      }
-      PCHK(ensure_fault_flag(c));
-      hipLaunchKernelGGL(pp::k_bilinear_chain, dim3((unsigned)wg), dim3(256), 0, c->stream, C, pyramids, pyramid_stride,
-                         c->w_chain.as<uint32_t>(), c->frame_flag_dev + 1, (uint32_t)c->opt_frame_test);
-      PCHK(launch_ok(c, "k_bilinear_chain"));
-    }
-  }
-  if (!chain)
-    for (int l = 0; l + 1 < nlevels; l++) {
-      const uint8_t *src = pyramids + (size_t)levels[l].row0 * vstep;
-      uint8_t *dst = pyramids + (size_t)levels[l + 1].row0 * vstep;
-      const int w = levels[l].width, h = levels[l].height;
-      if (steps[l] == 1)
-        PCHK((launch_bilinear<8, 7>(c, src, dst, vstep, vstep, pyramid_stride, pyramid_stride, batch, w, h)));
-      else
-        PCHK((launch_bilinear<16, 13>(c, src, dst, vstep, vstep, pyramid_stride, pyramid_stride, batch, w, h)));
-    }
-  return PISLAM_OK;
+  PCHK(check_frame_poison(c));
+  const pp::BuildPlan P = pp::make_build_plan(nlevels, steps, levels, frame_vstep, frame_stride, batch, vstep, rows, pyramid_stride,
+                                              flags, (unsigned)((uintptr_t)pyramids % 16), c->opt_build_chain && !c->chain_disabled);
+  if (P.refusal) return fail(c, PISLAM_ERR_INVALID, P.refusal);
+  if (P.margins)
+    PCHK(build_margins(c, P.Z, batch, pyramids, pyramid_stride, (flags & PISLAM_BUILD_MARGINS_CLEAN) != 0));
+  PCHK(build_level0(c, levels[0], frames, frame_vstep, frame_stride, batch, pyramids, vstep, pyramid_stride,
+                    (flags & PISLAM_BUILD_BLUR) != 0));
+  return build_reductions(c, P, nlevels, batch, pyramids, vstep, pyramid_stride);
 }
 
 // ===========================================================================

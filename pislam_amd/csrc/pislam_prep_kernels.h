@@ -5,6 +5,7 @@
 // All three are pure HBM streaming kernels (1 byte read + ~1 byte written per pixel).
 #pragma once
 #include "pislam_dev.h"
+#include "pislam_prep_plan.h"
 
 namespace pp {
 
@@ -318,36 +319,7 @@ __global__ __launch_bounds__(256) void k_bilinear4(const uint8_t *__restrict__ s
 //   * the launch's last workgroup re-arms the counters: a captured launch replays with no host-side reset.
 // Level 0 (the blurred frame) comes from the launch before this one (stream order): level 1 waits for nothing.
 // ---------------------------------------------------------------------------
-constexpr int CH_BAND = 16;
-struct ChainPlan {
-  int nlevels, vstep, batch, bands_per_frame;
-  int groups;                  // ceil(batch / 8) groups of eight frames (frame = 8 g + b % 8)
-  int wg0[17];                 // first workgroup of level l (1 .. nlevels-1), multiples of 8; wg0[nlevels] = grid size
-  // (Launch order: level-major.  Ordering by diagonals d = g + l - 1 — group g's level l + 1 one step behind its level l, so
-  //  that the small levels of the early groups run beside the big levels of the late ones instead of all at the end — was
-  //  measured: 202 us per 64-frame build against 166: consumers then sit right behind their producers in the dispatch order,
-  //  and a waiting workgroup holds a slot.)
-  int wpf[16];                 // workgroups per frame of level l
-  int kind[16];                // the reduction INTO level l: 1 = 7/8, 2 = 13/16
-  int row0[16];                // pyramid row of level l
-  int sw[16], sh[16];          // width / height of level l - 1 (the source of the reduction into level l)
-  int nq[16], oh[16];          // level l: items per output row, output rows written
-  int band0[16];               // index (within a frame's block) of level l's first band counter
-};
-// ctr: [batch][bands_per_frame] band counters (rounded up to a 128-byte line), then — every word on a 128-byte line of its
-// own (CH_LINE dwords apart) — [0] sticky fault (a wait timed out / a frame met two XCDs), [1] shards complete,
-// [2 .. 2 + CH_SHARDS) workgroups done per shard, [2 + CH_SHARDS ..) the XCD of each frame + 1 (0 = not yet known).  All
-// zero between launches (the fault word: until the host has seen it).
-// (Measured, 64 720p frames: ONE done counter next to the fault word every poller reads and the per-frame XCD words every
-//  workgroup reads made the kernel 837 us; without the done counter 134 us — 12 500 returning atomics on a line that 12 500
-//  other accesses want.  Hence the shards and the lines.)
-constexpr int CH_LINE = 32, CH_SHARDS = 64;
-__host__ __device__ constexpr size_t chain_tail_ofs(size_t batch, size_t bands_per_frame) {
-  return (batch * bands_per_frame + CH_LINE - 1) / CH_LINE * CH_LINE;
-}
-__host__ __device__ constexpr size_t chain_words(size_t batch, size_t bands_per_frame, size_t groups) {
-  return chain_tail_ofs(batch, bands_per_frame) + (2 + CH_SHARDS + 8 * groups) * CH_LINE;
-}
+// (pp::ChainPlan, CH_BAND and the counter layout — chain_tail_ofs, chain_words — are in pislam_prep_plan.h)
 __global__ __launch_bounds__(256) void k_bilinear_chain(const ChainPlan C, uint8_t *__restrict__ pyramids, size_t stride,
                                                         uint32_t *__restrict__ ctr, uint32_t *__restrict__ hflag,
                                                         uint32_t test) {
@@ -363,7 +335,7 @@ __global__ __launch_bounds__(256) void k_bilinear_chain(const ChainPlan C, uint8
   uint32_t *tail = ctr + chain_tail_ofs(C.batch, C.bands_per_frame);
   uint32_t *fault = tail, *top = tail + CH_LINE, *shard = tail + (2 + ((int)blockIdx.x & (CH_SHARDS - 1))) * CH_LINE;
   uint32_t *home = tail + (2 + CH_SHARDS) * CH_LINE;
-  const int N = C.kind[l] == 1 ? 8 : 16, M = C.kind[l] == 1 ? 7 : 13;
+  const int N = reduction(C.kind[l]).N, M = reduction(C.kind[l]).M;
   const bool idle = frame >= C.batch;               // (the batch is padded to whole groups of eight frames)
   uint32_t *fctr = ctr + (size_t)(idle ? 0 : frame) * C.bands_per_frame;
   if (tid == 0) sh_ok = 1;
@@ -491,11 +463,7 @@ __global__ __launch_bounds__(256) void k_bilinear(const uint8_t *__restrict__ sr
 // nobody's input and are left alone.  grid (2 * nlevels, batch): x = 2 l + {0: right, 1: bottom}; one workgroup
 // walks its rectangle.
 // ---------------------------------------------------------------------------
-struct ZeroPlan {
-  int nlevels, vstep;
-  int row0[16], ww[16], wh[16], slot_rows[16];
-};
-constexpr int ZM_COLS = 32, ZM_ROWS = 16;
+// (pp::ZeroPlan, ZM_COLS and ZM_ROWS are in pislam_prep_plan.h)
 // CHECK = true (debug flag PISLAM_BUILD_CHECK_MARGINS): nothing is written; the non-zero margin bytes are counted
 // into *dirty instead — what a caller's PISLAM_BUILD_MARGINS_CLEAN promise is verified with.
 template <bool CHECK>

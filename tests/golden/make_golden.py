@@ -12,6 +12,12 @@
   plan_summaries.json: what pislam_debug_build_plan answers for the seeded cases of tests/plan_fuzz.py and for every option
                        at the edges of its range (`make_golden.py plans`: recorded from the library that is loaded, which
                        must be the one whose planner is the reference for tests/test_plan_golden.py).
+  build_plans.json   : what pislam_pyramid_build_batch answered, before its planner moved into pislam_prep_plan.h, for the
+                       fixed cases of tools/probes/prep_host_check.cpp: one [name, answer] pair per line of that program's
+                       --dump.  Not made by this script: the function's text at that commit was compiled on the host with
+                       is_device_ptr, the HIP calls and the launches replaced by stubs that record them, and the line was
+                       printed from inside it (docs/experiments.md section V).  A planner that is meant to change plans
+                       re-records it as `prep_host_check --dump`.
 """
 import hashlib
 import os

@@ -184,7 +184,13 @@ def test_pyramid_build_equals_reference_functions_in_sequence(gpu_ctx, orc):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", [(1280, 720, (2, 1, 2, 2, 1, 2, 2), 64), (640, 480, (2, 1, 2, 2, 1, 2, 2), 5), (333, 251, (1, 2, 1), 3),
-                                   (1920, 1080, (2, 2, 1, 2), 2)])
+                                   (1920, 1080, (2, 2, 1, 2), 2),
+                                   # three reductions across the eight-frame group: at 48 columns a group of four 16-blocks would
+                                   # load past the row (both settings build level by level), at 64 it is the smallest one-launch build
+                                   (48, 40, (2, 1, 2), 9), (64, 40, (2, 1, 2), 9),
+                                   # the quad loads fit levels 0 and 1 but not level 2: the one launch is refused, per level the plain
+                                   # kernel takes the third reduction
+                                   (40, 40, (2, 2, 1), 2)])
 def test_one_launch_build_equals_one_launch_per_level(gpu_ctx, shape):
     """pp::k_bilinear_chain (every reduction of a build in ONE launch, row bands of level l handed to the workgroups of
     level l + 1 through counters) writes the bytes of the one-launch-per-level build (option "build_chain" 0) — at the bench's
@@ -277,4 +283,46 @@ def test_pyramid_build_flags_are_checked(gpu_ctx):
     assert build(1) == 0                                         # a normal build establishes the margins ...
     torch.cuda.synchronize()
     assert build(1 | 2 | 4) == 0                                 # ... and now the promise holds
+    torch.cuda.synchronize()
+
+
+@pytest.mark.gpu
+def test_pyramid_build_refusals_name_their_reason_and_write_nothing(gpu_ctx):
+    """Every refusal of pislam_pyramid_build_batch at 48 x 40, three reductions: PISLAM_ERR_INVALID, the text
+    tests/golden/build_plans.json records for that case (tools/probes/prep_host_check.cpp makes the same calls of the host
+    planner), and a destination nobody wrote to."""
+    import json
+    import os
+    import torch
+    from conftest import GOLDEN
+    from pislam_amd import capi
+    from pislam_amd.frontend import PyramidBuilder
+    with open(os.path.join(GOLDEN, "build_plans.json")) as f:
+        text = dict(json.load(f)["cases"])
+    pb = PyramidBuilder(48, 40, (2, 1, 2), ctx=gpu_ctx)
+    B = 2
+    d_fr = torch.randint(0, 256, (B, 40, 48), dtype=torch.uint8, device="cuda")
+    d_pyr = torch.full((B, pb.rows, pb.vstep), 0x5A, dtype=torch.uint8, device="cuda")
+    h_fr, h_pyr = np.zeros((B, 40, 48), np.uint8), np.full((B, pb.rows, pb.vstep), 0x5A, np.uint8)
+
+    def build(case, levels=pb.levels_c, frames=d_fr, frame_vstep=48, batch=B, pyramids=d_pyr, vstep=pb.vstep, flags=1):
+        rc = gpu_ctx.lib.pislam_pyramid_build_batch(gpu_ctx.h, pb.nlevels, pb.steps, levels, capi.ptr(frames), frame_vstep, 40 * 48, batch,
+                                                    capi.ptr(pyramids), vstep, pb.rows, pb.rows * pb.vstep, flags)
+        assert rc == -1, case                                    # PISLAM_ERR_INVALID
+        assert gpu_ctx.lib.pislam_last_error(gpu_ctx.h).decode() == text[case], case
+        torch.cuda.synchronize()
+        assert (d_pyr == 0x5A).all() and (h_pyr == 0x5A).all(), case
+
+    overrun = (capi.Level * pb.nlevels)(*[capi.Level(*l) for l in pb.levels])
+    overrun[2].row0 -= 8
+    build("refused-flags", flags=8)
+    build("refused-batch", batch=0)
+    build("refused-host-pointers", frames=h_fr)
+    build("refused-host-pointers", pyramids=h_pyr)
+    build("refused-level-does-not-fit", vstep=32)
+    build("refused-block-overrun", levels=overrun)
+    build("refused-frame-buffer", frame_vstep=47)
+    assert text["48x40-9"].startswith("ok ") and gpu_ctx.lib.pislam_pyramid_build_batch(
+        gpu_ctx.h, pb.nlevels, pb.steps, pb.levels_c, capi.ptr(d_fr), 48, 40 * 48, B, capi.ptr(d_pyr), pb.vstep, pb.rows,
+        pb.rows * pb.vstep, 1) == 0                              # (the same call without a fault is taken)
     torch.cuda.synchronize()
