@@ -646,6 +646,89 @@ int pislam_match_stereo_batch(pislam_ctx *ctx, int words, const pislam_level *le
                               int batch, int32_t *idx, uint32_t *dist, int32_t *disp_q8, uint32_t *sad,
                               uint32_t *nstereo);
 
+/* ---- pyramidal Lucas-Kanade tracking and sub-pixel match refinement ------ */
+
+/* The 2-D photometric step, with two uses.  Refinement: after any matcher and
+ * pislam_match_select_batch, start at the matched keypoint's position and get the Q8 sub-pixel position in the next
+ * frame.  Tracking: start at the previous position, or a prediction, and follow points coarse to fine through the
+ * stacked pyramid, with no descriptors.  The reference ships nothing of the kind: the semantics are this library's own,
+ * after the inverse-compositional Lucas-Kanade step (template gradients, as in Basalt's patch tracker; OpenCV's
+ * calcOpticalFlowPyrLK was not run against this), stated in integers from end to end.  This comment is the contract.
+ *
+ * Buffers.  Pair b is (prev pyramid b, next pyramid b), both uint8 [rows][vstep] at + b * pyramid_stride, both sharing
+ * `levels`.  pts_q8 and guess_q8 are device int32 [batch][stride][2] holding (x, y): stacked-pyramid coordinates in
+ * Q8 (256 is one pixel, pixel centres lie at integers).  guess_q8 is optional: NULL means the guess is the point
+ * itself.  n_b = min(counts[b], stride); PISLAM_COUNT_INVALID counts as 0; entries at and beyond n_b are not written.
+ * Outputs: next_q8 [batch][stride][2], status and err [batch][stride], ntracked [batch] (optional, device).  levels,
+ * scale_q16 and p are host arrays, read during the call (a captured graph keeps its own copy).
+ *
+ * Level and chain.  Point and guess coordinates are clamped to [-2^20, 2^20] first.  The point's level l is the
+ * rectangle that holds (x >> 8, y >> 8); with no such rectangle status = 1, next_q8 = the guess, err = 0xffffffff.
+ * Level-local coordinates: u = x - 256 * col0, v = y - 256 * row0 (the guess likewise, with level l's origin).  The
+ * chain is c_m = l + m * level_step for m = M .. 0, M = min(max_coarse, (nlevels - 1 - l) / level_step).  A level-l
+ * coordinate maps to level c, per axis in signed 64-bit with floor division, as
+ *   u_c = floor((u_l * s_l + floor(s_c / 2)) / s_c),     s = scale_q16,
+ * and back by the same formula with the roles exchanged; either result is clamped to [-2^22, 2^22] (no position that
+ * far out is inside a level; with scale tables that really describe one pyramid the clamp is never reached).  q
+ * starts as the guess.  For each coarse level (m > 0): map p and q to it and run the level procedure; if it ends with
+ * code 0, map its q back to level l and replace q, otherwise q is unchanged.  The own level (m = 0) decides the
+ * outputs.
+ *
+ * Level procedure, on a level of width W and height H with p and q level-local Q8, w = win_radius:
+ *  1. Sampling.  With x0 = x >> 8, ax = x & 255, likewise y0 and ay (arithmetic shifts):
+ *       Smp(x, y) = ((256-ax)*(256-ay)*B(x0,y0) + ax*(256-ay)*B(x0+1,y0) + (256-ax)*ay*B(x0,y0+1) + ax*ay*B(x0+1,y0+1)
+ *                    + 1024) >> 11,
+ *     Q5, 0..8160; B(x, y) is the level's byte at (row0 + y) * vstep + col0 + x.  inside(x, y, m) is true iff
+ *     x0 - m >= 0, y0 - m >= 0, x0 + m + 1 <= W - 1 and y0 + m + 1 <= H - 1.  No byte outside the level's rectangle
+ *     is ever read.
+ *  2. Template (prev).  If !inside(p, w + 1) the code is 1.  T(dx, dy) = Smp(px + 256 dx, py + 256 dy) for
+ *     |dx|, |dy| <= w + 1.  On the window |dx|, |dy| <= w: gx = (T(dx+1,dy) - T(dx-1,dy) + 4) >> 3 and
+ *     gy = (T(dx,dy+1) - T(dx,dy-1) + 4) >> 3 (arithmetic shift; |g| <= 1020).  A11 = sum gx^2, A12 = sum gx gy,
+ *     A22 = sum gy^2 (1020^2 * 225 < 2^28).
+ *  3. Conditioning.  n = (2w+1)^2, t = min_eig * n, det = A11 * A22 - A12^2 (64 bits).  The code is 2 unless
+ *     det > 0, A11 + A22 >= 2 t and (A11 - t) * (A22 - t) - A12^2 >= 0: lambda_min(A) >= t without a square root.
+ *  4. Search (next).  If !inside(q, w) the code is 3.  it = 0, then loop:
+ *       r = Smp(qx + 256 dx, qy + 256 dy) - T(dx, dy) over the window, sad = sum |r|.
+ *       If it == max_iters: stop with code 0.
+ *       b1 = sum r gx, b2 = sum r gy (8160 * 1020 * 225 < 2^31).  nx = A22 * b1 - A12 * b2, ny = A11 * b2 - A12 * b1.
+ *       step per axis = floor((-64 * n_axis + floor(det / 2)) / det) in exact integers (-64 n does not fit 64 bits in
+ *       the worst case, |n| < 2^60: the library splits n = k * det + rem and compares k with the clamp first), then
+ *       clamped to +- max_step_q8.
+ *       it += 1, q' = q + step.  If !inside(q', w): stop with code 3 and keep q.  Otherwise q = q'.
+ *       If both |step| <= eps_q8: recompute sad at q and stop with code 0.
+ *  5. Own level only: if the code is 0, max_err > 0 and sad > max_err * n, the code is 4.
+ *
+ * Outputs.  next_q8 = the final q on level l, back in stacked coordinates (+ 256 * col0, + 256 * row0): the q that
+ * entered the level when the own level could not start (code 1 or 2), the last position that was inside when it
+ * stopped on code 3.  status = code | it << 8, `it` the own level's iteration count (0 for codes 1 and 2); it ==
+ * max_iters with code 0 means the limit was hit, which still counts as tracked, as in OpenCV.  err = sad for codes 0
+ * and 4, else 0xffffffff.  ntracked[b] = the points of pair b with code 0.
+ *
+ * Limits: the parameter ranges in the struct comments; 1 <= nlevels <= 16, level rectangles non-empty, disjoint,
+ * inside [0, rows) x [0, vstep) and 12-bit coordinates, 1 <= scale_q16[l] <= 2^20 and every mapped extent <= 65535
+ * (as pislam_match_stereo_batch); stride < 2^31; batch >= 0 with no upper limit (batch == 0 is a no-op that returns
+ * PISLAM_OK after the checks of p, the tables, batch and stride; the data pointers are not looked at then).  Offsets
+ * use size_t arithmetic throughout: strides may carry a batch past 4 GiB.  No output may overlap an input or another
+ * output, except that next_q8 may be exactly guess_q8: each point reads its guess before it writes.  Any violation, or
+ * a host pointer where a device pointer is required: PISLAM_ERR_INVALID, before anything is launched or written.
+ * Asynchronous on the context stream; no workspace, no host round trip: the call can be captured into a hipGraph as
+ * it is, so there is no reserve call. */
+typedef struct pislam_lk_params {
+  int32_t win_radius;   /* w: window (2w+1)^2, 1..7 */
+  int32_t max_iters;    /* 1..32 */
+  int32_t eps_q8;       /* stop when both |step| <= eps_q8, 0..255 */
+  int32_t max_step_q8;  /* per-axis clamp of one step, 1..4096 */
+  int32_t level_step;   /* distance between chain levels, 1..15 */
+  int32_t max_coarse;   /* coarser levels used above the point's own, 0..15 */
+  int32_t min_eig;      /* smallest eigenvalue of A per window pixel, >= 0, <= 2^20 */
+  int32_t max_err;      /* mean |residual| limit (Q5 grey levels), 0 = no limit, <= 8160 */
+} pislam_lk_params;
+int pislam_track_lk_batch(pislam_ctx *ctx, const pislam_lk_params *p,
+                          const pislam_level *levels, int nlevels, const int32_t *scale_q16,
+                          const uint8_t *prev_pyr, const uint8_t *next_pyr, int vstep, int rows, size_t pyramid_stride,
+                          const int32_t *pts_q8, const uint32_t *counts, const int32_t *guess_q8, size_t stride,
+                          int batch, int32_t *next_q8, uint32_t *status, uint32_t *err, uint32_t *ntracked);
+
 /* ---- bag of words: quantisation, vector, word-guided matching ----------- */
 
 /* Matching without a position (relocalisation, loop closure, key frames

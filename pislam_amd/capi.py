@@ -35,6 +35,11 @@ class StereoParams(ctypes.Structure):
         "level_span", "min_disp", "max_disp", "max_hamming", "sad_radius", "search_radius", "median_filter")]
 
 
+class LkParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "win_radius", "max_iters", "eps_q8", "max_step_q8", "level_step", "max_coarse", "min_eig", "max_err")]
+
+
 class SelectParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "max_dist", "ratio_num", "ratio_den", "unique", "rot_keep", "rot_min_pct")]
@@ -117,6 +122,8 @@ SYMBOLS = {
     "pislam_match_stereo_batch": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),
                                        ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(StereoParams), _vp, _vp, _i, _i,
                                        _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pislam_track_lk_batch": (_i, [_vp, ctypes.POINTER(LkParams), ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),
+                                   _vp, _vp, _i, _i, _sz, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
     "pislam_vocab_create": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, ctypes.POINTER(_vp)]),
     "pislam_vocab_destroy": (_i, [_vp]),
     "pislam_vocab_nwords": (_i, [_vp]),

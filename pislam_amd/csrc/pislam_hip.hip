@@ -54,6 +54,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 
 #include "pislam_prep_kernels.h"
 #include "pislam_match_kernels.h"
+#include "pislam_track_kernels.h"
 #include "pislam_bow_kernels.h"
 #include "pislam_bowdb_kernels.h"
 #include "pislam_select_kernels.h"
@@ -2239,7 +2240,7 @@ void with_words(int words, F &&f) {
   }
 }
 
-// The same for sad_radius, which stereo_plan accepted (1..pm::ST_MAX_W).
+// The same for sad_radius, which stereo_plan accepted (1..pm::ST_MAX_W), and the tracker's win_radius (1..pt::LK_MAX_W, also 7).
 template <class F>
 void with_sad_radius(int sad_radius, F &&f) {
   switch (sad_radius) {
@@ -2601,6 +2602,112 @@ PISLAM_EXPORT int pislam_match_stereo_batch(pislam_ctx *c, int words, const pisl
     hipLaunchKernelGGL(pm::k_stereo_median, dim3((unsigned)batch), dim3(pm::ST_MEDIAN_THREADS), 0, c->stream,
                        p->median_filter, lcounts, l_stride, disp_q8, sad, nstereo);
     PCHK(launch_ok(c, "k_stereo_median"));
+  }
+  return PISLAM_OK;
+}
+
+// ---- pyramidal Lucas-Kanade tracking and match refinement ----------------------------------
+
+namespace {
+
+// nullptr, or what is wrong with the parameters and tables of a tracking call (host only).
+const char *lk_check_tables(const pislam_lk_params *p, const pislam_level *lv, int nlevels, const int32_t *scale_q16,
+                            int vstep, int rows) {
+  if (!p) return "null tracking parameters";
+  if (p->win_radius < 1 || p->win_radius > pt::LK_MAX_W) return "win_radius must be 1..7";
+  if (p->max_iters < 1 || p->max_iters > 32) return "max_iters must be 1..32";
+  if (p->eps_q8 < 0 || p->eps_q8 > 255) return "eps_q8 must be 0..255";
+  if (p->max_step_q8 < 1 || p->max_step_q8 > 4096) return "max_step_q8 must be 1..4096";
+  if (p->level_step < 1 || p->level_step > 15) return "level_step must be 1..15";
+  if (p->max_coarse < 0 || p->max_coarse > 15) return "max_coarse must be 0..15";
+  if (p->min_eig < 0 || p->min_eig > (1 << 20)) return "min_eig must be 0..2^20";
+  if (p->max_err < 0 || p->max_err > 8160) return "max_err must be 0..8160";
+  if (nlevels < 1 || nlevels > pt::LK_MAX_LEVELS) return "nlevels must be 1..16";
+  if (!lv || !scale_q16) return "null levels / scale_q16";
+  if (vstep < 1 || rows < 1) return "vstep and rows must be positive";
+  for (int l = 0; l < nlevels; l++) {
+    const pislam_level &L = lv[l];
+    if (L.width < 1 || L.height < 1 || L.col0 < 0 || L.row0 < 0 || L.col0 + L.width > 4096 || L.row0 + L.height > 4096)
+      return "level rectangles must be non-empty and fit 12-bit coordinates";
+    if (L.col0 + L.width > vstep || L.row0 + L.height > rows) return "a level rectangle lies outside [0, rows) x [0, vstep)";
+    if (scale_q16[l] < 1 || scale_q16[l] > (1 << 20)) return "scale_q16 must be 1..2^20";
+    const long long ex = ((long long)(L.width - 1) * scale_q16[l] + 32768) >> 16;
+    const long long ey = ((long long)(L.height - 1) * scale_q16[l] + 32768) >> 16;
+    if (ex > 65535 || ey > 65535) return "a level's mapped extent exceeds 65535";
+    for (int k = 0; k < l; k++) {
+      const pislam_level &K = lv[k];
+      if (L.col0 < K.col0 + K.width && K.col0 < L.col0 + L.width && L.row0 < K.row0 + K.height && K.row0 < L.row0 + L.height)
+        return "level rectangles overlap";
+    }
+  }
+  return nullptr;
+}
+
+struct LkRange {
+  const void *p;
+  size_t n;
+};
+bool lk_overlap(LkRange a, LkRange b) {
+  const uintptr_t pa = (uintptr_t)a.p, pb = (uintptr_t)b.p;
+  return a.p && b.p && a.n && b.n && pa < pb + b.n && pb < pa + a.n;
+}
+
+}  // namespace
+
+PISLAM_EXPORT int pislam_track_lk_batch(pislam_ctx *c, const pislam_lk_params *p, const pislam_level *levels, int nlevels,
+                                        const int32_t *scale_q16, const uint8_t *prev_pyr, const uint8_t *next_pyr,
+                                        int vstep, int rows, size_t pyramid_stride, const int32_t *pts_q8,
+                                        const uint32_t *counts, const int32_t *guess_q8, size_t stride, int batch,
+                                        int32_t *next_q8, uint32_t *status, uint32_t *err, uint32_t *ntracked) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (const char *bad = lk_check_tables(p, levels, nlevels, scale_q16, vstep, rows)) return fail(c, PISLAM_ERR_INVALID, bad);
+  if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
+  if (stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "stride too large");
+  if (batch == 0) return PISLAM_OK;
+  PCHK(device_ptrs(c, {prev_pyr, next_pyr, pts_q8, counts, next_q8, status, err}, "the tracker takes device pointers only"));
+  if (guess_q8 && !is_device_ptr(guess_q8)) return fail(c, PISLAM_ERR_INVALID, "guess_q8 must be a device pointer or null");
+  if (ntracked && !is_device_ptr(ntracked)) return fail(c, PISLAM_ERR_INVALID, "ntracked must be a device pointer or null");
+  {
+    const size_t B = (size_t)batch, pyr = (B - 1) * pyramid_stride + (size_t)rows * (size_t)vstep;
+    const size_t words = B * stride * sizeof(uint32_t);
+    const LkRange in[] = {{prev_pyr, pyr}, {next_pyr, pyr}, {pts_q8, 2 * words}, {counts, B * sizeof(uint32_t)},
+                          {guess_q8, 2 * words}};
+    const LkRange out[] = {{next_q8, 2 * words}, {status, words}, {err, words}, {ntracked, B * sizeof(uint32_t)}};
+    for (int o = 0; o < 4; o++) {
+      for (int i = 0; i < 5; i++) {
+        if (o == 0 && i == 4 && next_q8 == guess_q8) continue;          // each point reads its guess before it writes
+        if (lk_overlap(out[o], in[i])) return fail(c, PISLAM_ERR_INVALID, "an output overlaps an input");
+      }
+      for (int k = 0; k < o; k++)
+        if (lk_overlap(out[o], out[k])) return fail(c, PISLAM_ERR_INVALID, "two outputs overlap");
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  pt::LkArgs a{};
+  for (int l = 0; l < nlevels; l++)
+    a.lv[l] = pt::LkLevel{levels[l].col0, levels[l].row0, levels[l].width, levels[l].height, scale_q16[l]};
+  a.nlevels = nlevels, a.max_iters = p->max_iters, a.eps_q8 = p->eps_q8, a.max_step_q8 = p->max_step_q8;
+  a.level_step = p->level_step, a.max_coarse = p->max_coarse, a.min_eig = p->min_eig, a.max_err = p->max_err;
+  a.vstep = vstep, a.pyramid_stride = pyramid_stride, a.stride = stride;
+  for (int b0 = 0; b0 < batch; b0 += 65535) {                // (grid.y)
+    const int nb = std::min(batch - b0, 65535);
+    const size_t first = (size_t)b0 * stride;
+    if (stride > 0) {
+      a.prev = prev_pyr + (size_t)b0 * pyramid_stride, a.next = next_pyr + (size_t)b0 * pyramid_stride;
+      a.pts = pts_q8 + 2 * first, a.counts = counts + b0, a.guess = guess_q8 ? guess_q8 + 2 * first : nullptr;
+      a.next_q8 = next_q8 + 2 * first, a.status = status + first, a.err = err + first;
+      const dim3 grid = query_grid(c, stride, pt::LK_PPW, nb);
+      static_assert(pt::LK_MAX_W == pm::ST_MAX_W, "with_sad_radius covers 1..7");
+      with_sad_radius(p->win_radius, [&](auto w) {
+        hipLaunchKernelGGL(pt::k_track_lk<decltype(w)::value>, grid, dim3(pt::LK_THREADS), 0, c->stream, a);
+      });
+      PCHK(launch_ok(c, "k_track_lk"));
+    }
+    if (ntracked) {
+      hipLaunchKernelGGL(pt::k_lk_count, dim3((unsigned)nb), dim3(pt::LK_COUNT_THREADS), 0, c->stream, counts + b0, stride,
+                         status + first, ntracked + b0);
+      PCHK(launch_ok(c, "k_lk_count"));
+    }
   }
   return PISLAM_OK;
 }

@@ -17,7 +17,7 @@ import ctypes
 import numpy as np
 
 from . import capi
-from .capi import ClaheParams, Context, FrontendParams, Level, SelectParams, StereoParams, ptr
+from .capi import ClaheParams, Context, FrontendParams, Level, LkParams, SelectParams, StereoParams, ptr
 
 _default_ctx: Context | None = None
 
@@ -369,6 +369,131 @@ def matchStereoBatch(lkp, ldesc, lcounts, rkp, rdesc, rcounts, left_pyr, right_p
                                                 batch, *[ptr(t) for t in out], ptr(nstereo)),
               "pislam_match_stereo_batch")
     return (*out, nstereo)
+
+
+# ---- pyramidal Lucas-Kanade tracking and sub-pixel match refinement ----------
+def keypointsToQ8(kp):
+    """Keypoint words (encodeFast: x << 12 | y in the low 24 bits; numpy array or torch tensor of any shape) as
+    [..., 2] int32 (x, y) in Q8 stacked-pyramid coordinates, the pts_q8 of trackLKBatch."""
+    if isinstance(kp, np.ndarray):
+        k = kp.astype(np.int64)
+        return np.stack([((k >> 12) & 0xFFF) << 8, (k & 0xFFF) << 8], axis=-1).astype(np.int32)
+    import torch
+    return torch.stack([((kp >> 12) & 0xFFF) << 8, (kp & 0xFFF) << 8], dim=-1).to(torch.int32)
+
+
+def _lk_tables(levels, scale_q16):
+    lv, n, s, _ = _scaled_tables(levels, scale_q16, 0)
+    return lv, n, s
+
+
+def trackLKBatch(prev_pyr, next_pyr, pts_q8, counts, levels, scale_q16, *, guess_q8=None, win_radius=7, max_iters=10,
+                 eps_q8=8, max_step_q8=2048, level_step=3, max_coarse=2, min_eig=16, max_err=0, fb_max_q8=None,
+                 next_q8=None, status=None, err=None, ntracked=None, ctx: Context | None = None):
+    """Pyramidal Lucas-Kanade tracker (pislam_track_lk_batch; the contract is the comment in include/pislam_hip.h):
+    point i of pair b, pts_q8[b][i] = (x, y) in Q8 stacked-pyramid coordinates of prev_pyr[b], is followed into
+    next_pyr[b] (uint8 [batch][rows][vstep] device tensors of the same shape and stride) from guess_q8[b][i] (None:
+    from the point itself), through up to max_coarse levels level_step apart above the point's own and then on its
+    own level, with a (2 * win_radius + 1)^2 window.  scale_q16 as matchHammingScaledWindowBatch (None =
+    level_scales_q16(levels)).  Returns (next_q8, status, err, ntracked): int32 tensors [batch][stride][2],
+    [batch][stride] (code | iterations << 8; code 0 tracked, 1 no level or template at the border, 2 flat template,
+    3 left the level, 4 over max_err), [batch][stride] (the sum of |residual| in Q5, 0xffffffff without one) and
+    [batch].  Entries at and beyond counts[b] are not written.  Asynchronous on the ctx stream, no workspace.
+
+    fb_max_q8 (None: off) adds a forward-backward check: a second call with the pyramids exchanged follows next_q8 back
+    (no guess), and a fifth return value, a bool tensor [batch][stride], is true where both passes ended with code 0
+    and the round trip lands within fb_max_q8 of the start on both axes (entries beyond the counts are undefined).
+
+    The defaults min_eig = 16 and eps_q8 = 8 are guesses: nobody has measured them on real footage."""
+    import torch
+    ctx = ctx or default_context()
+    if prev_pyr.dim() != 3 or tuple(prev_pyr.shape) != tuple(next_pyr.shape) or prev_pyr.stride() != next_pyr.stride():
+        raise ValueError("prev_pyr and next_pyr must be [batch][rows][vstep] tensors of the same shape and stride")
+    if prev_pyr.dtype != torch.uint8 or next_pyr.dtype != torch.uint8 or prev_pyr.stride(2) != 1:
+        raise ValueError("pyramids must be uint8 with contiguous rows")
+    batch, rows, vstep = int(prev_pyr.shape[0]), int(prev_pyr.shape[1]), int(prev_pyr.stride(1))
+    if int(prev_pyr.shape[2]) > vstep:
+        raise ValueError("pyramid rows overlap")
+    if pts_q8.dtype != torch.int32 or pts_q8.dim() != 3 or int(pts_q8.shape[0]) != batch or int(pts_q8.shape[2]) != 2:
+        raise ValueError("pts_q8 must be an int32 tensor [batch][stride][2]")
+    stride = int(pts_q8.shape[1])
+    if guess_q8 is not None and (guess_q8.dtype != torch.int32 or tuple(guess_q8.shape) != (batch, stride, 2)):
+        raise ValueError("guess_q8 must be an int32 tensor [batch][stride][2]")
+    lv, n, s = _lk_tables(levels, scale_q16)
+    p = LkParams(int(win_radius), int(max_iters), int(eps_q8), int(max_step_q8), int(level_step), int(max_coarse),
+                 int(min_eig), int(max_err))
+    dev = pts_q8.device
+    pstride = int(prev_pyr.stride(0)) if batch else 0
+
+    def run(a, b, pts, guess, nq, st, er, nt):
+        nq = torch.empty((batch, stride, 2), dtype=torch.int32, device=dev) if nq is None else nq
+        st = torch.empty((batch, stride), dtype=torch.int32, device=dev) if st is None else st
+        er = torch.empty((batch, stride), dtype=torch.int32, device=dev) if er is None else er
+        nt = torch.empty((batch,), dtype=torch.int32, device=dev) if nt is None else nt
+        ctx.check(ctx.lib.pislam_track_lk_batch(ctx.h, ctypes.byref(p), lv, n, s, ptr(a), ptr(b), vstep, rows, pstride,
+                                                ptr(pts), ptr(counts), ptr(guess), stride, batch, ptr(nq), ptr(st),
+                                                ptr(er), ptr(nt)), "pislam_track_lk_batch")
+        return nq, st, er, nt
+
+    out = run(prev_pyr, next_pyr, pts_q8, guess_q8, next_q8, status, err, ntracked)
+    if fb_max_q8 is None:
+        return out
+    back, bst, _, _ = run(next_pyr, prev_pyr, out[0], None, None, None, None, None)
+    near = ((back - pts_q8).abs() <= int(fb_max_q8)).all(dim=-1)
+    return (*out, ((out[1] & 0xFF) == 0) & ((bst & 0xFF) == 0) & near)
+
+
+def refineMatchesBatch(prev_pyr, next_pyr, qkp, qcounts, tkp, idx, levels, scale_q16=None, *, sel=None, win_radius=7,
+                       max_iters=10, eps_q8=8, max_step_q8=2048, min_eig=16, max_err=0, ctx: Context | None = None):
+    """Sub-pixel refinement of descriptor matches: query keypoint i of pair b (qkp [batch][q_stride], a keypoint of
+    prev_pyr[b]) matched to train keypoint idx[b][i] (tkp [batch][t_stride], a keypoint of next_pyr[b]; idx as any
+    matcher returns it, negative = unmatched) is tracked on its own level only (trackLKBatch with max_coarse = 0)
+    from the train keypoint's position mapped to the query's level, u = floor((u_t * s_t + floor(s_q / 2)) / s_q) per
+    axis (the header's level mapping, here in torch int64).  sel = (sel_q, sel_t, nsel) of selectMatchesBatch keeps
+    only the selected matches.  Unmatched queries, and matches one of whose keypoints lies in no level, are given a
+    point in no level: their status is 1.  Returns (next_q8, status, err, ntracked) as trackLKBatch, next_q8 in the
+    stacked Q8 coordinates of the query's level.  The torch ops run on the current torch stream."""
+    import torch
+    batch, qs = (int(v) for v in qkp.shape)
+    dev = qkp.device
+    idx = idx.to(torch.int64)
+    if sel is not None:
+        sel_q, sel_t, nsel = sel
+        live = torch.arange(qs, device=dev)[None, :] < nsel.to(torch.int64)[:, None]
+        col = torch.where(live, sel_q.to(torch.int64), torch.full_like(idx, qs))       # dead slots go to a spare column
+        keep = torch.full((batch, qs + 1), -1, dtype=torch.int64, device=dev)
+        keep.scatter_(1, col, torch.where(live, sel_t.to(torch.int64), torch.full_like(idx, -1)))
+        idx = torch.where(keep[:, :qs] == idx, idx, torch.full_like(idx, -1))
+    matched = idx >= 0
+    tk = torch.gather(tkp.to(torch.int64), 1, idx.clamp(min=0, max=int(tkp.shape[1]) - 1))
+    qk = qkp.to(torch.int64)
+    lvn = [(int(t[0]), int(t[1]), int(t[2]), int(t[3]) if len(t) > 3 else 0) for t in levels]
+    sc = level_scales_q16(levels) if scale_q16 is None else ([int(scale_q16)] * len(lvn) if isinstance(
+        scale_q16, (int, np.integer)) else [int(v) for v in scale_q16])
+
+    def local(k):
+        """Level-local Q8 (u, v), scale and origin of keypoint words; scale 0 in no level."""
+        x, y = (k >> 12) & 0xFFF, k & 0xFFF
+        u, v, s, c0, r0 = (torch.zeros_like(k) for _ in range(5))
+        for (w, h, row0, col0), sl in zip(lvn, sc):
+            m = (x >= col0) & (x < col0 + w) & (y >= row0) & (y < row0 + h)
+            u, v = torch.where(m, (x - col0) << 8, u), torch.where(m, (y - row0) << 8, v)
+            s = torch.where(m, torch.full_like(k, sl), s)
+            c0, r0 = torch.where(m, torch.full_like(k, col0), c0), torch.where(m, torch.full_like(k, row0), r0)
+        return u, v, s, c0, r0
+
+    _, _, sq, qc0, qr0 = local(qk)
+    ut, vt, st, _, _ = local(tk)
+    ok = matched & (sq > 0) & (st > 0)
+    sq1 = sq.clamp(min=1)
+    gx = torch.div(ut * st + sq1 // 2, sq1, rounding_mode="floor") + (qc0 << 8)
+    gy = torch.div(vt * st + sq1 // 2, sq1, rounding_mode="floor") + (qr0 << 8)
+    pts = keypointsToQ8(qk)
+    pts = torch.where(ok[..., None], pts, torch.full_like(pts, -256))
+    guess = torch.where(ok[..., None], torch.stack([gx, gy], dim=-1).to(torch.int32), pts).contiguous()
+    return trackLKBatch(prev_pyr, next_pyr, pts.contiguous(), qcounts, levels, sc, guess_q8=guess, win_radius=win_radius,
+                        max_iters=max_iters, eps_q8=eps_q8, max_step_q8=max_step_q8, level_step=1, max_coarse=0,
+                        min_eig=min_eig, max_err=max_err, ctx=ctx)
 
 
 # ---- bag of words: vocabulary tree, quantisation, vector, word-guided matching ----------
