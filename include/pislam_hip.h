@@ -412,8 +412,9 @@ unsigned pislam_frontend_last_path(const pislam_ctx *ctx);
 #define PISLAM_COUNT_INVALID 0xffffffffu
 
 /* Host only — no device, no allocation, no launch: build the strip plan (and the bucket selection plan) a batch call with
- * these parameters would run and check the invariants the kernels rely on.  `options`: "key=value,key=value" with
- * pislam_ctx_set_option keys (NULL / "": defaults); num_cus <= 0: 256; lanes_in_flight: 1, or the depth of the pipeline the
+ * these parameters would run, with the planner the call itself uses (pislam_amd/csrc/pislam_frontend_plan.h), and check the
+ * invariants the kernels rely on.  `options`: "key=value,key=value" with pislam_ctx_set_option keys (NULL / "": defaults;
+ * own_stream is refused: it needs a device); num_cus <= 0: 256; lanes_in_flight: 1, or the depth of the pipeline the
  * call would be a lane of.  summary: [0] plan entries, [1] strips, [2] runs, [3] staging slots per pyramid, [4] strips per
  * run, [5] / [6] LDS bytes of the plain / aliased layout, [7] units of the bucket selection pass.  Returns
  * PISLAM_ERR_INVALID (message in `err`) when the parameters are refused or the staged pipeline would take the call. */

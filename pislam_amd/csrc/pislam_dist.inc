@@ -155,7 +155,7 @@ PISLAM_EXPORT int pislam_dist_finalize(pislam_ctx *c) {
 PISLAM_EXPORT int pislam_dist_init(pislam_ctx *c, const uint8_t id[PISLAM_DIST_ID_BYTES], int rank, int world) {
   if (!c) return PISLAM_ERR_INVALID;
   if (world < 1 || rank < 0 || rank >= world) return fail(c, PISLAM_ERR_INVALID, "bad rank / world");
-  if ((world > 1 || c->opt_dist_rccl_single) && !id) return fail(c, PISLAM_ERR_INVALID, "null unique id");
+  if ((world > 1 || c->opt.dist_rccl_single) && !id) return fail(c, PISLAM_ERR_INVALID, "null unique id");
   if (c->dist) PCHK(pislam_dist_finalize(c));
   HIPCHK(c, hipSetDevice(c->device));
   pislam_dist_state *d = new pislam_dist_state();
@@ -174,7 +174,7 @@ PISLAM_EXPORT int pislam_dist_init(pislam_ctx *c, const uint8_t id[PISLAM_DIST_I
   }
   // degrades to a single GPU without touching RCCL (SURVEY §8e); the test hook "dist_rccl_single" keeps the
   // RCCL path (a 1-rank communicator) so that it can be exercised on a 1-GPU box
-  if (world == 1 && !c->opt_dist_rccl_single) return PISLAM_OK;
+  if (world == 1 && !c->opt.dist_rccl_single) return PISLAM_OK;
   RcclApi *api = rccl_api();
   if (!api) {
     (void)pislam_dist_finalize(c);

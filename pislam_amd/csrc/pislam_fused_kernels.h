@@ -26,6 +26,7 @@
 // Deterministic: no result depends on the order of atomics.
 #pragma once
 #include "pislam_dev.h"
+#include "pislam_frontend_plan.h"   // FusedLevel, FusedParams, SelectPlan and the sizes the kernels share with the host planner
 
 // development switches (tools/ab_build.sh -D...): the defaults are the product
 #ifndef PISLAM_FRAME_SLEEP
@@ -36,9 +37,6 @@
 #endif
 #ifndef PISLAM_DIAG
 #define PISLAM_DIAG 1         // pretest also requires two adjacent DIAGONAL ring points (3/7/11/15) of one polarity
-#endif
-#ifndef PISLAM_ORB_PITCH_DW
-#define PISLAM_ORB_PITCH_DW 12   // dwords per ORB patch row in LDS (12 = round 1-5: 48-byte rows skewed by a dword per 8 rows)
 #endif
 
 namespace pf {
@@ -53,70 +51,7 @@ typedef __attribute__((address_space(3))) uint32_t lds_u32;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // plain clang vector (uint4 is a class)
 typedef __attribute__((address_space(3))) u32x4 lds_u4;
 
-constexpr int MAX_ORDER = 160;              // runs per pyramid the launch-order table holds
-constexpr int MAX_LEVELS = 24;              // plan entries: levels, wide ones cut into x-tiles (see FusedLevel::gn)
-constexpr int WAVES = 4;               // waves per strip workgroup
-constexpr int NT = WAVES * 64;         // threads per strip workgroup
-constexpr int QCAP_G = 128;            // 4-pixel groups that passed the SAD prefilter (< 64 before a <= 64 push)
-constexpr int QCAP_F = 192;            // FAST candidates (< 64 before a <= 128 half-push)
-constexpr int QCAP = QCAP_G + QCAP_F;  // dwords of private queue space per wave
-constexpr int QH_SHARED = 1024;        // workgroup-shared queue of corners awaiting their Harris score (a 28-row
-                                       // strip of a textured photo holds up to ~900: the reference's demo image)
-constexpr int QN_SHARED = 512;         // plain layout only: queue of pixels with a non-zero score (NMS candidates)
-constexpr int QS_SHARED = 256;         // survivors of one strip awaiting their rank
-constexpr int SHARED_Q = QH_SHARED + QN_SHARED;
-constexpr int NMS_SCRATCH = 3 * QS_SHARED;   // dwords: survivors, their keys (then ranks), bucket keep flags (in the idle per-wave queues)
-static_assert(NMS_SCRATCH <= WAVES * QCAP, "NMS scratch must fit the per-wave queue area");
-static_assert(QS_SHARED <= NT, "one survivor per thread (ranks are held in a register across a barrier)");
 constexpr uint32_t STRIP_DESCRIBED = 0x80000000u;   // strip_count bit 31: the strip wrote its keypoints' descriptors
-
-struct FusedLevel {
-  int w, h;          // level size
-  int row0, col0;    // position in the stacked pyramid
-  int R;             // strip height (even)
-  int nstrips;       // strips in this level
-  int strip0;        // index of the level's first strip within the pyramid
-  int slot0;         // staging slot (in keypoints) of the level's first strip
-  int nbx;           // 2x2 blocks per block-row
-  int xend;          // one past the last classified column (Fast.h:61,149)
-  int pitch;         // LDS SCORE tile pitch in bytes (multiple of 16): the score tile spans the full level width
-  int tpitch;        // LDS IMAGE tile pitch in bytes (multiple of 16) = classified columns + halo
-  int nruns, run0;   // runs (= workgroups) of this level: run_len consecutive strips each
-  int apad;          // ALIAS layout: bytes between the per-wave queues and the image tile (multiple of 16)
-  int qh;            // ALIAS layout: entries of the shared corner queue (>= QH_SHARED: the plan hands the LDS
-                     // a level's narrower tiles leave under the residency budget to its queue)
-  int tbytes;        // plain layout: bytes reserved for the image tile = max((R+10)*tpitch, the scan
-                     // fallbacks' survivor / per-cell buffers — larger only with narrow x-tiles)
-  uint32_t vpr_recip; // ceil(2^32 / (tpitch/16)): row = umulhi(i, vpr_recip) for a vector index i < 2^16
-  uint32_t tp_recip;  // ceil(2^32 / tpitch): tile row of a byte offset k < 2^16 into the tile = umulhi(k, tp_recip)
-  // A plan entry is a whole pyramid level, or one X-TILE of a wide level: a column range handled by its own
-  // workgroups like a level of its own (w / col0 describe the tile plus a halo of real image columns in place
-  // of the border), so that the LDS footprint — and with it the number of resident workgroups — does not grow
-  // with the level width.  Tiles classify and score a few columns beyond the blocks they own (the NMS of a
-  // boundary block reads its neighbours' scores), emit only the blocks whose origin lies in [ex0, ex1), and
-  // k_gather_orb merges the tiles' per-strip lists back into the level's block-raster order.
-  int ex0, ex1;      // block origins (entry-relative x) this entry emits: [ex0, ex1)   (whole level: [B, w-B))
-  int xscore;        // entry-relative x of the level's w-B: columns at / beyond it keep 0xff (Fast.h:172)
-  int gfirst, gn;    // the entries gfirst .. gfirst+gn-1 are the tiles of this entry's level (same R, nstrips)
-};
-
-struct FusedParams {
-  int nlevels, strips_per_pyr, slots_per_pyr;
-  int runs_per_pyr, run_len;   // a workgroup walks run_len consecutive strips of one level (see k_fused_strips)
-  int vstep, rows, border, thr;
-  int32_t hthr;
-  int batch;
-  int lbs, limit;    // fastExtract logBucketSize (0 = none; fused path: 2..5) and bucketLimit
-  int words;         // orbCompute words (descriptor dwords per keypoint)
-  int orb_in_strip;  // ALIAS + 16-byte-aligned kernels: strips describe their own keypoints (strip_body phase E)
-  int order_n;       // > 0: the launch order of a pyramid's runs is order[] (longest first)
-  int dump_score;    // debug: also write the score tile to the HBM score map
-  int ablate;        // profiling only: bit0 stop after staging, bit1 pretest only, bit2 no Harris, bit3 no NMS
-  FusedLevel lv[MAX_LEVELS];
-  // Runs of one pyramid in launch order, longest (estimated) first, so that the short ones fill the tail of
-  // the launch (longest-processing-time-first list scheduling); plans with more runs keep entry order.
-  uint32_t order[MAX_ORDER];                       // entry << 16 | run inside the entry (dwords: scalar loads)
-};
 
 // Workgroup barrier that orders LDS traffic only (s_waitcnt lgkmcnt(0); s_barrier).  __syncthreads()
 // also waits for every outstanding GLOBAL load (vmcnt(0)), which would serialise the next strip's
@@ -173,17 +108,6 @@ __device__ __attribute__((noinline)) void harris_overflow(lds_u8 *tile, lds_u8 *
 //   (Orb.h:310-387); the 256 BRIEF tests (Brief.h:52) read the LDS patch through the precomputed offset
 //   table g_brief_ofs, eight tests per lane = one descriptor byte per lane.
 // ===========================================================================
-constexpr int OWAVES = 4;                           // waves per k_gather_orb workgroup
-// One 48-byte window per patch row.  Default layout (PISLAM_ORB_PITCH_DW 12): rows 12 dwords apart, skewed by one dword per
-// 8 rows — the 9 row reads of the moments (lane = row) are conflict-free (a pitch of 12 dwords alone puts rows r, r+8, r+16,
-// r+24 on the same banks), and so are the three dword stores that park a 12-byte piece (lanes = (row, piece): 12 row + 3
-// piece + i hits 32 different banks for the 8 rows x 4 pieces of a half-wave).  With the 16-byte chunks of rounds 2-5 the
-// four stores of a chunk fell on 8 banks (4-way: 5.6 M of the kernel's 13.8 M conflict cycles per launch, 1.5 M now); rows 13
-// dwords apart (PISLAM_ORB_PITCH_DW 13, round 6) cured that at the price of 1 KB more LDS per workgroup and were not kept.
-constexpr int ORB_PITCH = 4 * PISLAM_ORB_PITCH_DW;
-__host__ __device__ constexpr int orb_row_ofs(int r) { return PISLAM_ORB_PITCH_DW == 12 ? r * 48 + 4 * (r >> 3) : r * ORB_PITCH; }
-// 31 rows (the idle lane's row 31 reads harmless bytes of whatever follows) + slack for the byte shift, a multiple of 16
-constexpr int ORB_PATCH_BYTES = PISLAM_ORB_PITCH_DW == 12 ? 32 * 48 + 32 : (31 * ORB_PITCH + 4 + 15) / 16 * 16;
 
 // Sums over each 32-lane half of the wave, results in every lane of that half: two values at once.  DPP row shifts
 // (zero fill) leave each 16-lane row's sum in its last lane, row_bcast:15 folds row 0 into row 1 and
@@ -1650,27 +1574,6 @@ __global__ __launch_bounds__(256) void k_gather(const FusedParams P,
 //   bucket boundary (origins are even offsets from B, 2^lbs is even).  Packed words compare alike in stacked and
 //   level-relative coordinates (the same offsets are added to every word of a level).
 // ===========================================================================
-struct SelectPlan {
-  int nlevels, lbs, limit, border;
-  int units_per_pyr, uslots_per_pyr;
-  int row0[16], col0[16], h[16];      // the level (not its tiles)
-  int g0[16], gn[16];                 // its plan entries in the strip plan
-  int unit0[16], nunits[16];          // its units (cell rows)
-  int cap[16], uslot0[16];            // slots per unit (buckets x limit), first slot of the level
-  int nb_max;                         // most buckets of any level (the dense path's LDS counters: 2 x nb_max dwords per wave)
-};
-// (k_bucket_select takes FusedParams + SelectPlan + four pointers by value: the kernel-argument segment holds 4 KiB)
-static_assert(sizeof(FusedParams) + sizeof(SelectPlan) + 5 * sizeof(void *) <= 4096, "k_bucket_select's arguments exceed the 4 KiB kernarg segment");
-constexpr int SEL_WAVES = 4;
-constexpr int SEL_NB = 1024;                         // buckets per cell row the dense path's LDS counters hold (the host checks)
-// The unit table (host-built, one record of SEL_REC dwords per unit = (level, cell row)): everything the fast path needs to
-// know about a unit arrives with ONE scalar load — until round 5 a wave found its level by a loop of dependent scalar
-// loads over the plan, and the strips overlapping its rows by two software divisions per x-tile with more plan loads
-// in between: the kernel is a single round of resident waves, its duration IS that chain.
-//   [0] lists overlapping the unit (0xffffffff: more than SEL_ML: the generic path), [1] level, [2] cell row,
-//   [3] first output slot (uslot0 + cell row * cap), [4] row0 + B, [5] col0 + B (stacked coordinates of the level's first
-//   block origin), [8 ..] staging slot of list j, [16 ..] strip-count index of list j.
-constexpr int SEL_REC = 24, SEL_ML = 6;
 __global__ __launch_bounds__(64 * SEL_WAVES) void k_bucket_select(const FusedParams F, const SelectPlan Q,
                                                                    const uint32_t *__restrict__ stage_kp,
                                                                    const uint32_t *__restrict__ strip_count,
@@ -1829,19 +1732,6 @@ __global__ __launch_bounds__(64 * SEL_WAVES) void k_bucket_select(const FusedPar
     }
   });
   if (lane == 0) ucount[(size_t)pyr * Q.units_per_pyr + u] = total;
-}
-
-// Small shared state of the gather + ORB role, carved from the FRONT of the dynamic LDS (not static: the strip
-// role's 5-workgroups-per-CU budget has no room for another 300 static bytes).
-struct OrbShared {
-  uint32_t wsum[4];
-  uint32_t carry, ntodo, flag, pad;
-  uint8_t rtab[256];                                // vrecpe estimate table (256 threads: one entry each)
-};
-__host__ __device__ constexpr size_t orb_lds_bytes(int strips_per_pyr, size_t per_max) {
-  return sizeof(OrbShared) + (size_t)OWAVES * 2 * ORB_PATCH_BYTES + sizeof(uint32_t) * (((size_t)strips_per_pyr + 1 + 3) & ~(size_t)3) +
-         sizeof(uint32_t) * (((size_t)strips_per_pyr + 3) & ~(size_t)3) +   // where each strip's list starts in the staging buffer
-         sizeof(uint32_t) * 2 * per_max;            // keypoints to describe here and their final positions
 }
 
 // The gather + ORB role of a workgroup: chunk `ch` of `nch` of pyramid `pyr` (see k_gather_orb).
@@ -2051,7 +1941,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void k
 // a wait timed out (only the host clears it).  `hflag`: the host-mapped copy of the sticky flag.
 // `test`: bit 0 = the first strip workgroup skips its release (forces the timeout: tests), bits 8.. = log2 of the poll limit.
 // ===========================================================================
-constexpr int FRAME_SYNC_PYR = 8, FRAME_SYNC_DONE = 8, FRAME_SYNC_POISON = 9, FRAME_SYNC_WORDS = 12;
 constexpr uint32_t COUNT_INVALID = 0xffffffffu;     // == PISLAM_COUNT_INVALID
 __global__ __launch_bounds__(NT) void k_frame(const FusedParams P, const uint8_t *__restrict__ pyramids, size_t pyr_stride,
                                               uint32_t *__restrict__ stage_kp, uint32_t *__restrict__ strip_count,

@@ -63,6 +63,9 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 
 #define PISLAM_EXPORT extern "C" __attribute__((visibility("default")))
 
+// the front end's host half (pislam_frontend_plan.h, included by pislam_fused_kernels.h)
+using fp::cdiv, fp::frame_max_batch, fp::FrontendPlan, fp::LDS_CAP, fp::LDS_OPT_IN;
+
 namespace {
 
 struct DevBuf {
@@ -106,6 +109,7 @@ struct pislam_ctx {
   hipStream_t own_stream = nullptr;    // option "own_stream": a non-blocking stream created and destroyed by the context
   pislam_dist_state *dist = nullptr;   // multi-GPU state (pislam_dist_init), nullptr for a single GPU
   std::string err;
+  fp::Options opt;                   // every integer option (pislam_ctx_set_option), the device's CUs, the pipeline depth: what the planner reads
   // staging for host-pointer calls
   DevBuf s_img, s_out, s_pts, s_desc, s_misc, s_rots, s_tmp;
   // compaction scratch (shared by extract and the batch pipeline)
@@ -138,40 +142,12 @@ struct pislam_ctx {
   uint32_t *frame_flag_dev = nullptr;
   bool frame_disabled = false;       // a timeout was seen: the context takes the three-launch path from then on
   unsigned long long frame_timeouts = 0;   // (counted into workspace_generation: graphs holding a k_frame node are dropped)
-  int opt_frame_test = 0;            // test hook: bit 0 = one strip workgroup skips its release, bits 8.. = log2 poll limit
   // pyramid build: all reductions in one launch (pp::k_bilinear_chain) — band counters + [done, sticky fault]; the host-mapped
   // fault word is frame_flag[1]
   DevBuf w_chain;
   size_t chain_words = 0;            // counters the last build laid out (a different layout starts from zeros)
   bool chain_disabled = false;
-  int opt_build_chain = 0;           // 1: pislam_pyramid_build_batch runs levels 1.. as ONE launch (pp::k_bilinear_chain); 0 (default): one
-                                     // launch per level — measured faster: 150 against 166 us per 64 720p frames (docs/experiments.md)
-  int num_cus = 0;
-  int opt_pipeline = 0;      // 0 auto, 1 staged (one launch group per level), 2 fused strips
-  int opt_dump_score = 0;    // fused pipeline: also materialise the score map (parity hook)
-  int opt_strip_rows = 0;    // fused pipeline: strip height override (0 = heuristic)
-  int opt_ablate = 0;        // profiling only: skip phases of the fused kernel (results invalid)
-  int opt_bucket_round_up = 0;  // profiling: bucket mode always rounds the strip height up to whole bucket rows (round-2 rule)
-  int opt_orb_chunks = 0;    // fused pipeline: workgroups per pyramid in k_gather_orb (0 = heuristic)
   uint32_t last_strips = 0;  // strips of the last fused batch call (pislam_frontend_last_stats)
-  int opt_repeat_strips = 1; // profiling: launch the strip kernel n times inside the stage-0 event bracket
-  int opt_alias = 1;         // fused pipeline: score tile laid over the dead image rows (0 = separate tiles)
-  int opt_run_len = 0;       // fused pipeline: strips per workgroup run (0 = default, 1 = independent strips)
-  int lanes_in_flight = 1;   // > 1: this context is a lane of a pislam_pipeline of that depth (other batches' kernels share the GPU)
-  int opt_lds_pad = 0;       // profiling only: extra dynamic LDS bytes per strip workgroup
-  int opt_wgs_per_cu = 0;    // fused pipeline: if > 0, size strip heights for this many workgroups per CU
-  int opt_strip_px = 16384;  // profiling: pixels per strip the height heuristic aims at
-  int opt_strip_rows_max = 0;    // profiling: upper bound of the heuristic strip height (0 = rule in build_fused_plan)
-  int opt_run_order = 1;     // fused pipeline: launch a pyramid's runs longest first (0: in entry order)
-  int opt_tile_cols = 0;     // fused pipeline: levels with more classified columns are cut into x-tiles (0 = 704, < 0 = never)
-  int opt_bucket_select = 1; // fused pipeline, buckets: 1 = strips as without buckets + pf::k_bucket_select (default), 0 = the strips select (round 1-3)
-  int opt_frame = 1;         // fused pipeline: small batches run as ONE launch (pf::k_frame): 1 = batches of 1 or 2 pyramids, n = up to n (<= 8), 0 = never
-  int opt_orb_in_strip = 0;  // fused pipeline: 1 = strips describe their own keypoints (measured slower: DESIGN.md §8), 0 = k_gather_orb describes all
-  int opt_match_mfma = 1;         // matcher on the matrix cores (0: the VALU popcount kernel)
-  int opt_warp_direct = 0;        // mesh warp: 1 = every tile takes the direct path (taps from global memory), 0 = by the tile plan
-  int opt_clahe_combine = 1;      // CLAHE table kernel: 1 = equal bytes of a lane's dword share one LDS atomic, 0 = one atomic per pixel
-  int opt_clahe_lut_global = 0;   // CLAHE apply kernel: 1 = the four tables are read from global memory per pixel, 0 = staged in LDS
-  int opt_dist_rccl_single = 0;   // test hook: pislam_dist_init(world = 1) still creates a (1-rank) RCCL communicator
   int last_pipeline = 0;
   unsigned last_path = 0;    // PISLAM_PATH_* of the last batch call
   size_t score_bytes_valid = 0;   // bytes of w_score known to be in a consistent (zero-border) state
@@ -185,11 +161,8 @@ struct pislam_ctx {
   // back on the context stream, the overflow pass + gather/ORB kernel of sub-batch i on `aux_stream` under the
   // strip kernel of sub-batch i+1 (fork / join with events: one call, one context).  A call being captured into a
   // hipGraph runs its sub-batches in order on the context stream instead (run_fused).
-  static constexpr int MAX_SUB = 16;
-  int opt_sub_batches = 1;             // 1 = one launch group (default), n = n sub-batches, 0 = by bytes per sub-batch
-  int opt_sub_mb = 0;                  // auto rule: target MiB of pyramids per sub-batch (0 = default)
   hipStream_t aux_stream = nullptr;    // created on first use (non-blocking)
-  hipEvent_t ev_sub[MAX_SUB] = {};     // strips of sub-batch i done (context stream -> aux stream)
+  hipEvent_t ev_sub[fp::MAX_SUB] = {};     // strips of sub-batch i done (context stream -> aux stream)
   hipEvent_t ev_join = nullptr;        // aux stream -> context stream at the end of the call
   int ovf_nsub = 0;                    // layout of w_ovf the last call / reserve established: lists, dwords per list
   size_t ovf_stride = 0;
@@ -282,7 +255,6 @@ int launch_ok(pislam_ctx *c, const char *what) {
   return PISLAM_OK;
 }
 
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // ---- the in-grid hand-overs' safety net (pf::k_frame, pp::k_bilinear_chain) --------------------------------------------
 // Both kernels contain workgroups that WAIT for other workgroups of the same grid; the waits are bounded, and a workgroup
@@ -496,8 +468,8 @@ PISLAM_EXPORT int pislam_ctx_create(int device, pislam_ctx **out) {
   CREATE_CHK(hipSetDevice(device));
   pislam_ctx *c = new pislam_ctx();
   c->device = device;
-  if (hipDeviceGetAttribute(&c->num_cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || c->num_cus <= 0)
-    c->num_cus = 256;
+  if (hipDeviceGetAttribute(&c->opt.num_cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || c->opt.num_cus <= 0)
+    c->opt.num_cus = 256;
   for (auto &e : c->ev) {
     hipError_t r = hipEventCreate(&e);
     if (r != hipSuccess) {
@@ -581,74 +553,20 @@ int use_own_stream(pislam_ctx *c, int mode) {
 }
 }  // namespace
 
-namespace {
-// The options that are one int member of the context: accepted range [lo, hi] with the message of a value outside it
-// (no message: every value is accepted), then what is stored (no normaliser: the value itself).
-struct OptionDef {
-  const char *key;
-  int pislam_ctx::*member;
-  int lo, hi;
-  const char *range_error;
-  int (*stored)(int);
-};
-int as_flag(int v) { return v != 0; }
-int at_least_0(int v) { return std::max(0, v); }
-const OptionDef OPTIONS[] = {
-    {"pipeline", &pislam_ctx::opt_pipeline, 0, 2, "pipeline must be 0 (auto), 1 (staged) or 2 (fused)", nullptr},
-    {"dump_score", &pislam_ctx::opt_dump_score, 0, 0, nullptr, as_flag},
-    {"repeat_strips", &pislam_ctx::opt_repeat_strips, 1, 64, "repeat_strips must be 1..64", nullptr},
-    {"alias", &pislam_ctx::opt_alias, 0, 0, nullptr, as_flag},
-    {"run_len", &pislam_ctx::opt_run_len, 0, 64, "run_len must be 0 (default) .. 64", nullptr},
-    {"lds_pad", &pislam_ctx::opt_lds_pad, 0, 0, nullptr, at_least_0},
-    {"wgs_per_cu", &pislam_ctx::opt_wgs_per_cu, 0, 8, "wgs_per_cu must be 0..8", nullptr},
-    {"match_mfma", &pislam_ctx::opt_match_mfma, 0, 0, nullptr, as_flag},
-    {"warp_direct", &pislam_ctx::opt_warp_direct, 0, 1, "warp_direct must be 0 or 1", nullptr},
-    {"clahe_combine", &pislam_ctx::opt_clahe_combine, 0, 1, "clahe_combine must be 0 or 1", nullptr},
-    {"clahe_lut_global", &pislam_ctx::opt_clahe_lut_global, 0, 1, "clahe_lut_global must be 0 or 1", nullptr},
-    {"run_order", &pislam_ctx::opt_run_order, 0, 0, nullptr, as_flag},
-    {"strip_px", &pislam_ctx::opt_strip_px, 0, 0, nullptr, [](int v) { return std::max(4096, v); }},
-    {"strip_rows_max", &pislam_ctx::opt_strip_rows_max, 0, 0, nullptr, [](int v) { return v <= 0 ? 0 : std::max(16, std::min(64, v & ~1)); }},
-    // 0: never one launch; 1 (default): batches of 1 or 2 pyramids; n = 2..8: batches of up to n
-    {"frame", &pislam_ctx::opt_frame, 0, 8, "frame must be 0..8", nullptr},
-    // test hook of the one-launch path's bounded wait (see pf::k_frame `test`)
-    {"frame_test", &pislam_ctx::opt_frame_test, 0, 0, nullptr, nullptr},
-    // pyramid build: 1 = levels 1.. in ONE launch (pp::k_bilinear_chain), 0 (default) one launch per level
-    {"build_chain", &pislam_ctx::opt_build_chain, 0, 0, nullptr, as_flag},
-    {"orb_in_strip", &pislam_ctx::opt_orb_in_strip, 0, 0, nullptr, as_flag},
-    {"bucket_select", &pislam_ctx::opt_bucket_select, 0, 0, nullptr, as_flag},
-    {"dist_rccl_single", &pislam_ctx::opt_dist_rccl_single, 0, 0, nullptr, as_flag},
-    {"bucket_round_up", &pislam_ctx::opt_bucket_round_up, 0, 0, nullptr, as_flag},
-    {"orb_chunks", &pislam_ctx::opt_orb_chunks, 0, 1024, "orb_chunks must be 0..1024", nullptr},
-    {"sub_batches", &pislam_ctx::opt_sub_batches, 0, pislam_ctx::MAX_SUB, "sub_batches must be 0 (auto) .. 16", nullptr},
-    {"sub_mb", &pislam_ctx::opt_sub_mb, 0, 0, nullptr, at_least_0},
-    {"ablate", &pislam_ctx::opt_ablate, 0, 0, nullptr, nullptr},
-};
-}  // namespace
-
 PISLAM_EXPORT int pislam_ctx_set_option(pislam_ctx *c, const char *key, int value) {
   if (!c || !key) return PISLAM_ERR_INVALID;
-  for (const OptionDef &o : OPTIONS) {
-    if (strcmp(key, o.key)) continue;
-    if (o.range_error && (value < o.lo || value > o.hi)) return fail(c, PISLAM_ERR_INVALID, o.range_error);
-    c->*o.member = o.stored ? o.stored(value) : value;
-    return PISLAM_OK;
-  }
-  // the options with a side effect, or a range that is no interval
+  // the two options with a side effect on the context; every other one is an int of fp::Options
   if (!strcmp(key, "own_stream")) {
     if (value < 0 || value > 2) return fail(c, PISLAM_ERR_INVALID, "own_stream must be 0, 1 (default flags) or 2 (non-blocking)");
     return use_own_stream(c, value);
-  } else if (!strcmp(key, "tile_cols")) {
-    if (value > 0 && value < 64) return fail(c, PISLAM_ERR_INVALID, "tile_cols must be 0 (default), < 0 (never) or >= 64");
-    c->opt_tile_cols = value;
-  } else if (!strcmp(key, "frame_rearm")) {  // 1: take the one-launch paths again after a reported timeout (tests)
-    if (value) c->frame_disabled = c->chain_disabled = false;
-  } else if (!strcmp(key, "strip_rows")) {
-    if (value < 0 || value > 64 || (value & 1)) return fail(c, PISLAM_ERR_INVALID, "strip_rows must be even, 0..64");
-    c->opt_strip_rows = value;
-  } else {
-    return fail(c, PISLAM_ERR_INVALID, "unknown option");
   }
-  return PISLAM_OK;
+  if (!strcmp(key, "frame_rearm")) {  // 1: take the one-launch paths again after a reported timeout (tests)
+    if (value) c->frame_disabled = c->chain_disabled = false;
+    return PISLAM_OK;
+  }
+  const char *refusal = nullptr;
+  if (!fp::set_option(c->opt, key, value, &refusal)) refusal = "unknown option";
+  return refusal ? fail(c, PISLAM_ERR_INVALID, refusal) : PISLAM_OK;
 }
 
 PISLAM_EXPORT int pislam_ctx_synchronize(pislam_ctx *c) {
@@ -1017,7 +935,7 @@ int build_reductions(pislam_ctx *c, const pp::BuildPlan &P, int nlevels, int bat
     }
     PCHK(ensure_fault_flag(c));
     hipLaunchKernelGGL(pp::k_bilinear_chain, dim3(P.chain_grid), dim3(256), 0, c->stream, P.C, pyramids, pyramid_stride,
-                       c->w_chain.as<uint32_t>(), c->frame_flag_dev + 1, (uint32_t)c->opt_frame_test);
+                       c->w_chain.as<uint32_t>(), c->frame_flag_dev + 1, (uint32_t)c->opt.frame_test);
     return launch_ok(c, "k_bilinear_chain");
   }
   for (int l = 0; l + 1 < nlevels; l++) {
@@ -1044,7 +962,7 @@ PISLAM_EXPORT int pislam_pyramid_build_batch(pislam_ctx *c, int nlevels, const i
   HIPCHK(c, hipSetDevice(c->device));
   PCHK(check_frame_poison(c));
   const pp::BuildPlan P = pp::make_build_plan(nlevels, steps, levels, frame_vstep, frame_stride, batch, vstep, rows, pyramid_stride,
-                                              flags, (unsigned)((uintptr_t)pyramids % 16), c->opt_build_chain && !c->chain_disabled);
+                                              flags, (unsigned)((uintptr_t)pyramids % 16), c->opt.build_chain && !c->chain_disabled);
   if (P.refusal) return fail(c, PISLAM_ERR_INVALID, P.refusal);
   if (P.margins)
     PCHK(build_margins(c, P.Z, batch, pyramids, pyramid_stride, (flags & PISLAM_BUILD_MARGINS_CLEAN) != 0));
@@ -1059,358 +977,8 @@ PISLAM_EXPORT int pislam_pyramid_build_batch(pislam_ctx *c, int nlevels, const i
 namespace {
 int check_params(pislam_ctx *c, const pislam_frontend_params *p, const pislam_level *lv, int batch) {
   if (!c) return PISLAM_ERR_INVALID;
-  if (!p || !lv) return fail(c, PISLAM_ERR_INVALID, "null params");
-  if (batch <= 0) return fail(c, PISLAM_ERR_INVALID, "batch must be positive");
-  if (p->vstep <= 0 || p->rows <= 0 || p->nlevels < 1 || p->nlevels > 16)
-    return fail(c, PISLAM_ERR_INVALID, "bad vstep/rows/nlevels");
-  if (p->border < 16) return fail(c, PISLAM_ERR_INVALID, "ORB needs border >= 16 (Fast.h:46-49)");
-  if (p->words < 1 || p->words > 8) return fail(c, PISLAM_ERR_INVALID, "words must be 1..8");
-  if (p->log_bucket_size < 0 || p->log_bucket_size > 8 || p->bucket_limit < 1 || p->bucket_limit > 64)
-    return fail(c, PISLAM_ERR_INVALID, "bad bucket parameters");
-  if (p->max_keypoints < 1) return fail(c, PISLAM_ERR_INVALID, "max_keypoints must be positive");
-  for (int l = 0; l < p->nlevels; l++) {
-    if (lv[l].width <= 0 || lv[l].height <= 0 || lv[l].row0 < 0 || lv[l].col0 < 0 ||
-        lv[l].col0 + lv[l].width > p->vstep || lv[l].row0 + lv[l].height > p->rows)
-      return fail(c, PISLAM_ERR_INVALID, "level does not fit the pyramid buffer");
-    if (lv[l].row0 + lv[l].height > 4096 || lv[l].col0 + lv[l].width > 4096)
-      return fail(c, PISLAM_ERR_INVALID, "stacked coordinates exceed 12 bits (Util.h:27-29)");
-  }
-  return PISLAM_OK;
-}
-}  // namespace
-
-
-namespace {
-
-// ---- the strip plan of the fused pipeline (build_fused_plan) ----
-// LDS figures every step of the plan, the launcher and the plan's invariant checks share.
-constexpr long CU_LDS = 160 * 1024;          // LDS of a CU: `wgs` resident workgroups have CU_LDS / wgs bytes each
-constexpr size_t LDS_CAP = 150 * 1024;       // most dynamic LDS a launch may ask for
-constexpr size_t LDS_OPT_IN = 64 * 1024;     // more than this: the kernel's hipFuncAttributeMaxDynamicSharedMemorySize is raised first
-// Queue bytes of a strip workgroup: the per-wave queues, plus the shared queues the two layouts differ in — ALIAS keeps one
-// corner queue (QH_SHARED entries at least: FusedLevel::qh), the plain layout the corner queue and the NMS candidates'.
-constexpr long WAVE_QUEUE_BYTES = (long)pf::WAVES * pf::QCAP * 4;
-constexpr long QUEUE_BYTES_ALIAS = WAVE_QUEUE_BYTES + pf::QH_SHARED * 4;
-constexpr long QUEUE_BYTES_PLAIN = WAVE_QUEUE_BYTES + pf::SHARED_Q * 4;
-// What a workgroup's dynamic LDS may take for `wgs` of them to stay resident on a CU.
-// (margin of 1280 B: static LDS + allocation granule — with 512 B the kernel measurably lost its 5th workgroup)
-inline long residency_budget(int wgs) { return CU_LDS / wgs - 1280; }
-// Residency target of the heuristic: 5 workgroups per CU.  (A search over 5 / 4 / 3 per CU with a cost model
-// "pixels * (R + 4) / R / measured throughput at that residency" was tried for the 1280-wide levels of BASELINE
-// config 4 — 12-row strips at 4 per CU instead of 16 rows at 3 — and measured no better: 1.24 vs 1.21 ms at
-// batch 256; forcing 5 per CU with 8-row strips and no halo carry gave 1.16 ms.  Option "wgs_per_cu" overrides.)
-inline int alias_wgs(const pislam_ctx *c) { return c->opt_wgs_per_cu > 0 ? c->opt_wgs_per_cu : 5; }
-// Strips a resident slot (5 per CU) works through in a launch of `batch` pyramids.
-inline double strips_per_slot(const pislam_ctx *c, int strips, int batch) {
-  return (double)strips * batch / (5.0 * std::max(1, c->num_cus));
-}
-
-inline int classified_end(int border, int nx) { return border + 16 * cdiv(nx, 16); }   // FusedLevel::xend for nx columns inside the border
-inline int score_pitch(int xend) { return (xend + 4 + 15) & ~15; }                     // FusedLevel::pitch
-// LDS pitch of an image tile row that stages columns [xbase, xend + 8), xbase = (border - 4) & ~15: a multiple of 16 bytes.
-// (An ODD number of 16-byte vectors — consecutive rows 4 banks apart instead of column x of every row in one bank at VGA
-// level 0's 640 bytes — was measured in round 4: bit-exact, the strip kernel within 0.5 % either way: the per-candidate
-// reads' bank conflicts, 45 % of its LDS cycles, come from the candidates' random columns, not from the row pitch.)
-inline int tile_pitch(int border, int xend) { return (xend - border + ((border - 4) & 15) + 4 + 8 + 15) & ~15; }
-
-// Step 1, plan entries: a level, or the x-tiles of a wide level (pf::FusedLevel: w, h, row0, col0, ex0, ex1, xscore, gfirst,
-// gn).  A level with more than `tile_max` classified columns is cut into tiles of T block-origin columns (T a multiple of
-// 32: tiles start on bucket boundaries for every fused bucket size); tile t > 0 starts HALO = 32 columns to the left of its
-// first block origin, so that, seen as a level of its own with the same border B, it classifies and scores the columns its
-// boundary blocks' NMS reads, and every tile but the last ends 2 columns past its last owned block origin.
-// False: more entries than a plan holds.
-bool plan_entries(const pislam_ctx *c, const pislam_frontend_params *p, const pislam_level *lv, pf::FusedParams *F) {
-  const int B = p->border, HALO = 32;
-  const int tile_max = c->opt_tile_cols > 0 ? c->opt_tile_cols : (c->opt_tile_cols < 0 ? 1 << 30 : 704);
-  int n = 0;
-  for (int l = 0; l < p->nlevels; l++) {
-    const int w = lv[l].width, nx = w - 2 * B, ny = lv[l].height - 2 * B;
-    int nt = 1;
-    // tiles of ~448 owned columns: with the 32-column halo a tile row is two full 256-pixel prefilter steps,
-    // and its strips reach the full 28 rows at 5 workgroups per CU (1280x960 batch 256: 0.94 ms with three
-    // 416-column tiles at level 0 against 1.01 ms with two of 624)
-    if (nx > 0 && ny > 0 && 16 * cdiv(nx, 16) > tile_max)
-      nt = std::max(2, tile_max >= 640 ? (nx + 224) / 448 : cdiv(nx, std::max(64, tile_max)));
-    const int T = nt > 1 ? (cdiv(nx, nt) + 31) & ~31 : 0;
-    nt = nt > 1 ? cdiv(nx, T) : 1;
-    if (n + nt > pf::MAX_LEVELS) {
-      memset(F->lv, 0, sizeof(F->lv));                 // (a refused plan holds no entries, not the first few)
-      return false;
-    }
-    const int g0 = n;
-    for (int t = 0; t < nt; t++) {
-      pf::FusedLevel &L = F->lv[n++];
-      const int o = t == 0 ? 0 : t * T - HALO;                           // level column of the entry's origin
-      const int E = nt == 1 ? w - B : std::min(B + (t + 1) * T, w - B);  // one past the last owned block origin (level x)
-      L.w = t == nt - 1 ? w - o : E - o + 2 + B;
-      L.h = lv[l].height;
-      L.row0 = lv[l].row0;
-      L.col0 = lv[l].col0 + o;
-      L.ex0 = t == 0 ? B : B + HALO;
-      L.ex1 = E - o;
-      L.xscore = (w - B) - o;
-      L.gfirst = g0;
-      L.gn = nt;
-    }
-  }
-  F->nlevels = n;
-  return true;
-}
-
-// The widest entry of entry e's level: all tiles of a level must cut the same strips, so its strip height comes from this one.
-int widest_tile(const pf::FusedParams &F, int e) {
-  int w = 0;
-  for (int t = F.lv[e].gfirst; t < F.lv[e].gfirst + F.lv[e].gn; t++) w = std::max(w, F.lv[t].w);
-  return w;
-}
-
-// Step 2, the strip height of a level whose widest entry has w columns (rows_max: build_fused_plan's cap).  Four rules, in
-// this precedence: option "strip_rows"; the ALIAS layout's residency rule; the generic 8k-pixel rule; and, where the strips
-// select per bucket themselves (lbs != 0), rounding to whole bucket rows on top of whichever rule gave the height.
-int strip_height(const pislam_ctx *c, const pislam_frontend_params *p, int lbs, int w, int rows_max) {
-  const int xend = classified_end(p->border, w - 2 * p->border), tpitch = tile_pitch(p->border, xend);
-  const int wgs = alias_wgs(c);
-  int R = c->opt_strip_rows;
-  if (R == 0 && c->opt_alias) {
-    // ALIAS layout under a residency target of `wgs` workgroups per CU: ~16k pixels per strip, 16..rows_max rows, capped so
-    // that queues + tile + the minimum shared queue fit CU_LDS / wgs where 16 rows allow it (VGA at 5 per CU: 24 rows at
-    // level 0, 28 below; measured 0.293 ms vs 0.311 ms with 16-row strips).
-    const int rcap = (int)((CU_LDS / wgs - QUEUE_BYTES_ALIAS) / tpitch - 10) & ~1;
-    if (wgs == 5 || rcap >= 10)                        // (else: an explicit residency request falls back to the generic rule)
-      R = std::max(16, std::min(std::min(rows_max, std::max(16, (c->opt_strip_px / w) & ~1)), rcap));
-  }
-  if (R == 0) {
-    R = (8192 / w) & ~1;                               // ~8k pixels per strip ...
-    R = std::min(32, std::max(16, R));
-    if (c->opt_wgs_per_cu > 0) {                       // ... capped so that tiles + queues fit CU_LDS / wgs_per_cu
-      const long budget = CU_LDS / c->opt_wgs_per_cu, pitch = score_pitch(xend);
-      if (budget > QUEUE_BYTES_PLAIN + 13 * pitch)
-        R = std::max(8, std::min(R, (int)(((budget - QUEUE_BYTES_PLAIN) / pitch - 13) / 2) & ~1));
-    }
-  }
-  if (lbs) {                                           // (selection inside the strips:) strips hold whole bucket rows
-    const int bs = 1 << lbs;
-    if (c->opt_strip_rows == 0 && c->opt_alias) {
-      // heuristic height: round UP to whole bucket rows (16-px buckets: 32-row strips — measured 0.315 ms
-      // vs 0.371 ms with 16-row strips) where that still fits the residency budget, DOWN on the levels where it
-      // does not: the launch has ONE LDS size, a single level over the budget costs every level its fifth workgroup
-      const int up = std::min(std::max(bs, 32), ((R + bs - 1) / bs) * bs), down = std::max(bs, (R / bs) * bs);
-      const long need = QUEUE_BYTES_ALIAS + (long)(up + 10) * tpitch;
-      R = (c->opt_bucket_round_up || need <= residency_budget(wgs)) ? up : down;
-    } else
-      R = std::max(bs, (R / bs) * bs);
-  }
-  return R;
-}
-
-// Step 3, the LDS of an entry whose R, nbx and xend are set: pitches, the reciprocals the kernel divides by them with, and
-// what a workgroup of this entry needs in the plain layout (tbytes) and in the ALIAS layout (apad, qh at `wgs` per CU),
-// raising the launch's *lds and *lds_alias to it.
-void level_lds(int border, int wgs, pf::FusedLevel &L, size_t *lds, size_t *lds_alias) {
-  const int R = L.R;
-  L.pitch = score_pitch(L.xend);
-  L.tpitch = tile_pitch(border, L.xend);
-  L.vpr_recip = (uint32_t)(((1ull << 32) + (L.tpitch / 16) - 1) / (L.tpitch / 16));
-  L.tp_recip = (uint32_t)(((1ull << 32) + L.tpitch - 1) / L.tpitch);
-  // scan fallbacks reuse the image tile: row buffers of R/2 x nbx dwords, or per-cell results (<= one
-  // dword per block) + per-cell counts (<= a quarter of that: a cell holds >= 2x2 blocks)
-  L.tbytes = std::max((R + 10) * L.tpitch, (((R / 2) * L.nbx * 5 + 64) + 15) & ~15);
-  *lds = std::max(*lds, (size_t)L.tbytes + (size_t)(R + 3) * L.pitch + (size_t)QUEUE_BYTES_PLAIN);
-  // ALIAS layout: the score tile (R+3 rows) is laid over [NMS scratch end, image row R): pad the
-  // per-wave queue area when that span is too short (levels wider than ~680 columns)
-  // ... and the ORB phase's 8 patches + vrecpe table are laid over the same span (strip_body phase E)
-  const long need = std::max((long)pf::NMS_SCRATCH * 4 + (long)(R + 3) * L.pitch,
-                             (long)pf::NMS_SCRATCH * 4 + (long)pf::WAVES * 2 * pf::ORB_PATCH_BYTES + 256);
-  const long have = WAVE_QUEUE_BYTES + (long)R * L.tpitch;
-  L.apad = need > have ? (int)((need - have + 15) & ~15L) : 0;
-  // one shared queue in this layout: at least QH_SHARED entries, and whatever LDS the level's tile
-  // leaves under the residency budget (narrow levels of a textured photo are the dense ones)
-  const long fixed = WAVE_QUEUE_BYTES + L.apad + (long)(R + 10) * L.tpitch;
-  const long spare = (residency_budget(wgs) - fixed) / 4;
-  L.qh = (int)std::min<long>(4096, std::max<long>(pf::QH_SHARED, spare & ~3L));
-  *lds_alias = std::max(*lds_alias, (size_t)fixed + (size_t)L.qh * 4);
-}
-
-// Step 4, the run length.  Runs: a workgroup walks run_len consecutive strips of a level (halo carried in LDS).  Longer runs
-// save the duplicated halo work but leave fewer, longer workgroups for the dispatcher to balance over the 5 resident
-// slots per CU.  Measured (strip kernel, ms): VGA batch 256 (15 strips per slot): 0.236 / 0.231 / 0.233 / 0.243 /
-// 0.242 / 0.235 / 0.231 / 0.229 / 0.229 / 0.243 for run_len 1 / 2 / 3 / 4 / 5 / 6 / 8 / 10 / 12 / 16 — the carry is
-// worth ~3 % at best and the curve is dispatch-quantisation noise; 720p batch 64 (10 strips per slot): 0.208 /
-// 0.207 / 0.216 / 0.227 / 0.238 for 1..5; 1280x960 batch 256 (54 per slot): 1.029 / 1.018 / 1.012 / 1.044 / 1.053 /
-// 1.010 for 4 / 5 / 6 / 7 / 8..10 / 12, batch 64: 0.278 / 0.307 / 0.376 for 2 / 3 / 8; VGA batch 32, 64: 1 is best.
-// Rule: ~6.5 workgroups per resident slot, at most 8 strips per run.  (List-scheduling and processor-sharing
-// simulations of one XCD were tried as a predictor: neither tracks the measured 2-3 % structure.)
-// With the runs of a pyramid launched longest first (order_runs) the curve flattens: VGA batch 256
-// 0.232 / 0.222 / 0.220 / 0.224 / 0.222 / 0.233 for run_len 1 / 2 / 3 / 4 / 6 / 8; 1280x960 batch 256 0.920 / 0.898 /
-// 0.899 / 0.889 / 0.889 for 2 / 4 / 6 / 8 / 12; 720p batch 64 0.191 / 0.191 / 0.197 / 0.206 for 1 / 2 / 3 / 4.
-int run_length(const pislam_ctx *c, const pf::FusedParams &F, int strips, int batch) {
-  if (c->opt_run_len > 0) return c->opt_run_len;
-  // Round 5 (strips of a run follow each other without a barrier): one call at a time the rule stands (VGA batch 256: strip
-  // kernel 0.164 / 0.166 / 0.171 ms for run_len 2 / 3 / 4), but as a LANE of a pipeline — other batches' kernels fill the
-  // tail of the launch — longer runs win: whole step 0.2233 / 0.2208 / 0.2203 ms for 2 / 3 / 4 (720p batch 64: 0.2974 /
-  // 0.2954 for 2 / 3; demo photo x 256: 0.3242 / 0.3208 for 2 / 4).  Lanes aim at ~3.25 workgroups per slot.
-  const double per_wg = c->lanes_in_flight > 1 ? 3.25 : 6.5;
-  const int by_slot = std::max(1, std::min(8, (int)(strips_per_slot(c, strips, batch) / per_wg + 0.5)));
-  if (c->lanes_in_flight <= 1) return by_slot;
-  // Round 6, lanes only: the LONGEST runs that still leave the launch 0.6 workgroups per resident slot (5 per CU) — whole
-  // levels per workgroup where the batch is large enough.  Re-swept after the pretest change, pipelined step in ms for
-  // run_len default (the rule above) / 12 / 16 / 24 / 32 / 64: VGA batch 256 0.2117 / 0.2087 / 0.2062 / 0.2072 / 0.2063 / 0.2068
-  // (8 whole-level runs per pyramid = 1.6 per slot); demo photo 0.3169 / 0.3153 / 0.3153 / 0.3144 / 0.3143 / 0.3140; 1280x960
-  // 0.6692 / 0.6674 / 0.6628 / 0.6637 / 0.6517 / 0.6531; 720p build batch 64 0.2865 / 0.2759 / 0.2671 / 0.2581 / 0.2589 / 0.2590
-  // (15 runs per pyramid = 0.75 per slot); bucket mode 0.2334 / 0.2293 / 0.2285 / 0.2281 / 0.2287 / 0.2277 — and where the
-  // launch gets too few workgroups it turns: VGA batch 64 0.0646 / 0.0631 (0.6 per slot) / 0.0681 (0.5) / 0.0720; batch 16
-  // 0.0208 / 0.0425.  The strip kernel ALONE is slower with long runs (0.156 -> 0.159-0.162 ms: a longer tail); on a lane
-  // another batch's kernels run in that tail, and a long run stages its halo once and prefetches every strip but the first.
-  const long want = (long)(0.6 * 5.0 * std::max(1, c->num_cus));
-  int longest = 1;
-  for (int l = 0; l < F.nlevels; l++) longest = std::max(longest, F.lv[l].nstrips);
-  longest = std::min(longest, 64);                     // (option range; k_frame keeps a 64-bit mask of a run's strips)
-  for (int rl = longest; rl > by_slot; rl--) {
-    long r = 0;
-    for (int l = 0; l < F.nlevels; l++) r += cdiv(F.lv[l].nstrips, rl);
-    if (r * batch >= want && r <= pf::MAX_ORDER) return rl;
-  }
-  return by_slot;
-}
-
-// Step 5, the launch order of a pyramid's runs: estimated cost (pixels + a fixed share per strip), longest first — the
-// longest-processing-time-first rule of list scheduling: workgroups are dispatched in blockIdx order to the
-// 5 resident slots per CU, so the short runs of the small levels fill the tail of the launch.  Entry order
-// (level by level) interleaves short last-runs of big levels with long runs of the next level: VGA batch 256
-// 0.232 -> 0.222 ms, 1280x960 batch 256 0.927 -> 0.895 ms.  Plans with more runs than order[] holds keep entry order.
-void order_runs(const pislam_ctx *c, pf::FusedParams *F) {
-  F->order_n = 0;
-  if (F->runs_per_pyr <= 0 || F->runs_per_pyr > pf::MAX_ORDER || !c->opt_run_order) return;
-  struct RunCost {
-    double cost;
-    int entry, run;
-  };
-  std::vector<RunCost> rc;
-  for (int l = 0; l < F->nlevels; l++) {
-    const pf::FusedLevel &L = F->lv[l];
-    const int ny = L.h - 2 * F->border;
-    for (int r = 0; r < L.nruns; r++) {
-      double cst = 0;
-      for (int sidx = r * F->run_len; sidx < std::min((r + 1) * F->run_len, L.nstrips); sidx++)
-        cst += 1.6 * L.w * std::min(L.R, ny - sidx * L.R) + 6000.0;
-      rc.push_back({cst, l, r});
-    }
-  }
-  std::stable_sort(rc.begin(), rc.end(), [](const RunCost &a, const RunCost &b) { return a.cost > b.cost; });
-  for (size_t i = 0; i < rc.size(); i++) F->order[i] = ((uint32_t)rc[i].entry << 16) | (uint32_t)rc[i].run;
-  F->order_n = (int)rc.size();
-}
-
-// The strip plan for heuristic strip heights of at most rows_max rows: the five steps above.  False: no strip plan for
-// these parameters (the staged pipeline takes the call).
-bool build_fused_plan_rows(const pislam_ctx *c, const pislam_frontend_params *p, const pislam_level *lv,
-                           int batch, int rows_max, pf::FusedParams *F, size_t *lds_bytes, size_t *lds_alias_bytes) {
-  if (p->nlevels > pf::MAX_LEVELS) return false;
-  memset(F, 0, sizeof(*F));
-  F->vstep = p->vstep;
-  F->rows = p->rows;
-  F->border = p->border;
-  F->thr = p->fast_threshold & 0xff;
-  F->hthr = p->harris_threshold;
-  F->batch = batch;
-  F->dump_score = c->opt_dump_score;
-  F->lbs = p->log_bucket_size;
-  F->limit = p->bucket_limit;
-  F->words = p->words;
-  F->orb_in_strip = c->opt_orb_in_strip;
-  // Buckets (fastExtract<.., logBucketSize, bucketLimit>): by default the strips run exactly as without buckets (F->lbs = 0:
-  // any strip height, the plain kernels) and pf::k_bucket_select applies the per-cell top-`limit` between the strip kernel and
-  // the gather (run_fused); option "bucket_select" 0 keeps the selection inside the strips (rounds 1-3: strips cut on bucket
-  // rows, cells of 4..32 px).
-  bool select = p->log_bucket_size != 0 && c->opt_bucket_select;
-  for (int l = 0; l < p->nlevels && select; l++)
-    if (lv[l].width - 2 * p->border > 0 && ((lv[l].width - 2 * p->border - 1) >> p->log_bucket_size) + 1 > pf::SEL_NB) select = false;
-  if (select) {
-    F->lbs = 0;
-    F->orb_in_strip = 0;
-  }
-  // fused bucket mode inside the strips: cells of 4..32 px (they must fit a strip and the per-wave scratch)
-  if (F->lbs != 0 && (p->log_bucket_size < 2 || p->log_bucket_size > 5)) return false;
-  F->ablate = c->opt_ablate;
-  if (!plan_entries(c, p, lv, F)) return false;
-  int strips = 0, slots = 0, runs = 0;
-  size_t lds = 0, lds_alias = 0;
-  for (int l = 0; l < F->nlevels; l++) {
-    pf::FusedLevel &L = F->lv[l];
-    const int nx = L.w - 2 * p->border, ny = L.h - 2 * p->border;
-    L.strip0 = strips;
-    L.slot0 = slots;
-    if (nx <= 0 || ny <= 0) {   // nothing to extract on this level (Fast.h loops do not run)
-      L.R = 16;                 // (nstrips and nbx stay 0)
-      L.xend = p->border;
-      L.pitch = 16;
-      continue;
-    }
-    L.R = strip_height(c, p, F->lbs, widest_tile(*F, l), rows_max);
-    L.nstrips = cdiv(ny, L.R);
-    L.nbx = (nx + 1) / 2;
-    L.xend = classified_end(p->border, nx);
-    level_lds(p->border, alias_wgs(c), L, &lds, &lds_alias);
-    strips += L.nstrips;
-    slots += L.nstrips * (L.R / 2) * L.nbx;
-  }
-  F->run_len = run_length(c, *F, strips, batch);
-  for (int l = 0; l < F->nlevels; l++) {
-    F->lv[l].run0 = runs;
-    F->lv[l].nruns = cdiv(F->lv[l].nstrips, F->run_len);
-    runs += F->lv[l].nruns;
-  }
-  F->strips_per_pyr = strips;
-  F->runs_per_pyr = runs;
-  F->slots_per_pyr = slots;
-  order_runs(c, F);
-  *lds_bytes = lds;
-  *lds_alias_bytes = lds_alias + (size_t)c->opt_lds_pad;   // profiling: opt_lds_pad lowers the residency artificially
-  if ((size_t)p->rows * p->vstep > 0x7fffffffu) return false;   // 32-bit byte offsets inside a pyramid
-  return lds <= LDS_CAP;          // (strips == 0: no level holds a classifiable pixel — the caller writes zero counts)
-}
-
-// Cap of the heuristic strip height.  Every strip pays a fixed share (set-up, barriers, the halo carried through
-// LDS, the ragged last wave step of each phase), so the narrow levels want strips as tall as the prefetch
-// registers allow (R * pitch <= 16 KiB) — but only when the launch has plenty of workgroups per resident slot;
-// a small launch is balanced better by more, shorter strips.  Measured, strip kernel alone (ms) for caps 28 / 36 /
-// 44 / 56 / 64: VGA batch 256 (15 strips per slot at cap 28) 0.221 / 0.212 / 0.209 / 0.207 / 0.211; 1280x960 batch
-// 256 (54 per slot) 0.885 / 0.857 / 0.861 / 0.861; 720p batch 64 (10 per slot): whole step 0.337 / 0.346 / 0.346 /
-// 0.344.  Rule: cap 56 from 12 strips per slot on, 28 below.  Option "strip_rows_max" overrides.
-bool build_fused_plan(const pislam_ctx *c, const pislam_frontend_params *p, const pislam_level *lv, int batch,
-                      pf::FusedParams *F, size_t *lds_bytes, size_t *lds_alias_bytes) {
-  if (c->opt_strip_rows_max > 0)
-    return build_fused_plan_rows(c, p, lv, batch, c->opt_strip_rows_max, F, lds_bytes, lds_alias_bytes);
-  if (!build_fused_plan_rows(c, p, lv, batch, 28, F, lds_bytes, lds_alias_bytes)) return false;
-  if (strips_per_slot(c, F->strips_per_pyr, batch) < 12.0) return true;
-  pf::FusedParams tall;
-  size_t l0 = 0, l1 = 0;
-  if (build_fused_plan_rows(c, p, lv, batch, 56, &tall, &l0, &l1)) {
-    *F = tall;
-    *lds_bytes = l0;
-    *lds_alias_bytes = l1;
-  }
-  return true;
-}
-
-// Sub-batches of a fused batch call (option "sub_batches", default 1 = one launch group): the strip kernels of the
-// sub-batches run back to back on the context stream, overflow pass + gather/ORB of sub-batch i on the context's
-// second stream under the strip kernel of sub-batch i+1 (fork / join by events inside the call).  MEASURED AND
-// NOT THE DEFAULT (MI355X, VGA batch 256, one call at a time): 0.286 ms with one launch group, 0.326 / 0.360 / 0.367
-// / 0.466 ms with 2 / 3 / 4 / 6 sub-batches — a strip launch of 128 pyramids takes 0.121 ms, not half of 0.206: every
-// launch ends in its own tail of partly filled CUs and the serialised launches add ~18 us each, more than the
-// overlap wins back (1280x960: 1.23 -> 1.36 ms with 4).  What does pay is whole batches in flight on separate
-// contexts (bench.py --streams, tools/pislam_demo --streams: 0.252 ms).  `0` = the MiB-per-sub-batch rule below.
-int choose_sub_batches(const pislam_ctx *c, const pislam_frontend_params *p, int batch) {
-  if (c->opt_dump_score || c->opt_ablate || c->opt_pipeline == 1) return 1;
-  int n = c->opt_sub_batches;
-  if (n == 0) {
-    const double mb = (double)p->rows * p->vstep * batch / (1024.0 * 1024.0);
-    const double target = c->opt_sub_mb > 0 ? c->opt_sub_mb : 128.0;
-    n = (int)(mb / target + 0.5);
-    n = std::min(n, batch / 16);
-  }
-  return std::max(1, std::min(std::min(n, batch), (int)pislam_ctx::MAX_SUB));
+  const char *refusal = fp::check_params(p, lv, batch);
+  return refusal ? fail(c, PISLAM_ERR_INVALID, refusal) : PISLAM_OK;
 }
 
 // Overflow lists: one per sub-batch ([0] count, [1] count of the previous step, [2..] entries), `stride` dwords
@@ -1439,67 +1007,6 @@ int ensure_aux(pislam_ctx *c, int nsub) {
   return PISLAM_OK;
 }
 
-// The bucket selection pass (pf::k_bucket_select) and the UNIT plan the gather runs on when the strips run as without buckets
-// (build_fused_plan): one "strip" per (level, cell row), `buckets x limit` slots each, lists final (lbs != 0, no tiles:
-// the gather concatenates).  Part of the call's plan (plan_frontend).
-int build_select_plan(pislam_ctx *c, const pislam_frontend_params *p, const pf::FusedParams &Fplan, pf::SelectPlan *Qp,
-                      pf::FusedParams *Up) {
-  pf::SelectPlan &Q = *Qp;
-  pf::FusedParams &U = *Up;
-  memset(&Q, 0, sizeof(Q));
-  memset(&U, 0, sizeof(U));
-  const int lbs = p->log_bucket_size, bs = 1 << lbs, B = p->border;
-  Q.lbs = lbs;
-  Q.limit = p->bucket_limit;
-  Q.border = B;
-  int nreal = 0;
-  for (int e = 0; e < Fplan.nlevels; e++) {
-    if (Fplan.lv[e].gfirst != e) continue;           // (the tiles of a level follow its first entry)
-    if (nreal >= 16) return fail(c, PISLAM_ERR_INVALID, "too many levels for the bucket selection pass");
-    const int l = nreal++;
-    const int gn = std::max(1, Fplan.lv[e].gn);
-    const pf::FusedLevel &last = Fplan.lv[e + gn - 1];
-    const int wl = last.col0 + last.w - Fplan.lv[e].col0, hl = Fplan.lv[e].h;       // the level's own size
-    const int nx = wl - 2 * B, ny = hl - 2 * B;
-    Q.row0[l] = Fplan.lv[e].row0;
-    Q.col0[l] = Fplan.lv[e].col0;
-    Q.h[l] = hl;
-    Q.g0[l] = e;
-    Q.gn[l] = gn;
-    Q.unit0[l] = Q.units_per_pyr;
-    Q.nunits[l] = (nx > 0 && ny > 0) ? cdiv(ny, bs) : 0;
-    Q.cap[l] = (nx > 0 ? ((nx - 1) >> lbs) + 1 : 1) * p->bucket_limit;             // Fast.h:201 numBuckets x bucketLimit
-    Q.uslot0[l] = Q.uslots_per_pyr;
-    Q.nb_max = std::max(Q.nb_max, Q.cap[l] / p->bucket_limit);
-    Q.units_per_pyr += Q.nunits[l];
-    Q.uslots_per_pyr += Q.nunits[l] * Q.cap[l];
-    pf::FusedLevel &ul = U.lv[l];
-    ul.w = wl;
-    ul.h = hl;
-    ul.row0 = Q.row0[l];
-    ul.col0 = Q.col0[l];
-    ul.R = 2;                                        // strip_slot_of: slot0 + s * (R >> 1) * nbx
-    ul.nbx = Q.cap[l];
-    ul.nstrips = Q.nunits[l];
-    ul.strip0 = Q.unit0[l];
-    ul.slot0 = Q.uslot0[l];
-    ul.gfirst = l;
-    ul.gn = 1;
-  }
-  Q.nlevels = nreal;
-  U.nlevels = nreal;
-  U.strips_per_pyr = Q.units_per_pyr;
-  U.slots_per_pyr = Q.uslots_per_pyr;
-  U.vstep = p->vstep;
-  U.rows = p->rows;
-  U.border = B;
-  U.lbs = lbs;
-  U.limit = p->bucket_limit;
-  U.words = p->words;
-  U.ablate = Fplan.ablate;
-  if (Q.units_per_pyr == 0) return fail(c, PISLAM_ERR_INVALID, "no extractable level");
-  return PISLAM_OK;
-}
 
 // The device copy of a host-built plan table: found by content, or created (hipMalloc + upload in stream order — never
 // inside a capture: the first occurrence of a call runs eagerly, and reserve_frontend uploads the tables).
@@ -1529,43 +1036,6 @@ int plan_table(pislam_ctx *c, const std::vector<uint32_t> &t, const uint32_t **o
   return PISLAM_OK;
 }
 
-// The unit table of the bucket selection pass (pf::k_bucket_select reads one record per unit instead of walking the plan):
-// built on the host from the strip plan and the selection plan (never empty); its device copy comes from plan_table().
-std::vector<uint32_t> unit_table(const pislam_frontend_params *p, const pf::FusedParams &F, const pf::SelectPlan &Q) {
-  std::vector<uint32_t> t((size_t)Q.units_per_pyr * pf::SEL_REC, 0u);
-  const int B = p->border, lbs = p->log_bucket_size, bs = 1 << lbs;
-  for (int l = 0; l < Q.nlevels; l++)
-    for (int cr = 0; cr < Q.nunits[l]; cr++) {
-      uint32_t *r = &t[(size_t)(Q.unit0[l] + cr) * pf::SEL_REC];
-      const int y0 = B + (cr << lbs), y1 = std::min(y0 + bs, Q.h[l] - B);
-      int nl = 0;
-      for (int k = 0; k < Q.gn[l]; k++) {
-        const pf::FusedLevel &E = F.lv[Q.g0[l] + k];
-        const int s_lo = (y0 - B) / E.R, s_hi = std::min((y1 - 1 - B) / E.R, E.nstrips - 1);
-        for (int sidx = s_lo; sidx <= s_hi; sidx++, nl++)
-          if (nl < pf::SEL_ML) {
-            r[8 + nl] = (uint32_t)(E.slot0 + sidx * (E.R >> 1) * E.nbx);
-            r[16 + nl] = (uint32_t)(E.strip0 + sidx);
-          }
-      }
-      r[0] = nl <= pf::SEL_ML ? (uint32_t)nl : 0xffffffffu;
-      r[1] = (uint32_t)l;
-      r[2] = (uint32_t)cr;
-      r[3] = (uint32_t)(Q.uslot0[l] + cr * Q.cap[l]);
-      r[4] = (uint32_t)(Q.row0[l] + B);
-      r[5] = (uint32_t)(Q.col0[l] + B);
-    }
-  return t;
-}
-
-// The one-launch path (pf::k_frame) takes batches of up to FRAME_MAX_BATCH pyramids: three launch floors are most of such
-// a call (one VGA pyramid: 31 us in three launches, 15 us of it work), and its gather + ORB workgroups — which wait inside
-// the grid for their pyramid's strips — stay a small fraction of an XCD's resident slots even with several such launches
-// in flight (at most 128 per launch).
-constexpr int FRAME_MAX_BATCH = 8;                                  // what option "frame" can be raised to
-constexpr int FRAME_DEFAULT_BATCH = 2;                              // measured: one launch wins for 1 and 2 pyramids per call
-inline int frame_max_batch(const pislam_ctx *c) { return c->opt_frame <= 0 ? 0 : c->opt_frame == 1 ? FRAME_DEFAULT_BATCH : std::min(c->opt_frame, FRAME_MAX_BATCH); }
-static_assert(FRAME_MAX_BATCH <= pf::FRAME_SYNC_PYR, "k_frame's hand-over counters");
 int ensure_frame_sync(pislam_ctx *c) {
   bool grew = false;
   if (c->w_sync.ensure(sizeof(uint32_t) * pf::FRAME_SYNC_WORDS, &grew) != PISLAM_OK)
@@ -1573,157 +1043,11 @@ int ensure_frame_sync(pislam_ctx *c) {
   if (grew) HIPCHK(c, hipMemsetAsync(c->w_sync.p, 0, c->w_sync.cap, c->stream));   // (the kernel re-arms them itself)
   return ensure_fault_flag(c);
 }
-// What a front-end batch call decides from the shape and the options (plan_frontend, host only): reserve_frontend sizes the
-// workspace from it and run_fused launches from it: after a reserve the call allocates nothing and can be captured into a hipGraph.
-struct FrontendPlan {
-  bool fused = false;                 // false: the staged pipeline (option "pipeline" 1, or no strip plan for the shape)
-  int nsub = 1, submax = 0;           // sub-batches, pyramids in the largest one
-  pf::FusedParams F{};                // the strip plan, built for submax pyramids (strips_per_pyr == 0: nothing to extract)
-  size_t lds = 0, lds_alias = 0, klds = 0;   // strip kernel LDS bytes: plain layout, ALIAS layout, the layout it runs with
-  bool sel = false;                   // the bucket selection pass: build_select_plan's two plans, the unit table
-  pf::SelectPlan Q{};
-  pf::FusedParams U{};
-  std::vector<uint32_t> utab;
-  size_t sel_lds = 0, glds = 0;       // LDS bytes of k_bucket_select and of k_gather
-  bool alias = false;                 // ALIAS layout: one overflow list of ovf_stride dwords per sub-batch
-  size_t ovf_stride = 0, sdesc_per_pyr = 0;
-  bool generic_orb = false;           // k_gather + per-keypoint k_orb instead of k_gather_orb
-  bool frame = false;                 // the one-launch path (pf::k_frame), as far as the shape and the options decide
-  int nch = 0, fch = 0;               // ORB workgroups per pyramid of k_gather_orb and of k_frame
-  size_t per_max = 0, olds = 0, fper = 0, flds = 0;   // keypoints per workgroup and LDS bytes of the two
-};
 
-// The plan of a batch call (parameters checked).  Fails only where build_select_plan does, with `fused` and F already set.
+// The plan of a batch call (parameters checked): fp::plan_frontend from the context's options.
 int plan_frontend(pislam_ctx *c, const pislam_frontend_params *p, const pislam_level *lv, int batch, FrontendPlan *P) {
-  P->nsub = choose_sub_batches(c, p, batch);
-  P->submax = batch / P->nsub + (batch % P->nsub ? 1 : 0);
-  P->fused = c->opt_pipeline != 1 && build_fused_plan(c, p, lv, P->submax, &P->F, &P->lds, &P->lds_alias);
-  const pf::FusedParams &F = P->F;
-  const int S = F.strips_per_pyr, nsub = P->nsub, submax = P->submax;
-  if (!P->fused || S == 0) return PISLAM_OK;
-  P->sel = p->log_bucket_size != 0 && F.lbs == 0;
-  if (P->sel) {
-    PCHK(build_select_plan(c, p, F, &P->Q, &P->U));
-    P->utab = unit_table(p, F, P->Q);
-    P->sel_lds = sizeof(uint32_t) * pf::SEL_WAVES * (64 + 2 * (size_t)P->Q.nb_max);
-  }
-  const int Sg = P->sel ? P->Q.units_per_pyr : S;   // "strips" of the plan the gather runs on
-  // descriptor staging: QS_SHARED slots of `words` dwords per strip (ALIAS strips hold at most QS_SHARED survivors)
-  // (only strips that describe their own keypoints write there: option "orb_in_strip")
-  P->sdesc_per_pyr = F.orb_in_strip ? (size_t)S * pf::QS_SHARED * (size_t)p->words : 0;
-  // ALIAS layout (score tile laid over the dead image rows, 26 KB instead of 39 KB of LDS per workgroup
-  // at VGA): the default.  Its overflow list (strips with overflowing queues) is drained by
-  // k_fused_overflow right after; the gather kernel empties the list for the next step.
-  P->alias = c->opt_alias && submax <= 65535 && S <= 65535;
-  P->ovf_stride = 2 + (size_t)S * submax;
-  P->klds = P->alias ? P->lds_alias : P->lds;
-  // k_gather_orb's 48-byte row windows assume a row-independent byte shift (vstep % 16 == 0) and
-  // 32-bit byte offsets inside a pyramid; other layouts take the generic gather + per-keypoint ORB kernels.
-  P->generic_orb = p->vstep % 16 != 0 || (size_t)p->rows * p->vstep > 0x7fffffffu;
-  P->glds = sizeof(uint32_t) * (Sg + 1);
-  // gather + orbCompute in one launch: (chunks, pyramids) workgroups
-  // Workgroups per pyramid: one per ~70 k classified pixels (keypoint counts are not known to the host; ~70-100
-  // keypoints per workgroup measured best: VGA, 981 keypoints: 14 = 21 chunks > 7, 28; 1280x960, 4389 keypoints: 42-49
-  // chunks 0.36 ms against 0.41 ms with 14), at least 16 for small batches, and such that the grid is a whole number
-  // of "waves" of resident workgroups (7 per CU: 64 VGPRs, 13.5 KB LDS) — batch 256: 14 chunks = 2 x 1792 workgroups
-  // measured 0.079 ms against 0.085 ms with 16 (2.3 waves: the last one 30 % full).
-  if (!P->generic_orb) {
-    long px = 0;
-    for (int l = 0; l < F.nlevels; l++) px += (long)(F.lv[l].ex1 - F.lv[l].ex0) * F.lv[l].nstrips * F.lv[l].R;
-    const int by_px = (int)(px / 70000);
-    int nch = std::min(64, submax >= 128 ? std::max(8, by_px) : std::max(by_px, std::max(16, 4096 / submax)));
-    if (nsub == 1) {
-      const long slots = 7L * std::max(1, c->num_cus);
-      long best = nch, bestd = 1L << 40;
-      for (long m = 1; m <= 64; m++) {
-        const long cand = m * slots / submax;
-        if (cand < 4 || cand > 64) continue;
-        const long d = std::labs(cand - nch);
-        if (d < bestd) {
-          bestd = d;
-          best = cand;
-        }
-      }
-      nch = (int)best;
-    } else {
-      // pipelined sub-batches: the kernel shares the GPU with the next sub-batch's strip kernel, whole "waves" of
-      // resident workgroups mean nothing there — one workgroup per ~70 k pixels
-      nch = std::min(64, std::max(8, by_px));
-    }
-    P->nch = c->opt_orb_chunks > 0 ? c->opt_orb_chunks : nch;
-    P->per_max = ((size_t)p->max_keypoints + P->nch - 1) / P->nch;
-    P->olds = pf::orb_lds_bytes(Sg, P->per_max);
-  }
-  // The one-launch path.  Occupancy gate: the gather + ORB workgroups WAIT inside the grid.  With `lanes_in_flight` such
-  // launches on the device at most lanes x batch x fch of them are resident, an eighth per XCD; they must stay a small
-  // fraction (a quarter) of the workgroups an XCD holds with this launch's LDS footprint (96 VGPRs: five 4-wave workgroups
-  // per CU at most), so that strip workgroups always find a slot.
-  if (P->alias && !P->sel && F.lbs == 0 && !F.dump_score && !F.ablate && !P->generic_orb && nsub == 1 && !F.orb_in_strip &&
-      c->opt_repeat_strips <= 1 && batch <= frame_max_batch(c)) {
-    P->fch = c->opt_orb_chunks > 0 ? std::min(c->opt_orb_chunks, 128) : std::min(64, std::max(16, 128 / batch));
-    P->fper = ((size_t)p->max_keypoints + P->fch - 1) / P->fch;
-    P->flds = std::max(std::max(P->lds_alias, P->lds), pf::orb_lds_bytes(S, P->fper));
-    const long wg_per_cu = std::max<long>(1, std::min<long>(5, CU_LDS / (long)std::max<size_t>(P->flds, 1)));
-    const long slots_per_xcd = wg_per_cu * std::max(1, c->num_cus / 8);
-    const long waiting_per_xcd = ((long)std::max(1, c->lanes_in_flight) * batch * P->fch + 7) / 8;
-    P->frame = P->flds <= LDS_CAP && 4 * waiting_per_xcd <= slots_per_xcd;
-  }
-  return PISLAM_OK;
-}
-
-// The invariants of a plan the kernels rely on (pislam_debug_build_plan checks every plan it builds): what is violated, or
-// nullptr.  The strip plan first; the selection plan's are a second function because plan_frontend may have refused it.
-const char *strip_plan_violation(const FrontendPlan &P, const pislam_frontend_params *p) {
-  const pf::FusedParams &F = P.F;
-  if (F.nlevels < 1 || F.nlevels > pf::MAX_LEVELS) return "entries";
-  int strips = 0, slots = 0, runs = 0;
-  for (int l = 0; l < F.nlevels; l++) {
-    const pf::FusedLevel &L = F.lv[l];
-    if (L.strip0 != strips || L.slot0 != slots || L.run0 != runs) return "prefix sums";
-    if (L.nstrips < 0 || (L.nstrips > 0 && (L.R < 2 || (L.R & 1)))) return "strip height";
-    if (L.nstrips > 0) {
-      if (L.col0 < 0 || L.row0 < 0 || L.col0 + L.w > p->vstep || L.row0 + L.h > p->rows) return "entry outside the pyramid";
-      if (L.tpitch % 16 || L.pitch % 16 || L.tpitch <= 0) return "pitch";
-      if ((L.R + 10) * L.tpitch > (int)LDS_CAP) return "tile larger than the LDS";
-      if (L.gfirst < 0 || L.gfirst > l || L.gn < 1 || L.gfirst + L.gn > F.nlevels) return "tile group";
-      if (L.ex0 < p->border || L.ex1 > L.w || L.ex0 > L.ex1) return "owned columns";
-      if (cdiv(L.nstrips, F.run_len) != L.nruns) return "runs";
-      if ((uint64_t)L.vpr_recip * (uint64_t)(L.tpitch / 16) < (1ull << 32)) return "vpr_recip";
-      if ((uint64_t)L.tp_recip * (uint64_t)L.tpitch < (1ull << 32)) return "tp_recip";
-      if (L.qh < pf::QH_SHARED) return "corner queue";
-    }
-    strips += L.nstrips;
-    slots += L.nstrips * (L.R / 2) * L.nbx;
-    runs += L.nruns;
-  }
-  if (strips != F.strips_per_pyr || slots != F.slots_per_pyr || runs != F.runs_per_pyr) return "totals";
-  if (F.order_n) {
-    if (F.order_n != runs || runs > pf::MAX_ORDER) return "order size";
-    std::vector<int> seen((size_t)runs, 0);
-    for (int i = 0; i < F.order_n; i++) {
-      const int e = (int)(F.order[i] >> 16), r = (int)(F.order[i] & 0xffff);
-      if (e >= F.nlevels || r >= F.lv[e].nruns) return "order entry";
-      seen[(size_t)(F.lv[e].run0 + r)]++;
-    }
-    for (int v : seen)
-      if (v != 1) return "order is not a permutation of the runs";
-  }
-  if (P.lds_alias > (size_t)CU_LDS) return "aliased LDS size";
-  return nullptr;
-}
-
-const char *select_plan_violation(const FrontendPlan &P, const pislam_frontend_params *p) {
-  const pf::SelectPlan &Q = P.Q;
-  int units = 0, uslots = 0;
-  for (int l = 0; l < Q.nlevels; l++) {
-    if (Q.unit0[l] != units || Q.uslot0[l] != uslots) return "selection plan prefix sums";
-    if (Q.g0[l] < 0 || Q.g0[l] + Q.gn[l] > P.F.nlevels) return "selection plan entries";
-    if (Q.cap[l] / p->bucket_limit > pf::SEL_NB) return "more buckets than the selection pass holds";
-    units += Q.nunits[l];
-    uslots += Q.nunits[l] * Q.cap[l];
-  }
-  if (units != Q.units_per_pyr || uslots != Q.uslots_per_pyr) return "selection plan totals";
-  return nullptr;
+  const char *refusal = fp::plan_frontend(c->opt, p, lv, batch, P);
+  return refusal ? fail(c, PISLAM_ERR_INVALID, refusal) : PISLAM_OK;
 }
 
 // The workspace of plan P: the only place the front end's buffers are allocated (option "ablate" 8192's profiling aside).
@@ -1764,7 +1088,7 @@ int reserve_frontend(pislam_ctx *c, const pislam_frontend_params *p, const pisla
     return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(fused staging)");
   if (P.alias) PCHK(prepare_ovf(c, P.nsub, P.ovf_stride));
   if (P.nsub > 1) PCHK(ensure_aux(c, P.nsub));
-  if (batch <= frame_max_batch(c)) PCHK(ensure_frame_sync(c));
+  if (batch <= frame_max_batch(c->opt)) PCHK(ensure_frame_sync(c));
   if (P.sel) {
     if (c->w_ustage.ensure(sizeof(uint32_t) * (size_t)P.Q.uslots_per_pyr * batch) != PISLAM_OK ||
         c->w_ucount.ensure(sizeof(uint32_t) * (size_t)P.Q.units_per_pyr * batch) != PISLAM_OK)
@@ -1869,7 +1193,7 @@ int launch_frame(pislam_ctx *c, const FusedCall &k) {
   hipLaunchKernelGGL(pf::k_frame, dim3(grid), dim3(pf::NT), P.flds, c->stream, F, k.pyramids, k.stride, c->w_stage.as<uint32_t>(),
                      c->w_stripcnt.as<uint32_t>(), k.kp, (size_t)p->max_keypoints, (uint32_t)p->max_keypoints, k.counts, k.desc,
                      (size_t)p->max_keypoints * p->words, p->words, (uint32_t)P.fper, P.fch, c->w_sync.as<uint32_t>(),
-                     c->w_ovf.as<uint32_t>(), c->frame_flag_dev, (uint32_t)c->opt_frame_test);
+                     c->w_ovf.as<uint32_t>(), c->frame_flag_dev, (uint32_t)c->opt.frame_test);
   PCHK(launch_ok(c, "k_frame"));
   c->last_path = PISLAM_PATH_FUSED | PISLAM_PATH_ONE_LAUNCH;
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));   // (one launch: the stage split of last_timing is all in stage 0)
@@ -1907,7 +1231,7 @@ int launch_sub_batch(pislam_ctx *c, const FusedCall &k, int sub) {
   // (profiling option "repeat_strips": the strip kernel launched n times back to back inside the stage-0
   //  event bracket, so that the per-launch duration is not inflated by the command-processor latency
   //  around a single eager launch; every launch rewrites the same outputs)
-  for (int rep = 0; rep < std::max(1, c->opt_repeat_strips); rep++) {
+  for (int rep = 0; rep < std::max(1, c->opt.repeat_strips); rep++) {
     if (rep && ovf) HIPCHK(c, hipMemsetAsync(ovf, 0, sizeof(uint32_t), M));   // the last launch's list counts
     hipLaunchKernelGGL(k.kern, grid, dim3(pf::NT), P.klds, M, F, s_pyr, k.stride, s_stage, s_cnt, s_dump, dump_stride, prof, ovf,
                        s_sdesc);
@@ -1928,7 +1252,7 @@ int launch_sub_batch(pislam_ctx *c, const FusedCall &k, int sub) {
     HIPCHK(c, hipEventRecord(c->ev[1], M));     // stage 0 = the strip kernel alone
   }
   if (P.alias) {
-    hipLaunchKernelGGL(k.okern, dim3((unsigned)std::max(8, c->num_cus / 2)), dim3(pf::NT), P.lds, X, F, s_pyr, k.stride, s_stage,
+    hipLaunchKernelGGL(k.okern, dim3((unsigned)std::max(8, c->opt.num_cus / 2)), dim3(pf::NT), P.lds, X, F, s_pyr, k.stride, s_stage,
                        s_cnt, s_dump, dump_stride, (const uint32_t *)ovf);
     PCHK(launch_ok(c, "k_fused_overflow"));
   }
@@ -2039,59 +1363,48 @@ int run_staged(pislam_ctx *c, const pislam_frontend_params *p, const pislam_leve
 
 }  // namespace
 
-// Host-only: plan a batch call for these parameters with the call's own planner (plan_frontend: no device, no allocation,
-// no launch) and check the invariants of its strip plan and bucket selection plan (strip_plan_violation, select_plan_violation).
+// Host-only: plan a batch call for these parameters with the call's own planner (fp::plan_frontend: no device, no allocation,
+// no launch) and check the invariants of its strip plan and bucket selection plan (fp::strip_plan_violation, fp::select_plan_violation).
 // For the sanitizer runs of the host code (tests/test_sanitizers.py runs thousands of random level tables through it in a library built
 // with -fsanitize=address,undefined) and for tools that want to know what a call will launch.  options: "key=value,key=value"
 // (pislam_ctx_set_option keys).  summary: [0] plan entries, [1] strips per pyramid, [2] runs per pyramid, [3] staging slots per pyramid,
 // [4] run length, [5] LDS bytes (plain layout), [6] LDS bytes (aliased layout), [7] units of the selection pass (0: none).
 PISLAM_EXPORT int pislam_debug_build_plan(const pislam_frontend_params *p, const pislam_level *lv, int batch, int num_cus,
                                           int lanes_in_flight, const char *options, uint32_t summary[8], char *err, size_t err_cap) {
-  pislam_ctx c;                                       // (never touches a device: plain members only)
-  auto say = [&](int rc) {
-    if (err && err_cap) snprintf(err, err_cap, "%s", c.err.c_str());
+  auto say = [&](int rc, const char *prefix, const char *what) {
+    if (err && err_cap) snprintf(err, err_cap, "%s%s", prefix, what);
     return rc;
   };
-  auto bad = [&](const char *what) {
-    c.err = std::string("plan invariant violated: ") + what;
-    return say(PISLAM_ERR_HIP);
-  };
-  c.num_cus = num_cus > 0 ? num_cus : 256;
-  c.lanes_in_flight = lanes_in_flight > 0 ? lanes_in_flight : 1;
+  auto refuse = [&](const char *what) { return say(PISLAM_ERR_INVALID, "", what); };
+  auto bad = [&](const char *what) { return say(PISLAM_ERR_HIP, "plan invariant violated: ", what); };
+  fp::Options o;
+  o.num_cus = num_cus > 0 ? num_cus : 256;
+  o.lanes_in_flight = lanes_in_flight > 0 ? lanes_in_flight : 1;
   if (!summary) return PISLAM_ERR_INVALID;
   memset(summary, 0, sizeof(uint32_t) * 8);
   for (const char *q = options; q && *q;) {
     const char *e = strchr(q, ','), *eq = strchr(q, '=');
     const size_t len = e ? (size_t)(e - q) : strlen(q);
-    if (!eq || (size_t)(eq - q) >= len) {
-      c.err = "options: key=value[,key=value...]";
-      return say(PISLAM_ERR_INVALID);
-    }
+    if (!eq || (size_t)(eq - q) >= len) return refuse("options: key=value[,key=value...]");
     const std::string key(q, eq - q);
-    if (key == "own_stream") {
-      c.err = "own_stream needs a device";
-      return say(PISLAM_ERR_INVALID);
-    }
-    const int rc = pislam_ctx_set_option(&c, key.c_str(), atoi(eq + 1));
-    if (rc != PISLAM_OK) return say(rc);
+    if (key == "own_stream") return refuse("own_stream needs a device");
+    const char *refusal = nullptr;
+    if (key != "frame_rearm" && !fp::set_option(o, key.c_str(), atoi(eq + 1), &refusal)) refusal = "unknown option";
+    if (refusal) return refuse(refusal);
     q += len + (e ? 1 : 0);
   }
-  const int rc = check_params(&c, p, lv, batch);
-  if (rc != PISLAM_OK) return say(rc);
+  if (const char *refusal = fp::check_params(p, lv, batch)) return refuse(refusal);
   FrontendPlan P;
-  const int plan_rc = plan_frontend(&c, p, lv, batch, &P);
-  if (!P.fused) {
-    c.err = "no strip plan for these parameters (the staged pipeline takes the call)";
-    return say(PISLAM_ERR_INVALID);
-  }
-  if (const char *what = strip_plan_violation(P, p)) return bad(what);
+  const char *plan_refusal = fp::plan_frontend(o, p, lv, batch, &P);
+  if (!P.fused) return refuse("no strip plan for these parameters (the staged pipeline takes the call)");
+  if (const char *what = fp::strip_plan_violation(P, p)) return bad(what);
   const uint32_t strip_summary[7] = {(uint32_t)P.F.nlevels,       (uint32_t)P.F.strips_per_pyr, (uint32_t)P.F.runs_per_pyr,
                                      (uint32_t)P.F.slots_per_pyr, (uint32_t)P.F.run_len,        (uint32_t)P.lds,
                                      (uint32_t)P.lds_alias};
   memcpy(summary, strip_summary, sizeof(strip_summary));
-  if (plan_rc != PISLAM_OK) return say(plan_rc);   // (a refusal of the selection plan: reported after the strip plan checks)
+  if (plan_refusal) return refuse(plan_refusal);   // (a refusal of the selection plan: reported after the strip plan checks)
   if (P.sel) {
-    if (const char *what = select_plan_violation(P, p)) return bad(what);
+    if (const char *what = fp::select_plan_violation(P, p)) return bad(what);
     summary[7] = (uint32_t)P.Q.units_per_pyr;
   }
   return PISLAM_OK;
@@ -2119,7 +1432,7 @@ PISLAM_EXPORT int pislam_orb_frontend_batch(pislam_ctx *c, const pislam_frontend
     return fail(c, PISLAM_ERR_INVALID, "the batch path takes device pointers only");
   FrontendPlan P;
   PCHK(plan_frontend(c, p, lv, batch, &P));
-  if (c->opt_pipeline >= 2 && !P.fused)
+  if (c->opt.pipeline >= 2 && !P.fused)
     return fail(c, PISLAM_ERR_INVALID, "fused pipeline unavailable for these parameters (bucket size / LDS size)");
   PCHK(reserve_frontend(c, p, lv, P, batch));
   c->last_stride = (size_t)p->rows * p->vstep;
@@ -2144,7 +1457,7 @@ PISLAM_EXPORT int pislam_frontend_get_score_map(pislam_ctx *c, int b, uint8_t *d
   if (!c || !dst) return PISLAM_ERR_INVALID;
   if (b < 0 || b >= c->last_batch || !c->w_score.p || !c->last_stride)
     return fail(c, PISLAM_ERR_INVALID, "no score map for that pyramid");
-  if (c->last_pipeline == 2 && !c->opt_dump_score)
+  if (c->last_pipeline == 2 && !c->opt.dump_score)
     return fail(c, PISLAM_ERR_INVALID, "the fused pipeline keeps the score map in LDS (set option dump_score)");
   HIPCHK(c, hipSetDevice(c->device));
   const size_t bytes = c->last_stride;
@@ -2160,7 +1473,7 @@ PISLAM_EXPORT int pislam_frontend_last_stats(pislam_ctx *c, uint32_t stats[2]) {
   HIPCHK(c, hipSetDevice(c->device));
   PCHK(sync(c));
   PCHK(check_frame_poison(c));
-  uint32_t prev[pislam_ctx::MAX_SUB] = {};
+  uint32_t prev[fp::MAX_SUB] = {};
   for (int i = 0; i < c->ovf_nsub; i++)          // one list per sub-batch: [1] = strips the last step deferred
     HIPCHK(c, hipMemcpyAsync(&prev[i], c->w_ovf.as<uint32_t>() + (size_t)i * c->ovf_stride + 1, sizeof(uint32_t),
                              hipMemcpyDeviceToHost, c->stream));
@@ -2259,12 +1572,12 @@ int launch_match(pislam_ctx *c, int words, const uint32_t *q, const uint32_t *qc
                  int32_t *idx, uint32_t *dist, uint32_t *dist2, size_t out_stride) {
   PCHK(check_words(c, words));
   const uint32_t cap_q = (uint32_t)std::min<size_t>(q_stride, 0xffffffffu), cap_t = (uint32_t)std::min<size_t>(t_stride, 65535);
-  if (c->opt_match_mfma) {
+  if (c->opt.match_mfma) {
     // matrix-core path (v_mfma_i32_32x32x32_i8): 4 waves x 32 queries per workgroup pass
     // query blocks per pair in flight: the batch API only knows the capacity (the counts live on the device), and a
     // workgroup that finds no queries still costs its launch (~30 ns each: 32 blocks per pair at batch 256 took
     // 0.27 ms against 0.09 ms with 8), so the grid aims at ~8 workgroups per CU and the workgroups loop
-    const int per_pair = batch > 1 ? std::max(1, std::min(cdiv((int)max_q, pm::MF_Q), cdiv(8 * std::max(1, c->num_cus), batch))) : 65535;
+    const int per_pair = batch > 1 ? std::max(1, std::min(cdiv((int)max_q, pm::MF_Q), cdiv(8 * std::max(1, c->opt.num_cus), batch))) : 65535;
     const dim3 mgrid((unsigned)std::min(cdiv((int)max_q, pm::MF_Q), per_pair), (unsigned)batch);
     with_words(words, [&](auto w) {
       constexpr int W = decltype(w)::value;
@@ -2426,7 +1739,7 @@ int device_ptrs(pislam_ctx *c, std::initializer_list<const void *> ptrs, const c
 // for the capacity and aims at ~16 workgroups per CU over the batch; a workgroup loops over further tiles of its pair.
 dim3 query_grid(const pislam_ctx *c, size_t q_stride, int qpw, int batch) {
   const int tiles = cdiv((int)std::min<size_t>(q_stride, 0x7fffffff - qpw), qpw);
-  const int per_pair = batch > 1 ? std::max(1, std::min(tiles, cdiv(16 * std::max(1, c->num_cus), batch))) : std::min(tiles, 65535);
+  const int per_pair = batch > 1 ? std::max(1, std::min(tiles, cdiv(16 * std::max(1, c->opt.num_cus), batch))) : std::min(tiles, 65535);
   return dim3((unsigned)per_pair, (unsigned)batch);
 }
 
@@ -2958,7 +2271,7 @@ PISLAM_EXPORT int pislam_warp_batch(pislam_ctx *c, const pislam_warp *w, const u
   a.mesh_x = w->mesh.as<int32_t>(), a.mesh_y = a.mesh_x + (size_t)w->mesh_w * w->mesh_h;
   a.mesh_w = w->mesh_w, a.log_cell = w->log_cell, a.width = w->width, a.height = w->height;
   a.src_width = w->src_width, a.src_height = w->src_height, a.border = w->border, a.tiles_x = w->tiles_x;
-  a.direct = c->opt_warp_direct;
+  a.direct = c->opt.warp_direct;
   a.src_vstep = src_vstep, a.src_stride = src_stride, a.dst_vstep = dst_vstep, a.dst_stride = dst_stride;
   for (int b0 = 0; b0 < batch; b0 += 65535) {                // (grid.y)
     const int nb = std::min(batch - b0, 65535);
@@ -3008,9 +2321,9 @@ int clahe_launch(pislam_ctx *c, pc::Args a, int batch, bool apply) {
     const dim3 grid(gx, (unsigned)std::min(batch - b0, 65535)), block(pc::THREADS);
     a.src = src + (size_t)b0 * a.src_stride, a.luts = luts + (size_t)b0 * ntiles * 256;
     if (apply) a.dst = dst + (size_t)b0 * a.dst_stride;
-    if (!apply && c->opt_clahe_combine) hipLaunchKernelGGL(pc::k_clahe_luts<true>, grid, block, 0, c->stream, a);
+    if (!apply && c->opt.clahe_combine) hipLaunchKernelGGL(pc::k_clahe_luts<true>, grid, block, 0, c->stream, a);
     else if (!apply) hipLaunchKernelGGL(pc::k_clahe_luts<false>, grid, block, 0, c->stream, a);
-    else if (c->opt_clahe_lut_global) hipLaunchKernelGGL(pc::k_clahe_apply<false>, grid, block, 0, c->stream, a);
+    else if (c->opt.clahe_lut_global) hipLaunchKernelGGL(pc::k_clahe_apply<false>, grid, block, 0, c->stream, a);
     else hipLaunchKernelGGL(pc::k_clahe_apply<true>, grid, block, 0, c->stream, a);
     PCHK(launch_ok(c, apply ? "k_clahe_apply" : "k_clahe_luts"));
   }
@@ -3440,7 +2753,7 @@ PISLAM_EXPORT int pislam_pipeline_create(int device, int depth, pislam_pipeline 
     pislam_ctx *c = nullptr;
     int rc = pislam_ctx_create(device, &c);
     if (rc == PISLAM_OK) rc = use_own_stream(c, 2);
-    if (rc == PISLAM_OK) c->lanes_in_flight = depth;
+    if (rc == PISLAM_OK) c->opt.lanes_in_flight = depth;
     hipEvent_t e = nullptr;
     if (rc == PISLAM_OK && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) rc = PISLAM_ERR_HIP;
     if (c) {

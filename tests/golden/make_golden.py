@@ -18,6 +18,15 @@
                        is_device_ptr, the HIP calls and the launches replaced by stubs that record them, and the line was
                        printed from inside it (docs/experiments.md section V).  A planner that is meant to change plans
                        re-records it as `prep_host_check --dump`.
+  frontend_plan_cases.txt : the fixed named cases tools/probes/frontend_host_check.cpp and tests/test_frontend_plan_golden.py
+                       run, one per line (`make_golden.py plan-cases`); the test appends tests/plan_fuzz.py's generated_lines().
+  frontend_plans.json: per case (fixed by name, seeds in order, options by key in the order of their values) the first 16 hex digits of the SHA-256 of its fp::plan_digest line, as
+                       the planner answered before it moved into pislam_frontend_plan.h.  Not made by this script: in a
+                       scratch copy of that commit plan_digest was pasted behind FrontendPlan and one extra exported function
+                       made the digest the way frontend_host_check does (options through pislam_ctx_set_option on a stack
+                       context, check_params, plan_frontend; the refusal is the context's error text); that library was built
+                       with `python -m pislam_amd.build` and called through ctypes for every case line (docs/experiments.md
+                       section X).  A planner that is meant to change plans re-records it from `frontend_host_check --dump`.
 """
 import hashlib
 import os
@@ -83,9 +92,30 @@ def plan_summaries():
     print("plan_summaries.json ok:", len(cases), "cases,", len(options), "options")
 
 
+def plan_cases():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import plan_fuzz
+    vga, par = plan_fuzz.vga_case(log_bucket_size=0)
+    lines = [plan_fuzz.case_line(f"vga-b{b}", vga, par, b, 256, 1, "") for b in (1, 2, 3, 64, 256)]
+    lines.append(plan_fuzz.case_line("vga-b256-lanes3", vga, par, 256, 256, 3, ""))
+    lines.append(plan_fuzz.case_line("vga-b256-sub3", vga, par, 256, 256, 1, "sub_batches=3"))
+    lines.append(plan_fuzz.case_line("vga-b256-buckets", *plan_fuzz.vga_case(), 256, 256, 1, ""))
+    wide = synth.packed_level_table()                          # 1280 x 960: the two largest levels are cut into x-tiles
+    lines.append(plan_fuzz.case_line("1280x960-b256", wide, dict(par, vstep=1280, rows=synth.pyramid_rows(wide)), 256, 256, 1, ""))
+    narrow = [(31, 40, 0, 0), (26, 33, 40, 0)]                 # every level narrower than 2 x border: strips_per_pyr == 0
+    lines.append(plan_fuzz.case_line("narrower-than-the-border", narrow, dict(par, vstep=32, rows=73, nlevels=2), 4, 256, 1, ""))
+    tiled = [(832, 40, 40 * i, 0) for i in range(12)] + [(100, 40, 480, 0)]   # 12 levels of two x-tiles + one: 25 plan entries
+    lines.append(plan_fuzz.case_line("25-plan-entries", tiled, dict(par, vstep=832, rows=520, nlevels=13), 64, 256, 1, ""))
+    with open(os.path.join(HERE, "frontend_plan_cases.txt"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("frontend_plan_cases.txt ok:", len(lines), "fixed cases")
+
+
 def main():
     if sys.argv[1:] == ["plans"]:
         return plan_summaries()
+    if sys.argv[1:] == ["plan-cases"]:
+        return plan_cases()
     from PIL import Image
     img = np.ascontiguousarray(np.array(Image.open("/root/reference/demo/input.png")))
     levels = synth.level_table()

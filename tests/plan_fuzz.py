@@ -3,7 +3,8 @@ host-only plan builder (pislam_debug_build_plan: strip plan, launch order, bucke
 with the sanitizer build of the library (tools/asan_round.sh: PISLAM_HIP_LIB + the ASan runtime preloaded), every
 out-of-bounds access, signed overflow or invalid shift of the host code on that path aborts the process.
 
-usage: python tests/plan_fuzz.py <cases> [<first seed>]      prints "<ok> plans, <refused> refused, 0 violations" """
+usage: python tests/plan_fuzz.py <cases> [<first seed>]      prints "<ok> plans, <refused> refused, 0 violations"
+       python tests/plan_fuzz.py lines [<cases> <first seed>]  prints cases as lines for tools/probes/frontend_host_check.cpp """
 import ctypes
 import os
 import sys
@@ -59,10 +60,13 @@ def case(seed):
     return levels, par, opts, batch, cus, lanes
 
 
+PARAM_FIELDS = ("vstep", "rows", "nlevels", "border", "fast_threshold", "harris_threshold", "log_bucket_size", "bucket_limit",
+                "words", "max_keypoints")
+
+
 def build_plan(lib, levels, par, batch, cus, lanes, options):
     """One call of pislam_debug_build_plan: (return code, summary[0..7], error string)."""
-    P = capi.FrontendParams(*[par[k] for k in ("vstep", "rows", "nlevels", "border", "fast_threshold", "harris_threshold",
-                                               "log_bucket_size", "bucket_limit", "words", "max_keypoints")])
+    P = capi.FrontendParams(*[par[k] for k in PARAM_FIELDS])
     L = (capi.Level * len(levels))(*[capi.Level(*t) for t in levels])
     summary = (ctypes.c_uint32 * 8)()
     err = ctypes.create_string_buffer(256)
@@ -70,9 +74,25 @@ def build_plan(lib, levels, par, batch, cus, lanes, options):
     return rc, list(summary), err.value.decode()
 
 
+def options_string(opts):
+    return ",".join(f"{k}={v}" for k, v in opts.items())
+
+
 def run_case(lib, seed):
     levels, par, opts, batch, cus, lanes = case(seed)
-    return build_plan(lib, levels, par, batch, cus, lanes, ",".join(f"{k}={v}" for k, v in opts.items()))
+    return build_plan(lib, levels, par, batch, cus, lanes, options_string(opts))
+
+
+def case_line(name, levels, par, batch, cus, lanes, options):
+    """A case as one line of the text tools/probes/frontend_host_check.cpp reads (tests/golden/frontend_plan_cases.txt): name,
+    the ten parameter fields, batch, CUs, lanes, the options string (- for none), then width height row0 col0 of every level."""
+    words = [name] + [par[k] for k in PARAM_FIELDS] + [batch, cus, lanes, options or "-"] + [v for t in levels for v in t]
+    return " ".join(str(w) for w in words)
+
+
+def seed_line(seed):
+    levels, par, opts, batch, cus, lanes = case(seed)
+    return case_line(f"seed{seed}", levels, par, batch, cus, lanes, options_string(opts))
 
 
 # Every key of pislam_ctx_set_option, and the values that straddle its range checks (tests/test_plan_golden.py passes each
@@ -84,15 +104,40 @@ OPTION_KEYS = ("pipeline", "own_stream", "dump_score", "repeat_strips", "alias",
 OPTION_VALUES = (-1, 0, 1, 5, 64, 65, 100000)
 
 
-def run_option(lib, key, value):
+def vga_case(log_bucket_size=4):
+    """The VGA level table and parameters of tests/test_abi.py (there without buckets; the option cases use 16-pixel ones)."""
     from pislam_amd import synth
     levels = [(w, h, r0, 0) for w, h, r0 in synth.level_table()]
-    par = dict(vstep=640, rows=2210, nlevels=8, border=16, fast_threshold=20, harris_threshold=1 << 15, log_bucket_size=4,
-               bucket_limit=3, words=8, max_keypoints=4096)
+    par = dict(vstep=640, rows=2210, nlevels=8, border=16, fast_threshold=20, harris_threshold=1 << 15,
+               log_bucket_size=log_bucket_size, bucket_limit=3, words=8, max_keypoints=4096)
+    return levels, par
+
+
+def run_option(lib, key, value):
+    levels, par = vga_case()
     return build_plan(lib, levels, par, 256, 256, 1, f"{key}={value}")
 
 
+def option_line(key, value):
+    levels, par = vga_case()
+    return case_line(f"{key}={value}", levels, par, 256, 256, 1, f"{key}={value}")
+
+
+# The generated cases of tests/test_frontend_plan_golden.py, behind the fixed ones of tests/golden/frontend_plan_cases.txt:
+# these seeds, then every option of fp::Options (own_stream and frame_rearm belong to the context) with every value.
+CASE_SEEDS = range(0, 400)
+
+
+def generated_lines():
+    return [seed_line(s) for s in CASE_SEEDS] + [option_line(k, v) for k in OPTION_KEYS if k not in ("own_stream", "frame_rearm")
+                                                 for v in OPTION_VALUES]
+
+
 def main():
+    if sys.argv[1:2] == ["lines"]:                    # lines [<seeds> <first seed>]: cases for tools/probes/frontend_host_check.cpp
+        lines = [seed_line(s) for s in range(int(sys.argv[3]), int(sys.argv[3]) + int(sys.argv[2]))] if len(sys.argv) > 3 else generated_lines()
+        print("\n".join(lines))
+        return 0
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
     first = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     lib = capi.load(rebuild_if_stale=False)
