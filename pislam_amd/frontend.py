@@ -191,8 +191,11 @@ def matchHamming(query, train, *, ctx: Context | None = None):
 
 def matchHammingBatch(qdesc, qcounts, tdesc, tcounts, idx=None, dist=None, dist2=None, *, ctx: Context | None = None):
     """Batched matcher on device-resident front-end outputs (torch tensors [batch][max_kp][words] and
-    [batch] counts, as OrbFrontend writes them): pair b matches qdesc[b] against tdesc[b].  Returns
-    (idx int32, dist int32, dist2 int32) tensors [batch][max_kp]; asynchronous on the ctx stream."""
+    [batch] counts, as OrbFrontend writes them): pair b matches the first min(qcounts[b], q_stride) descriptors of
+    qdesc[b] against the first min(tcounts[b], t_stride) of tdesc[b] (t_stride <= 65535).  Returns (idx, dist, dist2)
+    int32 tensors [batch][q_stride]: idx as matchHamming; dist and dist2 hold the library's uint32 values viewed as
+    int32, so "none" (0xffffffff: no train descriptor, or for dist2 fewer than two) reads as -1.  Entries at and beyond
+    a pair's query count are not written.  Asynchronous on the ctx stream."""
     import torch
     ctx = ctx or default_context()
     batch, qs, words = qdesc.shape
