@@ -1013,6 +1013,93 @@ int pislam_bowdb_query_batch(pislam_ctx *ctx, const pislam_bowdb *db, const uint
                              const uint32_t *q_n, size_t stride, int batch, const int32_t *id_limit, int min_common_pct,
                              int topk, int32_t *top_id, uint32_t *top_score, uint32_t *top_common, uint32_t *max_common);
 
+/* ---- two-view geometry: batched RANSAC for F and H ------------------------ */
+
+/* Geometric verification of matched point lists: per pair, a fundamental matrix (model 0) or a
+ * homography (model 1) by RANSAC over a FIXED number of hypotheses, scored as ORB-SLAM's Initializer scores them
+ * (CheckFundamental / CheckHomography), with the inlier mask of the winner.  Run it once per model and compare the
+ * scores (SH / (SH + SF)) to choose between them.  The reference ships nothing of the kind: the semantics are this
+ * library's own, stated so that integers and individually rounded binary32 operations reproduce every output word.
+ * This comment is the contract.  "float(v)" is the conversion of an integer to binary32, round to nearest even; every
+ * +, -, *, / below on floats is ONE binary32 operation rounded to nearest even, in the order the parentheses give
+ * (a + b + c means (a + b) + c); no fused multiply-add, no reciprocal or fast-division approximation, no square root;
+ * denormals are kept.
+ *
+ * Inputs.  p1_q8, p2_q8: device int32 [batch][stride][2], (x, y) of match i of pair b in image 1 and image 2, level-0
+ * pixels in Q8.  counts: device uint32 [batch]; n = min(counts[b], stride), PISLAM_COUNT_INVALID counts as 0.  Every
+ * coordinate is clamped to [-2^20, 2^20] first.  m = 8 (model 0) or 4 (model 1) matches make a hypothesis.
+ *
+ * Normalisation, per image, in signed 64-bit integers: Sx = sum x_i, Sy = sum y_i, ex_i = n * x_i - Sx,
+ * ey_i = n * y_i - Sy, D = sum |ex_i| + sum |ey_i| (below 2^53 for stride <= 16384).  With k = float(2 * n * n) /
+ * float(D), the normalised point is (float(ex_i) * k, float(ey_i) * k); one scale per image, so a normalised distance
+ * is a pixel distance times s = (256.0f * float(n)) * k.  Below, (x1, y1) and (x2, y2) are the normalised points of a
+ * match, and w_I = 1.0f / (t_I * t_I) with t_I = s_I * (float(sigma_q8) / 256.0f) for image I = 1, 2.
+ * n < m, D1 == 0 or D2 == 0: "no model" (see Outputs).
+ *
+ * Sampling.  mix(x) on uint32: x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.
+ *   hash(b, k, j) = mix(mix(mix(seed + 0x9e3779b9 * b) ^ (0x85ebca6b * (k + 1))) ^ (0xc2b2ae35 * (j + 1)))   (mod 2^32)
+ * Draw j = 0 .. m - 1 of hypothesis k of pair b: r = (hash(b, k, j) * (n - j)) >> 32 (64-bit product), then for every
+ * index c drawn before, in ASCENDING order of c: if r >= c then r += 1.  The m indices are distinct, and n == m draws
+ * every match.  Row order below is draw order.
+ *
+ * Solve.  An 8 x 9 system [A | b] whose unknowns are the first eight model entries, row-major; the ninth is 1.0f.
+ *   model 0, one row per drawn match:  x2*x1, x2*y1, x2, y2*x1, y2*y1, y2, x1, y1 | -1.0f       (x2' F x1 = 0)
+ *   model 1, two rows per drawn match: x1, y1, 1, 0, 0, 0, -(x2*x1), -(x2*y1) | x2
+ *                                      0, 0, 0, x1, y1, 1, -(y2*x1), -(y2*y1) | y2              (x2 ~ H x1)
+ * Gaussian elimination with partial pivoting, for c = 0 .. 7:
+ *   for r = c+1 .. 7 in turn: if |A[r][c]| > |A[c][c]|, rows r and c are exchanged (so row c ends as the FIRST row of
+ *     largest magnitude in column c; the rows passed over stay in the order this leaves them in);
+ *   the hypothesis is invalid unless |A[c][c]| >= 2^-20 (a NaN fails);
+ *   inv = 1.0f / A[c][c];  for r = c+1 .. 7: f = A[r][c] * inv;  for j = c+1 .. 8: A[r][j] = A[r][j] - f * A[c][j].
+ * Back substitution, r = 7 .. 0: t = A[r][8]; for j = r+1 .. 7 ascending: t = t - A[r][j] * x[j];  x[r] = t / A[r][r].
+ * The hypothesis is also invalid when an x[r] is not finite.  An invalid hypothesis scores 0.  F is NOT forced to
+ * rank 2: a caller who decomposes it does that on the host, after refitting from the inliers.
+ *
+ * Scoring.  For a 3 x 3 matrix M (row-major m0 .. m8) and points (xa, ya), (xb, yb):
+ *   line(M, a, b, w):     A = (m0*xa + m1*ya) + m2,  B = (m3*xa + m4*ya) + m5,  C = (m6*xa + m7*ya) + m8,
+ *                         N = (A*xb + B*yb) + C,  chi2 = ((N*N) / (A*A + B*B)) * w
+ *   transfer(M, a, b, w): I = 1.0f / ((m6*xa + m7*ya) + m8),  u = ((m0*xa + m1*ya) + m2) * I,
+ *                         v = ((m3*xa + m4*ya) + m5) * I,  du = xb - u, dv = yb - v,  chi2 = (du*du + dv*dv) * w
+ *   model 0: chi2_a = line(F, p1, p2, w_2), chi2_b = line(F transposed, p2, p1, w_1); th = 3.841f.
+ *   model 1: chi2_a = transfer(H, p1, p2, w_2), chi2_b = transfer(G, p2, p1, w_1); th = 5.991f.  G is the adjugate of
+ *     H (no division by the determinant): g0 = h4*h8 - h5*h7, g1 = h2*h7 - h1*h8, g2 = h1*h5 - h2*h4,
+ *     g3 = h5*h6 - h3*h8, g4 = h0*h8 - h2*h6, g5 = h2*h3 - h0*h5, g6 = h3*h7 - h4*h6, g7 = h1*h6 - h0*h7,
+ *     g8 = h0*h4 - h1*h3.
+ * A direction passes when chi2 < th (a NaN fails) and then adds (uint32)floor((5.991f - chi2) * 256.0f) to the
+ * hypothesis's score; a match is an inlier when both directions pass.  Scores are integer sums (at most
+ * 2 * 1534 * 16384).  The hypothesis of largest score wins, ties go to the smallest k; a largest score of 0 is "no
+ * model".  No float is ever summed across matches or hypotheses, so no result depends on an order of execution.
+ *
+ * Outputs, per pair, all device: best (int32) = the winning k, or -1 for "no model" (n < m, D == 0, every hypothesis
+ * invalid, or no score above 0); score, ninliers (uint32; 0 for "no model"); inlier uint8 [batch][stride], 0 or 1 for
+ * i < n (all 0 for "no model"), entries at and beyond n are not written; model_n float [batch][9], the winner in
+ * NORMALISED coordinates, row-major, last entry 1.0f (nine zeros for "no model"); stats int64 [batch][8] =
+ * {n, Sx1, Sy1, D1, Sx2, Sy2, D2, 0}, always written.
+ *
+ * pislam_two_view_denormalise (host only, pure, no context): the level-0-PIXEL matrix in double from one row of
+ * model_n and of stats, out = T2' * Fn * T1 (model 0) or inverse(T2) * Hn * T1 (model 1), with
+ * T = [s 0 -Sx*k; 0 s -Sy*k; 0 0 1], k = 2 n n / D and s = 256 n k in double.  PISLAM_ERR_INVALID for a NULL pointer,
+ * a model other than 0 / 1, n < 1 or a D < 1.
+ *
+ * Limits: the parameter ranges in the struct comments; 1 <= stride <= 16384; batch >= 0 with no upper limit (batch ==
+ * 0 is a no-op that returns PISLAM_OK after the checks of p, batch and stride; the pointers are not looked at then).
+ * Offsets use size_t arithmetic throughout.  No output may overlap an input or another output.  Any violation, or a
+ * NULL or host pointer where a device pointer is required: PISLAM_ERR_INVALID, before anything is launched or
+ * written.  `p` is a host struct, read during the call.  Asynchronous on the context stream; no workspace (the models
+ * of a pair live in LDS), no host round trip: the call can be captured into a hipGraph as it is, so there is no
+ * reserve call.  One workgroup works on a pair; a batch above 1024 pairs is walked by the same 1024 workgroups in
+ * passes. */
+typedef struct pislam_two_view_params {
+  int32_t model;       /* 0 = fundamental matrix (m = 8), 1 = homography (m = 4) */
+  int32_t hypotheses;  /* 1..1024, all of them are evaluated (ORB-SLAM: 200) */
+  uint32_t seed;       /* any */
+  int32_t sigma_q8;    /* measurement sigma in Q8 level-0 pixels, 1..4096 (ORB-SLAM: 256) */
+} pislam_two_view_params;
+int pislam_two_view_ransac_batch(pislam_ctx *ctx, const pislam_two_view_params *p, const int32_t *p1_q8,
+                                 const int32_t *p2_q8, const uint32_t *counts, size_t stride, int batch, int32_t *best,
+                                 uint32_t *score, uint32_t *ninliers, uint8_t *inlier, float *model_n, int64_t *stats);
+int pislam_two_view_denormalise(int model, const float *model_n, const int64_t *stats_row, double out[9]);
+
 /* ---- multi-GPU: one process per GPU, pyramids sharded, ONE collective ---- */
 
 /* The reference is a single-threaded per-frame loop without cross-frame state

@@ -45,6 +45,11 @@ class SelectParams(ctypes.Structure):
         "max_dist", "ratio_num", "ratio_den", "unique", "rot_keep", "rot_min_pct")]
 
 
+class TwoViewParams(ctypes.Structure):
+    _fields_ = [("model", ctypes.c_int32), ("hypotheses", ctypes.c_int32), ("seed", ctypes.c_uint32),
+                ("sigma_q8", ctypes.c_int32)]
+
+
 class ClaheParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "tiles_x", "tiles_y", "clip_q8")]
 
@@ -135,6 +140,10 @@ SYMBOLS = {
     "pislam_orb_angles_batch": (_i, [_vp, _vp, _i, _i, _sz, _vp, _vp, _sz, _i, _vp]),
     "pislam_match_select_batch": (_i, [_vp, ctypes.POINTER(SelectParams), _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp,
                                        _i, _vp, _vp, _vp, _vp, _vp]),
+    "pislam_two_view_ransac_batch": (_i, [_vp, ctypes.POINTER(TwoViewParams), _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp,
+                                          _vp]),
+    "pislam_two_view_denormalise": (_i, [_i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64),
+                                         ctypes.POINTER(ctypes.c_double)]),
     "pislam_bow_weight_batch": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, ctypes.c_uint32, _vp]),
     "pislam_bowdb_create": (_i, [_vp, ctypes.c_uint32, _sz, _i, ctypes.POINTER(_vp)]),
     "pislam_bowdb_destroy": (_i, [_vp]),

@@ -58,6 +58,8 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_bow_kernels.h"
 #include "pislam_bowdb_kernels.h"
 #include "pislam_select_kernels.h"
+#include "pislam_geom_kernels.h"
+#include "pislam_geom_host.h"
 #include "pislam_warp_kernels.h"
 #include "pislam_clahe_kernels.h"
 
@@ -2424,6 +2426,52 @@ PISLAM_EXPORT int pislam_match_select_batch(pislam_ctx *c, const pislam_select_p
   A.sel_q = sel_q, A.sel_t = sel_t, A.nsel = nsel, A.status = status, A.rot_hist = rot_hist;
   hipLaunchKernelGGL(ps::k_match_select, dim3((unsigned)batch), dim3(ps::SEL_THREADS), ps::SEL_LDS_BYTES, c->stream, A);
   return launch_ok(c, "k_match_select");
+}
+
+// ---- two-view geometry: batched RANSAC for F and H -----------------------------------------
+
+PISLAM_EXPORT int pislam_two_view_ransac_batch(pislam_ctx *c, const pislam_two_view_params *p, const int32_t *p1_q8,
+                                               const int32_t *p2_q8, const uint32_t *counts, size_t stride, int batch,
+                                               int32_t *best, uint32_t *score, uint32_t *ninliers, uint8_t *inlier,
+                                               float *model_n, int64_t *stats) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
+  if (p->model != 0 && p->model != 1) return fail(c, PISLAM_ERR_INVALID, "model must be 0 (fundamental) or 1 (homography)");
+  if (p->hypotheses < 1 || p->hypotheses > pg::TV_MAX_HYP) return fail(c, PISLAM_ERR_INVALID, "hypotheses must be 1..1024");
+  if (p->sigma_q8 < 1 || p->sigma_q8 > 4096) return fail(c, PISLAM_ERR_INVALID, "sigma_q8 must be 1..4096");
+  if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
+  if (stride < 1 || stride > (size_t)pg::TV_MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
+  if (batch == 0) return PISLAM_OK;
+  PCHK(device_ptrs(c, {p1_q8, p2_q8, counts, best, score, ninliers, inlier, model_n, stats},
+                   "the two-view call takes device pointers only"));
+  {
+    const size_t B = (size_t)batch, pts = B * stride * 2 * sizeof(int32_t), word = B * sizeof(uint32_t);
+    const LkRange in[] = {{p1_q8, pts}, {p2_q8, pts}, {counts, word}};
+    const LkRange out[] = {{best, word}, {score, word}, {ninliers, word}, {inlier, B * stride},
+                           {model_n, B * 9 * sizeof(float)}, {stats, B * 8 * sizeof(int64_t)}};
+    for (int o = 0; o < 6; o++) {
+      for (int i = 0; i < 3; i++)
+        if (lk_overlap(out[o], in[i])) return fail(c, PISLAM_ERR_INVALID, "an output overlaps an input");
+      for (int k = 0; k < o; k++)
+        if (lk_overlap(out[o], out[k])) return fail(c, PISLAM_ERR_INVALID, "two outputs overlap");
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  pg::TvArgs a{};
+  a.p1 = p1_q8, a.p2 = p2_q8, a.counts = counts, a.stride = stride, a.batch = batch, a.hypotheses = p->hypotheses;
+  a.seed = p->seed, a.sigma = (float)p->sigma_q8 / 256.0f;   // exact: an integer below 2^13 over a power of two
+  a.best = best, a.score = score, a.ninliers = ninliers, a.inlier = inlier, a.model_n = model_n;
+  a.stats = (long long *)stats;
+  const dim3 grid((unsigned)std::min(batch, pg::TV_GRID_CAP));
+  if (p->model == 0)
+    hipLaunchKernelGGL(pg::k_two_view<0>, grid, dim3(pg::TV_THREADS), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(pg::k_two_view<1>, grid, dim3(pg::TV_THREADS), 0, c->stream, a);
+  return launch_ok(c, "k_two_view");
+}
+
+PISLAM_EXPORT int pislam_two_view_denormalise(int model, const float *model_n, const int64_t *stats_row, double out[9]) {
+  return pgh::two_view_denormalise(model, model_n, stats_row, out) ? PISLAM_OK : PISLAM_ERR_INVALID;
 }
 
 // ---- bag of words: integer weights and the key-frame database -----------------------------

@@ -17,7 +17,8 @@ import ctypes
 import numpy as np
 
 from . import capi
-from .capi import ClaheParams, Context, FrontendParams, Level, LkParams, SelectParams, StereoParams, ptr
+from .capi import (ClaheParams, Context, FrontendParams, Level, LkParams, SelectParams, StereoParams, TwoViewParams,
+                   ptr)
 
 _default_ctx: Context | None = None
 
@@ -707,6 +708,133 @@ def selectMatchesBatch(idx, dist, dist2, qcounts, tcounts, *, max_dist=50, ratio
     if rot_hist is not None:
         out += (rot_hist,)
     return out
+
+
+# ---- two-view geometry: batched RANSAC for F and H ----------
+TWO_VIEW_MAX_STRIDE = 16384   # matches per pair (pislam_two_view_ransac_batch)
+_TWO_VIEW_MODELS = {0: 0, 1: 1, "F": 0, "H": 1, "fundamental": 0, "homography": 1}
+
+
+def matchedPointsQ8(qkp, tkp, sel, levels, scale_q16=None, refined=None):
+    """The matched point lists of twoViewRansacBatch from selectMatchesBatch's compacted lists: sel = (sel_q, sel_t,
+    nsel); slot s < nsel[b] pairs query keypoint qkp[b][sel_q[b][s]] (image 1) with train keypoint tkp[b][sel_t[b][s]]
+    (image 2).  Each keypoint is mapped from its level to level 0 by the header's formula, per axis with the
+    level-local Q8 coordinate u: floor((u * s_l + 32768) / 65536) in int64 (scale_q16 None = level_scales_q16(levels)).
+    refined = the next_q8 of refineMatchesBatch ([batch][q_stride][2], indexed by query, in the stacked Q8 coordinates
+    of the QUERY's level) replaces the train keypoint's position.  A match one of whose keypoints lies in no level is
+    dropped from the list.  Returns (p1_q8, p2_q8, counts): int32 [batch][q_stride][2] twice (slots at and beyond
+    counts[b] are zero) and int32 [batch].  Torch ops on the current torch stream."""
+    import torch
+    sel_q, sel_t, nsel = sel
+    batch, qs = (int(v) for v in sel_q.shape)
+    dev = sel_q.device
+    lvn = [(int(t[0]), int(t[1]), int(t[2]), int(t[3]) if len(t) > 3 else 0) for t in levels]
+    sc = level_scales_q16(levels) if scale_q16 is None else ([int(scale_q16)] * len(lvn) if isinstance(
+        scale_q16, (int, np.integer)) else [int(v) for v in scale_q16])
+    live = torch.arange(qs, device=dev)[None, :] < nsel.to(torch.int64)[:, None]
+    qi = torch.where(live, sel_q.to(torch.int64), torch.zeros_like(live, dtype=torch.int64)).clamp(0, int(qkp.shape[1]) - 1)
+    ti = torch.where(live, sel_t.to(torch.int64), torch.zeros_like(live, dtype=torch.int64)).clamp(0, int(tkp.shape[1]) - 1)
+    qk = torch.gather(qkp.to(torch.int64), 1, qi)
+    tk = torch.gather(tkp.to(torch.int64), 1, ti)
+
+    def level0(k, pos=None):
+        """Level-0 Q8 (x, y) of the stacked Q8 position `pos` (None: the keypoint itself) on the level that holds the
+        keypoint word k, and whether any level holds it."""
+        x, y = (k >> 12) & 0xFFF, k & 0xFFF
+        px, py = (x << 8, y << 8) if pos is None else (pos[..., 0], pos[..., 1])
+        X, Y, found = torch.zeros_like(k), torch.zeros_like(k), torch.zeros_like(k, dtype=torch.bool)
+        for (w, h, row0, col0), sl in zip(lvn, sc):
+            m = (x >= col0) & (x < col0 + w) & (y >= row0) & (y < row0 + h)
+            X = torch.where(m, torch.div((px - (col0 << 8)) * sl + 32768, 65536, rounding_mode="floor"), X)
+            Y = torch.where(m, torch.div((py - (row0 << 8)) * sl + 32768, 65536, rounding_mode="floor"), Y)
+            found |= m
+        return X, Y, found
+
+    x1, y1, ok1 = level0(qk)
+    if refined is None:
+        x2, y2, ok2 = level0(tk)
+    else:
+        pos = torch.gather(refined.to(torch.int64), 1, qi[..., None].expand(-1, -1, 2))
+        x2, y2, _ = level0(qk, pos)
+        ok2 = level0(tk)[2]
+    keep = live & ok1 & ok2
+    slot = torch.where(keep, torch.cumsum(keep.to(torch.int64), 1) - 1, torch.full_like(qi, qs))   # dropped: a spare column
+    out = torch.zeros((2, batch, qs + 1, 2), dtype=torch.int64, device=dev)
+    out[0].scatter_(1, slot[..., None].expand(-1, -1, 2), torch.stack([x1, y1], dim=-1))
+    out[1].scatter_(1, slot[..., None].expand(-1, -1, 2), torch.stack([x2, y2], dim=-1))
+    out = out[:, :, :qs].to(torch.int32)
+    return out[0].contiguous(), out[1].contiguous(), keep.sum(dim=1).to(torch.int32)
+
+
+def twoViewRansacBatch(p1_q8, p2_q8, counts, *, model, hypotheses=200, seed=0, sigma_q8=256, best=None, score=None,
+                       ninliers=None, inlier=None, model_n=None, stats=None, ctx: Context | None = None):
+    """Batched two-view RANSAC (pislam_two_view_ransac_batch; the contract is the comment in include/pislam_hip.h):
+    match i of pair b is p1_q8[b][i] (image 1) and p2_q8[b][i] (image 2), (x, y) in level-0 pixels in Q8, int32 device
+    tensors [batch][stride][2] with stride <= 16384; counts [batch].  model is 0 / "F" (fundamental matrix, 8 matches
+    per hypothesis) or 1 / "H" (homography, 4).  All `hypotheses` (1..1024) are evaluated, scored as ORB-SLAM's
+    Initializer does with a measurement sigma of sigma_q8 / 256 pixels.  Returns (best, score, ninliers, inlier,
+    model_n, stats): int32 [batch] (the winning hypothesis, -1 = no model), int32 [batch] twice, uint8 [batch][stride]
+    (entries at and beyond counts[b] are not written), float32 [batch][9] (the model in normalised coordinates:
+    twoViewDenormalise gives pixels; F is not forced to rank 2) and int64 [batch][8].  The same inputs and seed give the
+    same outputs, bit for bit.  Asynchronous on the ctx stream, no workspace: capturable as it is."""
+    import torch
+    ctx = ctx or default_context()
+    if model not in _TWO_VIEW_MODELS:
+        raise ValueError('model must be 0 / "F" or 1 / "H"')
+    if p1_q8.dtype != torch.int32 or p1_q8.dim() != 3 or int(p1_q8.shape[2]) != 2:
+        raise ValueError("p1_q8 must be an int32 tensor [batch][stride][2]")
+    if p2_q8.dtype != torch.int32 or tuple(p2_q8.shape) != tuple(p1_q8.shape):
+        raise ValueError("p2_q8 must be an int32 tensor of p1_q8's shape")
+    batch, stride = int(p1_q8.shape[0]), int(p1_q8.shape[1])
+    if stride > TWO_VIEW_MAX_STRIDE:
+        raise ValueError(f"at most {TWO_VIEW_MAX_STRIDE} matches per pair")
+    dev = p1_q8.device
+    p = TwoViewParams(_TWO_VIEW_MODELS[model], int(hypotheses), int(seed) & 0xFFFFFFFF, int(sigma_q8))
+    best = torch.empty((batch,), dtype=torch.int32, device=dev) if best is None else best
+    score = torch.empty((batch,), dtype=torch.int32, device=dev) if score is None else score
+    ninliers = torch.empty((batch,), dtype=torch.int32, device=dev) if ninliers is None else ninliers
+    inlier = torch.empty((batch, stride), dtype=torch.uint8, device=dev) if inlier is None else inlier
+    model_n = torch.empty((batch, 9), dtype=torch.float32, device=dev) if model_n is None else model_n
+    stats = torch.empty((batch, 8), dtype=torch.int64, device=dev) if stats is None else stats
+    ctx.check(ctx.lib.pislam_two_view_ransac_batch(ctx.h, ctypes.byref(p), ptr(p1_q8), ptr(p2_q8), ptr(counts), stride,
+                                                   batch, ptr(best), ptr(score), ptr(ninliers), ptr(inlier),
+                                                   ptr(model_n), ptr(stats)), "pislam_two_view_ransac_batch")
+    return best, score, ninliers, inlier, model_n, stats
+
+
+def twoViewDenormalise(model, model_n, stats) -> np.ndarray:
+    """pislam_two_view_denormalise on the host: the level-0-pixel matrices, float64 [batch][3][3] (or [3][3] for one
+    row), from twoViewRansacBatch's model_n and stats (tensors or arrays; device tensors are copied to the host, which
+    synchronises).  F = T2' Fn T1, H = inverse(T2) Hn T1.  A row without a model (n < 1 or D < 1) is NaN."""
+    if model not in _TWO_VIEW_MODELS:
+        raise ValueError('model must be 0 / "F" or 1 / "H"')
+    host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    m = np.ascontiguousarray(host(model_n), dtype=np.float32)
+    st = np.ascontiguousarray(host(stats), dtype=np.int64)
+    single = m.ndim == 1
+    m, st = m.reshape(-1, 9), st.reshape(-1, 8)
+    if len(m) != len(st):
+        raise ValueError("model_n and stats must have the same number of rows")
+    out = np.full((len(m), 9), np.nan)
+    lib = capi.load()
+    for b in range(len(m)):
+        row = (ctypes.c_double * 9)()
+        rc = lib.pislam_two_view_denormalise(_TWO_VIEW_MODELS[model], m[b].ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                             st[b].ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), row)
+        if rc == capi.PISLAM_OK:
+            out[b] = row[:]
+    out = out.reshape(-1, 3, 3)
+    return out[0] if single else out
+
+
+def twoViewModelRatio(score_h, score_f):
+    """ORB-SLAM's model choice RH = SH / (SH + SF) from the scores of the two calls (numbers, arrays or tensors;
+    float64 on the host; 0 where both scores are 0).  ORB-SLAM takes the homography when RH > 0.40."""
+    host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    sh = host(score_h).astype(np.int64).astype(np.float64) if not isinstance(score_h, (int, float)) else np.float64(score_h)
+    sf = host(score_f).astype(np.int64).astype(np.float64) if not isinstance(score_f, (int, float)) else np.float64(score_f)
+    tot = sh + sf
+    return np.where(tot > 0, sh / np.where(tot > 0, tot, 1.0), 0.0)[()]
 
 
 # ---- bag of words: integer weights and the key-frame database ----------
