@@ -331,7 +331,22 @@ typedef struct pislam_frontend_params {
  * Every byte a consumer reads — the levels, the whole output blocks of each reduction, the next reduction's
  * block padding and FAST's right-edge columns (a margin of 32 columns / 16 rows around each level's
  * rewritten rectangle, zeroed on every call) — equals running the reference functions level by level on a
- * zero-initialised buffer; bytes beyond those margins are left untouched. */
+ * zero-initialised buffer; bytes beyond those margins are left untouched.
+ * Layout of a build call (tests/test_build_layouts.py pins each of these, bit for bit, on whole allocations):
+ *   frames   : frame b at frames + b*frame_stride, rows frame_vstep bytes apart; any frame_vstep >= width and any
+ *              frame_stride >= height*frame_vstep.  Row padding and the gaps between frames are never read as pixels
+ *              (the blur reflects at `width`).
+ *   pyramids : pyramid b at pyramids + b*pyramid_stride, uint8 [rows][vstep]; any vstep that holds every level with
+ *              its block padding (pislam_pyramid_layout's, or wider) and any pyramid_stride >= rows*vstep.  Gaps
+ *              between pyramids are never written.
+ *   Both bases may have any alignment, and the strides may exceed 4 GiB.  Alignment decides the speed, not the bytes:
+ *   the blur stages a tile with 16-byte loads when the frame's address and frame_vstep are multiples of 16 (dwords
+ *   when multiples of 4, else bytes), chosen per frame; a reduction takes the 4-block kernel when `pyramids`, vstep
+ *   and pyramid_stride are multiples of 16 and vstep holds the level's blocks rounded up to groups of four (else a
+ *   one-lane kernel), and the one-launch build (option "build_chain") needs that of every reduction.
+ *   batch    : any positive int.  It goes into one grid dimension as it is (no walk in pieces of 65535, unlike the
+ *              per-keypoint calls): HIP on gfx950 launches grids beyond 65535 in y and z, and a build of 65537 frames
+ *              is part of the tests. */
 int pislam_pyramid_layout(int width, int height, int nlevels, const int32_t *steps, int vstep_min,
                           pislam_level *levels, int32_t *vstep, int32_t *rows);
 #define PISLAM_BUILD_BLUR 1          /* level 0 = gaussian5x5 of the frame (else the frame itself)              */

@@ -1168,7 +1168,11 @@ DEFAULT_CHAIN = (2, 1, 2, 2, 1, 2, 2)     # 13/16, 7/8, 13/16, ... : (13/16)^2 *
 
 class PyramidBuilder:
     """frames uint8 [batch][h][w] (device) -> stacked pyramids uint8 [batch][rows][vstep] (device):
-    level 0 = gaussian5x5(frame), level k+1 = bilinear13_16 / bilinear7_8 of level k."""
+    level 0 = gaussian5x5(frame), level k+1 = bilinear13_16 / bilinear7_8 of level k.
+
+    Always the contiguous layout: frame_vstep = width, frame_stride = height * width, the layout's own vstep and
+    pyramid_stride = rows * vstep, at the tensors' own (aligned) addresses.  pislam_pyramid_build_batch itself takes padded
+    rows, gaps and unaligned bases (include/pislam_hip.h; tests/test_build_layouts.py calls it that way through ctypes)."""
 
     def __init__(self, width: int, height: int, steps=DEFAULT_CHAIN, *, blur=True, vstep_min=0,
                  ctx: Context | None = None):
