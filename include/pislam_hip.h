@@ -1115,6 +1115,114 @@ int pislam_two_view_ransac_batch(pislam_ctx *ctx, const pislam_two_view_params *
                                  uint32_t *score, uint32_t *ninliers, uint8_t *inlier, float *model_n, int64_t *stats);
 int pislam_two_view_denormalise(int model, const float *model_n, const int64_t *stats_row, double out[9]);
 
+/* ---- motion-only pose optimisation from 3D-2D matches --------------------- */
+
+/* The camera pose of a frame from map points matched to its keypoints: what ORB-SLAM's
+ * Optimizer::PoseOptimization computes with g2o, per frame of a batch, with the inlier mask.  The reference ships
+ * nothing of the kind: the semantics are this library's own, stated so that individually rounded binary32 and binary64
+ * operations reproduce every output word.  This comment is the contract.  On floats every +, -, *, / and sqrt below is
+ * ONE operation of the stated format, rounded to nearest even, in the order the parentheses give (a + b + c means
+ * (a + b) + c); no fused multiply-add, no reciprocal or fast approximation: the division and the square root are the
+ * correctly rounded ones; denormals are kept.  "float(v)" converts to binary32 (round to nearest even), "double(v)"
+ * converts a binary32 to binary64 (exact).
+ *
+ * Inputs, all device unless said.  Frame b has n = min(counts[b], stride) observations (counts: uint32 [batch],
+ * PISLAM_COUNT_INVALID counts as 0).
+ *   pose_in     float [batch][12]: r0 .. r8 row-major, then t0 .. t2; Xc = R Xw + t.
+ *   cam         float [batch][5]: fx, fy, cx, cy, bf in level-0 pixels (bf = baseline * fx).
+ *   xw          float [batch][stride][3]: the map points (X, Y, Z).
+ *   obs_q8      int32 [batch][stride][3]: (u, v, u_right) in Q8 level-0 pixels, each clamped to [-2^22, 2^22] first and
+ *               then float(q) * (1.0f / 256.0f) (exact).  u_right == INT32_MIN (tested before the clamp) marks a
+ *               MONOCULAR observation (2 residual rows), any other value a STEREO one (3 rows).
+ *   level       uint8 [batch][stride] or NULL.  NULL: w = 1.0f for every observation.  Otherwise w =
+ *               inv_sigma2[level]; an observation whose level is >= nlevels is DEAD at every pose (it lives in device
+ *               memory, so the host cannot refuse it).
+ *   inv_sigma2  HOST float [nlevels], 1 <= nlevels <= 16, every entry finite and > 0, read during the call; not looked
+ *               at (and nlevels ignored) when level is NULL.
+ *
+ * One observation at a pose, binary32.  The pose is the binary64 state (below) rounded: r_k = float(R_k),
+ * t_k = float(t_k).
+ *   x = ((r0*X + r1*Y) + r2*Z) + t0,  y = ((r3*X + r4*Y) + r5*Z) + t1,  z = ((r6*X + r7*Y) + r8*Z) + t2
+ *   the observation is DEAD unless z >= 2^-10 (a NaN fails)
+ *   iz = 1.0f / z,  px = x*iz,  py = y*iz,  pu = fx*px + cx,  pv = fy*py + cy
+ *   eu = u - pu,  ev = v - pv;  stereo only: er = ur - (pu - bf*iz)
+ *   chi2 = (eu*eu + ev*ev) * w        (monocular)         chi2 = ((eu*eu + ev*ev) + er*er) * w      (stereo)
+ *   the observation is DEAD as well unless chi2 is finite (neither infinite nor a NaN)
+ *   th = 5.991f (monocular), 7.815f (stereo)
+ *   Huber with delta^2 = th, as in ORB-SLAM: if the pass is robust and chi2 > th:
+ *       k = sqrt(th / chi2),  wr = w*k,  rho = (chi2*k)*2.0f - th;     otherwise wr = w, rho = chi2.
+ * A dead observation contributes nothing and is an outlier.  Jacobian rows of the error for a left increment
+ * d = (omega, upsilon), with a = fx*iz, b = fy*iz, c = bf*iz, pxy = px*py:
+ *   Ju = [ pxy*fx, -((1.0f + px*px)*fx), py*fx, -a, 0.0f, px*a ]
+ *   Jv = [ (1.0f + py*py)*fy, -(pxy*fy), -(px*fy), 0.0f, -b, py*b ]
+ *   Jr = [ Ju0 - c*py, Ju1 + c*px, Ju2, Ju3, 0.0f, Ju5 - c*iz ]
+ * The observation's 28 terms, in this order: for j = 0 .. 5, for k = j .. 5 (21 terms, the upper triangle row by row)
+ *   H_jk = (Ju_j*Ju_k + Jv_j*Jv_k) * wr   or   ((Ju_j*Ju_k + Jv_j*Jv_k) + Jr_j*Jr_k) * wr   (stereo);
+ * for j = 0 .. 5:  g_j = (Ju_j*eu + Jv_j*ev) * wr   or   ((Ju_j*eu + Jv_j*ev) + Jr_j*er) * wr;   then rho.
+ * The products with the constant 0.0f entries are carried out like any other.
+ *
+ * A PASS evaluates every observation of the frame at one pose and sums, in binary64, the 28 terms of those that are
+ * ACTIVE and not dead, and with them the number 1.0 and double(chi2) (the plain chi2) of each of these: 30 sums S_0 ..
+ * S_29; S = (H, g, F = S_27, S_28, S_29).  The order is fixed and does not depend on the launch: 256 partial sums that
+ * start at +0.0; partial i mod 256 takes double(term) of observation i, in ascending i; then the partials are combined
+ * by halving: p[j] = p[j] + p[j + 128] for j < 128, then with 64, 32, 16, 8, 4, 2, 1; S is p[0].  (IEEE addition is
+ * commutative, so an exchange between j and j xor h, in which both partners add, gives every lane the same bits as the
+ * halving gives p[j mod h]: the kernel uses that.  Adding the +0.0 of an inactive or dead observation changes no
+ * partial.)  No other float is ever summed across observations.  A CLASSIFYING pass first sets the active set anew from
+ * EVERY observation: active iff not dead and chi2 <= th at the pass's pose (so an outlier can come back, as in
+ * ORB-SLAM); it then sums over that new set.
+ *
+ * Per frame, binary64.  The state T = (R, t) is double(pose_in) and stays in binary64 for the whole call.
+ *   Solve(S, lambda): A = the symmetric 6 x 6 matrix of the H sums, A_jj = H_jj * (1.0 + lambda), rhs_j = -g_j.
+ *     Gaussian elimination WITHOUT pivoting, for c = 0 .. 5: the solve fails unless A[c][c] > 0 (a NaN fails); for
+ *     r = c+1 .. 5: f = A[r][c] / A[c][c]; for j = c+1 .. 5: A[r][j] = A[r][j] - f*A[c][j]; rhs_r = rhs_r - f*rhs_c.
+ *     Back substitution, r = 5 .. 0: s = rhs_r; for j = r+1 .. 5 ascending: s = s - A[r][j]*d_j;  d_r = s / A[r][r].
+ *     The solve also fails when a d_r is not finite.
+ *   Retract(T, d), the Cayley map (no sine or cosine): a = (d_0*0.5, d_1*0.5, d_2*0.5), n = (a0*a0 + a1*a1) + a2*a2,
+ *     m = 1.0 - n, e = 1.0 + n, Q = ((1 - n) I + 2 a a' + 2 [a]x) / (1 + n) entry by entry:
+ *       Q00 = (m + 2.0*(a0*a0))/e       Q01 = (2.0*(a0*a1) - 2.0*a2)/e   Q02 = (2.0*(a0*a2) + 2.0*a1)/e
+ *       Q10 = (2.0*(a1*a0) + 2.0*a2)/e  Q11 = (m + 2.0*(a1*a1))/e        Q12 = (2.0*(a1*a2) - 2.0*a0)/e
+ *       Q20 = (2.0*(a2*a0) - 2.0*a1)/e  Q21 = (2.0*(a2*a1) + 2.0*a0)/e   Q22 = (m + 2.0*(a2*a2))/e
+ *     R'_ij = (Q_i0*R_0j + Q_i1*R_1j) + Q_i2*R_2j,   t'_i = ((Q_i0*t_0 + Q_i1*t_1) + Q_i2*t_2) + d_(3+i).
+ *   A ROUND (Levenberg) starts from S at T over the current active set, lambda = 2^-10, and repeats up to `iters`
+ *   times:  1. d = Solve(S, lambda);  2. on failure lambda = min(8.0*lambda, 2^20) and the iteration is spent;
+ *   3. otherwise T' = Retract(T, d) and S' = a pass at T' (same active set, same robust flag);  4. if F' < F (false
+ *   for a NaN): T = T', S = S', lambda = max(lambda*0.25, 2^-30), else lambda = min(8.0*lambda, 2^20);  5. either way
+ *   the round ends when max_j |d_j| <= eps.  One pass per iteration.
+ *   The call:  pose_in or cam not finite: code 2.  n < min_obs: code 1.  Otherwise every observation is active and a
+ *   pass at T gives round 0 its S; the passes of round r are robust iff r < huber_rounds.  After round r a CLASSIFYING
+ *   pass at T, robust iff r + 1 < huber_rounds, gives the inlier mask (= the new active set), ninliers = S_28 and
+ *   cost = S_29, and its S is the start of round r + 1, which runs unless r + 1 == rounds (code 0) or ninliers <
+ *   min_obs (code 1).  Unlike ORB-SLAM, a round continues from the pose the round before reached; it does not restart
+ *   from the initial pose.
+ *
+ * Outputs, per frame, always written, all device.  pose_out float [batch][12] = float(T) (pose_in itself for code 2
+ * and for a frame that never ran a round); it may be exactly pose_in.  inlier uint8 [batch][stride]: the last
+ * classification, 0 or 1 for i < n (all 0 for a frame that never ran a round); entries at and beyond n are not written.
+ * ninliers uint32 [batch].  cost double [batch]: the tree-ordered sum of the inliers' plain chi2 (0 without a round).
+ * status uint32 [batch] = code | evaluations << 8, evaluations = the number of passes made; code 0: all rounds ran;
+ * 1: stopped for min_obs, the pose is that of the last completed round, or pose_in; 2: pose_in or cam not finite.
+ *
+ * Limits: the parameter ranges in the struct comments; 1 <= stride <= 16384; batch >= 0 with no upper limit (batch ==
+ * 0 is a no-op that returns PISLAM_OK after the checks of p, the table, batch and stride; the pointers are not looked
+ * at then).  Offsets use size_t arithmetic throughout.  No output may overlap an input or another output, except that
+ * pose_out may be pose_in.  Any violation, or a NULL or host pointer where a device pointer is required:
+ * PISLAM_ERR_INVALID, before anything is launched or written.  `p` is a host struct, read during the call.
+ * Asynchronous on the context stream; no workspace, no host round trip: the call can be captured into a hipGraph as it
+ * is.  One workgroup runs a frame's whole call in one launch; a batch above 1024 frames is walked by the same 1024
+ * workgroups in passes. */
+typedef struct pislam_pose_params {
+  int32_t rounds;        /* 1..8 (ORB-SLAM: 4) */
+  int32_t iters;         /* 1..32 Levenberg iterations per round (ORB-SLAM: 10) */
+  int32_t huber_rounds;  /* 0..rounds: rounds 0 .. huber_rounds - 1 are robust (ORB-SLAM: 3) */
+  int32_t min_obs;       /* 3..16384 active observations needed to run a round (ORB-SLAM: 10) */
+  double eps;            /* >= 0: a round ends when no |d_j| exceeds it (1e-6) */
+} pislam_pose_params;
+int pislam_pose_refine_batch(pislam_ctx *ctx, const pislam_pose_params *p, const float *pose_in, const float *cam,
+                             const float *xw, const int32_t *obs_q8, const uint32_t *counts, const uint8_t *level,
+                             const float *inv_sigma2, int nlevels, size_t stride, int batch, float *pose_out,
+                             uint8_t *inlier, uint32_t *ninliers, double *cost, uint32_t *status);
+
 /* ---- multi-GPU: one process per GPU, pyramids sharded, ONE collective ---- */
 
 /* The reference is a single-threaded per-frame loop without cross-frame state

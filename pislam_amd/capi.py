@@ -50,6 +50,11 @@ class TwoViewParams(ctypes.Structure):
                 ("sigma_q8", ctypes.c_int32)]
 
 
+class PoseParams(ctypes.Structure):
+    _fields_ = [("rounds", ctypes.c_int32), ("iters", ctypes.c_int32), ("huber_rounds", ctypes.c_int32),
+                ("min_obs", ctypes.c_int32), ("eps", ctypes.c_double)]
+
+
 class ClaheParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "tiles_x", "tiles_y", "clip_q8")]
 
@@ -144,6 +149,8 @@ SYMBOLS = {
                                           _vp]),
     "pislam_two_view_denormalise": (_i, [_i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64),
                                          ctypes.POINTER(ctypes.c_double)]),
+    "pislam_pose_refine_batch": (_i, [_vp, ctypes.POINTER(PoseParams), _vp, _vp, _vp, _vp, _vp, _vp,
+                                      ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
     "pislam_bow_weight_batch": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, ctypes.c_uint32, _vp]),
     "pislam_bowdb_create": (_i, [_vp, ctypes.c_uint32, _sz, _i, ctypes.POINTER(_vp)]),
     "pislam_bowdb_destroy": (_i, [_vp]),

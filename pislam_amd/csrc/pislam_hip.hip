@@ -60,6 +60,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_select_kernels.h"
 #include "pislam_geom_kernels.h"
 #include "pislam_geom_host.h"
+#include "pislam_pose_kernels.h"
 #include "pislam_warp_kernels.h"
 #include "pislam_clahe_kernels.h"
 
@@ -2472,6 +2473,60 @@ PISLAM_EXPORT int pislam_two_view_ransac_batch(pislam_ctx *c, const pislam_two_v
 
 PISLAM_EXPORT int pislam_two_view_denormalise(int model, const float *model_n, const int64_t *stats_row, double out[9]) {
   return pgh::two_view_denormalise(model, model_n, stats_row, out) ? PISLAM_OK : PISLAM_ERR_INVALID;
+}
+
+// ---- motion-only pose optimisation from 3D-2D matches ---------------------------------------
+
+PISLAM_EXPORT int pislam_pose_refine_batch(pislam_ctx *c, const pislam_pose_params *p, const float *pose_in,
+                                           const float *cam, const float *xw, const int32_t *obs_q8,
+                                           const uint32_t *counts, const uint8_t *level, const float *inv_sigma2,
+                                           int nlevels, size_t stride, int batch, float *pose_out, uint8_t *inlier,
+                                           uint32_t *ninliers, double *cost, uint32_t *status) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
+  if (p->rounds < 1 || p->rounds > 8) return fail(c, PISLAM_ERR_INVALID, "rounds must be 1..8");
+  if (p->iters < 1 || p->iters > 32) return fail(c, PISLAM_ERR_INVALID, "iters must be 1..32");
+  if (p->huber_rounds < 0 || p->huber_rounds > p->rounds) return fail(c, PISLAM_ERR_INVALID, "huber_rounds must be 0..rounds");
+  if (p->min_obs < 3 || p->min_obs > pq::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "min_obs must be 3..16384");
+  if (!(p->eps >= 0.0)) return fail(c, PISLAM_ERR_INVALID, "eps must be >= 0");
+  if (level) {
+    if (!inv_sigma2 || nlevels < 1 || nlevels > pq::MAX_LEVELS)
+      return fail(c, PISLAM_ERR_INVALID, "level needs inv_sigma2 with 1..16 entries");
+    for (int l = 0; l < nlevels; l++)
+      if (!(inv_sigma2[l] > 0.0f) || !pq::finite_f(inv_sigma2[l]))
+        return fail(c, PISLAM_ERR_INVALID, "inv_sigma2 must be finite and > 0");
+  }
+  if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
+  if (stride < 1 || stride > (size_t)pq::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
+  if (batch == 0) return PISLAM_OK;
+  const char *what = "the pose call takes device pointers only";
+  PCHK(device_ptrs(c, {pose_in, cam, xw, obs_q8, counts, pose_out, inlier, ninliers, cost, status}, what));
+  if (level && !is_device_ptr(level)) return fail(c, PISLAM_ERR_INVALID, what);
+  {
+    const size_t B = (size_t)batch, word = B * sizeof(uint32_t), pose = B * 12 * sizeof(float);
+    const LkRange in[] = {{pose_in, pose}, {cam, B * 5 * sizeof(float)}, {xw, B * stride * 3 * sizeof(float)},
+                          {obs_q8, B * stride * 3 * sizeof(int32_t)}, {counts, word}, {level, B * stride}};
+    const LkRange out[] = {{pose_out, pose}, {inlier, B * stride}, {ninliers, word}, {cost, B * sizeof(double)},
+                           {status, word}};
+    for (int o = 0; o < 5; o++) {
+      for (int i = 0; i < 6; i++) {
+        if (o == 0 && i == 0 && pose_out == pose_in) continue;           // a frame reads its pose before it writes it
+        if (lk_overlap(out[o], in[i])) return fail(c, PISLAM_ERR_INVALID, "an output overlaps an input");
+      }
+      for (int k = 0; k < o; k++)
+        if (lk_overlap(out[o], out[k])) return fail(c, PISLAM_ERR_INVALID, "two outputs overlap");
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  po::PoArgs a{};
+  a.pose_in = pose_in, a.cam = cam, a.xw = xw, a.obs = obs_q8, a.level = level, a.counts = counts, a.stride = stride;
+  a.batch = batch, a.nlevels = level ? nlevels : 0;
+  for (int l = 0; l < a.nlevels; l++) a.inv_sigma2[l] = inv_sigma2[l];
+  a.p = pq::Params{p->rounds, p->iters, p->huber_rounds, p->min_obs, p->eps};
+  a.pose_out = pose_out, a.inlier = inlier, a.ninliers = ninliers, a.status = status, a.cost = cost;
+  hipLaunchKernelGGL(po::k_pose_refine, dim3((unsigned)std::min(batch, po::PO_GRID_CAP)), dim3(po::PO_THREADS), 0,
+                     c->stream, a);
+  return launch_ok(c, "k_pose_refine");
 }
 
 // ---- bag of words: integer weights and the key-frame database -----------------------------

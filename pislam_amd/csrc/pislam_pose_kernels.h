@@ -1,0 +1,257 @@
+// pislam_pose_kernels.h — batched motion-only pose optimisation on the device (pislam_pose_refine_batch;
+// include/pislam_hip.h).  The header comment is the contract; the arithmetic is stated once, in
+// pislam_pose_math.h, for this kernel and for the host probe.
+//
+// One workgroup of PO_THREADS = 256 runs the whole call for a frame in one launch (all rounds, passes, solves and
+// classifications), then the frame PO_GRID_CAP further on.  No workspace.
+//   * Thread (wave, lane) owns the contract's partial sum q = wave * 4 + lane / 16 + 16 * rev4(lane % 16), that is the
+//     observations q, q + 256, q + 512, ... in ascending order.  The bits of q are laid out so that the contract's
+//     halving tree runs fastest: its steps 128, 64, 32, 16 are the lane exchanges xor 1, xor 2, xor 4, xor 8 (four DPP
+//     moves inside a row of 16 lanes; addition is commutative, so both partners hold the same bits afterwards), and the
+//     steps 8, 4, 2, 1 combine the 16 row sums of the workgroup through LDS, one sum per lane.
+//   * A frame of at most PO_RES * 256 = 2048 observations is loaded once and stays in registers over all passes; a
+//     larger one is re-read (from L2) in every pass.  The active set is a bit mask per lane either way.
+//   * Lane 0 runs the solve, the retraction and the Levenberg rule on state kept in LDS and broadcasts the next pose
+//     as 12 floats: three barriers per pass.
+#pragma once
+#include "pislam_pose_math.h"
+
+namespace po {
+
+constexpr int PO_THREADS = 256;
+constexpr int PO_RES = 8;                      // register-resident observations per lane
+constexpr int PO_GRID_CAP = 1024;              // workgroups per launch; a larger batch is walked in passes
+
+#define PO_ROLLED _Pragma("clang loop unroll(disable) vectorize(disable) interleave(disable)")
+
+struct PoArgs {
+  const float *pose_in, *cam, *xw;
+  const int32_t *obs;
+  const uint8_t *level;                        // or null
+  const uint32_t *counts;
+  size_t stride;
+  int batch, nlevels;
+  float inv_sigma2[pq::MAX_LEVELS];
+  pq::Params p;
+  float *pose_out;
+  uint8_t *inlier;
+  uint32_t *ninliers, *status;
+  double *cost;
+};
+
+struct PoObs {
+  float X, Y, Z, u, v, ur, w;
+  uint32_t flags;                              // bit 0: present with a level in range, bit 1: stereo
+};
+
+struct PoFrame {
+  const float *xw;
+  const int32_t *obs;
+  const uint8_t *level;
+  uint8_t *inlier;
+  uint32_t n;
+};
+
+__device__ __forceinline__ PoObs po_load(const PoArgs &A, const PoFrame &F, uint32_t i) {
+  PoObs o;
+  o.X = o.Y = o.Z = o.u = o.v = o.ur = 0.0f, o.w = 1.0f, o.flags = 0;
+  if (i < F.n) {
+    const float *x = F.xw + 3 * (size_t)i;
+    const int32_t *q = F.obs + 3 * (size_t)i;
+    o.X = x[0], o.Y = x[1], o.Z = x[2];
+    const int32_t ur = q[2];
+    o.u = pq::obs_px(q[0]), o.v = pq::obs_px(q[1]);
+    o.flags = 1;
+    if (ur != pq::MONO) o.ur = pq::obs_px(ur), o.flags |= 2;
+    if (F.level) {
+      const int l = F.level[i];
+      const float *tab = A.inv_sigma2;
+      if (l < A.nlevels) o.w = tab[l];
+      else o.flags = 0;
+    }
+  }
+  return o;
+}
+
+template <int CTRL>
+__device__ __forceinline__ double po_dpp(double v) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
+  hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+
+// One observation of a pass: classification, the mask, the 30 per-lane partial sums.
+__device__ __forceinline__ void po_one(const PoObs &o, uint32_t i, int s, const float *Tf, const float *cam, bool classify,
+                                       bool robust, uint64_t &active, uint8_t *inlier, double (&acc)[pq::SUMS]) {
+  const uint64_t bit = 1ull << s;
+  const bool stereo = (o.flags & 2) != 0;
+  if (!(o.flags & 1)) {                        // dead by its level
+    if (classify) active &= ~bit, inlier[i] = 0;
+    return;
+  }
+  if (!classify && !(active & bit)) return;
+  float t[pq::TERMS], chi2 = 0.0f;
+  const bool live = pq::obs_terms(Tf, cam, o.X, o.Y, o.Z, o.u, o.v, o.ur, stereo, o.w, robust, t, &chi2);
+  if (classify) {
+    const bool in = live && chi2 <= (stereo ? pq::TH_STEREO : pq::TH_MONO);
+    active = in ? (active | bit) : (active & ~bit);
+    inlier[i] = in ? 1 : 0;
+  }
+  if (live && (active & bit)) {
+#pragma unroll
+    for (int k = 0; k < pq::TERMS; k++) acc[k] += (double)t[k];
+    acc[28] += 1.0;
+    acc[29] += (double)chi2;
+  }
+}
+
+// One pass over the frame's observations at the pose s_Tf: leaves the 30 sums in s_S (ends with a barrier).
+template <bool RES>
+__device__ __forceinline__ void po_pass(const PoArgs &A, const PoFrame &F, const PoObs (&r)[PO_RES], uint32_t q, int tid,
+                                        const float *s_Tf, double (*s_part)[16], double *s_S, bool classify, bool robust,
+                                        uint64_t &active) {
+  float Tf[12], cam[5];
+#pragma unroll
+  for (int i = 0; i < 12; i++) Tf[i] = s_Tf[i];
+#pragma unroll
+  for (int i = 0; i < 5; i++) cam[i] = s_Tf[12 + i];
+  double acc[pq::SUMS];
+#pragma unroll
+  for (int k = 0; k < pq::SUMS; k++) acc[k] = 0.0;
+  if (RES) {
+#pragma unroll
+    for (int s = 0; s < PO_RES; s++) {
+      const uint32_t i = q + 256u * (uint32_t)s;
+      if (i < F.n) po_one(r[s], i, s, Tf, cam, classify, robust, active, F.inlier, acc);
+    }
+  } else {
+    PO_ROLLED
+    for (int s = 0; s < pq::MAX_STRIDE / 256; s++) {
+      const uint32_t i = q + 256u * (uint32_t)s;
+      if (i < F.n) {
+        const PoObs o = po_load(A, F, i);
+        po_one(o, i, s, Tf, cam, classify, robust, active, F.inlier, acc);
+      }
+    }
+  }
+  // the tree: steps 128, 64, 32, 16 inside the rows of 16 lanes (every lane is active here) ...
+#pragma unroll
+  for (int k = 0; k < pq::SUMS; k++) {
+    double v = acc[k];
+    v += po_dpp<0xb1>(v);                      // quad_perm [1, 0, 3, 2]: lane ^ 1
+    v += po_dpp<0x4e>(v);                      // quad_perm [2, 3, 0, 1]: lane ^ 2
+    v += po_dpp<0x141>(v);                     // row_half_mirror: the other quad of the 8, whose lanes all hold its sum
+    v += po_dpp<0x140>(v);                     // row_mirror: the other 8 of the row
+    acc[k] = v;
+  }
+  if ((tid & 15) == 0) {
+#pragma unroll
+    for (int k = 0; k < pq::SUMS; k++) s_part[k][tid >> 4] = acc[k];   // row tid / 16 = wave * 4 + lane / 16 = q % 16
+  }
+  __syncthreads();
+  // ... steps 8, 4, 2, 1 over the 16 row sums, one sum per lane
+  if (tid < pq::SUMS) {
+    double v[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) v[j] = s_part[tid][j];
+#pragma unroll
+    for (int h = 8; h >= 1; h >>= 1) {
+#pragma unroll
+      for (int j = 0; j < h; j++) v[j] += v[j + h];
+    }
+    s_S[tid] = v[0];
+  }
+  __syncthreads();
+}
+
+template <bool RES>
+__device__ __forceinline__ void po_frame(const PoArgs &A, const PoFrame &F, uint32_t b, int tid, uint32_t q, float *s_Tf,
+                                         double (*s_part)[16], double *s_S, pq::Lm *s_lm, int *s_cmd) {
+  PoObs r[PO_RES];
+  if (RES) {
+#pragma unroll
+    for (int s = 0; s < PO_RES; s++) r[s] = po_load(A, F, q + 256u * (uint32_t)s);
+  }
+  const int rounds = A.p.rounds, iters = A.p.iters, hr = A.p.huber_rounds;
+  uint64_t active = ~0ull;
+  uint32_t evals = 1, code = 0, ninl = 0;
+  double cost = 0.0;
+  po_pass<RES>(A, F, r, q, tid, s_Tf, s_part, s_S, false, 0 < hr, active);
+  PO_ROLLED
+  for (int rd = 0; rd < rounds; rd++) {
+    if (tid == 0) s_lm->begin(s_S);
+    PO_ROLLED
+    for (;;) {
+      if (tid == 0) {
+        const bool go = s_lm->next(iters);
+        *s_cmd = go ? 1 : 0;
+#pragma unroll
+        for (int i = 0; i < 12; i++) s_Tf[i] = (float)(go ? s_lm->Tt[i] : s_lm->T[i]);
+      }
+      __syncthreads();
+      if (!*s_cmd) break;
+      po_pass<RES>(A, F, r, q, tid, s_Tf, s_part, s_S, false, rd < hr, active);
+      evals++;
+      if (tid == 0) s_lm->trial(s_S, A.p.eps);
+    }
+    po_pass<RES>(A, F, r, q, tid, s_Tf, s_part, s_S, true, rd + 1 < hr, active);
+    evals++;
+    ninl = (uint32_t)s_S[28], cost = s_S[29];
+    if (rd + 1 < rounds && ninl < (uint32_t)A.p.min_obs) {
+      code = 1;
+      break;
+    }
+  }
+  if (tid < 12) A.pose_out[12 * (size_t)b + tid] = (float)s_lm->T[tid];
+  if (tid == 0) A.ninliers[b] = ninl, A.cost[b] = cost, A.status[b] = code | evals << 8;
+}
+
+__global__ __launch_bounds__(PO_THREADS) void k_pose_refine(const PoArgs A) {
+  __shared__ pq::Lm s_lm;
+  __shared__ double s_part[pq::SUMS][16];
+  __shared__ double s_S[pq::SUMS + 2];
+  __shared__ float s_Tf[12 + 5];               // the pose of the pass, then the camera
+  __shared__ int s_cmd;
+
+  PO_ROLLED
+  for (uint32_t b = blockIdx.x; b < (uint32_t)A.batch; b += gridDim.x) {
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));              // keeps the per-thread predicates out of SGPRs held over the loop
+    const int lane = tid & 63, wave = tid >> 6;
+    const uint32_t l4 = (uint32_t)lane & 15u;
+    const uint32_t rev = (l4 & 1u) << 3 | (l4 & 2u) << 1 | (l4 & 4u) >> 1 | (l4 & 8u) >> 3;
+    const uint32_t q = (uint32_t)wave << 2 | (uint32_t)lane >> 4 | rev << 4;
+    const size_t row = (size_t)b * A.stride;
+    PoFrame F;
+    F.xw = A.xw + 3 * row, F.obs = A.obs + 3 * row, F.level = A.level ? A.level + row : nullptr, F.inlier = A.inlier + row;
+    uint32_t n = A.counts[b];
+    n = n == pq::COUNT_INVALID ? 0u : (n < A.stride ? n : (uint32_t)A.stride);
+    F.n = n;
+    float v = 0.0f;
+    if (tid < 12) v = A.pose_in[12 * (size_t)b + tid];
+    else if (tid < 17) v = A.cam[5 * (size_t)b + (tid - 12)];
+    if (tid < 17) s_Tf[tid] = v;
+    if (tid == 0) s_cmd = 1;
+    __syncthreads();
+    if (tid < 17 && !pq::finite_f(v)) s_cmd = 0;             // (every writer writes the same value)
+    __syncthreads();
+    const bool fin = s_cmd != 0;
+    if (!fin || n < (uint32_t)A.p.min_obs) {
+      PO_ROLLED
+      for (uint32_t i = tid; i < n; i += PO_THREADS) F.inlier[i] = 0;
+      if (tid < 12) A.pose_out[12 * (size_t)b + tid] = v;
+      if (tid == 0) A.ninliers[b] = 0, A.cost[b] = 0.0, A.status[b] = fin ? 1u : 2u;
+    } else {
+      if (tid < 12) s_lm.T[tid] = (double)v;
+      __syncthreads();
+      if (n <= (uint32_t)(PO_RES * 256))
+        po_frame<true>(A, F, b, tid, q, s_Tf, s_part, s_S, &s_lm, &s_cmd);
+      else
+        po_frame<false>(A, F, b, tid, q, s_Tf, s_part, s_S, &s_lm, &s_cmd);
+    }
+    __syncthreads();                                         // the next frame rewrites what this one still reads
+  }
+}
+
+}  // namespace po

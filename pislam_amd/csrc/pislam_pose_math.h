@@ -1,0 +1,302 @@
+// pislam_pose_math.h — the arithmetic of pislam_pose_refine_batch (include/pislam_hip.h: that comment is the contract),
+// stated ONCE for the device kernel (pislam_pose_kernels.h) and for a plain C++ compiler (tools/probes/
+// pose_host_check.cpp): the per-observation terms in binary32, the 6 x 6 solve, the Cayley retraction and the
+// Levenberg rule in binary64, and, for the host only, the whole procedure run serially with the contract's tree order.
+// Every operation is written out one rounding at a time; build with -ffp-contract=off.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define PQ_HD __host__ __device__ __forceinline__
+#define PQ_UNROLL _Pragma("unroll")
+#else
+#define PQ_HD inline
+#define PQ_UNROLL
+#endif
+
+namespace pq {
+
+constexpr int TERMS = 28;                      // 21 upper-triangle terms, 6 gradient terms, rho
+constexpr int SUMS = 30;                       // + the number of active observations that are not dead, + their chi2
+constexpr int PARTIALS = 256;
+constexpr int MAX_STRIDE = 16384;
+constexpr int MAX_LEVELS = 16;
+constexpr float Z_MIN = 0x1p-10f;
+constexpr float TH_MONO = 5.991f, TH_STEREO = 7.815f;
+constexpr double LAMBDA_0 = 0x1p-10, LAMBDA_MIN = 0x1p-30, LAMBDA_MAX = 0x1p20;
+constexpr int32_t OBS_MAX = 1 << 22;
+constexpr int32_t MONO = INT32_MIN;
+constexpr uint32_t COUNT_INVALID = 0xffffffffu;
+
+// The correctly rounded binary32 square root and quotient.  (sqrtf and / are correctly rounded on the device with
+// hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt; __fsqrt_rn is the NATIVE square root unless OCML's rounded
+// operations are switched on, so it is not used.)
+PQ_HD float fsqrt(float x) { return __builtin_sqrtf(x); }
+PQ_HD float fdiv(float a, float b) { return a / b; }
+
+PQ_HD bool finite_f(float v) { return fabsf(v) < __builtin_inff(); }   // false for a NaN
+PQ_HD bool finite_d(double v) { return fabs(v) < __builtin_inf(); }
+
+PQ_HD int32_t clamp_obs(int32_t v) { return v < -OBS_MAX ? -OBS_MAX : (v > OBS_MAX ? OBS_MAX : v); }
+PQ_HD float obs_px(int32_t q8) { return (float)clamp_obs(q8) * (1.0f / 256.0f); }   // exact
+
+// One observation at the pose T (r0..r8, t0..t2, already rounded to float) with the weight w.  False: dead (nothing
+// is written).  Otherwise *chi2_out is the plain chi2 and t[0..27] are the 28 terms.
+PQ_HD bool obs_terms(const float *T, const float *cam, float X, float Y, float Z, float u, float v, float ur, bool stereo,
+                     float w, bool robust, float *t, float *chi2_out) {
+  const float fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3], bf = cam[4];
+  const float x = ((T[0] * X + T[1] * Y) + T[2] * Z) + T[9];
+  const float y = ((T[3] * X + T[4] * Y) + T[5] * Z) + T[10];
+  const float z = ((T[6] * X + T[7] * Y) + T[8] * Z) + T[11];
+  if (!(z >= Z_MIN)) return false;
+  const float iz = fdiv(1.0f, z);
+  const float px = x * iz, py = y * iz;
+  const float pu = fx * px + cx, pv = fy * py + cy;
+  const float eu = u - pu, ev = v - pv;
+  float er = 0.0f;
+  float e2 = eu * eu + ev * ev;
+  if (stereo) {
+    er = ur - (pu - bf * iz);
+    e2 = e2 + er * er;
+  }
+  const float chi2 = e2 * w;
+  if (!finite_f(chi2)) return false;
+  *chi2_out = chi2;
+  const float th = stereo ? TH_STEREO : TH_MONO;
+  float wr = w, rho = chi2;
+  if (robust && chi2 > th) {
+    const float k = fsqrt(fdiv(th, chi2));
+    wr = w * k;
+    rho = (chi2 * k) * 2.0f - th;
+  }
+  const float a = fx * iz, b = fy * iz, c = bf * iz;
+  const float pxy = px * py;
+  float Ju[6], Jv[6], Jr[6];
+  Ju[0] = pxy * fx, Ju[1] = -((1.0f + px * px) * fx), Ju[2] = py * fx, Ju[3] = -a, Ju[4] = 0.0f, Ju[5] = px * a;
+  Jv[0] = (1.0f + py * py) * fy, Jv[1] = -(pxy * fy), Jv[2] = -(px * fy), Jv[3] = 0.0f, Jv[4] = -b, Jv[5] = py * b;
+  Jr[0] = Ju[0] - c * py, Jr[1] = Ju[1] + c * px, Jr[2] = Ju[2], Jr[3] = Ju[3], Jr[4] = 0.0f, Jr[5] = Ju[5] - c * iz;
+  int o = 0;
+PQ_UNROLL
+  for (int j = 0; j < 6; j++) {
+PQ_UNROLL
+    for (int k = j; k < 6; k++) {
+      float s = Ju[j] * Ju[k] + Jv[j] * Jv[k];
+      if (stereo) s = s + Jr[j] * Jr[k];
+      t[o++] = s * wr;
+    }
+  }
+PQ_UNROLL
+  for (int j = 0; j < 6; j++) {
+    float s = Ju[j] * eu + Jv[j] * ev;
+    if (stereo) s = s + Jr[j] * er;
+    t[21 + j] = s * wr;
+  }
+  t[27] = rho;
+  return true;
+}
+
+// A d = -g with A = H, A_jj = H_jj * (1 + lambda); S = the 28 sums.  Gaussian elimination without pivoting, back
+// substitution.  False: a pivot that is not > 0 (a NaN fails) or a d that is not finite.
+PQ_HD bool solve(const double *S, double lambda, double *d) {
+  double A[6][6], b[6];
+  {
+    int o = 0;
+PQ_UNROLL
+    for (int j = 0; j < 6; j++) {
+PQ_UNROLL
+      for (int k = j; k < 6; k++) {
+        A[j][k] = S[o], A[k][j] = S[o];
+        o++;
+      }
+    }
+  }
+  const double s = 1.0 + lambda;
+PQ_UNROLL
+  for (int j = 0; j < 6; j++) A[j][j] = A[j][j] * s, b[j] = -S[21 + j];
+  bool ok = true;
+PQ_UNROLL
+  for (int c = 0; c < 6; c++) {
+    ok = ok && A[c][c] > 0.0;
+PQ_UNROLL
+    for (int r = c + 1; r < 6; r++) {
+      const double f = A[r][c] / A[c][c];
+PQ_UNROLL
+      for (int j = c + 1; j < 6; j++) A[r][j] = A[r][j] - f * A[c][j];
+      b[r] = b[r] - f * b[c];
+    }
+  }
+PQ_UNROLL
+  for (int r = 5; r >= 0; r--) {
+    double t = b[r];
+PQ_UNROLL
+    for (int j = r + 1; j < 6; j++) t = t - A[r][j] * d[j];
+    d[r] = t / A[r][r];
+    ok = ok && finite_d(d[r]);
+  }
+  return ok;
+}
+
+// The Cayley retraction of T by d = (omega, upsilon): R' = Q R, t' = Q t + upsilon.
+PQ_HD void retract(const double *T, const double *d, double *Tn) {
+  const double a0 = d[0] * 0.5, a1 = d[1] * 0.5, a2 = d[2] * 0.5;
+  const double n = (a0 * a0 + a1 * a1) + a2 * a2;
+  const double m = 1.0 - n, den = 1.0 + n;
+  double Q[9];
+  Q[0] = (m + 2.0 * (a0 * a0)) / den, Q[1] = (2.0 * (a0 * a1) - 2.0 * a2) / den, Q[2] = (2.0 * (a0 * a2) + 2.0 * a1) / den;
+  Q[3] = (2.0 * (a1 * a0) + 2.0 * a2) / den, Q[4] = (m + 2.0 * (a1 * a1)) / den, Q[5] = (2.0 * (a1 * a2) - 2.0 * a0) / den;
+  Q[6] = (2.0 * (a2 * a0) - 2.0 * a1) / den, Q[7] = (2.0 * (a2 * a1) + 2.0 * a0) / den, Q[8] = (m + 2.0 * (a2 * a2)) / den;
+PQ_UNROLL
+  for (int i = 0; i < 3; i++) {
+PQ_UNROLL
+    for (int j = 0; j < 3; j++) Tn[3 * i + j] = (Q[3 * i] * T[j] + Q[3 * i + 1] * T[3 + j]) + Q[3 * i + 2] * T[6 + j];
+    Tn[9 + i] = ((Q[3 * i] * T[9] + Q[3 * i + 1] * T[10]) + Q[3 * i + 2] * T[11]) + d[3 + i];
+  }
+}
+
+// The Levenberg rule of one round, as a state machine around the passes over the observations: begin() takes the sums
+// at the round's pose, next() asks for the next trial pose (false: the round is over), trial() takes the sums at it.
+struct Lm {
+  double T[12], Tt[12], S[TERMS];
+  double lambda, dmax;
+  int it;
+  bool over;
+
+  PQ_HD void begin(const double *sums) {
+PQ_UNROLL
+    for (int i = 0; i < TERMS; i++) S[i] = sums[i];
+    lambda = LAMBDA_0, it = 0, over = false;
+  }
+  PQ_HD bool next(int iters) {
+    while (!over && it < iters) {
+      it++;
+      double d[6];
+      if (!solve(S, lambda, d)) {
+        lambda = fmin(8.0 * lambda, LAMBDA_MAX);
+        continue;
+      }
+      retract(T, d, Tt);
+      dmax = 0.0;
+PQ_UNROLL
+      for (int j = 0; j < 6; j++) dmax = fmax(dmax, fabs(d[j]));
+      return true;
+    }
+    return false;
+  }
+  PQ_HD void trial(const double *sums, double eps) {
+    if (sums[27] < S[27]) {
+PQ_UNROLL
+      for (int i = 0; i < 12; i++) T[i] = Tt[i];
+PQ_UNROLL
+      for (int i = 0; i < TERMS; i++) S[i] = sums[i];
+      lambda = fmax(lambda * 0.25, LAMBDA_MIN);
+    } else {
+      lambda = fmin(8.0 * lambda, LAMBDA_MAX);
+    }
+    if (dmax <= eps) over = true;
+  }
+};
+
+struct Params {
+  int rounds, iters, huber_rounds, min_obs;
+  double eps;
+};
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// ---- the host's serial form of the whole call for one frame (the probe; never the library's hot path) ---------------
+
+struct Frame {
+  const float *pose_in, *cam, *xw;             // [12], [5], [n][3]
+  const int32_t *obs;                          // [n][3]
+  const uint8_t *level;                        // [n] or null
+  const float *inv_sigma2;                     // [nlevels] or null with level == null
+  int nlevels;
+  uint32_t n;                                  // already min(count, stride), COUNT_INVALID as 0
+};
+struct Result {
+  float pose[12];
+  uint32_t ninliers, status;
+  double cost;
+};
+
+// One pass: the 30 sums at Tf in the contract's tree order.  classify: the active flags (and `inlier`) are set anew.
+inline void host_pass(const Frame &F, const float *Tf, bool classify, bool robust, uint8_t *active, double *sums) {
+  static thread_local double p[PARTIALS][SUMS];
+  for (int q = 0; q < PARTIALS; q++)
+    for (int t = 0; t < SUMS; t++) p[q][t] = 0.0;
+  for (uint32_t i = 0; i < F.n; i++) {
+    float w = 1.0f;
+    bool dead = false;
+    if (F.level) {
+      if (F.level[i] < F.nlevels) w = F.inv_sigma2[F.level[i]];
+      else dead = true;
+    }
+    const int32_t *o = F.obs + 3 * (size_t)i;
+    const float *X = F.xw + 3 * (size_t)i;
+    const bool stereo = o[2] != MONO;
+    float t[TERMS], chi2 = 0.0f;
+    const bool want = classify || active[i];
+    bool live = false;
+    if (!dead && want)
+      live = obs_terms(Tf, F.cam, X[0], X[1], X[2], obs_px(o[0]), obs_px(o[1]), stereo ? obs_px(o[2]) : 0.0f, stereo, w,
+                       robust, t, &chi2);
+    if (classify) active[i] = live && chi2 <= (stereo ? TH_STEREO : TH_MONO);
+    if (!live || !active[i]) continue;
+    double *a = p[i % PARTIALS];
+    for (int k = 0; k < TERMS; k++) a[k] += (double)t[k];
+    a[28] += 1.0;
+    a[29] += (double)chi2;
+  }
+  for (int h = PARTIALS / 2; h >= 1; h /= 2)
+    for (int q = 0; q < h; q++)
+      for (int t = 0; t < SUMS; t++) p[q][t] += p[q + h][t];
+  for (int t = 0; t < SUMS; t++) sums[t] = p[0][t];
+}
+
+inline void host_frame(const Frame &F, const Params &P, Result *R, uint8_t *inlier) {
+  for (uint32_t i = 0; i < F.n; i++) inlier[i] = 0;
+  for (int i = 0; i < 12; i++) R->pose[i] = F.pose_in[i];
+  R->ninliers = 0, R->cost = 0.0;
+  bool fin = true;
+  for (int i = 0; i < 12; i++) fin = fin && finite_f(F.pose_in[i]);
+  for (int i = 0; i < 5; i++) fin = fin && finite_f(F.cam[i]);
+  if (!fin) {
+    R->status = 2;
+    return;
+  }
+  if (F.n < (uint32_t)P.min_obs) {
+    R->status = 1;
+    return;
+  }
+  Lm L;
+  float Tf[12];
+  double sums[SUMS];
+  uint32_t evals = 0, code = 0;
+  for (int i = 0; i < 12; i++) L.T[i] = (double)F.pose_in[i], Tf[i] = F.pose_in[i];
+  uint8_t *active = inlier;                    // the mask is the active set
+  for (uint32_t i = 0; i < F.n; i++) active[i] = 1;
+  host_pass(F, Tf, false, 0 < P.huber_rounds, active, sums);
+  evals++;
+  for (int r = 0; r < P.rounds; r++) {
+    L.begin(sums);
+    while (L.next(P.iters)) {
+      for (int i = 0; i < 12; i++) Tf[i] = (float)L.Tt[i];
+      host_pass(F, Tf, false, r < P.huber_rounds, active, sums);
+      evals++;
+      L.trial(sums, P.eps);
+    }
+    for (int i = 0; i < 12; i++) Tf[i] = (float)L.T[i];
+    host_pass(F, Tf, true, r + 1 < P.huber_rounds, active, sums);
+    evals++;
+    R->ninliers = (uint32_t)sums[28], R->cost = sums[29];
+    if (r + 1 < P.rounds && R->ninliers < (uint32_t)P.min_obs) {
+      code = 1;
+      break;
+    }
+  }
+  for (int i = 0; i < 12; i++) R->pose[i] = (float)L.T[i];
+  R->status = code | evals << 8;
+}
+#endif
+
+}  // namespace pq

@@ -837,8 +837,129 @@ def twoViewModelRatio(score_h, score_f):
     return np.where(tot > 0, sh / np.where(tot > 0, tot, 1.0), 0.0)[()]
 
 
+# ---- motion-only pose optimisation from 3D-2D matches ----------
+POSE_MAX_STRIDE = 16384       # observations per frame (pislam_pose_refine_batch)
+POSE_MONO = -(1 << 31)        # u_right of a monocular observation
+POSE_NO_LEVEL = 255           # level of a keypoint that lies in no level: dead
+
+
+def poseLevelWeights(nlevels: int, scale: float = 1.2) -> np.ndarray:
+    """The inv_sigma2 table of poseRefineBatch for a pyramid of `nlevels` levels (1..16) with the scale factor
+    `scale`: float32 1 / scale^(2 l), computed one float32 operation at a time: s = float32(scale), f_0 = 1,
+    f_l = f_(l-1) * s, w_l = 1 / (f_l * f_l)  (ORB-SLAM's mvInvLevelSigma2)."""
+    if not 1 <= int(nlevels) <= 16:
+        raise ValueError("nlevels must be 1..16")
+    s, f = np.float32(scale), np.float32(1.0)
+    out = np.empty(int(nlevels), dtype=np.float32)
+    for l in range(int(nlevels)):
+        out[l] = np.float32(1.0) / (f * f)
+        f = f * s
+    return out
+
+
+def poseObservationsQ8(kp, levels, scale_q16=None, disp_q8=None, pos_q8=None):
+    """The obs_q8 and level of poseRefineBatch from keypoint words kp [batch][stride] (any integer tensor, device or
+    host): each keypoint is mapped from its level to level 0 by matchedPointsQ8's formula, per axis with the
+    level-local Q8 coordinate u: floor((u * s_l + 32768) / 65536) in int64 (scale_q16 None = level_scales_q16(levels)).
+    pos_q8 ([batch][stride][2], e.g. refineMatchesBatch's next_q8: stacked Q8 coordinates on the keypoint's level)
+    replaces the keypoint's position.  disp_q8 ([batch][stride], matchStereoBatch's, level-0 Q8): u_right = u - disp_q8
+    where disp_q8 >= 0, else the monocular sentinel INT32_MIN; None: every observation is monocular.  A keypoint in no
+    level gets the level 255 (dead in poseRefineBatch with a level table of at most 16 entries) and (0, 0, INT32_MIN).
+    Returns (obs_q8 int32 [batch][stride][3], level uint8 [batch][stride]).  Torch ops on the current torch stream."""
+    import torch
+    lvn = [(int(t[0]), int(t[1]), int(t[2]), int(t[3]) if len(t) > 3 else 0) for t in levels]
+    sc = level_scales_q16(levels) if scale_q16 is None else ([int(scale_q16)] * len(lvn) if isinstance(
+        scale_q16, (int, np.integer)) else [int(v) for v in scale_q16])
+    if len(lvn) > POSE_NO_LEVEL:
+        raise ValueError("at most 255 levels")
+    k = kp.to(torch.int64)
+    x, y = (k >> 12) & 0xFFF, k & 0xFFF
+    if pos_q8 is None:
+        px, py = x << 8, y << 8
+    else:
+        if tuple(pos_q8.shape) != tuple(kp.shape) + (2,):
+            raise ValueError("pos_q8 must be [batch][stride][2]")
+        p = pos_q8.to(torch.int64)
+        px, py = p[..., 0], p[..., 1]
+    U, V = torch.zeros_like(k), torch.zeros_like(k)
+    level = torch.full_like(k, POSE_NO_LEVEL)
+    for l, ((w, h, row0, col0), sl) in enumerate(zip(lvn, sc)):
+        m = (x >= col0) & (x < col0 + w) & (y >= row0) & (y < row0 + h)
+        U = torch.where(m, torch.div((px - (col0 << 8)) * sl + 32768, 65536, rounding_mode="floor"), U)
+        V = torch.where(m, torch.div((py - (row0 << 8)) * sl + 32768, 65536, rounding_mode="floor"), V)
+        level = torch.where(m, torch.full_like(k, l), level)
+    found = level != POSE_NO_LEVEL
+    ur = torch.full_like(k, POSE_MONO)
+    if disp_q8 is not None:
+        if tuple(disp_q8.shape) != tuple(kp.shape):
+            raise ValueError("disp_q8 must have kp's shape")
+        d = disp_q8.to(torch.int64)
+        ur = torch.where(found & (d >= 0), U - d, ur)
+    obs = torch.stack([U, V, ur], dim=-1).clamp(POSE_MONO, (1 << 31) - 1).to(torch.int32)
+    return obs.contiguous(), level.to(torch.uint8).contiguous()
+
+
+def poseRefineBatch(pose, cam, xw, obs_q8, counts, *, level=None, inv_sigma2=None, rounds=4, iters=10, huber_rounds=3,
+                    min_obs=10, eps=1e-6, pose_out=None, inlier=None, ninliers=None, cost=None, status=None,
+                    ctx: Context | None = None):
+    """Batched motion-only pose optimisation (pislam_pose_refine_batch; the contract is the comment in
+    include/pislam_hip.h): per frame, the pose that minimises the robust reprojection error of map points xw (float32
+    [batch][stride][3], stride <= 16384) against obs_q8 (int32 [batch][stride][3]: u, v, u_right in level-0 Q8 pixels,
+    u_right == INT32_MIN for a monocular observation; poseObservationsQ8 makes them), starting from pose (float32
+    [batch][12]: R row-major, then t; Xc = R Xw + t) with cam (float32 [batch][5]: fx, fy, cx, cy, bf); counts [batch].
+    level (uint8 [batch][stride]) with inv_sigma2 (a HOST sequence of 1..16 float32, e.g. poseLevelWeights) weights
+    each observation; without them every weight is 1.  ORB-SLAM's schedule: `rounds` rounds of up to `iters` Levenberg
+    iterations, the first `huber_rounds` with the Huber kernel, an inlier classification after each; a round needs
+    `min_obs` active observations.  Returns (pose_out float32 [batch][12], inlier uint8 [batch][stride] (entries at and
+    beyond counts[b] are not written), ninliers int32 [batch], cost float64 [batch], status int32 [batch] = code |
+    evaluations << 8; code 0 ok, 1 stopped for min_obs, 2 pose or cam not finite).  pose_out may be `pose` itself.
+    The same inputs give the same outputs, bit for bit.  Asynchronous on the ctx stream, no workspace: capturable."""
+    import torch
+    ctx = ctx or default_context()
+    if pose.dtype != torch.float32 or pose.dim() != 2 or int(pose.shape[1]) != 12:
+        raise ValueError("pose must be a float32 tensor [batch][12]")
+    batch = int(pose.shape[0])
+    if cam.dtype != torch.float32 or tuple(cam.shape) != (batch, 5):
+        raise ValueError("cam must be a float32 tensor [batch][5]")
+    if xw.dtype != torch.float32 or xw.dim() != 3 or int(xw.shape[0]) != batch or int(xw.shape[2]) != 3:
+        raise ValueError("xw must be a float32 tensor [batch][stride][3]")
+    stride = int(xw.shape[1])
+    if obs_q8.dtype != torch.int32 or tuple(obs_q8.shape) != (batch, stride, 3):
+        raise ValueError("obs_q8 must be an int32 tensor [batch][stride][3]")
+    if stride > POSE_MAX_STRIDE:
+        raise ValueError(f"at most {POSE_MAX_STRIDE} observations per frame")
+    if counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(counts.shape) != (batch,):
+        raise ValueError("counts must be a 32-bit integer tensor [batch]")
+    if (level is None) != (inv_sigma2 is None):
+        raise ValueError("level and inv_sigma2 go together")
+    tab, ntab = None, 0
+    if level is not None:
+        if level.dtype != torch.uint8 or tuple(level.shape) != (batch, stride):
+            raise ValueError("level must be a uint8 tensor [batch][stride]")
+        host = np.ascontiguousarray(np.asarray(inv_sigma2, dtype=np.float32).reshape(-1))
+        ntab = int(host.size)
+        if not 1 <= ntab <= 16:
+            raise ValueError("inv_sigma2 must have 1..16 entries")
+        tab = (ctypes.c_float * ntab)(*host.tolist())
+    for t in (pose, cam, xw, obs_q8, counts) + (() if level is None else (level,)):
+        if not t.is_contiguous():
+            raise ValueError("inputs must be contiguous")
+    dev = pose.device
+    p = capi.PoseParams(int(rounds), int(iters), int(huber_rounds), int(min_obs), float(eps))
+    pose_out = torch.empty((batch, 12), dtype=torch.float32, device=dev) if pose_out is None else pose_out
+    inlier = torch.empty((batch, stride), dtype=torch.uint8, device=dev) if inlier is None else inlier
+    ninliers = torch.empty((batch,), dtype=torch.int32, device=dev) if ninliers is None else ninliers
+    cost = torch.empty((batch,), dtype=torch.float64, device=dev) if cost is None else cost
+    status = torch.empty((batch,), dtype=torch.int32, device=dev) if status is None else status
+    ctx.check(ctx.lib.pislam_pose_refine_batch(ctx.h, ctypes.byref(p), ptr(pose), ptr(cam), ptr(xw), ptr(obs_q8),
+                                               ptr(counts), ptr(level), tab, ntab, stride, batch, ptr(pose_out),
+                                               ptr(inlier), ptr(ninliers), ptr(cost), ptr(status)),
+              "pislam_pose_refine_batch")
+    return pose_out, inlier, ninliers, cost, status
+
+
 # ---- bag of words: integer weights and the key-frame database ----------
-BOW_MAX_STRIDE = 16384       # entries of a bag-of-words vector (pislam_bow_vector_batch)
+BOW_MAX_STRIDE = 16384      # entries of a bag-of-words vector (pislam_bow_vector_batch)
 
 
 def _check_bow_rows(what, word, other, n):

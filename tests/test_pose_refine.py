@@ -1,0 +1,862 @@
+"""pislam_pose_refine_batch: batched motion-only pose optimisation from 3D-2D matches.
+
+The expectation is a numpy restatement of the contract (the comment in include/pislam_hip.h), independent of the
+library: float32 arrays and scalars with one operation per rounding for the per-observation work, float64 for the
+sums, the solve and the retraction, the tree order written as loops.  The host probe (tools/probes/
+pose_host_check.cpp, the library's own arithmetic header under the host compiler) and the library on the GPU must agree
+with it on every output word."""
+import ctypes
+import functools
+import math
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+F32, F64 = np.float32, np.float64
+COUNT_INVALID = 0xFFFFFFFF
+MONO = -(1 << 31)
+OBS_MAX = 1 << 22
+MAX_STRIDE = 16384
+Z_MIN = F32(2.0 ** -10)
+TH_MONO, TH_STEREO = F32(5.991), F32(7.815)
+LAMBDA_0, LAMBDA_MIN, LAMBDA_MAX = 2.0 ** -10, 2.0 ** -30, 2.0 ** 20
+SENT8, SENT32 = 0xA5, 0x5A5A5A5A
+POSE_FIELDS = ["rounds", "iters", "huber_rounds", "min_obs", "eps"]
+DEFAULT = (4, 10, 3, 10, 1e-6)                  # rounds, iters, huber_rounds, min_obs, eps
+
+
+# ---- the restatement ------------------------------------------------------------------------------------------------
+def ref_project(Tf, cam, xw, obs, w):
+    """Every observation at the float32 pose Tf: the contract's intermediates as float32 arrays."""
+    Tf, cam, xw = np.asarray(Tf, F32), np.asarray(cam, F32), np.asarray(xw, F32).reshape(-1, 3)
+    obs = np.asarray(obs, np.int64).reshape(-1, 3)
+    X, Y, Z = xw[:, 0], xw[:, 1], xw[:, 2]
+    fx, fy, cx, cy, bf = cam
+    stereo = obs[:, 2] != MONO
+    q = np.clip(obs, -OBS_MAX, OBS_MAX).astype(F32) * F32(1.0 / 256.0)
+    u, v, ur = q[:, 0], q[:, 1], q[:, 2]
+    with np.errstate(all="ignore"):
+        x = ((Tf[0] * X + Tf[1] * Y) + Tf[2] * Z) + Tf[9]
+        y = ((Tf[3] * X + Tf[4] * Y) + Tf[5] * Z) + Tf[10]
+        z = ((Tf[6] * X + Tf[7] * Y) + Tf[8] * Z) + Tf[11]
+        live = z >= Z_MIN
+        iz = F32(1.0) / z
+        px, py = x * iz, y * iz
+        pu, pv = fx * px + cx, fy * py + cy
+        eu, ev = u - pu, v - pv
+        er = ur - (pu - bf * iz)
+        e2 = eu * eu + ev * ev
+        e2 = np.where(stereo, e2 + er * er, e2)
+        chi2 = e2 * w
+        live = live & np.isfinite(chi2)
+        a, b, c = fx * iz, fy * iz, bf * iz
+        pxy = px * py
+        zero = np.zeros_like(px)
+        Ju = [pxy * fx, -((F32(1.0) + px * px) * fx), py * fx, -a, zero, px * a]
+        Jv = [(F32(1.0) + py * py) * fy, -(pxy * fy), -(px * fy), zero, -b, py * b]
+        Jr = [Ju[0] - c * py, Ju[1] + c * px, Ju[2], Ju[3], zero, Ju[5] - c * iz]
+    th = np.where(stereo, TH_STEREO, TH_MONO).astype(F32)
+    return dict(stereo=stereo, live=live, chi2=chi2, th=th, eu=eu, ev=ev, er=er, Ju=Ju, Jv=Jv, Jr=Jr)
+
+
+def ref_terms(P, w, robust):
+    """The 28 float32 terms of every observation, [n][28] (rows of dead observations hold rubbish)."""
+    stereo, chi2, th = P["stereo"], P["chi2"], P["th"]
+    Ju, Jv, Jr, eu, ev, er = P["Ju"], P["Jv"], P["Jr"], P["eu"], P["ev"], P["er"]
+    with np.errstate(all="ignore"):
+        wr, rho = w.astype(F32).copy(), chi2.copy()
+        if robust:
+            hub = chi2 > th
+            k = np.sqrt(th / chi2)
+            wr = np.where(hub, w * k, wr)
+            rho = np.where(hub, (chi2 * k) * F32(2.0) - th, rho)
+        cols = []
+        for j in range(6):
+            for kk in range(j, 6):
+                s = Ju[j] * Ju[kk] + Jv[j] * Jv[kk]
+                s = np.where(stereo, s + Jr[j] * Jr[kk], s)
+                cols.append(s * wr)
+        for j in range(6):
+            s = Ju[j] * eu + Jv[j] * ev
+            s = np.where(stereo, s + Jr[j] * er, s)
+            cols.append(s * wr)
+        cols.append(rho)
+    out = np.stack(cols, 1)
+    assert out.dtype == F32
+    return out
+
+
+def ref_tree(M):
+    """The sums of the rows of the float64 array M [n][K] in the contract's order."""
+    M = np.asarray(M, F64)
+    p = np.zeros((256, M.shape[1]))
+    for s in range(0, len(M), 256):                          # partial i mod 256, ascending i
+        chunk = M[s:s + 256]
+        p[:len(chunk)] = p[:len(chunk)] + chunk
+    h = 128
+    while h >= 1:
+        p[:h] = p[:h] + p[h:2 * h]
+        h //= 2
+    return p[0].copy()
+
+
+def frame_weights(fr):
+    n = len(fr["obs"])
+    if fr.get("level") is None:
+        return np.ones(n, F32), np.zeros(n, bool)
+    tab = np.asarray(fr["tab"], F32)
+    lv = np.asarray(fr["level"], np.int64)
+    bad = lv >= len(tab)
+    return tab[np.where(bad, 0, lv)].astype(F32), bad
+
+
+def ref_pass(fr, Tf, classify, robust, active):
+    w, bad = frame_weights(fr)
+    P = ref_project(Tf, fr["cam"], fr["xw"], fr["obs"], w)
+    live = P["live"] & ~bad
+    if classify:
+        with np.errstate(all="ignore"):
+            active = live & (P["chi2"] <= P["th"])
+    use = live & active
+    M = np.zeros((len(use), 30))
+    if use.any():
+        T = ref_terms(P, w, robust)
+        M[use, :28] = T[use].astype(F64)
+        M[use, 28] = 1.0
+        M[use, 29] = P["chi2"][use].astype(F64)
+    return ref_tree(M), active
+
+
+def ref_solve(S, lam):
+    A = np.zeros((6, 6))
+    o = 0
+    for j in range(6):
+        for k in range(j, 6):
+            A[j][k] = A[k][j] = S[o]
+            o += 1
+    b = np.array([-S[21 + j] for j in range(6)])
+    s = F64(1.0) + F64(lam)
+    for j in range(6):
+        A[j][j] = A[j][j] * s
+    ok = True
+    with np.errstate(all="ignore"):
+        for c in range(6):
+            ok = ok and bool(A[c][c] > 0.0)
+            for r in range(c + 1, 6):
+                f = A[r][c] / A[c][c]
+                for j in range(c + 1, 6):
+                    A[r][j] = A[r][j] - f * A[c][j]
+                b[r] = b[r] - f * b[c]
+        d = np.zeros(6)
+        for r in range(5, -1, -1):
+            t = b[r]
+            for j in range(r + 1, 6):
+                t = t - A[r][j] * d[j]
+            d[r] = t / A[r][r]
+            ok = ok and bool(np.isfinite(d[r]))
+    return ok, d
+
+
+def ref_retract(T, d):
+    T, d = np.asarray(T, F64), np.asarray(d, F64)
+    a = d[:3] * F64(0.5)
+    n = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]
+    m, e = F64(1.0) - n, F64(1.0) + n
+    two = F64(2.0)
+    Q = np.array([
+        [(m + two * (a[0] * a[0])) / e, (two * (a[0] * a[1]) - two * a[2]) / e, (two * (a[0] * a[2]) + two * a[1]) / e],
+        [(two * (a[1] * a[0]) + two * a[2]) / e, (m + two * (a[1] * a[1])) / e, (two * (a[1] * a[2]) - two * a[0]) / e],
+        [(two * (a[2] * a[0]) - two * a[1]) / e, (two * (a[2] * a[1]) + two * a[0]) / e, (m + two * (a[2] * a[2])) / e]])
+    R, t = T[:9].reshape(3, 3), T[9:]
+    out = np.zeros(12)
+    for i in range(3):
+        for j in range(3):
+            out[3 * i + j] = (Q[i][0] * R[0][j] + Q[i][1] * R[1][j]) + Q[i][2] * R[2][j]
+        out[9 + i] = ((Q[i][0] * t[0] + Q[i][1] * t[1]) + Q[i][2] * t[2]) + d[3 + i]
+    return out
+
+
+def ref_frame(fr, prm=DEFAULT):
+    """One frame of the call: dict(pose float32 [12], inlier uint8 [n], ninliers, cost, status)."""
+    rounds, iters, hr, min_obs, eps = prm
+    pose_in, cam = np.asarray(fr["pose"], F32), np.asarray(fr["cam"], F32)
+    n = len(fr["obs"])
+    out = dict(pose=pose_in.copy(), inlier=np.zeros(n, np.uint8), ninliers=0, cost=0.0, status=0)
+    if not (np.isfinite(pose_in).all() and np.isfinite(cam).all()):
+        out["status"] = 2
+        return out
+    if n < min_obs:
+        out["status"] = 1
+        return out
+    T = pose_in.astype(F64)
+    active = np.ones(n, bool)
+    S, _ = ref_pass(fr, T.astype(F32), False, 0 < hr, active)
+    evals, code = 1, 0
+    for r in range(rounds):
+        lam, it = LAMBDA_0, 0
+        while it < iters:
+            it += 1
+            ok, d = ref_solve(S, lam)
+            if not ok:
+                lam = min(8.0 * lam, LAMBDA_MAX)
+                continue
+            Tt = ref_retract(T, d)
+            St, _ = ref_pass(fr, Tt.astype(F32), False, r < hr, active)
+            evals += 1
+            if St[27] < S[27]:
+                T, S, lam = Tt, St, max(lam * 0.25, LAMBDA_MIN)
+            else:
+                lam = min(8.0 * lam, LAMBDA_MAX)
+            if np.abs(d).max() <= eps:
+                break
+        S, active = ref_pass(fr, T.astype(F32), True, r + 1 < hr, active)
+        evals += 1
+        out["ninliers"], out["cost"] = int(S[28]), float(S[29])
+        if r + 1 < rounds and out["ninliers"] < min_obs:
+            code = 1
+            break
+    out["pose"], out["inlier"], out["status"] = T.astype(F32), active.astype(np.uint8), code | evals << 8
+    return out
+
+
+def ref_level_weights(nlevels, scale=1.2):
+    s, f, out = F32(scale), F32(1.0), []
+    for _ in range(nlevels):
+        out.append(F32(1.0) / (f * f))
+        f = f * s
+    return np.array(out, F32)
+
+
+# ---- scenes -----------------------------------------------------------------------------------------------------------
+CAM = np.array([500, 500, 320, 240, 50], F32)
+IDENTITY = np.array([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], F32)
+
+
+def rodrigues(r):
+    th = np.linalg.norm(r)
+    K = np.array([[0, -r[2], r[1]], [r[2], 0, -r[0]], [-r[1], r[0], 0]])
+    if th < 1e-12:
+        return np.eye(3) + K
+    K = K / th
+    return np.eye(3) + math.sin(th) * K + (1 - math.cos(th)) * (K @ K)
+
+
+def scene(seed, n=200, stereo=0.5, outliers=0.2, noise=0.5, levels=True, rot=0.05, trans=0.2):
+    """The issue's scene.  Returns the frame, the true pose (R, t) and the mask of true inliers."""
+    rng = np.random.default_rng(seed)
+    xw = np.stack([rng.uniform(-4, 4, n), rng.uniform(-3, 3, n), rng.uniform(3, 15, n)], 1).astype(F32)
+    R, t = rodrigues(rng.normal(0, rot, 3)), rng.normal(0, trans, 3)
+    xc = xw.astype(F64) @ R.T + t
+    level = rng.integers(0, 8, n)
+    sig = noise * 1.2 ** level if levels else np.full(n, noise)
+    u = 500 * xc[:, 0] / xc[:, 2] + 320 + rng.normal(0, 1, n) * sig
+    v = 500 * xc[:, 1] / xc[:, 2] + 240 + rng.normal(0, 1, n) * sig
+    ur = u - 50 / xc[:, 2] + rng.normal(0, 1, n) * sig
+    out = rng.permutation(n)[:int(round(outliers * n))]
+    u[out] += rng.uniform(-40, 40, len(out))
+    v[out] += rng.uniform(-40, 40, len(out))
+    ur[out] += rng.uniform(-40, 40, len(out))
+    is_stereo = rng.uniform(0, 1, n) < stereo
+    obs = np.stack([np.rint(u * 256), np.rint(v * 256), np.where(is_stereo, np.rint(ur * 256), MONO)], 1).astype(np.int64)
+    good = np.ones(n, bool)
+    good[out] = False
+    fr = dict(pose=IDENTITY.copy(), cam=CAM.copy(), xw=xw, obs=obs, level=level.astype(np.uint8) if levels else None,
+              tab=ref_level_weights(8) if levels else None)
+    return fr, (R, t), good
+
+
+def pose_errors(pose, truth):
+    R, t = np.asarray(pose[:9], F64).reshape(3, 3), np.asarray(pose[9:], F64)
+    E = R @ truth[0].T                                       # (atan2 of sine and cosine: acos alone is blind below 3e-4 rad
+    s = np.array([E[2, 1] - E[1, 2], E[0, 2] - E[2, 0], E[1, 0] - E[0, 1]]) / 2   # on a rotation rounded to float32)
+    return math.degrees(math.atan2(np.linalg.norm(s), (np.trace(E) - 1) / 2)), float(np.linalg.norm(t - truth[1]))
+
+
+# ---- CPU: declarations, the expectation's anchors, behaviour ------------------------------------------------------------
+def test_pose_refine_is_declared_everywhere():
+    text = open(os.path.join(ROOT, "include", "pislam_hip.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    assert re.search(r"\bint\s+pislam_pose_refine_batch\s*\(", code), "not declared in include/pislam_hip.h"
+    m = re.search(r"typedef struct pislam_pose_params \{([^}]*)\} pislam_pose_params;", code)
+    assert m and re.findall(r"(?:int32_t|double)\s+(\w+)\s*;", m.group(1)) == POSE_FIELDS
+    from pislam_amd import capi, frontend
+    assert len(capi.SYMBOLS["pislam_pose_refine_batch"][1]) == 17
+    assert [n for n, _ in capi.PoseParams._fields_] == POSE_FIELDS and ctypes.sizeof(capi.PoseParams) == 24
+    for f in ("poseRefineBatch", "poseObservationsQ8", "poseLevelWeights"):
+        assert callable(getattr(frontend, f)), f
+    assert hasattr(capi.load(), "pislam_pose_refine_batch")
+    for word in ("5.991f", "7.815f", "2^-10", "2^-30", "2^20"):
+        assert word in text, word
+    for f in ("pislam_pose_math.h", "pislam_pose_kernels.h"):
+        assert os.path.exists(os.path.join(ROOT, "pislam_amd", "csrc", f)), f
+
+
+def test_ref_pose_anchors():
+    """The expectation itself, independent of the library."""
+    # noise-free scenes recover the pose.  The observations are rounded to Q8: 2^-9 px at fx = 500 is 4e-6 rad per
+    # observation and, at a depth of up to 15, 6e-5 in translation; 200 of them average well below that.
+    for seed, stereo in ((1, 0.0), (2, 0.5), (3, 1.0)):
+        fr, truth, _ = scene(seed, stereo=stereo, outliers=0.0, noise=0.0, levels=False)
+        r = ref_frame(fr)
+        rot, tr = pose_errors(r["pose"], truth)
+        assert r["status"] & 255 == 0 and r["ninliers"] == 200 and math.radians(rot) < 2e-5 and tr < 2e-4, (rot, tr)
+    # Jacobian rows against central differences of the restated residual in float64 (left increment through the
+    # retraction).  Step h = 1e-5: the truncation error is h^2 / 6 times a third derivative of the order of 10 * fx,
+    # about 1e-7; float64 rounding of a residual of the order of 10 over 2 h adds 1e-10; the float32 rows themselves
+    # carry a few ulps, 5e-7 relative.  Bound: 1e-5 * (1 + |J|).
+    fr, _, _ = scene(4, n=40, stereo=0.5, outliers=0.0)
+    T0 = ref_retract(IDENTITY.astype(F64), np.array([0.03, -0.02, 0.04, 0.1, -0.2, 0.05])).astype(F32)
+
+    def residual(d):
+        T = ref_retract(T0.astype(F64), d)
+        R, t = T[:9].reshape(3, 3), T[9:]
+        xc = fr["xw"].astype(F64) @ R.T + t
+        q = fr["obs"].astype(F64) / 256
+        pu = 500 * xc[:, 0] / xc[:, 2] + 320
+        return np.stack([q[:, 0] - pu, q[:, 1] - (500 * xc[:, 1] / xc[:, 2] + 240), q[:, 2] - (pu - 50 / xc[:, 2])], 1)
+
+    P = ref_project(T0, fr["cam"], fr["xw"], fr["obs"], np.ones(40, F32))
+    h = 1e-5
+    for j in range(6):
+        d = np.zeros(6)
+        d[j] = h
+        num = (residual(d) - residual(-d)) / (2 * h)
+        for row, name in enumerate(("Ju", "Jv", "Jr")):
+            ana = P[name][j].astype(F64)
+            sel = P["stereo"] if row == 2 else np.ones(40, bool)
+            assert (np.abs(num[:, row] - ana)[sel] <= 1e-5 * (1 + np.abs(ana[sel]))).all(), (name, j)
+    # the tree sum of integers is exact
+    rng = np.random.default_rng(5)
+    for n in (0, 1, 255, 256, 257, 513, 5000):
+        M = rng.integers(-1 << 40, 1 << 40, (n, 3)).astype(F64)
+        assert ref_tree(M).tolist() == [math.fsum(M[:, k]) for k in range(3)]
+    # the retraction's rotation is orthonormal
+    T = IDENTITY.astype(F64)
+    for k in range(50):
+        T = ref_retract(T, rng.normal(0, 0.3, 6))
+        R = T[:9].reshape(3, 3)
+        assert np.abs(R @ R.T - np.eye(3)).max() < 1e-14 and abs(np.linalg.det(R) - 1) < 1e-14
+    # codes: dead observations, min_obs, non-finite inputs
+    fr, _, _ = scene(6, n=30, outliers=0.0)
+    behind = dict(fr, xw=fr["xw"] * np.array([1, 1, -1], F32))
+    r = ref_frame(behind)
+    assert r["status"] == 1 | 2 << 8 and r["ninliers"] == 0 and not r["inlier"].any() and r["cost"] == 0.0
+    assert (r["pose"] == IDENTITY).all()
+    few = {k: (v[:9] if k in ("xw", "obs", "level") else v) for k, v in fr.items()}
+    r = ref_frame(few)
+    assert r["status"] == 1 and r["ninliers"] == 0 and (r["pose"] == IDENTITY).all()
+    assert ref_frame(few, (4, 10, 3, 9, 1e-6))["status"] & 255 == 0
+    for key, idx in (("pose", 3), ("pose", 11), ("cam", 0), ("cam", 4)):
+        for bad in (np.nan, np.inf):
+            g = dict(fr, **{key: fr[key].copy()})
+            g[key][idx] = bad
+            r = ref_frame(g)
+            assert r["status"] == 2 and r["ninliers"] == 0 and r["pose"].tobytes() == g["pose"].tobytes()
+    lv = dict(fr, level=np.full(30, 8, np.uint8))               # every level out of the table: all dead
+    assert ref_frame(lv)["status"] == 1 | 2 << 8
+
+
+# The issue's scene with seeds 1..5 and 0 %, 50 % and 100 % stereo: all 15 runs are checked.  With this restatement the
+# worst values over the 15 runs are written beside the bounds in check_behaviour.
+BEHAVIOUR_CASES = [(seed, stereo) for seed in (1, 2, 3, 4, 5) for stereo in (0.0, 0.5, 1.0)]
+
+
+@functools.lru_cache(maxsize=None)
+def behaviour_scenes():
+    return [scene(seed, stereo=stereo) for seed, stereo in BEHAVIOUR_CASES]
+
+
+def check_behaviour(run, report=None):
+    """run(frames, params) -> one result dict per frame.  Worst over the 15 runs with the restatement: rotation
+    0.057 deg, translation 0.0084, true inliers kept 99.4 %, outliers accepted 2.5 %, evaluations (passes) 15..32."""
+    scenes = behaviour_scenes()
+    res = run([s[0] for s in scenes], DEFAULT)
+    worst = dict(rot=0.0, tr=0.0, kept=1.0, acc=0.0, ev_min=1 << 30, ev_max=0)
+    for (fr, truth, good), r in zip(scenes, res):
+        rot, tr = pose_errors(r["pose"], truth)
+        inl = r["inlier"].astype(bool)
+        kept, acc = (inl & good).sum() / good.sum(), (inl & ~good).sum() / (~good).sum()
+        ev = r["status"] >> 8
+        worst = dict(rot=max(worst["rot"], rot), tr=max(worst["tr"], tr), kept=min(worst["kept"], kept),
+                     acc=max(worst["acc"], acc), ev_min=min(worst["ev_min"], ev), ev_max=max(worst["ev_max"], ev))
+    print("pose behaviour, worst of %d runs: %r" % (len(scenes), worst))
+    if report is not None:
+        report.update(worst)
+    for (fr, truth, good), r in zip(scenes, res):
+        rot, tr = pose_errors(r["pose"], truth)
+        inl = r["inlier"].astype(bool)
+        assert r["status"] & 255 == 0 and r["ninliers"] == inl.sum()
+        assert rot < 0.1 and tr < 0.02, (rot, tr)
+        assert (inl & good).sum() >= 0.95 * good.sum() and (inl & ~good).sum() <= 0.10 * (~good).sum()
+
+
+def test_behaviour_of_the_restatement():
+    check_behaviour(lambda frames, prm: [ref_frame(f, prm) for f in frames])
+
+
+# ---- the pin cases: the smallest shapes where the kernel can go wrong -------------------------------------------------
+PIN_STRIDE = 2304                                # 2049, one above the register-resident 2048, fits
+
+
+def sub(fr, n):
+    return {k: (v[:n] if k in ("xw", "obs", "level") and v is not None else v) for k, v in fr.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def pin_frames():
+    """(name, frame, count as passed) of the main pin batch; every frame carries levels (a call without a level table
+    ignores them)."""
+    th_tab = np.concatenate([ref_level_weights(8), [TH_MONO / F32(4), np.nextafter(TH_MONO, F32(9)) / F32(4),
+                                                    TH_STEREO / F32(4), np.nextafter(TH_STEREO, F32(9)) / F32(4)]]).astype(F32)
+    out = []
+    big, _, _ = scene(11, n=PIN_STRIDE, stereo=0.5)
+    for n in (0, 1, 2, 9, 10, 255, 256, 257, 513, 2049):
+        out.append(("n%d" % n, sub(big, n), n))
+    out.append(("invalid count", sub(big, 40), COUNT_INVALID))
+    out.append(("count above stride", big, -1))                         # the caller passes stride + 7
+    for name, st in (("mono", 0.0), ("stereo", 1.0), ("mixed", 0.5)):
+        out.append((name, scene(12, n=300, stereo=st)[0], 300))
+    fr = scene(13, n=120, stereo=0.5)[0]
+    fr["xw"][::7, 2] *= F32(-1)                                         # behind the camera
+    fr["level"][5::11] = 12 + (np.arange(len(fr["level"][5::11])) % 3) * 100  # levels out of the table: 12, 112, 212
+    out.append(("behind and bad levels", fr, 120))
+    fr = scene(14, n=64, stereo=0.5, outliers=0.0)[0]                    # z below, at and above 2^-10 at the first pose
+    fr["xw"][:6] = np.array([[0, 0, np.nextafter(Z_MIN, F32(0))], [0, 0, Z_MIN], [0, 0, np.nextafter(Z_MIN, F32(1))],
+                             [1e-4, 0, Z_MIN], [0, 0, 0], [0, 0, -Z_MIN]], F32)
+    out.append(("z at the limit", fr, 64))
+    fr = scene(15, n=64, stereo=0.5, outliers=0.0)[0]                    # chi2 exactly th and one ulp above (eu = 2, w = th / 4)
+    for i, (lv, st) in enumerate(((8, 0), (9, 0), (10, 1), (11, 1))):
+        fr["xw"][i] = (0, 0, 1)
+        fr["obs"][i] = (322 * 256, 240 * 256, 270 * 256 if st else MONO)
+        fr["level"][i] = lv
+    out.append(("chi2 at th", fr, 64))
+    fr = scene(16, n=80, stereo=0.5)[0]
+    fr["xw"][3], fr["xw"][10, 1], fr["xw"][20, 2], fr["xw"][30, 0] = np.nan, np.inf, -np.inf, np.inf
+    fr["obs"][40] = (1 << 30, -(1 << 30), (1 << 31) - 1)
+    out.append(("non-finite points", fr, 80))
+    for key, idx, bad in (("pose", 4, np.nan), ("pose", 10, np.inf), ("cam", 1, np.nan), ("cam", 4, -np.inf)):
+        fr = scene(17, n=40)[0]
+        fr[key][idx] = bad
+        out.append(("non-finite %s" % key, fr, 40))
+    fr = scene(18, n=50, stereo=0.5, outliers=0.0)[0]                    # every point the same: H is singular
+    fr["xw"][:], fr["obs"][:], fr["level"][:] = fr["xw"][0], fr["obs"][0], 0
+    fr["obs"][:, 2] = fr["obs"][0, 0] - 2000
+    out.append(("singular", fr, 50))
+    fr = scene(19, n=400, stereo=0.5, outliers=0.6)[0]                   # inliers fall below min_obs on the way
+    fr["obs"][40:, :2] += 40000
+    out.append(("mostly outliers", fr, 400))
+    far = scene(20, n=100, stereo=0.5, rot=0.3, trans=1.0)[0]             # a start far away: rejected steps
+    out.append(("far start", far, 100))
+    for _, fr, _ in out:                                                 # one call, one table: 12 entries
+        fr["tab"] = th_tab
+    return out
+
+
+PIN_PARAMS = [DEFAULT, (1, 1, 0, 3, 0.0), (8, 32, 8, 16384, 0.0), (8, 32, 8, 3, 0.0), (4, 10, 0, 10, 0.0), (2, 3, 2, 10, 1e-3)]
+PIN_SMALL = ("n2", "n9", "n10", "n257", "mixed", "behind and bad levels", "z at the limit", "chi2 at th", "singular",
+             "non-finite points", "non-finite pose", "far start")
+
+
+def pin_set(prm):
+    frames = pin_frames()
+    return frames if prm == DEFAULT else [f for f in frames if f[0] in PIN_SMALL]
+
+
+def clamp_count(count, stride):
+    count = stride + 7 if count == -1 else count
+    return 0 if count == COUNT_INVALID else min(count, stride)
+
+
+@functools.lru_cache(maxsize=None)
+def pin_reference(prm, with_level):
+    out = []
+    for _, fr, count in pin_set(prm):
+        f = sub(fr, clamp_count(count, PIN_STRIDE))
+        out.append(ref_frame(f if with_level else dict(f, level=None, tab=None), prm))
+    return out
+
+
+def hexf(a):
+    return " ".join("%08x" % v for v in np.asarray(a, F32).reshape(-1).view(np.uint32))
+
+
+def probe_line(fr, prm):
+    n = len(fr["obs"])
+    has = fr.get("level") is not None
+    tab = np.asarray(fr["tab"], F32) if has else np.zeros(0, F32)
+    head = "%d %d %d %d %016x %d %d %d" % (prm[0], prm[1], prm[2], prm[3], np.array(prm[4], F64).view(np.uint64), int(has),
+                                           len(tab), n)
+    parts = [head, hexf(fr["pose"]), hexf(fr["cam"]), hexf(tab)]
+    xw = np.asarray(fr["xw"], F32).reshape(-1, 3).view(np.uint32)
+    lv = fr["level"] if has else np.zeros(n, np.uint8)
+    for i in range(n):
+        o = fr["obs"][i]
+        parts.append("%08x %08x %08x %d %d %d %d" % (xw[i, 0], xw[i, 1], xw[i, 2], o[0], o[1], o[2], lv[i]))
+    return " ".join(parts)
+
+
+def result_line(r):
+    inl = "".join(str(int(v)) for v in r["inlier"]) or "-"
+    return "%d %d %016x %s %s" % (r["status"], r["ninliers"], np.array(r["cost"], F64).view(np.uint64), hexf(r["pose"]), inl)
+
+
+def test_host_probe_against_the_restatement(tmp_path):
+    """The library's own arithmetic header, compiled for the host with -ffp-contract=off, run serially: every output
+    word of every pin case, with and without the level table, for every parameter set."""
+    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    exe = str(tmp_path / "pose_host_check")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-I", os.path.join(ROOT, "pislam_amd", "csrc"),
+                           os.path.join(ROOT, "tools", "probes", "pose_host_check.cpp"), "-o", exe])
+    lines, want = [], []
+    for prm in PIN_PARAMS:
+        for with_level in (True, False):
+            if prm != DEFAULT and not with_level:
+                continue
+            for (_, fr, count), r in zip(pin_set(prm), pin_reference(prm, with_level)):
+                f = sub(fr, clamp_count(count, PIN_STRIDE))
+                lines.append(probe_line(f if with_level else dict(f, level=None, tab=None), prm))
+                want.append(result_line(r))
+    cases = tmp_path / "cases.txt"
+    cases.write_text("\n".join(lines) + "\n")
+    got = subprocess.run([exe, str(cases)], check=True, capture_output=True, text=True).stdout.splitlines()
+    assert len(got) == len(want)
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert g == w, "case %d: %s" % (k, lines[k][:60])
+
+
+# ---- the Python helpers on the host -----------------------------------------------------------------------------------
+PO_LEVELS = [(40, 30, 0, 0), (33, 25, 30, 0), (28, 21, 30, 36)]          # (width, height, row0, col0): three levels
+PO_SCALES = [65536, 79438, 93623]
+
+
+def observations_case(device):
+    import torch
+    from pislam_amd.frontend import poseObservationsQ8
+    rng = np.random.default_rng(21)
+    B, S = 3, 50
+    kp = np.zeros((B, S), np.int64)
+    for b in range(B):
+        for i in range(S):
+            w, h, row0, col0 = PO_LEVELS[rng.integers(0, 3)]
+            x, y = col0 + rng.integers(0, w), row0 + rng.integers(0, h)
+            if i % 9 == 4:
+                x, y = 70 + int(rng.integers(0, 20)), int(rng.integers(0, 60))          # in no level
+            kp[b, i] = int(rng.integers(0, 256)) << 24 | int(x) << 12 | int(y)
+    disp = rng.integers(-1, 4000, (B, S))
+    disp[:, ::5] = -1
+    pos = rng.integers(0, 64 * 256, (B, S, 2))
+
+    def want(use_disp, use_pos, scales):
+        obs, lev = np.zeros((B, S, 3), np.int64), np.full((B, S), 255, np.int64)
+        for b in range(B):
+            for i in range(S):
+                x, y = (int(kp[b, i]) >> 12) & 0xFFF, int(kp[b, i]) & 0xFFF
+                obs[b, i] = (0, 0, MONO)
+                for l, ((w, h, row0, col0), s) in enumerate(zip(PO_LEVELS, scales)):
+                    if col0 <= x < col0 + w and row0 <= y < row0 + h:
+                        px, py = (int(pos[b, i, 0]), int(pos[b, i, 1])) if use_pos else (x << 8, y << 8)
+                        u = ((px - (col0 << 8)) * s + 32768) // 65536
+                        v = ((py - (row0 << 8)) * s + 32768) // 65536
+                        d = int(disp[b, i]) if use_disp else -1
+                        obs[b, i], lev[b, i] = (u, v, u - d if d >= 0 else MONO), l
+        return obs, lev
+
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(device)
+    from pislam_amd.frontend import level_scales_q16
+    for use_disp, use_pos, scales in ((False, False, None), (True, False, PO_SCALES), (True, True, PO_SCALES),
+                                      (False, True, None)):
+        obs, lev = poseObservationsQ8(t(kp, torch.int32), PO_LEVELS, scales, t(disp, torch.int32) if use_disp else None,
+                                      t(pos, torch.int32) if use_pos else None)
+        wo, wl = want(use_disp, use_pos, scales or level_scales_q16(PO_LEVELS))
+        assert obs.dtype == torch.int32 and lev.dtype == torch.uint8 and str(obs.device).startswith(device)
+        assert (obs.cpu().numpy() == wo).all() and (lev.cpu().numpy() == wl).all()
+        assert (wl == 255).any() and (wl == 2).any() and (not use_disp or (wo[..., 2] != MONO).any())
+
+
+def test_pose_observations_q8_on_the_host():
+    observations_case("cpu")
+
+
+def test_pose_level_weights():
+    from pislam_amd.frontend import poseLevelWeights
+    for n, s in ((1, 1.2), (8, 1.2), (16, 1.2), (8, 2.0), (5, 1.4142135)):
+        got = poseLevelWeights(n, s)
+        assert got.dtype == np.float32 and got.tobytes() == ref_level_weights(n, s).tobytes()
+    assert poseLevelWeights(8)[0] == 1 and abs(float(poseLevelWeights(8)[7]) - 1.2 ** -14) < 1e-6
+    for bad in (0, 17):
+        with pytest.raises(ValueError):
+            poseLevelWeights(bad)
+
+
+# ---- GPU ----------------------------------------------------------------------------------------------------------------
+OUT_TYPES = dict(pose_out=(12, "float32"), inlier=(None, "uint8"), ninliers=(0, "int32"), cost=(0, "float64"),
+                 status=(0, "int32"))
+
+
+class Device:
+    def __init__(self, ctx):
+        import torch
+        from pislam_amd import capi
+        self.torch, self.capi, self.ctx, self.lib = torch, capi, ctx, ctx.lib
+
+    def up(self, a):
+        return self.torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
+
+    def sentinels(self, B, stride):
+        t = self.torch
+        return dict(pose_out=t.full((B, 12), SENT32, dtype=t.int32, device="cuda").view(t.float32),
+                    inlier=t.full((B, stride), SENT8, dtype=t.uint8, device="cuda"),
+                    ninliers=t.full((B,), SENT32, dtype=t.int32, device="cuda"),
+                    cost=t.full((B, 2), SENT32, dtype=t.int32, device="cuda").view(t.float64).reshape(B),
+                    status=t.full((B,), SENT32, dtype=t.int32, device="cuda"))
+
+    def pack(self, frames, counts, stride, with_level=True):
+        """Host arrays of a batch: slots at and beyond a frame's observations hold rubbish that must not be read."""
+        B = len(frames)
+        rng = np.random.default_rng(99)
+        xw = rng.normal(0, 1e30, (B, stride, 3)).astype(F32)
+        obs = rng.integers(-1 << 31, 1 << 31, (B, stride, 3)).astype(np.int32)
+        level = rng.integers(0, 256, (B, stride)).astype(np.uint8)
+        pose, cam = np.zeros((B, 12), F32), np.zeros((B, 5), F32)
+        tab = None
+        for b, fr in enumerate(frames):
+            n = len(fr["obs"])
+            pose[b], cam[b], xw[b, :n], obs[b, :n] = fr["pose"], fr["cam"], fr["xw"], fr["obs"]
+            if fr.get("level") is not None:
+                level[b, :n] = fr["level"]
+                if tab is None or len(fr["tab"]) > len(tab):
+                    tab = np.asarray(fr["tab"], F32)
+        cnt = np.array([stride + 7 if c == -1 else c for c in counts], np.uint32).view(np.int32)
+        return dict(pose=pose, cam=cam, xw=xw, obs=obs, counts=cnt, level=level if with_level else None,
+                    tab=tab if with_level else None)
+
+    def call(self, prm, d, stride, B, o, level="d", tab="d", nlevels=None):
+        ptr = self.capi.ptr
+        p = self.capi.PoseParams(*prm) if prm is not None else None
+        level = d.get("level") if isinstance(level, str) else level
+        tab = d.get("tab") if isinstance(tab, str) else tab
+        ctab = None if tab is None else (ctypes.c_float * len(tab))(*[float(v) for v in tab])
+        return self.lib.pislam_pose_refine_batch(self.ctx.h, None if p is None else ctypes.byref(p), ptr(d["pose"]),
+                                                 ptr(d["cam"]), ptr(d["xw"]), ptr(d["obs"]), ptr(d["counts"]), ptr(level),
+                                                 ctab, (0 if tab is None else len(tab)) if nlevels is None else nlevels,
+                                                 stride, B, ptr(o["pose_out"]), ptr(o["inlier"]), ptr(o["ninliers"]),
+                                                 ptr(o["cost"]), ptr(o["status"]))
+
+    def upload(self, h):
+        return {k: (self.up(v) if k != "tab" and v is not None else v) for k, v in h.items()}
+
+    def run(self, frames, counts, stride, prm, with_level=True):
+        h = self.pack(frames, counts, stride, with_level)
+        d = self.upload(h)
+        o = self.sentinels(len(frames), stride)
+        assert self.call(prm, d, stride, len(frames), o) == 0, self.lib.pislam_last_error(self.ctx.h)
+        self.ctx.synchronize()
+        return {k: v.cpu().numpy() for k, v in o.items()}
+
+
+def assert_frames(got, want, ns, what=""):
+    """Every output word of every frame, and the sentinels at and beyond n."""
+    for b, (w, n) in enumerate(zip(want, ns)):
+        tag = "%s frame %d" % (what, b)
+        assert int(got["status"][b]) == w["status"], (tag, int(got["status"][b]), w["status"])
+        assert int(got["ninliers"][b]) == w["ninliers"], tag
+        assert got["cost"][b:b + 1].view(np.uint64)[0] == np.array(w["cost"], F64).view(np.uint64), tag
+        assert got["pose_out"][b].view(np.uint32).tolist() == w["pose"].view(np.uint32).tolist(), tag
+        assert (got["inlier"][b, :n] == w["inlier"]).all(), tag
+        assert (got["inlier"][b, n:] == SENT8).all(), tag
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prm,with_level", [(p, True) for p in PIN_PARAMS] + [(DEFAULT, False)],
+                         ids=lambda v: "r%d_i%d_h%d_m%d_e%g" % v if isinstance(v, tuple) else str(v))
+def test_pose_refine_pins(gpu_ctx, prm, with_level):
+    cases = pin_set(prm)
+    frames = [sub(fr, clamp_count(c, PIN_STRIDE)) for _, fr, c in cases]
+    got = Device(gpu_ctx).run(frames, [c for _, _, c in cases], PIN_STRIDE, prm, with_level)
+    want = pin_reference(prm, with_level)
+    assert_frames(got, want, [len(f["obs"]) for f in frames], "%r" % (prm,))
+    if prm == DEFAULT:
+        codes = [w["status"] & 255 for w in want]
+        assert 0 in codes and 1 in codes and 2 in codes
+
+
+@pytest.mark.gpu
+def test_pose_refine_full_stride(gpu_ctx):
+    """One frame at stride 16384, every slot in use (64 observations per lane, re-read in every pass)."""
+    fr = scene(31, n=MAX_STRIDE, stereo=0.5)[0]
+    prm = (2, 3, 1, 10, 1e-6)
+    got = Device(gpu_ctx).run([fr], [MAX_STRIDE], MAX_STRIDE, prm)
+    want = ref_frame(fr, prm)
+    assert want["status"] & 255 == 0 and want["ninliers"] > 10000
+    assert_frames(got, [want], [MAX_STRIDE], "stride 16384")
+
+
+@pytest.mark.gpu
+def test_pose_refine_behaviour_on_the_library(gpu_ctx):
+    d = Device(gpu_ctx)
+
+    def run(frames, prm):
+        got = d.run(frames, [len(f["obs"]) for f in frames], 200, prm)
+        return [dict(pose=got["pose_out"][b], inlier=got["inlier"][b], ninliers=int(got["ninliers"][b]),
+                     cost=float(got["cost"][b]), status=int(got["status"][b])) for b in range(len(frames))]
+    check_behaviour(run)
+
+
+@pytest.mark.gpu
+def test_pose_refine_invalid_arguments_write_nothing(gpu_ctx):
+    d = Device(gpu_ctx)
+    t = d.torch
+    B, stride = 2, 64
+    frames = [scene(41, n=64)[0], scene(42, n=64)[0]]
+    h = d.pack(frames, [64, 64], stride)
+    dev = d.upload(h)
+    o = d.sentinels(B, stride)
+    good = DEFAULT
+    for prm in ((0, 10, 0, 10, 1e-6), (9, 10, 3, 10, 1e-6), (4, 0, 3, 10, 1e-6), (4, 33, 3, 10, 1e-6), (4, 10, -1, 10, 1e-6),
+                (4, 10, 5, 10, 1e-6), (4, 10, 3, 2, 1e-6), (4, 10, 3, 16385, 1e-6), (4, 10, 3, 10, -1e-9),
+                (4, 10, 3, 10, float("nan")), None):
+        assert d.call(prm, dev, stride, B, o) == -1, prm
+    assert d.call(good, dev, 0, B, o) == -1
+    assert d.call(good, dev, MAX_STRIDE + 1, B, o) == -1
+    assert d.call(good, dev, stride, -1, o) == -1
+    # the level table: missing, empty, too long, an entry that is not finite and positive
+    assert d.call(good, dev, stride, B, o, tab=None) == -1
+    assert d.call(good, dev, stride, B, o, nlevels=0) == -1
+    assert d.call(good, dev, stride, B, o, tab=[1.0] * 17) == -1
+    for bad in (0.0, -1.0, float("nan"), float("inf")):
+        assert d.call(good, dev, stride, B, o, tab=[1.0, bad, 1.0]) == -1, bad
+    host = np.zeros(B * stride * 3, np.int32)
+    for name in ("pose", "cam", "xw", "obs", "counts", "pose_out", "inlier", "ninliers", "cost", "status"):
+        for repl in (None, host):                                         # NULL, then a host pointer
+            ins, outs = dict(dev), dict(o)
+            (ins if name in ins else outs)[name] = repl
+            assert d.call(good, ins, stride, B, outs) == -1, name
+    assert d.call(good, dev, stride, B, o, level=host.view(np.uint8)) == -1
+    # overlaps: an output on an input, two outputs on each other (partly, too)
+    assert d.call(good, dev, stride, B, dict(o, ninliers=dev["counts"])) == -1
+    assert d.call(good, dev, stride, B, dict(o, inlier=dev["obs"].view(t.uint8))) == -1
+    assert d.call(good, dev, stride, B, dict(o, inlier=dev["level"])) == -1
+    assert d.call(good, dev, stride, B, dict(o, pose_out=dev["cam"])) == -1
+    assert d.call(good, dev, stride, B, dict(o, pose_out=dev["pose"].view(-1)[4:])) == -1
+    assert d.call(good, dev, stride, B, dict(o, status=o["ninliers"])) == -1
+    assert d.call(good, dev, stride, B, dict(o, ninliers=o["cost"].view(t.int32)[3:])) == -1
+    gpu_ctx.synchronize()
+    for k, v in o.items():
+        a = v.cpu().numpy()
+        assert (a == SENT8).all() if k == "inlier" else (a.view(np.uint8) == 0x5A).all(), k
+    for k in ("pose", "cam"):
+        assert dev[k].cpu().numpy().tobytes() == h[k].tobytes()
+    # batch 0 is a no-op after the checks: the pointers are not looked at
+    assert d.lib.pislam_pose_refine_batch(gpu_ctx.h, ctypes.byref(d.capi.PoseParams(*good)), None, None, None, None, None,
+                                          None, None, 0, stride, 0, None, None, None, None, None) == 0
+    # pose_out may be pose_in itself
+    want = [ref_frame(f) for f in frames]
+    assert d.call(good, dev, stride, B, dict(o, pose_out=dev["pose"])) == 0
+    gpu_ctx.synchronize()
+    got = {k: v.cpu().numpy() for k, v in o.items()}
+    got["pose_out"] = dev["pose"].cpu().numpy()
+    assert_frames(got, want, [64, 64], "in place")
+
+
+@pytest.mark.gpu
+def test_pose_refine_determinism_and_graph_replay(gpu_ctx):
+    """Two calls give the same bits; captured on a side stream (one stream, no parallel branches) of a fresh context
+    without a warm-up call, every replay writes what the eager call wrote."""
+    import torch as t
+    from pislam_amd.capi import Context
+    from pislam_amd.frontend import poseRefineBatch
+    d = Device(gpu_ctx)
+    frames = [scene(51, n=300)[0], scene(52, n=120, stereo=1.0)[0], scene(53, n=5)[0]]
+    h = d.pack(frames, [300, 120, 5], 300)
+    dev = d.upload(h)
+    args = (dev["pose"], dev["cam"], dev["xw"], dev["obs"], dev["counts"])
+    kw = dict(level=dev["level"], inv_sigma2=h["tab"])
+    first = [x.cpu().numpy().copy() for x in poseRefineBatch(*args, ctx=gpu_ctx, **kw, **d.sentinels(3, 300))]
+    again = [x.cpu().numpy().copy() for x in poseRefineBatch(*args, ctx=gpu_ctx, **kw, **d.sentinels(3, 300))]
+    for a, b in zip(first, again):
+        assert a.tobytes() == b.tobytes()
+    want = [ref_frame(f) for f in frames]
+    assert_frames(dict(zip(("pose_out", "inlier", "ninliers", "cost", "status"), first)), want, [300, 120, 5], "frontend")
+    gpu_ctx.synchronize()
+    t.cuda.synchronize()
+    side = t.cuda.Stream(t.device("cuda:0"))
+    with t.cuda.stream(side):
+        ctx = Context(device=0, stream=side.cuda_stream)
+        o = d.sentinels(3, 300)
+        side.synchronize()
+        g = t.cuda.CUDAGraph()
+        with t.cuda.graph(g, stream=side):
+            poseRefineBatch(*args, ctx=ctx, **kw, **o)
+        for _ in range(2):
+            for k, x in o.items():
+                x.view(t.uint8).fill_(SENT8 if k == "inlier" else 0x5A)
+            g.replay()
+            side.synchronize()
+            for a, b in zip(first, o.values()):
+                assert a.tobytes() == b.cpu().numpy().tobytes()
+        ctx.close()
+
+
+@pytest.mark.gpu
+def test_pose_refine_grid_passes(gpu_ctx):
+    """The grid is capped at 1024 workgroups: 2053 frames take three passes.  Frame b is variant b mod 13 of 13 frames
+    of 0..12 observations (13 and 1024 are coprime, so a frame taken for the one 1024 further on shows); every frame is
+    checked."""
+    B, stride, prm = 2053, 12, (3, 4, 2, 3, 1e-6)
+    variants = [sub(scene(60 + k, n=12, stereo=0.5, outliers=0.1)[0], k if k < 12 else 12) for k in range(13)]
+    want13 = [ref_frame(f, prm) for f in variants]
+    assert sum(w["status"] & 255 == 0 for w in want13) >= 8
+    frames = [variants[b % 13] for b in range(B)]
+    got = Device(gpu_ctx).run(frames, [len(f["obs"]) for f in frames], stride, prm)
+    assert_frames(got, [want13[b % 13] for b in range(B)], [len(f["obs"]) for f in frames], "grid passes")
+
+
+@pytest.mark.gpu
+def test_pose_refine_offsets_beyond_4_gib(gpu_ctx):
+    """stride 16384 and 21848 frames: the points and observations of the last frame begin beyond 2^32 bytes (each array
+    allocated in one piece, uninitialised: with a count of 0 a frame's observations are never read).  Only the first and
+    the last frame hold observations."""
+    d = Device(gpu_ctx)
+    t = d.torch
+    B, stride = 21848, MAX_STRIDE
+    free, _ = t.cuda.mem_get_info()
+    if free < 3 * (B * stride * 12):
+        pytest.skip("two buffers above 4 GiB and the mask do not fit the free device memory")
+    live = (0, B - 1)
+    assert live[-1] * stride * 12 > 1 << 32
+    xw = t.empty((B, stride, 3), dtype=t.float32, device="cuda")
+    obs = t.empty((B, stride, 3), dtype=t.int32, device="cuda")
+    counts = t.zeros((B,), dtype=t.int32, device="cuda")
+    o = d.sentinels(B, 1)
+    o["inlier"] = t.empty((B, stride), dtype=t.uint8, device="cuda")
+    frames = [scene(71, n=40, stereo=0.5, levels=False)[0], scene(72, n=40, stereo=0.5, levels=False)[0]]
+    pose = d.up(np.tile(IDENTITY, (B, 1)))
+    cam = d.up(np.tile(CAM, (B, 1)))
+    for fr, b in zip(frames, live):
+        xw[b, :40], obs[b, :40], counts[b] = d.up(fr["xw"]), d.up(fr["obs"].astype(np.int32)), 40
+        o["inlier"][b, :48] = SENT8
+    dev = dict(pose=pose, cam=cam, xw=xw, obs=obs, counts=counts, level=None, tab=None)
+    assert d.call(DEFAULT, dev, stride, B, o) == 0
+    gpu_ctx.synchronize()
+    status, ninl = o["status"].cpu().numpy(), o["ninliers"].cpu().numpy()
+    assert (np.delete(status, live) == 1).all() and (np.delete(ninl, live) == 0).all()
+    assert (np.delete(o["pose_out"].cpu().numpy(), live, 0) == IDENTITY).all()
+    for fr, b in zip(frames, live):
+        w = ref_frame(dict(fr, level=None, tab=None))
+        got = {k: v[b:b + 1].cpu().numpy() for k, v in o.items()}
+        got["inlier"] = got["inlier"][:, :48]
+        assert w["status"] & 255 == 0
+        assert_frames(got, [w], [40], "frame %d" % b)
+
+
+@pytest.mark.gpu
+def test_pose_observations_q8_on_the_device(gpu_ctx):
+    observations_case("cuda")
