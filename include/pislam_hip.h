@@ -1115,6 +1115,110 @@ int pislam_two_view_ransac_batch(pislam_ctx *ctx, const pislam_two_view_params *
                                  uint32_t *score, uint32_t *ninliers, uint8_t *inlier, float *model_n, int64_t *stats);
 int pislam_two_view_denormalise(int model, const float *model_n, const int64_t *stats_row, double out[9]);
 
+/* ---- two-view reconstruction: relative pose and map points ---------------- */
+
+/* From a verified two-view model to the first map: what ORB-SLAM's Initializer does in
+ * ReconstructF / ReconstructH with CheckRT, per pair of a batch: every used match is triangulated under every candidate
+ * motion, the good points are counted, one motion is chosen or the pair is refused, and the winner's points are handed
+ * back.  With ONE candidate (a known relative pose) it is the triangulation of local mapping between two key frames.
+ * pislam_two_view_decompose (below) makes the candidates from F or H on the host.  The reference ships nothing of the
+ * kind: the semantics are this library's own, stated so that integers and individually rounded binary32 operations
+ * reproduce every output word.  This comment is the contract.  "float(v)" is the conversion of an integer to binary32;
+ * every +, -, *, / and sqrt below on floats is ONE binary32 operation rounded to nearest even, in the order the
+ * parentheses give; no fused multiply-add, no reciprocal or fast approximation: the division and the square root are
+ * the correctly rounded ones; denormals are kept.
+ *
+ * Inputs, all device unless said.  p1_q8, p2_q8 (int32 [batch][stride][2]) and counts (uint32 [batch]) are the buffers
+ * of pislam_two_view_ransac_batch: n = min(counts[b], stride), PISLAM_COUNT_INVALID counts as 0, every coordinate is
+ * clamped to [-2^20, 2^20] first.
+ *   mask   uint8 [batch][stride] or NULL.  Match i is USED iff i < n and (mask == NULL or mask[b][i] != 0); the RANSAC
+ *          call's `inlier` fits as it is.  N = the number of used matches.
+ *   cam    float [batch][4]: fx, fy, cx, cy in level-0 pixels; both images share the one camera.
+ *   cand   float [batch][ncand][12]: r0 .. r8 row-major, then t0 .. t2, with X2 = R X1 + t (the layout of the pose
+ *          call's pose_in, so pose_out can feed it directly).
+ *
+ * Per pair:   ifx = 1.0f / fx,  ify = 1.0f / fy,  sg = float(sigma_q8) * (1.0f / 256.0f),  th2 = (sg*sg) * 4.0f.
+ * Per used match, with (xq1, yq1) and (xq2, yq2) its clamped coordinates in the two images:
+ *   u1 = float(xq1) * (1.0f / 256.0f), and likewise v1, u2, v2 (exact)
+ *   x1 = (u1 - cx)*ifx,  y1 = (v1 - cy)*ify,  x2 = (u2 - cx)*ifx,  y2 = (v2 - cy)*ify
+ *   bb = (x2*x2 + y2*y2) + 1.0f
+ * Per candidate (the closest points of the two rays, their midpoint, its two reprojections):
+ *   a0 = (r0*x1 + r1*y1) + r2,  a1 = (r3*x1 + r4*y1) + r5,  a2 = (r6*x1 + r7*y1) + r8              a = R (x1, y1, 1)
+ *   n0 = a1 - a2*y2,  n1 = a2*x2 - a0,  n2 = a0*y2 - a1*x2;   nn = (n0*n0 + n1*n1) + n2*n2        a x b, b = (x2, y2, 1)
+ *   p0 = y2*t2 - t1,  p1 = t0 - x2*t2,  p2 = x2*t1 - y2*t0                                         b x t
+ *   q0 = a1*t2 - a2*t1,  q1 = a2*t0 - a0*t2,  q2 = a0*t1 - a1*t0                                   a x t
+ *   z1 = ((p0*n0 + p1*n1) + p2*n2) / nn,   z2 = ((q0*n0 + q1*n1) + q2*n2) / nn
+ *   g0 = z2*x2 - t0,  g1 = z2*y2 - t1,  g2 = z2 - t2;   h_j = (r_(0+j)*g0 + r_(3+j)*g1) + r_(6+j)*g2   (j = 0, 1, 2: R' g)
+ *   X = ((z1*x1 + h0)*0.5f, (z1*y1 + h1)*0.5f, (z1 + h2)*0.5f)                                     the point, frame 1
+ *   Y_k = ((r_(3k)*X0 + r_(3k+1)*X1) + r_(3k+2)*X2) + t_k                                          the point, frame 2
+ *   cs = ((a0*x2 + a1*y2) + a2) / sqrt(((a0*a0 + a1*a1) + a2*a2) * bb)                             cosine of the rays
+ *   i1 = 1.0f / X2;  eu = u1 - (fx*(X0*i1) + cx),  ev = v1 - (fy*(X1*i1) + cy),  e1 = eu*eu + ev*ev
+ *   i2 = 1.0f / Y2;  eu = u2 - (fx*(Y0*i2) + cx),  ev = v2 - (fy*(Y1*i2) + cy),  e2 = eu*eu + ev*ev
+ * (R = I, t = (-1, 0, 0), (x1, y1) = (0, 0), (x2, y2) = (-0.5, 0) gives z1 = z2 = 2 and X = (0, 0, 2).)
+ * The match is GOOD under the candidate iff every component of X and Y is finite, and NOT ((X2 <= 0.0f or Y2 <= 0.0f)
+ * and cs < cos_point) (as in CheckRT, a point at infinity stays whatever the sign of its depth), and e1 <= th2 and
+ * e2 <= th2 (a NaN fails).  A good match HAS PARALLAX iff cs < cos_parallax and is a POINT iff cs < cos_point.  A
+ * candidate with an entry that is not finite has no good match.
+ *
+ * Counts and choice, integers only (no float is summed across matches, so no result depends on an order of
+ * execution).  G_c = the number of used matches that are good under candidate c, P_c = those of them with parallax.
+ * gmax = max G_c, cbest = the smallest c with G_c = gmax, g2 = the largest G_c over c != cbest (0 for ncand = 1).
+ * The code is that of the first row that holds:
+ *   4   N == 0, or cam is not finite, or fx == 0, or fy == 0 (nothing is evaluated: every count is 0)
+ *   1   gmax < min_good, or 100*gmax < min_good_pct*N
+ *   2   100*g2 >= similar_pct*gmax     (at exact equality ORB-SLAM's F path, which asks for more than 0.7 gmax in
+ *                                       floats, accepts; this contract rejects)
+ *   3   P_cbest < min(parallax_rank, gmax)     (ORB-SLAM's "the parallax_rank-th smallest cosine is below the
+ *                                               threshold", as a count: no sort, no acos)
+ *   0   otherwise
+ *
+ * Outputs, per pair, always written, all device: status uint32 [batch] = code | cbest << 8; best int32 [batch] =
+ * cbest for code 0, else -1; ngood, npar uint32 [batch][8] = G_c, P_c (0 for c >= ncand, all 0 for code 4); pose_out
+ * float [batch][12] = the twelve words of cand[b][cbest] for code 0, else twelve zeros; for i < n, point[b][i] = 1 and
+ * xw[b][i] = X under cbest iff the code is 0, match i is used and it is a point under cbest, otherwise 0 and three
+ * zeros (point uint8 [batch][stride], xw float [batch][stride][3]); entries at and beyond n are not written.
+ *
+ * pislam_two_view_decompose (host only, pure, no context; stated to a tolerance, not bit for bit): the candidate motions
+ * of a pixel matrix m_px (pislam_two_view_denormalise's output, row-major) under cam = fx, fy, cx, cy, with a 3 x 3
+ * singular value decomposition in double (one-sided Jacobi, at most 60 sweeps).  Model 0: E = K' F K = U S V'; the SVD
+ * takes the place of the rank-2 projection.  t = the third column of U, R1 = U W V', R2 = U W' V' with W = [0 -1 0;
+ * 1 0 0; 0 0 1], each negated if its determinant is negative; *ncand = 4: (R1, t), (R2, t), (R1, -t), (R2, -t), ORB-
+ * SLAM's order (*ncand = 0 when E has fewer than two singular values above 0).  Model 1: the eight Faugeras-Lustman solutions of A = inverse(K) H K = U diag(d1, d2, d3) V' as ORB-
+ * SLAM's ReconstructH lists them, s = det(U) det(V): with x1 = e1*sqrt((d1^2 - d2^2) / (d1^2 - d3^2)), x3 = e3*sqrt((d2^2
+ * - d3^2) / (d1^2 - d3^2)) over (e1, e3) = (+, +), (+, -), (-, +), (-, -) and the sign e = e1*e3 of the sine: first the
+ * four of d' = +d2, sin = e*sqrt((d1^2 - d2^2)(d2^2 - d3^2)) / ((d1 + d3) d2), cos = (d2^2 + d1 d3) / ((d1 + d3) d2),
+ * R = s U [cos 0 -sin; 0 1 0; sin 0 cos] V', t = U (x1, 0, -x3); then the four of d' = -d2, sin = e*sqrt((d1^2 - d2^2)
+ * (d2^2 - d3^2)) / ((d1 - d3) d2), cos = (d1 d3 - d2^2) / ((d1 - d3) d2), R = s U [cos 0 sin; 0 -1 0; sin 0 -cos] V',
+ * t = U (x1, 0, x3).  Every t is scaled to unit length.  *ncand = 8, or 0 with PISLAM_OK when the decomposition is
+ * degenerate: d1/d2 < 1.00001 or d2/d3 < 1.00001 (a pure rotation, or a plane through a camera centre).  Each R is
+ * checked in double before it is stored as floats: an entry of R'R - I or det R - 1 above 1e-12 also gives *ncand = 0.
+ * PISLAM_ERR_INVALID: a NULL pointer, a model other than 0 / 1, an entry of m_px or cam that is not finite, fx == 0 or
+ * fy == 0.  cand has room for 8 candidates; the rows from *ncand on are zeroed.
+ *
+ * Limits: the parameter ranges in the struct comments; 1 <= stride <= 16384; batch >= 0 with no upper limit (batch ==
+ * 0 is a no-op that returns PISLAM_OK after the checks of p, batch and stride; the pointers are not looked at then).
+ * Offsets use size_t arithmetic throughout.  No output may overlap an input or another output.  Any violation, or a
+ * NULL or host pointer where a device pointer is required (mask alone may be NULL): PISLAM_ERR_INVALID, before
+ * anything is launched or written.  `p` is a host struct, read during the call.  Asynchronous on the context stream;
+ * no workspace, no host round trip: the call can be captured into a hipGraph as it is, so there is no reserve call.
+ * One workgroup works on a pair; a batch above 1024 pairs is walked by the same 1024 workgroups in passes. */
+typedef struct pislam_reconstruct_params {
+  int32_t ncand;          /* 1..8 candidate motions per pair */
+  int32_t sigma_q8;       /* 1..4096, Q8 level-0 pixels (ORB-SLAM: 256) */
+  float cos_parallax;     /* in (0,1]; a match has parallax iff cs < this (cos 1 deg = 0.99984770f) */
+  float cos_point;        /* in (0,1]; a match yields a map point iff cs < this (ORB-SLAM: 0.99998f) */
+  int32_t min_good;       /* 1..16384 (ORB-SLAM: 50) */
+  int32_t min_good_pct;   /* 0..100 of the used matches (ORB-SLAM: 90) */
+  int32_t similar_pct;    /* 1..100: ambiguous iff 100*g2 >= similar_pct*gmax (ORB-SLAM: 70 for F, 75 for H) */
+  int32_t parallax_rank;  /* 1..16384 (ORB-SLAM: 51, i.e. index 50 of the sorted cosines) */
+} pislam_reconstruct_params;
+int pislam_two_view_reconstruct_batch(pislam_ctx *ctx, const pislam_reconstruct_params *p, const int32_t *p1_q8,
+                                      const int32_t *p2_q8, const uint32_t *counts, const uint8_t *mask,
+                                      const float *cam, const float *cand, size_t stride, int batch, int32_t *best,
+                                      uint32_t *status, uint32_t *ngood, uint32_t *npar, float *pose_out, float *xw,
+                                      uint8_t *point);
+int pislam_two_view_decompose(int model, const double m_px[9], const double cam[4], float *cand, int *ncand);
+
 /* ---- motion-only pose optimisation from 3D-2D matches --------------------- */
 
 /* The camera pose of a frame from map points matched to its keypoints: what ORB-SLAM's

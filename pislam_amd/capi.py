@@ -50,6 +50,12 @@ class TwoViewParams(ctypes.Structure):
                 ("sigma_q8", ctypes.c_int32)]
 
 
+class ReconstructParams(ctypes.Structure):
+    _fields_ = [("ncand", ctypes.c_int32), ("sigma_q8", ctypes.c_int32), ("cos_parallax", ctypes.c_float),
+                ("cos_point", ctypes.c_float), ("min_good", ctypes.c_int32), ("min_good_pct", ctypes.c_int32),
+                ("similar_pct", ctypes.c_int32), ("parallax_rank", ctypes.c_int32)]
+
+
 class PoseParams(ctypes.Structure):
     _fields_ = [("rounds", ctypes.c_int32), ("iters", ctypes.c_int32), ("huber_rounds", ctypes.c_int32),
                 ("min_obs", ctypes.c_int32), ("eps", ctypes.c_double)]
@@ -149,6 +155,10 @@ SYMBOLS = {
                                           _vp]),
     "pislam_two_view_denormalise": (_i, [_i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64),
                                          ctypes.POINTER(ctypes.c_double)]),
+    "pislam_two_view_reconstruct_batch": (_i, [_vp, ctypes.POINTER(ReconstructParams), _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                               _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pislam_two_view_decompose": (_i, [_i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                       ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_i)]),
     "pislam_pose_refine_batch": (_i, [_vp, ctypes.POINTER(PoseParams), _vp, _vp, _vp, _vp, _vp, _vp,
                                       ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
     "pislam_bow_weight_batch": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, ctypes.c_uint32, _vp]),

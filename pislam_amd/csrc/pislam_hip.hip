@@ -60,6 +60,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_select_kernels.h"
 #include "pislam_geom_kernels.h"
 #include "pislam_geom_host.h"
+#include "pislam_recon_kernels.h"
 #include "pislam_pose_kernels.h"
 #include "pislam_warp_kernels.h"
 #include "pislam_clahe_kernels.h"
@@ -2473,6 +2474,60 @@ PISLAM_EXPORT int pislam_two_view_ransac_batch(pislam_ctx *c, const pislam_two_v
 
 PISLAM_EXPORT int pislam_two_view_denormalise(int model, const float *model_n, const int64_t *stats_row, double out[9]) {
   return pgh::two_view_denormalise(model, model_n, stats_row, out) ? PISLAM_OK : PISLAM_ERR_INVALID;
+}
+
+// ---- two-view reconstruction: relative pose and map points ----------------------------------
+
+PISLAM_EXPORT int pislam_two_view_reconstruct_batch(pislam_ctx *c, const pislam_reconstruct_params *p,
+                                                    const int32_t *p1_q8, const int32_t *p2_q8, const uint32_t *counts,
+                                                    const uint8_t *mask, const float *cam, const float *cand,
+                                                    size_t stride, int batch, int32_t *best, uint32_t *status,
+                                                    uint32_t *ngood, uint32_t *npar, float *pose_out, float *xw,
+                                                    uint8_t *point) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
+  if (p->ncand < 1 || p->ncand > prm::MAX_CAND) return fail(c, PISLAM_ERR_INVALID, "ncand must be 1..8");
+  if (p->sigma_q8 < 1 || p->sigma_q8 > 4096) return fail(c, PISLAM_ERR_INVALID, "sigma_q8 must be 1..4096");
+  if (!(p->cos_parallax > 0.0f && p->cos_parallax <= 1.0f)) return fail(c, PISLAM_ERR_INVALID, "cos_parallax must be in (0, 1]");
+  if (!(p->cos_point > 0.0f && p->cos_point <= 1.0f)) return fail(c, PISLAM_ERR_INVALID, "cos_point must be in (0, 1]");
+  if (p->min_good < 1 || p->min_good > prm::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "min_good must be 1..16384");
+  if (p->min_good_pct < 0 || p->min_good_pct > 100) return fail(c, PISLAM_ERR_INVALID, "min_good_pct must be 0..100");
+  if (p->similar_pct < 1 || p->similar_pct > 100) return fail(c, PISLAM_ERR_INVALID, "similar_pct must be 1..100");
+  if (p->parallax_rank < 1 || p->parallax_rank > prm::MAX_STRIDE)
+    return fail(c, PISLAM_ERR_INVALID, "parallax_rank must be 1..16384");
+  if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
+  if (stride < 1 || stride > (size_t)prm::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
+  if (batch == 0) return PISLAM_OK;
+  const char *what = "the reconstruction call takes device pointers only";
+  PCHK(device_ptrs(c, {p1_q8, p2_q8, counts, cam, cand, best, status, ngood, npar, pose_out, xw, point}, what));
+  if (mask && !is_device_ptr(mask)) return fail(c, PISLAM_ERR_INVALID, what);
+  {
+    const size_t B = (size_t)batch, pts = B * stride * 2 * sizeof(int32_t), word = B * sizeof(uint32_t);
+    const LkRange in[] = {{p1_q8, pts}, {p2_q8, pts}, {counts, word}, {cam, B * 4 * sizeof(float)},
+                          {cand, B * (size_t)p->ncand * 12 * sizeof(float)}, {mask, B * stride}};
+    const LkRange out[] = {{best, word}, {status, word}, {ngood, 8 * word}, {npar, 8 * word},
+                           {pose_out, B * 12 * sizeof(float)}, {xw, B * stride * 3 * sizeof(float)}, {point, B * stride}};
+    for (int o = 0; o < 7; o++) {
+      for (int i = 0; i < 6; i++)
+        if (lk_overlap(out[o], in[i])) return fail(c, PISLAM_ERR_INVALID, "an output overlaps an input");
+      for (int k = 0; k < o; k++)
+        if (lk_overlap(out[o], out[k])) return fail(c, PISLAM_ERR_INVALID, "two outputs overlap");
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  pr::RcArgs a{};
+  a.p1 = p1_q8, a.p2 = p2_q8, a.counts = counts, a.mask = mask, a.cam = cam, a.cand = cand, a.stride = stride;
+  a.batch = batch;
+  a.p = prm::Params{p->ncand, p->sigma_q8, p->cos_parallax, p->cos_point, p->min_good, p->min_good_pct, p->similar_pct,
+                    p->parallax_rank};
+  a.best = best, a.status = status, a.ngood = ngood, a.npar = npar, a.pose_out = pose_out, a.xw = xw, a.point = point;
+  hipLaunchKernelGGL(pr::k_reconstruct, dim3((unsigned)std::min(batch, pr::RC_GRID_CAP)), dim3(pr::RC_THREADS), 0,
+                     c->stream, a);
+  return launch_ok(c, "k_reconstruct");
+}
+
+PISLAM_EXPORT int pislam_two_view_decompose(int model, const double m_px[9], const double cam[4], float *cand, int *ncand) {
+  return pgh::two_view_decompose(model, m_px, cam, cand, ncand) ? PISLAM_OK : PISLAM_ERR_INVALID;
 }
 
 // ---- motion-only pose optimisation from 3D-2D matches ---------------------------------------

@@ -837,6 +837,122 @@ def twoViewModelRatio(score_h, score_f):
     return np.where(tot > 0, sh / np.where(tot > 0, tot, 1.0), 0.0)[()]
 
 
+def _camera4(K) -> np.ndarray:
+    """fx, fy, cx, cy (float64) from a 3 x 3 camera matrix or from the four numbers themselves."""
+    host = K.detach().cpu().numpy() if hasattr(K, "detach") else np.asarray(K)
+    k = np.asarray(host, dtype=np.float64)
+    if k.shape == (3, 3):
+        return np.array([k[0, 0], k[1, 1], k[0, 2], k[1, 2]])
+    if k.shape == (4,):
+        return k.copy()
+    raise ValueError("K must be a 3 x 3 camera matrix or (fx, fy, cx, cy)")
+
+
+def twoViewCandidates(model, m_px, K) -> np.ndarray:
+    """pislam_two_view_decompose on the host: the candidate motions of the level-0-pixel matrix m_px (float64 [3][3] or
+    a batch [batch][3][3]: twoViewDenormalise's output) under the camera K (3 x 3, or fx, fy, cx, cy), as float32
+    [k][12] (or [batch][k][12]) rows r0 .. r8, t0 .. t2 with X2 = R X1 + t and |t| = 1: k = 4 for model 0 / "F" (the
+    four motions of the essential matrix K' F K), k = 8 for model 1 / "H" (Faugeras-Lustman), in ORB-SLAM's order:
+    twoViewReconstructBatch's cand.  A matrix whose decomposition is degenerate (or that is not finite) gives rows of
+    NaN, which the reconstruction counts as candidates without a good match."""
+    if model not in _TWO_VIEW_MODELS:
+        raise ValueError('model must be 0 / "F" or 1 / "H"')
+    host = m_px.detach().cpu().numpy() if hasattr(m_px, "detach") else np.asarray(m_px)
+    m = np.ascontiguousarray(host, dtype=np.float64)
+    if m.ndim not in (2, 3) or m.shape[-2:] != (3, 3):
+        raise ValueError("m_px must be [3][3] or [batch][3][3]")
+    single = m.ndim == 2
+    m = m.reshape(-1, 9)
+    cam = np.ascontiguousarray(_camera4(K))
+    k = 4 if _TWO_VIEW_MODELS[model] == 0 else 8
+    out = np.full((len(m), k, 12), np.nan, dtype=np.float32)
+    lib = capi.load()
+    dp = ctypes.POINTER(ctypes.c_double)
+    for b in range(len(m)):
+        row, got = (ctypes.c_float * 96)(), ctypes.c_int(0)
+        rc = lib.pislam_two_view_decompose(_TWO_VIEW_MODELS[model], m[b].ctypes.data_as(dp), cam.ctypes.data_as(dp), row,
+                                           ctypes.byref(got))
+        if rc == capi.PISLAM_OK and got.value == k:
+            out[b] = np.frombuffer(row, dtype=np.float32)[:12 * k].reshape(k, 12)
+    return out[0] if single else out
+
+
+RECONSTRUCT_MAX_STRIDE = 16384   # matches per pair (pislam_two_view_reconstruct_batch)
+
+
+def twoViewReconstructBatch(p1_q8, p2_q8, counts, cam, cand, *, mask=None, sigma_q8=256, min_parallax_deg=1.0,
+                            cos_point=0.99998, min_good=50, min_good_pct=90, similar_pct=70, parallax_rank=51,
+                            best=None, status=None, ngood=None, npar=None, pose_out=None, xw=None, point=None,
+                            ctx: Context | None = None):
+    """Batched two-view reconstruction (pislam_two_view_reconstruct_batch; the contract is the comment in
+    include/pislam_hip.h): per pair, every used match of p1_q8 / p2_q8 (int32 [batch][stride][2], level-0 Q8 pixels,
+    stride <= 16384; counts [batch]; mask uint8 [batch][stride] or None: twoViewRansacBatch's inlier fits) is
+    triangulated under every candidate motion cand (float32 [batch][ncand][12], ncand 1..8: twoViewCandidates, or one
+    known relative pose) with the camera cam (float32 [batch][4]: fx, fy, cx, cy); the motion with the most good points
+    wins unless too few are good (min_good, min_good_pct of the used matches), another motion has similar_pct per cent
+    as many, or fewer than min(parallax_rank, the winner's count) of them have min_parallax_deg of parallax
+    (cos_parallax = float32(cos(radians(min_parallax_deg)))).  Returns (best int32 [batch] (-1: refused), status int32
+    [batch] = code | cbest << 8 with code 0 ok, 1 too few, 2 ambiguous, 3 low parallax, 4 no input, ngood and npar
+    int32 [batch][8], pose_out float32 [batch][12] (the winner, ready for poseRefineBatch; zeros when refused), xw
+    float32 [batch][stride][3] and point uint8 [batch][stride]: the winner's map points in frame 1 (entries at and
+    beyond counts[b] are not written)).  The same inputs give the same outputs, bit for bit.  Asynchronous on the ctx
+    stream, no workspace: capturable as it is."""
+    import torch
+    if p1_q8.dtype != torch.int32 or p1_q8.dim() != 3 or int(p1_q8.shape[2]) != 2:
+        raise ValueError("p1_q8 must be an int32 tensor [batch][stride][2]")
+    if p2_q8.dtype != torch.int32 or tuple(p2_q8.shape) != tuple(p1_q8.shape):
+        raise ValueError("p2_q8 must be an int32 tensor of p1_q8's shape")
+    batch, stride = int(p1_q8.shape[0]), int(p1_q8.shape[1])
+    if stride > RECONSTRUCT_MAX_STRIDE:
+        raise ValueError(f"at most {RECONSTRUCT_MAX_STRIDE} matches per pair")
+    if counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(counts.shape) != (batch,):
+        raise ValueError("counts must be a 32-bit integer tensor [batch]")
+    if cam.dtype != torch.float32 or tuple(cam.shape) != (batch, 4):
+        raise ValueError("cam must be a float32 tensor [batch][4]")
+    if cand.dtype != torch.float32 or cand.dim() != 3 or int(cand.shape[0]) != batch or int(cand.shape[2]) != 12:
+        raise ValueError("cand must be a float32 tensor [batch][ncand][12]")
+    ncand = int(cand.shape[1])
+    if not 1 <= ncand <= 8:
+        raise ValueError("cand must hold 1..8 candidates per pair")
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (batch, stride)):
+        raise ValueError("mask must be a uint8 tensor [batch][stride]")
+    for t in (p1_q8, p2_q8, counts, cam, cand) + (() if mask is None else (mask,)):
+        if not t.is_contiguous():
+            raise ValueError("inputs must be contiguous")
+    cos_parallax = np.float32(np.cos(np.radians(min_parallax_deg)))
+    cos_point = np.float32(cos_point)
+    if not 1 <= int(sigma_q8) <= 4096:
+        raise ValueError("sigma_q8 must be 1..4096")
+    if not 0 < cos_parallax <= 1:
+        raise ValueError("min_parallax_deg must give a cosine in (0, 1]")
+    if not 0 < cos_point <= 1:
+        raise ValueError("cos_point must be in (0, 1]")
+    if not 1 <= int(min_good) <= RECONSTRUCT_MAX_STRIDE:
+        raise ValueError("min_good must be 1..16384")
+    if not 0 <= int(min_good_pct) <= 100:
+        raise ValueError("min_good_pct must be 0..100")
+    if not 1 <= int(similar_pct) <= 100:
+        raise ValueError("similar_pct must be 1..100")
+    if not 1 <= int(parallax_rank) <= RECONSTRUCT_MAX_STRIDE:
+        raise ValueError("parallax_rank must be 1..16384")
+    ctx = ctx or default_context()
+    dev = p1_q8.device
+    p = capi.ReconstructParams(ncand, int(sigma_q8), float(cos_parallax), float(cos_point), int(min_good),
+                               int(min_good_pct), int(similar_pct), int(parallax_rank))
+    best = torch.empty((batch,), dtype=torch.int32, device=dev) if best is None else best
+    status = torch.empty((batch,), dtype=torch.int32, device=dev) if status is None else status
+    ngood = torch.empty((batch, 8), dtype=torch.int32, device=dev) if ngood is None else ngood
+    npar = torch.empty((batch, 8), dtype=torch.int32, device=dev) if npar is None else npar
+    pose_out = torch.empty((batch, 12), dtype=torch.float32, device=dev) if pose_out is None else pose_out
+    xw = torch.empty((batch, stride, 3), dtype=torch.float32, device=dev) if xw is None else xw
+    point = torch.empty((batch, stride), dtype=torch.uint8, device=dev) if point is None else point
+    ctx.check(ctx.lib.pislam_two_view_reconstruct_batch(ctx.h, ctypes.byref(p), ptr(p1_q8), ptr(p2_q8), ptr(counts),
+                                                        ptr(mask), ptr(cam), ptr(cand), stride, batch, ptr(best),
+                                                        ptr(status), ptr(ngood), ptr(npar), ptr(pose_out), ptr(xw),
+                                                        ptr(point)), "pislam_two_view_reconstruct_batch")
+    return best, status, ngood, npar, pose_out, xw, point
+
+
 # ---- motion-only pose optimisation from 3D-2D matches ----------
 POSE_MAX_STRIDE = 16384       # observations per frame (pislam_pose_refine_batch)
 POSE_MONO = -(1 << 31)        # u_right of a monocular observation
