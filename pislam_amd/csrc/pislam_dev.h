@@ -7,6 +7,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// In front of a loop that must stay one copy: unrolled or interleaved copies of a loop that carries much state (the
+// loop vectoriser interleaves by two on its own) hold twice the state and spill SGPRs.
+#define PISLAM_ROLLED _Pragma("clang loop unroll(disable) vectorize(disable) interleave(disable)")
+
 namespace pdev {
 
 // ---------------------------------------------------------------------------
@@ -466,6 +470,36 @@ __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+// One DPP move of v inside the rows of 16 lanes (every lane active); a double moves as its two halves.
+template <int CTRL>
+__device__ __forceinline__ int dpp_mov(int v) {
+  return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, true);
+}
+template <int CTRL>
+__device__ __forceinline__ double dpp_mov(double v) {
+  const int lo = dpp_mov<CTRL>(__double2loint(v)), hi = dpp_mov<CTRL>(__double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+// The sum of v over each row of 16 lanes, the same in every lane of the row: xor 1, xor 2 inside the quads, then the
+// mirrored halves of 8 and of 16, whose partners hold equal partial sums by then.  Addition is commutative, so both
+// partners of a step end with the same bits: on doubles this is a fixed tree, halving 16 values in the order lane ^ 1,
+// lane ^ 2, lane ^ 4, lane ^ 8.
+template <class T>
+__device__ __forceinline__ T row16_sum(T v) {
+  v += dpp_mov<0xb1>(v);                       // quad_perm [1, 0, 3, 2]: lane ^ 1
+  v += dpp_mov<0x4e>(v);                       // quad_perm [2, 3, 0, 1]: lane ^ 2
+  v += dpp_mov<0x141>(v);                      // row_half_mirror: the other quad of the 8, whose lanes all hold its sum
+  v += dpp_mov<0x140>(v);                      // row_mirror: the other 8 of the row
+  return v;
+}
+// The sum of v over a full wave (all 64 lanes active), the same in every lane: four DPP steps leave each row of 16
+// lanes with its own sum, four lane reads add the rows.  (The six __shfl_xor steps of wave_sum are six LDS permutes and
+// their address arithmetic: a third of the two-view scoring loop.  wave_sum's own callers keep it.)
+__device__ __forceinline__ uint32_t wave_sum_dpp(uint32_t v) {
+  const int x = row16_sum((int)v);
+  return (uint32_t)(__builtin_amdgcn_readlane(x, 0) + __builtin_amdgcn_readlane(x, 16) + __builtin_amdgcn_readlane(x, 32) +
+                    __builtin_amdgcn_readlane(x, 48));
 }
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 #pragma unroll

@@ -1968,6 +1968,21 @@ bool lk_overlap(LkRange a, LkRange b) {
   const uintptr_t pa = (uintptr_t)a.p, pb = (uintptr_t)b.p;
   return a.p && b.p && a.n && b.n && pa < pb + b.n && pb < pa + a.n;
 }
+// What is wrong with a call's byte ranges, or null: no output may overlap an input or another output (a null or empty
+// range overlaps nothing).  The one alias a call allows, out[0] on in[alias_in] when both begin at the same address
+// (each item is read before it is written), is passed as alias_in.
+template <size_t NI, size_t NO>
+const char *ranges_overlap(const LkRange (&in)[NI], const LkRange (&out)[NO], int alias_in = -1) {
+  for (size_t o = 0; o < NO; o++) {
+    for (size_t i = 0; i < NI; i++) {
+      if (o == 0 && (int)i == alias_in && out[o].p == in[i].p) continue;
+      if (lk_overlap(out[o], in[i])) return "an output overlaps an input";
+    }
+    for (size_t k = 0; k < o; k++)
+      if (lk_overlap(out[o], out[k])) return "two outputs overlap";
+  }
+  return nullptr;
+}
 
 }  // namespace
 
@@ -1990,14 +2005,8 @@ PISLAM_EXPORT int pislam_track_lk_batch(pislam_ctx *c, const pislam_lk_params *p
     const LkRange in[] = {{prev_pyr, pyr}, {next_pyr, pyr}, {pts_q8, 2 * words}, {counts, B * sizeof(uint32_t)},
                           {guess_q8, 2 * words}};
     const LkRange out[] = {{next_q8, 2 * words}, {status, words}, {err, words}, {ntracked, B * sizeof(uint32_t)}};
-    for (int o = 0; o < 4; o++) {
-      for (int i = 0; i < 5; i++) {
-        if (o == 0 && i == 4 && next_q8 == guess_q8) continue;          // each point reads its guess before it writes
-        if (lk_overlap(out[o], in[i])) return fail(c, PISLAM_ERR_INVALID, "an output overlaps an input");
-      }
-      for (int k = 0; k < o; k++)
-        if (lk_overlap(out[o], out[k])) return fail(c, PISLAM_ERR_INVALID, "two outputs overlap");
-    }
+    // next_q8 == guess_q8 is allowed: each point reads its guess before it writes
+    if (const char *bad = ranges_overlap(in, out, 4)) return fail(c, PISLAM_ERR_INVALID, bad);
   }
   HIPCHK(c, hipSetDevice(c->device));
   pt::LkArgs a{};
@@ -2439,10 +2448,10 @@ PISLAM_EXPORT int pislam_two_view_ransac_batch(pislam_ctx *c, const pislam_two_v
   if (!c) return PISLAM_ERR_INVALID;
   if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
   if (p->model != 0 && p->model != 1) return fail(c, PISLAM_ERR_INVALID, "model must be 0 (fundamental) or 1 (homography)");
-  if (p->hypotheses < 1 || p->hypotheses > pg::TV_MAX_HYP) return fail(c, PISLAM_ERR_INVALID, "hypotheses must be 1..1024");
+  if (p->hypotheses < 1 || p->hypotheses > pgm::MAX_HYP) return fail(c, PISLAM_ERR_INVALID, "hypotheses must be 1..1024");
   if (p->sigma_q8 < 1 || p->sigma_q8 > 4096) return fail(c, PISLAM_ERR_INVALID, "sigma_q8 must be 1..4096");
   if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
-  if (stride < 1 || stride > (size_t)pg::TV_MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
+  if (stride < 1 || stride > (size_t)pgm::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
   if (batch == 0) return PISLAM_OK;
   PCHK(device_ptrs(c, {p1_q8, p2_q8, counts, best, score, ninliers, inlier, model_n, stats},
                    "the two-view call takes device pointers only"));
@@ -2451,17 +2460,12 @@ PISLAM_EXPORT int pislam_two_view_ransac_batch(pislam_ctx *c, const pislam_two_v
     const LkRange in[] = {{p1_q8, pts}, {p2_q8, pts}, {counts, word}};
     const LkRange out[] = {{best, word}, {score, word}, {ninliers, word}, {inlier, B * stride},
                            {model_n, B * 9 * sizeof(float)}, {stats, B * 8 * sizeof(int64_t)}};
-    for (int o = 0; o < 6; o++) {
-      for (int i = 0; i < 3; i++)
-        if (lk_overlap(out[o], in[i])) return fail(c, PISLAM_ERR_INVALID, "an output overlaps an input");
-      for (int k = 0; k < o; k++)
-        if (lk_overlap(out[o], out[k])) return fail(c, PISLAM_ERR_INVALID, "two outputs overlap");
-    }
+    if (const char *bad = ranges_overlap(in, out)) return fail(c, PISLAM_ERR_INVALID, bad);
   }
   HIPCHK(c, hipSetDevice(c->device));
   pg::TvArgs a{};
   a.p1 = p1_q8, a.p2 = p2_q8, a.counts = counts, a.stride = stride, a.batch = batch, a.hypotheses = p->hypotheses;
-  a.seed = p->seed, a.sigma = (float)p->sigma_q8 / 256.0f;   // exact: an integer below 2^13 over a power of two
+  a.seed = p->seed, a.sigma = pgm::sigma_px(p->sigma_q8);
   a.best = best, a.score = score, a.ninliers = ninliers, a.inlier = inlier, a.model_n = model_n;
   a.stats = (long long *)stats;
   const dim3 grid((unsigned)std::min(batch, pg::TV_GRID_CAP));
@@ -2507,12 +2511,7 @@ PISLAM_EXPORT int pislam_two_view_reconstruct_batch(pislam_ctx *c, const pislam_
                           {cand, B * (size_t)p->ncand * 12 * sizeof(float)}, {mask, B * stride}};
     const LkRange out[] = {{best, word}, {status, word}, {ngood, 8 * word}, {npar, 8 * word},
                            {pose_out, B * 12 * sizeof(float)}, {xw, B * stride * 3 * sizeof(float)}, {point, B * stride}};
-    for (int o = 0; o < 7; o++) {
-      for (int i = 0; i < 6; i++)
-        if (lk_overlap(out[o], in[i])) return fail(c, PISLAM_ERR_INVALID, "an output overlaps an input");
-      for (int k = 0; k < o; k++)
-        if (lk_overlap(out[o], out[k])) return fail(c, PISLAM_ERR_INVALID, "two outputs overlap");
-    }
+    if (const char *bad = ranges_overlap(in, out)) return fail(c, PISLAM_ERR_INVALID, bad);
   }
   HIPCHK(c, hipSetDevice(c->device));
   pr::RcArgs a{};
@@ -2563,14 +2562,8 @@ PISLAM_EXPORT int pislam_pose_refine_batch(pislam_ctx *c, const pislam_pose_para
                           {obs_q8, B * stride * 3 * sizeof(int32_t)}, {counts, word}, {level, B * stride}};
     const LkRange out[] = {{pose_out, pose}, {inlier, B * stride}, {ninliers, word}, {cost, B * sizeof(double)},
                            {status, word}};
-    for (int o = 0; o < 5; o++) {
-      for (int i = 0; i < 6; i++) {
-        if (o == 0 && i == 0 && pose_out == pose_in) continue;           // a frame reads its pose before it writes it
-        if (lk_overlap(out[o], in[i])) return fail(c, PISLAM_ERR_INVALID, "an output overlaps an input");
-      }
-      for (int k = 0; k < o; k++)
-        if (lk_overlap(out[o], out[k])) return fail(c, PISLAM_ERR_INVALID, "two outputs overlap");
-    }
+    // pose_out == pose_in is allowed: a frame reads its pose before it writes it
+    if (const char *bad = ranges_overlap(in, out, 0)) return fail(c, PISLAM_ERR_INVALID, bad);
   }
   HIPCHK(c, hipSetDevice(c->device));
   po::PoArgs a{};

@@ -14,6 +14,7 @@
 //   * Lane 0 runs the solve, the retraction and the Levenberg rule on state kept in LDS and broadcasts the next pose
 //     as 12 floats: three barriers per pass.
 #pragma once
+#include "pislam_dev.h"
 #include "pislam_pose_math.h"
 
 namespace po {
@@ -21,8 +22,6 @@ namespace po {
 constexpr int PO_THREADS = 256;
 constexpr int PO_RES = 8;                      // register-resident observations per lane
 constexpr int PO_GRID_CAP = 1024;              // workgroups per launch; a larger batch is walked in passes
-
-#define PO_ROLLED _Pragma("clang loop unroll(disable) vectorize(disable) interleave(disable)")
 
 struct PoArgs {
   const float *pose_in, *cam, *xw;
@@ -73,14 +72,6 @@ __device__ __forceinline__ PoObs po_load(const PoArgs &A, const PoFrame &F, uint
   return o;
 }
 
-template <int CTRL>
-__device__ __forceinline__ double po_dpp(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-  hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-
 // One observation of a pass: classification, the mask, the 30 per-lane partial sums.
 __device__ __forceinline__ void po_one(const PoObs &o, uint32_t i, int s, const float *Tf, const float *cam, bool classify,
                                        bool robust, uint64_t &active, uint8_t *inlier, double (&acc)[pq::SUMS]) {
@@ -126,7 +117,7 @@ __device__ __forceinline__ void po_pass(const PoArgs &A, const PoFrame &F, const
       if (i < F.n) po_one(r[s], i, s, Tf, cam, classify, robust, active, F.inlier, acc);
     }
   } else {
-    PO_ROLLED
+    PISLAM_ROLLED
     for (int s = 0; s < pq::MAX_STRIDE / 256; s++) {
       const uint32_t i = q + 256u * (uint32_t)s;
       if (i < F.n) {
@@ -137,14 +128,7 @@ __device__ __forceinline__ void po_pass(const PoArgs &A, const PoFrame &F, const
   }
   // the tree: steps 128, 64, 32, 16 inside the rows of 16 lanes (every lane is active here) ...
 #pragma unroll
-  for (int k = 0; k < pq::SUMS; k++) {
-    double v = acc[k];
-    v += po_dpp<0xb1>(v);                      // quad_perm [1, 0, 3, 2]: lane ^ 1
-    v += po_dpp<0x4e>(v);                      // quad_perm [2, 3, 0, 1]: lane ^ 2
-    v += po_dpp<0x141>(v);                     // row_half_mirror: the other quad of the 8, whose lanes all hold its sum
-    v += po_dpp<0x140>(v);                     // row_mirror: the other 8 of the row
-    acc[k] = v;
-  }
+  for (int k = 0; k < pq::SUMS; k++) acc[k] = pdev::row16_sum(acc[k]);
   if ((tid & 15) == 0) {
 #pragma unroll
     for (int k = 0; k < pq::SUMS; k++) s_part[k][tid >> 4] = acc[k];   // row tid / 16 = wave * 4 + lane / 16 = q % 16
@@ -178,10 +162,10 @@ __device__ __forceinline__ void po_frame(const PoArgs &A, const PoFrame &F, uint
   uint32_t evals = 1, code = 0, ninl = 0;
   double cost = 0.0;
   po_pass<RES>(A, F, r, q, tid, s_Tf, s_part, s_S, false, 0 < hr, active);
-  PO_ROLLED
+  PISLAM_ROLLED
   for (int rd = 0; rd < rounds; rd++) {
     if (tid == 0) s_lm->begin(s_S);
-    PO_ROLLED
+    PISLAM_ROLLED
     for (;;) {
       if (tid == 0) {
         const bool go = s_lm->next(iters);
@@ -214,7 +198,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_refine(const PoArgs A) {
   __shared__ float s_Tf[12 + 5];               // the pose of the pass, then the camera
   __shared__ int s_cmd;
 
-  PO_ROLLED
+  PISLAM_ROLLED
   for (uint32_t b = blockIdx.x; b < (uint32_t)A.batch; b += gridDim.x) {
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));              // keeps the per-thread predicates out of SGPRs held over the loop
@@ -225,8 +209,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_refine(const PoArgs A) {
     const size_t row = (size_t)b * A.stride;
     PoFrame F;
     F.xw = A.xw + 3 * row, F.obs = A.obs + 3 * row, F.level = A.level ? A.level + row : nullptr, F.inlier = A.inlier + row;
-    uint32_t n = A.counts[b];
-    n = n == pq::COUNT_INVALID ? 0u : (n < A.stride ? n : (uint32_t)A.stride);
+    const uint32_t n = psm::clamp_count(A.counts[b], A.stride);
     F.n = n;
     float v = 0.0f;
     if (tid < 12) v = A.pose_in[12 * (size_t)b + tid];
@@ -238,7 +221,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_refine(const PoArgs A) {
     __syncthreads();
     const bool fin = s_cmd != 0;
     if (!fin || n < (uint32_t)A.p.min_obs) {
-      PO_ROLLED
+      PISLAM_ROLLED
       for (uint32_t i = tid; i < n; i += PO_THREADS) F.inlier[i] = 0;
       if (tid < 12) A.pose_out[12 * (size_t)b + tid] = v;
       if (tid == 0) A.ninliers[b] = 0, A.cost[b] = 0.0, A.status[b] = fin ? 1u : 2u;

@@ -4,18 +4,14 @@
 // Levenberg rule in binary64, and, for the host only, the whole procedure run serially with the contract's tree order.
 // Every operation is written out one rounding at a time; build with -ffp-contract=off.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define PQ_HD __host__ __device__ __forceinline__
-#define PQ_UNROLL _Pragma("unroll")
-#else
-#define PQ_HD inline
-#define PQ_UNROLL
-#endif
+#include "pislam_scalar_math.h"
 
 namespace pq {
+
+using psm::fdiv;
+using psm::finite_d;
+using psm::finite_f;
+using psm::fsqrt;
 
 constexpr int TERMS = 28;                      // 21 upper-triangle terms, 6 gradient terms, rho
 constexpr int SUMS = 30;                       // + the number of active observations that are not dead, + their chi2
@@ -27,23 +23,13 @@ constexpr float TH_MONO = 5.991f, TH_STEREO = 7.815f;
 constexpr double LAMBDA_0 = 0x1p-10, LAMBDA_MIN = 0x1p-30, LAMBDA_MAX = 0x1p20;
 constexpr int32_t OBS_MAX = 1 << 22;
 constexpr int32_t MONO = INT32_MIN;
-constexpr uint32_t COUNT_INVALID = 0xffffffffu;
 
-// The correctly rounded binary32 square root and quotient.  (sqrtf and / are correctly rounded on the device with
-// hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt; __fsqrt_rn is the NATIVE square root unless OCML's rounded
-// operations are switched on, so it is not used.)
-PQ_HD float fsqrt(float x) { return __builtin_sqrtf(x); }
-PQ_HD float fdiv(float a, float b) { return a / b; }
-
-PQ_HD bool finite_f(float v) { return fabsf(v) < __builtin_inff(); }   // false for a NaN
-PQ_HD bool finite_d(double v) { return fabs(v) < __builtin_inf(); }
-
-PQ_HD int32_t clamp_obs(int32_t v) { return v < -OBS_MAX ? -OBS_MAX : (v > OBS_MAX ? OBS_MAX : v); }
-PQ_HD float obs_px(int32_t q8) { return (float)clamp_obs(q8) * (1.0f / 256.0f); }   // exact
+PISLAM_HD int32_t clamp_obs(int32_t v) { return v < -OBS_MAX ? -OBS_MAX : (v > OBS_MAX ? OBS_MAX : v); }
+PISLAM_HD float obs_px(int32_t q8) { return (float)clamp_obs(q8) * (1.0f / 256.0f); }   // exact
 
 // One observation at the pose T (r0..r8, t0..t2, already rounded to float) with the weight w.  False: dead (nothing
 // is written).  Otherwise *chi2_out is the plain chi2 and t[0..27] are the 28 terms.
-PQ_HD bool obs_terms(const float *T, const float *cam, float X, float Y, float Z, float u, float v, float ur, bool stereo,
+PISLAM_HD bool obs_terms(const float *T, const float *cam, float X, float Y, float Z, float u, float v, float ur, bool stereo,
                      float w, bool robust, float *t, float *chi2_out) {
   const float fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3], bf = cam[4];
   const float x = ((T[0] * X + T[1] * Y) + T[2] * Z) + T[9];
@@ -77,16 +63,16 @@ PQ_HD bool obs_terms(const float *T, const float *cam, float X, float Y, float Z
   Jv[0] = (1.0f + py * py) * fy, Jv[1] = -(pxy * fy), Jv[2] = -(px * fy), Jv[3] = 0.0f, Jv[4] = -b, Jv[5] = py * b;
   Jr[0] = Ju[0] - c * py, Jr[1] = Ju[1] + c * px, Jr[2] = Ju[2], Jr[3] = Ju[3], Jr[4] = 0.0f, Jr[5] = Ju[5] - c * iz;
   int o = 0;
-PQ_UNROLL
+PISLAM_UNROLL
   for (int j = 0; j < 6; j++) {
-PQ_UNROLL
+PISLAM_UNROLL
     for (int k = j; k < 6; k++) {
       float s = Ju[j] * Ju[k] + Jv[j] * Jv[k];
       if (stereo) s = s + Jr[j] * Jr[k];
       t[o++] = s * wr;
     }
   }
-PQ_UNROLL
+PISLAM_UNROLL
   for (int j = 0; j < 6; j++) {
     float s = Ju[j] * eu + Jv[j] * ev;
     if (stereo) s = s + Jr[j] * er;
@@ -98,13 +84,13 @@ PQ_UNROLL
 
 // A d = -g with A = H, A_jj = H_jj * (1 + lambda); S = the 28 sums.  Gaussian elimination without pivoting, back
 // substitution.  False: a pivot that is not > 0 (a NaN fails) or a d that is not finite.
-PQ_HD bool solve(const double *S, double lambda, double *d) {
+PISLAM_HD bool solve(const double *S, double lambda, double *d) {
   double A[6][6], b[6];
   {
     int o = 0;
-PQ_UNROLL
+PISLAM_UNROLL
     for (int j = 0; j < 6; j++) {
-PQ_UNROLL
+PISLAM_UNROLL
       for (int k = j; k < 6; k++) {
         A[j][k] = S[o], A[k][j] = S[o];
         o++;
@@ -112,24 +98,24 @@ PQ_UNROLL
     }
   }
   const double s = 1.0 + lambda;
-PQ_UNROLL
+PISLAM_UNROLL
   for (int j = 0; j < 6; j++) A[j][j] = A[j][j] * s, b[j] = -S[21 + j];
   bool ok = true;
-PQ_UNROLL
+PISLAM_UNROLL
   for (int c = 0; c < 6; c++) {
     ok = ok && A[c][c] > 0.0;
-PQ_UNROLL
+PISLAM_UNROLL
     for (int r = c + 1; r < 6; r++) {
       const double f = A[r][c] / A[c][c];
-PQ_UNROLL
+PISLAM_UNROLL
       for (int j = c + 1; j < 6; j++) A[r][j] = A[r][j] - f * A[c][j];
       b[r] = b[r] - f * b[c];
     }
   }
-PQ_UNROLL
+PISLAM_UNROLL
   for (int r = 5; r >= 0; r--) {
     double t = b[r];
-PQ_UNROLL
+PISLAM_UNROLL
     for (int j = r + 1; j < 6; j++) t = t - A[r][j] * d[j];
     d[r] = t / A[r][r];
     ok = ok && finite_d(d[r]);
@@ -138,7 +124,7 @@ PQ_UNROLL
 }
 
 // The Cayley retraction of T by d = (omega, upsilon): R' = Q R, t' = Q t + upsilon.
-PQ_HD void retract(const double *T, const double *d, double *Tn) {
+PISLAM_HD void retract(const double *T, const double *d, double *Tn) {
   const double a0 = d[0] * 0.5, a1 = d[1] * 0.5, a2 = d[2] * 0.5;
   const double n = (a0 * a0 + a1 * a1) + a2 * a2;
   const double m = 1.0 - n, den = 1.0 + n;
@@ -146,9 +132,9 @@ PQ_HD void retract(const double *T, const double *d, double *Tn) {
   Q[0] = (m + 2.0 * (a0 * a0)) / den, Q[1] = (2.0 * (a0 * a1) - 2.0 * a2) / den, Q[2] = (2.0 * (a0 * a2) + 2.0 * a1) / den;
   Q[3] = (2.0 * (a1 * a0) + 2.0 * a2) / den, Q[4] = (m + 2.0 * (a1 * a1)) / den, Q[5] = (2.0 * (a1 * a2) - 2.0 * a0) / den;
   Q[6] = (2.0 * (a2 * a0) - 2.0 * a1) / den, Q[7] = (2.0 * (a2 * a1) + 2.0 * a0) / den, Q[8] = (m + 2.0 * (a2 * a2)) / den;
-PQ_UNROLL
+PISLAM_UNROLL
   for (int i = 0; i < 3; i++) {
-PQ_UNROLL
+PISLAM_UNROLL
     for (int j = 0; j < 3; j++) Tn[3 * i + j] = (Q[3 * i] * T[j] + Q[3 * i + 1] * T[3 + j]) + Q[3 * i + 2] * T[6 + j];
     Tn[9 + i] = ((Q[3 * i] * T[9] + Q[3 * i + 1] * T[10]) + Q[3 * i + 2] * T[11]) + d[3 + i];
   }
@@ -162,12 +148,12 @@ struct Lm {
   int it;
   bool over;
 
-  PQ_HD void begin(const double *sums) {
-PQ_UNROLL
+  PISLAM_HD void begin(const double *sums) {
+PISLAM_UNROLL
     for (int i = 0; i < TERMS; i++) S[i] = sums[i];
     lambda = LAMBDA_0, it = 0, over = false;
   }
-  PQ_HD bool next(int iters) {
+  PISLAM_HD bool next(int iters) {
     while (!over && it < iters) {
       it++;
       double d[6];
@@ -177,17 +163,17 @@ PQ_UNROLL
       }
       retract(T, d, Tt);
       dmax = 0.0;
-PQ_UNROLL
+PISLAM_UNROLL
       for (int j = 0; j < 6; j++) dmax = fmax(dmax, fabs(d[j]));
       return true;
     }
     return false;
   }
-  PQ_HD void trial(const double *sums, double eps) {
+  PISLAM_HD void trial(const double *sums, double eps) {
     if (sums[27] < S[27]) {
-PQ_UNROLL
+PISLAM_UNROLL
       for (int i = 0; i < 12; i++) T[i] = Tt[i];
-PQ_UNROLL
+PISLAM_UNROLL
       for (int i = 0; i < TERMS; i++) S[i] = sums[i];
       lambda = fmax(lambda * 0.25, LAMBDA_MIN);
     } else {
@@ -211,7 +197,7 @@ struct Frame {
   const uint8_t *level;                        // [n] or null
   const float *inv_sigma2;                     // [nlevels] or null with level == null
   int nlevels;
-  uint32_t n;                                  // already min(count, stride), COUNT_INVALID as 0
+  uint32_t n;                                  // already psm::clamp_count(count, stride)
 };
 struct Result {
   float pose[12];

@@ -12,6 +12,7 @@
 //   * The counters are summed over the wave by DPP and over the four waves through LDS; lane 0 makes the choice.
 //   * Pass 2 recomputes the winner only and writes xw / point (zeros where the pair has no winner).
 #pragma once
+#include "pislam_dev.h"
 #include "pislam_recon_math.h"
 
 namespace pr {
@@ -20,8 +21,6 @@ constexpr int RC_THREADS = 256;
 constexpr int RC_WAVES = RC_THREADS / 64;
 constexpr int RC_GRID_CAP = 1024;              // workgroups per launch; a larger batch is walked in passes
 constexpr int RC_COUNTERS = 2 * prm::MAX_CAND + 1;
-
-#define RC_ROLLED _Pragma("clang loop unroll(disable) vectorize(disable) interleave(disable)")
 
 struct RcArgs {
   const int32_t *p1, *p2;
@@ -37,17 +36,6 @@ struct RcArgs {
   uint8_t *point;
 };
 
-// The sum of v over a full wave (all 64 lanes active), the same in every lane (pg::tv_wave_sum's steps).
-__device__ __forceinline__ uint32_t rc_wave_sum(uint32_t v) {
-  int x = (int)v;
-  x += __builtin_amdgcn_mov_dpp(x, 0xb1, 0xf, 0xf, true);    // quad_perm [1, 0, 3, 2]
-  x += __builtin_amdgcn_mov_dpp(x, 0x4e, 0xf, 0xf, true);    // quad_perm [2, 3, 0, 1]
-  x += __builtin_amdgcn_mov_dpp(x, 0x141, 0xf, 0xf, true);   // row_half_mirror
-  x += __builtin_amdgcn_mov_dpp(x, 0x140, 0xf, 0xf, true);   // row_mirror
-  return (uint32_t)(__builtin_amdgcn_readlane(x, 0) + __builtin_amdgcn_readlane(x, 16) + __builtin_amdgcn_readlane(x, 32) +
-                    __builtin_amdgcn_readlane(x, 48));
-}
-
 __device__ __forceinline__ prm::Match rc_match(const prm::Pair &P, const int32_t *p1, const int32_t *p2, uint32_t i) {
   const int2 u = *(const int2 *)(p1 + 2 * (size_t)i), v = *(const int2 *)(p2 + 2 * (size_t)i);
   return prm::match_setup(P, u.x, u.y, v.x, v.y);
@@ -58,7 +46,7 @@ __global__ __launch_bounds__(RC_THREADS) void k_reconstruct(const RcArgs A) {
   __shared__ uint32_t s_fin[prm::MAX_CAND];
   __shared__ uint32_t s_code, s_cbest;
 
-  RC_ROLLED
+  PISLAM_ROLLED
   for (uint32_t b = blockIdx.x; b < (uint32_t)A.batch; b += gridDim.x) {   // b + 1024 fits 32 bits unsigned
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));              // keeps the per-thread predicates out of SGPRs held over the loop
@@ -68,8 +56,7 @@ __global__ __launch_bounds__(RC_THREADS) void k_reconstruct(const RcArgs A) {
     const int32_t *p1 = A.p1 + 2 * row, *p2 = A.p2 + 2 * row;
     const uint8_t *mask = A.mask ? A.mask + row : nullptr;
     const float *cand = A.cand + 12 * ((size_t)b * (size_t)ncand);
-    uint32_t n = A.counts[b];
-    n = n == prm::COUNT_INVALID ? 0u : (n < A.stride ? n : (uint32_t)A.stride);
+    const uint32_t n = psm::clamp_count(A.counts[b], A.stride);
     prm::Pair P;
     const bool cam_ok = prm::pair_setup(A.cam + 4 * (size_t)b, A.p.sigma_q8, &P);
     if (tid < prm::MAX_CAND) s_fin[tid] = tid < ncand && prm::cand_finite(cand + 12 * tid) ? 1u : 0u;
@@ -82,13 +69,13 @@ __global__ __launch_bounds__(RC_THREADS) void k_reconstruct(const RcArgs A) {
     // ---- pass 1: the counts ----
     unsigned long long good = 0, par = 0;      // a byte per candidate, at most 64 each
     uint32_t used = 0;
-    RC_ROLLED
+    PISLAM_ROLLED
     for (uint32_t i = tid; i < n; i += RC_THREADS) {
       if (mask && !mask[i]) continue;
       used++;
       if (!cam_ok) continue;
       const prm::Match m = rc_match(P, p1, p2, i);
-      RC_ROLLED
+      PISLAM_ROLLED
       for (int c = 0; c < ncand; c++) {
         if (!(fin >> c & 1u)) continue;
         const float *cd = cand + 12 * c;
@@ -102,12 +89,12 @@ __global__ __launch_bounds__(RC_THREADS) void k_reconstruct(const RcArgs A) {
     }
 #pragma unroll
     for (int c = 0; c < prm::MAX_CAND; c++) {
-      const uint32_t g = rc_wave_sum((uint32_t)(good >> (8 * c)) & 0xffu);
-      const uint32_t q = rc_wave_sum((uint32_t)(par >> (8 * c)) & 0xffu);
+      const uint32_t g = pdev::wave_sum_dpp((uint32_t)(good >> (8 * c)) & 0xffu);
+      const uint32_t q = pdev::wave_sum_dpp((uint32_t)(par >> (8 * c)) & 0xffu);
       if (lane == 0) s_cnt[wave][c] = g, s_cnt[wave][prm::MAX_CAND + c] = q;
     }
     {
-      const uint32_t u = rc_wave_sum(used);
+      const uint32_t u = pdev::wave_sum_dpp(used);
       if (lane == 0) s_cnt[wave][2 * prm::MAX_CAND] = u;
     }
     __syncthreads();
@@ -145,7 +132,7 @@ __global__ __launch_bounds__(RC_THREADS) void k_reconstruct(const RcArgs A) {
       for (int k = 0; k < 12; k++) C[k] = ok ? win[k] : 0.0f;
       float *xw = A.xw + 3 * row;
       uint8_t *point = A.point + row;
-      RC_ROLLED
+      PISLAM_ROLLED
       for (uint32_t i = tid; i < n; i += RC_THREADS) {
         float X[3] = {0.0f, 0.0f, 0.0f};
         bool is_point = false;

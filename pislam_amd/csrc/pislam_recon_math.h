@@ -4,21 +4,17 @@
 // the choice in integers, and, for the host only, the whole call for one pair run serially.  Every operation is written
 // out one rounding at a time; build with -ffp-contract=off.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define PRM_HD __host__ __device__ __forceinline__
-#else
-#define PRM_HD inline
-#endif
+#include "pislam_scalar_math.h"
 
 namespace prm {
 
+using psm::clamp_q8;
+using psm::fdiv;
+using psm::finite_f;
+using psm::fsqrt;
+
 constexpr int MAX_CAND = 8;
 constexpr int MAX_STRIDE = 16384;
-constexpr int32_t COORD_MAX = 1 << 20;
-constexpr uint32_t COUNT_INVALID = 0xffffffffu;
 constexpr uint32_t GOOD = 1, PARALLAX = 2, POINT = 4;        // the flags of a match under a candidate
 
 enum Code { OK = 0, FEW = 1, AMBIGUOUS = 2, LOW_PARALLAX = 3, NO_INPUT = 4 };
@@ -29,26 +25,20 @@ struct Params {
   int32_t min_good, min_good_pct, similar_pct, parallax_rank;
 };
 
-PRM_HD bool params_ok(const Params &p) {
+PISLAM_HD bool params_ok(const Params &p) {
   return p.ncand >= 1 && p.ncand <= MAX_CAND && p.sigma_q8 >= 1 && p.sigma_q8 <= 4096 && p.cos_parallax > 0.0f &&
          p.cos_parallax <= 1.0f && p.cos_point > 0.0f && p.cos_point <= 1.0f && p.min_good >= 1 &&
          p.min_good <= MAX_STRIDE && p.min_good_pct >= 0 && p.min_good_pct <= 100 && p.similar_pct >= 1 &&
          p.similar_pct <= 100 && p.parallax_rank >= 1 && p.parallax_rank <= MAX_STRIDE;
 }
 
-// The correctly rounded binary32 square root and quotient, as in pislam_pose_math.h.
-PRM_HD float fsqrt(float x) { return __builtin_sqrtf(x); }
-PRM_HD float fdiv(float a, float b) { return a / b; }
-PRM_HD bool finite_f(float v) { return fabsf(v) < __builtin_inff(); }   // false for a NaN
-
-PRM_HD int32_t clamp_q8(int32_t v) { return v < -COORD_MAX ? -COORD_MAX : (v > COORD_MAX ? COORD_MAX : v); }
-PRM_HD float px(int32_t q8) { return (float)clamp_q8(q8) * (1.0f / 256.0f); }   // exact
+PISLAM_HD float px(int32_t q8) { return (float)clamp_q8(q8) * (1.0f / 256.0f); }   // exact
 
 // What a pair's matches share.  False: cam is not finite, or fx == 0 or fy == 0 (code 4).
 struct Pair {
   float fx, fy, cx, cy, ifx, ify, th2;
 };
-PRM_HD bool pair_setup(const float *cam, int32_t sigma_q8, Pair *P) {
+PISLAM_HD bool pair_setup(const float *cam, int32_t sigma_q8, Pair *P) {
   P->fx = cam[0], P->fy = cam[1], P->cx = cam[2], P->cy = cam[3];
   P->ifx = fdiv(1.0f, P->fx), P->ify = fdiv(1.0f, P->fy);
   const float sg = (float)sigma_q8 * (1.0f / 256.0f);
@@ -59,7 +49,7 @@ PRM_HD bool pair_setup(const float *cam, int32_t sigma_q8, Pair *P) {
 struct Match {
   float u1, v1, u2, v2, x1, y1, x2, y2, bb;
 };
-PRM_HD Match match_setup(const Pair &P, int32_t xq1, int32_t yq1, int32_t xq2, int32_t yq2) {
+PISLAM_HD Match match_setup(const Pair &P, int32_t xq1, int32_t yq1, int32_t xq2, int32_t yq2) {
   Match m;
   m.u1 = px(xq1), m.v1 = px(yq1), m.u2 = px(xq2), m.v2 = px(yq2);
   m.x1 = (m.u1 - P.cx) * P.ifx, m.y1 = (m.v1 - P.cy) * P.ify;
@@ -68,7 +58,7 @@ PRM_HD Match match_setup(const Pair &P, int32_t xq1, int32_t yq1, int32_t xq2, i
   return m;
 }
 
-PRM_HD bool cand_finite(const float *c) {
+PISLAM_HD bool cand_finite(const float *c) {
   bool ok = true;
   for (int i = 0; i < 12; i++) ok = ok && finite_f(c[i]);
   return ok;
@@ -76,7 +66,7 @@ PRM_HD bool cand_finite(const float *c) {
 
 // One match under the candidate c (r0 .. r8, t0 .. t2, every entry finite): its flags, and in X the midpoint of the two
 // rays' closest points in frame 1.
-PRM_HD uint32_t evaluate(const float *c, const Pair &P, const Match &m, float cos_parallax, float cos_point, float *X) {
+PISLAM_HD uint32_t evaluate(const float *c, const Pair &P, const Match &m, float cos_parallax, float cos_point, float *X) {
   const float x1 = m.x1, y1 = m.y1, x2 = m.x2, y2 = m.y2;
   const float t0 = c[9], t1 = c[10], t2 = c[11];
   const float a0 = (c[0] * x1 + c[1] * y1) + c[2];
@@ -113,7 +103,7 @@ PRM_HD uint32_t evaluate(const float *c, const Pair &P, const Match &m, float co
 
 // The choice of a pair from its integer counts: G[c] good matches and Pc[c] of them with parallax under candidate c,
 // N used matches.  Returns the code; *cbest is the smallest c of the largest G.
-PRM_HD uint32_t choose(const uint32_t *G, const uint32_t *Pc, const Params &p, uint32_t N, bool cam_ok, int *cbest) {
+PISLAM_HD uint32_t choose(const uint32_t *G, const uint32_t *Pc, const Params &p, uint32_t N, bool cam_ok, int *cbest) {
   uint32_t gmax = 0, g2 = 0;
   int cb = 0;
   for (int c = 0; c < p.ncand; c++)
@@ -136,7 +126,7 @@ struct PairIn {
   const int32_t *p1, *p2;                      // [n][2]
   const uint8_t *mask;                         // [n] or null
   const float *cam, *cand;                     // [4], [ncand][12]
-  uint32_t n;                                  // already min(count, stride), COUNT_INVALID as 0
+  uint32_t n;                                  // already psm::clamp_count(count, stride)
 };
 struct PairOut {
   int32_t best;

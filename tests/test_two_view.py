@@ -11,6 +11,8 @@ import ctypes
 import functools
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -548,6 +550,37 @@ def pin_batch(model, small):
 def pin_reference(model, hypotheses, small):
     p1, p2, counts = pin_batch(model, small)
     return ref_batch(p1, p2, counts, model, hypotheses, 12345, 256)
+
+
+def test_host_probe_against_the_restatement(tmp_path):
+    """The library's own arithmetic header, compiled for the host with -ffp-contract=off, run serially: every output
+    word of every pair of the twelve pin cases."""
+    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    exe = str(tmp_path / "ransac_host_check")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-I", os.path.join(ROOT, "pislam_amd", "csrc"),
+                           os.path.join(ROOT, "tools", "probes", "ransac_host_check.cpp"), "-o", exe])
+    lines, want = [], []
+    for model in (FUND, HOMOG):
+        for hypotheses in (1, 63, 64, 65, 200, 1024):
+            small = hypotheses not in (64, 200)                                       # as in test_two_view_pins
+            p1, p2, counts = pin_batch(model, small)
+            r = pin_reference(model, hypotheses, small)
+            for b in range(len(counts)):
+                n = 0 if int(counts[b]) == COUNT_INVALID else min(int(counts[b]), PIN_STRIDE)
+                pts = np.concatenate([p1[b, :n], p2[b, :n]], 1).astype(np.int32)      # the call reads 32-bit words
+                lines.append(" ".join(str(v) for v in [model, hypotheses, 12345, 256, b, n] + pts.ravel().tolist()))
+                want.append(" ".join([str(int(r["best"][b])), str(int(r["score"][b])), str(int(r["ninliers"][b])),
+                                      "".join(str(int(v)) for v in r["inlier"][b, :n]) or "-"] +
+                                     ["%08x" % int(v) for v in r["model_n"][b].view(np.uint32)] +
+                                     [str(int(v)) for v in r["stats"][b]]))
+    cases = tmp_path / "cases.txt"
+    cases.write_text("\n".join(lines) + "\n")
+    got = subprocess.run([exe, str(cases)], check=True, capture_output=True, text=True).stdout.splitlines()
+    assert len(got) == len(want) == 2 * (4 * 3 + 2 * 14)
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert g == w, "case %d: %s" % (k, lines[k][:60])
 
 
 @pytest.mark.gpu

@@ -10,18 +10,9 @@
 //   then per observation: X Y Z  u_q8 v_q8 ur_q8  level
 // (n is what the call makes of counts[b] and stride: already clamped.)  One line of output per frame:
 //   status ninliers cost(64 bit) pose_out[12] inlier[n] as a string of 0 / 1 ("-" for n == 0)
-#include <inttypes.h>
-#include <stdio.h>
-#include <string.h>
 #include <vector>
+#include "hex_words.h"
 #include "pislam_pose_math.h"
-
-static bool rd_f32(FILE *f, float *v) {
-  uint32_t u;
-  if (fscanf(f, "%" SCNx32, &u) != 1) return false;
-  memcpy(v, &u, 4);
-  return true;
-}
 
 int main(int argc, char **argv) {
   FILE *f = argc > 1 ? fopen(argv[1], "r") : stdin;
@@ -65,11 +56,7 @@ int main(int argc, char **argv) {
     uint64_t cost_bits;
     memcpy(&cost_bits, &R.cost, 8);
     printf("%" PRIu32 " %" PRIu32 " %016" PRIx64, R.status, R.ninliers, cost_bits);
-    for (int i = 0; i < 12; i++) {
-      uint32_t u;
-      memcpy(&u, &R.pose[i], 4);
-      printf(" %08" PRIx32, u);
-    }
+    for (int i = 0; i < 12; i++) pr_f32(R.pose[i]);
     printf(" ");
     if (n == 0) printf("-");
     for (long long i = 0; i < n; i++) putchar(inlier[(size_t)i] ? '1' : '0');

@@ -10,24 +10,9 @@
 //   cand[ncand][12]  then per match: x1_q8 y1_q8 x2_q8 y2_q8 mask
 // (n is what the call makes of counts[b] and stride: already clamped.)  One line of output per pair:
 //   best status ngood[8] npar[8] pose_out[12] point[n] as a string of 0 / 1 ("-" for n == 0) xw[n][3]
-#include <inttypes.h>
-#include <stdio.h>
-#include <string.h>
 #include <vector>
+#include "hex_words.h"
 #include "pislam_recon_math.h"
-
-static bool rd_f32(FILE *f, float *v) {
-  uint32_t u;
-  if (fscanf(f, "%" SCNx32, &u) != 1) return false;
-  memcpy(v, &u, 4);
-  return true;
-}
-
-static void pr_f32(float v) {
-  uint32_t u;
-  memcpy(&u, &v, 4);
-  printf(" %08" PRIx32, u);
-}
 
 int main(int argc, char **argv) {
   FILE *f = argc > 1 ? fopen(argv[1], "r") : stdin;
