@@ -1327,6 +1327,121 @@ int pislam_pose_refine_batch(pislam_ctx *ctx, const pislam_pose_params *p, const
                              const float *inv_sigma2, int nlevels, size_t stride, int batch, float *pose_out,
                              uint8_t *inlier, uint32_t *ninliers, double *cost, uint32_t *status);
 
+/* ---- absolute pose from 3D-2D matches: P3P RANSAC ------------------------- */
+
+/* A pose from nothing: what ORB-SLAM's relocalisation and loop closing do with their PnP
+ * solver, per frame of a batch: minimal samples of three 3D-2D matches are solved for the camera pose (P3P in the
+ * Lambda Twist formulation, Persson & Nordberg, ECCV 2018: nothing beyond + - * / and the square root), a fourth match
+ * chooses among the solutions, every hypothesis is scored against every observation with the pose call's monocular
+ * chi2, and the best one is handed back with its inlier mask.  The inputs are the pose call's buffers and pose_out is
+ * its pose_in, so pislam_pose_refine_batch is the refit.  The reference ships nothing of the kind: the semantics are
+ * this library's own, stated so that integers and individually rounded binary32 operations reproduce every output
+ * word.  This comment is the contract.  Every +, -, *, / and sqrt below is ONE binary32 operation rounded to nearest
+ * even, in the order the parentheses give (a + b + c means (a + b) + c, -a - b means (-a) - b); no fused multiply-add,
+ * no reciprocal or fast approximation: the division and the square root are the correctly rounded ones; denormals are
+ * kept.  A comparison with a NaN is false.
+ *
+ * Inputs: cam, xw, obs_q8, counts, level, inv_sigma2, nlevels exactly as in pislam_pose_refine_batch (same layouts,
+ * same rules for level / inv_sigma2 / nlevels).  cam = (fx, fy, cx, cy, bf); bf is read for the finiteness test only.
+ * (u, v) = (float(clamp(q, -2^22, 2^22)) * (1.0f/256.0f)) of the first two words of an observation; the third word is
+ * ignored: every observation is monocular here.  n = min(counts[b], stride), PISLAM_COUNT_INVALID counts as 0.
+ * w = 1.0f without a level table, else inv_sigma2[level]; an observation whose level is >= nlevels is DEAD under every
+ * pose (as a sample of draws 0 .. 2 it is still used: only its point and pixel are read there).
+ * ifx = 1.0f / fx, ify = 1.0f / fy.
+ *
+ * One observation under one pose T = (r0 .. r8 row-major, t0 .. t2), the pose call's monocular arithmetic:
+ *   x = ((r0*X + r1*Y) + r2*Z) + t0,  y = ((r3*X + r4*Y) + r5*Z) + t1,  z = ((r6*X + r7*Y) + r8*Z) + t2
+ *   dead unless z >= 2^-10;  iz = 1.0f / z,  pu = fx*(x*iz) + cx,  pv = fy*(y*iz) + cy,  eu = u - pu,  ev = v - pv
+ *   chi2 = (eu*eu + ev*ev) * w;  dead unless chi2 is finite.
+ * A live observation with chi2 < 5.991f is an INLIER and adds (uint32)floor((5.991f - chi2) * 256.0f) to the
+ * hypothesis's integer score (at most 1533 * 16384).
+ *
+ * Sampling: the sampler of pislam_two_view_ransac_batch with m = 4, the same hash(seed; b, k, j) and draw order.  Draws
+ * 0, 1, 2 are the minimal problem (points x1, x2, x3 with pixels (u_i, v_i)), draw 3 chooses among its solutions.
+ * n < 4: no model.
+ *
+ * The solver.  dot(a, b) = (a0*b0 + a1*b1) + a2*b2;  cross(a, b) = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0).
+ *  1. Bearings: xn = (u - cx) * ifx,  yn = (v - cy) * ify,  r = 1.0f / sqrt((xn*xn + yn*yn) + 1.0f),
+ *     y_i = (xn*r, yn*r, r).
+ *  2. b12 = -2.0f * dot(y1, y2),  b13 = -2.0f * dot(y1, y3),  b23 = -2.0f * dot(y2, y3);
+ *     d12 = x1 - x2,  d13 = x1 - x3,  d23 = x2 - x3 (by component);  a_ij = dot(d_ij, d_ij);
+ *     c12 = -0.5f * b12,  c23 = -0.5f * b23,  c31 = -0.5f * b13;  s12 = 1.0f - c12*c12,  s23, s31 alike;
+ *     blob = (c12*c23)*c31 - 1.0f.
+ *  3. p3 = a13 * (a23*s31 - a13*s23)
+ *     p2 = (((2.0f*blob)*a23)*a13 + (a13*(2.0f*a12 + a13))*s23) + (a23*(a23 - a12))*s31
+ *     p1 = ((a23*(a13 - a23))*s12 - (a12*a12)*s23) - (2.0f*a12)*(blob*a23 + a13*s23)
+ *     p0 = a12 * (a12*s23 - a23*s12)
+ *     p3 == 0: the hypothesis is invalid.  ip = 1.0f / p3;  B = p2*ip,  C = p1*ip,  D = p0*ip.
+ *  4. One real root g of r^3 + B r^2 + C r + D.  h(t) = ((t + B)*t + C)*t + D,  h'(t) = (3.0f*t + 2.0f*B)*t + C.
+ *     If B*B >= 3.0f*C:  v = sqrt(B*B - 3.0f*C),  t1 = (-B - v) / 3.0f,  k = h(t1);
+ *       if k > 0: r = t1 - sqrt(-k / (3.0f*t1 + B));
+ *       else t2 = (-B + v) / 3.0f,  k = h(t2),  r = t2 + sqrt(-k / (3.0f*t2 + B)).
+ *     Otherwise r = -B / 3.0f, and if |h'(r)| < 1e-4f then r = r + 1.0f.
+ *     Then 12 Newton steps, all of them taken: f = h(r), f' = h'(r), if f' != 0: r = r - f / f'.  g = r.
+ *  5. A00 = a23*(1.0f - g),  A01 = (a23*b12)*0.5f,  A02 = ((a23*b13)*g)*(-0.5f),  A11 = (a23 - a12) + a13*g,
+ *     A12 = (b23*(a13*g - a12))*0.5f,  A22 = g*(a13 - a23) - a12.  One eigenvalue of this symmetric matrix is 0; the
+ *     other two are the roots of e^2 + eb e + ec:  x01 = A01*A01,  eb = (-A00 - A11) - A22,
+ *     ec = (((-x01 - A02*A02) - A12*A12) + A00*(A11 + A22)) + A11*A22,  disc = eb*eb - 4.0f*ec, 0 unless disc > 0,
+ *     L0 = ((eb < 0 ? -eb + sqrt(disc) : -eb - sqrt(disc))) * 0.5f (the larger magnitude),  L1 = ec / L0.
+ *     Eigenvector of e (for L0: V0 = (V00, V10, V20); for L1: V1 = (V01, V11, V21)), with
+ *     prec0 = A01*A12 - A02*A11,  prec1 = A01*A02 - A00*A12:
+ *       tmp = 1.0f / (((e*(A00 + A11) - A00*A11) - e*e) + x01),  a1 = -((e*A02 + prec0)*tmp),
+ *       a2 = -((e*A12 + prec1)*tmp),  rn = 1.0f / sqrt((a1*a1 + a2*a2) + 1.0f),  vector = (a1*rn, a2*rn, rn).
+ *  6. q = -L1 / L0,  v = sqrt(q) if q > 0, else 0.  For s = +v, then s = -v:
+ *       w2 = 1.0f / (s*V01 - V00),  w0 = (V10 - s*V11)*w2,  w1 = (V20 - s*V21)*w2
+ *       qa = 1.0f / ((((a13 - a12)*w1)*w1 - (a12*b13)*w1) - a12)
+ *       qb = (((a13*b12)*w1 - (a12*b13)*w0) - ((2.0f*w0)*w1)*(a12 - a13)) * qa
+ *       qc = ((((a13 - a12)*w0)*w0 + (a13*b12)*w0) + a13) * qa
+ *       disc = qb*qb - 4.0f*qc; nothing unless disc >= 0;  tau = (-qb + sqrt(disc))*0.5f, then (-qb - sqrt(disc))*0.5f.
+ *     That is up to four candidates, numbered in this order.  A candidate exists when tau > 0,
+ *     d = a23 / (tau*(b23 + tau) + 1.0f) > 0, and with l2 = sqrt(d), l3 = tau*l2, l1 = w0*l2 + w1*l3: l1 >= 0.
+ *  7. 5 Gauss-Newton steps on (l1, l2, l3), all of them taken:
+ *       r1 = ((l1*l1 + l2*l2) + (b12*l1)*l2) - a12,  r2 = ((l1*l1 + l3*l3) + (b13*l1)*l3) - a13,
+ *       r3 = ((l2*l2 + l3*l3) + (b23*l2)*l3) - a23
+ *       v0 = 2.0f*l1 + b12*l2,  v1 = 2.0f*l2 + b12*l1,  v3 = 2.0f*l1 + b13*l3,  v5 = 2.0f*l3 + b13*l1,
+ *       v7 = 2.0f*l2 + b23*l3,  v8 = 2.0f*l3 + b23*l2,  idet = 1.0f / (-((v0*v5)*v7) - (v1*v3)*v8)
+ *       n1 = ((v1*v5)*r3 - (v5*v7)*r1) - (v1*v8)*r2,  n2 = ((v0*v8)*r2 - (v3*v8)*r1) - (v0*v5)*r3,
+ *       n3 = ((v3*v7)*r1 - (v0*v7)*r2) - (v1*v3)*r3;   l_i = l_i - n_i*idet  (all three from the old values).
+ *  8. The inverse Xi of X = [d12, d13, nx = cross(d12, d13)] (columns; m_rc = entry of row r, column c) by cofactors:
+ *       i00 = m11*m22 - m12*m21,  i01 = m02*m21 - m01*m22,  i02 = m01*m12 - m02*m11,
+ *       i10 = m12*m20 - m10*m22,  i11 = m00*m22 - m02*m20,  i12 = m02*m10 - m00*m12,
+ *       i20 = m10*m21 - m11*m20,  i21 = m01*m20 - m00*m21,  i22 = m00*m11 - m01*m10,
+ *       idet = 1.0f / ((m00*i00 + m01*i10) + m02*i20),  Xi_rc = i_rc * idet.
+ *     ry1 = l1*y1,  e1 = ry1 - l2*y2,  e2 = ry1 - l3*y3 (by component),  e3 = cross(e1, e2);
+ *     R_ij = (e1_i*Xi_0j + e2_i*Xi_1j) + e3_i*Xi_2j,   t_i = ry1_i - ((R_i0*x1_0 + R_i1*x1_1) + R_i2*x1_2).
+ *  9. A candidate with a pose entry that is not finite, or under whose pose draw 3 is dead, is dropped.  Of the others
+ *     the one with the smallest chi2 of draw 3 is the hypothesis's pose (strict <: the lower number wins a tie).  The
+ *     hypothesis is invalid when there is none.  (Collinear x1, x2, x3 end here: nx = 0 makes Xi not finite.)
+ *
+ * The best: the valid hypothesis of largest score wins, ties go to the smallest k; a largest score of 0 is "no model".
+ * No float is ever summed across observations or hypotheses, so no result depends on an order of execution.
+ *
+ * Outputs, per frame, always written, all device.  best (int32) = the winning k, or -1.  score, ninliers (uint32; 0
+ * without a model).  inlier uint8 [batch][stride]: 0 or 1 for i < n under the winning pose (all 0 without a model);
+ * entries at and beyond n are not written.  pose_out float [batch][12] = the winner's (R row-major, t): the layout of
+ * the pose call's pose_in; twelve zeros without a model.  status uint32 = code | valid_hypotheses << 8 (the number of
+ * valid hypotheses among those evaluated; 0 when nothing is evaluated).  code 0: ok;  1: a model, but ninliers <
+ * min_inliers (pose and mask are written all the same);  2: no model (n < 4, every hypothesis invalid, or no score
+ * above 0);  3: cam not finite, fx == 0 or fy == 0: nothing is evaluated.
+ *
+ * Limits: the parameter ranges in the struct comments; 1 <= stride <= 16384; batch >= 0 with no upper limit (batch ==
+ * 0 is a no-op that returns PISLAM_OK after the checks of p, the table, batch and stride; the pointers are not looked
+ * at then).  Offsets use size_t arithmetic throughout.  No output may overlap an input or another output.  Any
+ * violation, or a NULL or host pointer where a device pointer is required: PISLAM_ERR_INVALID, before anything is
+ * launched or written.  `p` is a host struct, read during the call.  Asynchronous on the context stream; no workspace
+ * (the poses of a frame's hypotheses live in LDS), no host round trip: the call can be captured into a hipGraph as it
+ * is, so there is no reserve call.  One workgroup works on a frame; a batch above 1024 frames is walked by the same
+ * 1024 workgroups in passes. */
+typedef struct pislam_pnp_params {
+  int32_t hypotheses;   /* 1..1024, all of them are evaluated */
+  uint32_t seed;        /* any */
+  int32_t min_inliers;  /* 4..16384 (ORB-SLAM: 10) */
+} pislam_pnp_params;
+int pislam_pnp_ransac_batch(pislam_ctx *ctx, const pislam_pnp_params *p, const float *cam, const float *xw,
+                            const int32_t *obs_q8, const uint32_t *counts, const uint8_t *level,
+                            const float *inv_sigma2, int nlevels, size_t stride, int batch, int32_t *best,
+                            uint32_t *score, uint32_t *ninliers, uint8_t *inlier, float *pose_out, uint32_t *status);
+
 /* ---- multi-GPU: one process per GPU, pyramids sharded, ONE collective ---- */
 
 /* The reference is a single-threaded per-frame loop without cross-frame state

@@ -62,6 +62,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_geom_host.h"
 #include "pislam_recon_kernels.h"
 #include "pislam_pose_kernels.h"
+#include "pislam_pnp_kernels.h"
 #include "pislam_warp_kernels.h"
 #include "pislam_clahe_kernels.h"
 
@@ -2575,6 +2576,50 @@ PISLAM_EXPORT int pislam_pose_refine_batch(pislam_ctx *c, const pislam_pose_para
   hipLaunchKernelGGL(po::k_pose_refine, dim3((unsigned)std::min(batch, po::PO_GRID_CAP)), dim3(po::PO_THREADS), 0,
                      c->stream, a);
   return launch_ok(c, "k_pose_refine");
+}
+
+// ---- absolute pose from 3D-2D matches: batched P3P RANSAC -----------------------------------
+
+PISLAM_EXPORT int pislam_pnp_ransac_batch(pislam_ctx *c, const pislam_pnp_params *p, const float *cam, const float *xw,
+                                          const int32_t *obs_q8, const uint32_t *counts, const uint8_t *level,
+                                          const float *inv_sigma2, int nlevels, size_t stride, int batch, int32_t *best,
+                                          uint32_t *score, uint32_t *ninliers, uint8_t *inlier, float *pose_out,
+                                          uint32_t *status) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
+  if (p->hypotheses < 1 || p->hypotheses > pnm::MAX_HYP) return fail(c, PISLAM_ERR_INVALID, "hypotheses must be 1..1024");
+  if (p->min_inliers < pnm::SAMPLE || p->min_inliers > pnm::MAX_STRIDE)
+    return fail(c, PISLAM_ERR_INVALID, "min_inliers must be 4..16384");
+  if (level) {
+    if (!inv_sigma2 || nlevels < 1 || nlevels > pnm::MAX_LEVELS)
+      return fail(c, PISLAM_ERR_INVALID, "level needs inv_sigma2 with 1..16 entries");
+    for (int l = 0; l < nlevels; l++)
+      if (!(inv_sigma2[l] > 0.0f) || !psm::finite_f(inv_sigma2[l]))
+        return fail(c, PISLAM_ERR_INVALID, "inv_sigma2 must be finite and > 0");
+  }
+  if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
+  if (stride < 1 || stride > (size_t)pnm::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
+  if (batch == 0) return PISLAM_OK;
+  const char *what = "the absolute-pose call takes device pointers only";
+  PCHK(device_ptrs(c, {cam, xw, obs_q8, counts, best, score, ninliers, inlier, pose_out, status}, what));
+  if (level && !is_device_ptr(level)) return fail(c, PISLAM_ERR_INVALID, what);
+  {
+    const size_t B = (size_t)batch, word = B * sizeof(uint32_t);
+    const LkRange in[] = {{cam, B * 5 * sizeof(float)}, {xw, B * stride * 3 * sizeof(float)},
+                          {obs_q8, B * stride * 3 * sizeof(int32_t)}, {counts, word}, {level, B * stride}};
+    const LkRange out[] = {{best, word}, {score, word}, {ninliers, word}, {inlier, B * stride},
+                           {pose_out, B * 12 * sizeof(float)}, {status, word}};
+    if (const char *bad = ranges_overlap(in, out)) return fail(c, PISLAM_ERR_INVALID, bad);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  pn::PnArgs a{};
+  a.cam = cam, a.xw = xw, a.obs = obs_q8, a.level = level, a.counts = counts, a.stride = stride, a.batch = batch;
+  a.hypotheses = p->hypotheses, a.nlevels = level ? nlevels : 0, a.min_inliers = p->min_inliers, a.seed = p->seed;
+  for (int l = 0; l < a.nlevels; l++) a.inv_sigma2[l] = inv_sigma2[l];
+  a.best = best, a.score = score, a.ninliers = ninliers, a.inlier = inlier, a.pose_out = pose_out, a.status = status;
+  hipLaunchKernelGGL(pn::k_pnp_ransac, dim3((unsigned)std::min(batch, pn::PN_GRID_CAP)), dim3(pn::PN_THREADS), 0,
+                     c->stream, a);
+  return launch_ok(c, "k_pnp_ransac");
 }
 
 // ---- bag of words: integer weights and the key-frame database -----------------------------

@@ -1074,6 +1074,61 @@ def poseRefineBatch(pose, cam, xw, obs_q8, counts, *, level=None, inv_sigma2=Non
     return pose_out, inlier, ninliers, cost, status
 
 
+# ---- absolute pose from 3D-2D matches: P3P RANSAC ----------
+def pnpRansacBatch(cam, xw, obs_q8, counts, *, level=None, inv_sigma2=None, hypotheses=200, seed=0, min_inliers=10,
+                   best=None, score=None, ninliers=None, inlier=None, pose_out=None, status=None,
+                   ctx: Context | None = None):
+    """Batched absolute-pose RANSAC (pislam_pnp_ransac_batch; the contract is the comment in include/pislam_hip.h): per
+    frame, a camera pose from nothing, by P3P on `hypotheses` minimal samples of the 3D-2D matches xw (float32
+    [batch][stride][3], stride <= 16384) and obs_q8 (int32 [batch][stride][3], poseRefineBatch's; the third word is
+    ignored), with cam (float32 [batch][5]) and counts [batch]; level / inv_sigma2 as in poseRefineBatch.  Inputs are
+    torch tensors or numpy arrays (numpy goes to the current device).  Returns (best int32 [batch] = the winning
+    hypothesis or -1, score int32 [batch], ninliers int32 [batch], inlier uint8 [batch][stride] (entries at and beyond
+    counts[b] are not written), pose_out float32 [batch][12] = poseRefineBatch's `pose`, status int32 [batch] = code |
+    valid hypotheses << 8; code 0 ok, 1 fewer than min_inliers inliers, 2 no model, 3 bad camera).  The same inputs
+    and seed give the same outputs, bit for bit.  Asynchronous on the ctx stream, no workspace: capturable."""
+    import torch
+    ctx = ctx or default_context()
+    as_t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda") if isinstance(a, np.ndarray) else a
+    cam, xw, obs_q8, counts, level = as_t(cam), as_t(xw), as_t(obs_q8), as_t(counts), as_t(level)
+    if cam.dtype != torch.float32 or cam.dim() != 2 or int(cam.shape[1]) != 5:
+        raise ValueError("cam must be a float32 tensor [batch][5]")
+    batch = int(cam.shape[0])
+    if xw.dtype != torch.float32 or xw.dim() != 3 or int(xw.shape[0]) != batch or int(xw.shape[2]) != 3:
+        raise ValueError("xw must be a float32 tensor [batch][stride][3]")
+    stride = int(xw.shape[1])
+    if obs_q8.dtype != torch.int32 or tuple(obs_q8.shape) != (batch, stride, 3):
+        raise ValueError("obs_q8 must be an int32 tensor [batch][stride][3]")
+    if stride > POSE_MAX_STRIDE:
+        raise ValueError(f"at most {POSE_MAX_STRIDE} observations per frame")
+    if counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(counts.shape) != (batch,):
+        raise ValueError("counts must be a 32-bit integer tensor [batch]")
+    if (level is None) != (inv_sigma2 is None):
+        raise ValueError("level and inv_sigma2 go together")
+    tab, ntab = None, 0
+    if level is not None:
+        if level.dtype != torch.uint8 or tuple(level.shape) != (batch, stride):
+            raise ValueError("level must be a uint8 tensor [batch][stride]")
+        host = np.ascontiguousarray(np.asarray(inv_sigma2, dtype=np.float32).reshape(-1))
+        ntab = int(host.size)
+        if not 1 <= ntab <= 16:
+            raise ValueError("inv_sigma2 must have 1..16 entries")
+        tab = (ctypes.c_float * ntab)(*host.tolist())
+    for t in (cam, xw, obs_q8, counts) + (() if level is None else (level,)):
+        if not t.is_contiguous():
+            raise ValueError("inputs must be contiguous")
+    dev = cam.device
+    p = capi.PnpParams(int(hypotheses), int(seed) & 0xFFFFFFFF, int(min_inliers))
+    word = lambda t: torch.empty((batch,), dtype=torch.int32, device=dev) if t is None else t
+    best, score, ninliers, status = word(best), word(score), word(ninliers), word(status)
+    inlier = torch.empty((batch, stride), dtype=torch.uint8, device=dev) if inlier is None else inlier
+    pose_out = torch.empty((batch, 12), dtype=torch.float32, device=dev) if pose_out is None else pose_out
+    ctx.check(ctx.lib.pislam_pnp_ransac_batch(ctx.h, ctypes.byref(p), ptr(cam), ptr(xw), ptr(obs_q8), ptr(counts),
+                                              ptr(level), tab, ntab, stride, batch, ptr(best), ptr(score), ptr(ninliers),
+                                              ptr(inlier), ptr(pose_out), ptr(status)), "pislam_pnp_ransac_batch")
+    return best, score, ninliers, inlier, pose_out, status
+
+
 # ---- bag of words: integer weights and the key-frame database ----------
 BOW_MAX_STRIDE = 16384      # entries of a bag-of-words vector (pislam_bow_vector_batch)
 
