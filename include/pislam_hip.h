@@ -1442,6 +1442,109 @@ int pislam_pnp_ransac_batch(pislam_ctx *ctx, const pislam_pnp_params *p, const f
                             const float *inv_sigma2, int nlevels, size_t stride, int batch, int32_t *best,
                             uint32_t *score, uint32_t *ninliers, uint8_t *inlier, float *pose_out, uint32_t *status);
 
+/* ---- similarity from 3D-3D matches: Sim(3) RANSAC (Horn) ------------------ */
+
+/* The loop-closing step: what ORB-SLAM's LoopClosing::ComputeSim3 asks of its Sim3Solver, per
+ * (key frame, loop candidate) pair of a batch.  A monocular map drifts in scale, so the two key frames are related by a
+ * similarity X1 = s R X2 + t, not by a rigid pose.  Minimal samples of three matched map points, each given in both
+ * camera frames, are solved in closed form (Horn 1987, "Closed-form solution of absolute orientation using unit
+ * quaternions"), every hypothesis is scored against every match by reprojection into BOTH images with the pose call's
+ * monocular chi2, and the best one is handed back with its inlier mask.  The reference ships nothing of the kind: the
+ * semantics are this library's own, stated so that integers and individually rounded binary32 operations reproduce
+ * every output word.  This comment is the contract.  Every +, -, *, / and sqrt below is ONE binary32 operation rounded
+ * to nearest even, in the order the parentheses give (a + b + c means (a + b) + c); no fused multiply-add, no
+ * reciprocal or fast approximation: the division and the square root are the correctly rounded ones; denormals are
+ * kept.  A comparison with a NaN is false.  Nothing but those five operations is used: no atan2, sin or cos (ORB-SLAM's
+ * detour through the angle-axis form of the quaternion is not taken).
+ *
+ * Inputs, device unless said.  n = min(counts[b], stride), PISLAM_COUNT_INVALID counts as 0.  cam1, cam2 float
+ * [batch][5] = (fx, fy, cx, cy, bf) as in pislam_pose_refine_batch; bf is read for the finiteness test only.  x1, x2
+ * float [batch][stride][3]: match i's map point in camera 1's frame and in camera 2's frame.  obs1_q8, obs2_q8 int32
+ * [batch][stride][3], the pose call's observation layout: (u, v) = (float(clamp(q, -2^22, 2^22)) * (1.0f/256.0f)) of
+ * the first two words, the third word is ignored.  (ORB-SLAM compares with the points' own projections: a caller who
+ * wants exactly that passes those.)  level1, level2 uint8 [batch][stride], both given or both NULL; with them
+ * inv_sigma2 (HOST, nlevels entries) follows the pose call's rules, w1 = inv_sigma2[level1], w2 = inv_sigma2[level2],
+ * and a match with a level >= nlevels on either side is DEAD under every hypothesis (as a sample it is still used:
+ * only its points are read there); without them w1 = w2 = 1.0f.
+ *
+ * Sampling: the sampler of pislam_two_view_ransac_batch with m = 3, the same hash(seed; b, k, j) and draw order.
+ * n < 3: no model.
+ *
+ * The solver, on the draws j = 0, 1, 2 with points P1_j (of x1) and P2_j (of x2).
+ * dot(a, b) = (a0*b0 + a1*b1) + a2*b2.
+ *  1. Centroids, by component: O1 = ((P1_0 + P1_1) + P1_2) / 3.0f, O2 alike;  p1_j = P1_j - O1,  p2_j = P2_j - O2.
+ *  2. M_ab = (p2_0[a]*p1_0[b] + p2_1[a]*p1_1[b]) + p2_2[a]*p1_2[b]   (a, b = 0 .. 2: the sum of p2 p1').
+ *  3. The symmetric 4 x 4 matrix N:
+ *       N00 = (M00 + M11) + M22,  N11 = (M00 - M11) - M22,  N22 = (M11 - M00) - M22,  N33 = (M22 - M00) - M11,
+ *       N01 = M12 - M21,  N02 = M20 - M02,  N03 = M01 - M10,  N12 = M01 + M10,  N13 = M20 + M02,  N23 = M12 + M21,
+ *     each stored at both places.  V = the 4 x 4 identity.
+ *  4. Cyclic Jacobi: 4 sweeps, all of them taken (no convergence test); a sweep visits the pivots (p, q) = (0,1), (0,2),
+ *     (0,3), (1,2), (1,3), (2,3) in this order.  A pivot with N_pq == 0 is skipped.  Otherwise
+ *       th = (N_qq - N_pp) / (2.0f * N_pq),  tt = (th >= 0 ? 1.0f : -1.0f) / (|th| + sqrt(th*th + 1.0f)),
+ *       c = 1.0f / sqrt(tt*tt + 1.0f),  sn = tt * c;
+ *     then for k = 0 .. 3 (columns):  (N_kp, N_kq) = (c*N_kp - sn*N_kq,  sn*N_kp + c*N_kq)   (both from the old pair);
+ *     then for k = 0 .. 3 (rows):     (N_pk, N_qk) = (c*N_pk - sn*N_qk,  sn*N_pk + c*N_qk);
+ *     then for k = 0 .. 3 (vectors):  (V_kp, V_kq) = (c*V_kp - sn*V_kq,  sn*V_kp + c*V_kq).
+ *     (All 16 entries of N are carried; the two triangles may differ in the last bit.  th*th overflows to infinity for
+ *     a tiny pivot: tt = 0, the identity rotation, which is harmless and not branched round.)
+ *  5. The quaternion is the column j of V with the largest N_jj after the last sweep (strict >: the lowest j wins a
+ *     tie):  rn = 1.0f / sqrt(((V_0j*V_0j + V_1j*V_1j) + V_2j*V_2j) + V_3j*V_3j),  (w, x, y, z) = (V_0j*rn, .. V_3j*rn).
+ *  6. R, entry by entry from the products ww = w*w, xx, yy, zz, xy, xz, yz, wx, wy, wz:
+ *       R00 = ((ww + xx) - yy) - zz,  R01 = 2.0f*(xy - wz),         R02 = 2.0f*(xz + wy),
+ *       R10 = 2.0f*(xy + wz),         R11 = ((ww - xx) + yy) - zz,  R12 = 2.0f*(yz - wx),
+ *       R20 = 2.0f*(xz - wy),         R21 = 2.0f*(yz + wx),         R22 = ((ww - xx) - yy) + zz.
+ *  7. Scale.  fixed_scale: s = 1.0f.  Otherwise (ORB-SLAM's asymmetric form) with g_j = R p2_j, that is
+ *     g_j[i] = (Ri0*p2_j[0] + Ri1*p2_j[1]) + Ri2*p2_j[2]:
+ *       s = ((dot(p1_0, g_0) + dot(p1_1, g_1)) + dot(p1_2, g_2)) / ((dot(p2_0, p2_0) + dot(p2_1, p2_1)) + dot(p2_2, p2_2)).
+ *  8. t_i = O1_i - s * ((Ri0*O2_0 + Ri1*O2_1) + Ri2*O2_2);   is = 1.0f / s.
+ *  9. The hypothesis is invalid when any of the 13 words R, t, s is not finite, or when s > 0 does not hold.
+ *
+ * Scoring, ORB-SLAM's CheckInliers: every match under every valid hypothesis, in the stored form (R, t, s, is).
+ *   forward:   a_i = s * ((Ri0*X2_0 + Ri1*X2_1) + Ri2*X2_2) + t_i,       projected with cam1 against (u1, v1), w1;
+ *   backward:  d = X1 - t,  b_i = ((R0i*d_0 + R1i*d_1) + R2i*d_2) * is,  projected with cam2 against (u2, v2), w2.
+ * A side with the camera point (x, y, z), the pose call's monocular arithmetic:
+ *   dead unless z >= 2^-10;  iz = 1.0f / z,  pu = fx*(x*iz) + cx,  pv = fy*(y*iz) + cy,  eu = u - pu,  ev = v - pv,
+ *   chi2 = (eu*eu + ev*ev) * w;  dead unless chi2 is finite.
+ * A match is an INLIER when both sides are live and chi2_1 < 9.210f and chi2_2 < 9.210f; it then adds
+ * (uint32)floor((9.210f - chi2_1) * 256.0f) + (uint32)floor((9.210f - chi2_2) * 256.0f) to the hypothesis's integer
+ * score (at most 2 * 2358 * 16384 < 2^27).
+ *
+ * The best: the valid hypothesis of largest score wins, ties go to the smallest k; a largest score of 0 is "no model".
+ * No float is ever summed across matches or hypotheses, so no result depends on an order of execution or on the
+ * launch shape.
+ *
+ * Outputs, per pair, always written, all device.  best (int32) = the winning k, or -1.  score, ninliers (uint32; 0
+ * without a model).  inlier uint8 [batch][stride]: 0 or 1 for i < n under the winner (all 0 without a model); entries
+ * at and beyond n are not written.  sim_out float [batch][13] = the winner's (R row-major, t, s); the first twelve
+ * words are the layout of the pose call's pose_in, so a fixed-scale result feeds pislam_pose_refine_batch directly;
+ * thirteen zeros without a model.  status uint32 = code | valid_hypotheses << 8 (the number of valid hypotheses among
+ * those evaluated; 0 when nothing is evaluated).  code 0: ok;  1: a model, but ninliers < min_inliers (similarity and
+ * mask are written all the same);  2: no model (n < 3, every hypothesis invalid, or no score above 0);  3: cam1 or cam2
+ * not finite, or an fx or fy == 0: nothing is evaluated.
+ *
+ * Limits: the parameter ranges in the struct comments; 1 <= stride <= 16384; batch >= 0 with no upper limit (batch ==
+ * 0 is a no-op that returns PISLAM_OK after the checks of p, the levels, the table, batch and stride; the other
+ * pointers are not looked at then).  Offsets use size_t arithmetic throughout.  No output may overlap an input or
+ * another output.  Any violation, one level pointer without the other, or a NULL or host pointer where a device
+ * pointer is required: PISLAM_ERR_INVALID, before anything is launched or written.  `p` is a host struct, read during
+ * the call.  Asynchronous on the context stream; no workspace (a pair's hypotheses live in LDS), no host round trip:
+ * the call can be captured into a hipGraph as it is, so there is no reserve call.  One workgroup works on a pair; a
+ * batch above 1024 pairs is walked by the same 1024 workgroups in passes.
+ *
+ * Not here: ORB-SLAM's 7-degree-of-freedom refinement of the result (OptimizeSim3), and SearchBySim3, which
+ * pislam_match_hamming_scaled_window_batch with predicted centres covers, given this call's output. */
+typedef struct pislam_sim3_params {
+  int32_t hypotheses;   /* 1..1024, all of them are evaluated (ORB-SLAM: up to 300) */
+  uint32_t seed;        /* any */
+  int32_t min_inliers;  /* 3..16384 (ORB-SLAM: 20) */
+  int32_t fixed_scale;  /* 0 / 1: 1 forces s = 1.0f (stereo / RGB-D maps) */
+} pislam_sim3_params;
+int pislam_sim3_ransac_batch(pislam_ctx *ctx, const pislam_sim3_params *p, const float *cam1, const float *cam2,
+                             const float *x1, const float *x2, const int32_t *obs1_q8, const int32_t *obs2_q8,
+                             const uint32_t *counts, const uint8_t *level1, const uint8_t *level2,
+                             const float *inv_sigma2, int nlevels, size_t stride, int batch, int32_t *best,
+                             uint32_t *score, uint32_t *ninliers, uint8_t *inlier, float *sim_out, uint32_t *status);
+
 /* ---- multi-GPU: one process per GPU, pyramids sharded, ONE collective ---- */
 
 /* The reference is a single-threaded per-frame loop without cross-frame state

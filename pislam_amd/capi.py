@@ -65,6 +65,11 @@ class PnpParams(ctypes.Structure):
     _fields_ = [("hypotheses", ctypes.c_int32), ("seed", ctypes.c_uint32), ("min_inliers", ctypes.c_int32)]
 
 
+class Sim3Params(ctypes.Structure):
+    _fields_ = [("hypotheses", ctypes.c_int32), ("seed", ctypes.c_uint32), ("min_inliers", ctypes.c_int32),
+                ("fixed_scale", ctypes.c_int32)]
+
+
 class ClaheParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "tiles_x", "tiles_y", "clip_q8")]
 
@@ -167,6 +172,8 @@ SYMBOLS = {
                                       ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
     "pislam_pnp_ransac_batch": (_i, [_vp, ctypes.POINTER(PnpParams), _vp, _vp, _vp, _vp, _vp,
                                      ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pislam_sim3_ransac_batch": (_i, [_vp, ctypes.POINTER(Sim3Params), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pislam_bow_weight_batch": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, ctypes.c_uint32, _vp]),
     "pislam_bowdb_create": (_i, [_vp, ctypes.c_uint32, _sz, _i, ctypes.POINTER(_vp)]),
     "pislam_bowdb_destroy": (_i, [_vp]),

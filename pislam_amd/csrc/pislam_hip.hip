@@ -63,6 +63,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_recon_kernels.h"
 #include "pislam_pose_kernels.h"
 #include "pislam_pnp_kernels.h"
+#include "pislam_sim3_kernels.h"
 #include "pislam_warp_kernels.h"
 #include "pislam_clahe_kernels.h"
 
@@ -2620,6 +2621,56 @@ PISLAM_EXPORT int pislam_pnp_ransac_batch(pislam_ctx *c, const pislam_pnp_params
   hipLaunchKernelGGL(pn::k_pnp_ransac, dim3((unsigned)std::min(batch, pn::PN_GRID_CAP)), dim3(pn::PN_THREADS), 0,
                      c->stream, a);
   return launch_ok(c, "k_pnp_ransac");
+}
+
+// ---- similarity from 3D-3D matches: batched Sim(3) RANSAC -----------------------------------
+
+PISLAM_EXPORT int pislam_sim3_ransac_batch(pislam_ctx *c, const pislam_sim3_params *p, const float *cam1,
+                                           const float *cam2, const float *x1, const float *x2, const int32_t *obs1_q8,
+                                           const int32_t *obs2_q8, const uint32_t *counts, const uint8_t *level1,
+                                           const uint8_t *level2, const float *inv_sigma2, int nlevels, size_t stride,
+                                           int batch, int32_t *best, uint32_t *score, uint32_t *ninliers,
+                                           uint8_t *inlier, float *sim_out, uint32_t *status) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
+  if (p->hypotheses < 1 || p->hypotheses > s3m::MAX_HYP) return fail(c, PISLAM_ERR_INVALID, "hypotheses must be 1..1024");
+  if (p->min_inliers < s3m::SAMPLE || p->min_inliers > s3m::MAX_STRIDE)
+    return fail(c, PISLAM_ERR_INVALID, "min_inliers must be 3..16384");
+  if (p->fixed_scale != 0 && p->fixed_scale != 1) return fail(c, PISLAM_ERR_INVALID, "fixed_scale must be 0 or 1");
+  if ((level1 != nullptr) != (level2 != nullptr)) return fail(c, PISLAM_ERR_INVALID, "level1 and level2 go together");
+  if (level1) {
+    if (!inv_sigma2 || nlevels < 1 || nlevels > s3m::MAX_LEVELS)
+      return fail(c, PISLAM_ERR_INVALID, "levels need inv_sigma2 with 1..16 entries");
+    for (int l = 0; l < nlevels; l++)
+      if (!(inv_sigma2[l] > 0.0f) || !psm::finite_f(inv_sigma2[l]))
+        return fail(c, PISLAM_ERR_INVALID, "inv_sigma2 must be finite and > 0");
+  }
+  if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
+  if (stride < 1 || stride > (size_t)s3m::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
+  if (batch == 0) return PISLAM_OK;
+  const char *what = "the similarity call takes device pointers only";
+  PCHK(device_ptrs(c, {cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts, best, score, ninliers, inlier, sim_out, status},
+                   what));
+  if (level1 && (!is_device_ptr(level1) || !is_device_ptr(level2))) return fail(c, PISLAM_ERR_INVALID, what);
+  {
+    const size_t B = (size_t)batch, word = B * sizeof(uint32_t), cam = B * 5 * sizeof(float);
+    const size_t pts = B * stride * 3 * sizeof(float), obs = B * stride * 3 * sizeof(int32_t);
+    const LkRange in[] = {{cam1, cam}, {cam2, cam}, {x1, pts}, {x2, pts}, {obs1_q8, obs}, {obs2_q8, obs}, {counts, word},
+                          {level1, B * stride}, {level2, B * stride}};
+    const LkRange out[] = {{best, word}, {score, word}, {ninliers, word}, {inlier, B * stride},
+                           {sim_out, B * s3m::OUT_WORDS * sizeof(float)}, {status, word}};
+    if (const char *bad = ranges_overlap(in, out)) return fail(c, PISLAM_ERR_INVALID, bad);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  s3::S3Args a{};
+  a.cam1 = cam1, a.cam2 = cam2, a.x1 = x1, a.x2 = x2, a.obs1 = obs1_q8, a.obs2 = obs2_q8, a.level1 = level1;
+  a.level2 = level2, a.counts = counts, a.stride = stride, a.batch = batch, a.hypotheses = p->hypotheses;
+  a.nlevels = level1 ? nlevels : 0, a.min_inliers = p->min_inliers, a.fixed_scale = p->fixed_scale, a.seed = p->seed;
+  for (int l = 0; l < a.nlevels; l++) a.inv_sigma2[l] = inv_sigma2[l];
+  a.best = best, a.score = score, a.ninliers = ninliers, a.inlier = inlier, a.sim_out = sim_out, a.status = status;
+  hipLaunchKernelGGL(s3::k_sim3_ransac, dim3((unsigned)std::min(batch, s3::S3_GRID_CAP)), dim3(s3::S3_THREADS), 0,
+                     c->stream, a);
+  return launch_ok(c, "k_sim3_ransac");
 }
 
 // ---- bag of words: integer weights and the key-frame database -----------------------------

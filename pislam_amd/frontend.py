@@ -1129,6 +1129,80 @@ def pnpRansacBatch(cam, xw, obs_q8, counts, *, level=None, inv_sigma2=None, hypo
     return best, score, ninliers, inlier, pose_out, status
 
 
+# ---- similarity from 3D-3D matches: Sim(3) RANSAC (Horn) ----------
+def cameraPoints(pose, xw):
+    """Map points in camera frames: Xc = R Xw + t per frame, for pose float32 [batch][12] (R row-major, then t: the pose
+    calls' layout) and world points xw float32 [batch][stride][3].  Plain torch; this is how callers who hold world
+    points and key-frame poses make sim3RansacBatch's x1 and x2."""
+    R, t = pose[:, :9].reshape(-1, 3, 3), pose[:, 9:12]
+    return (xw @ R.transpose(1, 2) + t[:, None, :]).contiguous()
+
+
+def sim3RansacBatch(cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts, *, level1=None, level2=None, inv_sigma2=None,
+                    hypotheses=200, seed=0, min_inliers=20, fixed_scale=False, best=None, score=None, ninliers=None,
+                    inlier=None, sim_out=None, status=None, ctx: Context | None = None):
+    """Batched Sim(3) RANSAC (pislam_sim3_ransac_batch; the contract is the comment in include/pislam_hip.h): per (key
+    frame, loop candidate) pair, the similarity X1 = s R X2 + t by Horn's closed form on `hypotheses` minimal samples
+    of the matched map points x1, x2 (float32 [batch][stride][3]: the same points in camera 1's and camera 2's frame,
+    stride <= 16384), scored by reprojection against obs1_q8, obs2_q8 (int32 [batch][stride][3], poseRefineBatch's; the
+    third word is ignored) with cam1, cam2 (float32 [batch][5]) and counts [batch]; level1 / level2 (both or neither)
+    and inv_sigma2 as in poseRefineBatch.  fixed_scale forces s = 1 (stereo / RGB-D maps).  Inputs are torch tensors
+    or numpy arrays (numpy goes to the current device).  Returns (best int32 [batch] = the winning hypothesis or -1,
+    score int32 [batch], ninliers int32 [batch], inlier uint8 [batch][stride] (entries at and beyond counts[b] are not
+    written), sim_out float32 [batch][13] = R row-major, t, s (the first 12 words are poseRefineBatch's `pose`),
+    status int32 [batch] = code | valid hypotheses << 8; code 0 ok, 1 fewer than min_inliers inliers, 2 no model, 3 bad
+    camera).  The same inputs and seed give the same outputs, bit for bit.  Asynchronous on the ctx stream, no
+    workspace: capturable."""
+    import torch
+    ctx = ctx or default_context()
+    as_t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda") if isinstance(a, np.ndarray) else a
+    cam1, cam2, x1, x2, obs1_q8, obs2_q8 = as_t(cam1), as_t(cam2), as_t(x1), as_t(x2), as_t(obs1_q8), as_t(obs2_q8)
+    counts, level1, level2 = as_t(counts), as_t(level1), as_t(level2)
+    if cam1.dtype != torch.float32 or cam1.dim() != 2 or int(cam1.shape[1]) != 5:
+        raise ValueError("cam1 must be a float32 tensor [batch][5]")
+    batch = int(cam1.shape[0])
+    if cam2.dtype != torch.float32 or tuple(cam2.shape) != (batch, 5):
+        raise ValueError("cam2 must be a float32 tensor [batch][5]")
+    if x1.dtype != torch.float32 or x1.dim() != 3 or int(x1.shape[0]) != batch or int(x1.shape[2]) != 3:
+        raise ValueError("x1 must be a float32 tensor [batch][stride][3]")
+    stride = int(x1.shape[1])
+    if x2.dtype != torch.float32 or tuple(x2.shape) != (batch, stride, 3):
+        raise ValueError("x2 must be a float32 tensor of x1's shape")
+    for o in (obs1_q8, obs2_q8):
+        if o.dtype != torch.int32 or tuple(o.shape) != (batch, stride, 3):
+            raise ValueError("obs1_q8 and obs2_q8 must be int32 tensors [batch][stride][3]")
+    if stride > POSE_MAX_STRIDE:
+        raise ValueError(f"at most {POSE_MAX_STRIDE} matches per pair")
+    if counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(counts.shape) != (batch,):
+        raise ValueError("counts must be a 32-bit integer tensor [batch]")
+    if (level1 is None) != (level2 is None) or (level1 is None) != (inv_sigma2 is None):
+        raise ValueError("level1, level2 and inv_sigma2 go together")
+    tab, ntab = None, 0
+    if level1 is not None:
+        for lv in (level1, level2):
+            if lv.dtype != torch.uint8 or tuple(lv.shape) != (batch, stride):
+                raise ValueError("level1 and level2 must be uint8 tensors [batch][stride]")
+        host = np.ascontiguousarray(np.asarray(inv_sigma2, dtype=np.float32).reshape(-1))
+        ntab = int(host.size)
+        if not 1 <= ntab <= 16:
+            raise ValueError("inv_sigma2 must have 1..16 entries")
+        tab = (ctypes.c_float * ntab)(*host.tolist())
+    for t in (cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts) + (() if level1 is None else (level1, level2)):
+        if not t.is_contiguous():
+            raise ValueError("inputs must be contiguous")
+    dev = cam1.device
+    p = capi.Sim3Params(int(hypotheses), int(seed) & 0xFFFFFFFF, int(min_inliers), int(bool(fixed_scale)))
+    word = lambda t: torch.empty((batch,), dtype=torch.int32, device=dev) if t is None else t
+    best, score, ninliers, status = word(best), word(score), word(ninliers), word(status)
+    inlier = torch.empty((batch, stride), dtype=torch.uint8, device=dev) if inlier is None else inlier
+    sim_out = torch.empty((batch, 13), dtype=torch.float32, device=dev) if sim_out is None else sim_out
+    ctx.check(ctx.lib.pislam_sim3_ransac_batch(ctx.h, ctypes.byref(p), ptr(cam1), ptr(cam2), ptr(x1), ptr(x2),
+                                               ptr(obs1_q8), ptr(obs2_q8), ptr(counts), ptr(level1), ptr(level2), tab,
+                                               ntab, stride, batch, ptr(best), ptr(score), ptr(ninliers), ptr(inlier),
+                                               ptr(sim_out), ptr(status)), "pislam_sim3_ransac_batch")
+    return best, score, ninliers, inlier, sim_out, status
+
+
 # ---- bag of words: integer weights and the key-frame database ----------
 BOW_MAX_STRIDE = 16384      # entries of a bag-of-words vector (pislam_bow_vector_batch)
 
