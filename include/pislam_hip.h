@@ -1531,8 +1531,8 @@ int pislam_pnp_ransac_batch(pislam_ctx *ctx, const pislam_pnp_params *p, const f
  * the call can be captured into a hipGraph as it is, so there is no reserve call.  One workgroup works on a pair; a
  * batch above 1024 pairs is walked by the same 1024 workgroups in passes.
  *
- * Not here: ORB-SLAM's 7-degree-of-freedom refinement of the result (OptimizeSim3), and SearchBySim3, which
- * pislam_match_hamming_scaled_window_batch with predicted centres covers, given this call's output. */
+ * Not here: SearchBySim3, which pislam_match_hamming_scaled_window_batch with predicted centres covers, given this
+ * call's output.  ORB-SLAM's 7-degree-of-freedom refinement of the result is pislam_sim3_refine_batch, below. */
 typedef struct pislam_sim3_params {
   int32_t hypotheses;   /* 1..1024, all of them are evaluated (ORB-SLAM: up to 300) */
   uint32_t seed;        /* any */
@@ -1544,6 +1544,122 @@ int pislam_sim3_ransac_batch(pislam_ctx *ctx, const pislam_sim3_params *p, const
                              const uint32_t *counts, const uint8_t *level1, const uint8_t *level2,
                              const float *inv_sigma2, int nlevels, size_t stride, int batch, int32_t *best,
                              uint32_t *score, uint32_t *ninliers, uint8_t *inlier, float *sim_out, uint32_t *status);
+
+/* ---- similarity refinement after the RANSAC: OptimizeSim3 ----------------- */
+
+/* The last step of the loop-closing chain: what ORB-SLAM's Optimizer::OptimizeSim3 computes
+ * with g2o, per (key frame, loop candidate) pair of a batch.  The similarity X1 = s R X2 + t that the RANSAC call found
+ * on three points is refined over all its matches (or over those of a guided re-match) by minimising the robust
+ * reprojection error in BOTH images; the map points stay fixed, as in ORB-SLAM.  LoopClosing::ComputeSim3 accepts a loop
+ * on the number of inliers AFTER this step: that is `ninliers`.  The call is pislam_pose_refine_batch's procedure on a
+ * 7-dimensional increment, and wherever this comment says "the pose call's" the words of that comment hold unchanged.
+ * The reference ships nothing of the kind: the semantics are this library's own, stated so that individually rounded
+ * binary32 and binary64 operations reproduce every output word.  This comment is the contract.  On floats every +, -, *,
+ * / and sqrt below is ONE operation of the stated format, rounded to nearest even, in the order the parentheses give
+ * (a + b + c means (a + b) + c); no fused multiply-add, no reciprocal or fast approximation; denormals are kept; no
+ * transcendental function is used.  "float(v)" converts to binary32 (round to nearest even), "double(v)" converts a
+ * binary32 to binary64 (exact).  A comparison with a NaN is false.
+ *
+ * Inputs, device unless said.  cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts, level1, level2, inv_sigma2 (HOST),
+ * nlevels, stride, batch: pislam_sim3_ransac_batch's own buffers, read by its rules (n = min(counts[b], stride),
+ * PISLAM_COUNT_INVALID counts as 0; (u, v) from the first two Q8 words; w1, w2 from the levels or 1.0f; a match with a
+ * level >= nlevels on either side is DEAD under every similarity).
+ *   sim_in  float [batch][13] = (R row-major, t, s): the RANSAC call's sim_out layout.
+ *   mask    uint8 [batch][stride] or NULL.  A 0 makes match i DEAD under every similarity; any other value, or NULL,
+ *           leaves it alone.  The RANSAC call's `inlier`, or the validity of a re-match, goes straight in.  Entries at
+ *           and beyond n are not read.
+ *
+ * One match under one similarity, binary32.  The similarity of a pass is the binary64 state (below) rounded word by
+ * word, R_ij = float(R_ij), t_i = float(t_i), s = float(s), and is = 1.0f / s.  With P = X1 and X = X2 of the match:
+ *   forward:   a_i = s * ((Ri0*X_0 + Ri1*X_1) + Ri2*X_2) + t_i,          projected with cam1 against (u1, v1), w1;
+ *   backward:  d = P - t,  b_i = ((R0i*d_0 + R1i*d_1) + R2i*d_2) * is,   projected with cam2 against (u2, v2), w2
+ * (the RANSAC call's scoring arithmetic, to the letter).  A side with the camera point (x, y, z), the weight w and the
+ * camera (fx, fy, cx, cy):
+ *   dead unless z >= 2^-10;  iz = 1.0f / z,  px = x*iz,  py = y*iz,  pu = fx*px + cx,  pv = fy*py + cy,
+ *   eu = u - pu,  ev = v - pv,  chi2 = (eu*eu + ev*ev) * w;  dead unless chi2 is finite.
+ * A match is DEAD unless both sides are live; a dead match contributes nothing and is an outlier.  Each side carries
+ * its own Huber weight with delta^2 = th2, the pose call's formula: if the pass is robust and chi2 > th2:
+ *   k = sqrt(th2 / chi2),  wr = w*k,  rho = (chi2*k)*2.0f - th2;     otherwise wr = w, rho = chi2.
+ *
+ * The increment is a LEFT one, d = (omega_0..2, upsilon_0..2, sigma): S' = dS . S with dS = (Q(omega), upsilon,
+ * k(sigma)), Q the pose call's Cayley map and k = (2 + sigma) / (2 - sigma), the Pade form of exp(sigma).  To first
+ * order the forward camera point moves by da = omega x a + upsilon + sigma*a and the backward one by
+ * db = is * R'(P x omega - upsilon - sigma*P).  Jacobian rows of the error (eu, ev) of a side, seven entries each:
+ *   forward, with A = fx*iz, B = fy*iz, pxy = px*py (the pose call's monocular rows; the projection annihilates the
+ *   scale column, sigma*a being along the ray, and that column is the constant 0.0f):
+ *     Ju = [ pxy*fx, -((1.0f + px*px)*fx), py*fx, -A, 0.0f, px*A, 0.0f ]
+ *     Jv = [ (1.0f + py*py)*fy, -(pxy*fy), -(px*fy), 0.0f, -B, py*B, 0.0f ]
+ *   backward, with A = fx*iz, B = fy*iz of camera 2 at b: first the seven columns W_c of R'(P x e_c), -R'e_c, -R'P, for
+ *   i = 0 .. 2 with (r0, r1, r2) = (R0i, R1i, R2i), column i of R:
+ *     W_0i = r1*P_2 - r2*P_1,   W_1i = r2*P_0 - r0*P_2,   W_2i = r0*P_1 - r1*P_0,
+ *     W_3i = -r0,  W_4i = -r1,  W_5i = -r2,   W_6i = -((r0*P_0 + r1*P_1) + r2*P_2);
+ *   then for c = 0 .. 6:  D_ci = W_ci * is  (i = 0 .. 2),
+ *     Ju_c = -(A * (D_c0 - px*D_c2)),   Jv_c = -(B * (D_c1 - py*D_c2)).
+ * A side's 36 terms, in this order: for j = 0 .. 6, for k = j .. 6 (28 terms, the upper triangle row by row)
+ *   H_jk = (Ju_j*Ju_k + Jv_j*Jv_k) * wr;   for j = 0 .. 6:  g_j = (Ju_j*eu + Jv_j*ev) * wr;   then rho.
+ * The products with the constant 0.0f entries are carried out like any other.
+ *
+ * A PASS evaluates every match of the pair at one similarity and sums, in binary64, over the matches that are ACTIVE
+ * and not dead: 38 sums S_0 .. S_37; S = (H, g, F = S_35, S_36, S_37).  The order is the pose call's: 256 partial sums
+ * that start at +0.0; match i adds to partial i mod 256, in ascending i, first double(term) of each of its 36 forward
+ * terms, then double(term) of each of its 36 backward terms (two additions to each of the sums 0 .. 35), then 1.0 to
+ * sum 36, then double(chi2_1) and then double(chi2_2) to sum 37 (the plain chi2 of both sides); the partials are
+ * combined by the pose call's halving tree (128, 64, 32, 16, 8, 4, 2, 1), unchanged; S is p[0].  No other float is ever
+ * summed across matches.  A CLASSIFYING pass first sets the active set anew from EVERY match: active iff not dead and
+ * chi2_1 <= th2 and chi2_2 <= th2 at the pass's similarity; it then sums over that new set.
+ *
+ * Per pair, binary64.  The state T = (R, t, s) is double(sim_in) and stays in binary64 for the whole call.
+ *   Solve(S, lambda): the pose call's elimination on 7 x 7: A = the symmetric matrix of the H sums, A_jj = H_jj *
+ *     (1.0 + lambda), rhs_j = -g_j.  With fixed_scale, row and column 6 are then replaced: A_j6 = A_6j = 0.0 for j < 6,
+ *     A_66 = 1.0, rhs_6 = 0.0.  Gaussian elimination WITHOUT pivoting, for c = 0 .. 6: the solve fails unless
+ *     A[c][c] > 0; for r = c+1 .. 6: f = A[r][c] / A[c][c]; for j = c+1 .. 6: A[r][j] = A[r][j] - f*A[c][j];
+ *     rhs_r = rhs_r - f*rhs_c.  Back substitution, r = 6 .. 0: s = rhs_r; for j = r+1 .. 6 ascending: s = s - A[r][j]*d_j;
+ *     d_r = s / A[r][r].  The solve also fails when a d_r is not finite, or unless |d_6| < 2.0.  (With fixed_scale
+ *     d_6 = +0.0 and k = 1.0 exactly, so s stays double(sim_in[12]) bit for bit.)
+ *   Retract(T, d): Q from (d_0, d_1, d_2) by the pose call's Cayley formulas;  k = (2.0 + d_6) / (2.0 - d_6);
+ *     R'_ij = (Q_i0*R_0j + Q_i1*R_1j) + Q_i2*R_2j,   t'_i = k * ((Q_i0*t_0 + Q_i1*t_1) + Q_i2*t_2) + d_(3+i),
+ *     s' = k * s.
+ *   A ROUND is the pose call's Levenberg round, word for word, with this Solve, this Retract and F = S_35: lambda starts
+ *   at 2^-10, up to `iters` iterations, a failed solve spends its iteration with lambda = min(8.0*lambda, 2^20), a trial
+ *   is accepted iff F' < F (then lambda = max(lambda*0.25, 2^-30), else lambda = min(8.0*lambda, 2^20)), and the round
+ *   ends when max_j |d_j| <= eps.  One pass per iteration.
+ *   The call:  sim_in, cam1 or cam2 not finite, s > 0 false, or an fx or fy == 0: code 2.  n < min_obs: code 1.
+ *   Otherwise every match is active and a pass at T gives round 0 its S; the passes of round r are robust iff
+ *   r < huber_rounds.  After round r a CLASSIFYING pass at T, robust iff r + 1 < huber_rounds, gives the inlier mask
+ *   (= the new active set), ninliers = S_36 and cost = S_37, and its S is the start of round r + 1, which runs unless
+ *   r + 1 == rounds (code 0) or ninliers < min_obs (code 1).  A round continues from where the last ended.  (ORB-SLAM
+ *   runs 5 iterations, removes the outliers and runs 10 or 5 more without the kernels; rounds = 2, iters = 5,
+ *   huber_rounds = 2 keeps its kernels on and leaves the surplus iterations to the Levenberg stop.)
+ *
+ * Outputs, per pair, always written, all device.  sim_out float [batch][13] = float(T) (sim_in itself for code 2 and
+ * for a pair that never ran a round); it may be exactly sim_in.  inlier uint8 [batch][stride]: the last classification,
+ * 0 or 1 for i < n (all 0 for a pair that never ran a round); entries at and beyond n are not written.  ninliers uint32
+ * [batch].  cost double [batch]: the tree-ordered sum of the inliers' plain chi2 of both sides (0 without a round).
+ * status uint32 [batch] = code | evaluations << 8, evaluations = the number of passes made; code 0: all rounds ran;
+ * 1: stopped for min_obs, the similarity is that of the last completed round, or sim_in; 2: as above.
+ *
+ * Limits: the parameter ranges in the struct comments; 1 <= stride <= 16384; batch >= 0 with no upper limit (batch ==
+ * 0 is a no-op that returns PISLAM_OK after the checks of p, the levels, the table, batch and stride; the other
+ * pointers are not looked at then).  Offsets use size_t arithmetic throughout.  No output may overlap an input or
+ * another output, except that sim_out may be sim_in (so `inlier` is never `mask`).  Any violation, one level pointer
+ * without the other, or a NULL or host pointer where a device pointer is required: PISLAM_ERR_INVALID, before anything
+ * is launched or written.  `p` is a host struct, read during the call.  Asynchronous on the context stream; no
+ * workspace, no host round trip: the call can be captured into a hipGraph as it is.  One workgroup runs a pair's whole
+ * call in one launch; a batch above 1024 pairs is walked by the same 1024 workgroups in passes. */
+typedef struct pislam_sim3_refine_params {
+  int32_t rounds;        /* 1..8 (ORB-SLAM: 2) */
+  int32_t iters;         /* 1..32 Levenberg iterations per round (ORB-SLAM: 5) */
+  int32_t huber_rounds;  /* 0..rounds: rounds 0 .. huber_rounds - 1 are robust (ORB-SLAM: 2) */
+  int32_t min_obs;       /* 3..16384 active matches needed to run a round (ORB-SLAM: 10) */
+  float th2;             /* finite, > 0: the chi2 bound of one side and delta^2 of its Huber kernel (ORB-SLAM: 10.0f) */
+  int32_t fixed_scale;   /* 0 / 1: 1 keeps s (stereo / RGB-D maps) */
+  double eps;            /* >= 0: a round ends when no |d_j| exceeds it (1e-6) */
+} pislam_sim3_refine_params;
+int pislam_sim3_refine_batch(pislam_ctx *ctx, const pislam_sim3_refine_params *p, const float *sim_in, const float *cam1,
+                             const float *cam2, const float *x1, const float *x2, const int32_t *obs1_q8,
+                             const int32_t *obs2_q8, const uint32_t *counts, const uint8_t *level1, const uint8_t *level2,
+                             const uint8_t *mask, const float *inv_sigma2, int nlevels, size_t stride, int batch,
+                             float *sim_out, uint8_t *inlier, uint32_t *ninliers, double *cost, uint32_t *status);
 
 /* ---- multi-GPU: one process per GPU, pyramids sharded, ONE collective ---- */
 

@@ -70,6 +70,12 @@ class Sim3Params(ctypes.Structure):
                 ("fixed_scale", ctypes.c_int32)]
 
 
+class Sim3RefineParams(ctypes.Structure):
+    _fields_ = [("rounds", ctypes.c_int32), ("iters", ctypes.c_int32), ("huber_rounds", ctypes.c_int32),
+                ("min_obs", ctypes.c_int32), ("th2", ctypes.c_float), ("fixed_scale", ctypes.c_int32),
+                ("eps", ctypes.c_double)]
+
+
 class ClaheParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "tiles_x", "tiles_y", "clip_q8")]
 
@@ -174,6 +180,8 @@ SYMBOLS = {
                                      ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pislam_sim3_ransac_batch": (_i, [_vp, ctypes.POINTER(Sim3Params), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pislam_sim3_refine_batch": (_i, [_vp, ctypes.POINTER(Sim3RefineParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
     "pislam_bow_weight_batch": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, ctypes.c_uint32, _vp]),
     "pislam_bowdb_create": (_i, [_vp, ctypes.c_uint32, _sz, _i, ctypes.POINTER(_vp)]),
     "pislam_bowdb_destroy": (_i, [_vp]),

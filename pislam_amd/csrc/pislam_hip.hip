@@ -64,6 +64,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_pose_kernels.h"
 #include "pislam_pnp_kernels.h"
 #include "pislam_sim3_kernels.h"
+#include "pislam_sim3_refine_kernels.h"
 #include "pislam_warp_kernels.h"
 #include "pislam_clahe_kernels.h"
 
@@ -2671,6 +2672,63 @@ PISLAM_EXPORT int pislam_sim3_ransac_batch(pislam_ctx *c, const pislam_sim3_para
   hipLaunchKernelGGL(s3::k_sim3_ransac, dim3((unsigned)std::min(batch, s3::S3_GRID_CAP)), dim3(s3::S3_THREADS), 0,
                      c->stream, a);
   return launch_ok(c, "k_sim3_ransac");
+}
+
+// ---- similarity refinement after the RANSAC: batched OptimizeSim3 ---------------------------
+
+PISLAM_EXPORT int pislam_sim3_refine_batch(pislam_ctx *c, const pislam_sim3_refine_params *p, const float *sim_in,
+                                           const float *cam1, const float *cam2, const float *x1, const float *x2,
+                                           const int32_t *obs1_q8, const int32_t *obs2_q8, const uint32_t *counts,
+                                           const uint8_t *level1, const uint8_t *level2, const uint8_t *mask,
+                                           const float *inv_sigma2, int nlevels, size_t stride, int batch,
+                                           float *sim_out, uint8_t *inlier, uint32_t *ninliers, double *cost,
+                                           uint32_t *status) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
+  if (p->rounds < 1 || p->rounds > 8) return fail(c, PISLAM_ERR_INVALID, "rounds must be 1..8");
+  if (p->iters < 1 || p->iters > 32) return fail(c, PISLAM_ERR_INVALID, "iters must be 1..32");
+  if (p->huber_rounds < 0 || p->huber_rounds > p->rounds) return fail(c, PISLAM_ERR_INVALID, "huber_rounds must be 0..rounds");
+  if (p->min_obs < 3 || p->min_obs > s3r::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "min_obs must be 3..16384");
+  if (!(p->th2 > 0.0f) || !psm::finite_f(p->th2)) return fail(c, PISLAM_ERR_INVALID, "th2 must be finite and > 0");
+  if (p->fixed_scale != 0 && p->fixed_scale != 1) return fail(c, PISLAM_ERR_INVALID, "fixed_scale must be 0 or 1");
+  if (!(p->eps >= 0.0)) return fail(c, PISLAM_ERR_INVALID, "eps must be >= 0");
+  if ((level1 != nullptr) != (level2 != nullptr)) return fail(c, PISLAM_ERR_INVALID, "level1 and level2 go together");
+  if (level1) {
+    if (!inv_sigma2 || nlevels < 1 || nlevels > s3r::MAX_LEVELS)
+      return fail(c, PISLAM_ERR_INVALID, "levels need inv_sigma2 with 1..16 entries");
+    for (int l = 0; l < nlevels; l++)
+      if (!(inv_sigma2[l] > 0.0f) || !psm::finite_f(inv_sigma2[l]))
+        return fail(c, PISLAM_ERR_INVALID, "inv_sigma2 must be finite and > 0");
+  }
+  if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
+  if (stride < 1 || stride > (size_t)s3r::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
+  if (batch == 0) return PISLAM_OK;
+  const char *what = "the similarity refinement takes device pointers only";
+  PCHK(device_ptrs(c, {sim_in, cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts, sim_out, inlier, ninliers, cost, status}, what));
+  if (level1 && (!is_device_ptr(level1) || !is_device_ptr(level2))) return fail(c, PISLAM_ERR_INVALID, what);
+  if (mask && !is_device_ptr(mask)) return fail(c, PISLAM_ERR_INVALID, what);
+  {
+    const size_t B = (size_t)batch, word = B * sizeof(uint32_t), cam = B * 5 * sizeof(float);
+    const size_t sim = B * s3r::STATE * sizeof(float);
+    const size_t pts = B * stride * 3 * sizeof(float), obs = B * stride * 3 * sizeof(int32_t);
+    const LkRange in[] = {{sim_in, sim}, {cam1, cam}, {cam2, cam}, {x1, pts}, {x2, pts}, {obs1_q8, obs}, {obs2_q8, obs},
+                          {counts, word}, {level1, B * stride}, {level2, B * stride}, {mask, B * stride}};
+    const LkRange out[] = {{sim_out, sim}, {inlier, B * stride}, {ninliers, word}, {cost, B * sizeof(double)},
+                           {status, word}};
+    // sim_out == sim_in is allowed: a pair reads its similarity before it writes it
+    if (const char *bad = ranges_overlap(in, out, 0)) return fail(c, PISLAM_ERR_INVALID, bad);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  sr::SrArgs a{};
+  a.sim_in = sim_in, a.cam1 = cam1, a.cam2 = cam2, a.x1 = x1, a.x2 = x2, a.obs1 = obs1_q8, a.obs2 = obs2_q8;
+  a.level1 = level1, a.level2 = level2, a.mask = mask, a.counts = counts, a.stride = stride, a.batch = batch;
+  a.nlevels = level1 ? nlevels : 0;
+  for (int l = 0; l < a.nlevels; l++) a.inv_sigma2[l] = inv_sigma2[l];
+  a.p = s3r::Params{p->rounds, p->iters, p->huber_rounds, p->min_obs, p->th2, p->fixed_scale, p->eps};
+  a.sim_out = sim_out, a.inlier = inlier, a.ninliers = ninliers, a.status = status, a.cost = cost;
+  hipLaunchKernelGGL(sr::k_sim3_refine, dim3((unsigned)std::min(batch, sr::SR_GRID_CAP)), dim3(sr::SR_THREADS), 0,
+                     c->stream, a);
+  return launch_ok(c, "k_sim3_refine");
 }
 
 // ---- bag of words: integer weights and the key-frame database -----------------------------

@@ -82,16 +82,19 @@ PISLAM_UNROLL
   return true;
 }
 
-// A d = -g with A = H, A_jj = H_jj * (1 + lambda); S = the 28 sums.  Gaussian elimination without pivoting, back
-// substitution.  False: a pivot that is not > 0 (a NaN fails) or a d that is not finite.
-PISLAM_HD bool solve(const double *S, double lambda, double *d) {
-  double A[6][6], b[6];
+// A d = -g with A = H, A_jj = H_jj * (1 + lambda); S = the N (N + 1) / 2 sums of H's upper triangle, row by row, then
+// the N sums of g.  Gaussian elimination without pivoting, back substitution.  False: a pivot that is not > 0 (a NaN
+// fails) or a d that is not finite.  pin_last: the last unknown is taken out first (row and column N - 1 become those
+// of the identity, its right-hand side 0), so it comes out as 0.
+template <int N>
+PISLAM_HD bool solve_n(const double *S, double lambda, double *d, bool pin_last = false) {
+  double A[N][N], b[N];
   {
     int o = 0;
 PISLAM_UNROLL
-    for (int j = 0; j < 6; j++) {
+    for (int j = 0; j < N; j++) {
 PISLAM_UNROLL
-      for (int k = j; k < 6; k++) {
+      for (int k = j; k < N; k++) {
         A[j][k] = S[o], A[k][j] = S[o];
         o++;
       }
@@ -99,39 +102,50 @@ PISLAM_UNROLL
   }
   const double s = 1.0 + lambda;
 PISLAM_UNROLL
-  for (int j = 0; j < 6; j++) A[j][j] = A[j][j] * s, b[j] = -S[21 + j];
+  for (int j = 0; j < N; j++) A[j][j] = A[j][j] * s, b[j] = -S[N * (N + 1) / 2 + j];
+  if (pin_last) {
+PISLAM_UNROLL
+    for (int j = 0; j < N - 1; j++) A[j][N - 1] = 0.0, A[N - 1][j] = 0.0;
+    A[N - 1][N - 1] = 1.0, b[N - 1] = 0.0;
+  }
   bool ok = true;
 PISLAM_UNROLL
-  for (int c = 0; c < 6; c++) {
+  for (int c = 0; c < N; c++) {
     ok = ok && A[c][c] > 0.0;
 PISLAM_UNROLL
-    for (int r = c + 1; r < 6; r++) {
+    for (int r = c + 1; r < N; r++) {
       const double f = A[r][c] / A[c][c];
 PISLAM_UNROLL
-      for (int j = c + 1; j < 6; j++) A[r][j] = A[r][j] - f * A[c][j];
+      for (int j = c + 1; j < N; j++) A[r][j] = A[r][j] - f * A[c][j];
       b[r] = b[r] - f * b[c];
     }
   }
 PISLAM_UNROLL
-  for (int r = 5; r >= 0; r--) {
+  for (int r = N - 1; r >= 0; r--) {
     double t = b[r];
 PISLAM_UNROLL
-    for (int j = r + 1; j < 6; j++) t = t - A[r][j] * d[j];
+    for (int j = r + 1; j < N; j++) t = t - A[r][j] * d[j];
     d[r] = t / A[r][r];
     ok = ok && finite_d(d[r]);
   }
   return ok;
 }
+PISLAM_HD bool solve(const double *S, double lambda, double *d) { return solve_n<6>(S, lambda, d); }
 
-// The Cayley retraction of T by d = (omega, upsilon): R' = Q R, t' = Q t + upsilon.
-PISLAM_HD void retract(const double *T, const double *d, double *Tn) {
+// The Cayley map of the rotation vector d[0..2]: Q = ((1 - n) I + 2 a a' + 2 [a]x) / (1 + n) with a = d / 2, n = a'a.
+PISLAM_HD void cayley(const double *d, double *Q) {
   const double a0 = d[0] * 0.5, a1 = d[1] * 0.5, a2 = d[2] * 0.5;
   const double n = (a0 * a0 + a1 * a1) + a2 * a2;
   const double m = 1.0 - n, den = 1.0 + n;
-  double Q[9];
   Q[0] = (m + 2.0 * (a0 * a0)) / den, Q[1] = (2.0 * (a0 * a1) - 2.0 * a2) / den, Q[2] = (2.0 * (a0 * a2) + 2.0 * a1) / den;
   Q[3] = (2.0 * (a1 * a0) + 2.0 * a2) / den, Q[4] = (m + 2.0 * (a1 * a1)) / den, Q[5] = (2.0 * (a1 * a2) - 2.0 * a0) / den;
   Q[6] = (2.0 * (a2 * a0) - 2.0 * a1) / den, Q[7] = (2.0 * (a2 * a1) + 2.0 * a0) / den, Q[8] = (m + 2.0 * (a2 * a2)) / den;
+}
+
+// The Cayley retraction of T by d = (omega, upsilon): R' = Q R, t' = Q t + upsilon.
+PISLAM_HD void retract(const double *T, const double *d, double *Tn) {
+  double Q[9];
+  cayley(d, Q);
 PISLAM_UNROLL
   for (int i = 0; i < 3; i++) {
 PISLAM_UNROLL

@@ -172,9 +172,12 @@ PISLAM_HD bool hypothesis(const FETCH &fetch, uint32_t n, uint32_t seed, uint32_
   return solve(fetch(draw[0]), fetch(draw[1]), fetch(draw[2]), fixed_scale, S);
 }
 
-// chi2 of the pixel (u, v) against the projection of the camera point (x, y, z): the pose call's monocular arithmetic.
-// False: dead (nothing is written).
-PISLAM_HD bool chi2_at(const Cam &C, float x, float y, float z, float u, float v, float w, float *chi2_out) {
+// The pixel (u, v) against the projection of the camera point (x, y, z): the pose call's monocular arithmetic, with the
+// intermediates a Jacobian needs (pislam_sim3_refine_math.h).  False: dead (nothing is written).
+struct Side {
+  float iz, px, py, eu, ev, chi2;
+};
+PISLAM_HD bool side_at(const Cam &C, float x, float y, float z, float u, float v, float w, Side *out) {
   if (!(z >= pq::Z_MIN)) return false;
   const float iz = fdiv(1.0f, z);
   const float px = x * iz, py = y * iz;
@@ -182,15 +185,20 @@ PISLAM_HD bool chi2_at(const Cam &C, float x, float y, float z, float u, float v
   const float eu = u - pu, ev = v - pv;
   const float chi2 = (eu * eu + ev * ev) * w;
   if (!finite_f(chi2)) return false;
-  *chi2_out = chi2;
+  *out = Side{iz, px, py, eu, ev, chi2};
+  return true;
+}
+PISLAM_HD bool chi2_at(const Cam &C, float x, float y, float z, float u, float v, float w, float *chi2_out) {
+  Side s;
+  if (!side_at(C, x, y, z, u, v, w, &s)) return false;
+  *chi2_out = s.chi2;
   return true;
 }
 
-// What one match adds to a hypothesis's score; *inl = it is an inlier.
-PISLAM_HD uint32_t score(const float (&S)[WORDS], const Cam &C1, const Cam &C2, const Match &m, bool *inl) {
-  *inl = false;
-  if (!m.live) return 0u;
-  float a[3], b[3], d[3];
+// The two camera points of a match under S = (R, t, s, 1 / s): a = s (R X2) + t in camera 1, b = (R'(X1 - t)) / s in
+// camera 2.
+PISLAM_HD void camera_points(const float *S, const Match &m, float (&a)[3], float (&b)[3]) {
+  float d[3];
 PISLAM_UNROLL
   for (int i = 0; i < 3; i++) {
     a[i] = S[12] * ((S[3 * i] * m.X2[0] + S[3 * i + 1] * m.X2[1]) + S[3 * i + 2] * m.X2[2]) + S[9 + i];
@@ -198,6 +206,14 @@ PISLAM_UNROLL
   }
 PISLAM_UNROLL
   for (int i = 0; i < 3; i++) b[i] = ((S[i] * d[0] + S[3 + i] * d[1]) + S[6 + i] * d[2]) * S[13];
+}
+
+// What one match adds to a hypothesis's score; *inl = it is an inlier.
+PISLAM_HD uint32_t score(const float (&S)[WORDS], const Cam &C1, const Cam &C2, const Match &m, bool *inl) {
+  *inl = false;
+  if (!m.live) return 0u;
+  float a[3], b[3];
+  camera_points(S, m, a, b);
   float c1 = 0.0f, c2 = 0.0f;
   if (!chi2_at(C1, a[0], a[1], a[2], m.u1, m.v1, m.w1, &c1)) return 0u;
   if (!chi2_at(C2, b[0], b[1], b[2], m.u2, m.v2, m.w2, &c2)) return 0u;

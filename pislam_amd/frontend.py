@@ -1203,6 +1203,77 @@ def sim3RansacBatch(cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts, *, level1=None
     return best, score, ninliers, inlier, sim_out, status
 
 
+def sim3RefineBatch(sim_in, cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts, *, level1=None, level2=None, inv_sigma2=None,
+                    mask=None, rounds=2, iters=5, huber_rounds=2, min_obs=10, th2=10.0, fixed_scale=False, eps=1e-6,
+                    sim_out=None, inlier=None, ninliers=None, cost=None, status=None, ctx: Context | None = None):
+    """Batched Sim(3) refinement (pislam_sim3_refine_batch; the contract is the comment in include/pislam_hip.h): per
+    (key frame, loop candidate) pair, ORB-SLAM's OptimizeSim3: the similarity sim_in (float32 [batch][13]: R row-major,
+    t, s; sim3RansacBatch's sim_out goes straight in) is refined over the matches by minimising the robust reprojection
+    error in both images, the map points fixed.  cam1 .. counts, level1 / level2 / inv_sigma2 and fixed_scale are
+    sim3RansacBatch's arguments, by its conventions.  mask (uint8 [batch][stride], optional): a 0 takes the match out
+    (sim3RansacBatch's `inlier`, or the validity of a guided re-match).  ORB-SLAM's schedule: `rounds` rounds of up to
+    `iters` Levenberg iterations, the first `huber_rounds` with a Huber kernel of delta^2 = th2 on each side, an inlier
+    classification (both chi2 <= th2) after each; a round needs `min_obs` active matches.  Returns (sim_out float32
+    [batch][13], inlier uint8 [batch][stride] (entries at and beyond counts[b] are not written), ninliers int32 [batch],
+    cost float64 [batch], status int32 [batch] = code | evaluations << 8; code 0 ok, 1 stopped for min_obs, 2 bad
+    similarity or camera).  sim_out may be `sim_in` itself.  The same inputs give the same outputs, bit for bit.
+    Asynchronous on the ctx stream, no workspace: capturable."""
+    import torch
+    ctx = ctx or default_context()
+    as_t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda") if isinstance(a, np.ndarray) else a
+    sim_in, cam1, cam2, x1, x2 = as_t(sim_in), as_t(cam1), as_t(cam2), as_t(x1), as_t(x2)
+    obs1_q8, obs2_q8, counts, level1, level2, mask = (as_t(obs1_q8), as_t(obs2_q8), as_t(counts), as_t(level1),
+                                                       as_t(level2), as_t(mask))
+    if sim_in.dtype != torch.float32 or sim_in.dim() != 2 or int(sim_in.shape[1]) != 13:
+        raise ValueError("sim_in must be a float32 tensor [batch][13]")
+    batch = int(sim_in.shape[0])
+    for c in (cam1, cam2):
+        if c.dtype != torch.float32 or tuple(c.shape) != (batch, 5):
+            raise ValueError("cam1 and cam2 must be float32 tensors [batch][5]")
+    if x1.dtype != torch.float32 or x1.dim() != 3 or int(x1.shape[0]) != batch or int(x1.shape[2]) != 3:
+        raise ValueError("x1 must be a float32 tensor [batch][stride][3]")
+    stride = int(x1.shape[1])
+    if x2.dtype != torch.float32 or tuple(x2.shape) != (batch, stride, 3):
+        raise ValueError("x2 must be a float32 tensor of x1's shape")
+    for o in (obs1_q8, obs2_q8):
+        if o.dtype != torch.int32 or tuple(o.shape) != (batch, stride, 3):
+            raise ValueError("obs1_q8 and obs2_q8 must be int32 tensors [batch][stride][3]")
+    if stride > POSE_MAX_STRIDE:
+        raise ValueError(f"at most {POSE_MAX_STRIDE} matches per pair")
+    if counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(counts.shape) != (batch,):
+        raise ValueError("counts must be a 32-bit integer tensor [batch]")
+    if (level1 is None) != (level2 is None) or (level1 is None) != (inv_sigma2 is None):
+        raise ValueError("level1, level2 and inv_sigma2 go together")
+    tab, ntab = None, 0
+    if level1 is not None:
+        for lv in (level1, level2):
+            if lv.dtype != torch.uint8 or tuple(lv.shape) != (batch, stride):
+                raise ValueError("level1 and level2 must be uint8 tensors [batch][stride]")
+        host = np.ascontiguousarray(np.asarray(inv_sigma2, dtype=np.float32).reshape(-1))
+        ntab = int(host.size)
+        if not 1 <= ntab <= 16:
+            raise ValueError("inv_sigma2 must have 1..16 entries")
+        tab = (ctypes.c_float * ntab)(*host.tolist())
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (batch, stride)):
+        raise ValueError("mask must be a uint8 tensor [batch][stride]")
+    for t in (sim_in, cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts) + tuple(v for v in (level1, level2, mask) if v is not None):
+        if not t.is_contiguous():
+            raise ValueError("inputs must be contiguous")
+    dev = sim_in.device
+    p = capi.Sim3RefineParams(int(rounds), int(iters), int(huber_rounds), int(min_obs), float(th2), int(bool(fixed_scale)),
+                              float(eps))
+    word = lambda t: torch.empty((batch,), dtype=torch.int32, device=dev) if t is None else t
+    ninliers, status = word(ninliers), word(status)
+    sim_out = torch.empty((batch, 13), dtype=torch.float32, device=dev) if sim_out is None else sim_out
+    inlier = torch.empty((batch, stride), dtype=torch.uint8, device=dev) if inlier is None else inlier
+    cost = torch.empty((batch,), dtype=torch.float64, device=dev) if cost is None else cost
+    ctx.check(ctx.lib.pislam_sim3_refine_batch(ctx.h, ctypes.byref(p), ptr(sim_in), ptr(cam1), ptr(cam2), ptr(x1), ptr(x2),
+                                               ptr(obs1_q8), ptr(obs2_q8), ptr(counts), ptr(level1), ptr(level2), ptr(mask),
+                                               tab, ntab, stride, batch, ptr(sim_out), ptr(inlier), ptr(ninliers),
+                                               ptr(cost), ptr(status)), "pislam_sim3_refine_batch")
+    return sim_out, inlier, ninliers, cost, status
+
+
 # ---- bag of words: integer weights and the key-frame database ----------
 BOW_MAX_STRIDE = 16384      # entries of a bag-of-words vector (pislam_bow_vector_batch)
 
