@@ -1,15 +1,16 @@
 // pislam_geom_math.h — the arithmetic of pislam_two_view_ransac_batch (include/pislam_hip.h: that comment is the
 // contract), stated ONCE for the device kernel (pislam_geom_kernels.h) and for a plain C++ compiler (tools/probes/
 // ransac_host_check.cpp): a pair's normalisation, the counter-based sampler, the 8 x 9 system and its elimination, the
-// two chi-square forms in binary32, the integer score, the best-of rule, and, for the host only, the whole call for one
-// pair run serially.  Every operation is written out one rounding at a time; build with -ffp-contract=off.
+// two chi-square forms in binary32, the integer score, the pair as the RANSAC skeleton sees it (pislam_ransac_math.h,
+// which holds the best-of rule and the serial form of the steps), and, for the host only, the whole call for one pair
+// run serially.  Every operation is written out one rounding at a time; build with -ffp-contract=off.
 #pragma once
 #include <stdlib.h>
-#include "pislam_scalar_math.h"
+#include "pislam_ransac_math.h"
 
 namespace pgm {
 
-constexpr int MAX_HYP = 1024;
+constexpr int MAX_HYP = prk::MAX_HYP;
 constexpr int MAX_STRIDE = 16384;
 constexpr float PIVOT_MIN = 0x1p-20f;
 constexpr float TH_SCORE = 5.991f;
@@ -206,22 +207,51 @@ PISLAM_HD uint32_t score(const Model<MODEL> &m, const Point &P, float w1, float 
   return s;
 }
 
-// The best-of rule as one integer: the largest key wins, that is the largest score and, on a tie, the smallest k.  A
-// score of 0 never competes, so a key of 0 means "no model".
-PISLAM_HD unsigned long long best_key(uint32_t s, int k) {
-  return ((unsigned long long)s << 10) | (unsigned long long)(MAX_HYP - 1 - k);
-}
-PISLAM_HD int key_hypothesis(unsigned long long key) { return MAX_HYP - 1 - (int)(key & (MAX_HYP - 1)); }
-PISLAM_HD uint32_t key_score(unsigned long long key) { return (uint32_t)(key >> 10); }
-
-#if !defined(__HIP_DEVICE_COMPILE__)
-// ---- the host's serial form of the whole call for one pair (the probe; never the library's hot path) ----------------
-
+// One pair as the call reads it.
 struct PairIn {
   const int32_t *p1, *p2;                      // [n][2]
   uint32_t n;                                  // already psm::clamp_count(count, stride)
   uint32_t b;                                  // the pair's index in the batch: the sampler hashes it
 };
+PISLAM_HD Match match_at(const PairIn &I, uint32_t i) {
+  return match(I.p1[2 * (size_t)i], I.p1[2 * (size_t)i + 1], I.p2[2 * (size_t)i], I.p2[2 * (size_t)i + 1]);
+}
+
+// The pair as the RANSAC skeleton sees it (pislam_ransac_math.h), from its integer sums: N with n and the four
+// coordinate sums, D1 and D2 the two spreads.
+template <int MODEL>
+struct Problem {
+  static constexpr int WORDS = 8;
+  using Item = Point;
+  PairIn I;
+  Norm N;
+  float w1, w2;
+  uint32_t seed, n;
+  bool have;
+  PISLAM_HD Problem(const PairIn &I_, const Norm &N_, long long D1, long long D2, float sigma, uint32_t seed_)
+      : I(I_), N(N_), w1(0.0f), w2(0.0f), seed(seed_), n(I_.n) {
+    have = n >= (uint32_t)sample_size(MODEL) && D1 != 0 && D2 != 0;
+    if (have) {
+      N.k1 = scale(N.n, D1), N.k2 = scale(N.n, D2);
+      w1 = weight(N.n, N.k1, sigma), w2 = weight(N.n, N.k2, sigma);
+    }
+  }
+  PISLAM_HD Point item(uint32_t i) const { return point(N, match_at(I, i)); }
+  PISLAM_HD bool hypothesis(uint32_t k, float (&x)[8]) const {
+    const PairIn &J = I;
+    return pgm::hypothesis<MODEL>(N, [&J](uint32_t i) { return match_at(J, i); }, seed, I.b, k, x);
+  }
+  PISLAM_HD uint32_t score(const float (&x)[8], const Point &P, bool *inl) const {
+    return pgm::score<MODEL>(Model<MODEL>(x), P, w1, w2, inl);
+  }
+};
+PISLAM_HD void stats_row(const Norm &N, long long D1, long long D2, long long *st) {
+  st[0] = N.n, st[1] = N.sx1, st[2] = N.sy1, st[3] = D1, st[4] = N.sx2, st[5] = N.sy2, st[6] = D2, st[7] = 0;
+}
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// ---- the host's serial form of the whole call for one pair (the probe; never the library's hot path) ----------------
+
 struct PairOut {
   int32_t best;
   uint32_t score, ninliers;
@@ -231,54 +261,23 @@ struct PairOut {
 
 template <int MODEL>
 inline void host_pair(const PairIn &I, int hypotheses, uint32_t seed, int32_t sigma_q8, PairOut *O, uint8_t *inlier) {
-  const auto fetch = [&I](uint32_t i) {
-    return match(I.p1[2 * (size_t)i], I.p1[2 * (size_t)i + 1], I.p2[2 * (size_t)i], I.p2[2 * (size_t)i + 1]);
-  };
   Norm N{};
   N.n = (int32_t)I.n;
   for (uint32_t i = 0; i < I.n; i++) {
-    const Match m = fetch(i);
+    const Match m = match_at(I, i);
     N.sx1 += m.x1, N.sy1 += m.y1, N.sx2 += m.x2, N.sy2 += m.y2;
   }
   long long D1 = 0, D2 = 0;
   for (uint32_t i = 0; i < I.n; i++) {
-    const Match m = fetch(i);
+    const Match m = match_at(I, i);
     D1 += spread(N.n, m.x1, m.y1, N.sx1, N.sy1), D2 += spread(N.n, m.x2, m.y2, N.sx2, N.sy2);
   }
-  long long *st = O->stats;
-  st[0] = N.n, st[1] = N.sx1, st[2] = N.sy1, st[3] = D1, st[4] = N.sx2, st[5] = N.sy2, st[6] = D2, st[7] = 0;
-  O->best = -1, O->score = 0, O->ninliers = 0;
-  for (int i = 0; i < 9; i++) O->model_n[i] = 0.0f;
-  for (uint32_t i = 0; i < I.n; i++) inlier[i] = 0;
-  if (!(I.n >= (uint32_t)sample_size(MODEL) && D1 != 0 && D2 != 0)) return;
-  const float sigma = sigma_px(sigma_q8);
-  N.k1 = scale(N.n, D1), N.k2 = scale(N.n, D2);
-  const float w1 = weight(N.n, N.k1, sigma), w2 = weight(N.n, N.k2, sigma);
-  unsigned long long best = 0;
-  float xb[8] = {0};
-  for (int k = 0; k < hypotheses; k++) {
-    float x[8];
-    if (!hypothesis<MODEL>(N, fetch, seed, I.b, (uint32_t)k, x)) continue;
-    const Model<MODEL> m(x);
-    uint32_t s = 0;
-    for (uint32_t i = 0; i < I.n; i++) {
-      bool inl;
-      s += score<MODEL>(m, point(N, fetch(i)), w1, w2, &inl);
-    }
-    if (s && best_key(s, k) > best) {
-      best = best_key(s, k);
-      for (int i = 0; i < 8; i++) xb[i] = x[i];
-    }
-  }
-  if (!best) return;
-  const Model<MODEL> m(xb);
-  for (uint32_t i = 0; i < I.n; i++) {
-    bool inl;
-    (void)score<MODEL>(m, point(N, fetch(i)), w1, w2, &inl);
-    inlier[i] = inl ? 1 : 0, O->ninliers += inl ? 1u : 0u;
-  }
-  O->best = key_hypothesis(best), O->score = key_score(best);
-  for (int i = 0; i < 9; i++) O->model_n[i] = i < 8 ? xb[i] : 1.0f;
+  stats_row(N, D1, D2, O->stats);
+  float x[8] = {0};
+  const Problem<MODEL> P(I, N, D1, D2, sigma_px(sigma_q8), seed);
+  const prk::Outcome R = prk::host_ransac(P, hypotheses, x, inlier);
+  O->best = R.best, O->score = R.score, O->ninliers = R.ninliers;
+  for (int i = 0; i < 9; i++) O->model_n[i] = R.best < 0 ? 0.0f : i < 8 ? x[i] : 1.0f;
 }
 #endif
 

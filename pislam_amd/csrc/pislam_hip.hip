@@ -1987,6 +1987,22 @@ const char *ranges_overlap(const LkRange (&in)[NI], const LkRange (&out)[NO], in
   return nullptr;
 }
 
+// The level table of the pose, PnP and Sim(3) calls, checked when the call has levels; `needs` opens the caller's text.
+int check_level_table(pislam_ctx *c, const char *needs, const float *inv_sigma2, int nlevels) {
+  if (!inv_sigma2 || nlevels < 1 || nlevels > pq::MAX_LEVELS)
+    return fail(c, PISLAM_ERR_INVALID, (std::string(needs) + " inv_sigma2 with 1..16 entries").c_str());
+  for (int l = 0; l < nlevels; l++)
+    if (!(inv_sigma2[l] > 0.0f) || !psm::finite_f(inv_sigma2[l]))
+      return fail(c, PISLAM_ERR_INVALID, "inv_sigma2 must be finite and > 0");
+  return PISLAM_OK;
+}
+// ... and copied into the kernel's arguments: nlevels is 0 for a call without levels.
+template <class ARGS>
+void copy_level_table(ARGS *a, const float *inv_sigma2, int nlevels) {
+  a->nlevels = nlevels;
+  for (int l = 0; l < nlevels; l++) a->inv_sigma2[l] = inv_sigma2[l];
+}
+
 }  // namespace
 
 PISLAM_EXPORT int pislam_track_lk_batch(pislam_ctx *c, const pislam_lk_params *p, const pislam_level *levels, int nlevels,
@@ -2471,11 +2487,11 @@ PISLAM_EXPORT int pislam_two_view_ransac_batch(pislam_ctx *c, const pislam_two_v
   a.seed = p->seed, a.sigma = pgm::sigma_px(p->sigma_q8);
   a.best = best, a.score = score, a.ninliers = ninliers, a.inlier = inlier, a.model_n = model_n;
   a.stats = (long long *)stats;
-  const dim3 grid((unsigned)std::min(batch, pg::TV_GRID_CAP));
+  const dim3 grid((unsigned)std::min(batch, prk::GRID_CAP));
   if (p->model == 0)
-    hipLaunchKernelGGL(pg::k_two_view<0>, grid, dim3(pg::TV_THREADS), 0, c->stream, a);
+    hipLaunchKernelGGL(pg::k_two_view<0>, grid, dim3(prk::THREADS), 0, c->stream, a);
   else
-    hipLaunchKernelGGL(pg::k_two_view<1>, grid, dim3(pg::TV_THREADS), 0, c->stream, a);
+    hipLaunchKernelGGL(pg::k_two_view<1>, grid, dim3(prk::THREADS), 0, c->stream, a);
   return launch_ok(c, "k_two_view");
 }
 
@@ -2546,13 +2562,7 @@ PISLAM_EXPORT int pislam_pose_refine_batch(pislam_ctx *c, const pislam_pose_para
   if (p->huber_rounds < 0 || p->huber_rounds > p->rounds) return fail(c, PISLAM_ERR_INVALID, "huber_rounds must be 0..rounds");
   if (p->min_obs < 3 || p->min_obs > pq::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "min_obs must be 3..16384");
   if (!(p->eps >= 0.0)) return fail(c, PISLAM_ERR_INVALID, "eps must be >= 0");
-  if (level) {
-    if (!inv_sigma2 || nlevels < 1 || nlevels > pq::MAX_LEVELS)
-      return fail(c, PISLAM_ERR_INVALID, "level needs inv_sigma2 with 1..16 entries");
-    for (int l = 0; l < nlevels; l++)
-      if (!(inv_sigma2[l] > 0.0f) || !pq::finite_f(inv_sigma2[l]))
-        return fail(c, PISLAM_ERR_INVALID, "inv_sigma2 must be finite and > 0");
-  }
+  if (level) PCHK(check_level_table(c, "level needs", inv_sigma2, nlevels));
   if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
   if (stride < 1 || stride > (size_t)pq::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
   if (batch == 0) return PISLAM_OK;
@@ -2571,8 +2581,8 @@ PISLAM_EXPORT int pislam_pose_refine_batch(pislam_ctx *c, const pislam_pose_para
   HIPCHK(c, hipSetDevice(c->device));
   po::PoArgs a{};
   a.pose_in = pose_in, a.cam = cam, a.xw = xw, a.obs = obs_q8, a.level = level, a.counts = counts, a.stride = stride;
-  a.batch = batch, a.nlevels = level ? nlevels : 0;
-  for (int l = 0; l < a.nlevels; l++) a.inv_sigma2[l] = inv_sigma2[l];
+  a.batch = batch;
+  copy_level_table(&a, inv_sigma2, level ? nlevels : 0);
   a.p = pq::Params{p->rounds, p->iters, p->huber_rounds, p->min_obs, p->eps};
   a.pose_out = pose_out, a.inlier = inlier, a.ninliers = ninliers, a.status = status, a.cost = cost;
   hipLaunchKernelGGL(po::k_pose_refine, dim3((unsigned)std::min(batch, po::PO_GRID_CAP)), dim3(po::PO_THREADS), 0,
@@ -2592,13 +2602,7 @@ PISLAM_EXPORT int pislam_pnp_ransac_batch(pislam_ctx *c, const pislam_pnp_params
   if (p->hypotheses < 1 || p->hypotheses > pnm::MAX_HYP) return fail(c, PISLAM_ERR_INVALID, "hypotheses must be 1..1024");
   if (p->min_inliers < pnm::SAMPLE || p->min_inliers > pnm::MAX_STRIDE)
     return fail(c, PISLAM_ERR_INVALID, "min_inliers must be 4..16384");
-  if (level) {
-    if (!inv_sigma2 || nlevels < 1 || nlevels > pnm::MAX_LEVELS)
-      return fail(c, PISLAM_ERR_INVALID, "level needs inv_sigma2 with 1..16 entries");
-    for (int l = 0; l < nlevels; l++)
-      if (!(inv_sigma2[l] > 0.0f) || !psm::finite_f(inv_sigma2[l]))
-        return fail(c, PISLAM_ERR_INVALID, "inv_sigma2 must be finite and > 0");
-  }
+  if (level) PCHK(check_level_table(c, "level needs", inv_sigma2, nlevels));
   if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
   if (stride < 1 || stride > (size_t)pnm::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
   if (batch == 0) return PISLAM_OK;
@@ -2616,10 +2620,10 @@ PISLAM_EXPORT int pislam_pnp_ransac_batch(pislam_ctx *c, const pislam_pnp_params
   HIPCHK(c, hipSetDevice(c->device));
   pn::PnArgs a{};
   a.cam = cam, a.xw = xw, a.obs = obs_q8, a.level = level, a.counts = counts, a.stride = stride, a.batch = batch;
-  a.hypotheses = p->hypotheses, a.nlevels = level ? nlevels : 0, a.min_inliers = p->min_inliers, a.seed = p->seed;
-  for (int l = 0; l < a.nlevels; l++) a.inv_sigma2[l] = inv_sigma2[l];
+  a.hypotheses = p->hypotheses, a.min_inliers = p->min_inliers, a.seed = p->seed;
+  copy_level_table(&a, inv_sigma2, level ? nlevels : 0);
   a.best = best, a.score = score, a.ninliers = ninliers, a.inlier = inlier, a.pose_out = pose_out, a.status = status;
-  hipLaunchKernelGGL(pn::k_pnp_ransac, dim3((unsigned)std::min(batch, pn::PN_GRID_CAP)), dim3(pn::PN_THREADS), 0,
+  hipLaunchKernelGGL(pn::k_pnp_ransac, dim3((unsigned)std::min(batch, prk::GRID_CAP)), dim3(prk::THREADS), 0,
                      c->stream, a);
   return launch_ok(c, "k_pnp_ransac");
 }
@@ -2639,13 +2643,7 @@ PISLAM_EXPORT int pislam_sim3_ransac_batch(pislam_ctx *c, const pislam_sim3_para
     return fail(c, PISLAM_ERR_INVALID, "min_inliers must be 3..16384");
   if (p->fixed_scale != 0 && p->fixed_scale != 1) return fail(c, PISLAM_ERR_INVALID, "fixed_scale must be 0 or 1");
   if ((level1 != nullptr) != (level2 != nullptr)) return fail(c, PISLAM_ERR_INVALID, "level1 and level2 go together");
-  if (level1) {
-    if (!inv_sigma2 || nlevels < 1 || nlevels > s3m::MAX_LEVELS)
-      return fail(c, PISLAM_ERR_INVALID, "levels need inv_sigma2 with 1..16 entries");
-    for (int l = 0; l < nlevels; l++)
-      if (!(inv_sigma2[l] > 0.0f) || !psm::finite_f(inv_sigma2[l]))
-        return fail(c, PISLAM_ERR_INVALID, "inv_sigma2 must be finite and > 0");
-  }
+  if (level1) PCHK(check_level_table(c, "levels need", inv_sigma2, nlevels));
   if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
   if (stride < 1 || stride > (size_t)s3m::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
   if (batch == 0) return PISLAM_OK;
@@ -2666,10 +2664,10 @@ PISLAM_EXPORT int pislam_sim3_ransac_batch(pislam_ctx *c, const pislam_sim3_para
   s3::S3Args a{};
   a.cam1 = cam1, a.cam2 = cam2, a.x1 = x1, a.x2 = x2, a.obs1 = obs1_q8, a.obs2 = obs2_q8, a.level1 = level1;
   a.level2 = level2, a.counts = counts, a.stride = stride, a.batch = batch, a.hypotheses = p->hypotheses;
-  a.nlevels = level1 ? nlevels : 0, a.min_inliers = p->min_inliers, a.fixed_scale = p->fixed_scale, a.seed = p->seed;
-  for (int l = 0; l < a.nlevels; l++) a.inv_sigma2[l] = inv_sigma2[l];
+  a.min_inliers = p->min_inliers, a.fixed_scale = p->fixed_scale, a.seed = p->seed;
+  copy_level_table(&a, inv_sigma2, level1 ? nlevels : 0);
   a.best = best, a.score = score, a.ninliers = ninliers, a.inlier = inlier, a.sim_out = sim_out, a.status = status;
-  hipLaunchKernelGGL(s3::k_sim3_ransac, dim3((unsigned)std::min(batch, s3::S3_GRID_CAP)), dim3(s3::S3_THREADS), 0,
+  hipLaunchKernelGGL(s3::k_sim3_ransac, dim3((unsigned)std::min(batch, prk::GRID_CAP)), dim3(prk::THREADS), 0,
                      c->stream, a);
   return launch_ok(c, "k_sim3_ransac");
 }
@@ -2693,13 +2691,7 @@ PISLAM_EXPORT int pislam_sim3_refine_batch(pislam_ctx *c, const pislam_sim3_refi
   if (p->fixed_scale != 0 && p->fixed_scale != 1) return fail(c, PISLAM_ERR_INVALID, "fixed_scale must be 0 or 1");
   if (!(p->eps >= 0.0)) return fail(c, PISLAM_ERR_INVALID, "eps must be >= 0");
   if ((level1 != nullptr) != (level2 != nullptr)) return fail(c, PISLAM_ERR_INVALID, "level1 and level2 go together");
-  if (level1) {
-    if (!inv_sigma2 || nlevels < 1 || nlevels > s3r::MAX_LEVELS)
-      return fail(c, PISLAM_ERR_INVALID, "levels need inv_sigma2 with 1..16 entries");
-    for (int l = 0; l < nlevels; l++)
-      if (!(inv_sigma2[l] > 0.0f) || !psm::finite_f(inv_sigma2[l]))
-        return fail(c, PISLAM_ERR_INVALID, "inv_sigma2 must be finite and > 0");
-  }
+  if (level1) PCHK(check_level_table(c, "levels need", inv_sigma2, nlevels));
   if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
   if (stride < 1 || stride > (size_t)s3r::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
   if (batch == 0) return PISLAM_OK;
@@ -2722,8 +2714,7 @@ PISLAM_EXPORT int pislam_sim3_refine_batch(pislam_ctx *c, const pislam_sim3_refi
   sr::SrArgs a{};
   a.sim_in = sim_in, a.cam1 = cam1, a.cam2 = cam2, a.x1 = x1, a.x2 = x2, a.obs1 = obs1_q8, a.obs2 = obs2_q8;
   a.level1 = level1, a.level2 = level2, a.mask = mask, a.counts = counts, a.stride = stride, a.batch = batch;
-  a.nlevels = level1 ? nlevels : 0;
-  for (int l = 0; l < a.nlevels; l++) a.inv_sigma2[l] = inv_sigma2[l];
+  copy_level_table(&a, inv_sigma2, level1 ? nlevels : 0);
   a.p = s3r::Params{p->rounds, p->iters, p->huber_rounds, p->min_obs, p->th2, p->fixed_scale, p->eps};
   a.sim_out = sim_out, a.inlier = inlier, a.ninliers = ninliers, a.status = status, a.cost = cost;
   hipLaunchKernelGGL(sr::k_sim3_refine, dim3((unsigned)std::min(batch, sr::SR_GRID_CAP)), dim3(sr::SR_THREADS), 0,

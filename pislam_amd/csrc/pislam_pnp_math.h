@@ -1,11 +1,12 @@
 // pislam_pnp_math.h — the arithmetic of pislam_pnp_ransac_batch (include/pislam_hip.h: that comment is the contract),
 // stated ONCE for the device kernel (pislam_pnp_kernels.h) and for a plain C++ compiler (tools/probes/
 // pnp_host_check.cpp): the camera test, an observation as the call reads it, its chi2 and score under a pose, the
-// bearing, the P3P solver (Lambda Twist: Persson & Nordberg, ECCV 2018) with the choice among its solutions, and, for
-// the host only, the whole call for one frame run serially.  The sampler, the best-of rule and the observation's
-// constants are those of pislam_geom_math.h and pislam_pose_math.h.  Every operation is written out one rounding at a
-// time; build with -ffp-contract=off.  Static indices only: the solver keeps a running best over its (at most four)
-// solutions and never indexes an array with a runtime value, so on the device it stays in VGPRs.
+// bearing, the P3P solver (Lambda Twist: Persson & Nordberg, ECCV 2018) with the choice among its solutions, the frame
+// as the RANSAC skeleton sees it (pislam_ransac_math.h) and, for the host only, the whole call for one frame run
+// serially.  The sampler and the observation's constants are those of pislam_geom_math.h and pislam_pose_math.h.
+// Every operation is written out one rounding at a time; build with -ffp-contract=off.  Static indices only: the solver
+// keeps a running best over its (at most four) solutions and never indexes an array with a runtime value, so on the
+// device it stays in VGPRs.
 #pragma once
 #include "pislam_geom_math.h"
 #include "pislam_pose_math.h"
@@ -275,9 +276,7 @@ PISLAM_HD bool hypothesis(const Cam &C, const FETCH &fetch, uint32_t n, uint32_t
   return solve(C, fetch(draw[0]), fetch(draw[1]), fetch(draw[2]), fetch(draw[3]), T);
 }
 
-#if !defined(__HIP_DEVICE_COMPILE__)
-// ---- the host's serial form of the whole call for one frame (the probe; never the library's hot path) ---------------
-
+// One frame as the call reads it.
 struct Frame {
   const float *cam, *xw;                       // [5], [n][3]
   const int32_t *obs;                          // [n][3]
@@ -287,6 +286,35 @@ struct Frame {
   uint32_t n;                                  // already psm::clamp_count(count, stride)
   uint32_t b;                                  // the frame's index in the batch: the sampler hashes it
 };
+
+// The frame as the RANSAC skeleton sees it (pislam_ransac_math.h).
+struct Problem {
+  static constexpr int WORDS = 12;
+  using Item = Obs;
+  Frame F;
+  Cam C;
+  uint32_t seed, n;
+  bool cam_ok, have;
+  PISLAM_HD Problem(const Frame &F_, uint32_t seed_) : F(F_), seed(seed_), n(F_.n) {
+    float cam[5];
+PISLAM_UNROLL
+    for (int i = 0; i < 5; i++) cam[i] = F.cam[i];
+    cam_ok = pnm::cam_ok(cam), C = make_cam(cam);
+    have = cam_ok && n >= (uint32_t)SAMPLE;
+  }
+  PISLAM_HD Obs item(uint32_t i) const {
+    return obs(F.xw + 3 * (size_t)i, F.obs + 3 * (size_t)i, F.level ? F.level + i : nullptr, F.inv_sigma2, F.nlevels);
+  }
+  PISLAM_HD bool hypothesis(uint32_t k, float (&T)[12]) const {
+    const Problem &P = *this;
+    return pnm::hypothesis(C, [&P](uint32_t i) { return P.item(i); }, n, seed, F.b, k, T);
+  }
+  PISLAM_HD uint32_t score(const float (&T)[12], const Obs &o, bool *inl) const { return pnm::score(T, C, o, inl); }
+};
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// ---- the host's serial form of the whole call for one frame (the probe; never the library's hot path) ---------------
+
 struct Result {
   int32_t best;
   uint32_t score, ninliers, status;
@@ -294,46 +322,11 @@ struct Result {
 };
 
 inline void host_frame(const Frame &F, int hypotheses, uint32_t seed, int min_inliers, Result *R, uint8_t *inlier) {
-  R->best = -1, R->score = 0, R->ninliers = 0;
-  for (int i = 0; i < 12; i++) R->pose[i] = 0.0f;
-  for (uint32_t i = 0; i < F.n; i++) inlier[i] = 0;
-  if (!cam_ok(F.cam)) {
-    R->status = 3;
-    return;
-  }
-  R->status = 2;
-  if (F.n < (uint32_t)SAMPLE) return;
-  const Cam C = make_cam(F.cam);
-  const auto fetch = [&F](uint32_t i) {
-    return obs(F.xw + 3 * (size_t)i, F.obs + 3 * (size_t)i, F.level ? F.level + i : nullptr, F.inv_sigma2, F.nlevels);
-  };
-  unsigned long long best = 0;
-  uint32_t valid = 0;
-  float Tb[12] = {0};
-  for (int k = 0; k < hypotheses; k++) {
-    float T[12];
-    if (!hypothesis(C, fetch, F.n, seed, F.b, (uint32_t)k, T)) continue;
-    valid++;
-    uint32_t s = 0;
-    for (uint32_t i = 0; i < F.n; i++) {
-      bool inl;
-      s += score(T, C, fetch(i), &inl);
-    }
-    if (s && pgm::best_key(s, k) > best) {
-      best = pgm::best_key(s, k);
-      for (int i = 0; i < 12; i++) Tb[i] = T[i];
-    }
-  }
-  R->status = 2u | valid << 8;
-  if (!best) return;
-  for (uint32_t i = 0; i < F.n; i++) {
-    bool inl;
-    (void)score(Tb, C, fetch(i), &inl);
-    inlier[i] = inl ? 1 : 0, R->ninliers += inl ? 1u : 0u;
-  }
-  R->best = pgm::key_hypothesis(best), R->score = pgm::key_score(best);
-  for (int i = 0; i < 12; i++) R->pose[i] = Tb[i];
-  R->status = (R->ninliers < (uint32_t)min_inliers ? 1u : 0u) | valid << 8;
+  const Problem P(F, seed);
+  float T[12] = {0};
+  const prk::Outcome O = prk::host_ransac(P, hypotheses, T, inlier);
+  R->best = O.best, R->score = O.score, R->ninliers = O.ninliers, R->status = prk::status(O, P.cam_ok, min_inliers);
+  for (int i = 0; i < 12; i++) R->pose[i] = O.best < 0 ? 0.0f : T[i];
 }
 #endif
 

@@ -1,11 +1,12 @@
 // pislam_sim3_math.h — the arithmetic of pislam_sim3_ransac_batch (include/pislam_hip.h: that comment is the contract),
 // stated ONCE for the device kernel (pislam_sim3_kernels.h) and for a plain C++ compiler (tools/probes/
 // sim3_host_check.cpp): the camera test, a match as the call reads it, Horn's closed-form absolute orientation on three
-// points with its 4 x 4 eigenvector by cyclic Jacobi, the two-sided chi2 and score of a match under a similarity, and,
-// for the host only, the whole call for one pair run serially.  The sampler, the best-of rule and the observation's
-// constants are those of pislam_geom_math.h and pislam_pose_math.h.  Every operation is written out one rounding at a
-// time; build with -ffp-contract=off.  Static indices only: the Jacobi pivots are template parameters and the choice of
-// the eigenvector is a running best, so on the device the solver stays in VGPRs.
+// points with its 4 x 4 eigenvector by cyclic Jacobi, the two-sided chi2 and score of a match under a similarity, the
+// pair as the RANSAC skeleton sees it (pislam_ransac_math.h) and, for the host only, the whole call for one pair run
+// serially.  The sampler and the observation's constants are those of pislam_geom_math.h and pislam_pose_math.h.
+// Every operation is written out one rounding at a time; build with -ffp-contract=off.  Static indices only: the Jacobi
+// pivots are template parameters and the choice of the eigenvector is a running best, so on the device the solver
+// stays in VGPRs.
 #pragma once
 #include "pislam_geom_math.h"
 #include "pislam_pose_math.h"
@@ -222,9 +223,7 @@ PISLAM_HD uint32_t score(const float (&S)[WORDS], const Cam &C1, const Cam &C2, 
   return (uint32_t)floorf((TH - c1) * 256.0f) + (uint32_t)floorf((TH - c2) * 256.0f);
 }
 
-#if !defined(__HIP_DEVICE_COMPILE__)
-// ---- the host's serial form of the whole call for one pair (the probe; never the library's hot path) ----------------
-
+// One pair as the call reads it.
 struct Pair {
   const float *cam1, *cam2, *x1, *x2;          // [5], [5], [n][3], [n][3]
   const int32_t *obs1, *obs2;                  // [n][3]
@@ -234,6 +233,39 @@ struct Pair {
   uint32_t n;                                  // already psm::clamp_count(count, stride)
   uint32_t b;                                  // the pair's index in the batch: the sampler hashes it
 };
+
+// The pair as the RANSAC skeleton sees it (pislam_ransac_math.h).
+struct Problem {
+  static constexpr int WORDS = s3m::WORDS;
+  using Item = Match;
+  Pair F;
+  Cam C1, C2;
+  uint32_t seed, n;
+  bool fixed_scale, cam_ok, have;
+  PISLAM_HD Problem(const Pair &F_, uint32_t seed_, bool fixed_scale_)
+      : F(F_), seed(seed_), n(F_.n), fixed_scale(fixed_scale_) {
+    float cam1[5], cam2[5];
+PISLAM_UNROLL
+    for (int i = 0; i < 5; i++) cam1[i] = F.cam1[i], cam2[i] = F.cam2[i];
+    cam_ok = s3m::cam_ok(cam1) && s3m::cam_ok(cam2), C1 = make_cam(cam1), C2 = make_cam(cam2);
+    have = cam_ok && n >= (uint32_t)SAMPLE;
+  }
+  PISLAM_HD Match item(uint32_t i) const {
+    return match(F.x1 + 3 * (size_t)i, F.x2 + 3 * (size_t)i, F.obs1 + 3 * (size_t)i, F.obs2 + 3 * (size_t)i,
+                 F.level1 ? F.level1 + i : nullptr, F.level1 ? F.level2 + i : nullptr, F.inv_sigma2, F.nlevels);
+  }
+  PISLAM_HD bool hypothesis(uint32_t k, float (&S)[WORDS]) const {
+    const Problem &P = *this;
+    return s3m::hypothesis([&P](uint32_t i) { return P.item(i); }, n, seed, F.b, k, fixed_scale, S);
+  }
+  PISLAM_HD uint32_t score(const float (&S)[WORDS], const Match &m, bool *inl) const {
+    return s3m::score(S, C1, C2, m, inl);
+  }
+};
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// ---- the host's serial form of the whole call for one pair (the probe; never the library's hot path) ----------------
+
 struct Result {
   int32_t best;
   uint32_t score, ninliers, status;
@@ -242,47 +274,11 @@ struct Result {
 
 inline void host_pair(const Pair &F, int hypotheses, uint32_t seed, int min_inliers, bool fixed_scale, Result *R,
                       uint8_t *inlier) {
-  R->best = -1, R->score = 0, R->ninliers = 0;
-  for (int i = 0; i < OUT_WORDS; i++) R->sim[i] = 0.0f;
-  for (uint32_t i = 0; i < F.n; i++) inlier[i] = 0;
-  if (!cam_ok(F.cam1) || !cam_ok(F.cam2)) {
-    R->status = 3;
-    return;
-  }
-  R->status = 2;
-  if (F.n < (uint32_t)SAMPLE) return;
-  const Cam C1 = make_cam(F.cam1), C2 = make_cam(F.cam2);
-  const auto fetch = [&F](uint32_t i) {
-    return match(F.x1 + 3 * (size_t)i, F.x2 + 3 * (size_t)i, F.obs1 + 3 * (size_t)i, F.obs2 + 3 * (size_t)i,
-                 F.level1 ? F.level1 + i : nullptr, F.level1 ? F.level2 + i : nullptr, F.inv_sigma2, F.nlevels);
-  };
-  unsigned long long best = 0;
-  uint32_t valid = 0;
-  float Sb[WORDS] = {0};
-  for (int k = 0; k < hypotheses; k++) {
-    float S[WORDS];
-    if (!hypothesis(fetch, F.n, seed, F.b, (uint32_t)k, fixed_scale, S)) continue;
-    valid++;
-    uint32_t s = 0;
-    for (uint32_t i = 0; i < F.n; i++) {
-      bool inl;
-      s += score(S, C1, C2, fetch(i), &inl);
-    }
-    if (s && pgm::best_key(s, k) > best) {
-      best = pgm::best_key(s, k);
-      for (int i = 0; i < WORDS; i++) Sb[i] = S[i];
-    }
-  }
-  R->status = 2u | valid << 8;
-  if (!best) return;
-  for (uint32_t i = 0; i < F.n; i++) {
-    bool inl;
-    (void)score(Sb, C1, C2, fetch(i), &inl);
-    inlier[i] = inl ? 1 : 0, R->ninliers += inl ? 1u : 0u;
-  }
-  R->best = pgm::key_hypothesis(best), R->score = pgm::key_score(best);
-  for (int i = 0; i < OUT_WORDS; i++) R->sim[i] = Sb[i];
-  R->status = (R->ninliers < (uint32_t)min_inliers ? 1u : 0u) | valid << 8;
+  const Problem P(F, seed, fixed_scale);
+  float S[WORDS] = {0};
+  const prk::Outcome O = prk::host_ransac(P, hypotheses, S, inlier);
+  R->best = O.best, R->score = O.score, R->ninliers = O.ninliers, R->status = prk::status(O, P.cam_ok, min_inliers);
+  for (int i = 0; i < OUT_WORDS; i++) R->sim[i] = O.best < 0 ? 0.0f : S[i];
 }
 #endif
 

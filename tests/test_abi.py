@@ -201,6 +201,15 @@ def test_compiler_resources_of_the_two_measured_kernels(tmp_path):
     gather = rows["void pf::k_gather_orb<false>"]
     assert 73 <= int(gather["VGPRs"]) <= 80 and int(gather["ScratchSize [bytes/lane]"]) == 0, gather
     assert int(gather["VGPRs Spill"]) == 0 and int(gather["SGPRs Spill"]) == 0, gather
+    # The RANSAC kernels share one skeleton (pislam_ransac_kernels.h); each keeps what it had as a kernel of its own:
+    # (waves per SIMD, spilled SGPRs, bytes of LDS), no private segment, no spilled VGPR.
+    ransac = {"void pg::k_two_view<0>": (3, 0, 37952), "void pg::k_two_view<1>": (4, 0, 37952),
+              "pn::k_pnp_ransac": (3, 0, 54288), "s3::k_sim3_ransac": (3, 4, 70672)}
+    for name, (waves, sgpr_spill, lds) in ransac.items():
+        r = rows[name]
+        assert int(r["Occupancy [waves/SIMD]"]) == waves, (name, r)
+        assert int(r["ScratchSize [bytes/lane]"]) == 0 and int(r["VGPRs Spill"]) == 0, (name, r)
+        assert int(r["SGPRs Spill"]) <= sgpr_spill and int(r["LDS Size [bytes/block]"]) <= lds, (name, r)
 
 
 def test_debug_build_plan_reports_the_strip_plan_without_a_device():

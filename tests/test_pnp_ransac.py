@@ -454,7 +454,7 @@ def test_ref_pnp_anchors():
 
 # ---- the pin cases: the smallest shapes where the kernel can go wrong -------------------------------------------------
 PIN_STRIDE = 96
-PIN_HYPOTHESES = (1, 63, 64, 65, 200, 1024)
+PIN_HYPOTHESES = (1, 63, 64, 65, 200, 512, 513, 1024)   # 512 / 513: the hypothesis loop's second trip
 PIN_SEED, PIN_MIN = 5, 10
 
 
@@ -671,6 +671,31 @@ def test_pnp_pins(gpu_ctx, hypotheses, with_level):
     got = Device(gpu_ctx).run(frames, [c for _, _, c in cases], PIN_STRIDE, (hypotheses, PIN_SEED, PIN_MIN), with_level)
     want = pin_reference(hypotheses, with_level)
     assert_frames(got, want, [len(f["obs"]) for f in frames], "h%d" % hypotheses)
+
+
+TRIP_HYPOTHESES, TRIP_NS = 65, (512, 513)
+
+
+@functools.lru_cache(maxsize=None)
+def second_trip_case():
+    """Frames of 512 and 513 observations with levels: a workgroup scores 64 x 8 waves = 512 per trip, so the 513th is
+    the scoring and the mask loop's second trip.  (frames, the restated results)."""
+    big = scene(27, n=TRIP_NS[-1], outliers=0.3, levels=True)[0]
+    frames = [sub(big, n) for n in TRIP_NS]
+    return frames, [ref_frame(fr, b, TRIP_HYPOTHESES, PIN_SEED, PIN_MIN) for b, fr in enumerate(frames)]
+
+
+def test_second_trip_case_has_models():
+    for w in second_trip_case()[1]:
+        assert w["best"] >= 0 and w["status"] & 255 == 0 and w["ninliers"] > 200
+    assert second_trip_case()[1][1]["inlier"][512] == 1                       # the 513th is an inlier of its frame
+
+
+@pytest.mark.gpu
+def test_pnp_second_trip_of_the_item_loops(gpu_ctx):
+    frames, want = second_trip_case()
+    got = Device(gpu_ctx).run(frames, list(TRIP_NS), TRIP_NS[-1], (TRIP_HYPOTHESES, PIN_SEED, PIN_MIN))
+    assert_frames(got, want, list(TRIP_NS), "second trip")
 
 
 @pytest.mark.gpu

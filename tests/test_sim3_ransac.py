@@ -813,6 +813,31 @@ def test_sim3_pins(gpu_ctx, hypotheses, with_level, fixed):
     assert_pairs(got, want, [len(f["obs1"]) for f in pairs], "h%d" % hypotheses)
 
 
+TRIP_HYPOTHESES, TRIP_NS = 65, (512, 513)
+
+
+@functools.lru_cache(maxsize=None)
+def second_trip_case():
+    """Pairs of 512 and 513 matches with levels: a workgroup scores 64 x 8 waves = 512 per trip, so the 513th is the
+    scoring and the mask loop's second trip.  (pairs, the restated results)."""
+    big = scene(27, n=TRIP_NS[-1], outliers=0.3, levels=True)[0]
+    pairs = [sub(big, n) for n in TRIP_NS]
+    return pairs, [ref_pair(pr, b, TRIP_HYPOTHESES, PIN_SEED, PIN_MIN) for b, pr in enumerate(pairs)]
+
+
+def test_second_trip_case_has_models():
+    for w in second_trip_case()[1]:
+        assert w["best"] >= 0 and w["status"] & 255 == 0 and w["ninliers"] > 200
+    assert second_trip_case()[1][1]["inlier"][512] == 1                       # the 513th is an inlier of its pair
+
+
+@pytest.mark.gpu
+def test_sim3_second_trip_of_the_item_loops(gpu_ctx):
+    pairs, want = second_trip_case()
+    got = Device(gpu_ctx).run(pairs, list(TRIP_NS), TRIP_NS[-1], (TRIP_HYPOTHESES, PIN_SEED, PIN_MIN, 0))
+    assert_pairs(got, want, list(TRIP_NS), "second trip")
+
+
 @pytest.mark.gpu
 def test_sim3_degenerate_inputs(gpu_ctx):
     d = Device(gpu_ctx)

@@ -509,6 +509,7 @@ def assert_same(got, want, what=""):
 
 
 PIN_STRIDE = 320
+PIN_HYPOTHESES = (1, 63, 64, 65, 200, 512, 513, 1024)       # 512 / 513: the hypothesis loop's second trip
 
 
 @functools.lru_cache(maxsize=None)
@@ -563,7 +564,7 @@ def test_host_probe_against_the_restatement(tmp_path):
                            os.path.join(ROOT, "tools", "probes", "ransac_host_check.cpp"), "-o", exe])
     lines, want = [], []
     for model in (FUND, HOMOG):
-        for hypotheses in (1, 63, 64, 65, 200, 1024):
+        for hypotheses in PIN_HYPOTHESES:
             small = hypotheses not in (64, 200)                                       # as in test_two_view_pins
             p1, p2, counts = pin_batch(model, small)
             r = pin_reference(model, hypotheses, small)
@@ -578,13 +579,13 @@ def test_host_probe_against_the_restatement(tmp_path):
     cases = tmp_path / "cases.txt"
     cases.write_text("\n".join(lines) + "\n")
     got = subprocess.run([exe, str(cases)], check=True, capture_output=True, text=True).stdout.splitlines()
-    assert len(got) == len(want) == 2 * (4 * 3 + 2 * 14)
+    assert len(got) == len(want) == 2 * (6 * 3 + 2 * 14)
     for k, (g, w) in enumerate(zip(got, want)):
         assert g == w, "case %d: %s" % (k, lines[k][:60])
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("hypotheses", [1, 63, 64, 65, 200, 1024])
+@pytest.mark.parametrize("hypotheses", PIN_HYPOTHESES)
 @pytest.mark.parametrize("model", [FUND, HOMOG])
 def test_two_view_pins(gpu_ctx, model, hypotheses):
     """Every output word of the library equals the restatement's; what a call must not write keeps the sentinel."""
@@ -601,6 +602,38 @@ def test_two_view_pins(gpu_ctx, model, hypotheses):
         if hypotheses == 200:
             assert (want["best"][[3, 4, 5, 6, 7, 12]] >= 0).all() and want["ninliers"][7] > 150
             assert want["best"][13] >= 0                                  # the clamped pair still has a model
+
+
+TRIP_HYPOTHESES, TRIP_NS = 65, (512, 513)
+
+
+@functools.lru_cache(maxsize=None)
+def second_trip_case(model):
+    """Pairs of 512 and 513 matches: a workgroup scores 64 x 8 waves = 512 per trip, so the 513th is the scoring and the
+    mask loop's second trip.  (p1, p2, counts, the restated outputs); the stride is just large enough."""
+    u, v, good = scene(51, model == HOMOG, n=TRIP_NS[-1])
+    assert good[512]                                                          # the scene's 513th match is a true one
+    rng = np.random.default_rng(78)
+    p1 = rng.integers(-(1 << 31), 1 << 31, (2, TRIP_NS[-1], 2)).astype(np.int64)      # garbage beyond the counts
+    p2 = rng.integers(-(1 << 31), 1 << 31, (2, TRIP_NS[-1], 2)).astype(np.int64)
+    for b, n in enumerate(TRIP_NS):
+        p1[b, :n], p2[b, :n] = u[:n], v[:n]
+    counts = np.array(TRIP_NS, np.int64)
+    return p1, p2, counts, ref_batch(p1, p2, counts, model, TRIP_HYPOTHESES, 12345, 256)
+
+
+@pytest.mark.parametrize("model", [FUND, HOMOG])
+def test_second_trip_case_has_models(model):
+    want = second_trip_case(model)[3]
+    assert (want["best"] >= 0).all() and (want["ninliers"] > 200).all()
+    assert want["inlier"][0, 512] == SENT8 and want["inlier"][1, 512] == 1    # the 513th is an inlier of its pair
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("model", [FUND, HOMOG])
+def test_two_view_second_trip_of_the_item_loops(gpu_ctx, model):
+    p1, p2, counts, want = second_trip_case(model)
+    assert_same(Device(gpu_ctx).run(p1, p2, counts, model, TRIP_HYPOTHESES, 12345, 256), want, (model, "second trip"))
 
 
 @pytest.mark.gpu
