@@ -582,6 +582,106 @@ int pislam_match_hamming_scaled_window_batch(pislam_ctx *ctx, int words,
                                              const uint32_t *tkp, const uint32_t *tdesc, const uint32_t *tcounts,
                                              size_t t_stride, int batch, int32_t *idx, uint32_t *dist, uint32_t *dist2);
 
+/* Map-point search by projection, after ORB-SLAM's
+ * ORBmatcher::SearchByProjection (TrackWithMotionModel, TrackLocalMap,
+ * relocalisation): the queries are 3D map points with a descriptor each, the
+ * train side is a frame's keypoints.  Pair b is one frame.  The train side
+ * (tkp, tdesc, tcounts, t_stride, levels, nlevels, scale_q16), the counts
+ * (min(count, stride), PISLAM_COUNT_INVALID as 0), the level of a train
+ * position and its Q16 mapping to level 0 (Xt, Yt) are exactly those of
+ * pislam_match_hamming_scaled_window_batch.  Query side, per pair b:
+ *   pose    float [batch][12]   r0..r8 row-major, then t: Xc = R Xw + t (the
+ *                               pose_in of pislam_pose_refine_batch)
+ *   cam     float [batch][5]    fx, fy, cx, cy, bf; bf is read for finiteness
+ *                               only
+ *   xw      float [batch][q_stride][3]      map points
+ *   qdesc   uint32 [batch][q_stride][words]
+ *   qcounts uint32 [batch]                  nq_b = min(qcounts[b], q_stride)
+ * and the query's level from exactly one of two modes:
+ *   map mode    drange float [batch][q_stride][2] = (dmin, dmax) is given and
+ *               qlevel is NULL; normal float [batch][q_stride][3] is optional.
+ *   level mode  qlevel uint8 [batch][q_stride] is given, drange and normal
+ *               are NULL (the motion model, or any caller that knows the level).
+ * Host tables of nlevels entries, read during the call and carried by value in
+ * the kernel arguments (a captured graph keeps its own copy): level_scale
+ * float (ORB-SLAM's mvScaleFactors), radius_far and radius_near int32 in
+ * level-0 pixels; radius_near may be NULL, which means radius_far.
+ *
+ * A pair whose 12 pose words or 5 cam words are not all finite, or whose fx
+ * or fy is 0, has every query dead.  Otherwise, per query i < nq_b, in
+ * binary32 with one rounding per written operation, in this order (R = pose
+ * words 0..8 row-major, t = words 9..11, (X, Y, Z) = xw):
+ *  1. x = ((R0*X + R1*Y) + R2*Z) + t0,  y = ((R3*X + R4*Y) + R5*Z) + t1,
+ *     z = ((R6*X + R7*Y) + R8*Z) + t2.  Dead unless z >= 2^-10.
+ *     iz = 1.0f / z,  pu = fx*(x*iz) + cx,  pv = fy*(y*iz) + cy.
+ *  2. Dead unless pu >= min_x & pu <= max_x & pv >= min_y & pv <= max_y
+ *     (a NaN fails).  Centre xc = (int32)floorf(pu + 0.5f),
+ *     yc = (int32)floorf(pv + 0.5f).
+ *  3. Map mode only: d = sqrt((x*x + y*y) + z*z), correctly rounded.  Dead
+ *     unless dmin <= d & d <= dmax.
+ *  4. Only with normal n: nc_k = (R[3k]*n0 + R[3k+1]*n1) + R[3k+2]*n2,
+ *     c = (x*nc0 + y*nc1) + z*nc2.  Dead unless c >= cos_min * d; NEAR when
+ *     c > cos_near * d.  (No division and no camera centre: |Xc| is the
+ *     distance to it.)  Without normal there is no test and no query is near.
+ *  5. Predicted level.  Map mode: pl = the number of l in 0 .. nlevels - 2
+ *     with d * level_scale[l] < dmax (ORB-SLAM's ceil(log(dmax / d) / log s)
+ *     clamped to the level range, without a logarithm).  Level mode:
+ *     pl = qlevel[i]; dead when pl >= nlevels.
+ *  6. r = near ? radius_near[pl] : radius_far[pl].
+ *  7. Train j on level lt is a candidate when pl - level_below <= lt <=
+ *     pl + level_above, |xc - Xt| <= r and |yc - Yt| <= r.
+ *  8. idx, dist, dist2 as the scaled matcher writes them, restricted to these
+ *     candidates: best and second on dist << 16 | j (ties: the smallest train
+ *     index), idx -1 and dist 0xffffffff without candidates, dist2 0xffffffff
+ *     with fewer than 2.  With second_same_level 1, dist2 is 0xffffffff when
+ *     the runner-up's level differs from the best's (ORB-SLAM applies the
+ *     ratio test within a level only), so pislam_match_select_batch can be
+ *     used as it is.  pred int32 [batch][q_stride][2] = (xc, yc) and plevel
+ *     uint8 [batch][q_stride] = pl (ORB-SLAM's "visible" flag: 0xff for a dead
+ *     query) may each be NULL.  A dead query writes idx -1, dist and dist2
+ *     0xffffffff, pred (0, 0), plevel 0xff.  Entries at and beyond nq_b are
+ *     not written.
+ * No float is summed across queries: the results are bit-for-bit reproducible
+ * and independent of the launch shape.
+ *
+ * Limits: words in {1,2,4,8}; levels, nlevels, scale_q16 and t_stride as the
+ * scaled matcher's; radius_far / radius_near 0..65535; level_scale finite,
+ * level_scale[0] > 0, non-decreasing; min_x, max_x, min_y, max_y finite, within
+ * +-2^20, min <= max; level_below, level_above 0..nlevels-1; second_same_level
+ * 0 or 1; cos_min, cos_near any value; q_stride < 2^31.  Offsets use size_t
+ * arithmetic throughout.  Any violation, both or neither of drange / qlevel,
+ * normal with qlevel, or a host pointer where a device pointer is required:
+ * PISLAM_ERR_INVALID, before anything is launched or written.  Device pointers
+ * only, except levels, scale_q16, level_scale, radius_far, radius_near and p
+ * (host, read during the call).  Asynchronous on the context stream; the
+ * workspace is the context's own for this call (not the scaled matcher's) and
+ * grows on demand, which synchronises; after pislam_match_projection_reserve
+ * of the same or a larger shape the call allocates nothing and never
+ * synchronises, so it can be captured into a hipGraph.
+ *
+ * Not here: the stereo right-coordinate test of SearchByProjection, Fuse's
+ * replacement of map points, and the rotation histogram, which
+ * pislam_match_select_batch applies from angles. */
+typedef struct pislam_projection_params {
+  float min_x, max_x, min_y, max_y; /* image bounds of pu, pv (ORB-SLAM: mnMinX ..) */
+  float cos_min;                    /* viewing-angle limit (ORB-SLAM: 0.5) */
+  float cos_near;                   /* above it the near radius applies (ORB-SLAM: 0.998) */
+  int32_t level_below;              /* 0..nlevels-1 (local map: 1) */
+  int32_t level_above;              /* 0..nlevels-1 (local map: 0) */
+  int32_t second_same_level;        /* 0 / 1 */
+} pislam_projection_params;
+int pislam_match_projection_reserve(pislam_ctx *ctx, int words, const pislam_level *levels, int nlevels,
+                                    const int32_t *scale_q16, const int32_t *radius_far, const int32_t *radius_near,
+                                    int level_below, int level_above, size_t t_stride, int batch);
+int pislam_match_projection_batch(pislam_ctx *ctx, int words, const pislam_level *levels, int nlevels,
+                                  const int32_t *scale_q16, const float *level_scale, const int32_t *radius_far,
+                                  const int32_t *radius_near, const pislam_projection_params *p, const float *pose,
+                                  const float *cam, const float *xw, const float *normal, const float *drange,
+                                  const uint8_t *qlevel, const uint32_t *qdesc, const uint32_t *qcounts, size_t q_stride,
+                                  const uint32_t *tkp, const uint32_t *tdesc, const uint32_t *tcounts, size_t t_stride,
+                                  int batch, int32_t *idx, uint32_t *dist, uint32_t *dist2, int32_t *pred,
+                                  uint8_t *plevel);
+
 /* Rectified stereo matching: left <-> right
  * correspondences of rectified stereo pairs with an SAD sub-pixel refinement,
  * after ORB-SLAM2's Frame::ComputeStereoMatches, stated in integers.  Pair b

@@ -76,6 +76,11 @@ class Sim3RefineParams(ctypes.Structure):
                 ("eps", ctypes.c_double)]
 
 
+class ProjectionParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_float) for n in ("min_x", "max_x", "min_y", "max_y", "cos_min", "cos_near")] + [
+        (n, ctypes.c_int32) for n in ("level_below", "level_above", "second_same_level")]
+
+
 class ClaheParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "tiles_x", "tiles_y", "clip_q8")]
 
@@ -148,6 +153,13 @@ SYMBOLS = {
     "pislam_match_hamming_scaled_window_batch": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),
                                                       ctypes.POINTER(ctypes.c_int32), _i, _vp, _vp, _vp, _vp, _sz, _vp,
                                                       _vp, _vp, _sz, _i, _vp, _vp, _vp]),
+    "pislam_match_projection_reserve": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),
+                                             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), _i, _i, _sz,
+                                             _i]),
+    "pislam_match_projection_batch": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),
+                                           ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),
+                                           ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ProjectionParams), _vp, _vp, _vp,
+                                           _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
     "pislam_match_stereo_reserve": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),
                                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(StereoParams), _sz, _i]),
     "pislam_match_stereo_batch": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),

@@ -54,6 +54,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 
 #include "pislam_prep_kernels.h"
 #include "pislam_match_kernels.h"
+#include "pislam_project_kernels.h"
 #include "pislam_track_kernels.h"
 #include "pislam_bow_kernels.h"
 #include "pislam_bowdb_kernels.h"
@@ -125,11 +126,11 @@ struct pislam_ctx {
   DevBuf w_score, w_stage, w_stripcnt, w_work, w_prof, w_ovf, w_stagedesc;
   DevBuf w_ustage, w_ucount;         // bucket selection pass (pf::k_bucket_select): per-unit lists and counts
   // Guided matchers: pm::k_scaled_index's cell offsets, cell-sorted train entries and their descriptors.  One set per
-  // matcher (windowed, scaled, stereo), so a graph captured for one is never invalidated by another's reserve.
+  // matcher (windowed, scaled, stereo, projection), so a graph captured for one is never invalidated by another's reserve.
   struct CellIndex {
     DevBuf off, meta, desc;
   };
-  CellIndex w_win, w_sc, w_st;
+  CellIndex w_win, w_sc, w_st, w_proj;   // (w_proj: the projection matcher)
   CellIndex w_bow;                   // word-guided matcher (pb::k_bow_index): group offsets, group-sorted indices (meta), descriptors
   DevBuf w_db;                       // key-frame database query (pd::k_db_accumulate .. k_db_merge): accumulator planes, maxima, partial lists
   // Host-built plan tables the kernels read instead of walking the plan (the bucket selection pass's unit table): one
@@ -506,7 +507,7 @@ PISLAM_EXPORT int pislam_ctx_destroy(pislam_ctx *c) {
                     &c->w_off, &c->w_total, &c->w_cellkp, &c->w_score, &c->w_stage, &c->w_stripcnt, &c->w_work, &c->w_prof, &c->w_ovf,
                     &c->w_stagedesc, &c->w_ustage, &c->w_ucount, &c->w_sync, &c->w_chain})
     b->release();
-  for (pislam_ctx::CellIndex *w : {&c->w_win, &c->w_sc, &c->w_st, &c->w_bow})
+  for (pislam_ctx::CellIndex *w : {&c->w_win, &c->w_sc, &c->w_st, &c->w_proj, &c->w_bow})
     for (DevBuf *b : {&w->off, &w->meta, &w->desc}) b->release();
   c->w_db.release();
   for (auto *t : c->plan_tables) {
@@ -1653,15 +1654,19 @@ namespace {
 
 // Checks the arguments every scaled-window call shares and lays out the per-pair cell grids (host only).  Level lt's
 // grid covers its mapped extent [0, ext_x] x [0, ext_y] in level-0 pixels with square cells of side m[lt] * f, where
-// m[lt] is the largest max(1, radius0[lq]) of the query levels lq that reach lt (|lq - lt| <= span) and f >= 1 is the
+// m[lt] is the largest max(1, radius0[lq]) of the query levels lq that reach lt and f >= 1 is the
 // smallest factor that keeps all levels' cells within pm::WIN_MAX_CELLS (the LDS histogram of k_scaled_index).  Results
 // do not depend on the side: the match applies the exact window test.
+// The general form (the projection matcher's): a query on level lq sees the train levels lq - level_below ..
+// lq + level_above, so level lt is reached by the query levels lt - level_above .. lt + level_below.
 int scaled_plan(pislam_ctx *c, int words, const pislam_level *lv, int nlevels, const int32_t *scale_q16,
-                const int32_t *radius0, int level_span, size_t t_stride, int batch, pm::ScaledPlan *P) {
+                const int32_t *radius0, int level_below, int level_above, size_t t_stride, int batch, pm::ScaledPlan *P) {
   PCHK(check_words(c, words));
   if (nlevels < 1 || nlevels > pm::WIN_MAX_LEVELS) return fail(c, PISLAM_ERR_INVALID, "nlevels must be 1..16");
   if (!lv || !scale_q16 || !radius0) return fail(c, PISLAM_ERR_INVALID, "null levels / scale_q16 / radius0");
-  if (level_span < 0 || level_span > nlevels - 1) return fail(c, PISLAM_ERR_INVALID, "level_span must be 0..nlevels-1");
+  if (level_below < 0 || level_below > nlevels - 1 || level_above < 0 || level_above > nlevels - 1)
+    return fail(c, PISLAM_ERR_INVALID, level_below == level_above ? "level_span must be 0..nlevels-1"
+                                                                  : "level_below / level_above must be 0..nlevels-1");
   PCHK(check_train_stride(c, t_stride, "at most 65535 train entries per pair"));
   PCHK(check_batch(c, batch));
   int32_t ext_x[pm::WIN_MAX_LEVELS], ext_y[pm::WIN_MAX_LEVELS];
@@ -1684,7 +1689,7 @@ int scaled_plan(pislam_ctx *c, int words, const pislam_level *lv, int nlevels, c
   long long m[pm::WIN_MAX_LEVELS];
   for (int lt = 0; lt < nlevels; lt++) {
     m[lt] = 1;
-    for (int lq = std::max(0, lt - level_span); lq <= std::min(nlevels - 1, lt + level_span); lq++)
+    for (int lq = std::max(0, lt - level_above); lq <= std::min(nlevels - 1, lt + level_below); lq++)
       m[lt] = std::max<long long>(m[lt], radius0[lq]);
   }
   auto side = [&](int l, long long f) { return (int)std::min<long long>(65536, m[l] * f); };
@@ -1706,8 +1711,14 @@ int scaled_plan(pislam_ctx *c, int words, const pislam_level *lv, int nlevels, c
   }
   P->nlevels = nlevels;
   P->ncells = base;
-  P->span = level_span;
+  P->span = level_below;                                 // (k_match_scaled reads it; its callers pass below == above)
   return PISLAM_OK;
+}
+
+// The symmetric form of the windowed, the scaled and the stereo call: |lq - lt| <= level_span.
+int scaled_plan(pislam_ctx *c, int words, const pislam_level *lv, int nlevels, const int32_t *scale_q16,
+                const int32_t *radius0, int level_span, size_t t_stride, int batch, pm::ScaledPlan *P) {
+  return scaled_plan(c, words, lv, nlevels, scale_q16, radius0, level_span, level_span, t_stride, batch, P);
 }
 
 // The windowed matcher's plan: the scaled plan with unit scales (mapped = level-local coordinates), span 0 and
@@ -1840,6 +1851,102 @@ PISLAM_EXPORT int pislam_match_hamming_scaled_window_batch(pislam_ctx *c, int wo
                        "hipMalloc(scaled window matcher workspace)"));
   return launch_guided(c, c->w_sc, P, words, qkp, qdesc, qcounts, qpred, q_stride, tkp, tdesc, tcounts, t_stride, batch,
                        idx, dist, dist2);
+}
+
+// ---- map-point search by projection -------------------------------------------------------
+
+namespace {
+
+// Checks the tables of a projection call and lays out the train side: the scaled plan with the one-sided level window
+// and, per level, the larger of the two radii (the match applies the exact radius of the query's predicted level).
+int projection_plan(pislam_ctx *c, int words, const pislam_level *lv, int nlevels, const int32_t *scale_q16,
+                    const int32_t *radius_far, const int32_t *radius_near, int level_below, int level_above,
+                    size_t t_stride, int batch, pm::ScaledPlan *P, pjm::Tables *tab) {
+  if (nlevels < 1 || nlevels > pm::WIN_MAX_LEVELS) return fail(c, PISLAM_ERR_INVALID, "nlevels must be 1..16");
+  if (!radius_far) return fail(c, PISLAM_ERR_INVALID, "null radius_far");
+  int32_t rmax[pm::WIN_MAX_LEVELS];
+  *tab = pjm::Tables{};
+  for (int l = 0; l < nlevels; l++) {
+    const int32_t rf = radius_far[l], rn = radius_near ? radius_near[l] : rf;
+    if (rf < 0 || rf > pjm::MAX_RADIUS || rn < 0 || rn > pjm::MAX_RADIUS)
+      return fail(c, PISLAM_ERR_INVALID, "radius_far / radius_near must be 0..65535");
+    tab->radius_far[l] = rf, tab->radius_near[l] = rn;
+    rmax[l] = std::max(rf, rn);
+  }
+  tab->nlevels = nlevels;
+  return scaled_plan(c, words, lv, nlevels, scale_q16, rmax, level_below, level_above, t_stride, batch, P);
+}
+
+}  // namespace
+
+PISLAM_EXPORT int pislam_match_projection_reserve(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
+                                                  const int32_t *scale_q16, const int32_t *radius_far,
+                                                  const int32_t *radius_near, int level_below, int level_above,
+                                                  size_t t_stride, int batch) {
+  if (!c) return PISLAM_ERR_INVALID;
+  pm::ScaledPlan P;
+  pjm::Tables tab;
+  PCHK(projection_plan(c, words, levels, nlevels, scale_q16, radius_far, radius_near, level_below, level_above, t_stride,
+                       batch, &P, &tab));
+  HIPCHK(c, hipSetDevice(c->device));
+  return index_workspace(c, c->w_proj, (size_t)P.ncells + 1, sizeof(uint2), words, t_stride, batch,
+                         "hipMalloc(projection matcher workspace)");
+}
+
+PISLAM_EXPORT int pislam_match_projection_batch(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
+                                                const int32_t *scale_q16, const float *level_scale,
+                                                const int32_t *radius_far, const int32_t *radius_near,
+                                                const pislam_projection_params *p, const float *pose, const float *cam,
+                                                const float *xw, const float *normal, const float *drange,
+                                                const uint8_t *qlevel, const uint32_t *qdesc, const uint32_t *qcounts,
+                                                size_t q_stride, const uint32_t *tkp, const uint32_t *tdesc,
+                                                const uint32_t *tcounts, size_t t_stride, int batch, int32_t *idx,
+                                                uint32_t *dist, uint32_t *dist2, int32_t *pred, uint8_t *plevel) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
+  pm::ScaledPlan P;
+  pjm::Tables tab;
+  PCHK(projection_plan(c, words, levels, nlevels, scale_q16, radius_far, radius_near, p->level_below, p->level_above,
+                       t_stride, batch, &P, &tab));
+  if (!level_scale) return fail(c, PISLAM_ERR_INVALID, "null level_scale");
+  for (int l = 0; l < nlevels; l++) {
+    if (!psm::finite_f(level_scale[l]) || !(level_scale[0] > 0.0f) || (l && !(level_scale[l] >= level_scale[l - 1])))
+      return fail(c, PISLAM_ERR_INVALID, "level_scale must be finite, positive and non-decreasing");
+    tab.level_scale[l] = level_scale[l];
+  }
+  for (float v : {p->min_x, p->max_x, p->min_y, p->max_y})
+    if (!(fabsf(v) <= pjm::BOUND_LIMIT)) return fail(c, PISLAM_ERR_INVALID, "the image bounds must lie within +-2^20");
+  if (!(p->min_x <= p->max_x) || !(p->min_y <= p->max_y)) return fail(c, PISLAM_ERR_INVALID, "need min_x <= max_x and min_y <= max_y");
+  if (p->second_same_level != 0 && p->second_same_level != 1)
+    return fail(c, PISLAM_ERR_INVALID, "second_same_level must be 0 or 1");
+  if ((drange != nullptr) == (qlevel != nullptr))
+    return fail(c, PISLAM_ERR_INVALID, "exactly one of drange (map mode) and qlevel (level mode) must be given");
+  if (normal && qlevel) return fail(c, PISLAM_ERR_INVALID, "normal needs drange (map mode)");
+  if (q_stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "q_stride too large");
+  const char *what = "the projection matcher takes device pointers only";
+  for (const void *opt : {(const void *)normal, (const void *)drange, (const void *)qlevel, (const void *)pred,
+                          (const void *)plevel})
+    if (opt && !is_device_ptr(opt)) return fail(c, PISLAM_ERR_INVALID, what);
+  if (batch == 0 || q_stride == 0) return PISLAM_OK;
+  PCHK(device_ptrs(c, {pose, cam, xw, qdesc, qcounts, tkp, tdesc, tcounts, idx, dist, dist2}, what));
+  HIPCHK(c, hipSetDevice(c->device));
+  const pislam_ctx::CellIndex &w = c->w_proj;
+  PCHK(index_workspace(c, c->w_proj, (size_t)P.ncells + 1, sizeof(uint2), words, t_stride, batch,
+                       "hipMalloc(projection matcher workspace)"));
+  PCHK(launch_scaled_index(c, w, P, words, tkp, tdesc, tcounts, t_stride, batch));
+  const pjm::Params prm{p->min_x, p->max_x, p->min_y, p->max_y, p->cos_min, p->cos_near,
+                        p->level_below, p->level_above, p->second_same_level};
+  pj::ProjArgs a{};
+  a.pose = pose, a.cam = cam, a.xw = xw, a.normal = normal, a.drange = drange, a.qlevel = qlevel;
+  a.qdesc = qdesc, a.qcount = qcounts, a.tkp = tkp, a.q_stride = q_stride, a.t_stride = t_stride;
+  a.cell_off = w.off.as<uint32_t>(), a.ent_meta = w.meta.as<uint2>(), a.ent_desc = w.desc.as<uint32_t>();
+  a.idx = idx, a.dist = dist, a.dist2 = dist2, a.pred = pred, a.plevel = plevel;
+  const dim3 grid = query_grid(c, q_stride, pm::WIN_QPW, batch);
+  with_words(words, [&](auto wd) {
+    hipLaunchKernelGGL(pj::k_match_projection<decltype(wd)::value>, grid, dim3(pm::WIN_THREADS), 0, c->stream, P, tab, prm,
+                       a);
+  });
+  return launch_ok(c, "k_match_projection");
 }
 
 // ---- rectified stereo matching ------------------------------------------------------------

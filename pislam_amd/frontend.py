@@ -314,6 +314,109 @@ def matchHammingScaledWindowBatch(qkp, qdesc, qcounts, tkp, tdesc, tcounts, leve
     return idx, dist, dist2
 
 
+def projectionRadii(scale_q16, th, near=2.5, far=4.0):
+    """The (radius_far, radius_near) tables of matchProjectionBatch, ORB-SLAM's th * RadiusByViewingCos * scaleFactor[l]
+    in level-0 pixels: per level l, floor(f * th * scale_q16[l] / 65536 + 0.5) with f = far and f = near, evaluated in
+    float64 in that order of operations (halves round up) and clamped to 0..65535.  Returns two int32 numpy arrays."""
+    s = np.asarray([int(v) for v in scale_q16], dtype=np.float64)
+
+    def table(f):
+        return np.clip(np.floor(np.float64(f) * np.float64(th) * s / 65536.0 + 0.5), 0, 65535).astype(np.int32)
+    return table(far), table(near)
+
+
+def _projection_tables(levels, scale_q16, level_scale, radius_far, radius_near, th):
+    """levels, scale_q16 (None = level_scales_q16), level_scale (None = float32(scale_q16 / 65536)) and the two radius
+    tables (both None = projectionRadii(scale_q16, th); radius_near alone None = NULL, i.e. radius_far) as C arrays."""
+    if scale_q16 is None:
+        scale_q16 = level_scales_q16(levels)
+    if radius_far is None:
+        if radius_near is not None:
+            raise ValueError("radius_near needs radius_far")
+        sq = [int(scale_q16)] * len(levels) if isinstance(scale_q16, (int, np.integer)) else scale_q16
+        radius_far, radius_near = (t.tolist() for t in projectionRadii(sq, th))
+    lv, n, s, rf = _scaled_tables(levels, scale_q16, radius_far)
+    rn = None
+    if radius_near is not None:
+        rn = _window_tables(levels, radius_near)[2]
+    if level_scale is None:
+        level_scale = [np.float32(np.float32(v) / np.float32(65536.0)) for v in s[:n]]
+    ls = [float(np.float32(v)) for v in np.asarray(level_scale, dtype=np.float32).reshape(-1)]
+    if len(ls) != n:
+        raise ValueError(f"level_scale: {len(ls)} values for {n} levels")
+    return lv, n, s, (ctypes.c_float * max(1, n))(*ls), rf, rn
+
+
+def reserveMatchProjection(levels, t_stride: int, batch: int, *, scale_q16=None, radius_far=None, radius_near=None, th=3,
+                           level_below=1, level_above=0, words=8, ctx: Context | None = None):
+    """Sizes the context's projection-matcher workspace (pislam_match_projection_reserve): afterwards
+    matchProjectionBatch of the same or a smaller shape allocates nothing and can be captured into a hipGraph.  The
+    tables default as in matchProjectionBatch."""
+    ctx = ctx or default_context()
+    lv, n, s, _, rf, rn = _projection_tables(levels, scale_q16, None, radius_far, radius_near, th)
+    ctx.check(ctx.lib.pislam_match_projection_reserve(ctx.h, words, lv, n, s, rf, rn, int(level_below), int(level_above),
+                                                      t_stride, batch), "pislam_match_projection_reserve")
+
+
+def matchProjectionBatch(pose, cam, xw, qdesc, qcounts, tkp, tdesc, tcounts, levels, *, drange=None, normal=None,
+                         qlevel=None, scale_q16=None, level_scale=None, radius_far=None, radius_near=None, th=3,
+                         bounds=None, cos_min=0.5, cos_near=0.998, level_below=1, level_above=0, second_same_level=True,
+                         idx=None, dist=None, dist2=None, pred=None, plevel=None, want_pred=True, want_plevel=True,
+                         ctx: Context | None = None):
+    """Map-point search by projection (pislam_match_projection_batch; the contract is the comment in
+    include/pislam_hip.h), ORB-SLAM's SearchByProjection: per frame b, map points xw (float32 [batch][q_stride][3])
+    with descriptors qdesc ([batch][q_stride][words]) are projected through pose (float32 [batch][12]) and cam (float32
+    [batch][5]) and matched against the frame's keypoints (tkp, tdesc, tcounts as for matchHammingScaledWindowBatch) in a
+    window round the projection on the predicted pyramid level.  Map mode: drange (float32 [batch][q_stride][2] = dmin,
+    dmax) and optionally normal (float32 [batch][q_stride][3]); level mode: qlevel (uint8 [batch][q_stride]).  The
+    defaults are ORB-SLAM's local-map search: bounds = (min_x, max_x, min_y, max_y) = (0, width_0 - 1, 0, height_0 - 1),
+    cos_min 0.5, cos_near 0.998, levels pl - 1 .. pl, the ratio test's runner-up on the best's level only; scale_q16
+    None = level_scales_q16(levels), level_scale None = float32(scale_q16 / 65536), radius tables both None =
+    projectionRadii(scale_q16, th), radius_near alone None = radius_far.  Returns (idx, dist, dist2, pred, plevel): int32
+    [batch][q_stride] three times, pred int32 [batch][q_stride][2] (None with want_pred False) and plevel uint8
+    [batch][q_stride] (0xff = not visible; None with want_plevel False).  Asynchronous on the ctx stream."""
+    import torch
+    ctx = ctx or default_context()
+    batch, qs, words = (int(v) for v in qdesc.shape)
+    ts = int(tdesc.shape[1])
+    if int(tdesc.shape[2]) != words:
+        raise ValueError("query and train descriptors differ in words")
+    if pose.dtype != torch.float32 or tuple(pose.shape) != (batch, 12):
+        raise ValueError("pose must be a float32 tensor [batch][12]")
+    if cam.dtype != torch.float32 or tuple(cam.shape) != (batch, 5):
+        raise ValueError("cam must be a float32 tensor [batch][5]")
+    for name, t, k in (("xw", xw, 3), ("normal", normal, 3), ("drange", drange, 2)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (batch, qs, k)):
+            raise ValueError(f"{name} must be a float32 tensor [batch][q_stride][{k}]")
+    if qlevel is not None and (qlevel.dtype != torch.uint8 or tuple(qlevel.shape) != (batch, qs)):
+        raise ValueError("qlevel must be a uint8 tensor [batch][q_stride]")
+    for t in (pose, cam, xw, normal, drange, qlevel, qdesc, qcounts, tkp, tdesc, tcounts):
+        if t is not None and not t.is_contiguous():
+            raise ValueError("inputs must be contiguous")
+    lv, n, s, ls, rf, rn = _projection_tables(levels, scale_q16, level_scale, radius_far, radius_near, th)
+    if bounds is None:
+        bounds = (0.0, float(int(levels[0][0]) - 1), 0.0, float(int(levels[0][1]) - 1))
+    p = capi.ProjectionParams(*(float(v) for v in bounds), float(cos_min), float(cos_near), int(level_below),
+                              int(level_above), 1 if second_same_level else 0)
+    dev = qdesc.device
+    if idx is None:
+        idx = torch.empty((batch, qs), dtype=torch.int32, device=dev)
+    if dist is None:
+        dist = torch.empty((batch, qs), dtype=torch.int32, device=dev)
+    if dist2 is None:
+        dist2 = torch.empty((batch, qs), dtype=torch.int32, device=dev)
+    if pred is None and want_pred:
+        pred = torch.empty((batch, qs, 2), dtype=torch.int32, device=dev)
+    if plevel is None and want_plevel:
+        plevel = torch.empty((batch, qs), dtype=torch.uint8, device=dev)
+    ctx.check(ctx.lib.pislam_match_projection_batch(ctx.h, words, lv, n, s, ls, rf, rn, ctypes.byref(p), ptr(pose), ptr(cam),
+                                                    ptr(xw), ptr(normal), ptr(drange), ptr(qlevel), ptr(qdesc),
+                                                    ptr(qcounts), qs, ptr(tkp), ptr(tdesc), ptr(tcounts), ts, batch,
+                                                    ptr(idx), ptr(dist), ptr(dist2), ptr(pred), ptr(plevel)),
+              "pislam_match_projection_batch")
+    return idx, dist, dist2, pred, plevel
+
+
 def _stereo_tables(levels, scale_q16, row_radius0, level_span, min_disp, max_disp, max_hamming, sad_radius,
                    search_radius, median_filter):
     """levels, scale_q16 (None = level_scales_q16), row_radius0 (int, or one per level) and the parameters as C."""
@@ -1013,6 +1116,30 @@ def poseObservationsQ8(kp, levels, scale_q16=None, disp_q8=None, pos_q8=None):
         ur = torch.where(found & (d >= 0), U - d, ur)
     obs = torch.stack([U, V, ur], dim=-1).clamp(POSE_MONO, (1 << 31) - 1).to(torch.int32)
     return obs.contiguous(), level.to(torch.uint8).contiguous()
+
+
+def matchedMapObservations(xw, tkp, sel, levels, scale_q16=None):
+    """The (xw, obs_q8, level, counts) of poseRefineBatch from matchProjectionBatch's matches after selectMatchesBatch:
+    sel = (sel_q, sel_t, nsel); slot s < nsel[b] pairs map point xw[b][sel_q[b][s]] with the observation
+    poseObservationsQ8 makes of keypoint tkp[b][sel_t[b][s]] (monocular).  The slots at and beyond nsel[b] of sel_q and
+    sel_t are unwritten memory: they are masked before gathering and come out as the point (0, 0, 0), the observation
+    (0, 0, INT32_MIN) and the level 255.  Returns (xw float32 [batch][q_stride][3], obs_q8 int32 [batch][q_stride][3],
+    level uint8 [batch][q_stride], counts int32 [batch] = nsel).  Torch ops on the current torch stream."""
+    import torch
+    sel_q, sel_t, nsel = sel
+    batch, qs = (int(v) for v in sel_q.shape)
+    dev = sel_q.device
+    live = torch.arange(qs, device=dev)[None, :] < nsel.to(torch.int64)[:, None]
+    zero = torch.zeros_like(live, dtype=torch.int64)
+    qi = torch.where(live, sel_q.to(torch.int64), zero).clamp(0, int(xw.shape[1]) - 1)
+    ti = torch.where(live, sel_t.to(torch.int64), zero).clamp(0, int(tkp.shape[1]) - 1)
+    pts = torch.gather(xw, 1, qi[..., None].expand(-1, -1, 3))
+    pts = torch.where(live[..., None], pts, torch.zeros_like(pts))
+    obs, level = poseObservationsQ8(torch.gather(tkp.to(torch.int64), 1, ti), levels, scale_q16)
+    dead = torch.tensor([0, 0, POSE_MONO], dtype=torch.int32, device=dev).expand(batch, qs, 3)
+    obs = torch.where(live[..., None], obs, dead)
+    level = torch.where(live, level, torch.full_like(level, POSE_NO_LEVEL))
+    return pts.contiguous(), obs.contiguous(), level.contiguous(), nsel.to(torch.int32).clone()
 
 
 def poseRefineBatch(pose, cam, xw, obs_q8, counts, *, level=None, inv_sigma2=None, rounds=4, iters=10, huber_rounds=3,
