@@ -2109,6 +2109,22 @@ void copy_level_table(ARGS *a, const float *inv_sigma2, int nlevels) {
   a->nlevels = nlevels;
   for (int l = 0; l < nlevels; l++) a->inv_sigma2[l] = inv_sigma2[l];
 }
+// The level arrays of the two Sim(3) calls: both or neither, and with them the table.
+int check_level_pair(pislam_ctx *c, const uint8_t *level1, const uint8_t *level2, const float *inv_sigma2, int nlevels) {
+  if ((level1 != nullptr) != (level2 != nullptr)) return fail(c, PISLAM_ERR_INVALID, "level1 and level2 go together");
+  return level1 ? check_level_table(c, "levels need", inv_sigma2, nlevels) : PISLAM_OK;
+}
+// What the two refinement calls check of their schedule, in their order; eps comes after the Sim(3) call's own checks.
+int check_refine_schedule(pislam_ctx *c, int rounds, int iters, int huber_rounds, int min_obs) {
+  if (rounds < 1 || rounds > 8) return fail(c, PISLAM_ERR_INVALID, "rounds must be 1..8");
+  if (iters < 1 || iters > 32) return fail(c, PISLAM_ERR_INVALID, "iters must be 1..32");
+  if (huber_rounds < 0 || huber_rounds > rounds) return fail(c, PISLAM_ERR_INVALID, "huber_rounds must be 0..rounds");
+  if (min_obs < 3 || min_obs > prf::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "min_obs must be 3..16384");
+  return PISLAM_OK;
+}
+int check_refine_eps(pislam_ctx *c, double eps) {
+  return eps >= 0.0 ? PISLAM_OK : fail(c, PISLAM_ERR_INVALID, "eps must be >= 0");
+}
 
 }  // namespace
 
@@ -2664,11 +2680,8 @@ PISLAM_EXPORT int pislam_pose_refine_batch(pislam_ctx *c, const pislam_pose_para
                                            uint32_t *ninliers, double *cost, uint32_t *status) {
   if (!c) return PISLAM_ERR_INVALID;
   if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
-  if (p->rounds < 1 || p->rounds > 8) return fail(c, PISLAM_ERR_INVALID, "rounds must be 1..8");
-  if (p->iters < 1 || p->iters > 32) return fail(c, PISLAM_ERR_INVALID, "iters must be 1..32");
-  if (p->huber_rounds < 0 || p->huber_rounds > p->rounds) return fail(c, PISLAM_ERR_INVALID, "huber_rounds must be 0..rounds");
-  if (p->min_obs < 3 || p->min_obs > pq::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "min_obs must be 3..16384");
-  if (!(p->eps >= 0.0)) return fail(c, PISLAM_ERR_INVALID, "eps must be >= 0");
+  PCHK(check_refine_schedule(c, p->rounds, p->iters, p->huber_rounds, p->min_obs));
+  PCHK(check_refine_eps(c, p->eps));
   if (level) PCHK(check_level_table(c, "level needs", inv_sigma2, nlevels));
   if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
   if (stride < 1 || stride > (size_t)pq::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
@@ -2692,7 +2705,7 @@ PISLAM_EXPORT int pislam_pose_refine_batch(pislam_ctx *c, const pislam_pose_para
   copy_level_table(&a, inv_sigma2, level ? nlevels : 0);
   a.p = pq::Params{p->rounds, p->iters, p->huber_rounds, p->min_obs, p->eps};
   a.pose_out = pose_out, a.inlier = inlier, a.ninliers = ninliers, a.status = status, a.cost = cost;
-  hipLaunchKernelGGL(po::k_pose_refine, dim3((unsigned)std::min(batch, po::PO_GRID_CAP)), dim3(po::PO_THREADS), 0,
+  hipLaunchKernelGGL(po::k_pose_refine, dim3((unsigned)std::min(batch, prf::GRID_CAP)), dim3(prf::THREADS), 0,
                      c->stream, a);
   return launch_ok(c, "k_pose_refine");
 }
@@ -2749,8 +2762,7 @@ PISLAM_EXPORT int pislam_sim3_ransac_batch(pislam_ctx *c, const pislam_sim3_para
   if (p->min_inliers < s3m::SAMPLE || p->min_inliers > s3m::MAX_STRIDE)
     return fail(c, PISLAM_ERR_INVALID, "min_inliers must be 3..16384");
   if (p->fixed_scale != 0 && p->fixed_scale != 1) return fail(c, PISLAM_ERR_INVALID, "fixed_scale must be 0 or 1");
-  if ((level1 != nullptr) != (level2 != nullptr)) return fail(c, PISLAM_ERR_INVALID, "level1 and level2 go together");
-  if (level1) PCHK(check_level_table(c, "levels need", inv_sigma2, nlevels));
+  PCHK(check_level_pair(c, level1, level2, inv_sigma2, nlevels));
   if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
   if (stride < 1 || stride > (size_t)s3m::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
   if (batch == 0) return PISLAM_OK;
@@ -2790,15 +2802,11 @@ PISLAM_EXPORT int pislam_sim3_refine_batch(pislam_ctx *c, const pislam_sim3_refi
                                            uint32_t *status) {
   if (!c) return PISLAM_ERR_INVALID;
   if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
-  if (p->rounds < 1 || p->rounds > 8) return fail(c, PISLAM_ERR_INVALID, "rounds must be 1..8");
-  if (p->iters < 1 || p->iters > 32) return fail(c, PISLAM_ERR_INVALID, "iters must be 1..32");
-  if (p->huber_rounds < 0 || p->huber_rounds > p->rounds) return fail(c, PISLAM_ERR_INVALID, "huber_rounds must be 0..rounds");
-  if (p->min_obs < 3 || p->min_obs > s3r::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "min_obs must be 3..16384");
+  PCHK(check_refine_schedule(c, p->rounds, p->iters, p->huber_rounds, p->min_obs));
   if (!(p->th2 > 0.0f) || !psm::finite_f(p->th2)) return fail(c, PISLAM_ERR_INVALID, "th2 must be finite and > 0");
   if (p->fixed_scale != 0 && p->fixed_scale != 1) return fail(c, PISLAM_ERR_INVALID, "fixed_scale must be 0 or 1");
-  if (!(p->eps >= 0.0)) return fail(c, PISLAM_ERR_INVALID, "eps must be >= 0");
-  if ((level1 != nullptr) != (level2 != nullptr)) return fail(c, PISLAM_ERR_INVALID, "level1 and level2 go together");
-  if (level1) PCHK(check_level_table(c, "levels need", inv_sigma2, nlevels));
+  PCHK(check_refine_eps(c, p->eps));
+  PCHK(check_level_pair(c, level1, level2, inv_sigma2, nlevels));
   if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
   if (stride < 1 || stride > (size_t)s3r::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
   if (batch == 0) return PISLAM_OK;
@@ -2824,7 +2832,7 @@ PISLAM_EXPORT int pislam_sim3_refine_batch(pislam_ctx *c, const pislam_sim3_refi
   copy_level_table(&a, inv_sigma2, level1 ? nlevels : 0);
   a.p = s3r::Params{p->rounds, p->iters, p->huber_rounds, p->min_obs, p->th2, p->fixed_scale, p->eps};
   a.sim_out = sim_out, a.inlier = inlier, a.ninliers = ninliers, a.status = status, a.cost = cost;
-  hipLaunchKernelGGL(sr::k_sim3_refine, dim3((unsigned)std::min(batch, sr::SR_GRID_CAP)), dim3(sr::SR_THREADS), 0,
+  hipLaunchKernelGGL(sr::k_sim3_refine, dim3((unsigned)std::min(batch, prf::GRID_CAP)), dim3(prf::THREADS), 0,
                      c->stream, a);
   return launch_ok(c, "k_sim3_refine");
 }

@@ -1,27 +1,20 @@
 // pislam_pose_kernels.h — batched motion-only pose optimisation on the device (pislam_pose_refine_batch;
 // include/pislam_hip.h).  The header comment is the contract; the arithmetic is stated once, in
-// pislam_pose_math.h, for this kernel and for the host probe.
+// pislam_pose_math.h and, the Levenberg rule, in pislam_refine_math.h, for this kernel and for the host probe.
 //
-// One workgroup of PO_THREADS = 256 runs the whole call for a frame in one launch (all rounds, passes, solves and
-// classifications), then the frame PO_GRID_CAP further on.  No workspace.
-//   * Thread (wave, lane) owns the contract's partial sum q = wave * 4 + lane / 16 + 16 * rev4(lane % 16), that is the
-//     observations q, q + 256, q + 512, ... in ascending order.  The bits of q are laid out so that the contract's
-//     halving tree runs fastest: its steps 128, 64, 32, 16 are the lane exchanges xor 1, xor 2, xor 4, xor 8 (four DPP
-//     moves inside a row of 16 lanes; addition is commutative, so both partners hold the same bits afterwards), and the
-//     steps 8, 4, 2, 1 combine the 16 row sums of the workgroup through LDS, one sum per lane.
+// One workgroup runs the whole call for a frame in one launch (all rounds, passes, solves and classifications).  The
+// launch shape, the partial sum a thread owns, the tree and the refused frame are those of pislam_refine_kernels.h.
 //   * A frame of at most PO_RES * 256 = 2048 observations is loaded once and stays in registers over all passes; a
 //     larger one is re-read (from L2) in every pass.  The active set is a bit mask per lane either way.
-//   * Lane 0 runs the solve, the retraction and the Levenberg rule on state kept in LDS and broadcasts the next pose
-//     as 12 floats: three barriers per pass.
+//   * Lane 0 runs the solve, the retraction and the Levenberg rule (prf::Lm) on state kept in LDS and broadcasts the
+//     next pose as 12 floats: three barriers per pass.
 #pragma once
-#include "pislam_dev.h"
+#include "pislam_refine_kernels.h"
 #include "pislam_pose_math.h"
 
 namespace po {
 
-constexpr int PO_THREADS = 256;
 constexpr int PO_RES = 8;                      // register-resident observations per lane
-constexpr int PO_GRID_CAP = 1024;              // workgroups per launch; a larger batch is walked in passes
 
 struct PoArgs {
   const float *pose_in, *cam, *xw;
@@ -126,27 +119,7 @@ __device__ __forceinline__ void po_pass(const PoArgs &A, const PoFrame &F, const
       }
     }
   }
-  // the tree: steps 128, 64, 32, 16 inside the rows of 16 lanes (every lane is active here) ...
-#pragma unroll
-  for (int k = 0; k < pq::SUMS; k++) acc[k] = pdev::row16_sum(acc[k]);
-  if ((tid & 15) == 0) {
-#pragma unroll
-    for (int k = 0; k < pq::SUMS; k++) s_part[k][tid >> 4] = acc[k];   // row tid / 16 = wave * 4 + lane / 16 = q % 16
-  }
-  __syncthreads();
-  // ... steps 8, 4, 2, 1 over the 16 row sums, one sum per lane
-  if (tid < pq::SUMS) {
-    double v[16];
-#pragma unroll
-    for (int j = 0; j < 16; j++) v[j] = s_part[tid][j];
-#pragma unroll
-    for (int h = 8; h >= 1; h >>= 1) {
-#pragma unroll
-      for (int j = 0; j < h; j++) v[j] += v[j + h];
-    }
-    s_S[tid] = v[0];
-  }
-  __syncthreads();
+  prf::tree_sums(acc, tid, s_part, s_S);
 }
 
 template <bool RES>
@@ -168,7 +141,7 @@ __device__ __forceinline__ void po_frame(const PoArgs &A, const PoFrame &F, uint
     PISLAM_ROLLED
     for (;;) {
       if (tid == 0) {
-        const bool go = s_lm->next(iters);
+        const bool go = s_lm->next(pq::Rule{}, iters);
         *s_cmd = go ? 1 : 0;
 #pragma unroll
         for (int i = 0; i < 12; i++) s_Tf[i] = (float)(go ? s_lm->Tt[i] : s_lm->T[i]);
@@ -191,7 +164,7 @@ __device__ __forceinline__ void po_frame(const PoArgs &A, const PoFrame &F, uint
   if (tid == 0) A.ninliers[b] = ninl, A.cost[b] = cost, A.status[b] = code | evals << 8;
 }
 
-__global__ __launch_bounds__(PO_THREADS) void k_pose_refine(const PoArgs A) {
+__global__ __launch_bounds__(prf::THREADS) void k_pose_refine(const PoArgs A) {
   __shared__ pq::Lm s_lm;
   __shared__ double s_part[pq::SUMS][16];
   __shared__ double s_S[pq::SUMS + 2];
@@ -202,10 +175,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_refine(const PoArgs A) {
   for (uint32_t b = blockIdx.x; b < (uint32_t)A.batch; b += gridDim.x) {
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));              // keeps the per-thread predicates out of SGPRs held over the loop
-    const int lane = tid & 63, wave = tid >> 6;
-    const uint32_t l4 = (uint32_t)lane & 15u;
-    const uint32_t rev = (l4 & 1u) << 3 | (l4 & 2u) << 1 | (l4 & 4u) >> 1 | (l4 & 8u) >> 3;
-    const uint32_t q = (uint32_t)wave << 2 | (uint32_t)lane >> 4 | rev << 4;
+    const uint32_t q = prf::partial_of(tid);
     const size_t row = (size_t)b * A.stride;
     PoFrame F;
     F.xw = A.xw + 3 * row, F.obs = A.obs + 3 * row, F.level = A.level ? A.level + row : nullptr, F.inlier = A.inlier + row;
@@ -221,10 +191,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_refine(const PoArgs A) {
     __syncthreads();
     const bool fin = s_cmd != 0;
     if (!fin || n < (uint32_t)A.p.min_obs) {
-      PISLAM_ROLLED
-      for (uint32_t i = tid; i < n; i += PO_THREADS) F.inlier[i] = 0;
-      if (tid < 12) A.pose_out[12 * (size_t)b + tid] = v;
-      if (tid == 0) A.ninliers[b] = 0, A.cost[b] = 0.0, A.status[b] = fin ? 1u : 2u;
+      prf::refuse<12>(A, b, tid, n, F.inlier, A.pose_out, v, fin);
     } else {
       if (tid < 12) s_lm.T[tid] = (double)v;
       __syncthreads();

@@ -1,10 +1,11 @@
 // pislam_pose_math.h — the arithmetic of pislam_pose_refine_batch (include/pislam_hip.h: that comment is the contract),
 // stated ONCE for the device kernel (pislam_pose_kernels.h) and for a plain C++ compiler (tools/probes/
-// pose_host_check.cpp): the per-observation terms in binary32, the 6 x 6 solve, the Cayley retraction and the
-// Levenberg rule in binary64, and, for the host only, the whole procedure run serially with the contract's tree order.
+// pose_host_check.cpp): the per-observation terms in binary32, the 6 x 6 solve and the Cayley retraction in binary64,
+// what the Levenberg rule of pislam_refine_math.h needs of the call (Rule) and, for the host's serial form of the whole
+// procedure there (prf::host_refine), the frame as a Problem.
 // Every operation is written out one rounding at a time; build with -ffp-contract=off.
 #pragma once
-#include "pislam_scalar_math.h"
+#include "pislam_refine_math.h"
 
 namespace pq {
 
@@ -15,12 +16,10 @@ using psm::fsqrt;
 
 constexpr int TERMS = 28;                      // 21 upper-triangle terms, 6 gradient terms, rho
 constexpr int SUMS = 30;                       // + the number of active observations that are not dead, + their chi2
-constexpr int PARTIALS = 256;
-constexpr int MAX_STRIDE = 16384;
+constexpr int MAX_STRIDE = prf::MAX_STRIDE;
 constexpr int MAX_LEVELS = 16;
 constexpr float Z_MIN = 0x1p-10f;
 constexpr float TH_MONO = 5.991f, TH_STEREO = 7.815f;
-constexpr double LAMBDA_0 = 0x1p-10, LAMBDA_MIN = 0x1p-30, LAMBDA_MAX = 0x1p20;
 constexpr int32_t OBS_MAX = 1 << 22;
 constexpr int32_t MONO = INT32_MIN;
 
@@ -130,7 +129,6 @@ PISLAM_UNROLL
   }
   return ok;
 }
-PISLAM_HD bool solve(const double *S, double lambda, double *d) { return solve_n<6>(S, lambda, d); }
 
 // The Cayley map of the rotation vector d[0..2]: Q = ((1 - n) I + 2 a a' + 2 [a]x) / (1 + n) with a = d / 2, n = a'a.
 PISLAM_HD void cayley(const double *d, double *Q) {
@@ -154,57 +152,7 @@ PISLAM_UNROLL
   }
 }
 
-// The Levenberg rule of one round, as a state machine around the passes over the observations: begin() takes the sums
-// at the round's pose, next() asks for the next trial pose (false: the round is over), trial() takes the sums at it.
-struct Lm {
-  double T[12], Tt[12], S[TERMS];
-  double lambda, dmax;
-  int it;
-  bool over;
-
-  PISLAM_HD void begin(const double *sums) {
-PISLAM_UNROLL
-    for (int i = 0; i < TERMS; i++) S[i] = sums[i];
-    lambda = LAMBDA_0, it = 0, over = false;
-  }
-  PISLAM_HD bool next(int iters) {
-    while (!over && it < iters) {
-      it++;
-      double d[6];
-      if (!solve(S, lambda, d)) {
-        lambda = fmin(8.0 * lambda, LAMBDA_MAX);
-        continue;
-      }
-      retract(T, d, Tt);
-      dmax = 0.0;
-PISLAM_UNROLL
-      for (int j = 0; j < 6; j++) dmax = fmax(dmax, fabs(d[j]));
-      return true;
-    }
-    return false;
-  }
-  PISLAM_HD void trial(const double *sums, double eps) {
-    if (sums[27] < S[27]) {
-PISLAM_UNROLL
-      for (int i = 0; i < 12; i++) T[i] = Tt[i];
-PISLAM_UNROLL
-      for (int i = 0; i < TERMS; i++) S[i] = sums[i];
-      lambda = fmax(lambda * 0.25, LAMBDA_MIN);
-    } else {
-      lambda = fmin(8.0 * lambda, LAMBDA_MAX);
-    }
-    if (dmax <= eps) over = true;
-  }
-};
-
-struct Params {
-  int rounds, iters, huber_rounds, min_obs;
-  double eps;
-};
-
-#if !defined(__HIP_DEVICE_COMPILE__)
-// ---- the host's serial form of the whole call for one frame (the probe; never the library's hot path) ---------------
-
+// One frame as the call reads it.
 struct Frame {
   const float *pose_in, *cam, *xw;             // [12], [5], [n][3]
   const int32_t *obs;                          // [n][3]
@@ -213,18 +161,43 @@ struct Frame {
   int nlevels;
   uint32_t n;                                  // already psm::clamp_count(count, stride)
 };
-struct Result {
-  float pose[12];
-  uint32_t ninliers, status;
-  double cost;
-};
 
-// One pass: the 30 sums at Tf in the contract's tree order.  classify: the active flags (and `inlier`) are set anew.
-inline void host_pass(const Frame &F, const float *Tf, bool classify, bool robust, uint8_t *active, double *sums) {
-  static thread_local double p[PARTIALS][SUMS];
-  for (int q = 0; q < PARTIALS; q++)
-    for (int t = 0; t < SUMS; t++) p[q][t] = 0.0;
-  for (uint32_t i = 0; i < F.n; i++) {
+using Params = prf::Params;
+
+// What the Levenberg rule needs of the call (prf::Lm, pislam_refine_math.h).
+struct Rule {
+  static constexpr int STATE = 12, DIM = 6, TERMS = pq::TERMS, RHO = 27;
+  static PISLAM_HD bool solve(const double *S, double lambda, double *d) { return solve_n<6>(S, lambda, d); }
+  static PISLAM_HD void retract(const double *T, const double *d, double *Tn) { pq::retract(T, d, Tn); }
+};
+using Lm = prf::Lm<Rule>;
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// ---- the host's serial form of the whole call for one frame (the probe; never the library's hot path) ---------------
+
+// The frame as prf::host_refine sees it.  A pass reads the pose, then the camera.
+struct Problem : Rule {
+  static constexpr int SUMS = pq::SUMS, BCAST = 12 + 5;
+  Frame F;
+  uint32_t n;
+  explicit Problem(const Frame &F_) : F(F_), n(F_.n) {}
+
+  bool ok() const {
+    bool fin = true;
+    for (int i = 0; i < 12; i++) fin = fin && finite_f(F.pose_in[i]);
+    for (int i = 0; i < 5; i++) fin = fin && finite_f(F.cam[i]);
+    return fin;
+  }
+  void inputs(float *in, float *W) const {
+    for (int i = 0; i < 12; i++) in[i] = F.pose_in[i], W[i] = F.pose_in[i];
+    for (int i = 0; i < 5; i++) W[12 + i] = F.cam[i];
+  }
+  static void pass_words(const double *T, float *W) {
+    for (int i = 0; i < 12; i++) W[i] = (float)T[i];
+  }
+  // Observation i of a pass at W: its active flag (set anew on classification) and what it adds to its partial sums:
+  // the 28 terms, then the count, then chi2.
+  void one(const float *W, uint32_t i, bool classify, bool robust, uint8_t *active, double *a) const {
     float w = 1.0f;
     bool dead = false;
     if (F.level) {
@@ -235,67 +208,21 @@ inline void host_pass(const Frame &F, const float *Tf, bool classify, bool robus
     const float *X = F.xw + 3 * (size_t)i;
     const bool stereo = o[2] != MONO;
     float t[TERMS], chi2 = 0.0f;
-    const bool want = classify || active[i];
     bool live = false;
-    if (!dead && want)
-      live = obs_terms(Tf, F.cam, X[0], X[1], X[2], obs_px(o[0]), obs_px(o[1]), stereo ? obs_px(o[2]) : 0.0f, stereo, w,
+    if (!dead && (classify || *active))
+      live = obs_terms(W, W + 12, X[0], X[1], X[2], obs_px(o[0]), obs_px(o[1]), stereo ? obs_px(o[2]) : 0.0f, stereo, w,
                        robust, t, &chi2);
-    if (classify) active[i] = live && chi2 <= (stereo ? TH_STEREO : TH_MONO);
-    if (!live || !active[i]) continue;
-    double *a = p[i % PARTIALS];
+    if (classify) *active = live && chi2 <= (stereo ? TH_STEREO : TH_MONO);
+    if (!live || !*active) return;
     for (int k = 0; k < TERMS; k++) a[k] += (double)t[k];
     a[28] += 1.0;
     a[29] += (double)chi2;
   }
-  for (int h = PARTIALS / 2; h >= 1; h /= 2)
-    for (int q = 0; q < h; q++)
-      for (int t = 0; t < SUMS; t++) p[q][t] += p[q + h][t];
-  for (int t = 0; t < SUMS; t++) sums[t] = p[0][t];
-}
+};
+using Result = prf::Result<Problem>;
 
 inline void host_frame(const Frame &F, const Params &P, Result *R, uint8_t *inlier) {
-  for (uint32_t i = 0; i < F.n; i++) inlier[i] = 0;
-  for (int i = 0; i < 12; i++) R->pose[i] = F.pose_in[i];
-  R->ninliers = 0, R->cost = 0.0;
-  bool fin = true;
-  for (int i = 0; i < 12; i++) fin = fin && finite_f(F.pose_in[i]);
-  for (int i = 0; i < 5; i++) fin = fin && finite_f(F.cam[i]);
-  if (!fin) {
-    R->status = 2;
-    return;
-  }
-  if (F.n < (uint32_t)P.min_obs) {
-    R->status = 1;
-    return;
-  }
-  Lm L;
-  float Tf[12];
-  double sums[SUMS];
-  uint32_t evals = 0, code = 0;
-  for (int i = 0; i < 12; i++) L.T[i] = (double)F.pose_in[i], Tf[i] = F.pose_in[i];
-  uint8_t *active = inlier;                    // the mask is the active set
-  for (uint32_t i = 0; i < F.n; i++) active[i] = 1;
-  host_pass(F, Tf, false, 0 < P.huber_rounds, active, sums);
-  evals++;
-  for (int r = 0; r < P.rounds; r++) {
-    L.begin(sums);
-    while (L.next(P.iters)) {
-      for (int i = 0; i < 12; i++) Tf[i] = (float)L.Tt[i];
-      host_pass(F, Tf, false, r < P.huber_rounds, active, sums);
-      evals++;
-      L.trial(sums, P.eps);
-    }
-    for (int i = 0; i < 12; i++) Tf[i] = (float)L.T[i];
-    host_pass(F, Tf, true, r + 1 < P.huber_rounds, active, sums);
-    evals++;
-    R->ninliers = (uint32_t)sums[28], R->cost = sums[29];
-    if (r + 1 < P.rounds && R->ninliers < (uint32_t)P.min_obs) {
-      code = 1;
-      break;
-    }
-  }
-  for (int i = 0; i < 12; i++) R->pose[i] = (float)L.T[i];
-  R->status = code | evals << 8;
+  prf::host_refine(Problem(F), P, R, inlier);
 }
 #endif
 

@@ -1,28 +1,25 @@
 // pislam_sim3_refine_kernels.h — batched Sim(3) refinement on the device (pislam_sim3_refine_batch; include/pislam_hip.h,
 // DESIGN.md section 5.5): ORB-SLAM's OptimizeSim3 per (key frame, loop candidate) pair.  The header comment is the
-// contract; the arithmetic is stated once, in pislam_sim3_refine_math.h, for this kernel and for the host probe.
+// contract; the arithmetic is stated once, in pislam_sim3_refine_math.h and, the Levenberg rule, in
+// pislam_refine_math.h, for this kernel and for the host probe.
 //
-// The shape is k_pose_refine's (pislam_pose_kernels.h).  One workgroup of SR_THREADS = 256 runs the whole call for a
-// pair in one launch (all rounds, passes, solves and classifications), then the pair SR_GRID_CAP further on.  No
-// workspace.
-//   * Thread (wave, lane) owns the contract's partial sum q = wave * 4 + lane / 16 + 16 * rev4(lane % 16), that is the
-//     matches q, q + 256, q + 512, ... in ascending order, so the halving tree's steps 128, 64, 32, 16 are four DPP
-//     exchanges inside a row of 16 lanes and the steps 8, 4, 2, 1 combine the 16 row sums through LDS, one sum per lane.
+// The shape is k_pose_refine's (pislam_pose_kernels.h): one workgroup runs the whole call for a pair in one launch, with
+// the launch shape and the partial sum a thread owns of pislam_refine_kernels.h.  The tree and the refused pair are
+// written out here: through prf::tree_sums or prf::refuse this kernel spills 16 or 18 SGPRs where it spilled 14
+// (docs/experiments.md AF).
 //   * A pair of at most SR_RES * 256 = 1024 matches is loaded once and stays in registers over all passes (12 floats
 //     and a flag per match); a larger one is re-read (from L2) in every pass.  The active set is a bit mask per lane.
 //   * A match's forward terms are added to the lane's 38 binary64 accumulators before its backward terms are computed:
 //     36 terms are alive at a time, not 72, and the order of the additions is the contract's.
-//   * Lane 0 runs the 7 x 7 solve, the retraction and the Levenberg rule on state kept in LDS and broadcasts the next
-//     similarity as 14 floats (R, t, s, 1 / s): three barriers per pass.
+//   * Lane 0 runs the 7 x 7 solve, the retraction and the Levenberg rule (prf::Lm) on state kept in LDS and broadcasts
+//     the next similarity as 14 floats (R, t, s, 1 / s): three barriers per pass.
 #pragma once
-#include "pislam_dev.h"
+#include "pislam_refine_kernels.h"
 #include "pislam_sim3_refine_math.h"
 
 namespace sr {
 
-constexpr int SR_THREADS = 256;
 constexpr int SR_RES = 4;                      // register-resident matches per lane
-constexpr int SR_GRID_CAP = 1024;              // workgroups per launch; a larger batch is walked in passes
 constexpr int SR_BCAST = s3m::WORDS + 10;      // the similarity of the pass, then the two cameras
 
 struct SrArgs {
@@ -168,7 +165,7 @@ __device__ __forceinline__ void sr_pair(const SrArgs &A, const SrPair &F, uint32
     PISLAM_ROLLED
     for (;;) {
       if (tid == 0) {
-        const bool go = s_lm->next(iters, fixed);
+        const bool go = s_lm->next(s3r::Rule{fixed}, iters);
         *s_cmd = go ? 1 : 0;
         s3r::pass_words(go ? s_lm->Tt : s_lm->T, s_bc);
       }
@@ -190,7 +187,7 @@ __device__ __forceinline__ void sr_pair(const SrArgs &A, const SrPair &F, uint32
   if (tid == 0) A.ninliers[b] = ninl, A.cost[b] = cost, A.status[b] = code | evals << 8;
 }
 
-__global__ __launch_bounds__(SR_THREADS) void k_sim3_refine(const SrArgs A) {
+__global__ __launch_bounds__(prf::THREADS) void k_sim3_refine(const SrArgs A) {
   __shared__ s3r::Lm s_lm;
   __shared__ double s_part[s3r::SUMS][16];
   __shared__ double s_S[s3r::SUMS + 2];
@@ -201,10 +198,7 @@ __global__ __launch_bounds__(SR_THREADS) void k_sim3_refine(const SrArgs A) {
   for (uint32_t b = blockIdx.x; b < (uint32_t)A.batch; b += gridDim.x) {
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));              // keeps the per-thread predicates out of SGPRs held over the loop
-    const int lane = tid & 63, wave = tid >> 6;
-    const uint32_t l4 = (uint32_t)lane & 15u;
-    const uint32_t rev = (l4 & 1u) << 3 | (l4 & 2u) << 1 | (l4 & 4u) >> 1 | (l4 & 8u) >> 3;
-    const uint32_t q = (uint32_t)wave << 2 | (uint32_t)lane >> 4 | rev << 4;
+    const uint32_t q = prf::partial_of(tid);
     const size_t row = (size_t)b * A.stride;
     SrPair F;
     F.x1 = A.x1 + 3 * row, F.x2 = A.x2 + 3 * row, F.obs1 = A.obs1 + 3 * row, F.obs2 = A.obs2 + 3 * row;
@@ -228,7 +222,7 @@ __global__ __launch_bounds__(SR_THREADS) void k_sim3_refine(const SrArgs A) {
     const bool fin = s_cmd != 0;
     if (!fin || n < (uint32_t)A.p.min_obs) {
       PISLAM_ROLLED
-      for (uint32_t i = tid; i < n; i += SR_THREADS) F.inlier[i] = 0;
+      for (uint32_t i = tid; i < n; i += prf::THREADS) F.inlier[i] = 0;
       if (tid < s3r::STATE) A.sim_out[s3r::STATE * (size_t)b + tid] = v;
       if (tid == 0) A.ninliers[b] = 0, A.cost[b] = 0.0, A.status[b] = fin ? 1u : 2u;
     } else {

@@ -1,9 +1,10 @@
 // pislam_sim3_refine_math.h — the arithmetic of pislam_sim3_refine_batch (include/pislam_hip.h: that comment is the
 // contract), stated ONCE for the device kernel (pislam_sim3_refine_kernels.h) and for a plain C++ compiler (tools/probes/
 // sim3_refine_host_check.cpp): the two sides of a match and their 36 terms in binary32, the 7 x 7 solve, the retraction
-// of a similarity and the Levenberg rule in binary64, and, for the host only, the whole procedure run serially with the
-// contract's tree order.  A match, its camera points and a side's projection are those of pislam_sim3_math.h; the
-// elimination, the Cayley map and the rule's constants are those of pislam_pose_math.h.  Every operation is written out
+// of a similarity in binary64, what the Levenberg rule of pislam_refine_math.h needs of the call (Rule) and, for the
+// host's serial form of the whole procedure there (prf::host_refine), the pair as a Problem.  A match, its camera points
+// and a side's projection are those of pislam_sim3_math.h; the elimination and the Cayley map are those of
+// pislam_pose_math.h.  Every operation is written out
 // one rounding at a time; build with -ffp-contract=off.
 #pragma once
 #include "pislam_sim3_math.h"
@@ -17,7 +18,6 @@ using psm::fsqrt;
 constexpr int DIM = 7;                         // the increment: omega, upsilon, sigma
 constexpr int TERMS = 36;                      // per side: 28 upper-triangle terms, 7 gradient terms, rho
 constexpr int SUMS = 38;                       // + the number of active matches that are not dead, + their chi2
-constexpr int PARTIALS = 256;
 constexpr int STATE = 13;                      // R row-major, t, s
 constexpr int MAX_STRIDE = pq::MAX_STRIDE;
 constexpr int MAX_LEVELS = pq::MAX_LEVELS;
@@ -124,137 +124,71 @@ PISLAM_UNROLL
   Tn[12] = k * T[12];
 }
 
-// The pose call's Levenberg rule on the 7-dimensional increment: begin() takes the sums at the round's similarity,
-// next() asks for the next trial (false: the round is over), trial() takes the sums at it.
-struct Lm {
-  double T[STATE], Tt[STATE], S[TERMS];
-  double lambda, dmax;
-  int it;
-  bool over;
-
-  PISLAM_HD void begin(const double *sums) {
-PISLAM_UNROLL
-    for (int i = 0; i < TERMS; i++) S[i] = sums[i];
-    lambda = pq::LAMBDA_0, it = 0, over = false;
-  }
-  PISLAM_HD bool next(int iters, bool fixed_scale) {
-    while (!over && it < iters) {
-      it++;
-      double d[DIM];
-      if (!(pq::solve_n<DIM>(S, lambda, d, fixed_scale) && fabs(d[6]) < 2.0)) {
-        lambda = fmin(8.0 * lambda, pq::LAMBDA_MAX);
-        continue;
-      }
-      retract(T, d, Tt);
-      dmax = 0.0;
-PISLAM_UNROLL
-      for (int j = 0; j < DIM; j++) dmax = fmax(dmax, fabs(d[j]));
-      return true;
-    }
-    return false;
-  }
-  PISLAM_HD void trial(const double *sums, double eps) {
-    if (sums[35] < S[35]) {
-PISLAM_UNROLL
-      for (int i = 0; i < STATE; i++) T[i] = Tt[i];
-PISLAM_UNROLL
-      for (int i = 0; i < TERMS; i++) S[i] = sums[i];
-      lambda = fmax(lambda * 0.25, pq::LAMBDA_MIN);
-    } else {
-      lambda = fmin(8.0 * lambda, pq::LAMBDA_MAX);
-    }
-    if (dmax <= eps) over = true;
-  }
-};
-
-#if !defined(__HIP_DEVICE_COMPILE__)
-// ---- the host's serial form of the whole call for one pair (the probe; never the library's hot path) ----------------
-
+// One pair as the call reads it.
 struct Pair {
   const float *sim_in;                         // [13]
   s3m::Pair m;                                 // the matches as the RANSAC call reads them (b is not used)
   const uint8_t *mask;                         // [n] or null
 };
-struct Result {
-  float sim[STATE];
-  uint32_t ninliers, status;
-  double cost;
-};
 
-// One pass: the 38 sums at Sf in the contract's tree order.  classify: the active flags (and `inlier`) are set anew.
-inline void host_pass(const Pair &F, const float *Sf, float th2, bool classify, bool robust, uint8_t *active, double *sums) {
-  static thread_local double p[PARTIALS][SUMS];
-  for (int q = 0; q < PARTIALS; q++)
-    for (int t = 0; t < SUMS; t++) p[q][t] = 0.0;
-  const s3m::Pair &M = F.m;
-  const s3m::Cam C1 = s3m::make_cam(M.cam1), C2 = s3m::make_cam(M.cam2);
-  for (uint32_t i = 0; i < M.n; i++) {
+// What the Levenberg rule needs of the call (prf::Lm, pislam_refine_math.h).
+struct Rule {
+  static constexpr int STATE = s3r::STATE, DIM = s3r::DIM, TERMS = s3r::TERMS, RHO = 35;
+  bool fixed_scale;
+  // A fixed scale pins sigma to 0; |sigma| < 2 keeps the scale factor of the retraction positive and finite.
+  PISLAM_HD bool solve(const double *S, double lambda, double *d) const {
+    return pq::solve_n<DIM>(S, lambda, d, fixed_scale) && fabs(d[6]) < 2.0;
+  }
+  static PISLAM_HD void retract(const double *T, const double *d, double *Tn) { s3r::retract(T, d, Tn); }
+};
+using Lm = prf::Lm<Rule>;
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+// ---- the host's serial form of the whole call for one pair (the probe; never the library's hot path) ----------------
+
+// The pair as prf::host_refine sees it.  A pass reads the similarity in s3m's stored form (R, t, s, 1 / s), then the
+// two cameras.
+struct Problem : Rule {
+  static constexpr int SUMS = s3r::SUMS, BCAST = s3m::WORDS + 10;
+  Pair F;
+  uint32_t n;
+  float th2;
+  Problem(const Pair &F_, const Params &P) : Rule{P.fixed_scale != 0}, F(F_), n(F_.m.n), th2(P.th2) {}
+
+  bool ok() const { return sim_ok(F.sim_in) && s3m::cam_ok(F.m.cam1) && s3m::cam_ok(F.m.cam2); }
+  void inputs(float *in, float *W) const {
+    for (int i = 0; i < STATE; i++) in[i] = F.sim_in[i], W[i] = F.sim_in[i];
+    W[13] = fdiv(1.0f, W[12]);
+    for (int i = 0; i < 5; i++) W[s3m::WORDS + i] = F.m.cam1[i], W[s3m::WORDS + 5 + i] = F.m.cam2[i];
+  }
+  static void pass_words(const double *T, float *W) { s3r::pass_words(T, W); }
+  // Match i of a pass at W: its active flag (set anew on classification) and what it adds to its partial sums: the 36
+  // forward terms, then the 36 backward terms, then the count, the forward chi2, the backward chi2.
+  void one(const float *W, uint32_t i, bool classify, bool robust, uint8_t *active, double *a) const {
+    const s3m::Pair &M = F.m;
+    const s3m::Cam C1 = s3m::make_cam(W + s3m::WORDS), C2 = s3m::make_cam(W + s3m::WORDS + 5);
     s3m::Match m = s3m::match(M.x1 + 3 * (size_t)i, M.x2 + 3 * (size_t)i, M.obs1 + 3 * (size_t)i, M.obs2 + 3 * (size_t)i,
                               M.level1 ? M.level1 + i : nullptr, M.level1 ? M.level2 + i : nullptr, M.inv_sigma2, M.nlevels);
     if (F.mask && !F.mask[i]) m.live = false;
     s3m::Side f{}, b{};
     bool live = false;
-    if (classify || active[i]) live = sides(Sf, C1, C2, m, &f, &b);
-    if (classify) active[i] = live && f.chi2 <= th2 && b.chi2 <= th2;
-    if (!live || !active[i]) continue;
-    double *a = p[i % PARTIALS];
+    if (classify || *active) live = sides(W, C1, C2, m, &f, &b);
+    if (classify) *active = live && f.chi2 <= th2 && b.chi2 <= th2;
+    if (!live || !*active) return;
     float t[TERMS];
     forward_terms(C1, f, m.w1, robust, th2, t);
     for (int k = 0; k < TERMS; k++) a[k] += (double)t[k];
-    backward_terms(Sf, C2, m.X1, b, m.w2, robust, th2, t);
+    backward_terms(W, C2, m.X1, b, m.w2, robust, th2, t);
     for (int k = 0; k < TERMS; k++) a[k] += (double)t[k];
     a[36] += 1.0;
     a[37] += (double)f.chi2;
     a[37] += (double)b.chi2;
   }
-  for (int h = PARTIALS / 2; h >= 1; h /= 2)
-    for (int q = 0; q < h; q++)
-      for (int t = 0; t < SUMS; t++) p[q][t] += p[q + h][t];
-  for (int t = 0; t < SUMS; t++) sums[t] = p[0][t];
-}
+};
+using Result = prf::Result<Problem>;
 
 inline void host_pair(const Pair &F, const Params &P, Result *R, uint8_t *inlier) {
-  const uint32_t n = F.m.n;
-  for (uint32_t i = 0; i < n; i++) inlier[i] = 0;
-  for (int i = 0; i < STATE; i++) R->sim[i] = F.sim_in[i];
-  R->ninliers = 0, R->cost = 0.0;
-  if (!(sim_ok(F.sim_in) && s3m::cam_ok(F.m.cam1) && s3m::cam_ok(F.m.cam2))) {
-    R->status = 2;
-    return;
-  }
-  if (n < (uint32_t)P.min_obs) {
-    R->status = 1;
-    return;
-  }
-  Lm L;
-  float Sf[s3m::WORDS];
-  double sums[SUMS];
-  uint32_t evals = 0, code = 0;
-  for (int i = 0; i < STATE; i++) L.T[i] = (double)F.sim_in[i];
-  uint8_t *active = inlier;                    // the mask is the active set
-  for (uint32_t i = 0; i < n; i++) active[i] = 1;
-  pass_words(L.T, Sf);
-  host_pass(F, Sf, P.th2, false, 0 < P.huber_rounds, active, sums);
-  evals++;
-  for (int r = 0; r < P.rounds; r++) {
-    L.begin(sums);
-    while (L.next(P.iters, P.fixed_scale != 0)) {
-      pass_words(L.Tt, Sf);
-      host_pass(F, Sf, P.th2, false, r < P.huber_rounds, active, sums);
-      evals++;
-      L.trial(sums, P.eps);
-    }
-    pass_words(L.T, Sf);
-    host_pass(F, Sf, P.th2, true, r + 1 < P.huber_rounds, active, sums);
-    evals++;
-    R->ninliers = (uint32_t)sums[36], R->cost = sums[37];
-    if (r + 1 < P.rounds && R->ninliers < (uint32_t)P.min_obs) {
-      code = 1;
-      break;
-    }
-  }
-  for (int i = 0; i < STATE; i++) R->sim[i] = (float)L.T[i];
-  R->status = code | evals << 8;
+  prf::host_refine(Problem(F, P), P, R, inlier);
 }
 #endif
 

@@ -416,7 +416,7 @@ def pin_frames():
                                                     TH_STEREO / F32(4), np.nextafter(TH_STEREO, F32(9)) / F32(4)]]).astype(F32)
     out = []
     big, _, _ = scene(11, n=PIN_STRIDE, stereo=0.5)
-    for n in (0, 1, 2, 9, 10, 255, 256, 257, 513, 2049):
+    for n in (0, 1, 2, 9, 10, 255, 256, 257, 513, 2048, 2049):           # 2048: the last register-resident count
         out.append(("n%d" % n, sub(big, n), n))
     out.append(("invalid count", sub(big, 40), COUNT_INVALID))
     out.append(("count above stride", big, -1))                         # the caller passes stride + 7
@@ -482,6 +482,35 @@ def pin_reference(prm, with_level):
     return out
 
 
+# One workgroup's LDS over refused and refined frames: 1026 frames at a stride of 16, so that workgroups 0 and 1 run two
+# frames each (b and b + 1024).  Workgroup 0: a refused frame (a non-finite pose, status 2), then a valid one; workgroup
+# 1: a valid frame that runs all its rounds, then a refused one (a count below min_obs, status 1).  The other 1022 frames
+# are 13 valid variants of 4 .. 16 observations.
+REUSE_B, REUSE_STRIDE, REUSE_PRM = 1026, 16, (3, 4, 2, 3, 1e-6)
+
+
+@functools.lru_cache(maxsize=None)
+def reuse_batch():
+    """(the distinct frames, their restated results, the index of each of the 1026 frames into them)."""
+    distinct = [sub(scene(70 + k, n=16, stereo=0.5, outliers=0.1)[0], 4 + k) for k in range(13)]
+    bad = dict(distinct[12], pose=distinct[12]["pose"].copy())
+    bad["pose"][7] = np.nan
+    full = scene(90, n=16, stereo=0.5, outliers=0.0)[0]
+    distinct += [bad, full, sub(distinct[5], 2)]
+    which = [b % 13 for b in range(REUSE_B)]
+    which[0], which[1], which[1025] = 13, 14, 15
+    want = [ref_frame(f, REUSE_PRM) for f in distinct]
+    return distinct, want, which
+
+
+def test_reuse_batch_is_what_it_says():
+    distinct, want, which = reuse_batch()
+    assert want[13]["status"] == 2 and want[15]["status"] == 1                            # refused: no pass at all
+    assert want[14]["status"] & 255 == 0 and want[14]["status"] >> 8 > 1 + REUSE_PRM[0]   # all rounds, and trial passes
+    assert all(w["status"] >> 8 > 0 for w in want[:13])                                   # not refused
+    assert [which[b] for b in (0, 1024, 1, 1025)] == [13, 1024 % 13, 14, 15]
+
+
 def hexf(a):
     return " ".join("%08x" % v for v in np.asarray(a, F32).reshape(-1).view(np.uint32))
 
@@ -524,6 +553,9 @@ def test_host_probe_against_the_restatement(tmp_path):
                 f = sub(fr, clamp_count(count, PIN_STRIDE))
                 lines.append(probe_line(f if with_level else dict(f, level=None, tab=None), prm))
                 want.append(result_line(r))
+    for f, r in zip(*reuse_batch()[:2]):
+        lines.append(probe_line(f, REUSE_PRM))
+        want.append(result_line(r))
     cases = tmp_path / "cases.txt"
     cases.write_text("\n".join(lines) + "\n")
     got = subprocess.run([exe, str(cases)], check=True, capture_output=True, text=True).stdout.splitlines()
@@ -686,6 +718,37 @@ def test_pose_refine_pins(gpu_ctx, prm, with_level):
     if prm == DEFAULT:
         codes = [w["status"] & 255 for w in want]
         assert 0 in codes and 1 in codes and 2 in codes
+
+
+@pytest.mark.gpu
+def test_pose_refine_lds_reuse_after_refused_frames(gpu_ctx):
+    """A workgroup that refuses a frame and then refines one, and one that refines a frame and then refuses one (see
+    reuse_batch): every output word of all 1026 frames."""
+    distinct, want, which = reuse_batch()
+    frames = [distinct[k] for k in which]
+    ns = [len(f["obs"]) for f in frames]
+    got = Device(gpu_ctx).run(frames, ns, REUSE_STRIDE, REUSE_PRM)
+    assert_frames(got, [want[k] for k in which], ns, "lds reuse")
+
+
+@pytest.mark.gpu
+def test_pose_refine_reports_the_first_bad_parameter(gpu_ctx):
+    """Two parameters bad at once: the text is that of the check that comes first (rounds, iters, huber_rounds, min_obs,
+    eps, the level table, batch, stride)."""
+    d = Device(gpu_ctx)
+    dev = d.upload(d.pack([scene(41, n=8)[0]], [8], 8))
+    o = d.sentinels(1, 8)
+    nan = float("nan")
+    for prm, kw, B, text in (((0, 10, 0, 10, -1.0), {}, 1, "rounds must be 1..8"),
+                             ((4, 0, 9, 10, 1e-6), {}, 1, "iters must be 1..32"),
+                             ((4, 10, 5, 2, 1e-6), {}, 1, "huber_rounds must be 0..rounds"),
+                             ((4, 10, 3, 16385, nan), {}, 1, "min_obs must be 3..16384"),
+                             ((4, 10, 3, 10, nan), dict(tab=None), 1, "eps must be >= 0"),
+                             (DEFAULT, dict(tab=None), -1, "level needs inv_sigma2 with 1..16 entries")):
+        assert d.call(prm, dev, 8, B, o, **kw) == -1
+        assert d.lib.pislam_last_error(gpu_ctx.h).decode() == text, (prm, kw)
+    gpu_ctx.synchronize()
+    assert (o["status"].cpu().numpy() == SENT32).all()
 
 
 @pytest.mark.gpu

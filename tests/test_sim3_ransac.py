@@ -905,6 +905,22 @@ def test_sim3_camera_points():
 
 
 @pytest.mark.gpu
+def test_sim3_reports_the_first_bad_level_argument(gpu_ctx):
+    """Two arguments bad at once: fixed_scale comes before the level pointers, the pointers before the table, the table
+    before the batch."""
+    d = Device(gpu_ctx)
+    dev = d.upload(d.pack([scene(41, n=8, levels=True)[0]], [8], 8))
+    o = d.sentinels(1, 8)
+    for prm, kw, B, text in (((8, 0, 20, 2), dict(level2=None), 1, "fixed_scale must be 0 or 1"),
+                             ((8, 0, 20, 0), dict(level1=None, tab=None), 1, "level1 and level2 go together"),
+                             ((8, 0, 20, 0), dict(tab=None), -1, "levels need inv_sigma2 with 1..16 entries")):
+        assert d.call(prm, dev, 8, B, o, **kw) == -1
+        assert d.lib.pislam_last_error(gpu_ctx.h).decode() == text, (prm, kw)
+    gpu_ctx.synchronize()
+    assert (o["status"].cpu().numpy() == SENT32).all()
+
+
+@pytest.mark.gpu
 def test_sim3_invalid_arguments_write_nothing(gpu_ctx):
     d = Device(gpu_ctx)
     t = d.torch

@@ -589,6 +589,38 @@ def pin_reference(prm, with_level):
 
 PIN_CONFIGS = [(p, True) for p in PIN_PARAMS] + [(DEFAULT, False), (PIN_PARAMS[1], False)]
 
+# One workgroup's LDS over refused and refined pairs: 1026 pairs at a stride of 16, so that workgroups 0 and 1 run two
+# pairs each (b and b + 1024).  Workgroup 0: a refused pair (s = NaN, status 2), then a valid one; workgroup 1: a valid
+# pair that runs all its rounds, then a refused one (a count below min_obs, status 1).  The other 1022 pairs are 13 valid
+# variants of 4 .. 16 matches, some with a mask.
+REUSE_B, REUSE_STRIDE, REUSE_PRM = 1026, 16, (3, 4, 2, 3, 10.0, 0, 1e-6)
+
+
+@functools.lru_cache(maxsize=None)
+def reuse_batch():
+    """(the distinct (pair, sim_in, mask), their restated results, the index of each of the 1026 pairs into them)."""
+    distinct = []
+    for k in range(13):
+        pr, truth, _ = scene(70 + k, n=16, outliers=0.1, levels=True)
+        distinct.append((sub(pr, 4 + k), truth_sim(truth, 0.01, 0.05, 0.02, seed=k), with_mask(4 + k, k) if k % 4 == 3 else None))
+    bad = distinct[12][1].copy()
+    bad[12] = np.nan
+    pr, truth, _ = scene(90, n=16, outliers=0.0, levels=True)
+    distinct += [(distinct[12][0], bad, None), (pr, truth_sim(truth, 0.01, 0.05, 0.02, seed=20), None),
+                 (sub(distinct[5][0], 2), distinct[5][1], None)]
+    which = [b % 13 for b in range(REUSE_B)]
+    which[0], which[1], which[1025] = 13, 14, 15
+    want = [ref_refine(pr, sim, REUSE_PRM, mask) for pr, sim, mask in distinct]
+    return distinct, want, which
+
+
+def test_reuse_batch_is_what_it_says():
+    distinct, want, which = reuse_batch()
+    assert want[13]["status"] == 2 and want[15]["status"] == 1                            # refused: no pass at all
+    assert want[14]["status"] & 255 == 0 and want[14]["status"] >> 8 > 1 + REUSE_PRM[0]   # all rounds, and trial passes
+    assert all(w["status"] >> 8 > 0 for w in want[:13])                                   # not refused
+    assert [which[b] for b in (0, 1024, 1, 1025)] == [13, 1024 % 13, 14, 15]
+
 
 def test_pin_cases_cover_the_codes():
     names = [c[0] for c in pin_cases()]
@@ -626,6 +658,9 @@ def test_host_probe_against_the_restatement(run_probe):
             pr, sim, mask = pin_pair(c, with_level)
             lines.append(probe_line(pr, sim, prm, mask))
             want.append(result_line(r))
+    for (pr, sim, mask), r in zip(*reuse_batch()[:2]):
+        lines.append(probe_line(pr, sim, REUSE_PRM, mask))
+        want.append(result_line(r))
     got = run_probe(lines)
     for k, (g, w) in enumerate(zip(got, want)):
         assert g == w, "case %d: %s" % (k, lines[k][:60])
@@ -889,6 +924,40 @@ def test_sim3_refine_pins(gpu_ctx, prm, with_level):
     trip = [pin_pair(c, with_level) for c in cases]
     got = Device(gpu_ctx).run(trip, [c[4] if c[4] != -1 else PIN_STRIDE + 7 for c in cases], PIN_STRIDE, prm, with_level)
     assert_pairs(got, pin_reference(prm, with_level), [len(t[0]["obs1"]) for t in trip], "%r" % (prm,))
+
+
+@pytest.mark.gpu
+def test_sim3_refine_lds_reuse_after_refused_pairs(gpu_ctx):
+    """A workgroup that refuses a pair and then refines one, and one that refines a pair and then refuses one (see
+    reuse_batch): every output word of all 1026 pairs."""
+    distinct, want, which = reuse_batch()
+    trip = [distinct[k] for k in which]
+    ns = [len(t[0]["obs1"]) for t in trip]
+    got = Device(gpu_ctx).run(trip, ns, REUSE_STRIDE, REUSE_PRM)
+    assert_pairs(got, [want[k] for k in which], ns, "lds reuse")
+
+
+@pytest.mark.gpu
+def test_sim3_refine_reports_the_first_bad_parameter(gpu_ctx):
+    """Two parameters bad at once: the text is that of the check that comes first (rounds, iters, huber_rounds, min_obs,
+    th2, fixed_scale, eps, the level pointers, the level table, batch, stride)."""
+    d = Device(gpu_ctx)
+    dev = d.upload(d.pack([(scene(41, n=8, levels=True)[0], IDENTITY, None)], [8], 8))
+    o = d.sentinels(1, 8)
+    nan = float("nan")
+    for prm, kw, B, text in (((0, 5, 0, 10, 10.0, 0, -1.0), {}, 1, "rounds must be 1..8"),
+                             ((2, 33, 3, 10, 10.0, 0, 1e-6), {}, 1, "iters must be 1..32"),
+                             ((2, 5, 3, 2, 10.0, 0, 1e-6), {}, 1, "huber_rounds must be 0..rounds"),
+                             ((2, 5, 2, 2, 0.0, 0, 1e-6), {}, 1, "min_obs must be 3..16384"),
+                             ((2, 5, 2, 10, nan, 2, nan), {}, 1, "th2 must be finite and > 0"),
+                             ((2, 5, 2, 10, 10.0, 2, nan), {}, 1, "fixed_scale must be 0 or 1"),
+                             ((2, 5, 2, 10, 10.0, 0, nan), dict(level2=None), 1, "eps must be >= 0"),
+                             (DEFAULT, dict(level2=None, tab=None), 1, "level1 and level2 go together"),
+                             (DEFAULT, dict(tab=None), -1, "levels need inv_sigma2 with 1..16 entries")):
+        assert d.call(prm, dev, 8, B, o, **kw) == -1
+        assert d.lib.pislam_last_error(gpu_ctx.h).decode() == text, (prm, kw)
+    gpu_ctx.synchronize()
+    assert (o["status"].cpu().numpy() == SENT32).all()
 
 
 @pytest.mark.gpu

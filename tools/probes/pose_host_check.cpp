@@ -56,7 +56,7 @@ int main(int argc, char **argv) {
     uint64_t cost_bits;
     memcpy(&cost_bits, &R.cost, 8);
     printf("%" PRIu32 " %" PRIu32 " %016" PRIx64, R.status, R.ninliers, cost_bits);
-    for (int i = 0; i < 12; i++) pr_f32(R.pose[i]);
+    for (int i = 0; i < 12; i++) pr_f32(R.state[i]);
     printf(" ");
     if (n == 0) printf("-");
     for (long long i = 0; i < n; i++) putchar(inlier[(size_t)i] ? '1' : '0');
