@@ -1761,6 +1761,174 @@ int pislam_sim3_refine_batch(pislam_ctx *ctx, const pislam_sim3_refine_params *p
                              const uint8_t *mask, const float *inv_sigma2, int nlevels, size_t stride, int batch,
                              float *sim_out, uint8_t *inlier, uint32_t *ninliers, double *cost, uint32_t *status);
 
+/* ---- new map points from two key frames: the epipolar search -------------- */
+
+/* The epipolar geometry of a key-frame pair (host only, pure, no context; stated to a tolerance, not bit for bit, like
+ * pislam_two_view_decompose).  pose1, pose2: float [12], r0 .. r8 row-major, then t, Xc = R Xw + t (the pose call's
+ * layout); cam1, cam2: float [4], fx, fy, cx, cy.  f12: float [9], row-major, with x1' F12 x2 = 0 for level-0 pixels x1 =
+ * (u1, v1, 1) of key frame 1 and x2 of key frame 2: F12 = K1^-T [t12]x R12 K2^-1 with R12 = R1 R2', t12 = t1 - R12 t2
+ * (ORB-SLAM's ComputeF12).  epipole: float [2], the centre of camera 1, -R1' t1, projected into image 2.  Everything is
+ * computed in binary64 from the inputs converted exactly and rounded once to binary32: an entry of f12 is within one
+ * binary32 ulp of the largest |entry| of the exact matrix, an epipole coordinate within one ulp of its own exact value.
+ * An epipole behind camera 2 or at infinity is returned as it comes out: it may be infinite or a NaN, and that is legal
+ * input below.  PISLAM_ERR_INVALID: a NULL pointer, an input that is not finite, or an fx or fy equal to 0. */
+int pislam_epipolar_from_poses(const float *pose1, const float *pose2, const float *cam1, const float *cam2, float *f12,
+                               float *epipole);
+
+/* Epipolar search: ORB-SLAM's ORBmatcher::SearchForTriangulation without its selection tail,
+ * which pislam_match_select_batch applies as it does for every matcher (the distance threshold too: ORB-SLAM tests it
+ * before the geometry, and thresholding the best candidate gives the same winner).  It is the word-guided matcher with a
+ * geometric test on every candidate: pairs, qdesc / tdesc, qgroup / tgroup, ngroups, counts and strides are exactly those
+ * of pislam_match_hamming_bow_batch, and so are idx, dist and dist2 with their tie rule dist << 16 | j.  Pair b is (key
+ * frame 1 = the query side, key frame 2 = the train side).  In addition, all device unless said:
+ *   qobs_q8, tobs_q8  int32 [batch][stride][3]: (u, v, u_right) in Q8 level-0 pixels, read as pislam_pose_refine_batch
+ *                     reads obs_q8: u and v clamped to [-2^22, 2^22], then float(q) * (1.0f / 256.0f) (exact); u_right
+ *                     == INT32_MIN marks a MONOCULAR keypoint, nothing else of u_right is read.
+ *   qlevel, tlevel    uint8 [batch][stride]: the pyramid level of each keypoint.
+ *   qmask, tmask      uint8 [batch][stride] or NULL: a keypoint takes part iff its byte is non-zero ("has no map point
+ *                     yet"); NULL: every keypoint takes part.
+ *   f12, epipole      float [batch][9] and [batch][2], as pislam_epipolar_from_poses writes them.
+ *   level_sigma2, level_scale   HOST float [nlevels], 1 <= nlevels <= 16, read during the call and carried by value in
+ *                     the kernel arguments (a captured graph keeps its own copy).
+ *   p                 HOST struct: chi2 (ORB-SLAM: 3.84f) and epipole_r2 (ORB-SLAM: 100.0f).
+ * A pair whose nine f12 words are not all finite has no candidates.  In binary32, one rounding per written operation,
+ * in the order the parentheses give, no fused multiply-add; every comparison is false for a NaN.  Per query i with the
+ * pixel (u1, v1), once:
+ *   a = (u1*F0 + v1*F3) + F6,  b = (u1*F1 + v1*F4) + F7,  c = (u1*F2 + v1*F5) + F8,  den = a*a + b*b
+ * Train j with the pixel (u2, v2) on level lt = tlevel[j] is a candidate for query i iff
+ *   qgroup[i] == tgroup[j] and both are below ngroups (the word-guided matcher's rule), and
+ *   qmask is NULL or qmask[i] != 0, and tmask is NULL or tmask[j] != 0, and
+ *   qlevel[i] < nlevels and lt < nlevels, and
+ *   with num = (a*u2 + b*v2) + c:  num*num < (chi2*level_sigma2[lt])*den    (no division; den == 0 fails), and
+ *   NOT (both keypoints are monocular and dx*dx + dy*dy < epipole_r2*level_scale[lt]), dx = ex - u2, dy = ey - v2,
+ *   (ex, ey) = epipole (an epipole that is not finite excludes nothing).
+ * Best and second are taken over these candidates only.  A query that takes no part (its mask byte is 0, its level or
+ * group has no entry, its pair's f12 is not finite) writes idx -1 and dist and dist2 0xffffffff; entries at and beyond
+ * nq_b are not written.  With chi2 = +inf, epipole_r2 = 0, NULL masks, every level below nlevels and a line with den > 0
+ * (and num*num finite) for every query, the outputs equal pislam_match_hamming_bow_batch's word for word.
+ * Limits: those of pislam_match_hamming_bow_batch (words in {1,2,4,8}; 1 <= ngroups <= 16384; t_stride <= 65535;
+ * q_stride < 2^31; batch 0..65535); chi2 > 0 (+inf is allowed), epipole_r2 >= 0; level_sigma2 and level_scale finite
+ * and > 0, level_scale non-decreasing.  Offsets use size_t arithmetic throughout.  Any violation, or a NULL or host
+ * pointer where a device pointer is required (the masks alone may be NULL): PISLAM_ERR_INVALID, before anything is
+ * launched or written.  Asynchronous on the context stream; the workspace is the context's own for this call (not the
+ * word-guided matcher's) and grows on demand, which synchronises; after pislam_match_epipolar_reserve of the same or a
+ * larger shape the call allocates nothing and never synchronises, so it can be captured into a hipGraph.
+ *
+ * Not here: the baseline test that skips a key-frame pair (the caller's), the rotation histogram and the uniqueness of
+ * SearchForTriangulation's tail (pislam_match_select_batch), ORBmatcher::Fuse, and local bundle adjustment. */
+typedef struct pislam_epipolar_params {
+  float chi2;       /* > 0, +inf allowed: squared distance to the epipolar line in units of level_sigma2 (ORB-SLAM: 3.84f) */
+  float epipole_r2; /* >= 0: two monocular keypoints are not matched this close to the epipole, times level_scale (100.0f) */
+} pislam_epipolar_params;
+int pislam_match_epipolar_reserve(pislam_ctx *ctx, int words, int ngroups, size_t t_stride, int batch);
+int pislam_match_hamming_epipolar_batch(pislam_ctx *ctx, int words, int ngroups, const pislam_epipolar_params *p,
+                                        const float *level_sigma2, const float *level_scale, int nlevels, const float *f12,
+                                        const float *epipole, const uint32_t *qdesc, const uint32_t *qgroup,
+                                        const int32_t *qobs_q8, const uint8_t *qlevel, const uint8_t *qmask,
+                                        const uint32_t *qcounts, size_t q_stride, const uint32_t *tdesc,
+                                        const uint32_t *tgroup, const int32_t *tobs_q8, const uint8_t *tlevel,
+                                        const uint8_t *tmask, const uint32_t *tcounts, size_t t_stride, int batch,
+                                        int32_t *idx, uint32_t *dist, uint32_t *dist2);
+
+/* ---- new map points from two key frames: triangulation and stereo unprojection ---- */
+
+/* The geometry of ORB-SLAM's LocalMapping::CreateNewMapPoints: per pair of key frames with
+ * known poses, every selected match of two keypoints that have no map point yet becomes a map point or is refused.  The
+ * point is triangulated, or unprojected from a stereo observation when that gives more parallax; it then has to lie in
+ * front of both cameras, reproject within the per-level bound in both, and sit at distances that fit the two pyramid
+ * levels.  The reference ships nothing of the kind: the semantics are this library's own, stated so that individually
+ * rounded binary32 operations reproduce every output word.  This comment is the contract.  "float(v)" converts an
+ * integer to binary32; every +, -, *, / and sqrt below is ONE binary32 operation rounded to nearest even, in the order
+ * the parentheses give (a + b + c means (a + b) + c); no fused multiply-add, no reciprocal or fast approximation: the
+ * division and the square root are the correctly rounded ones; denormals are kept.  Every comparison is false for a NaN.
+ *
+ * Inputs, all device unless said.  Pair b has n = min(counts[b], stride) slots (counts: uint32 [batch],
+ * PISLAM_COUNT_INVALID counts as 0); slot s is one selected match.
+ *   pose1, pose2    float [batch][12]: r0 .. r8 row-major, then t0 .. t2; Xc = R Xw + t (the pose call's layout).
+ *   cam1, cam2      float [batch][5]: fx, fy, cx, cy, bf in level-0 pixels, one camera per key frame.
+ *   obs1_q8, obs2_q8  int32 [batch][stride][3]: (u, v, u_right) in Q8 level-0 pixels, read exactly as
+ *                   pislam_pose_refine_batch reads obs_q8: each clamped to [-2^22, 2^22], then float(q) * (1.0f / 256.0f)
+ *                   (exact); u_right == INT32_MIN (tested before the clamp) marks a monocular keypoint.
+ *   level1, level2  uint8 [batch][stride]: the pyramid level of each keypoint.
+ *   level_scale, level_sigma2   HOST float [nlevels], 1 <= nlevels <= 16 (ORB-SLAM's mvScaleFactors and mvLevelSigma2),
+ *                   read during the call and carried by value in the kernel arguments.
+ *
+ * Per pair, with R1, t1, R2, t2 the two poses and (fx_k, fy_k, cx_k, cy_k, bf_k) = cam_k:
+ *   c_(3i+j) = (R2_(3i)*R1_(3j) + R2_(3i+1)*R1_(3j+1)) + R2_(3i+2)*R1_(3j+2)        R21 = R2 R1', row-major, i, j = 0..2
+ *   c_(9+i)  = t2_i - ((c_(3i)*t1_0 + c_(3i+1)*t1_1) + c_(3i+2)*t1_2)               t21 = t2 - R21 t1
+ *   O1_j = -((R1_j*t1_0 + R1_(3+j)*t1_1) + R1_(6+j)*t1_2), O2 likewise from R2, t2  the camera centres, -R' t
+ *   ifx_k = 1.0f / fx_k,  ify_k = 1.0f / fy_k,  hb_k = (bf_k / fx_k) * 0.5f          (half the stereo baseline)
+ * A pair with a pose or camera word that is not finite, or with an fx or fy equal to 0, gives every slot the status 9
+ * and evaluates nothing.
+ *
+ * Per slot, `status` is the code of the first test that fails, or 0.  With l_k = level_k, (u_k, v_k, ur_k) the slot's
+ * observation in key frame k:
+ *  1. Status 1 (NO_LEVEL) if l_1 >= nlevels or l_2 >= nlevels.
+ *  2. x_k = (u_k - cx_k)*ifx_k,  y_k = (v_k - cy_k)*ify_k;  bb = (x_2*x_2 + y_2*y_2) + 1.0f;
+ *     a_i = (c_(3i)*x_1 + c_(3i+1)*y_1) + c_(3i+2)   (a = R21 (x_1, y_1, 1));
+ *     cs = ((a_0*x_2 + a_1*y_2) + a_2) / sqrt(((a_0*a_0 + a_1*a_1) + a_2*a_2) * bb)     the cosine of the two rays
+ *     (pislam_two_view_reconstruct_batch's formula, with each side's own camera).
+ *  3. Side k is STEREO iff its u_right is not INT32_MIN and d_k = u_k - ur_k > 0.0f.  Then zs_k = bf_k / d_k and
+ *     cs_k = (zs_k*zs_k - hb_k*hb_k) / (zs_k*zs_k + hb_k*hb_k)  (= cos(2 atan(hb_k / zs_k)), without a trigonometric
+ *     call).  A side that is not stereo is monocular in every step below and has cs_k = cs + 1.0f.
+ *  4. mn = cs_2 < cs_1 ? cs_2 : cs_1.  The mode is
+ *       TRIANGULATE  iff cs < mn and cs > 0.0f and (side 1 is stereo or side 2 is stereo or cs < cos_min_parallax),
+ *       else STEREO1 iff side 1 is stereo and cs_1 < cs_2,
+ *       else STEREO2 iff side 2 is stereo and cs_2 < cs_1,
+ *       else status 2 (LOW_PARALLAX).
+ *  5. The point.  TRIANGULATE: the midpoint X of the two rays' closest points in frame 1, which is
+ *     pislam_two_view_reconstruct_batch's n, nn, p, q, z1, z2, g, h and X word for word with r = c_0 .. c_8,
+ *     t = c_9 .. c_11, (x1, y1) = (x_1, y_1), (x2, y2) = (x_2, y_2); then with e = X - t1 (three subtractions)
+ *     Xw_j = (R1_j*e_0 + R1_(3+j)*e_1) + R1_(6+j)*e_2.  (Both poses the identity but t2 = (-1, 0, 0), both cameras
+ *     (1, 1, 0, 0, 0), (u_1, v_1) = (0, 0), (u_2, v_2) = (-0.5, 0): z1 = z2 = 2 and Xw = (0, 0, 2).)
+ *     STEREOk: X = (x_k*zs_k, y_k*zs_k, zs_k) in frame k, to the world the same way with Rk, tk.
+ *     Status 3 (NOT_FINITE) unless the three words of Xw are finite.
+ *  6. Through each pose: x = ((r0*Xw_0 + r1*Xw_1) + r2*Xw_2) + t0, y and z likewise (the pose call's).  Status 4
+ *     (DEPTH1) unless z > 0.0f in key frame 1, else status 5 (DEPTH2) unless z > 0.0f in key frame 2.
+ *  7. In each key frame iz = 1.0f / z, px = x*iz, py = y*iz, pu = fx*px + cx, pv = fy*py + cy, eu = u - pu,
+ *     ev = v - pv, and on a stereo side er = ur - (pu - bf*iz) (the pose call's).  A monocular side passes iff
+ *     eu*eu + ev*ev <= chi2_mono*level_sigma2[l], a stereo side iff (eu*eu + ev*ev) + er*er <=
+ *     chi2_stereo*level_sigma2[l].  Status 6 (REPROJ1) unless side 1 passes, else status 7 (REPROJ2) unless side 2 does.
+ *  8. e = Xw - O1, f = Xw - O2 (three subtractions each), d_1 = sqrt((e_0*e_0 + e_1*e_1) + e_2*e_2), d_2 likewise from
+ *     f; r_1 = d_1*level_scale[l_1], r_2 = d_2*level_scale[l_2].  Status 8 (SCALE) if d_1 == 0.0f or d_2 == 0.0f, or
+ *     unless (d_2*ratio_factor)*level_scale[l_2] >= r_1 and r_2 <= r_1*ratio_factor (ORB-SLAM's ratioDist against
+ *     ratioOctave, the two divisions multiplied out).
+ *
+ * Outputs, device, written for every slot s < n and for no other:
+ *   status  uint8 [batch][stride]
+ *   xw      float [batch][stride][3]: Xw for status 0, else three zeros
+ *   normal  float [batch][stride][3] or NULL: for status 0, w_j = e_j / d_1 + f_j / d_2,
+ *           wn = sqrt((w_0*w_0 + w_1*w_1) + w_2*w_2), normal_j = w_j / wn (the mean viewing direction); else zeros
+ *   drange  float [batch][stride][2] or NULL: for status 0, (r_1 / level_scale[nlevels - 1], r_1); else zeros
+ *           (ORB-SLAM's UpdateNormalAndDepth for a point with two observations and key frame 1 as its reference: exactly
+ *           the normal and drange that pislam_match_projection_batch reads in map mode)
+ * and, per pair, always written: npoints uint32 [batch] = the number of status-0 slots, an integer count.  No float is
+ * summed across slots: the results are bit-for-bit reproducible and independent of the launch shape.
+ *
+ * Limits: level_scale and level_sigma2 finite and > 0, level_scale non-decreasing; chi2_mono, chi2_stereo and
+ * ratio_factor finite and > 0; cos_min_parallax finite; 1 <= stride <= 16384; batch >= 0 with no upper limit (batch ==
+ * 0 is a no-op that returns PISLAM_OK after the checks of p, the tables, batch and stride; the pointers are not looked
+ * at then).  Offsets use size_t arithmetic throughout.  No output may overlap an input or another output.  Any
+ * violation, or a NULL or host pointer where a device pointer is required (normal and drange alone may be NULL):
+ * PISLAM_ERR_INVALID, before anything is launched or written.  `p` and the tables are host memory, read during the
+ * call.  Asynchronous on the context stream; no workspace, no host round trip: the call can be captured into a
+ * hipGraph as it is, so there is no reserve call.  One lane works on a slot, one workgroup on a pair; a batch above
+ * 1024 pairs is walked by the same 1024 workgroups in passes.
+ *
+ * Not here: the baseline test that skips a key-frame pair (the caller's), ORBmatcher::Fuse, and local bundle
+ * adjustment, the step after this one.  (The matches come from pislam_match_hamming_epipolar_batch.) */
+typedef struct pislam_triangulate_params {
+  float cos_min_parallax; /* finite; two monocular keypoints are triangulated iff cs < this (ORB-SLAM: 0.9998f) */
+  float chi2_mono;        /* finite, > 0 (ORB-SLAM: 5.991f) */
+  float chi2_stereo;      /* finite, > 0 (7.815f; ORB-SLAM uses 7.8f here) */
+  float ratio_factor;     /* finite, > 0 (ORB-SLAM: 1.5f * the pyramid's scale factor) */
+} pislam_triangulate_params;
+int pislam_triangulate_batch(pislam_ctx *ctx, const pislam_triangulate_params *p, const float *pose1, const float *pose2,
+                             const float *cam1, const float *cam2, const int32_t *obs1_q8, const int32_t *obs2_q8,
+                             const uint8_t *level1, const uint8_t *level2, const uint32_t *counts,
+                             const float *level_scale, const float *level_sigma2, int nlevels, size_t stride, int batch,
+                             float *xw, uint8_t *status, float *normal, float *drange, uint32_t *npoints);
+
 /* ---- multi-GPU: one process per GPU, pyramids sharded, ONE collective ---- */
 
 /* The reference is a single-threaded per-frame loop without cross-frame state

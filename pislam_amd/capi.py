@@ -81,6 +81,14 @@ class ProjectionParams(ctypes.Structure):
         (n, ctypes.c_int32) for n in ("level_below", "level_above", "second_same_level")]
 
 
+class EpipolarParams(ctypes.Structure):
+    _fields_ = [("chi2", ctypes.c_float), ("epipole_r2", ctypes.c_float)]
+
+
+class TriangulateParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_float) for n in ("cos_min_parallax", "chi2_mono", "chi2_stereo", "ratio_factor")]
+
+
 class ClaheParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "tiles_x", "tiles_y", "clip_q8")]
 
@@ -194,6 +202,14 @@ SYMBOLS = {
                                       ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pislam_sim3_refine_batch": (_i, [_vp, ctypes.POINTER(Sim3RefineParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pislam_epipolar_from_poses": (_i, [ctypes.POINTER(ctypes.c_float)] * 6),
+    "pislam_match_epipolar_reserve": (_i, [_vp, _i, _i, _sz, _i]),
+    "pislam_match_hamming_epipolar_batch": (_i, [_vp, _i, _i, ctypes.POINTER(EpipolarParams), ctypes.POINTER(ctypes.c_float),
+                                                 ctypes.POINTER(ctypes.c_float), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp]),
+    "pislam_triangulate_batch": (_i, [_vp, ctypes.POINTER(TriangulateParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp,
+                                      _vp, _vp, _vp, _vp]),
     "pislam_bow_weight_batch": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _vp, ctypes.c_uint32, _vp]),
     "pislam_bowdb_create": (_i, [_vp, ctypes.c_uint32, _sz, _i, ctypes.POINTER(_vp)]),
     "pislam_bowdb_destroy": (_i, [_vp]),

@@ -58,6 +58,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_track_kernels.h"
 #include "pislam_bow_kernels.h"
 #include "pislam_bowdb_kernels.h"
+#include "pislam_epipolar_kernels.h"
 #include "pislam_select_kernels.h"
 #include "pislam_geom_kernels.h"
 #include "pislam_geom_host.h"
@@ -66,6 +67,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_pnp_kernels.h"
 #include "pislam_sim3_kernels.h"
 #include "pislam_sim3_refine_kernels.h"
+#include "pislam_mappoint_kernels.h"
 #include "pislam_warp_kernels.h"
 #include "pislam_clahe_kernels.h"
 
@@ -132,6 +134,7 @@ struct pislam_ctx {
   };
   CellIndex w_win, w_sc, w_st, w_proj;   // (w_proj: the projection matcher)
   CellIndex w_bow;                   // word-guided matcher (pb::k_bow_index): group offsets, group-sorted indices (meta), descriptors
+  CellIndex w_epi;                   // epipolar matcher (pe::k_epi_index): group offsets, group-sorted entries with their geometry (meta), descriptors
   DevBuf w_db;                       // key-frame database query (pd::k_db_accumulate .. k_db_merge): accumulator planes, maxima, partial lists
   // Host-built plan tables the kernels read instead of walking the plan (the bucket selection pass's unit table): one
   // device buffer per distinct CONTENT, never rewritten in place — a captured graph keeps reading the table
@@ -507,7 +510,7 @@ PISLAM_EXPORT int pislam_ctx_destroy(pislam_ctx *c) {
                     &c->w_off, &c->w_total, &c->w_cellkp, &c->w_score, &c->w_stage, &c->w_stripcnt, &c->w_work, &c->w_prof, &c->w_ovf,
                     &c->w_stagedesc, &c->w_ustage, &c->w_ucount, &c->w_sync, &c->w_chain})
     b->release();
-  for (pislam_ctx::CellIndex *w : {&c->w_win, &c->w_sc, &c->w_st, &c->w_proj, &c->w_bow})
+  for (pislam_ctx::CellIndex *w : {&c->w_win, &c->w_sc, &c->w_st, &c->w_proj, &c->w_bow, &c->w_epi})
     for (DevBuf *b : {&w->off, &w->meta, &w->desc}) b->release();
   c->w_db.release();
   for (auto *t : c->plan_tables) {
@@ -2348,6 +2351,79 @@ PISLAM_EXPORT int pislam_match_hamming_bow_batch(pislam_ctx *c, int words, int n
   return launch_ok(c, "k_match_bow");
 }
 
+// ---- epipolar search between two key frames -------------------------------------------------
+
+PISLAM_EXPORT int pislam_epipolar_from_poses(const float *pose1, const float *pose2, const float *cam1, const float *cam2,
+                                             float *f12, float *epipole) {
+  return pem::epipolar_from_poses(pose1, pose2, cam1, cam2, f12, epipole) ? PISLAM_OK : PISLAM_ERR_INVALID;
+}
+
+namespace {
+
+int epipolar_tables(pislam_ctx *c, const float *level_sigma2, const float *level_scale, int nlevels, pem::Tables *tab) {
+  if (!level_sigma2 || !level_scale || nlevels < 1 || nlevels > pem::MAX_LEVELS)
+    return fail(c, PISLAM_ERR_INVALID, "level_sigma2 and level_scale need 1..16 entries");
+  *tab = pem::Tables{};
+  tab->nlevels = nlevels;
+  for (int l = 0; l < nlevels; l++) {
+    if (!(level_sigma2[l] > 0.0f) || !psm::finite_f(level_sigma2[l]) || !(level_scale[l] > 0.0f) ||
+        !psm::finite_f(level_scale[l]))
+      return fail(c, PISLAM_ERR_INVALID, "level_sigma2 and level_scale must be finite and > 0");
+    if (l > 0 && level_scale[l] < level_scale[l - 1]) return fail(c, PISLAM_ERR_INVALID, "level_scale must not decrease");
+    tab->level_sigma2[l] = level_sigma2[l], tab->level_scale[l] = level_scale[l];
+  }
+  return PISLAM_OK;
+}
+
+}  // namespace
+
+PISLAM_EXPORT int pislam_match_epipolar_reserve(pislam_ctx *c, int words, int ngroups, size_t t_stride, int batch) {
+  if (!c) return PISLAM_ERR_INVALID;
+  PCHK(bow_match_args(c, words, ngroups, t_stride, batch));
+  HIPCHK(c, hipSetDevice(c->device));
+  return index_workspace(c, c->w_epi, (size_t)ngroups + 1, sizeof(pe::Ent), words, t_stride, batch,
+                         "hipMalloc(epipolar matcher workspace)");
+}
+
+PISLAM_EXPORT int pislam_match_hamming_epipolar_batch(
+    pislam_ctx *c, int words, int ngroups, const pislam_epipolar_params *p, const float *level_sigma2,
+    const float *level_scale, int nlevels, const float *f12, const float *epipole, const uint32_t *qdesc,
+    const uint32_t *qgroup, const int32_t *qobs_q8, const uint8_t *qlevel, const uint8_t *qmask, const uint32_t *qcounts,
+    size_t q_stride, const uint32_t *tdesc, const uint32_t *tgroup, const int32_t *tobs_q8, const uint8_t *tlevel,
+    const uint8_t *tmask, const uint32_t *tcounts, size_t t_stride, int batch, int32_t *idx, uint32_t *dist,
+    uint32_t *dist2) {
+  if (!c) return PISLAM_ERR_INVALID;
+  PCHK(bow_match_args(c, words, ngroups, t_stride, batch));
+  if (q_stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "q_stride too large");
+  if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
+  const pem::Params prm{p->chi2, p->epipole_r2};
+  if (!pem::params_ok(prm)) return fail(c, PISLAM_ERR_INVALID, "chi2 must be > 0 and epipole_r2 >= 0");
+  pem::Tables tab;
+  PCHK(epipolar_tables(c, level_sigma2, level_scale, nlevels, &tab));
+  if (batch == 0 || q_stride == 0) return PISLAM_OK;
+  const char *what = "the epipolar matcher takes device pointers only";
+  PCHK(device_ptrs(c, {f12, epipole, qdesc, qgroup, qobs_q8, qlevel, qcounts, tdesc, tgroup, tobs_q8, tlevel, tcounts, idx,
+                       dist, dist2}, what));
+  if ((qmask && !is_device_ptr(qmask)) || (tmask && !is_device_ptr(tmask))) return fail(c, PISLAM_ERR_INVALID, what);
+  HIPCHK(c, hipSetDevice(c->device));
+  PCHK(index_workspace(c, c->w_epi, (size_t)ngroups + 1, sizeof(pe::Ent), words, t_stride, batch,
+                       "hipMalloc(epipolar matcher workspace)"));
+  pe::EpiArgs a{};
+  a.ngroups = (uint32_t)ngroups;
+  a.qdesc = qdesc, a.qgroup = qgroup, a.qcount = qcounts, a.qobs = qobs_q8, a.qlevel = qlevel, a.qmask = qmask;
+  a.tdesc = tdesc, a.tgroup = tgroup, a.tcount = tcounts, a.tobs = tobs_q8, a.tlevel = tlevel, a.tmask = tmask;
+  a.f12 = f12, a.epipole = epipole, a.q_stride = q_stride, a.t_stride = t_stride;
+  a.grp_off = c->w_epi.off.as<uint32_t>(), a.ent = c->w_epi.meta.as<pe::Ent>(), a.ent_desc = c->w_epi.desc.as<uint32_t>();
+  a.idx = idx, a.dist = dist, a.dist2 = dist2;
+  hipLaunchKernelGGL(pe::k_epi_index, dim3((unsigned)batch), dim3(pm::WIN_INDEX_THREADS), 0, c->stream, words, nlevels, a);
+  PCHK(launch_ok(c, "k_epi_index"));
+  const dim3 grid = query_grid(c, q_stride, pm::WIN_QPW, batch);
+  with_words(words, [&](auto w) {
+    hipLaunchKernelGGL(pe::k_match_epipolar<decltype(w)::value>, grid, dim3(pm::WIN_THREADS), 0, c->stream, tab, prm, a);
+  });
+  return launch_ok(c, "k_match_epipolar");
+}
+
 // ---- image preparation: lens undistortion and stereo rectification as a mesh warp ----------
 
 struct pislam_warp {
@@ -2835,6 +2911,55 @@ PISLAM_EXPORT int pislam_sim3_refine_batch(pislam_ctx *c, const pislam_sim3_refi
   hipLaunchKernelGGL(sr::k_sim3_refine, dim3((unsigned)std::min(batch, prf::GRID_CAP)), dim3(prf::THREADS), 0,
                      c->stream, a);
   return launch_ok(c, "k_sim3_refine");
+}
+
+// ---- new map points from two key frames: triangulation and stereo unprojection ------------
+
+PISLAM_EXPORT int pislam_triangulate_batch(pislam_ctx *c, const pislam_triangulate_params *p, const float *pose1,
+                                           const float *pose2, const float *cam1, const float *cam2,
+                                           const int32_t *obs1_q8, const int32_t *obs2_q8, const uint8_t *level1,
+                                           const uint8_t *level2, const uint32_t *counts, const float *level_scale,
+                                           const float *level_sigma2, int nlevels, size_t stride, int batch, float *xw,
+                                           uint8_t *status, float *normal, float *drange, uint32_t *npoints) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
+  const pmp::Params prm{p->cos_min_parallax, p->chi2_mono, p->chi2_stereo, p->ratio_factor};
+  if (!pmp::params_ok(prm))
+    return fail(c, PISLAM_ERR_INVALID, "cos_min_parallax must be finite; chi2_mono, chi2_stereo and ratio_factor finite and > 0");
+  if (!level_scale || !level_sigma2 || nlevels < 1 || nlevels > pmp::MAX_LEVELS)
+    return fail(c, PISLAM_ERR_INVALID, "level_scale and level_sigma2 need 1..16 entries");
+  for (int l = 0; l < nlevels; l++) {
+    if (!(level_scale[l] > 0.0f) || !psm::finite_f(level_scale[l]) || !(level_sigma2[l] > 0.0f) ||
+        !psm::finite_f(level_sigma2[l]))
+      return fail(c, PISLAM_ERR_INVALID, "level_scale and level_sigma2 must be finite and > 0");
+    if (l > 0 && level_scale[l] < level_scale[l - 1]) return fail(c, PISLAM_ERR_INVALID, "level_scale must not decrease");
+  }
+  if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
+  if (stride < 1 || stride > (size_t)pmp::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
+  if (batch == 0) return PISLAM_OK;
+  const char *what = "the triangulation takes device pointers only";
+  PCHK(device_ptrs(c, {pose1, pose2, cam1, cam2, obs1_q8, obs2_q8, level1, level2, counts, xw, status, npoints}, what));
+  if ((normal && !is_device_ptr(normal)) || (drange && !is_device_ptr(drange))) return fail(c, PISLAM_ERR_INVALID, what);
+  {
+    const size_t B = (size_t)batch, word = B * sizeof(uint32_t), pose = B * 12 * sizeof(float), cam = B * 5 * sizeof(float);
+    const size_t obs = B * stride * 3 * sizeof(int32_t), pts = B * stride * 3 * sizeof(float);
+    const LkRange in[] = {{pose1, pose}, {pose2, pose}, {cam1, cam}, {cam2, cam}, {obs1_q8, obs}, {obs2_q8, obs},
+                          {level1, B * stride}, {level2, B * stride}, {counts, word}};
+    const LkRange out[] = {{xw, pts}, {status, B * stride}, {normal, pts}, {drange, B * stride * 2 * sizeof(float)},
+                           {npoints, word}};
+    if (const char *bad = ranges_overlap(in, out)) return fail(c, PISLAM_ERR_INVALID, bad);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  pmk::MpArgs a{};
+  a.pose1 = pose1, a.pose2 = pose2, a.cam1 = cam1, a.cam2 = cam2, a.obs1 = obs1_q8, a.obs2 = obs2_q8;
+  a.level1 = level1, a.level2 = level2, a.counts = counts, a.stride = stride, a.batch = batch;
+  a.tab.nlevels = nlevels;
+  for (int l = 0; l < nlevels; l++) a.tab.level_scale[l] = level_scale[l], a.tab.level_sigma2[l] = level_sigma2[l];
+  a.p = prm;
+  a.xw = xw, a.status = status, a.normal = normal, a.drange = drange, a.npoints = npoints;
+  hipLaunchKernelGGL(pmk::k_triangulate, dim3((unsigned)std::min(batch, pmk::MP_GRID_CAP)), dim3(pmk::MP_THREADS), 0,
+                     c->stream, a);
+  return launch_ok(c, "k_triangulate");
 }
 
 // ---- bag of words: integer weights and the key-frame database -----------------------------

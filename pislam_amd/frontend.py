@@ -1401,6 +1401,212 @@ def sim3RefineBatch(sim_in, cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts, *, lev
     return sim_out, inlier, ninliers, cost, status
 
 
+# ---- new map points from two key frames ----------
+def epipolarGeometry(pose1, pose2, cam1, cam2):
+    """pislam_epipolar_from_poses on the host: the fundamental matrix and the epipole of key-frame pairs with known
+    poses.  pose1, pose2: [12] or [batch][12] (R row-major, then t; Xc = R Xw + t), cam1, cam2: [4] or [5] (bf is
+    ignored) or [batch][4 or 5]: fx, fy, cx, cy; tensors (host or device) or arrays.  Returns (f12 float32 [..][9] with
+    x1' F12 x2 = 0 in level-0 pixels, epipole float32 [..][2] = camera 1's centre in image 2): matchEpipolarBatch's
+    inputs, after a copy to the device.  A pair whose pose or camera is not finite, or whose fx or fy is 0, gives rows of
+    NaN, which the matcher treats as a pair without candidates."""
+    host = lambda a: np.asarray(a.detach().cpu().numpy() if hasattr(a, "detach") else a, dtype=np.float32)
+    p1, p2, c1, c2 = host(pose1), host(pose2), host(cam1), host(cam2)
+    single = p1.ndim == 1
+    p1, p2 = np.ascontiguousarray(p1.reshape(-1, 12)), np.ascontiguousarray(p2.reshape(-1, 12))
+    c1 = np.ascontiguousarray(c1.reshape(len(p1), -1)[:, :4])
+    c2 = np.ascontiguousarray(c2.reshape(len(p1), -1)[:, :4])
+    if p2.shape != p1.shape or c1.shape != (len(p1), 4) or c2.shape != (len(p1), 4):
+        raise ValueError("poses must be [batch][12] and cameras [batch][4 or 5]")
+    f12 = np.full((len(p1), 9), np.nan, dtype=np.float32)
+    epipole = np.full((len(p1), 2), np.nan, dtype=np.float32)
+    lib = capi.load()
+    fp = ctypes.POINTER(ctypes.c_float)
+    for b in range(len(p1)):
+        f, e = np.empty(9, np.float32), np.empty(2, np.float32)
+        rc = lib.pislam_epipolar_from_poses(p1[b].ctypes.data_as(fp), p2[b].ctypes.data_as(fp), c1[b].ctypes.data_as(fp),
+                                            c2[b].ctypes.data_as(fp), f.ctypes.data_as(fp), e.ctypes.data_as(fp))
+        if rc == capi.PISLAM_OK:
+            f12[b], epipole[b] = f, e
+    return (f12[0], epipole[0]) if single else (f12, epipole)
+
+
+def reserveMatchEpipolar(ngroups: int, t_stride: int, batch: int, *, words=8, ctx: Context | None = None):
+    """Sizes the context's epipolar matcher workspace (pislam_match_epipolar_reserve): afterwards matchEpipolarBatch of
+    the same or a smaller shape allocates nothing and can be captured into a hipGraph."""
+    ctx = ctx or default_context()
+    ctx.check(ctx.lib.pislam_match_epipolar_reserve(ctx.h, words, int(ngroups), t_stride, batch),
+              "pislam_match_epipolar_reserve")
+
+
+def matchEpipolarBatch(qdesc, qgroup, qobs_q8, qlevel, qcounts, tdesc, tgroup, tobs_q8, tlevel, tcounts, ngroups: int, f12,
+                       epipole, *, qmask=None, tmask=None, level_sigma2=None, level_scale=None, nlevels=8, scale=1.2,
+                       chi2=3.84, epipole_r2=100.0, idx=None, dist=None, dist2=None, ctx: Context | None = None):
+    """Epipolar search between two key frames (pislam_match_hamming_epipolar_batch; the contract is the comment in
+    include/pislam_hip.h), ORB-SLAM's SearchForTriangulation before its selection: matchHammingBowBatch (same
+    descriptors, groups and counts) restricted to the train keypoints that lie within chi2 * level_sigma2[their level] of
+    the query's epipolar line and, when both keypoints are monocular, outside the disc of epipole_r2 *
+    level_scale[their level] around the epipole.  qobs_q8 / tobs_q8 (int32 [batch][stride][3]) and qlevel / tlevel (uint8
+    [batch][stride]) are poseObservationsQ8's outputs; qmask / tmask (uint8 [batch][stride] or None) keep the keypoints
+    that have no map point yet; f12 float32 [batch][9] and epipole float32 [batch][2] are epipolarGeometry's, on the
+    device.  level_sigma2 / level_scale: HOST sequences of 1..16 float32 (default: mapPointLevelTables(nlevels, scale)).
+    Returns (idx, dist, dist2) int32 tensors [batch][q_stride] for selectMatchesBatch; asynchronous on the ctx stream."""
+    import torch
+    ctx = ctx or default_context()
+    batch, qs, words = (int(v) for v in qdesc.shape)
+    ts = int(tdesc.shape[1])
+    if int(tdesc.shape[0]) != batch or int(tdesc.shape[2]) != words:
+        raise ValueError("query and train descriptors differ in batch or words")
+    for name, t, shape, dt in (("qgroup", qgroup, (batch, qs), None), ("tgroup", tgroup, (batch, ts), None),
+                               ("qobs_q8", qobs_q8, (batch, qs, 3), torch.int32), ("tobs_q8", tobs_q8, (batch, ts, 3), torch.int32),
+                               ("qlevel", qlevel, (batch, qs), torch.uint8), ("tlevel", tlevel, (batch, ts), torch.uint8),
+                               ("qmask", qmask, (batch, qs), torch.uint8), ("tmask", tmask, (batch, ts), torch.uint8),
+                               ("f12", f12, (batch, 9), torch.float32), ("epipole", epipole, (batch, 2), torch.float32)):
+        if t is None and name in ("qmask", "tmask"):
+            continue
+        if tuple(t.shape) != shape or (dt is not None and t.dtype != dt) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous tensor of shape {shape}" + (f" and type {dt}" if dt else ""))
+    if (level_sigma2 is None) != (level_scale is None):
+        raise ValueError("level_sigma2 and level_scale go together")
+    if level_sigma2 is None:
+        level_scale, level_sigma2 = mapPointLevelTables(nlevels, scale)
+    sg = np.ascontiguousarray(np.asarray(level_sigma2, dtype=np.float32).reshape(-1))
+    ls = np.ascontiguousarray(np.asarray(level_scale, dtype=np.float32).reshape(-1))
+    ntab = int(sg.size)
+    if not 1 <= ntab <= 16 or int(ls.size) != ntab:
+        raise ValueError("level_sigma2 and level_scale must have the same 1..16 entries")
+    tab_sg, tab_ls = (ctypes.c_float * ntab)(*sg.tolist()), (ctypes.c_float * ntab)(*ls.tolist())
+    p = capi.EpipolarParams(float(np.float32(chi2)), float(np.float32(epipole_r2)))
+    dev = qdesc.device
+    idx = torch.empty((batch, qs), dtype=torch.int32, device=dev) if idx is None else idx
+    dist = torch.empty((batch, qs), dtype=torch.int32, device=dev) if dist is None else dist
+    dist2 = torch.empty((batch, qs), dtype=torch.int32, device=dev) if dist2 is None else dist2
+    ctx.check(ctx.lib.pislam_match_hamming_epipolar_batch(
+        ctx.h, words, int(ngroups), ctypes.byref(p), tab_sg, tab_ls, ntab, ptr(f12), ptr(epipole), ptr(qdesc), ptr(qgroup),
+        ptr(qobs_q8), ptr(qlevel), ptr(qmask), ptr(qcounts), qs, ptr(tdesc), ptr(tgroup), ptr(tobs_q8), ptr(tlevel),
+        ptr(tmask), ptr(tcounts), ts, batch, ptr(idx), ptr(dist), ptr(dist2)), "pislam_match_hamming_epipolar_batch")
+    return idx, dist, dist2
+
+
+TRIANGULATE_MAX_STRIDE = 16384   # slots per pair (pislam_triangulate_batch)
+TRIANGULATE_STATUS = ("ok", "no level", "low parallax", "not finite", "depth 1", "depth 2", "reprojection 1",
+                      "reprojection 2", "scale", "pair")
+
+
+def mapPointLevelTables(nlevels: int, scale: float = 1.2):
+    """The (level_scale, level_sigma2) tables of triangulateBatch for a pyramid of `nlevels` levels (1..16) with the
+    scale factor `scale`, computed one float32 operation at a time as poseLevelWeights does: s = float32(scale),
+    f_0 = 1, f_l = f_(l-1) * s, level_scale_l = f_l, level_sigma2_l = f_l * f_l (ORB-SLAM's mvScaleFactors and
+    mvLevelSigma2; poseLevelWeights(nlevels, scale) is 1 / level_sigma2 entry by entry)."""
+    if not 1 <= int(nlevels) <= 16:
+        raise ValueError("nlevels must be 1..16")
+    s, f = np.float32(scale), np.float32(1.0)
+    level_scale = np.empty(int(nlevels), dtype=np.float32)
+    for l in range(int(nlevels)):
+        level_scale[l] = f
+        f = f * s
+    return level_scale, level_scale * level_scale
+
+
+def matchedObservationPairs(qobs, qlevel, tobs, tlevel, sel):
+    """The (obs1_q8, level1, obs2_q8, level2, counts) of triangulateBatch from two key frames' observations
+    (poseObservationsQ8's outputs: qobs / tobs int32 [batch][stride][3], qlevel / tlevel uint8 [batch][stride]) and the
+    matches selectMatchesBatch accepted between them: sel = (sel_q, sel_t, nsel); slot s < nsel[b] pairs keypoint
+    sel_q[b][s] of the query key frame (side 1) with keypoint sel_t[b][s] of the train key frame (side 2).  The slots at
+    and beyond nsel[b] of sel_q and sel_t are unwritten memory: they are masked before gathering and come out as the
+    observation (0, 0, INT32_MIN) and the level 255, as in matchedMapObservations.  Torch ops on the current torch
+    stream."""
+    import torch
+    sel_q, sel_t, nsel = sel
+    batch, qs = (int(v) for v in sel_q.shape)
+    dev = sel_q.device
+    live = torch.arange(qs, device=dev)[None, :] < nsel.to(torch.int64)[:, None]
+    zero = torch.zeros_like(live, dtype=torch.int64)
+    dead = torch.tensor([0, 0, POSE_MONO], dtype=torch.int32, device=dev).expand(batch, qs, 3)
+    out = []
+    for obs, level, sel_i in ((qobs, qlevel, sel_q), (tobs, tlevel, sel_t)):
+        if obs.dtype != torch.int32 or obs.dim() != 3 or int(obs.shape[2]) != 3:
+            raise ValueError("observations must be int32 tensors [batch][stride][3]")
+        if level.dtype != torch.uint8 or tuple(level.shape) != tuple(obs.shape[:2]):
+            raise ValueError("levels must be uint8 tensors [batch][stride]")
+        i = torch.where(live, sel_i.to(torch.int64), zero).clamp(0, int(obs.shape[1]) - 1)
+        o = torch.where(live[..., None], torch.gather(obs, 1, i[..., None].expand(-1, -1, 3)), dead)
+        l = torch.where(live, torch.gather(level, 1, i), torch.full_like(i, POSE_NO_LEVEL, dtype=torch.uint8))
+        out += [o.contiguous(), l.contiguous()]
+    return out[0], out[1], out[2], out[3], nsel.to(torch.int32).clone()
+
+
+def triangulateBatch(pose1, pose2, cam1, cam2, obs1_q8, obs2_q8, level1, level2, counts, *, level_scale=None,
+                     level_sigma2=None, nlevels=8, scale=1.2, cos_min_parallax=0.9998, chi2_mono=5.991, chi2_stereo=7.815,
+                     ratio_factor=None, want_normal=True, want_drange=True, xw=None, status=None, normal=None,
+                     drange=None, npoints=None, ctx: Context | None = None):
+    """Batched creation of map points from the matches of two key frames (pislam_triangulate_batch; the contract is the
+    comment in include/pislam_hip.h), the geometry of ORB-SLAM's CreateNewMapPoints: per pair, slot s < counts[b] holds
+    one match as two observations obs1_q8 / obs2_q8 (int32 [batch][stride][3]: u, v, u_right in level-0 Q8 pixels,
+    u_right == INT32_MIN for a monocular keypoint) on the levels level1 / level2 (uint8 [batch][stride]);
+    matchedObservationPairs makes all five.  pose1, pose2 (float32 [batch][12]: R row-major, then t; Xc = R Xw + t) and
+    cam1, cam2 (float32 [batch][5]: fx, fy, cx, cy, bf) are the key frames.  The point is triangulated, or unprojected
+    from a stereo observation when that has more parallax, and kept iff it lies in front of both cameras, reprojects
+    within chi2 * level_sigma2 in both and its distances fit the two levels within ratio_factor (default: float32(1.5)
+    * float32(scale)).  level_scale / level_sigma2: HOST sequences of 1..16 float32 (default: mapPointLevelTables(nlevels,
+    scale)).  Returns (xw float32 [batch][stride][3] (zeros unless status is 0), status uint8 [batch][stride]
+    (TRIANGULATE_STATUS names the codes), normal float32 [batch][stride][3] and drange float32 [batch][stride][2] (what
+    matchProjectionBatch reads in map mode; None when not wanted), npoints int32 [batch]).  Entries at and beyond
+    counts[b] are not written.  The same inputs give the same outputs, bit for bit.  Asynchronous on the ctx stream, no
+    workspace: capturable as it is."""
+    import torch
+    ctx = ctx or default_context()
+    if pose1.dtype != torch.float32 or pose1.dim() != 2 or int(pose1.shape[1]) != 12:
+        raise ValueError("pose1 must be a float32 tensor [batch][12]")
+    batch = int(pose1.shape[0])
+    if pose2.dtype != torch.float32 or tuple(pose2.shape) != (batch, 12):
+        raise ValueError("pose2 must be a float32 tensor [batch][12]")
+    for cam in (cam1, cam2):
+        if cam.dtype != torch.float32 or tuple(cam.shape) != (batch, 5):
+            raise ValueError("cam1 and cam2 must be float32 tensors [batch][5]")
+    if obs1_q8.dtype != torch.int32 or obs1_q8.dim() != 3 or int(obs1_q8.shape[0]) != batch or int(obs1_q8.shape[2]) != 3:
+        raise ValueError("obs1_q8 must be an int32 tensor [batch][stride][3]")
+    stride = int(obs1_q8.shape[1])
+    if obs2_q8.dtype != torch.int32 or tuple(obs2_q8.shape) != (batch, stride, 3):
+        raise ValueError("obs2_q8 must be an int32 tensor of obs1_q8's shape")
+    if stride > TRIANGULATE_MAX_STRIDE:
+        raise ValueError(f"at most {TRIANGULATE_MAX_STRIDE} slots per pair")
+    for level in (level1, level2):
+        if level.dtype != torch.uint8 or tuple(level.shape) != (batch, stride):
+            raise ValueError("level1 and level2 must be uint8 tensors [batch][stride]")
+    if counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(counts.shape) != (batch,):
+        raise ValueError("counts must be a 32-bit integer tensor [batch]")
+    for t in (pose1, pose2, cam1, cam2, obs1_q8, obs2_q8, level1, level2, counts):
+        if not t.is_contiguous():
+            raise ValueError("inputs must be contiguous")
+    if (level_scale is None) != (level_sigma2 is None):
+        raise ValueError("level_scale and level_sigma2 go together")
+    if level_scale is None:
+        level_scale, level_sigma2 = mapPointLevelTables(nlevels, scale)
+    ls = np.ascontiguousarray(np.asarray(level_scale, dtype=np.float32).reshape(-1))
+    sg = np.ascontiguousarray(np.asarray(level_sigma2, dtype=np.float32).reshape(-1))
+    ntab = int(ls.size)
+    if not 1 <= ntab <= 16 or int(sg.size) != ntab:
+        raise ValueError("level_scale and level_sigma2 must have the same 1..16 entries")
+    tab_ls, tab_sg = (ctypes.c_float * ntab)(*ls.tolist()), (ctypes.c_float * ntab)(*sg.tolist())
+    if ratio_factor is None:
+        ratio_factor = np.float32(1.5) * np.float32(scale)
+    p = capi.TriangulateParams(float(np.float32(cos_min_parallax)), float(np.float32(chi2_mono)),
+                               float(np.float32(chi2_stereo)), float(np.float32(ratio_factor)))
+    dev = pose1.device
+    xw = torch.empty((batch, stride, 3), dtype=torch.float32, device=dev) if xw is None else xw
+    status = torch.empty((batch, stride), dtype=torch.uint8, device=dev) if status is None else status
+    if normal is None and want_normal:
+        normal = torch.empty((batch, stride, 3), dtype=torch.float32, device=dev)
+    if drange is None and want_drange:
+        drange = torch.empty((batch, stride, 2), dtype=torch.float32, device=dev)
+    npoints = torch.empty((batch,), dtype=torch.int32, device=dev) if npoints is None else npoints
+    ctx.check(ctx.lib.pislam_triangulate_batch(ctx.h, ctypes.byref(p), ptr(pose1), ptr(pose2), ptr(cam1), ptr(cam2),
+                                               ptr(obs1_q8), ptr(obs2_q8), ptr(level1), ptr(level2), ptr(counts), tab_ls,
+                                               tab_sg, ntab, stride, batch, ptr(xw), ptr(status), ptr(normal),
+                                               ptr(drange), ptr(npoints)), "pislam_triangulate_batch")
+    return xw, status, normal, drange, npoints
+
+
 # ---- bag of words: integer weights and the key-frame database ----------
 BOW_MAX_STRIDE = 16384      # entries of a bag-of-words vector (pislam_bow_vector_batch)
 
