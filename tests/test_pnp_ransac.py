@@ -304,20 +304,21 @@ def rodrigues(r):
     return np.eye(3) + math.sin(th) * K + (1 - math.cos(th)) * (K @ K)
 
 
-def scene(seed, n=300, outliers=0.4, noise=0.75, levels=False, scale=1.0):
+def scene(seed, n=300, outliers=0.4, noise=0.75, levels=False, scale=1.0, cam=CAM):
     """The issue's scene: pixels uniform over a VGA image, depths 2..20, a rotation of up to 1 rad, pixel noise uniform
     in +-noise, a share `outliers` displaced by 30..200 px; Q8-rounded pixels.  `scale` multiplies the world (points and
-    translation).  Returns the frame, the true pose (R, t) and the mask of undisplaced observations."""
+    translation), `cam` is the camera (fx, fy, cx, cy, bf).  Returns the frame, the true pose (R, t) and the mask of undisplaced observations."""
     rng = np.random.default_rng(seed)
+    fx, fy, cx, cy = (float(c) for c in cam[:4])
     px = np.stack([rng.uniform(0, 640, n), rng.uniform(0, 480, n)], 1)
     z = rng.uniform(2, 20, n)
-    xc = np.stack([(px[:, 0] - 320) / 500 * z, (px[:, 1] - 240) / 500 * z, z], 1)
+    xc = np.stack([(px[:, 0] - cx) / fx * z, (px[:, 1] - cy) / fy * z, z], 1)
     axis = rng.normal(0, 1, 3)
     R, t = rodrigues(axis / np.linalg.norm(axis) * rng.uniform(0, 1)), rng.uniform(-2, 2, 3)
     xw = ((xc - t) @ R) * scale                                              # xc = R xw + t
     xw = xw.astype(F32)
     xc = xw.astype(F64) @ R.T + t * scale
-    uv = np.stack([500 * xc[:, 0] / xc[:, 2] + 320, 500 * xc[:, 1] / xc[:, 2] + 240], 1) + rng.uniform(-noise, noise, (n, 2))
+    uv = np.stack([fx * xc[:, 0] / xc[:, 2] + cx, fy * xc[:, 1] / xc[:, 2] + cy], 1) + rng.uniform(-noise, noise, (n, 2))
     out = rng.permutation(n)[:int(round(outliers * n))]
     ang, mag = rng.uniform(0, 2 * math.pi, len(out)), rng.uniform(30, 200, len(out))
     uv[out] += np.stack([np.cos(ang), np.sin(ang)], 1) * mag[:, None]
@@ -326,7 +327,7 @@ def scene(seed, n=300, outliers=0.4, noise=0.75, levels=False, scale=1.0):
     good[out] = False
     level = rng.integers(0, 4, n).astype(np.uint8) if levels else None
     tab = np.array([1.0, 0.7, 0.5, 0.35], F32) if levels else None
-    return dict(cam=CAM.copy(), xw=xw, obs=obs, level=level, tab=tab), (R, t * scale), good
+    return dict(cam=np.array(cam, F32), xw=xw, obs=obs, level=level, tab=tab), (R, t * scale), good
 
 
 def sub(fr, n):

@@ -300,41 +300,45 @@ def rodrigues(r):
     return np.eye(3) + math.sin(th) * K + (1 - math.cos(th)) * (K @ K)
 
 
-def project(X):
-    return np.stack([500 * X[:, 0] / X[:, 2] + 320, 500 * X[:, 1] / X[:, 2] + 240], 1)
+def project(X, cam=CAM):
+    fx, fy, cx, cy = (float(c) for c in cam[:4])
+    return np.stack([fx * X[:, 0] / X[:, 2] + cx, fy * X[:, 1] / X[:, 2] + cy], 1)
 
 
-def frustum(rng, n):
+def frustum(rng, n, cam=CAM):
+    fx, fy, cx, cy = (float(c) for c in cam[:4])
     px = np.stack([rng.uniform(0, 640, n), rng.uniform(0, 480, n)], 1)
     z = rng.uniform(2, 20, n)
-    return np.stack([(px[:, 0] - 320) / 500 * z, (px[:, 1] - 240) / 500 * z, z], 1)
+    return np.stack([(px[:, 0] - cx) / fx * z, (px[:, 1] - cy) / fy * z, z], 1)
 
 
-def scene(seed, n=300, outliers=0.4, noise=0.75, depth_noise=0.01, levels=False, fixed_scale=False):
+def scene(seed, n=300, outliers=0.4, noise=0.75, depth_noise=0.01, levels=False, fixed_scale=False, cam1=CAM,
+          cam2=CAM):
     """The issue's scene.  Points of camera 1's frustum (pixels uniform over a VGA image, depths 2..20); a similarity of
     a rotation of up to 0.3 rad, a translation of up to 1 per axis and a scale drift of e^-0.7 .. e^0.7 (1 with
     fixed_scale) takes camera 2's frame into camera 1's.  The observations are the true projections plus pixel noise
     uniform in +-noise, Q8-rounded; each point is then moved along its ray by a normal depth error of `depth_noise`; a
     share `outliers` of the matches has its camera-2 side (point and pixel) replaced by a random point of the frustum.
-    Returns the pair, the truth (R, t, s) and the mask of matches that were not replaced."""
+    cam1 and cam2 are the two cameras (fx, fy, cx, cy, bf).  Returns the pair, the truth (R, t, s) and the mask of matches
+    that were not replaced."""
     rng = np.random.default_rng(seed)
-    X1 = frustum(rng, n)
+    X1 = frustum(rng, n, cam1)
     axis = rng.normal(0, 1, 3)
     R, t = rodrigues(axis / np.linalg.norm(axis) * rng.uniform(0, 0.3)), rng.uniform(-1, 1, 3)
     s = 1.0 if fixed_scale else math.exp(rng.uniform(-0.7, 0.7))
     X2 = (X1 - t) @ R / s
-    uv1 = project(X1) + rng.uniform(-noise, noise, (n, 2))
-    uv2 = project(X2) + rng.uniform(-noise, noise, (n, 2))
+    uv1 = project(X1, cam1) + rng.uniform(-noise, noise, (n, 2))
+    uv2 = project(X2, cam2) + rng.uniform(-noise, noise, (n, 2))
     X1 = X1 * (1 + depth_noise * rng.normal(0, 1, (n, 1)))
     X2 = X2 * (1 + depth_noise * rng.normal(0, 1, (n, 1)))
     out = rng.permutation(n)[:int(round(outliers * n))]
-    Y = frustum(rng, len(out)) / s
-    X2[out], uv2[out] = Y, project(Y)
+    Y = frustum(rng, len(out), cam2) / s
+    X2[out], uv2[out] = Y, project(Y, cam2)
     q = lambda uv: np.concatenate([np.rint(uv * 256), np.full((n, 1), MONO)], 1).astype(np.int64)
     good = np.ones(n, bool)
     good[out] = False
     lv = lambda: rng.integers(0, 4, n).astype(np.uint8) if levels else None
-    pr = dict(cam1=CAM.copy(), cam2=CAM.copy(), x1=X1.astype(F32), x2=X2.astype(F32), obs1=q(uv1), obs2=q(uv2), level1=lv(),
+    pr = dict(cam1=np.array(cam1, F32), cam2=np.array(cam2, F32), x1=X1.astype(F32), x2=X2.astype(F32), obs1=q(uv1), obs2=q(uv2), level1=lv(),
               level2=lv(), tab=TAB.copy() if levels else None)
     return pr, (R, t, s), good
 

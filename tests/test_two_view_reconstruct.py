@@ -156,9 +156,10 @@ def project(X, cam):
     return np.rint(np.stack([u, v], 1) * 256).astype(np.int64)
 
 
-def scene(seed, n, depth=(4.0, 8.0), rot_deg=6.0, baseline=0.5, far=0):
+def scene(seed, n, depth=(4.0, 8.0), rot_deg=6.0, baseline=0.5, far=0, cam=CAM):
     """n points seen from two cameras: X2 = R X1 + t, a rotation of rot_deg about a random axis, t = (-baseline, 0, 0)
-    (camera 2 sits `baseline` along x).  The last `far` points lie 2000 to 4000 units away: no parallax."""
+    (camera 2 sits `baseline` along x), both under the camera `cam` (fx, fy, cx, cy).  The last `far` points lie 2000 to
+    4000 units away: no parallax."""
     rng = np.random.default_rng(seed)
     axis = rng.normal(size=3)
     R, t = rodrigues(axis / np.linalg.norm(axis) * np.radians(rot_deg)), np.array([-baseline, 0.0, 0.0])
@@ -166,7 +167,7 @@ def scene(seed, n, depth=(4.0, 8.0), rot_deg=6.0, baseline=0.5, far=0):
     z[n - far:] = rng.uniform(2000, 4000, far)
     X1 = np.stack([rng.uniform(-0.4, 0.4, n) * z, rng.uniform(-0.3, 0.3, n) * z, z], 1)
     X2 = X1 @ R.T + t
-    return dict(q1=project(X1, CAM), q2=project(X2, CAM), R=R, t=t, X1=X1)
+    return dict(q1=project(X1, cam), q2=project(X2, cam), R=R, t=t, X1=X1)
 
 
 def motion(R, t):
@@ -354,13 +355,14 @@ def sequence_scene():
                 cam=np.tile(CAM, (SEQ_B, 1)), truth=np.array(truth), z=np.stack([s["X1"][:, 2] for s in scs]))
 
 
-def check_sequence(best, status, xw, point):
+def check_sequence(best, status, xw, point, s=None):
     """status 0, the true motion, every match a point, depths within 1e-3 of the truth (t has unit length and the
     baseline is 0.5, so the map is twice the scene).  The bound is derived, not measured: a Q8 rounding error of at most
     1/512 px over f = 500 against a ray angle of at least 0.06 rad is about 7e-5 relative for one image; 1e-3 leaves
     about 15 times that.  Largest error seen: 1.25e-4, on the restatement and on the library alike (they agree bit for
-    bit): both images are rounded, and the smallest ray angle of the scene is nearer 0.05 rad."""
-    s = sequence_scene()
+    bit): both images are rounded, and the smallest ray angle of the scene is nearer 0.05 rad.  `s` is another scene of
+    sequence_scene()'s layout."""
+    s = sequence_scene() if s is None else s
     assert (np.asarray(status) == (s["truth"] << 8)).all() and (np.asarray(best) == s["truth"]).all()
     assert (np.asarray(point) == 1).all()
     err = np.abs(np.asarray(xw)[:, :, 2].astype(np.float64) * 0.5 - s["z"]) / s["z"]
