@@ -1815,7 +1815,8 @@ int pislam_epipolar_from_poses(const float *pose1, const float *pose2, const flo
  * larger shape the call allocates nothing and never synchronises, so it can be captured into a hipGraph.
  *
  * Not here: the baseline test that skips a key-frame pair (the caller's), the rotation histogram and the uniqueness of
- * SearchForTriangulation's tail (pislam_match_select_batch), ORBmatcher::Fuse, and local bundle adjustment. */
+ * SearchForTriangulation's tail (pislam_match_select_batch), ORBmatcher::Fuse, and local bundle adjustment, which is
+ * pislam_local_ba_batch, below. */
 typedef struct pislam_epipolar_params {
   float chi2;       /* > 0, +inf allowed: squared distance to the epipolar line in units of level_sigma2 (ORB-SLAM: 3.84f) */
   float epipole_r2; /* >= 0: two monocular keypoints are not matched this close to the epipole, times level_scale (100.0f) */
@@ -1916,7 +1917,8 @@ int pislam_match_hamming_epipolar_batch(pislam_ctx *ctx, int words, int ngroups,
  * 1024 pairs is walked by the same 1024 workgroups in passes.
  *
  * Not here: the baseline test that skips a key-frame pair (the caller's), ORBmatcher::Fuse, and local bundle
- * adjustment, the step after this one.  (The matches come from pislam_match_hamming_epipolar_batch.) */
+ * adjustment, the step after this one: pislam_local_ba_batch, below, takes xw and the pose layout as they are.  (The
+ * matches come from pislam_match_hamming_epipolar_batch.) */
 typedef struct pislam_triangulate_params {
   float cos_min_parallax; /* finite; two monocular keypoints are triangulated iff cs < this (ORB-SLAM: 0.9998f) */
   float chi2_mono;        /* finite, > 0 (ORB-SLAM: 5.991f) */
@@ -1928,6 +1930,128 @@ int pislam_triangulate_batch(pislam_ctx *ctx, const pislam_triangulate_params *p
                              const uint8_t *level1, const uint8_t *level2, const uint32_t *counts,
                              const float *level_scale, const float *level_sigma2, int nlevels, size_t stride, int batch,
                              float *xw, uint8_t *status, float *normal, float *drange, uint32_t *npoints);
+
+/* ---- local bundle adjustment: key-frame poses and map points together ---- */
+
+/* What ORB-SLAM's Optimizer::LocalBundleAdjustment does, per WINDOW of a batch: the poses of
+ * the window's free key frames and all of its map points are moved together so that the robust reprojection error of
+ * every observation of a point in a key frame becomes minimal; the other key frames of the window are held fixed and
+ * only anchor the points they see.  Levenberg on the Schur complement: the points are eliminated, a reduced system in
+ * the 6 * kf_free camera unknowns is solved, the points follow.  The reference ships nothing of the kind: the semantics
+ * are this library's own, stated so that individually rounded binary32 and binary64 operations reproduce every output
+ * word.  This comment is the contract.  Every +, -, *, / and sqrt below is ONE binary32 or binary64 operation (as
+ * marked) rounded to nearest even, NEVER fused into an FMA; the divisions and the square root are correctly rounded;
+ * a NaN fails every comparison.  tests/test_local_ba.py restates it in numpy; tools/probes/ba_host_check.cpp compiles
+ * the kernel's own arithmetic header (pislam_ba_math.h) for the host and runs a window serially.
+ *
+ * Inputs, all device, read only.  Window b has nkf = min(kf_counts[b], kf_stride) key frames, npt = min(pt_counts[b],
+ * pt_stride) points and n = min(counts[b], stride) observations (PISLAM_COUNT_INVALID counts as 0); entries at and
+ * beyond a count are never read.
+ *   poses      float [batch][kf_stride][12]: per key frame R row-major, then t (Xc = R Xw + t): the pose call's layout
+ *   cams       float [batch][kf_stride][5] = (fx, fy, cx, cy, bf), one camera per key frame
+ *   kf_free    uint32 [batch]: key frames [0, kf_free) are optimised (FREE), the rest are held FIXED
+ *   xw         float [batch][pt_stride][3]: the map points (pislam_triangulate_batch's xw goes in as it is)
+ *   obs_q8     int32 [batch][stride][3], level uint8 [batch][stride] or NULL, inv_sigma2 HOST float [nlevels]: read
+ *              exactly as pislam_pose_refine_batch reads them (u_right == INT32_MIN marks a monocular observation, a
+ *              level >= nlevels makes the observation DEAD, NULL level: w = 1.0f)
+ *   obs_kf     uint8 [batch][stride], obs_pt uint16 [batch][stride]: observation i is of point obs_pt[i] in key frame
+ *              obs_kf[i].  The observations are SORTED by point and by key frame within a point: obs_pt is
+ *              non-decreasing and obs_kf strictly increasing within a point (at most one observation per pair).
+ *
+ * One observation, binary32: exactly the pose call's, at r = float(R_k), t = float(t_k) of its key frame k (the state
+ * rounded if k is free, the input if fixed), under cams[k], with (X, Y, Z) = float(state of its point): x, y, z, the
+ * DEAD tests (z >= 2^-10, chi2 finite), iz, px, py, pu, pv, eu, ev, er, chi2, th, Huber's wr and rho, the rows Ju, Jv,
+ * Jr and the 21 + 6 camera terms H_jk, g_j as stated there.  In addition the rows with respect to the point (minus the
+ * projection's derivative times R; the products with the constant 0.0f entries are NOT carried out here), j = 0..2:
+ *   Pu_j = Ju_3*r_(0j) + Ju_5*r_(2j),   Pv_j = Jv_4*r_(1j) + Jv_5*r_(2j),   Pr_j = Jr_3*r_(0j) + Jr_5*r_(2j)
+ * (r_(ij) = r_(3i+j)), and from them, with "(+ ...)" for a stereo observation only, as in H_jk:
+ *   cross terms, a = 0..5, j = 0..2:      W_aj = ((Ju_a*Pu_j + Jv_a*Pv_j) (+ Jr_a*Pr_j)) * wr
+ *   point terms, j = 0..2, k = j..2:      V_jk = ((Pu_j*Pu_k + Pv_j*Pv_k) (+ Pr_j*Pr_k)) * wr
+ *                j = 0..2:                gp_j = ((Pu_j*eu + Pv_j*ev) (+ Pr_j*er)) * wr
+ *
+ * A PASS evaluates the window at one state.  An observation CONTRIBUTES iff it is ACTIVE and not dead.  All sums are
+ * binary64 sums of double(term), start at +0.0 and take the contributing observations only, in these orders, none of
+ * which depends on the launch:
+ *   per point p:           V_p (6), g_p (3), and (rho_p, n_p, c_p) = the sums of rho, of 1.0 and of chi2: over the
+ *                          point's observations in ascending index
+ *   F, the count, chi2:    256 partial sums; partial p mod 256 takes (rho_p, n_p, c_p) in ascending p; then the
+ *                          partials are combined by halving as in the pose call (128, 64, .. 1): S = (F, S_1, S_2)
+ *   per free key frame k:  H_k (21), g_k (6): over the key frame's observations in ascending index
+ * The terms W of an observation are kept as binary32 words.  An observation of a fixed key frame adds to its point and
+ * to F only.  A CLASSIFYING pass first sets the active set anew from EVERY observation (active iff not dead and chi2 <=
+ * th), as in the pose call.
+ *
+ * A SOLVE at lambda, binary64, s = 1.0 + lambda, N = 6 * kf_free.
+ *   Point blocks: a00 = V00*s, a01 = V01, a02 = V02, a11 = V11*s, a12 = V12, a22 = V22*s; eliminated without pivoting:
+ *     f1 = a01/a00, f2 = a02/a00, b11 = a11 - f1*a01, b12 = a12 - f1*a02, b21 = a12 - f2*a01, b22 = a22 - f2*a02,
+ *     f3 = b21/b11, c22 = b22 - f3*b12.  The point is HELD in this solve unless a00 > 0, b11 > 0 and c22 > 0.
+ *     Sol(b0, b1, b2): b1 = b1 - f1*b0; b2 = b2 - f2*b0; b2 = b2 - f3*b1; x2 = b2/c22; x1 = (b1 - b12*x2)/b11;
+ *     x0 = ((b0 - a01*x1) - a02*x2)/a00.
+ *     HELD POINTS ARE THE NORMAL PATH, not an error: a point with no contributing observation (V = 0), or with too few
+ *     to constrain it, is held; it takes no step and its terms leave the reduced system untouched.  After the first
+ *     classification of a window with gross outliers such points are common.
+ *   For each contributing observation o of a free key frame whose point p is not held, and each a: Y_o,a = Sol_p(
+ *     double(W_a0), double(W_a1), double(W_a2)).
+ *   The reduced system A d = rhs, for rows i = 6*ki + ai and columns j = 6*kj + aj >= i (A_ji = A_ij):
+ *     A_ij starts at H_ki's sum (ai, aj) if ki == kj, times s if i == j, and at +0.0 if ki != kj; then, over the
+ *     observations oi of key frame ki in ascending index (that is ascending point) that contribute, whose point p is not
+ *     held and has a contributing observation oj in key frame kj:  A_ij = A_ij - ((y0*w0 + y1*w1) + y2*w2) with y =
+ *     Y_oi,ai and w = double(W_aj,0..2 of oj).
+ *     rhs_i starts at -g_ki[ai]; over the same observations oi:  rhs_i = rhs_i + ((y0*g0 + y1*g1) + y2*g2), g = g_p.
+ *   Gaussian elimination WITHOUT pivoting, exactly as the pose call's: for c = 0 .. N-1 the solve fails unless A[c][c]
+ *     > 0; for r > c: f = A[r][c]/A[c][c]; A[r][j] = A[r][j] - f*A[c][j] for j > c; rhs_r = rhs_r - f*rhs_c.
+ *     Back substitution, r = N-1 .. 0:  d_r = rhs_r/A[r][r], then rhs_q = rhs_q - A[q][r]*d_r for every q < r.
+ *   Points: a held point has dp = 0.  Otherwise b_j = -g_p[j]; over the point's contributing observations of free key
+ *     frames k in ascending index, with e = d[6k .. 6k+5]:  b_j = b_j - (((((w_0j*e0 + w_1j*e1) + w_2j*e2) + w_3j*e3) +
+ *     w_4j*e4) + w_5j*e5), w = double(W);  dp = Sol_p(b0, b1, b2).
+ *   The solve fails as well when a word of d or of a dp is not finite.  dmax = the largest |word| of d and of all dp.
+ *   Trial state: T'_k = Retract(T_k, d[6k .. 6k+5]), the pose call's Cayley retraction; X'_p = X_p + dp.
+ *
+ * Per window.  The state (the free poses, all points) is double(input) and stays in binary64 for the whole call.
+ *   Refused on the device, in this order: code 3: kf_free > 16 or > nkf, an obs_kf >= nkf, an obs_pt >= npt, or the
+ *   order above violated; code 2: a word of poses or cams below nkf, or of xw below npt, is not finite; code 1:
+ *   n < min_obs.  Otherwise every observation is active and a pass gives round 0 its sums.  A ROUND is the pose call's
+ *   Levenberg rule word for word (lambda = 2^-10; up to iters[r] iterations; a failed solve: lambda = min(8.0*lambda,
+ *   2^20), the iteration is spent; otherwise one pass at the trial state, same active set, robust iff r < huber_rounds;
+ *   F' < F: the trial state and its sums are taken, lambda = max(lambda*0.25, 2^-30), else lambda = min(8.0*lambda,
+ *   2^20); the round ends when dmax <= eps).  After round r a CLASSIFYING pass, robust iff r + 1 < huber_rounds, gives
+ *   the inlier mask (= the new active set), ninliers = S_1, cost = S_2 and the sums round r + 1 starts from, which runs
+ *   unless r + 1 == rounds (code 0) or ninliers < min_obs (code 1).  A free key frame without a contributing
+ *   observation makes every solve fail (its pivot is 0): the window then keeps its state, and ends with code 0 or 1.
+ *
+ * Outputs, per window, all device.  poses_out float [batch][kf_stride][12]: float(T_k) for a free key frame, the input
+ * copied for a fixed one; xw_out float [batch][pt_stride][3] = float(X_p); inlier uint8 [batch][stride]: the last
+ * classification; ninliers uint32, cost double, status uint32 [batch] = code | evaluations << 8 (evaluations = the
+ * passes made).  For the codes 2 and 3, and for a window that never ran a round, the outputs are the inputs copied, the
+ * mask is all 0, ninliers and cost are 0.  Entries at and beyond a count are never written.  poses_out may be exactly
+ * poses and xw_out exactly xw (a window reads its inputs before it writes); no other overlap of an output with an input
+ * or another output is allowed.
+ *
+ * Limits: the parameter ranges in the struct comments; 1 <= kf_stride <= 32, 1 <= pt_stride <= 4096, 1 <= stride <=
+ * 16384; batch >= 0 with no upper limit (batch == 0 is a no-op that returns PISLAM_OK after the checks of p, the table
+ * and the shape).  Any violation, or a NULL or host pointer where a device pointer is required (level alone may be
+ * NULL): PISLAM_ERR_INVALID, before anything is launched or written.  `p` and inv_sigma2 are host memory, read during
+ * the call.  Asynchronous on the context stream.  The workspace (per workgroup: what grows with pt_stride and stride,
+ * about 500 bytes per observation and 300 per point) belongs to the context and grows on demand, which synchronises;
+ * after pislam_local_ba_reserve of the same or a larger shape the call allocates nothing and never synchronises, so it
+ * can be captured into a hipGraph.  One workgroup runs a window's whole call in one launch; a batch above 1024 windows
+ * is walked by the same 1024 workgroups in passes.
+ *
+ * Not here: ORBmatcher::Fuse, global bundle adjustment and windows beyond the limits, marginalisation, IMU terms. */
+typedef struct pislam_ba_params {
+  int32_t rounds;        /* 1..4 (ORB-SLAM: 2) */
+  int32_t iters[4];      /* 1..32 Levenberg iterations of round r, r < rounds (ORB-SLAM: 5, 10) */
+  int32_t huber_rounds;  /* 0..rounds: rounds 0 .. huber_rounds - 1 are robust (ORB-SLAM: 1) */
+  int32_t min_obs;       /* 1..16384 active observations needed to run a round */
+  double eps;            /* >= 0: a round ends when no |increment word| exceeds it (1e-6) */
+} pislam_ba_params;
+int pislam_local_ba_reserve(pislam_ctx *ctx, size_t kf_stride, size_t pt_stride, size_t stride, int batch);
+int pislam_local_ba_batch(pislam_ctx *ctx, const pislam_ba_params *p, const float *poses, const float *cams,
+                          const uint32_t *kf_counts, const uint32_t *kf_free, const float *xw, const uint32_t *pt_counts,
+                          const int32_t *obs_q8, const uint8_t *obs_kf, const uint16_t *obs_pt, const uint8_t *level,
+                          const uint32_t *counts, const float *inv_sigma2, int nlevels, size_t kf_stride,
+                          size_t pt_stride, size_t stride, int batch, float *poses_out, float *xw_out, uint8_t *inlier,
+                          uint32_t *ninliers, double *cost, uint32_t *status);
 
 /* ---- multi-GPU: one process per GPU, pyramids sharded, ONE collective ---- */
 

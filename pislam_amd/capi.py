@@ -61,6 +61,11 @@ class PoseParams(ctypes.Structure):
                 ("min_obs", ctypes.c_int32), ("eps", ctypes.c_double)]
 
 
+class BaParams(ctypes.Structure):
+    _fields_ = [("rounds", ctypes.c_int32), ("iters", ctypes.c_int32 * 4), ("huber_rounds", ctypes.c_int32),
+                ("min_obs", ctypes.c_int32), ("eps", ctypes.c_double)]
+
+
 class PnpParams(ctypes.Structure):
     _fields_ = [("hypotheses", ctypes.c_int32), ("seed", ctypes.c_uint32), ("min_inliers", ctypes.c_int32)]
 
@@ -196,6 +201,9 @@ SYMBOLS = {
                                        ctypes.POINTER(ctypes.c_float), ctypes.POINTER(_i)]),
     "pislam_pose_refine_batch": (_i, [_vp, ctypes.POINTER(PoseParams), _vp, _vp, _vp, _vp, _vp, _vp,
                                       ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pislam_local_ba_reserve": (_i, [_vp, _sz, _sz, _sz, _i]),
+    "pislam_local_ba_batch": (_i, [_vp, ctypes.POINTER(BaParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   ctypes.POINTER(ctypes.c_float), _i, _sz, _sz, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pislam_pnp_ransac_batch": (_i, [_vp, ctypes.POINTER(PnpParams), _vp, _vp, _vp, _vp, _vp,
                                      ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pislam_sim3_ransac_batch": (_i, [_vp, ctypes.POINTER(Sim3Params), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

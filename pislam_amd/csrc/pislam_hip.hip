@@ -68,6 +68,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_sim3_kernels.h"
 #include "pislam_sim3_refine_kernels.h"
 #include "pislam_mappoint_kernels.h"
+#include "pislam_ba_kernels.h"
 #include "pislam_warp_kernels.h"
 #include "pislam_clahe_kernels.h"
 
@@ -135,6 +136,7 @@ struct pislam_ctx {
   CellIndex w_win, w_sc, w_st, w_proj;   // (w_proj: the projection matcher)
   CellIndex w_bow;                   // word-guided matcher (pb::k_bow_index): group offsets, group-sorted indices (meta), descriptors
   CellIndex w_epi;                   // epipolar matcher (pe::k_epi_index): group offsets, group-sorted entries with their geometry (meta), descriptors
+  DevBuf w_ba;                       // local bundle adjustment (pbk::k_local_ba): a slice per workgroup (pbk::ws_bytes)
   DevBuf w_db;                       // key-frame database query (pd::k_db_accumulate .. k_db_merge): accumulator planes, maxima, partial lists
   // Host-built plan tables the kernels read instead of walking the plan (the bucket selection pass's unit table): one
   // device buffer per distinct CONTENT, never rewritten in place — a captured graph keeps reading the table
@@ -513,6 +515,7 @@ PISLAM_EXPORT int pislam_ctx_destroy(pislam_ctx *c) {
   for (pislam_ctx::CellIndex *w : {&c->w_win, &c->w_sc, &c->w_st, &c->w_proj, &c->w_bow, &c->w_epi})
     for (DevBuf *b : {&w->off, &w->meta, &w->desc}) b->release();
   c->w_db.release();
+  c->w_ba.release();
   for (auto *t : c->plan_tables) {
     t->dev.release();
     delete t;
@@ -2960,6 +2963,89 @@ PISLAM_EXPORT int pislam_triangulate_batch(pislam_ctx *c, const pislam_triangula
   hipLaunchKernelGGL(pmk::k_triangulate, dim3((unsigned)std::min(batch, pmk::MP_GRID_CAP)), dim3(pmk::MP_THREADS), 0,
                      c->stream, a);
   return launch_ok(c, "k_triangulate");
+}
+
+// ---- local bundle adjustment: key-frame poses and map points together -----------------------
+
+namespace {
+
+int local_ba_shape(pislam_ctx *c, size_t kf_stride, size_t pt_stride, size_t stride, int batch) {
+  if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
+  if (kf_stride < 1 || kf_stride > (size_t)pba::MAX_KF) return fail(c, PISLAM_ERR_INVALID, "kf_stride must be 1..32");
+  if (pt_stride < 1 || pt_stride > (size_t)pba::MAX_PTS) return fail(c, PISLAM_ERR_INVALID, "pt_stride must be 1..4096");
+  if (stride < 1 || stride > (size_t)pba::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..16384");
+  return PISLAM_OK;
+}
+
+int local_ba_workspace(pislam_ctx *c, size_t pt_stride, size_t stride, int batch) {
+  const size_t groups = (size_t)std::min(batch, prf::GRID_CAP);
+  if (c->w_ba.ensure(pbk::ws_bytes(pt_stride, stride) * groups) != PISLAM_OK)
+    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(local bundle adjustment workspace)");
+  return PISLAM_OK;
+}
+
+}  // namespace
+
+PISLAM_EXPORT int pislam_local_ba_reserve(pislam_ctx *c, size_t kf_stride, size_t pt_stride, size_t stride, int batch) {
+  if (!c) return PISLAM_ERR_INVALID;
+  PCHK(local_ba_shape(c, kf_stride, pt_stride, stride, batch));
+  if (batch == 0) return PISLAM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  return local_ba_workspace(c, pt_stride, stride, batch);
+}
+
+PISLAM_EXPORT int pislam_local_ba_batch(pislam_ctx *c, const pislam_ba_params *p, const float *poses, const float *cams,
+                                        const uint32_t *kf_counts, const uint32_t *kf_free, const float *xw,
+                                        const uint32_t *pt_counts, const int32_t *obs_q8, const uint8_t *obs_kf,
+                                        const uint16_t *obs_pt, const uint8_t *level, const uint32_t *counts,
+                                        const float *inv_sigma2, int nlevels, size_t kf_stride, size_t pt_stride,
+                                        size_t stride, int batch, float *poses_out, float *xw_out, uint8_t *inlier,
+                                        uint32_t *ninliers, double *cost, uint32_t *status) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
+  if (p->rounds < 1 || p->rounds > pba::MAX_ROUNDS) return fail(c, PISLAM_ERR_INVALID, "rounds must be 1..4");
+  for (int r = 0; r < p->rounds; r++)
+    if (p->iters[r] < 1 || p->iters[r] > 32) return fail(c, PISLAM_ERR_INVALID, "iters must be 1..32");
+  if (p->huber_rounds < 0 || p->huber_rounds > p->rounds) return fail(c, PISLAM_ERR_INVALID, "huber_rounds must be 0..rounds");
+  if (p->min_obs < 1 || p->min_obs > pba::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "min_obs must be 1..16384");
+  PCHK(check_refine_eps(c, p->eps));
+  if (level) PCHK(check_level_table(c, "level needs", inv_sigma2, nlevels));
+  PCHK(local_ba_shape(c, kf_stride, pt_stride, stride, batch));
+  if (batch == 0) return PISLAM_OK;
+  const char *what = "the local bundle adjustment takes device pointers only";
+  PCHK(device_ptrs(c, {poses, cams, kf_counts, kf_free, xw, pt_counts, obs_q8, obs_kf, obs_pt, counts, poses_out, xw_out,
+                       inlier, ninliers, cost, status}, what));
+  if (level && !is_device_ptr(level)) return fail(c, PISLAM_ERR_INVALID, what);
+  {
+    const size_t B = (size_t)batch, word = B * sizeof(uint32_t), pose = B * kf_stride * 12 * sizeof(float);
+    const size_t pts = B * pt_stride * 3 * sizeof(float);
+    const LkRange in[] = {{poses, pose}, {xw, pts}, {cams, B * kf_stride * 5 * sizeof(float)}, {kf_counts, word},
+                          {kf_free, word}, {pt_counts, word}, {obs_q8, B * stride * 3 * sizeof(int32_t)},
+                          {obs_kf, B * stride}, {obs_pt, B * stride * sizeof(uint16_t)}, {level, B * stride}, {counts, word}};
+    const LkRange out[] = {{poses_out, pose}, {xw_out, pts}, {inlier, B * stride}, {ninliers, word},
+                           {cost, B * sizeof(double)}, {status, word}};
+    // poses_out == poses and xw_out == xw are allowed: a window reads its inputs before it writes them
+    for (size_t o = 0; o < sizeof(out) / sizeof(out[0]); o++) {
+      for (size_t i = 0; i < sizeof(in) / sizeof(in[0]); i++) {
+        if (o < 2 && i == o && out[o].p == in[i].p) continue;
+        if (lk_overlap(out[o], in[i])) return fail(c, PISLAM_ERR_INVALID, "an output overlaps an input");
+      }
+      for (size_t k = 0; k < o; k++)
+        if (lk_overlap(out[o], out[k])) return fail(c, PISLAM_ERR_INVALID, "two outputs overlap");
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  PCHK(local_ba_workspace(c, pt_stride, stride, batch));
+  pbk::BaArgs a{};
+  a.poses = poses, a.cams = cams, a.xw = xw, a.kf_counts = kf_counts, a.kf_free = kf_free, a.pt_counts = pt_counts;
+  a.counts = counts, a.obs = obs_q8, a.obs_kf = obs_kf, a.obs_pt = obs_pt, a.level = level;
+  a.kf_stride = kf_stride, a.pt_stride = pt_stride, a.stride = stride, a.batch = batch;
+  copy_level_table(&a, inv_sigma2, level ? nlevels : 0);
+  a.p = pba::Params{p->rounds, {p->iters[0], p->iters[1], p->iters[2], p->iters[3]}, p->huber_rounds, p->min_obs, p->eps};
+  a.poses_out = poses_out, a.xw_out = xw_out, a.inlier = inlier, a.ninliers = ninliers, a.status = status, a.cost = cost;
+  a.ws = c->w_ba.as<char>();
+  hipLaunchKernelGGL(pbk::k_local_ba, dim3((unsigned)std::min(batch, prf::GRID_CAP)), dim3(prf::THREADS), 0, c->stream, a);
+  return launch_ok(c, "k_local_ba");
 }
 
 // ---- bag of words: integer weights and the key-frame database -----------------------------

@@ -26,10 +26,16 @@ constexpr int32_t MONO = INT32_MIN;
 PISLAM_HD int32_t clamp_obs(int32_t v) { return v < -OBS_MAX ? -OBS_MAX : (v > OBS_MAX ? OBS_MAX : v); }
 PISLAM_HD float obs_px(int32_t q8) { return (float)clamp_obs(q8) * (1.0f / 256.0f); }   // exact
 
+// What one observation leaves before its terms are formed: the Jacobian rows of the error for the left increment, the
+// errors, the robust weight and rho.  (The local bundle adjustment, pislam_ba_math.h, forms more terms from them.)
+struct ObsRows {
+  float Ju[6], Jv[6], Jr[6], eu, ev, er, wr, rho;
+};
+
 // One observation at the pose T (r0..r8, t0..t2, already rounded to float) with the weight w.  False: dead (nothing
-// is written).  Otherwise *chi2_out is the plain chi2 and t[0..27] are the 28 terms.
-PISLAM_HD bool obs_terms(const float *T, const float *cam, float X, float Y, float Z, float u, float v, float ur, bool stereo,
-                     float w, bool robust, float *t, float *chi2_out) {
+// is written).  Otherwise *chi2_out is the plain chi2 and o holds the rows.
+PISLAM_HD bool obs_rows(const float *T, const float *cam, float X, float Y, float Z, float u, float v, float ur, bool stereo,
+                        float w, bool robust, ObsRows &o, float *chi2_out) {
   const float fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3], bf = cam[4];
   const float x = ((T[0] * X + T[1] * Y) + T[2] * Z) + T[9];
   const float y = ((T[3] * X + T[4] * Y) + T[5] * Z) + T[10];
@@ -57,10 +63,18 @@ PISLAM_HD bool obs_terms(const float *T, const float *cam, float X, float Y, flo
   }
   const float a = fx * iz, b = fy * iz, c = bf * iz;
   const float pxy = px * py;
-  float Ju[6], Jv[6], Jr[6];
+  float *Ju = o.Ju, *Jv = o.Jv, *Jr = o.Jr;
   Ju[0] = pxy * fx, Ju[1] = -((1.0f + px * px) * fx), Ju[2] = py * fx, Ju[3] = -a, Ju[4] = 0.0f, Ju[5] = px * a;
   Jv[0] = (1.0f + py * py) * fy, Jv[1] = -(pxy * fy), Jv[2] = -(px * fy), Jv[3] = 0.0f, Jv[4] = -b, Jv[5] = py * b;
   Jr[0] = Ju[0] - c * py, Jr[1] = Ju[1] + c * px, Jr[2] = Ju[2], Jr[3] = Ju[3], Jr[4] = 0.0f, Jr[5] = Ju[5] - c * iz;
+  o.eu = eu, o.ev = ev, o.er = er, o.wr = wr, o.rho = rho;
+  return true;
+}
+
+// The 28 terms t[0..27] of an observation's rows.
+PISLAM_HD void row_terms(const ObsRows &r, bool stereo, float *t) {
+  const float *Ju = r.Ju, *Jv = r.Jv, *Jr = r.Jr;
+  const float eu = r.eu, ev = r.ev, er = r.er, wr = r.wr, rho = r.rho;
   int o = 0;
 PISLAM_UNROLL
   for (int j = 0; j < 6; j++) {
@@ -78,6 +92,15 @@ PISLAM_UNROLL
     t[21 + j] = s * wr;
   }
   t[27] = rho;
+}
+
+// One observation as the pose call sums it: false: dead (nothing is written).  Otherwise *chi2_out is the plain chi2
+// and t[0..27] are the 28 terms.
+PISLAM_HD bool obs_terms(const float *T, const float *cam, float X, float Y, float Z, float u, float v, float ur, bool stereo,
+                     float w, bool robust, float *t, float *chi2_out) {
+  ObsRows r;
+  if (!obs_rows(T, cam, X, Y, Z, u, v, ur, stereo, w, robust, r, chi2_out)) return false;
+  row_terms(r, stereo, t);
   return true;
 }
 

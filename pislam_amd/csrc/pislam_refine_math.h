@@ -29,6 +29,10 @@ struct Params {
   double eps;
 };
 
+// The damping of the Levenberg rule: down after a step that lowered F, up after one that did not or a failed solve.
+PISLAM_HD double lambda_down(double lambda) { return fmax(lambda * 0.25, LAMBDA_MIN); }
+PISLAM_HD double lambda_up(double lambda) { return fmin(8.0 * lambda, LAMBDA_MAX); }
+
 // The Levenberg rule of one round, as a state machine around the passes over the items: begin() takes the sums at the
 // round's state, next() asks for the next trial state (false: the round is over), trial() takes the sums at it.
 template <class RULE>
@@ -49,7 +53,7 @@ PISLAM_UNROLL
       it++;
       double d[DIM];
       if (!R.solve(S, lambda, d)) {
-        lambda = fmin(8.0 * lambda, LAMBDA_MAX);
+        lambda = lambda_up(lambda);
         continue;
       }
       RULE::retract(T, d, Tt);
@@ -66,9 +70,9 @@ PISLAM_UNROLL
       for (int i = 0; i < STATE; i++) T[i] = Tt[i];
 PISLAM_UNROLL
       for (int i = 0; i < TERMS; i++) S[i] = sums[i];
-      lambda = fmax(lambda * 0.25, LAMBDA_MIN);
+      lambda = lambda_down(lambda);
     } else {
-      lambda = fmin(8.0 * lambda, LAMBDA_MAX);
+      lambda = lambda_up(lambda);
     }
     if (dmax <= eps) over = true;
   }

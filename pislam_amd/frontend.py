@@ -1607,6 +1607,119 @@ def triangulateBatch(pose1, pose2, cam1, cam2, obs1_q8, obs2_q8, level1, level2,
     return xw, status, normal, drange, npoints
 
 
+# ---- local bundle adjustment: key-frame poses and map points together ----------
+BA_MAX_KF, BA_MAX_FREE, BA_MAX_POINTS = 32, 16, 4096
+
+
+def localWindow(obs_kf, obs_pt, kp, counts, levels, scale_q16=None, disp_q8=None, pos_q8=None):
+    """The observations of localBundleAdjustBatch from per-observation lists in any order: obs_kf, obs_pt and kp are
+    integer tensors [batch][stride] (key frame of the window, point of the window, keypoint word), counts [batch].  The
+    first counts[b] entries of a row are sorted by point and by key frame within a point (a stable sort of the key
+    obs_pt * 64 + obs_kf; the call itself refuses a window in which a pair occurs twice); the entries behind them stay
+    behind.  The coordinates and levels are poseObservationsQ8's (levels, scale_q16, disp_q8, pos_q8 as there), sorted
+    alike.  Returns (obs_q8 int32 [batch][stride][3], obs_kf uint8 [batch][stride], obs_pt int16 [batch][stride] (the
+    uint16 words of the call: a point index is below 4096), level uint8 [batch][stride], counts int32 [batch]).  Torch
+    ops on the current torch stream."""
+    import torch
+    if obs_kf.dim() != 2 or tuple(obs_pt.shape) != tuple(obs_kf.shape) or tuple(kp.shape) != tuple(obs_kf.shape):
+        raise ValueError("obs_kf, obs_pt and kp must be [batch][stride]")
+    batch, stride = (int(v) for v in obs_kf.shape)
+    if tuple(counts.shape) != (batch,):
+        raise ValueError("counts must be [batch]")
+    obs, level = poseObservationsQ8(kp, levels, scale_q16, disp_q8, pos_q8)
+    k, p = obs_kf.to(torch.int64), obs_pt.to(torch.int64)
+    live = torch.arange(stride, device=k.device)[None, :] < counts.to(torch.int64).clamp(0, stride)[:, None]
+    key = torch.where(live, p.clamp(0, 0xFFFF) * 64 + k.clamp(0, 63), torch.full_like(k, 1 << 40))
+    order = torch.argsort(key, dim=1, stable=True)
+    g = lambda t: torch.gather(t, 1, order)
+    obs = torch.gather(obs, 1, order[..., None].expand(-1, -1, 3))
+    return (obs.contiguous(), g(k).clamp(0, 255).to(torch.uint8).contiguous(),
+            g(p).clamp(0, 0x7FFF).to(torch.int16).contiguous(), g(level).contiguous(),
+            counts.to(torch.int64).clamp(0, stride).to(torch.int32))
+
+
+def reserveLocalBundleAdjust(kf_stride: int, pt_stride: int, stride: int, batch: int, *, ctx: Context | None = None):
+    """Size the context's workspace for localBundleAdjustBatch calls of up to this shape (pislam_local_ba_reserve):
+    afterwards such calls allocate nothing and never synchronise, so they can be captured into a hipGraph."""
+    ctx = ctx or default_context()
+    ctx.check(ctx.lib.pislam_local_ba_reserve(ctx.h, int(kf_stride), int(pt_stride), int(stride), int(batch)),
+              "pislam_local_ba_reserve")
+
+
+def localBundleAdjustBatch(poses, cams, kf_counts, kf_free, xw, pt_counts, obs_q8, obs_kf, obs_pt, counts, *, level=None,
+                           inv_sigma2=None, rounds=2, iters=(5, 10), huber_rounds=1, min_obs=10, eps=1e-6,
+                           poses_out=None, xw_out=None, inlier=None, ninliers=None, cost=None, status=None,
+                           ctx: Context | None = None):
+    """Batched local bundle adjustment (pislam_local_ba_batch; the contract is the comment in include/pislam_hip.h):
+    per window, the poses of the free key frames [0, kf_free[b]) and all map points are moved together to minimise the
+    robust reprojection error of the observations; the key frames from kf_free[b] on are held fixed.  poses float32
+    [batch][kf_stride][12] (kf_stride <= 32, at most 16 free), cams float32 [batch][kf_stride][5], xw float32
+    [batch][pt_stride][3] (pt_stride <= 4096; triangulateBatch's xw as it is), obs_q8 int32 [batch][stride][3] (stride
+    <= 16384) with obs_kf uint8 and obs_pt int16 or uint16 [batch][stride], sorted by point and key frame (localWindow
+    makes them); kf_counts, kf_free, pt_counts, counts [batch]; level and inv_sigma2 as in poseRefineBatch.  ORB-SLAM's
+    schedule: `rounds` rounds of up to iters[r] Levenberg iterations, the first `huber_rounds` robust, an inlier
+    classification after each.  Returns (poses_out, xw_out, inlier uint8 [batch][stride], ninliers int32 [batch], cost
+    float64 [batch], status int32 [batch] = code | evaluations << 8; code 0 ok, 1 stopped for min_obs, 2 an input is
+    not finite, 3 the window is malformed).  poses_out may be `poses` and xw_out may be `xw`.  The same inputs give the
+    same outputs, bit for bit.  Asynchronous on the ctx stream; capturable after reserveLocalBundleAdjust."""
+    import torch
+    ctx = ctx or default_context()
+    if poses.dtype != torch.float32 or poses.dim() != 3 or int(poses.shape[2]) != 12:
+        raise ValueError("poses must be a float32 tensor [batch][kf_stride][12]")
+    batch, kfs = int(poses.shape[0]), int(poses.shape[1])
+    if cams.dtype != torch.float32 or tuple(cams.shape) != (batch, kfs, 5):
+        raise ValueError("cams must be a float32 tensor [batch][kf_stride][5]")
+    if xw.dtype != torch.float32 or xw.dim() != 3 or int(xw.shape[0]) != batch or int(xw.shape[2]) != 3:
+        raise ValueError("xw must be a float32 tensor [batch][pt_stride][3]")
+    pts = int(xw.shape[1])
+    if obs_q8.dtype != torch.int32 or obs_q8.dim() != 3 or int(obs_q8.shape[0]) != batch or int(obs_q8.shape[2]) != 3:
+        raise ValueError("obs_q8 must be an int32 tensor [batch][stride][3]")
+    stride = int(obs_q8.shape[1])
+    if obs_kf.dtype != torch.uint8 or tuple(obs_kf.shape) != (batch, stride):
+        raise ValueError("obs_kf must be a uint8 tensor [batch][stride]")
+    if obs_pt.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) or tuple(obs_pt.shape) != (batch, stride):
+        raise ValueError("obs_pt must be a 16-bit integer tensor [batch][stride]")
+    if kfs > BA_MAX_KF or pts > BA_MAX_POINTS or stride > POSE_MAX_STRIDE:
+        raise ValueError(f"at most {BA_MAX_KF} key frames, {BA_MAX_POINTS} points and {POSE_MAX_STRIDE} observations per window")
+    words = (torch.int32, getattr(torch, "uint32", torch.int32))
+    for t in (kf_counts, kf_free, pt_counts, counts):
+        if t.dtype not in words or tuple(t.shape) != (batch,):
+            raise ValueError("kf_counts, kf_free, pt_counts and counts must be 32-bit integer tensors [batch]")
+    if (level is None) != (inv_sigma2 is None):
+        raise ValueError("level and inv_sigma2 go together")
+    tab, ntab = None, 0
+    if level is not None:
+        if level.dtype != torch.uint8 or tuple(level.shape) != (batch, stride):
+            raise ValueError("level must be a uint8 tensor [batch][stride]")
+        host = np.ascontiguousarray(np.asarray(inv_sigma2, dtype=np.float32).reshape(-1))
+        ntab = int(host.size)
+        if not 1 <= ntab <= 16:
+            raise ValueError("inv_sigma2 must have 1..16 entries")
+        tab = (ctypes.c_float * ntab)(*host.tolist())
+    for t in (poses, cams, kf_counts, kf_free, xw, pt_counts, obs_q8, obs_kf, obs_pt, counts) + (
+            () if level is None else (level,)):
+        if not t.is_contiguous():
+            raise ValueError("inputs must be contiguous")
+    its = [int(v) for v in (iters if hasattr(iters, "__len__") else [iters] * int(rounds))]
+    if len(its) < int(rounds) or len(its) > 4:
+        raise ValueError("iters needs an entry per round, at most 4")
+    p = capi.BaParams(int(rounds), (ctypes.c_int32 * 4)(*(its + [1] * (4 - len(its)))), int(huber_rounds), int(min_obs),
+                      float(eps))
+    dev = poses.device
+    poses_out = torch.empty_like(poses) if poses_out is None else poses_out
+    xw_out = torch.empty_like(xw) if xw_out is None else xw_out
+    inlier = torch.empty((batch, stride), dtype=torch.uint8, device=dev) if inlier is None else inlier
+    ninliers = torch.empty((batch,), dtype=torch.int32, device=dev) if ninliers is None else ninliers
+    cost = torch.empty((batch,), dtype=torch.float64, device=dev) if cost is None else cost
+    status = torch.empty((batch,), dtype=torch.int32, device=dev) if status is None else status
+    ctx.check(ctx.lib.pislam_local_ba_batch(ctx.h, ctypes.byref(p), ptr(poses), ptr(cams), ptr(kf_counts), ptr(kf_free),
+                                            ptr(xw), ptr(pt_counts), ptr(obs_q8), ptr(obs_kf), ptr(obs_pt), ptr(level),
+                                            ptr(counts), tab, ntab, kfs, pts, stride, batch, ptr(poses_out), ptr(xw_out),
+                                            ptr(inlier), ptr(ninliers), ptr(cost), ptr(status)),
+              "pislam_local_ba_batch")
+    return poses_out, xw_out, inlier, ninliers, cost, status
+
+
 # ---- bag of words: integer weights and the key-frame database ----------
 BOW_MAX_STRIDE = 16384      # entries of a bag-of-words vector (pislam_bow_vector_batch)
 
