@@ -659,9 +659,11 @@ int pislam_match_hamming_scaled_window_batch(pislam_ctx *ctx, int words,
  * of the same or a larger shape the call allocates nothing and never
  * synchronises, so it can be captured into a hipGraph.
  *
- * Not here: the stereo right-coordinate test of SearchByProjection, Fuse's
- * replacement of map points, and the rotation histogram, which
- * pislam_match_select_batch applies from angles. */
+ * Not here: the stereo right-coordinate test of SearchByProjection, the
+ * reprojection test of ORBmatcher::Fuse (pislam_match_fuse_batch, below, is
+ * this call with that test; the replacement of map points stays with the
+ * caller), and the rotation histogram, which pislam_match_select_batch applies
+ * from angles. */
 typedef struct pislam_projection_params {
   float min_x, max_x, min_y, max_y; /* image bounds of pu, pv (ORB-SLAM: mnMinX ..) */
   float cos_min;                    /* viewing-angle limit (ORB-SLAM: 0.5) */
@@ -681,6 +683,81 @@ int pislam_match_projection_batch(pislam_ctx *ctx, int words, const pislam_level
                                   const uint32_t *tkp, const uint32_t *tdesc, const uint32_t *tcounts, size_t t_stride,
                                   int batch, int32_t *idx, uint32_t *dist, uint32_t *dist2, int32_t *pred,
                                   uint8_t *plevel);
+
+/* Map-point fusion search, after ORB-SLAM's
+ * ORBmatcher::Fuse (LocalMapping::SearchInNeighbors, LoopClosing::
+ * SearchAndFuse): project map points into a key frame and find, for each, the
+ * keypoint it should have been observed at.  It is
+ * pislam_match_projection_batch plus a per-candidate reprojection test: every
+ * argument of that call has the same meaning, layout, limits and NULL rules
+ * here, both query modes and the same pislam_projection_params included.  In
+ * addition:
+ *   tobs_q8    int32 [batch][t_stride][3]  device: (u, v, u_right) of train
+ *              keypoint j in Q8 level-0 pixels, read by
+ *              pislam_match_hamming_epipolar_batch's rule: a word that is read
+ *              is clamped to [-2^22, 2^22], then float(q) * (1.0f / 256.0f);
+ *              u_right == INT32_MIN marks a monocular keypoint (u_right is
+ *              then not converted).  Only rows of candidates by step 7 of the
+ *              projection call are read.
+ *   qmask      uint8 [batch][q_stride]  device, or NULL: 0 makes query i dead
+ *              (ORB-SLAM's pMP->IsInKeyFrame(pKF) or isBad()).
+ *   inv_sigma2 HOST float [nlevels], finite and > 0, carried by value in the
+ *              kernel arguments (ORB-SLAM's mvInvLevelSigma2).
+ *   f          HOST pislam_fuse_params: chi2_mono (ORB-SLAM: 5.99f) and
+ *              chi2_stereo (7.8f), both > 0; +inf is allowed, a NaN is refused.
+ *   cam        bf = cam[4] is read, not only tested for finiteness.
+ * Per query i < nq_b, in binary32 with one rounding per written operation (no
+ * fused multiply-add, no reciprocal approximation; a comparison with a NaN is
+ * false), the projection call's steps 1-8 apply word for word, except:
+ *  0. A query whose qmask byte is 0 is dead: idx -1, dist and dist2
+ *     0xffffffff, pred (0, 0), plevel 0xff.
+ *  1. also makes pur = pu - bf*iz.
+ *  7. Train j on level lt is a candidate iff it is one by the projection
+ *     call's step 7 AND passes the reprojection test with (u, v, r) its
+ *     tobs_q8 words: ex = pu - u, ey = pv - v.
+ *       Monocular (r == INT32_MIN): e2 = ex*ex + ey*ey; passes iff
+ *         e2 * inv_sigma2[lt] <= chi2_mono.
+ *       Otherwise: er = pur - r, e2 = (ex*ex + ey*ey) + er*er; passes iff
+ *         e2 * inv_sigma2[lt] <= chi2_stereo.
+ *     lt is the level the train keypoint's POSITION (tkp) lies in, the level
+ *     whose cell grid the keypoint is indexed in.
+ * Equivalence: with both bounds +inf and qmask NULL all five outputs equal
+ * pislam_match_projection_batch's on the same inputs, whatever tobs_q8 holds:
+ * for a live query pu and pv lie inside the bounds, bf and iz are finite, so
+ * e2 * inv_sigma2[lt] is never a NaN, and inf <= inf is true.
+ *
+ * Limits, refusals (PISLAM_ERR_INVALID before anything is launched or
+ * written: every refusal of the projection call, chi2_mono or chi2_stereo not
+ * > 0, inv_sigma2 NULL, not finite or not > 0, f NULL, tobs_q8 NULL or a host
+ * pointer, qmask a host pointer), size_t offsets and asynchrony are the
+ * projection call's.  The workspace is the context's own for this call (not
+ * the projection matcher's: a graph captured for either call survives a
+ * reserve of the other) and grows on demand, which synchronises; after
+ * pislam_match_fuse_reserve of the same or a larger shape the call allocates
+ * nothing and never synchronises, so it can be captured into a hipGraph.
+ * Fuse(pKF, Scw, ...) of loop closing is this call with the pose (R, t / s) of
+ * the similarity and both bounds +inf (ORB-SLAM2 applies no chi-square test
+ * there).
+ *
+ * Not here: what follows a match (add the observation, or replace the point
+ * with fewer observations by the other: the map is the caller's), descriptor
+ * and normal updates of fused points, and the stereo right-coordinate test of
+ * the motion-model SearchByProjection. */
+typedef struct pislam_fuse_params {
+  float chi2_mono;   /* > 0, +inf allowed (ORB-SLAM: 5.99f) */
+  float chi2_stereo; /* > 0, +inf allowed (ORB-SLAM: 7.8f) */
+} pislam_fuse_params;
+int pislam_match_fuse_reserve(pislam_ctx *ctx, int words, const pislam_level *levels, int nlevels,
+                              const int32_t *scale_q16, const int32_t *radius_far, const int32_t *radius_near,
+                              int level_below, int level_above, size_t t_stride, int batch);
+int pislam_match_fuse_batch(pislam_ctx *ctx, int words, const pislam_level *levels, int nlevels,
+                            const int32_t *scale_q16, const float *level_scale, const int32_t *radius_far,
+                            const int32_t *radius_near, const pislam_projection_params *p, const float *inv_sigma2,
+                            const pislam_fuse_params *f, const float *pose, const float *cam, const float *xw,
+                            const float *normal, const float *drange, const uint8_t *qlevel, const uint8_t *qmask,
+                            const uint32_t *qdesc, const uint32_t *qcounts, size_t q_stride, const uint32_t *tkp,
+                            const uint32_t *tdesc, const int32_t *tobs_q8, const uint32_t *tcounts, size_t t_stride,
+                            int batch, int32_t *idx, uint32_t *dist, uint32_t *dist2, int32_t *pred, uint8_t *plevel);
 
 /* Rectified stereo matching: left <-> right
  * correspondences of rectified stereo pairs with an SAD sub-pixel refinement,
@@ -1815,8 +1892,8 @@ int pislam_epipolar_from_poses(const float *pose1, const float *pose2, const flo
  * larger shape the call allocates nothing and never synchronises, so it can be captured into a hipGraph.
  *
  * Not here: the baseline test that skips a key-frame pair (the caller's), the rotation histogram and the uniqueness of
- * SearchForTriangulation's tail (pislam_match_select_batch), ORBmatcher::Fuse, and local bundle adjustment, which is
- * pislam_local_ba_batch, below. */
+ * SearchForTriangulation's tail (pislam_match_select_batch), ORBmatcher::Fuse, which is pislam_match_fuse_batch, and
+ * local bundle adjustment, which is pislam_local_ba_batch, below. */
 typedef struct pislam_epipolar_params {
   float chi2;       /* > 0, +inf allowed: squared distance to the epipolar line in units of level_sigma2 (ORB-SLAM: 3.84f) */
   float epipole_r2; /* >= 0: two monocular keypoints are not matched this close to the epipole, times level_scale (100.0f) */
@@ -1916,9 +1993,10 @@ int pislam_match_hamming_epipolar_batch(pislam_ctx *ctx, int words, int ngroups,
  * hipGraph as it is, so there is no reserve call.  One lane works on a slot, one workgroup on a pair; a batch above
  * 1024 pairs is walked by the same 1024 workgroups in passes.
  *
- * Not here: the baseline test that skips a key-frame pair (the caller's), ORBmatcher::Fuse, and local bundle
- * adjustment, the step after this one: pislam_local_ba_batch, below, takes xw and the pose layout as they are.  (The
- * matches come from pislam_match_hamming_epipolar_batch.) */
+ * Not here: the baseline test that skips a key-frame pair (the caller's), ORBmatcher::Fuse, the step after this one
+ * (pislam_match_fuse_batch takes xw, normal and drange as they are), and local bundle adjustment, the step after that:
+ * pislam_local_ba_batch, below, takes xw and the pose layout as they are.  (The matches come from
+ * pislam_match_hamming_epipolar_batch.) */
 typedef struct pislam_triangulate_params {
   float cos_min_parallax; /* finite; two monocular keypoints are triangulated iff cs < this (ORB-SLAM: 0.9998f) */
   float chi2_mono;        /* finite, > 0 (ORB-SLAM: 5.991f) */
@@ -2037,7 +2115,8 @@ int pislam_triangulate_batch(pislam_ctx *ctx, const pislam_triangulate_params *p
  * can be captured into a hipGraph.  One workgroup runs a window's whole call in one launch; a batch above 1024 windows
  * is walked by the same 1024 workgroups in passes.
  *
- * Not here: ORBmatcher::Fuse, global bundle adjustment and windows beyond the limits, marginalisation, IMU terms. */
+ * Not here: ORBmatcher::Fuse (pislam_match_fuse_batch, which runs before this call so that a landmark is optimised
+ * once), global bundle adjustment and windows beyond the limits, marginalisation, IMU terms. */
 typedef struct pislam_ba_params {
   int32_t rounds;        /* 1..4 (ORB-SLAM: 2) */
   int32_t iters[4];      /* 1..32 Levenberg iterations of round r, r < rounds (ORB-SLAM: 5, 10) */

@@ -86,6 +86,10 @@ class ProjectionParams(ctypes.Structure):
         (n, ctypes.c_int32) for n in ("level_below", "level_above", "second_same_level")]
 
 
+class FuseParams(ctypes.Structure):
+    _fields_ = [("chi2_mono", ctypes.c_float), ("chi2_stereo", ctypes.c_float)]
+
+
 class EpipolarParams(ctypes.Structure):
     _fields_ = [("chi2", ctypes.c_float), ("epipole_r2", ctypes.c_float)]
 
@@ -173,6 +177,13 @@ SYMBOLS = {
                                            ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),
                                            ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ProjectionParams), _vp, _vp, _vp,
                                            _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pislam_match_fuse_reserve": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),
+                                       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), _i, _i, _sz, _i]),
+    "pislam_match_fuse_batch": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),
+                                     ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),
+                                     ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ProjectionParams),
+                                     ctypes.POINTER(ctypes.c_float), ctypes.POINTER(FuseParams), _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
     "pislam_match_stereo_reserve": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),
                                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(StereoParams), _sz, _i]),
     "pislam_match_stereo_batch": (_i, [_vp, _i, ctypes.POINTER(Level), _i, ctypes.POINTER(ctypes.c_int32),

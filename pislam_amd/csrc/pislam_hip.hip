@@ -129,11 +129,11 @@ struct pislam_ctx {
   DevBuf w_score, w_stage, w_stripcnt, w_work, w_prof, w_ovf, w_stagedesc;
   DevBuf w_ustage, w_ucount;         // bucket selection pass (pf::k_bucket_select): per-unit lists and counts
   // Guided matchers: pm::k_scaled_index's cell offsets, cell-sorted train entries and their descriptors.  One set per
-  // matcher (windowed, scaled, stereo, projection), so a graph captured for one is never invalidated by another's reserve.
+  // matcher (windowed, scaled, stereo, projection, fuse), so a graph captured for one is never invalidated by another's reserve.
   struct CellIndex {
     DevBuf off, meta, desc;
   };
-  CellIndex w_win, w_sc, w_st, w_proj;   // (w_proj: the projection matcher)
+  CellIndex w_win, w_sc, w_st, w_proj, w_fuse;   // (w_proj: the projection matcher, w_fuse: the fuse matcher)
   CellIndex w_bow;                   // word-guided matcher (pb::k_bow_index): group offsets, group-sorted indices (meta), descriptors
   CellIndex w_epi;                   // epipolar matcher (pe::k_epi_index): group offsets, group-sorted entries with their geometry (meta), descriptors
   DevBuf w_ba;                       // local bundle adjustment (pbk::k_local_ba): a slice per workgroup (pbk::ws_bytes)
@@ -512,7 +512,7 @@ PISLAM_EXPORT int pislam_ctx_destroy(pislam_ctx *c) {
                     &c->w_off, &c->w_total, &c->w_cellkp, &c->w_score, &c->w_stage, &c->w_stripcnt, &c->w_work, &c->w_prof, &c->w_ovf,
                     &c->w_stagedesc, &c->w_ustage, &c->w_ucount, &c->w_sync, &c->w_chain})
     b->release();
-  for (pislam_ctx::CellIndex *w : {&c->w_win, &c->w_sc, &c->w_st, &c->w_proj, &c->w_bow, &c->w_epi})
+  for (pislam_ctx::CellIndex *w : {&c->w_win, &c->w_sc, &c->w_st, &c->w_proj, &c->w_fuse, &c->w_bow, &c->w_epi})
     for (DevBuf *b : {&w->off, &w->meta, &w->desc}) b->release();
   c->w_db.release();
   c->w_ba.release();
@@ -1899,16 +1899,18 @@ PISLAM_EXPORT int pislam_match_projection_reserve(pislam_ctx *c, int words, cons
                          "hipMalloc(projection matcher workspace)");
 }
 
-PISLAM_EXPORT int pislam_match_projection_batch(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
-                                                const int32_t *scale_q16, const float *level_scale,
-                                                const int32_t *radius_far, const int32_t *radius_near,
-                                                const pislam_projection_params *p, const float *pose, const float *cam,
-                                                const float *xw, const float *normal, const float *drange,
-                                                const uint8_t *qlevel, const uint32_t *qdesc, const uint32_t *qcounts,
-                                                size_t q_stride, const uint32_t *tkp, const uint32_t *tdesc,
-                                                const uint32_t *tcounts, size_t t_stride, int batch, int32_t *idx,
-                                                uint32_t *dist, uint32_t *dist2, int32_t *pred, uint8_t *plevel) {
-  if (!c) return PISLAM_ERR_INVALID;
+namespace {
+
+// The projection call and the fuse call: every check of the projection call's contract, then the index and the match.
+// fz null: pislam_match_projection_batch on w; otherwise pislam_match_fuse_batch (fz's table and bounds are checked by
+// the caller, its two pointers here).
+int projection_call(pislam_ctx *c, pislam_ctx::CellIndex &w, const char *alloc_what, const pj::FuseArgs *fz, int words,
+                    const pislam_level *levels, int nlevels, const int32_t *scale_q16, const float *level_scale,
+                    const int32_t *radius_far, const int32_t *radius_near, const pislam_projection_params *p,
+                    const float *pose, const float *cam, const float *xw, const float *normal, const float *drange,
+                    const uint8_t *qlevel, const uint32_t *qdesc, const uint32_t *qcounts, size_t q_stride,
+                    const uint32_t *tkp, const uint32_t *tdesc, const uint32_t *tcounts, size_t t_stride, int batch,
+                    int32_t *idx, uint32_t *dist, uint32_t *dist2, int32_t *pred, uint8_t *plevel) {
   if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
   pm::ScaledPlan P;
   pjm::Tables tab;
@@ -1929,16 +1931,15 @@ PISLAM_EXPORT int pislam_match_projection_batch(pislam_ctx *c, int words, const 
     return fail(c, PISLAM_ERR_INVALID, "exactly one of drange (map mode) and qlevel (level mode) must be given");
   if (normal && qlevel) return fail(c, PISLAM_ERR_INVALID, "normal needs drange (map mode)");
   if (q_stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "q_stride too large");
-  const char *what = "the projection matcher takes device pointers only";
+  const char *what = fz ? "the fuse matcher takes device pointers only" : "the projection matcher takes device pointers only";
   for (const void *opt : {(const void *)normal, (const void *)drange, (const void *)qlevel, (const void *)pred,
-                          (const void *)plevel})
+                          (const void *)plevel, (const void *)(fz ? fz->qmask : nullptr)})
     if (opt && !is_device_ptr(opt)) return fail(c, PISLAM_ERR_INVALID, what);
   if (batch == 0 || q_stride == 0) return PISLAM_OK;
   PCHK(device_ptrs(c, {pose, cam, xw, qdesc, qcounts, tkp, tdesc, tcounts, idx, dist, dist2}, what));
+  if (fz) PCHK(device_ptrs(c, {fz->tobs}, what));
   HIPCHK(c, hipSetDevice(c->device));
-  const pislam_ctx::CellIndex &w = c->w_proj;
-  PCHK(index_workspace(c, c->w_proj, (size_t)P.ncells + 1, sizeof(uint2), words, t_stride, batch,
-                       "hipMalloc(projection matcher workspace)"));
+  PCHK(index_workspace(c, w, (size_t)P.ncells + 1, sizeof(uint2), words, t_stride, batch, alloc_what));
   PCHK(launch_scaled_index(c, w, P, words, tkp, tdesc, tcounts, t_stride, batch));
   const pjm::Params prm{p->min_x, p->max_x, p->min_y, p->max_y, p->cos_min, p->cos_near,
                         p->level_below, p->level_above, p->second_same_level};
@@ -1949,10 +1950,75 @@ PISLAM_EXPORT int pislam_match_projection_batch(pislam_ctx *c, int words, const 
   a.idx = idx, a.dist = dist, a.dist2 = dist2, a.pred = pred, a.plevel = plevel;
   const dim3 grid = query_grid(c, q_stride, pm::WIN_QPW, batch);
   with_words(words, [&](auto wd) {
-    hipLaunchKernelGGL(pj::k_match_projection<decltype(wd)::value>, grid, dim3(pm::WIN_THREADS), 0, c->stream, P, tab, prm,
-                       a);
+    if (fz)
+      hipLaunchKernelGGL(pj::k_match_fuse<decltype(wd)::value>, grid, dim3(pm::WIN_THREADS), 0, c->stream, P, tab, prm, a,
+                         *fz);
+    else
+      hipLaunchKernelGGL(pj::k_match_projection<decltype(wd)::value>, grid, dim3(pm::WIN_THREADS), 0, c->stream, P, tab, prm,
+                         a);
   });
-  return launch_ok(c, "k_match_projection");
+  return launch_ok(c, fz ? "k_match_fuse" : "k_match_projection");
+}
+
+}  // namespace
+
+PISLAM_EXPORT int pislam_match_projection_batch(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
+                                                const int32_t *scale_q16, const float *level_scale,
+                                                const int32_t *radius_far, const int32_t *radius_near,
+                                                const pislam_projection_params *p, const float *pose, const float *cam,
+                                                const float *xw, const float *normal, const float *drange,
+                                                const uint8_t *qlevel, const uint32_t *qdesc, const uint32_t *qcounts,
+                                                size_t q_stride, const uint32_t *tkp, const uint32_t *tdesc,
+                                                const uint32_t *tcounts, size_t t_stride, int batch, int32_t *idx,
+                                                uint32_t *dist, uint32_t *dist2, int32_t *pred, uint8_t *plevel) {
+  if (!c) return PISLAM_ERR_INVALID;
+  return projection_call(c, c->w_proj, "hipMalloc(projection matcher workspace)", nullptr, words, levels, nlevels,
+                         scale_q16, level_scale, radius_far, radius_near, p, pose, cam, xw, normal, drange, qlevel, qdesc,
+                         qcounts, q_stride, tkp, tdesc, tcounts, t_stride, batch, idx, dist, dist2, pred, plevel);
+}
+
+// ---- map-point fusion search --------------------------------------------------------------
+
+PISLAM_EXPORT int pislam_match_fuse_reserve(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
+                                            const int32_t *scale_q16, const int32_t *radius_far,
+                                            const int32_t *radius_near, int level_below, int level_above, size_t t_stride,
+                                            int batch) {
+  if (!c) return PISLAM_ERR_INVALID;
+  pm::ScaledPlan P;
+  pjm::Tables tab;
+  PCHK(projection_plan(c, words, levels, nlevels, scale_q16, radius_far, radius_near, level_below, level_above, t_stride,
+                       batch, &P, &tab));
+  HIPCHK(c, hipSetDevice(c->device));
+  return index_workspace(c, c->w_fuse, (size_t)P.ncells + 1, sizeof(uint2), words, t_stride, batch,
+                         "hipMalloc(fuse matcher workspace)");
+}
+
+PISLAM_EXPORT int pislam_match_fuse_batch(pislam_ctx *c, int words, const pislam_level *levels, int nlevels,
+                                          const int32_t *scale_q16, const float *level_scale, const int32_t *radius_far,
+                                          const int32_t *radius_near, const pislam_projection_params *p,
+                                          const float *inv_sigma2, const pislam_fuse_params *f, const float *pose,
+                                          const float *cam, const float *xw, const float *normal, const float *drange,
+                                          const uint8_t *qlevel, const uint8_t *qmask, const uint32_t *qdesc,
+                                          const uint32_t *qcounts, size_t q_stride, const uint32_t *tkp,
+                                          const uint32_t *tdesc, const int32_t *tobs_q8, const uint32_t *tcounts,
+                                          size_t t_stride, int batch, int32_t *idx, uint32_t *dist, uint32_t *dist2,
+                                          int32_t *pred, uint8_t *plevel) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!f) return fail(c, PISLAM_ERR_INVALID, "null fuse parameters");
+  if (!(f->chi2_mono > 0.0f) || !(f->chi2_stereo > 0.0f))      // (a NaN fails; +inf passes)
+    return fail(c, PISLAM_ERR_INVALID, "chi2_mono and chi2_stereo must be > 0");
+  if (nlevels < 1 || nlevels > pm::WIN_MAX_LEVELS) return fail(c, PISLAM_ERR_INVALID, "nlevels must be 1..16");
+  if (!inv_sigma2) return fail(c, PISLAM_ERR_INVALID, "null inv_sigma2");
+  pj::FuseArgs fz{};
+  for (int l = 0; l < nlevels; l++) {
+    if (!(inv_sigma2[l] > 0.0f) || !psm::finite_f(inv_sigma2[l]))
+      return fail(c, PISLAM_ERR_INVALID, "inv_sigma2 must be finite and > 0");
+    fz.inv_sigma2[l] = inv_sigma2[l];
+  }
+  fz.tobs = tobs_q8, fz.qmask = qmask, fz.chi2_mono = f->chi2_mono, fz.chi2_stereo = f->chi2_stereo;
+  return projection_call(c, c->w_fuse, "hipMalloc(fuse matcher workspace)", &fz, words, levels, nlevels, scale_q16,
+                         level_scale, radius_far, radius_near, p, pose, cam, xw, normal, drange, qlevel, qdesc, qcounts,
+                         q_stride, tkp, tdesc, tcounts, t_stride, batch, idx, dist, dist2, pred, plevel);
 }
 
 // ---- rectified stereo matching ------------------------------------------------------------

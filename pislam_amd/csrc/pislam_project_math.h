@@ -2,7 +2,9 @@
 // is the contract), stated ONCE for the device kernel (pislam_project_kernels.h) and for a plain C++ compiler
 // (tools/probes/project_host_check.cpp): the frame test, the projection of a map point through the pose (the pose call's
 // monocular arithmetic, pnm::chi2_at), the image bounds and the window centre, the distance and viewing-angle tests, the
-// predicted level and the radius.  Every operation is written out one rounding at a time; build with -ffp-contract=off.
+// predicted level and the radius; and, for pislam_match_fuse_batch (tools/probes/fuse_host_check.cpp), the reprojection
+// test of one candidate keypoint (fuse_ok).  Every operation is written out one rounding at a time; build with
+// -ffp-contract=off.
 // The level tables are only ever indexed by the counter of a loop over the levels (uniform across a wave: scalar loads of
 // kernel arguments), the entry of a query's own level is picked by a select, so on the device nothing goes through
 // scratch.
@@ -46,11 +48,17 @@ struct Query {
   int32_t xc, yc, pl, r;
 };
 
+// The unrounded projection of a live query, for the fuse call's reprojection test: pu, pv and pur = pu - bf * iz.
+struct Pixel {
+  float pu, pv, pur;
+};
+
 // Steps 1-6 of the contract for one map point of a live frame.  T: the pose (r0..r8 row-major, then t), cam: fx, fy,
-// cx, cy (bf is not read), xw: the point. Map mode: drange = (dmin, dmax), normal or null, qlevel < 0.  Level mode: drange and normal
-// null, qlevel = the query's level (0..255).
+// cx, cy (bf is read only when pix is given), xw: the point. Map mode: drange = (dmin, dmax), normal or null, qlevel < 0.
+// Level mode: drange and normal null, qlevel = the query's level (0..255).  pix (optional): the pixel of a query that
+// passed steps 1-2, unwritten otherwise.
 PISLAM_HD Query project(const float (&T)[12], const float (&cam)[5], const float *xw, const float *normal,
-                        const float *drange, int qlevel, const Tables &tab, const Params &p) {
+                        const float *drange, int qlevel, const Tables &tab, const Params &p, Pixel *pix = nullptr) {
   Query q{false, false, 0, 0, DEAD_LEVEL, 0};
   const float X = xw[0], Y = xw[1], Z = xw[2];
   // 1. the camera point and its pixel
@@ -64,6 +72,7 @@ PISLAM_HD Query project(const float (&T)[12], const float (&cam)[5], const float
   // 2. the image bounds (every comparison is false for a NaN) and the window centre
   live = live & (pu >= p.min_x) & (pu <= p.max_x) & (pv >= p.min_y) & (pv <= p.max_y);
   if (!live) return q;
+  if (pix) *pix = Pixel{pu, pv, pu - cam[4] * iz};
   const int32_t xc = (int32_t)floorf(pu + 0.5f), yc = (int32_t)floorf(pv + 0.5f);   // |pu|, |pv| <= 2^20: no overflow
   int32_t pl = 0;
   bool near = false;
@@ -96,6 +105,17 @@ PISLAM_HD Query project(const float (&T)[12], const float (&cam)[5], const float
     r = l == pl ? rl : r;
   }
   return Query{true, near, xc, yc, pl, r};
+}
+
+// The fuse call's reprojection test of one candidate keypoint: (u, v, ur) its Q8 observation words (the pose call's
+// clamp and conversion; ur == pq::MONO: monocular), w = inv_sigma2 of the keypoint's level.  A NaN fails; with both
+// bounds +inf every candidate of a live query passes (no NaN can arise: pu, pv, bf and iz are finite).
+PISLAM_HD bool fuse_ok(const Pixel &p, int32_t u, int32_t v, int32_t ur, float w, float chi2_mono, float chi2_stereo) {
+  const float ex = p.pu - pq::obs_px(u), ey = p.pv - pq::obs_px(v);
+  const float e2 = ex * ex + ey * ey;
+  if (ur == pq::MONO) return e2 * w <= chi2_mono;
+  const float er = p.pur - pq::obs_px(ur);
+  return (e2 + er * er) * w <= chi2_stereo;
 }
 
 }  // namespace pjm

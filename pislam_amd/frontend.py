@@ -375,8 +375,23 @@ def matchProjectionBatch(pose, cam, xw, qdesc, qcounts, tkp, tdesc, tcounts, lev
     projectionRadii(scale_q16, th), radius_near alone None = radius_far.  Returns (idx, dist, dist2, pred, plevel): int32
     [batch][q_stride] three times, pred int32 [batch][q_stride][2] (None with want_pred False) and plevel uint8
     [batch][q_stride] (0xff = not visible; None with want_plevel False).  Asynchronous on the ctx stream."""
-    import torch
     ctx = ctx or default_context()
+    batch, qs, words, ts = _projection_inputs(pose, cam, xw, qdesc, qcounts, tkp, tdesc, tcounts, normal, drange, qlevel)
+    lv, n, s, ls, rf, rn = _projection_tables(levels, scale_q16, level_scale, radius_far, radius_near, th)
+    p = _projection_params(levels, bounds, cos_min, cos_near, level_below, level_above, second_same_level)
+    idx, dist, dist2, pred, plevel = _projection_outputs(qdesc, idx, dist, dist2, pred, plevel, want_pred, want_plevel)
+    ctx.check(ctx.lib.pislam_match_projection_batch(ctx.h, words, lv, n, s, ls, rf, rn, ctypes.byref(p), ptr(pose), ptr(cam),
+                                                    ptr(xw), ptr(normal), ptr(drange), ptr(qlevel), ptr(qdesc),
+                                                    ptr(qcounts), qs, ptr(tkp), ptr(tdesc), ptr(tcounts), ts, batch,
+                                                    ptr(idx), ptr(dist), ptr(dist2), ptr(pred), ptr(plevel)),
+              "pislam_match_projection_batch")
+    return idx, dist, dist2, pred, plevel
+
+
+def _projection_inputs(pose, cam, xw, qdesc, qcounts, tkp, tdesc, tcounts, normal, drange, qlevel, **more):
+    """Shape, type and contiguity checks shared by matchProjectionBatch and matchFuseBatch (`more`: further tensors
+    that must be contiguous when given); returns (batch, q_stride, words, t_stride)."""
+    import torch
     batch, qs, words = (int(v) for v in qdesc.shape)
     ts = int(tdesc.shape[1])
     if int(tdesc.shape[2]) != words:
@@ -390,14 +405,22 @@ def matchProjectionBatch(pose, cam, xw, qdesc, qcounts, tkp, tdesc, tcounts, lev
             raise ValueError(f"{name} must be a float32 tensor [batch][q_stride][{k}]")
     if qlevel is not None and (qlevel.dtype != torch.uint8 or tuple(qlevel.shape) != (batch, qs)):
         raise ValueError("qlevel must be a uint8 tensor [batch][q_stride]")
-    for t in (pose, cam, xw, normal, drange, qlevel, qdesc, qcounts, tkp, tdesc, tcounts):
+    for t in (pose, cam, xw, normal, drange, qlevel, qdesc, qcounts, tkp, tdesc, tcounts) + tuple(more.values()):
         if t is not None and not t.is_contiguous():
             raise ValueError("inputs must be contiguous")
-    lv, n, s, ls, rf, rn = _projection_tables(levels, scale_q16, level_scale, radius_far, radius_near, th)
+    return batch, qs, words, ts
+
+
+def _projection_params(levels, bounds, cos_min, cos_near, level_below, level_above, second_same_level):
     if bounds is None:
         bounds = (0.0, float(int(levels[0][0]) - 1), 0.0, float(int(levels[0][1]) - 1))
-    p = capi.ProjectionParams(*(float(v) for v in bounds), float(cos_min), float(cos_near), int(level_below),
-                              int(level_above), 1 if second_same_level else 0)
+    return capi.ProjectionParams(*(float(v) for v in bounds), float(cos_min), float(cos_near), int(level_below),
+                                 int(level_above), 1 if second_same_level else 0)
+
+
+def _projection_outputs(qdesc, idx, dist, dist2, pred, plevel, want_pred, want_plevel):
+    import torch
+    batch, qs = int(qdesc.shape[0]), int(qdesc.shape[1])
     dev = qdesc.device
     if idx is None:
         idx = torch.empty((batch, qs), dtype=torch.int32, device=dev)
@@ -409,12 +432,129 @@ def matchProjectionBatch(pose, cam, xw, qdesc, qcounts, tkp, tdesc, tcounts, lev
         pred = torch.empty((batch, qs, 2), dtype=torch.int32, device=dev)
     if plevel is None and want_plevel:
         plevel = torch.empty((batch, qs), dtype=torch.uint8, device=dev)
-    ctx.check(ctx.lib.pislam_match_projection_batch(ctx.h, words, lv, n, s, ls, rf, rn, ctypes.byref(p), ptr(pose), ptr(cam),
-                                                    ptr(xw), ptr(normal), ptr(drange), ptr(qlevel), ptr(qdesc),
-                                                    ptr(qcounts), qs, ptr(tkp), ptr(tdesc), ptr(tcounts), ts, batch,
-                                                    ptr(idx), ptr(dist), ptr(dist2), ptr(pred), ptr(plevel)),
-              "pislam_match_projection_batch")
     return idx, dist, dist2, pred, plevel
+
+
+def _fuse_tables(levels, scale_q16, radius_far, th):
+    """Fuse's defaults: scale_q16 None = level_scales_q16(levels), radius_far None = projectionRadii(scale_q16, th,
+    near=1, far=1)[0] (ORB-SLAM's th * scaleFactor[l])."""
+    if scale_q16 is None:
+        scale_q16 = level_scales_q16(levels)
+    if radius_far is None:
+        sq = [int(scale_q16)] * len(levels) if isinstance(scale_q16, (int, np.integer)) else scale_q16
+        radius_far = projectionRadii(sq, th, near=1, far=1)[0].tolist()
+    return scale_q16, radius_far
+
+
+def reserveMatchFuse(levels, t_stride: int, batch: int, *, scale_q16=None, radius_far=None, radius_near=None, th=3,
+                     level_below=1, level_above=0, words=8, ctx: Context | None = None):
+    """Sizes the context's fuse-matcher workspace (pislam_match_fuse_reserve; its own, not the projection matcher's):
+    afterwards matchFuseBatch of the same or a smaller shape allocates nothing and can be captured into a hipGraph.  The
+    tables default as in matchFuseBatch."""
+    ctx = ctx or default_context()
+    scale_q16, radius_far = _fuse_tables(levels, scale_q16, radius_far, th)
+    lv, n, s, _, rf, rn = _projection_tables(levels, scale_q16, None, radius_far, radius_near, th)
+    ctx.check(ctx.lib.pislam_match_fuse_reserve(ctx.h, words, lv, n, s, rf, rn, int(level_below), int(level_above),
+                                                t_stride, batch), "pislam_match_fuse_reserve")
+
+
+def matchFuseBatch(pose, cam, xw, qdesc, qcounts, tkp, tdesc, tobs_q8, tcounts, levels, *, drange=None, normal=None,
+                   qlevel=None, qmask=None, inv_sigma2=None, chi2_mono=5.99, chi2_stereo=7.8, scale_q16=None,
+                   level_scale=None, radius_far=None, radius_near=None, th=3, bounds=None, cos_min=0.5, cos_near=0.998,
+                   level_below=1, level_above=0, second_same_level=True, idx=None, dist=None, dist2=None, pred=None,
+                   plevel=None, want_pred=True, want_plevel=True, ctx: Context | None = None):
+    """Map-point fusion search (pislam_match_fuse_batch; the contract is the comment in include/pislam_hip.h),
+    ORB-SLAM's ORBmatcher::Fuse: matchProjectionBatch with, per candidate keypoint, the chi-square test of the point's
+    reprojection error against the keypoint's own observation tobs_q8 (int32 [batch][t_stride][3] = u, v, u_right in Q8
+    level-0 pixels, INT32_MIN = monocular: poseObservationsQ8's layout) weighted by inv_sigma2 of the keypoint's level
+    (None = poseLevelWeights(nlevels)); cam's bf is used.  qmask (uint8 [batch][q_stride], optional): 0 = the point is
+    already in the key frame, or bad.  The defaults are Fuse's: th 3 with radius_far = projectionRadii(scale_q16, th,
+    near=1, far=1)[0] and no near radius, levels pl - 1 .. pl, cos_min 0.5, chi2 5.99 / 7.8.  Pass both bounds as
+    float("inf") for the Sim(3) form of Fuse (with pose = rigidFromSim3(sim)).  Every other argument and the returned
+    (idx, dist, dist2, pred, plevel) are matchProjectionBatch's.  Asynchronous on the ctx stream."""
+    import torch
+    ctx = ctx or default_context()
+    batch, qs, words, ts = _projection_inputs(pose, cam, xw, qdesc, qcounts, tkp, tdesc, tcounts, normal, drange, qlevel,
+                                              tobs_q8=tobs_q8, qmask=qmask)
+    if tobs_q8 is None or tobs_q8.dtype != torch.int32 or tuple(tobs_q8.shape) != (batch, ts, 3):
+        raise ValueError("tobs_q8 must be an int32 tensor [batch][t_stride][3]")
+    if qmask is not None and (qmask.dtype != torch.uint8 or tuple(qmask.shape) != (batch, qs)):
+        raise ValueError("qmask must be a uint8 tensor [batch][q_stride]")
+    scale_q16, radius_far = _fuse_tables(levels, scale_q16, radius_far, th)
+    lv, n, s, ls, rf, rn = _projection_tables(levels, scale_q16, level_scale, radius_far, radius_near, th)
+    if inv_sigma2 is None:
+        inv_sigma2 = poseLevelWeights(n)
+    w = [float(v) for v in np.asarray(inv_sigma2, dtype=np.float32).reshape(-1)]
+    if len(w) != n:
+        raise ValueError(f"inv_sigma2: {len(w)} values for {n} levels")
+    wt = (ctypes.c_float * max(1, n))(*w)
+    p = _projection_params(levels, bounds, cos_min, cos_near, level_below, level_above, second_same_level)
+    f = capi.FuseParams(float(chi2_mono), float(chi2_stereo))
+    idx, dist, dist2, pred, plevel = _projection_outputs(qdesc, idx, dist, dist2, pred, plevel, want_pred, want_plevel)
+    ctx.check(ctx.lib.pislam_match_fuse_batch(ctx.h, words, lv, n, s, ls, rf, rn, ctypes.byref(p), wt, ctypes.byref(f),
+                                              ptr(pose), ptr(cam), ptr(xw), ptr(normal), ptr(drange), ptr(qlevel),
+                                              ptr(qmask), ptr(qdesc), ptr(qcounts), qs, ptr(tkp), ptr(tdesc), ptr(tobs_q8),
+                                              ptr(tcounts), ts, batch, ptr(idx), ptr(dist), ptr(dist2), ptr(pred),
+                                              ptr(plevel)), "pislam_match_fuse_batch")
+    return idx, dist, dist2, pred, plevel
+
+
+def rigidFromSim3(sim):
+    """The pose of matchFuseBatch / matchProjectionBatch for the Sim(3) form of Fuse (Fuse(pKF, Scw, ...)): sim
+    [batch][13] = (R row-major, t, s) with Xc = s R Xw + t becomes [batch][12] = (R, t / s); the pixel of a point is
+    the same, since the projection divides by z.  Computed in float64 and rounded once to float32.  A torch tensor
+    (device or host) or a numpy array, returned as the same kind."""
+    if isinstance(sim, np.ndarray):
+        a = sim.astype(np.float64)
+        if a.ndim != 2 or a.shape[1] != 13:
+            raise ValueError("sim must be [batch][13]")
+        return np.concatenate([a[:, :9], a[:, 9:12] / a[:, 12:13]], axis=1).astype(np.float32)
+    import torch
+    if sim.dim() != 2 or int(sim.shape[1]) != 13:
+        raise ValueError("sim must be [batch][13]")
+    a = sim.to(torch.float64)
+    return torch.cat([a[:, :9], a[:, 9:12] / a[:, 12:13]], dim=1).to(torch.float32).contiguous()
+
+
+def fuseDecisions(sel, qid, tpoint, nobs):
+    """What ORBmatcher::Fuse does with each accepted match, after matchFuseBatch and selectMatchesBatch (max_dist 50,
+    ratio None, rot_keep 0): sel = (sel_q, sel_t, nsel); qid (integer [batch][q_stride]) is the map's id of each query
+    point, tpoint (integer [batch][t_stride]) the id of the point each keypoint holds or -1, nobs (integer [npoints])
+    the number of observations of every point.  Per slot s < nsel[b], with o = tpoint[b][sel_t[b][s]] and
+    me = qid[b][sel_q[b][s]]:
+      o < 0               action 1: add the observation (keep me, drop -1)
+      o == me             action 0: nothing to do (keep -1, drop -1)
+      nobs[o] > nobs[me]  action 2: the keypoint's point replaces the query (keep o, drop me)
+      otherwise           action 3: the query replaces the keypoint's point (keep me, drop o); a tie keeps the query,
+                          as ORB-SLAM does.
+    The slots at and beyond nsel[b] of sel_q and sel_t are unwritten memory: they are masked before gathering and come
+    out as action 0, keep -1, drop -1.  Returns (action uint8, keep int64, drop int64), each [batch][q_stride], slot by
+    slot as in sel.  Torch ops on the current torch stream.
+    With the caller stay: applying the decisions to the map, in batch order (a point dropped in frame b may be the
+    keep of a later frame: follow the chain of replacements across key frames, as ORB-SLAM's GetReplaced does), and
+    descriptor / normal updates of the kept points.  With unique=0 in the selection several queries may share one
+    keypoint; each gets its decision against the state passed in, not against the others' outcome."""
+    import torch
+    sel_q, sel_t, nsel = sel
+    batch, qs = (int(v) for v in sel_q.shape)
+    dev = sel_q.device
+    live = torch.arange(qs, device=dev)[None, :] < nsel.to(torch.int64)[:, None]
+    zero = torch.zeros_like(live, dtype=torch.int64)
+    qi = torch.where(live, sel_q.to(torch.int64), zero).clamp(0, int(qid.shape[1]) - 1)
+    ti = torch.where(live, sel_t.to(torch.int64), zero).clamp(0, int(tpoint.shape[1]) - 1)
+    me = torch.gather(qid.to(torch.int64), 1, qi)
+    o = torch.gather(tpoint.to(torch.int64), 1, ti)
+    n = nobs.to(torch.int64).reshape(-1)
+    last = max(int(n.shape[0]) - 1, 0)
+    n_o, n_me = n[o.clamp(0, last)], n[me.clamp(0, last)]
+    none = torch.full_like(me, -1)
+    add, same = live & (o < 0), live & (o >= 0) & (o == me)
+    theirs = live & (o >= 0) & (o != me) & (n_o > n_me)
+    ours = live & (o >= 0) & (o != me) & ~(n_o > n_me)
+    action = (add.to(torch.uint8) + 2 * theirs.to(torch.uint8) + 3 * ours.to(torch.uint8)).contiguous()
+    keep = torch.where(add | ours, me, torch.where(theirs, o, none))
+    drop = torch.where(theirs, me, torch.where(ours, o, none))
+    return action, keep.contiguous(), drop.contiguous()
 
 
 def _stereo_tables(levels, scale_q16, row_radius0, level_span, min_disp, max_disp, max_hamming, sad_radius,
