@@ -2132,6 +2132,142 @@ int pislam_local_ba_batch(pislam_ctx *ctx, const pislam_ba_params *p, const floa
                           size_t pt_stride, size_t stride, int batch, float *poses_out, float *xw_out, uint8_t *inlier,
                           uint32_t *ninliers, double *cost, uint32_t *status);
 
+/* ---- after a loop is accepted: essential-graph optimisation, map points moved ---- */
+
+/* What ORB-SLAM's Optimizer::OptimizeEssentialGraph does, per GRAPH of a batch (one map, or
+ * one loop hypothesis of one map): the FREE vertex similarities are moved so that the sum of the squared relative-Sim(3)
+ * errors over the edges becomes minimal; the FIXED vertices (ORB-SLAM holds the loop key frame) are the gauge.
+ * Levenberg; the damped normal equations are solved matrix-free by block-Jacobi preconditioned conjugate gradients.
+ * The reference ships nothing of the kind: the semantics are this library's own.  This comment is the contract.
+ * ALL arithmetic of this call is binary64: an input word v is converted exactly, double(v), an output is rounded once,
+ * float(v).  Every +, -, *, / below is ONE binary64 operation rounded to nearest even, in the order the parentheses
+ * give (a op b op c without parentheses is (a op b) op c), NEVER fused into an FMA; there is no transcendental
+ * function; a NaN fails every comparison.  tests/test_pose_graph.py restates it in numpy; tools/probes/
+ * graph_host_check.cpp compiles the kernel's own arithmetic header (pislam_graph_math.h) for the host and runs a graph
+ * serially.
+ *
+ * Inputs, all device, read only.  Graph b has nv = min(v_counts[b], v_stride) vertices and ne = min(e_counts[b],
+ * e_stride) edges (PISLAM_COUNT_INVALID counts as 0); entries at and beyond a count are never read.
+ *   sims       float [batch][v_stride][13]: S_k = (R row-major, t, s), world to camera, Xc = s R Xw + t: the sim_out
+ *              layout of pislam_sim3_ransac_batch and pislam_sim3_refine_batch
+ *   fixed      uint8 [batch][v_stride]: nonzero = the vertex is held
+ *   edges      uint32 [batch][e_stride][2] = (i, j): the vertex pair of edge e
+ *   meas       float [batch][e_stride][13]: M_e, the measured S_j o S_i^-1 (ORB-SLAM's Sji)
+ *   weight     float [batch][e_stride] or NULL: w_e, finite and >= 0; NULL: every w_e = 1.0 (ORB-SLAM: identity
+ *              information)
+ *   inc_ptr    uint32 [batch][v_stride + 1], inc uint32 [batch][2 * e_stride]: the incidence index.  Vertex k's ENTRIES
+ *              are inc[inc_ptr[k] .. inc_ptr[k+1]); an entry is edge << 1 | side, side 0: k is the edge's i, side 1: its
+ *              j.  The index is CONSISTENT iff inc_ptr[0] == 0, inc_ptr[k] <= inc_ptr[k+1], inc_ptr[nv] == 2 * ne, every
+ *              entry of k names an edge < ne whose stated side is k, and the entries of a vertex are strictly ascending.
+ *              Then every (edge, side) is an entry of exactly one vertex, and every per-vertex sum below has one owner
+ *              and one order: ascending entries.
+ *
+ * Similarities.  A o B = (R_A R_B, s_A*(R_A t_B) + t_A, s_A*s_B), where a matrix product entry and a matrix-vector
+ * entry is (x0*y0 + x1*y1) + x2*y2.  The ERROR of edge e at a state, with G = M_e o S_i:
+ *   R_E = R_G R_j' (entry (a, b) = (G_a0*Rj_b0 + G_a1*Rj_b1) + G_a2*Rj_b2),  s_E = s_G / s_j,
+ *   t_E = t_G - s_E*(R_E t_j)   (componentwise), that is E = M_e o S_i o S_j^-1.
+ * The RESIDUAL r = (omega, upsilon, sigma) in R^7, with c = 1.0 + ((R_E00 + R_E11) + R_E22):
+ *   omega = ((2.0*(R_E21 - R_E12))/c, (2.0*(R_E02 - R_E20))/c, (2.0*(R_E10 - R_E01))/c),  upsilon = t_E,
+ *   sigma = (2.0*(s_E - 1.0))/(s_E + 1.0).
+ * omega is the inverse of the pose call's Cayley map and sigma the inverse of the similarity refinement's factor
+ * k(sigma) = (2 + sigma)/(2 - sigma), so r is the inverse of Retract at the identity: rational, no acos and no log, and
+ * zero exactly when E is the identity.  It differs from g2o's Sim3 log in the terms of higher order in r only (the
+ * rotation part is 2 tan(theta/2) against theta, the scale part 2 tanh(log(s)/2) against log s, the translation is not
+ * multiplied by the inverse of the log's V matrix), which moves the minimiser of an inconsistent graph slightly and the
+ * minimiser of a consistent one not at all.  The edge is ADMISSIBLE iff c > 2^-10 (a rotation error short of pi);
+ * otherwise the state is INADMISSIBLE.  A dot product of two 7-vectors is ((((((a0*b0 + a1*b1) + a2*b2) + a3*b3) +
+ * a4*b4) + a5*b5) + a6*b6).
+ *   F = the sum over the edges of w_e*(r_e . r_e): 256 partial sums start at +0.0; partial e mod 256 takes its edges in
+ *   ascending e; then the partials are combined by halving as in the pose call (128, 64, .. 1).
+ *
+ * The JACOBIANS of r_e with respect to the left increments d = (omega, upsilon, sigma) of S_i and S_j (S' = Retract(S,
+ * d), pislam_sim3_refine_batch's Retract word for word: R' = Q R, t' = k*(Q t) + upsilon, s' = k*s), in closed form
+ * from the 13 words of E and of M = M_e, with c = t_M - t_E:
+ *   J_i d  = (a, ((c x a) + s_M*(R_M upsilon)) - sigma*c, sigma)  with a = R_M omega
+ *   J_j d  = -(R_E omega, s_E*(R_E upsilon), sigma)
+ *   J_i' u = (R_M' (u_w - (c x u_v)), s_M*(R_M' u_v), u_s - (c . u_v)),   J_j' u = -(R_E' u_w, s_E*(R_E' u_v), u_s)
+ * (x: the cross product, each component one difference of two products; the sums of the upsilon row from the left).
+ * The translation rows are the exact derivative at any E; the rotation and scale rows are exact to first order at
+ * r = 0 (J_i = L_E Ad(M), J_j = -L_E Ad(E) with L_E the identity plus the upsilon-row terms -[t_E]x and t_E).  The
+ * acceptance test on the exact F guards the approximation away from r = 0.  As a dense 7 x 7 matrix J_i has the rows
+ * (R_M, 0, 0), ([c]x R_M, s_M*R_M, -c), (0, 0, 1.0) and J_j is -diag(R_E, s_E*R_E, 1.0), the other entries +0.0.
+ *
+ * A SOLVE at lambda of (J'WJ + lambda diag(J'WJ)) d = -J'W r in the 7 unknowns of every free vertex.
+ *   Per free vertex k, over its entries in ascending order, starting at +0.0: the block H_k (upper triangle) gets
+ *     H_ab = H_ab + w_e*h with h = the sum over the rows q = 0..6 of J_qa*J_qb in ascending q, all seven products
+ *     carried out, J the dense matrix of the entry's side; the gradient gets g_k = g_k + J'(w_e*r_e).  diag_k = the
+ *     diagonal of H_k.  The block with its diagonal times (1.0 + lambda) is eliminated WITHOUT pivoting exactly as the
+ *     pose call's solve (f = A[r][c]/A[c][c]; A[r][j] = A[r][j] - f*A[c][j] for j > c); the solve FAILS unless every
+ *     pivot is > 0, so a free vertex without an edge makes every solve fail.  Sol_k(b): b_r = b_r - f_rc*b_c for c
+ *     ascending, r > c ascending; x_r = (b_r - A_r,r+1*x_r+1 - .. - A_r6*x_6)/A_rr for r = 6 .. 0.
+ *   Start: x_k = 0, r_k = -g_k, z_k = Sol_k(r_k), p_k = z_k; p of a fixed vertex is +0.0 throughout.  A sum over the
+ *     vertices, here rz = sum of r_k . z_k: 256 partial sums from +0.0; partial k mod 256 takes its free vertices in
+ *     ascending k; then the halving tree.  thr = (cg_tol*cg_tol)*rz.
+ *   Iteration n = 0 .. cg_iters - 1: stop if rz <= thr.  Per edge u_e = w_e*(J_i p_i + J_j p_j) componentwise.  Per
+ *     free vertex (A p)_k = the sum over its entries in ascending order, from +0.0, of J' u_e (the entry's side), then
+ *     (A p)_k,a = (A p)_k,a + (lambda*diag_k,a)*p_k,a.  pAp = the vertex sum of p_k . (A p)_k; the solve FAILS unless
+ *     pAp > 0.  alpha = rz/pAp; x_k = x_k + alpha*p_k; r_k = r_k - alpha*(A p)_k; z_k = Sol_k(r_k); rz' = the vertex sum
+ *     of r_k . z_k; beta = rz'/rz; p_k = z_k + beta*p_k; rz = rz'.
+ *   d = x.  The solve fails as well when a word of d is not finite or |sigma_k| < 2 is false for a free vertex.  dmax =
+ *     the largest |word| of d.  Trial state: S'_k = Retract(S_k, d_k) for every free vertex.
+ *
+ * Per graph.  The state is double(input) and stays in binary64 for the whole call, as two sets: current and trial.
+ *   Refused on the device, in this order: code 3 (structure): an edge index >= nv, i == j, an inconsistent incidence
+ *   index, or no fixed vertex; code 2 (values): a word of sims below nv, of meas or of weight below ne is not finite,
+ *   an s <= 0, a weight < 0, or the input state is inadmissible; code 1: ne == 0 or no free vertex: nothing to do.
+ *   Otherwise ONE round of the pose call's Levenberg rule word for word: lambda = 2^-10; up to `iters` iterations; a
+ *   failed solve: lambda = min(8.0*lambda, 2^20), the iteration is spent; otherwise one evaluation of F at the trial
+ *   state; an inadmissible trial state is rejected like a failed solve; F' < F: the trial state is taken, lambda =
+ *   max(lambda*0.25, 2^-30), else lambda = min(8.0*lambda, 2^20); the round ends when dmax <= eps.  No robust kernel and
+ *   no classification: ORB-SLAM has none here.
+ *
+ * Outputs, per graph, all device.  sims_out float [batch][v_stride][13]: float(S_k) for a free vertex, the input copied
+ * for a fixed one; cost double [batch] = F at the final state; status uint32 [batch] = code | evaluations << 8
+ * (evaluations = the evaluations of F made, the input state's included).  For the codes 1 to 3 the outputs are the
+ * inputs copied, cost is 0 and status is the code.  Entries at and beyond a count are never written.  sims_out may be
+ * exactly sims (a graph reads its similarities before it writes); no other overlap of an output with an input or
+ * another output is allowed.
+ *
+ * Limits: the parameter ranges in the struct comments; 1 <= v_stride <= 4096, 1 <= e_stride <= 16384; batch >= 0 with
+ * no upper limit (batch == 0 is a no-op that returns PISLAM_OK after the checks of p and the shape); offsets use size_t
+ * arithmetic.  Any violation, or a NULL or host pointer where a device pointer is required (weight alone may be NULL):
+ * PISLAM_ERR_INVALID, before anything is launched or written.  `p` is host memory, read during the call.  Asynchronous
+ * on the context stream.  The workspace (per workgroup 936 bytes per vertex of v_stride and 328 per edge of e_stride,
+ * each array rounded up to 16 bytes and the slice to 256: 8.8 MiB at the limits) belongs to the context and grows on
+ * demand, which synchronises; after pislam_pose_graph_reserve of the same or a larger shape the call allocates nothing
+ * and never synchronises, so it can be captured into a hipGraph.  One workgroup runs a graph's whole call in one
+ * launch, so a single large graph uses one compute unit; a batch above 1024 graphs is walked by the same 1024
+ * workgroups in passes.
+ *
+ * Not here: a robust kernel, a several-workgroup form for one large graph, global bundle adjustment afterwards. */
+typedef struct pislam_pose_graph_params {
+  int32_t iters;     /* 1..64 Levenberg iterations (ORB-SLAM: 20) */
+  int32_t cg_iters;  /* 1..1024 conjugate-gradient iterations of a solve at the most */
+  double cg_tol;     /* in [0, 1): a solve stops when r'z <= cg_tol^2 times its first value */
+  double eps;        /* >= 0: the round ends when no |increment word| exceeds it */
+} pislam_pose_graph_params;
+int pislam_pose_graph_reserve(pislam_ctx *ctx, size_t v_stride, size_t e_stride, int batch);
+int pislam_pose_graph_batch(pislam_ctx *ctx, const pislam_pose_graph_params *p, const float *sims,
+                            const uint32_t *v_counts, const uint8_t *fixed, const uint32_t *edges, const float *meas,
+                            const float *weight, const uint32_t *e_counts, const uint32_t *inc_ptr, const uint32_t *inc,
+                            size_t v_stride, size_t e_stride, int batch, float *sims_out, double *cost, uint32_t *status);
+
+/* The last step of LoopClosing::CorrectLoop: every map point moves with its reference key frame.  Point p < npt =
+ * min(pt_counts[b], pt_stride) of element b with k = ref[p]: in binary64, one rounded operation at a time, with O =
+ * double(sims_old[b][k]) and N = double(sims_new[b][k]) and X = double(xw[p]):
+ *   c_a = s_O*((O_a0*X0 + O_a1*X1) + O_a2*X2) + t_O,a        (to the camera with the old similarity)
+ *   d = c - t_N;  X'_a = ((N_0a*d0 + N_1a*d1) + N_2a*d2)/s_N  (back to the world with the new one)
+ * xw_out[p] = float(X'), status[p] = 0.  If k >= nv = min(v_counts[b], v_stride) or a word of float(X') is not finite,
+ * the point stays as it was (xw_out[p] = xw[p]) and status[p] = 1.  xw float [batch][pt_stride][3], ref uint16
+ * [batch][pt_stride], sims_old and sims_new float [batch][v_stride][13], xw_out as xw, status uint8 [batch][pt_stride];
+ * entries at and beyond npt are neither read nor written.  xw_out may be exactly xw; no other overlap of an output with
+ * an input or another output is allowed.  1 <= pt_stride < 2^31, 1 <= v_stride <= 65536, batch >= 0; all pointers
+ * device; a violation: PISLAM_ERR_INVALID before anything is launched.  One thread per point, walked in grid passes;
+ * asynchronous on the context stream, no workspace: capturable as it is. */
+int pislam_map_points_correct_batch(pislam_ctx *ctx, const float *xw, const uint16_t *ref, const uint32_t *pt_counts,
+                                    const float *sims_old, const float *sims_new, const uint32_t *v_counts,
+                                    size_t pt_stride, size_t v_stride, int batch, float *xw_out, uint8_t *status);
+
 /* ---- multi-GPU: one process per GPU, pyramids sharded, ONE collective ---- */
 
 /* The reference is a single-threaded per-frame loop without cross-frame state

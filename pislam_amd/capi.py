@@ -66,6 +66,11 @@ class BaParams(ctypes.Structure):
                 ("min_obs", ctypes.c_int32), ("eps", ctypes.c_double)]
 
 
+class PoseGraphParams(ctypes.Structure):
+    _fields_ = [("iters", ctypes.c_int32), ("cg_iters", ctypes.c_int32), ("cg_tol", ctypes.c_double),
+                ("eps", ctypes.c_double)]
+
+
 class PnpParams(ctypes.Structure):
     _fields_ = [("hypotheses", ctypes.c_int32), ("seed", ctypes.c_uint32), ("min_inliers", ctypes.c_int32)]
 
@@ -215,6 +220,10 @@ SYMBOLS = {
     "pislam_local_ba_reserve": (_i, [_vp, _sz, _sz, _sz, _i]),
     "pislam_local_ba_batch": (_i, [_vp, ctypes.POINTER(BaParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    ctypes.POINTER(ctypes.c_float), _i, _sz, _sz, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pislam_pose_graph_reserve": (_i, [_vp, _sz, _sz, _i]),
+    "pislam_pose_graph_batch": (_i, [_vp, ctypes.POINTER(PoseGraphParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                     _sz, _i, _vp, _vp, _vp]),
+    "pislam_map_points_correct_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i, _vp, _vp]),
     "pislam_pnp_ransac_batch": (_i, [_vp, ctypes.POINTER(PnpParams), _vp, _vp, _vp, _vp, _vp,
                                      ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pislam_sim3_ransac_batch": (_i, [_vp, ctypes.POINTER(Sim3Params), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -69,6 +69,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_sim3_refine_kernels.h"
 #include "pislam_mappoint_kernels.h"
 #include "pislam_ba_kernels.h"
+#include "pislam_graph_kernels.h"
 #include "pislam_warp_kernels.h"
 #include "pislam_clahe_kernels.h"
 
@@ -137,6 +138,7 @@ struct pislam_ctx {
   CellIndex w_bow;                   // word-guided matcher (pb::k_bow_index): group offsets, group-sorted indices (meta), descriptors
   CellIndex w_epi;                   // epipolar matcher (pe::k_epi_index): group offsets, group-sorted entries with their geometry (meta), descriptors
   DevBuf w_ba;                       // local bundle adjustment (pbk::k_local_ba): a slice per workgroup (pbk::ws_bytes)
+  DevBuf w_pg;                       // essential-graph optimisation (pgk::k_pose_graph): a slice per workgroup (pgr::ws_bytes)
   DevBuf w_db;                       // key-frame database query (pd::k_db_accumulate .. k_db_merge): accumulator planes, maxima, partial lists
   // Host-built plan tables the kernels read instead of walking the plan (the bucket selection pass's unit table): one
   // device buffer per distinct CONTENT, never rewritten in place — a captured graph keeps reading the table
@@ -516,6 +518,7 @@ PISLAM_EXPORT int pislam_ctx_destroy(pislam_ctx *c) {
     for (DevBuf *b : {&w->off, &w->meta, &w->desc}) b->release();
   c->w_db.release();
   c->w_ba.release();
+  c->w_pg.release();
   for (auto *t : c->plan_tables) {
     t->dev.release();
     delete t;
@@ -3112,6 +3115,100 @@ PISLAM_EXPORT int pislam_local_ba_batch(pislam_ctx *c, const pislam_ba_params *p
   a.ws = c->w_ba.as<char>();
   hipLaunchKernelGGL(pbk::k_local_ba, dim3((unsigned)std::min(batch, prf::GRID_CAP)), dim3(prf::THREADS), 0, c->stream, a);
   return launch_ok(c, "k_local_ba");
+}
+
+// ---- essential-graph optimisation and map-point correction after a loop ---------------------
+
+namespace {
+
+int pose_graph_shape(pislam_ctx *c, size_t v_stride, size_t e_stride, int batch) {
+  if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
+  if (v_stride < 1 || v_stride > (size_t)pgr::MAX_V) return fail(c, PISLAM_ERR_INVALID, "v_stride must be 1..4096");
+  if (e_stride < 1 || e_stride > (size_t)pgr::MAX_E) return fail(c, PISLAM_ERR_INVALID, "e_stride must be 1..16384");
+  return PISLAM_OK;
+}
+
+int pose_graph_workspace(pislam_ctx *c, size_t v_stride, size_t e_stride, int batch) {
+  const size_t groups = (size_t)std::min(batch, prf::GRID_CAP);
+  if (c->w_pg.ensure(pgr::ws_bytes(v_stride, e_stride) * groups) != PISLAM_OK)
+    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(pose graph workspace)");
+  return PISLAM_OK;
+}
+
+}  // namespace
+
+PISLAM_EXPORT int pislam_pose_graph_reserve(pislam_ctx *c, size_t v_stride, size_t e_stride, int batch) {
+  if (!c) return PISLAM_ERR_INVALID;
+  PCHK(pose_graph_shape(c, v_stride, e_stride, batch));
+  if (batch == 0) return PISLAM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  return pose_graph_workspace(c, v_stride, e_stride, batch);
+}
+
+PISLAM_EXPORT int pislam_pose_graph_batch(pislam_ctx *c, const pislam_pose_graph_params *p, const float *sims,
+                                          const uint32_t *v_counts, const uint8_t *fixed, const uint32_t *edges,
+                                          const float *meas, const float *weight, const uint32_t *e_counts,
+                                          const uint32_t *inc_ptr, const uint32_t *inc, size_t v_stride, size_t e_stride,
+                                          int batch, float *sims_out, double *cost, uint32_t *status) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
+  if (p->iters < 1 || p->iters > 64) return fail(c, PISLAM_ERR_INVALID, "iters must be 1..64");
+  if (p->cg_iters < 1 || p->cg_iters > 1024) return fail(c, PISLAM_ERR_INVALID, "cg_iters must be 1..1024");
+  if (!(p->cg_tol >= 0.0 && p->cg_tol < 1.0)) return fail(c, PISLAM_ERR_INVALID, "cg_tol must be in [0, 1)");
+  PCHK(check_refine_eps(c, p->eps));
+  PCHK(pose_graph_shape(c, v_stride, e_stride, batch));
+  if (batch == 0) return PISLAM_OK;
+  const char *what = "the pose graph call takes device pointers only";
+  PCHK(device_ptrs(c, {sims, v_counts, fixed, edges, meas, e_counts, inc_ptr, inc, sims_out, cost, status}, what));
+  if (weight && !is_device_ptr(weight)) return fail(c, PISLAM_ERR_INVALID, what);
+  {
+    const size_t B = (size_t)batch, word = B * sizeof(uint32_t), sim = B * v_stride * 13 * sizeof(float);
+    const LkRange in[] = {{sims, sim}, {v_counts, word}, {fixed, B * v_stride}, {edges, B * e_stride * 2 * sizeof(uint32_t)},
+                          {meas, B * e_stride * 13 * sizeof(float)}, {weight, B * e_stride * sizeof(float)}, {e_counts, word},
+                          {inc_ptr, B * (v_stride + 1) * sizeof(uint32_t)}, {inc, B * e_stride * 2 * sizeof(uint32_t)}};
+    const LkRange out[] = {{sims_out, sim}, {cost, B * sizeof(double)}, {status, word}};
+    // sims_out == sims is allowed: a graph reads its similarities before it writes them
+    if (const char *bad = ranges_overlap(in, out, 0)) return fail(c, PISLAM_ERR_INVALID, bad);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  PCHK(pose_graph_workspace(c, v_stride, e_stride, batch));
+  pgk::PgArgs a{};
+  a.sims = sims, a.meas = meas, a.weight = weight, a.fixed = fixed, a.v_counts = v_counts, a.e_counts = e_counts;
+  a.edges = edges, a.inc_ptr = inc_ptr, a.inc = inc, a.v_stride = v_stride, a.e_stride = e_stride, a.batch = batch;
+  a.p = pgr::Params{p->iters, p->cg_iters, p->cg_tol, p->eps};
+  a.sims_out = sims_out, a.cost = cost, a.status = status, a.ws = c->w_pg.as<char>();
+  hipLaunchKernelGGL(pgk::k_pose_graph, dim3((unsigned)std::min(batch, prf::GRID_CAP)), dim3(prf::THREADS), 0, c->stream, a);
+  return launch_ok(c, "k_pose_graph");
+}
+
+PISLAM_EXPORT int pislam_map_points_correct_batch(pislam_ctx *c, const float *xw, const uint16_t *ref,
+                                                  const uint32_t *pt_counts, const float *sims_old, const float *sims_new,
+                                                  const uint32_t *v_counts, size_t pt_stride, size_t v_stride, int batch,
+                                                  float *xw_out, uint8_t *status) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
+  if (pt_stride < 1 || pt_stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "pt_stride must be 1..2^31 - 1");
+  if (v_stride < 1 || v_stride > 65536) return fail(c, PISLAM_ERR_INVALID, "v_stride must be 1..65536");
+  if (batch == 0) return PISLAM_OK;
+  PCHK(device_ptrs(c, {xw, ref, pt_counts, sims_old, sims_new, v_counts, xw_out, status},
+                   "the map-point correction takes device pointers only"));
+  {
+    const size_t B = (size_t)batch, word = B * sizeof(uint32_t), pts = B * pt_stride * 3 * sizeof(float);
+    const size_t sim = B * v_stride * 13 * sizeof(float);
+    const LkRange in[] = {{xw, pts}, {ref, B * pt_stride * sizeof(uint16_t)}, {pt_counts, word}, {sims_old, sim},
+                          {sims_new, sim}, {v_counts, word}};
+    const LkRange out[] = {{xw_out, pts}, {status, B * pt_stride}};
+    // xw_out == xw is allowed: a point is read before it is written, by the same thread
+    if (const char *bad = ranges_overlap(in, out, 0)) return fail(c, PISLAM_ERR_INVALID, bad);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  pgk::McArgs a{};
+  a.xw = xw, a.sims_old = sims_old, a.sims_new = sims_new, a.ref = ref, a.pt_counts = pt_counts, a.v_counts = v_counts;
+  a.pt_stride = pt_stride, a.v_stride = v_stride, a.total = (size_t)batch * pt_stride, a.xw_out = xw_out, a.status = status;
+  const size_t groups = (a.total + pgk::MC_THREADS - 1) / pgk::MC_THREADS;
+  hipLaunchKernelGGL(pgk::k_map_points_correct, dim3((unsigned)std::min<size_t>(groups, pgk::MC_GRID_CAP)),
+                     dim3(pgk::MC_THREADS), 0, c->stream, a);
+  return launch_ok(c, "k_map_points_correct");
 }
 
 // ---- bag of words: integer weights and the key-frame database -----------------------------

@@ -1860,6 +1860,174 @@ def localBundleAdjustBatch(poses, cams, kf_counts, kf_free, xw, pt_counts, obs_q
     return poses_out, xw_out, inlier, ninliers, cost, status
 
 
+# ---- after a loop is accepted: essential-graph optimisation, map points moved ----------
+POSE_GRAPH_MAX_VERTICES, POSE_GRAPH_MAX_EDGES = 4096, 16384
+
+
+def relativeSim3(sim_i, sim_j):
+    """M = S_j o S_i^-1 for similarities [..][13] = (R row-major, t, s): the measurement of an essential-graph edge (i,
+    j) taken from the two vertices (ORB-SLAM's Sji).  Computed in float64 and rounded once to float32.  Torch tensors."""
+    import torch
+    a, b = sim_i.to(torch.float64), sim_j.to(torch.float64)
+    Ri, Rj = a[..., :9].reshape(*a.shape[:-1], 3, 3), b[..., :9].reshape(*b.shape[:-1], 3, 3)
+    R = Rj @ Ri.transpose(-1, -2)
+    s = b[..., 12:13] / a[..., 12:13]
+    t = b[..., 9:12] - s * (R @ a[..., 9:12, None])[..., 0]
+    return torch.cat([R.reshape(*a.shape[:-1], 9), t, s], dim=-1).to(torch.float32)
+
+
+def essentialGraph(sims, fixed, pairs, meas=None, weight=None):
+    """The padded batch arrays and the incidence index of poseGraphBatch from per-graph lists.  One graph: sims float32
+    [nv][13] (world to camera, the sim_out layout), fixed a boolean or integer tensor [nv] (nonzero: held), pairs an
+    integer tensor [ne][2] = (i, j); a batch: lists of such tensors, one entry per graph.  meas: None, or float32
+    [m][13] with m <= ne, the measurements S_j o S_i^-1 of the LAST m pairs (the loop edges, which come with their own
+    measurement); the pairs before them (spanning tree, covisibility) get relativeSim3 of the similarities passed in, as
+    ORB-SLAM takes them from the uncorrected poses.  weight: None or float32 [ne].  Returns (sims [batch][v_stride][13],
+    v_counts int32, fixed uint8 [batch][v_stride], edges int32 [batch][e_stride][2], meas float32
+    [batch][e_stride][13], weight float32 [batch][e_stride] or None, e_counts int32, inc_ptr int32
+    [batch][v_stride + 1], inc int32 [batch][2 * e_stride]) with the strides of the largest graph (at least 1).  A vertex's
+    entries edge << 1 | side are ascending.  The pairs are not checked: the call refuses a malformed graph with code 3.
+    Torch ops on the current torch stream."""
+    import torch
+    one = not isinstance(sims, (list, tuple))
+    if one:
+        sims, fixed, pairs, meas, weight = [sims], [fixed], [pairs], [meas], [weight]
+    B = len(sims)
+    meas = [None] * B if meas is None else meas
+    have_w = weight is not None and any(w is not None for w in weight)
+    weight = [None] * B if weight is None else weight
+    if not (len(fixed) == len(pairs) == len(meas) == len(weight) == B) or B == 0:
+        raise ValueError("one entry per graph in every list")
+    dev = sims[0].device
+    V = max(max(int(s.shape[0]) for s in sims), 1)
+    E = max(max(int(p.shape[0]) for p in pairs), 1)
+    if V > POSE_GRAPH_MAX_VERTICES or E > POSE_GRAPH_MAX_EDGES:
+        raise ValueError(f"at most {POSE_GRAPH_MAX_VERTICES} vertices and {POSE_GRAPH_MAX_EDGES} edges per graph")
+    o_s = torch.zeros((B, V, 13), dtype=torch.float32, device=dev)
+    o_f = torch.zeros((B, V), dtype=torch.uint8, device=dev)
+    o_e = torch.zeros((B, E, 2), dtype=torch.int32, device=dev)
+    o_m = torch.zeros((B, E, 13), dtype=torch.float32, device=dev)
+    o_w = torch.ones((B, E), dtype=torch.float32, device=dev) if have_w else None
+    o_p = torch.zeros((B, V + 1), dtype=torch.int32, device=dev)
+    o_i = torch.zeros((B, 2 * E), dtype=torch.int32, device=dev)
+    nvs, nes = [], []
+    for b in range(B):
+        s, p = sims[b], pairs[b].to(torch.int64).reshape(-1, 2)
+        nv, ne = int(s.shape[0]), int(p.shape[0])
+        if s.dtype != torch.float32 or tuple(s.shape) != (nv, 13) or tuple(fixed[b].shape) != (nv,):
+            raise ValueError("sims must be float32 [nv][13] and fixed [nv]")
+        nvs.append(nv), nes.append(ne)
+        o_s[b, :nv], o_f[b, :nv], o_e[b, :ne] = s, (fixed[b] != 0).to(torch.uint8), p.to(torch.int32)
+        m = 0 if meas[b] is None else int(meas[b].shape[0])
+        if m > ne or (m and tuple(meas[b].shape) != (m, 13)):
+            raise ValueError("meas must be float32 [m][13] with m <= ne")
+        if ne > m:
+            i, j = p[:ne - m, 0].clamp(0, max(nv - 1, 0)), p[:ne - m, 1].clamp(0, max(nv - 1, 0))
+            o_m[b, :ne - m] = relativeSim3(s[i], s[j]) if nv else 0.0
+        if m:
+            o_m[b, ne - m:ne] = meas[b].to(torch.float32)
+        if have_w and weight[b] is not None:
+            o_w[b, :ne] = weight[b].to(torch.float32)
+        # the index: the entries edge << 1 | side sorted by (vertex, entry)
+        ent = torch.arange(2 * ne, device=dev, dtype=torch.int64)
+        vert = p.reshape(-1).clamp(0, V)                     # (a vertex out of range is refused by the call anyway)
+        order = torch.argsort(vert * (2 * ne + 1) + ent, stable=True)
+        o_i[b, :2 * ne] = ent[order].to(torch.int32)
+        cnt = torch.bincount(vert[vert < nv], minlength=nv)[:nv] if nv else torch.zeros(0, dtype=torch.int64, device=dev)
+        o_p[b, 1:nv + 1] = torch.cumsum(cnt, 0).to(torch.int32)
+    cnts = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
+    return o_s, cnts(nvs), o_f, o_e, o_m, o_w, cnts(nes), o_p, o_i
+
+
+def reservePoseGraph(v_stride: int, e_stride: int, batch: int, *, ctx: Context | None = None):
+    """Size the context's workspace for poseGraphBatch calls of up to this shape (pislam_pose_graph_reserve): afterwards
+    such calls allocate nothing and never synchronise, so they can be captured into a hipGraph."""
+    ctx = ctx or default_context()
+    ctx.check(ctx.lib.pislam_pose_graph_reserve(ctx.h, int(v_stride), int(e_stride), int(batch)), "pislam_pose_graph_reserve")
+
+
+def poseGraphBatch(sims, v_counts, fixed, edges, meas, weight, e_counts, inc_ptr, inc, *, iters=20, cg_iters=256,
+                   cg_tol=1e-6, eps=1e-9, sims_out=None, cost=None, status=None, ctx: Context | None = None):
+    """Batched essential-graph optimisation (pislam_pose_graph_batch; the contract is the comment in include/
+    pislam_hip.h), ORB-SLAM's OptimizeEssentialGraph: per graph the free vertex similarities are moved so that the sum
+    of the squared relative-Sim(3) errors over the edges becomes minimal.  The arguments are essentialGraph's outputs
+    in order: sims float32 [batch][v_stride][13], v_counts, fixed uint8 [batch][v_stride], edges 32-bit integers
+    [batch][e_stride][2], meas float32 [batch][e_stride][13], weight float32 [batch][e_stride] or None, e_counts, inc_ptr
+    [batch][v_stride + 1], inc [batch][2 * e_stride].  One Levenberg round of up to `iters` iterations, each a
+    preconditioned conjugate-gradient solve of up to cg_iters iterations that stops at a relative residual of cg_tol.
+    Returns (sims_out, cost float64 [batch], status int32 [batch] = code | evaluations << 8; code 0 ok, 1 nothing to do,
+    2 a bad value or an inadmissible input state, 3 the graph is malformed).  sims_out may be `sims`.  The same inputs
+    give the same outputs, bit for bit.  Asynchronous on the ctx stream; capturable after reservePoseGraph.  Key-frame
+    poses afterwards: rigidFromSim3(sims_out[b])."""
+    import torch
+    ctx = ctx or default_context()
+    if sims.dtype != torch.float32 or sims.dim() != 3 or int(sims.shape[2]) != 13:
+        raise ValueError("sims must be a float32 tensor [batch][v_stride][13]")
+    batch, V = int(sims.shape[0]), int(sims.shape[1])
+    words = (torch.int32, getattr(torch, "uint32", torch.int32))
+    if edges.dtype not in words or edges.dim() != 3 or int(edges.shape[0]) != batch or int(edges.shape[2]) != 2:
+        raise ValueError("edges must be a 32-bit integer tensor [batch][e_stride][2]")
+    E = int(edges.shape[1])
+    if V > POSE_GRAPH_MAX_VERTICES or E > POSE_GRAPH_MAX_EDGES:
+        raise ValueError(f"at most {POSE_GRAPH_MAX_VERTICES} vertices and {POSE_GRAPH_MAX_EDGES} edges per graph")
+    if fixed.dtype != torch.uint8 or tuple(fixed.shape) != (batch, V):
+        raise ValueError("fixed must be a uint8 tensor [batch][v_stride]")
+    if meas.dtype != torch.float32 or tuple(meas.shape) != (batch, E, 13):
+        raise ValueError("meas must be a float32 tensor [batch][e_stride][13]")
+    if weight is not None and (weight.dtype != torch.float32 or tuple(weight.shape) != (batch, E)):
+        raise ValueError("weight must be a float32 tensor [batch][e_stride]")
+    for t, shape in ((v_counts, (batch,)), (e_counts, (batch,)), (inc_ptr, (batch, V + 1)), (inc, (batch, 2 * E))):
+        if t.dtype not in words or tuple(t.shape) != shape:
+            raise ValueError("v_counts, e_counts [batch], inc_ptr [batch][v_stride + 1] and inc [batch][2 * e_stride] must "
+                             "be 32-bit integer tensors")
+    for t in (sims, v_counts, fixed, edges, meas, e_counts, inc_ptr, inc) + (() if weight is None else (weight,)):
+        if not t.is_contiguous():
+            raise ValueError("inputs must be contiguous")
+    p = capi.PoseGraphParams(int(iters), int(cg_iters), float(cg_tol), float(eps))
+    dev = sims.device
+    sims_out = torch.empty_like(sims) if sims_out is None else sims_out
+    cost = torch.empty((batch,), dtype=torch.float64, device=dev) if cost is None else cost
+    status = torch.empty((batch,), dtype=torch.int32, device=dev) if status is None else status
+    ctx.check(ctx.lib.pislam_pose_graph_batch(ctx.h, ctypes.byref(p), ptr(sims), ptr(v_counts), ptr(fixed), ptr(edges),
+                                              ptr(meas), ptr(weight), ptr(e_counts), ptr(inc_ptr), ptr(inc), V, E, batch,
+                                              ptr(sims_out), ptr(cost), ptr(status)), "pislam_pose_graph_batch")
+    return sims_out, cost, status
+
+
+def correctMapPointsBatch(xw, ref, pt_counts, sims_old, sims_new, v_counts, *, xw_out=None, status=None,
+                          ctx: Context | None = None):
+    """Map points moved with their reference key frames after a loop correction (pislam_map_points_correct_batch, the end
+    of LoopClosing::CorrectLoop): point p becomes S_new[ref[p]]^-1(S_old[ref[p]](X_p)), computed in binary64.  xw float32
+    [batch][pt_stride][3], ref int16 or uint16 [batch][pt_stride] (the uint16 words of the call), pt_counts [batch],
+    sims_old and sims_new float32 [batch][v_stride][13] (poseGraphBatch's input and output), v_counts [batch].  Returns
+    (xw_out, status uint8 [batch][pt_stride]: 1 where ref is out of range or the result is not finite; such a point
+    stays as it was).  xw_out may be `xw`.  Asynchronous on the ctx stream, no workspace: capturable as it is."""
+    import torch
+    ctx = ctx or default_context()
+    if xw.dtype != torch.float32 or xw.dim() != 3 or int(xw.shape[2]) != 3:
+        raise ValueError("xw must be a float32 tensor [batch][pt_stride][3]")
+    batch, pts = int(xw.shape[0]), int(xw.shape[1])
+    if ref.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) or tuple(ref.shape) != (batch, pts):
+        raise ValueError("ref must be a 16-bit integer tensor [batch][pt_stride]")
+    if sims_old.dtype != torch.float32 or sims_old.dim() != 3 or int(sims_old.shape[0]) != batch or int(sims_old.shape[2]) != 13:
+        raise ValueError("sims_old must be a float32 tensor [batch][v_stride][13]")
+    if sims_new.dtype != torch.float32 or tuple(sims_new.shape) != tuple(sims_old.shape):
+        raise ValueError("sims_new must be a float32 tensor of sims_old's shape")
+    words = (torch.int32, getattr(torch, "uint32", torch.int32))
+    for t in (pt_counts, v_counts):
+        if t.dtype not in words or tuple(t.shape) != (batch,):
+            raise ValueError("pt_counts and v_counts must be 32-bit integer tensors [batch]")
+    for t in (xw, ref, pt_counts, sims_old, sims_new, v_counts):
+        if not t.is_contiguous():
+            raise ValueError("inputs must be contiguous")
+    xw_out = torch.empty_like(xw) if xw_out is None else xw_out
+    status = torch.empty((batch, pts), dtype=torch.uint8, device=xw.device) if status is None else status
+    ctx.check(ctx.lib.pislam_map_points_correct_batch(ctx.h, ptr(xw), ptr(ref), ptr(pt_counts), ptr(sims_old),
+                                                      ptr(sims_new), ptr(v_counts), pts, int(sims_old.shape[1]), batch,
+                                                      ptr(xw_out), ptr(status)), "pislam_map_points_correct_batch")
+    return xw_out, status
+
+
 # ---- bag of words: integer weights and the key-frame database ----------
 BOW_MAX_STRIDE = 16384      # entries of a bag-of-words vector (pislam_bow_vector_batch)
 

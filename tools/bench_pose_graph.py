@@ -1,0 +1,170 @@
+"""Batched essential-graph optimisation (pislam_pose_graph_batch) on synthetic loops, next to a device copy of its input
+bytes; prints one JSON line.
+
+Setup: a key-frame trajectory on a ring, world to camera, its odometry drifted (every relative motion off by about 0.003
+rad, 0.015 units and 0.3 % of scale), vertex 0 held; a chain edge between consecutive key frames and covisibility edges
+to key frames a few places on, all measured from the drifted similarities as ORB-SLAM takes them from the uncorrected
+poses; one loop edge from the last key frame to the first, measured from the truth, which the drift contradicts.  Two
+shapes: `graphs` graphs of `vertices` vertices and about `edges` edges in one call, and ONE graph of `big_vertices`
+vertices and about `big_edges` edges, which one workgroup, that is one compute unit, runs alone.  Timed, each as the
+median device-event time of single calls after a warm-up (the workspace is reserved first): the call with ORB-SLAM's 20
+Levenberg iterations at the most, and a device-to-device copy of its input bytes.  `evaluations` is the mean number of
+evaluations of F (status >> 8); `cg_per_solve` the mean conjugate-gradient iterations of a solve, taken from the host
+probe (tools/probes/graph_host_check.cpp: the same arithmetic, word for word) on the same graphs, null without a host
+compiler; map-point correction of `points` points per graph is timed beside the small shape."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tools")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from bench_local_ba import rotations  # noqa: E402
+from bench_sim3 import timed  # noqa: E402
+
+
+def sims_of(R, t, s):
+    return np.concatenate([R.reshape(len(R), 9), t, s[:, None]], 1)
+
+
+def mul(A, B):
+    Ra, Rb = A[:, :9].reshape(-1, 3, 3), B[:, :9].reshape(-1, 3, 3)
+    t = A[:, 12:13] * np.einsum("nij,nj->ni", Ra, B[:, 9:12]) + A[:, 9:12]
+    return sims_of(Ra @ Rb, t, A[:, 12] * B[:, 12])
+
+
+def inv(A):
+    Rt = A[:, :9].reshape(-1, 3, 3).transpose(0, 2, 1)
+    return sims_of(Rt, -np.einsum("nij,nj->ni", Rt, A[:, 9:12]) / A[:, 12:13], 1.0 / A[:, 12])
+
+
+def loop_graph(rng, nv, ne):
+    """(sims float32 [nv][13], fixed, pairs [ne'][2], loop measurement [1][13])."""
+    a = 2 * np.pi * np.arange(nv) / nv
+    R = rotations(np.stack([np.zeros(nv), a, np.zeros(nv)], 1)) @ rotations(rng.normal(0, 0.05, (nv, 3)))
+    c = np.stack([4 * np.cos(a), rng.normal(0, 0.1, nv), 4 * np.sin(a)], 1)
+    s = np.exp(rng.normal(0, 0.05, nv))
+    truth = sims_of(R, -s[:, None] * np.einsum("nij,nj->ni", R, c), s)
+    step = mul(truth[1:], inv(truth[:-1]))
+    noise = sims_of(rotations(rng.normal(0, 0.003 / np.sqrt(3), (nv - 1, 3))), rng.normal(0, 0.015 / np.sqrt(3), (nv - 1, 3)),
+                    np.exp(rng.normal(0, 0.003, nv - 1)))
+    step = mul(noise, step)
+    est = [truth[:1]]
+    for k in range(nv - 1):
+        est.append(mul(step[k:k + 1], est[-1]))
+    est = np.concatenate(est).astype(np.float32)
+    pairs = {(k, k + 1) for k in range(nv - 1)}
+    while len(pairs) < ne - 1:
+        i = int(rng.integers(0, nv - 2))
+        pairs.add((i, int(min(i + rng.integers(2, 8), nv - 1))))
+    pairs = sorted(pairs) + [(nv - 1, 0)]
+    fixed = np.zeros(nv, np.uint8)
+    fixed[0] = 1
+    return est, fixed, np.array(pairs, np.int32), mul(truth[:1], inv(truth[nv - 1:])).astype(np.float32)
+
+
+def probe_cg(G, prm):
+    """The mean conjugate-gradient iterations per solve over the graphs of essentialGraph's arrays G, from the host probe."""
+    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
+    if cxx is None:
+        return None
+    hexf = lambda a: " ".join("%08x" % v for v in np.asarray(a, np.float32).reshape(-1).view(np.uint32))
+    hexd = lambda v: "%016x" % int(np.array(v, np.float64).view(np.uint64))
+    sims, vc, fixed, edges, meas, _, ec, ptr, inc = [None if x is None else x.cpu().numpy() for x in G]
+    lines = []
+    for b in range(len(sims)):
+        nv, ne = int(vc[b]), int(ec[b])
+        parts = ["G %d %d %s %s 0 %d %d" % (prm[0], prm[1], hexd(prm[2]), hexd(prm[3]), nv, ne)]
+        parts += ["%d %s" % (fixed[b, k], hexf(sims[b, k])) for k in range(nv)]
+        parts += ["%d %d %s %s" % (edges[b, e, 0], edges[b, e, 1], hexf(meas[b, e]), hexf([1.0])) for e in range(ne)]
+        parts += [" ".join(str(int(v)) for v in ptr[b, :nv + 1]), " ".join(str(int(v)) for v in inc[b, :2 * ne])]
+        lines.append(" ".join(parts))
+    tmp = tempfile.mkdtemp(prefix="bench_pose_graph_")
+    try:
+        exe, cases = os.path.join(tmp, "graph_host_check"), os.path.join(tmp, "cases.txt")
+        subprocess.check_call([cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-I", os.path.join(ROOT, "pislam_amd", "csrc"),
+                               os.path.join(ROOT, "tools", "probes", "graph_host_check.cpp"), "-o", exe])
+        with open(cases, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        out = subprocess.run([exe, cases], check=True, capture_output=True, text=True).stdout.splitlines()
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    cg, solves = sum(int(ln.split()[2]) for ln in out), sum(int(ln.split()[3]) for ln in out)
+    return round(cg / max(solves, 1), 2)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--graphs", type=int, default=256)
+    ap.add_argument("--vertices", type=int, default=64)
+    ap.add_argument("--edges", type=int, default=300)
+    ap.add_argument("--big-vertices", type=int, default=2048)
+    ap.add_argument("--big-edges", type=int, default=10000)
+    ap.add_argument("--points", type=int, default=4096, help="map points per graph moved by the correction call")
+    ap.add_argument("--lm-iters", type=int, default=20)
+    ap.add_argument("--cg-iters", type=int, default=256)
+    ap.add_argument("--cg-tol", type=float, default=1e-4)
+    ap.add_argument("--eps", type=float, default=1e-6)
+    ap.add_argument("--iters", type=int, default=10, help="timed calls per entry point")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_pose_graph needs a GPU (there is no CPU fallback)")
+    from pislam_amd.capi import Context
+    from pislam_amd.frontend import correctMapPointsBatch, essentialGraph, poseGraphBatch, reservePoseGraph
+    rng = np.random.default_rng(args.seed)
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.Stream(dev)
+    ctx = Context(device=0, stream=stream.cuda_stream)
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    prm = (args.lm_iters, args.cg_iters, args.cg_tol, args.eps)
+    kw = dict(iters=prm[0], cg_iters=prm[1], cg_tol=prm[2], eps=prm[3])
+    res = {}
+    with torch.cuda.stream(stream):
+        for tag, B, nv, ne in (("batch", args.graphs, args.vertices, args.edges), ("big", 1, args.big_vertices, args.big_edges)):
+            gs = [loop_graph(rng, nv, ne) for _ in range(B)]
+            G = essentialGraph([T(g[0]) for g in gs], [T(g[1]) for g in gs], [T(g[2]) for g in gs], [T(g[3]) for g in gs])
+            reservePoseGraph(int(G[0].shape[1]), int(G[3].shape[1]), B, ctx=ctx)
+            keep = dict(zip(("sims_out", "cost", "status"), poseGraphBatch(*G, ctx=ctx, **kw)))
+            ms = timed(lambda: poseGraphBatch(*G, ctx=ctx, **kw, **keep), stream, torch, args.warmup, args.iters)
+            ins = [x for x in G if x is not None]
+            dst = [torch.empty_like(a) for a in ins]
+
+            def copy():
+                for d, s in zip(dst, ins):
+                    d.copy_(s)
+            copy_ms = timed(copy, stream, torch, args.warmup, args.iters)
+            stream.synchronize()
+            status, cost = keep["status"].cpu().numpy(), keep["cost"].cpu().numpy()
+            r = {"graphs": B, "vertices": nv, "mean_edges": round(float(G[6].float().mean()), 1), "pose_graph_ms": round(ms, 4),
+                 "copy_inputs_ms": round(copy_ms, 4), "input_bytes": int(sum(a.numel() * a.element_size() for a in ins)),
+                 "codes_ok": int((status & 255 == 0).sum()), "evaluations": round(float((status >> 8).mean()), 2),
+                 "cg_per_solve": probe_cg(G, prm), "mean_cost": float(cost.mean())}
+            if tag == "batch":
+                P = args.points
+                xw = T(rng.uniform(-6, 6, (B, P, 3)).astype(np.float32))
+                ref = T(rng.integers(0, nv, (B, P)).astype(np.int16))
+                cnt = T(np.full(B, P, np.int32))
+                pk = dict(zip(("xw_out", "status"), correctMapPointsBatch(xw, ref, cnt, G[0], keep["sims_out"], G[1], ctx=ctx)))
+                r["correct_points_ms"] = round(timed(lambda: correctMapPointsBatch(xw, ref, cnt, G[0], keep["sims_out"], G[1], ctx=ctx,
+                                                                                   **pk), stream, torch, args.warmup, args.iters), 4)
+                r["points"] = B * P
+            res[tag] = r
+        stream.synchronize()
+    print(json.dumps({"tool": "bench_pose_graph", "iters": args.iters, "params": kw, "results": res}))
+
+
+if __name__ == "__main__":
+    main()
