@@ -7,12 +7,17 @@ arguments, `vstep` is taken from the array's row stride.  Every function forward
 to the C ABI of libpislam_hip.so — nothing is computed in Python and nothing
 falls back to the CPU.
 
+The batched matchers and the back-end calls behind them (match selection, two-view geometry, pose and Sim(3) estimation,
+new map points, local bundle adjustment, the pose graph, bag of words) live here too; they have no counterpart in the
+reference, and their contracts are the comments in include/pislam_hip.h.
+
 Arrays may be numpy (host; staged through the device by the library) or torch
 CUDA/HIP tensors (used in place).
 """
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import numpy as np
 
@@ -190,6 +195,14 @@ def matchHamming(query, train, *, ctx: Context | None = None):
     return idx, dist, dist2
 
 
+def _match_outputs(qdesc, idx, dist, dist2):
+    """The (idx, dist, dist2) of a batched matcher: each the caller's tensor, or a new int32 one [batch][q_stride] on the
+    device of the query descriptors [batch][q_stride][words]."""
+    import torch
+    new = lambda t: torch.empty(tuple(qdesc.shape[:2]), dtype=torch.int32, device=qdesc.device) if t is None else t
+    return new(idx), new(dist), new(dist2)
+
+
 def matchHammingBatch(qdesc, qcounts, tdesc, tcounts, idx=None, dist=None, dist2=None, *, ctx: Context | None = None):
     """Batched matcher on device-resident front-end outputs (torch tensors [batch][max_kp][words] and
     [batch] counts, as OrbFrontend writes them): pair b matches the first min(qcounts[b], q_stride) descriptors of
@@ -197,16 +210,10 @@ def matchHammingBatch(qdesc, qcounts, tdesc, tcounts, idx=None, dist=None, dist2
     int32 tensors [batch][q_stride]: idx as matchHamming; dist and dist2 hold the library's uint32 values viewed as
     int32, so "none" (0xffffffff: no train descriptor, or for dist2 fewer than two) reads as -1.  Entries at and beyond
     a pair's query count are not written.  Asynchronous on the ctx stream."""
-    import torch
     ctx = ctx or default_context()
     batch, qs, words = qdesc.shape
     ts = tdesc.shape[1]
-    if idx is None:
-        idx = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
-    if dist is None:
-        dist = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
-    if dist2 is None:
-        dist2 = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
+    idx, dist, dist2 = _match_outputs(qdesc, idx, dist, dist2)
     ctx.check(ctx.lib.pislam_match_hamming_batch(ctx.h, words, ptr(qdesc), ptr(qcounts), qs, ptr(tdesc), ptr(tcounts), ts,
                                                  batch, ptr(idx), ptr(dist), ptr(dist2)), "pislam_match_hamming_batch")
     return idx, dist, dist2
@@ -237,19 +244,13 @@ def matchHammingWindowBatch(qkp, qdesc, qcounts, tkp, tdesc, tcounts, levels, ra
     only the train keypoints on its own level within `radius` (int, or one per level) in x and in y.  `levels` is
     [(w, h, row0[, col0])].  Returns (idx, dist, dist2) int32 tensors [batch][max_kp] like matchHammingBatch
     (pislam_match_hamming_window_batch); asynchronous on the ctx stream."""
-    import torch
     ctx = ctx or default_context()
     batch, qs, words = qdesc.shape
     ts = tdesc.shape[1]
     if tdesc.shape[2] != words:
         raise ValueError("query and train descriptors differ in words")
     lv, n, r = _window_tables(levels, radius)
-    if idx is None:
-        idx = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
-    if dist is None:
-        dist = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
-    if dist2 is None:
-        dist2 = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
+    idx, dist, dist2 = _match_outputs(qdesc, idx, dist, dist2)
     ctx.check(ctx.lib.pislam_match_hamming_window_batch(ctx.h, words, lv, n, r, ptr(qkp), ptr(qdesc), ptr(qcounts), qs,
                                                         ptr(tkp), ptr(tdesc), ptr(tcounts), ts, batch, ptr(idx), ptr(dist),
                                                         ptr(dist2)), "pislam_match_hamming_window_batch")
@@ -301,12 +302,7 @@ def matchHammingScaledWindowBatch(qkp, qdesc, qcounts, tkp, tdesc, tcounts, leve
     if qpred is not None and (qpred.dtype != torch.int32 or tuple(qpred.shape) != (batch, qs, 2)):
         raise ValueError("qpred must be an int32 tensor [batch][q_stride][2]")
     lv, n, s, r = _scaled_tables(levels, scale_q16, radius0)
-    if idx is None:
-        idx = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
-    if dist is None:
-        dist = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
-    if dist2 is None:
-        dist2 = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
+    idx, dist, dist2 = _match_outputs(qdesc, idx, dist, dist2)
     ctx.check(ctx.lib.pislam_match_hamming_scaled_window_batch(ctx.h, words, lv, n, s, r, int(level_span), ptr(qkp),
                                                                ptr(qdesc), ptr(qcounts), ptr(qpred), qs, ptr(tkp),
                                                                ptr(tdesc), ptr(tcounts), ts, batch, ptr(idx), ptr(dist),
@@ -862,7 +858,6 @@ def matchHammingBowBatch(qdesc, qgroup, qcounts, tdesc, tgroup, tcounts, ngroups
     bowTransformBatch wrote for them ([batch][max_kp]): query i of pair b sees the train descriptors of the same
     group; ids at or above ngroups match nothing.  Returns (idx, dist, dist2) int32 tensors [batch][q_stride] like
     matchHammingBatch; asynchronous on the ctx stream."""
-    import torch
     ctx = ctx or default_context()
     batch, qs, words = qdesc.shape
     ts = tdesc.shape[1]
@@ -870,16 +865,91 @@ def matchHammingBowBatch(qdesc, qgroup, qcounts, tdesc, tgroup, tcounts, ngroups
         raise ValueError("query and train descriptors differ in words")
     if tuple(qgroup.shape) != (batch, qs) or tuple(tgroup.shape) != (tdesc.shape[0], ts):
         raise ValueError("qgroup / tgroup must be [batch][stride] like the descriptors")
-    if idx is None:
-        idx = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
-    if dist is None:
-        dist = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
-    if dist2 is None:
-        dist2 = torch.empty((batch, qs), dtype=torch.int32, device=qdesc.device)
+    idx, dist, dist2 = _match_outputs(qdesc, idx, dist, dist2)
     ctx.check(ctx.lib.pislam_match_hamming_bow_batch(ctx.h, words, int(ngroups), ptr(qdesc), ptr(qgroup), ptr(qcounts),
                                                      qs, ptr(tdesc), ptr(tgroup), ptr(tcounts), ts, batch, ptr(idx),
                                                      ptr(dist), ptr(dist2)), "pislam_match_hamming_bow_batch")
     return idx, dist, dist2
+
+
+# ---- what the batched wrappers below share: tensor checks and host tables, each rule stated once ----------
+@functools.cache
+def _word32():
+    """The dtypes that count as a 32-bit word: int32, and uint32 where this torch has it."""
+    import torch
+    return (torch.int32, getattr(torch, "uint32", torch.int32))
+
+
+@functools.cache
+def _word16():
+    """The dtypes that count as a 16-bit word: int16, and uint16 where this torch has it."""
+    import torch
+    return (torch.int16, getattr(torch, "uint16", torch.int16))
+
+
+def _tensor(t, dtype, shape, message):
+    """Refuses, with the caller's message, a tensor that has not the dtype (one, or a tuple such as _word32(); None: any) or
+    not the shape.  An extent given as None is free: the free extents are returned, in order."""
+    if t.dtype != dtype and dtype is not None and not (type(dtype) is tuple and t.dtype in dtype):
+        raise ValueError(message)
+    have, free = t.shape, ()
+    if have != shape:
+        if len(have) != len(shape):
+            raise ValueError(message)
+        for h, w in zip(have, shape):
+            if w is None:
+                free += (h,)
+            elif h != w:
+                raise ValueError(message)
+    return free
+
+
+def _counts(message, batch, *counts):
+    """Counts tensors: 32-bit words, one per batch entry."""
+    words, shape = _word32(), (batch,)
+    for t in counts:
+        if t.dtype not in words or t.shape != shape:
+            raise ValueError(message)
+
+
+def _float_table(values, message, entries=None):
+    """A HOST sequence of float32 as the C array the library reads: (array, length).  The library takes 1..16 entries;
+    `entries` given: exactly that many (the second of two tables that go together)."""
+    host = np.asarray(values, dtype=np.float32).ravel()        # (contiguous: ravel copies where it has to)
+    n = host.size
+    if not 1 <= n <= 16 or (entries is not None and n != entries):
+        raise ValueError(message)
+    return (ctypes.c_float * n).from_buffer_copy(host), n
+
+
+def _level_table(levels, inv_sigma2, batch, stride, together, shaped):
+    """The level arguments of the pose, Sim(3) and bundle-adjustment calls: the tensors `levels` (level, or level1 and
+    level2) and the host table inv_sigma2 are given together or not at all (else ValueError(together)); each level tensor
+    is uint8 [batch][stride] (else ValueError(shaped)).  Returns _float_table's (tab, ntab), (None, 0) without levels."""
+    for level in levels:
+        if (level is None) != (inv_sigma2 is None):
+            raise ValueError(together)
+    if inv_sigma2 is None:
+        return None, 0
+    import torch
+    for level in levels:
+        _tensor(level, torch.uint8, (batch, stride), shaped)
+    return _float_table(inv_sigma2, "inv_sigma2 must have 1..16 entries")
+
+
+def _contiguous(*tensors, message="inputs must be contiguous"):
+    """Every input given (None: an optional one that is absent) is contiguous."""
+    for t in tensors:
+        if t is not None and not t.is_contiguous():
+            raise ValueError(message)
+
+
+def _on_device(a):
+    """A numpy input as a tensor on the current device; anything else as it is."""
+    if isinstance(a, np.ndarray):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
+    return a
 
 
 # ---- after the match: angle bins and match selection ---------------------
@@ -1024,11 +1094,8 @@ def twoViewRansacBatch(p1_q8, p2_q8, counts, *, model, hypotheses=200, seed=0, s
     ctx = ctx or default_context()
     if model not in _TWO_VIEW_MODELS:
         raise ValueError('model must be 0 / "F" or 1 / "H"')
-    if p1_q8.dtype != torch.int32 or p1_q8.dim() != 3 or int(p1_q8.shape[2]) != 2:
-        raise ValueError("p1_q8 must be an int32 tensor [batch][stride][2]")
-    if p2_q8.dtype != torch.int32 or tuple(p2_q8.shape) != tuple(p1_q8.shape):
-        raise ValueError("p2_q8 must be an int32 tensor of p1_q8's shape")
-    batch, stride = int(p1_q8.shape[0]), int(p1_q8.shape[1])
+    batch, stride = _tensor(p1_q8, torch.int32, (None, None, 2), "p1_q8 must be an int32 tensor [batch][stride][2]")
+    _tensor(p2_q8, torch.int32, (batch, stride, 2), "p2_q8 must be an int32 tensor of p1_q8's shape")
     if stride > TWO_VIEW_MAX_STRIDE:
         raise ValueError(f"at most {TWO_VIEW_MAX_STRIDE} matches per pair")
     dev = p1_q8.device
@@ -1141,27 +1208,18 @@ def twoViewReconstructBatch(p1_q8, p2_q8, counts, cam, cand, *, mask=None, sigma
     beyond counts[b] are not written)).  The same inputs give the same outputs, bit for bit.  Asynchronous on the ctx
     stream, no workspace: capturable as it is."""
     import torch
-    if p1_q8.dtype != torch.int32 or p1_q8.dim() != 3 or int(p1_q8.shape[2]) != 2:
-        raise ValueError("p1_q8 must be an int32 tensor [batch][stride][2]")
-    if p2_q8.dtype != torch.int32 or tuple(p2_q8.shape) != tuple(p1_q8.shape):
-        raise ValueError("p2_q8 must be an int32 tensor of p1_q8's shape")
-    batch, stride = int(p1_q8.shape[0]), int(p1_q8.shape[1])
+    batch, stride = _tensor(p1_q8, torch.int32, (None, None, 2), "p1_q8 must be an int32 tensor [batch][stride][2]")
+    _tensor(p2_q8, torch.int32, (batch, stride, 2), "p2_q8 must be an int32 tensor of p1_q8's shape")
     if stride > RECONSTRUCT_MAX_STRIDE:
         raise ValueError(f"at most {RECONSTRUCT_MAX_STRIDE} matches per pair")
-    if counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(counts.shape) != (batch,):
-        raise ValueError("counts must be a 32-bit integer tensor [batch]")
-    if cam.dtype != torch.float32 or tuple(cam.shape) != (batch, 4):
-        raise ValueError("cam must be a float32 tensor [batch][4]")
-    if cand.dtype != torch.float32 or cand.dim() != 3 or int(cand.shape[0]) != batch or int(cand.shape[2]) != 12:
-        raise ValueError("cand must be a float32 tensor [batch][ncand][12]")
-    ncand = int(cand.shape[1])
+    _counts("counts must be a 32-bit integer tensor [batch]", batch, counts)
+    _tensor(cam, torch.float32, (batch, 4), "cam must be a float32 tensor [batch][4]")
+    ncand, = _tensor(cand, torch.float32, (batch, None, 12), "cand must be a float32 tensor [batch][ncand][12]")
     if not 1 <= ncand <= 8:
         raise ValueError("cand must hold 1..8 candidates per pair")
-    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (batch, stride)):
-        raise ValueError("mask must be a uint8 tensor [batch][stride]")
-    for t in (p1_q8, p2_q8, counts, cam, cand) + (() if mask is None else (mask,)):
-        if not t.is_contiguous():
-            raise ValueError("inputs must be contiguous")
+    if mask is not None:
+        _tensor(mask, torch.uint8, (batch, stride), "mask must be a uint8 tensor [batch][stride]")
+    _contiguous(p1_q8, p2_q8, counts, cam, cand, mask)
     cos_parallax = np.float32(np.cos(np.radians(min_parallax_deg)))
     cos_point = np.float32(cos_point)
     if not 1 <= int(sigma_q8) <= 4096:
@@ -1299,34 +1357,16 @@ def poseRefineBatch(pose, cam, xw, obs_q8, counts, *, level=None, inv_sigma2=Non
     The same inputs give the same outputs, bit for bit.  Asynchronous on the ctx stream, no workspace: capturable."""
     import torch
     ctx = ctx or default_context()
-    if pose.dtype != torch.float32 or pose.dim() != 2 or int(pose.shape[1]) != 12:
-        raise ValueError("pose must be a float32 tensor [batch][12]")
-    batch = int(pose.shape[0])
-    if cam.dtype != torch.float32 or tuple(cam.shape) != (batch, 5):
-        raise ValueError("cam must be a float32 tensor [batch][5]")
-    if xw.dtype != torch.float32 or xw.dim() != 3 or int(xw.shape[0]) != batch or int(xw.shape[2]) != 3:
-        raise ValueError("xw must be a float32 tensor [batch][stride][3]")
-    stride = int(xw.shape[1])
-    if obs_q8.dtype != torch.int32 or tuple(obs_q8.shape) != (batch, stride, 3):
-        raise ValueError("obs_q8 must be an int32 tensor [batch][stride][3]")
+    batch, = _tensor(pose, torch.float32, (None, 12), "pose must be a float32 tensor [batch][12]")
+    _tensor(cam, torch.float32, (batch, 5), "cam must be a float32 tensor [batch][5]")
+    stride, = _tensor(xw, torch.float32, (batch, None, 3), "xw must be a float32 tensor [batch][stride][3]")
+    _tensor(obs_q8, torch.int32, (batch, stride, 3), "obs_q8 must be an int32 tensor [batch][stride][3]")
     if stride > POSE_MAX_STRIDE:
         raise ValueError(f"at most {POSE_MAX_STRIDE} observations per frame")
-    if counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(counts.shape) != (batch,):
-        raise ValueError("counts must be a 32-bit integer tensor [batch]")
-    if (level is None) != (inv_sigma2 is None):
-        raise ValueError("level and inv_sigma2 go together")
-    tab, ntab = None, 0
-    if level is not None:
-        if level.dtype != torch.uint8 or tuple(level.shape) != (batch, stride):
-            raise ValueError("level must be a uint8 tensor [batch][stride]")
-        host = np.ascontiguousarray(np.asarray(inv_sigma2, dtype=np.float32).reshape(-1))
-        ntab = int(host.size)
-        if not 1 <= ntab <= 16:
-            raise ValueError("inv_sigma2 must have 1..16 entries")
-        tab = (ctypes.c_float * ntab)(*host.tolist())
-    for t in (pose, cam, xw, obs_q8, counts) + (() if level is None else (level,)):
-        if not t.is_contiguous():
-            raise ValueError("inputs must be contiguous")
+    _counts("counts must be a 32-bit integer tensor [batch]", batch, counts)
+    tab, ntab = _level_table((level,), inv_sigma2, batch, stride, "level and inv_sigma2 go together",
+                             "level must be a uint8 tensor [batch][stride]")
+    _contiguous(pose, cam, xw, obs_q8, counts, level)
     dev = pose.device
     p = capi.PoseParams(int(rounds), int(iters), int(huber_rounds), int(min_obs), float(eps))
     pose_out = torch.empty((batch, 12), dtype=torch.float32, device=dev) if pose_out is None else pose_out
@@ -1356,34 +1396,16 @@ def pnpRansacBatch(cam, xw, obs_q8, counts, *, level=None, inv_sigma2=None, hypo
     and seed give the same outputs, bit for bit.  Asynchronous on the ctx stream, no workspace: capturable."""
     import torch
     ctx = ctx or default_context()
-    as_t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda") if isinstance(a, np.ndarray) else a
-    cam, xw, obs_q8, counts, level = as_t(cam), as_t(xw), as_t(obs_q8), as_t(counts), as_t(level)
-    if cam.dtype != torch.float32 or cam.dim() != 2 or int(cam.shape[1]) != 5:
-        raise ValueError("cam must be a float32 tensor [batch][5]")
-    batch = int(cam.shape[0])
-    if xw.dtype != torch.float32 or xw.dim() != 3 or int(xw.shape[0]) != batch or int(xw.shape[2]) != 3:
-        raise ValueError("xw must be a float32 tensor [batch][stride][3]")
-    stride = int(xw.shape[1])
-    if obs_q8.dtype != torch.int32 or tuple(obs_q8.shape) != (batch, stride, 3):
-        raise ValueError("obs_q8 must be an int32 tensor [batch][stride][3]")
+    cam, xw, obs_q8, counts, level = map(_on_device, (cam, xw, obs_q8, counts, level))
+    batch, = _tensor(cam, torch.float32, (None, 5), "cam must be a float32 tensor [batch][5]")
+    stride, = _tensor(xw, torch.float32, (batch, None, 3), "xw must be a float32 tensor [batch][stride][3]")
+    _tensor(obs_q8, torch.int32, (batch, stride, 3), "obs_q8 must be an int32 tensor [batch][stride][3]")
     if stride > POSE_MAX_STRIDE:
         raise ValueError(f"at most {POSE_MAX_STRIDE} observations per frame")
-    if counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(counts.shape) != (batch,):
-        raise ValueError("counts must be a 32-bit integer tensor [batch]")
-    if (level is None) != (inv_sigma2 is None):
-        raise ValueError("level and inv_sigma2 go together")
-    tab, ntab = None, 0
-    if level is not None:
-        if level.dtype != torch.uint8 or tuple(level.shape) != (batch, stride):
-            raise ValueError("level must be a uint8 tensor [batch][stride]")
-        host = np.ascontiguousarray(np.asarray(inv_sigma2, dtype=np.float32).reshape(-1))
-        ntab = int(host.size)
-        if not 1 <= ntab <= 16:
-            raise ValueError("inv_sigma2 must have 1..16 entries")
-        tab = (ctypes.c_float * ntab)(*host.tolist())
-    for t in (cam, xw, obs_q8, counts) + (() if level is None else (level,)):
-        if not t.is_contiguous():
-            raise ValueError("inputs must be contiguous")
+    _counts("counts must be a 32-bit integer tensor [batch]", batch, counts)
+    tab, ntab = _level_table((level,), inv_sigma2, batch, stride, "level and inv_sigma2 go together",
+                             "level must be a uint8 tensor [batch][stride]")
+    _contiguous(cam, xw, obs_q8, counts, level)
     dev = cam.device
     p = capi.PnpParams(int(hypotheses), int(seed) & 0xFFFFFFFF, int(min_inliers))
     word = lambda t: torch.empty((batch,), dtype=torch.int32, device=dev) if t is None else t
@@ -1422,41 +1444,20 @@ def sim3RansacBatch(cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts, *, level1=None
     workspace: capturable."""
     import torch
     ctx = ctx or default_context()
-    as_t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda") if isinstance(a, np.ndarray) else a
-    cam1, cam2, x1, x2, obs1_q8, obs2_q8 = as_t(cam1), as_t(cam2), as_t(x1), as_t(x2), as_t(obs1_q8), as_t(obs2_q8)
-    counts, level1, level2 = as_t(counts), as_t(level1), as_t(level2)
-    if cam1.dtype != torch.float32 or cam1.dim() != 2 or int(cam1.shape[1]) != 5:
-        raise ValueError("cam1 must be a float32 tensor [batch][5]")
-    batch = int(cam1.shape[0])
-    if cam2.dtype != torch.float32 or tuple(cam2.shape) != (batch, 5):
-        raise ValueError("cam2 must be a float32 tensor [batch][5]")
-    if x1.dtype != torch.float32 or x1.dim() != 3 or int(x1.shape[0]) != batch or int(x1.shape[2]) != 3:
-        raise ValueError("x1 must be a float32 tensor [batch][stride][3]")
-    stride = int(x1.shape[1])
-    if x2.dtype != torch.float32 or tuple(x2.shape) != (batch, stride, 3):
-        raise ValueError("x2 must be a float32 tensor of x1's shape")
+    cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts, level1, level2 = map(
+        _on_device, (cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts, level1, level2))
+    batch, = _tensor(cam1, torch.float32, (None, 5), "cam1 must be a float32 tensor [batch][5]")
+    _tensor(cam2, torch.float32, (batch, 5), "cam2 must be a float32 tensor [batch][5]")
+    stride, = _tensor(x1, torch.float32, (batch, None, 3), "x1 must be a float32 tensor [batch][stride][3]")
+    _tensor(x2, torch.float32, (batch, stride, 3), "x2 must be a float32 tensor of x1's shape")
     for o in (obs1_q8, obs2_q8):
-        if o.dtype != torch.int32 or tuple(o.shape) != (batch, stride, 3):
-            raise ValueError("obs1_q8 and obs2_q8 must be int32 tensors [batch][stride][3]")
+        _tensor(o, torch.int32, (batch, stride, 3), "obs1_q8 and obs2_q8 must be int32 tensors [batch][stride][3]")
     if stride > POSE_MAX_STRIDE:
         raise ValueError(f"at most {POSE_MAX_STRIDE} matches per pair")
-    if counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(counts.shape) != (batch,):
-        raise ValueError("counts must be a 32-bit integer tensor [batch]")
-    if (level1 is None) != (level2 is None) or (level1 is None) != (inv_sigma2 is None):
-        raise ValueError("level1, level2 and inv_sigma2 go together")
-    tab, ntab = None, 0
-    if level1 is not None:
-        for lv in (level1, level2):
-            if lv.dtype != torch.uint8 or tuple(lv.shape) != (batch, stride):
-                raise ValueError("level1 and level2 must be uint8 tensors [batch][stride]")
-        host = np.ascontiguousarray(np.asarray(inv_sigma2, dtype=np.float32).reshape(-1))
-        ntab = int(host.size)
-        if not 1 <= ntab <= 16:
-            raise ValueError("inv_sigma2 must have 1..16 entries")
-        tab = (ctypes.c_float * ntab)(*host.tolist())
-    for t in (cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts) + (() if level1 is None else (level1, level2)):
-        if not t.is_contiguous():
-            raise ValueError("inputs must be contiguous")
+    _counts("counts must be a 32-bit integer tensor [batch]", batch, counts)
+    tab, ntab = _level_table((level1, level2), inv_sigma2, batch, stride, "level1, level2 and inv_sigma2 go together",
+                             "level1 and level2 must be uint8 tensors [batch][stride]")
+    _contiguous(cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts, level1, level2)
     dev = cam1.device
     p = capi.Sim3Params(int(hypotheses), int(seed) & 0xFFFFFFFF, int(min_inliers), int(bool(fixed_scale)))
     word = lambda t: torch.empty((batch,), dtype=torch.int32, device=dev) if t is None else t
@@ -1487,45 +1488,23 @@ def sim3RefineBatch(sim_in, cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts, *, lev
     Asynchronous on the ctx stream, no workspace: capturable."""
     import torch
     ctx = ctx or default_context()
-    as_t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda") if isinstance(a, np.ndarray) else a
-    sim_in, cam1, cam2, x1, x2 = as_t(sim_in), as_t(cam1), as_t(cam2), as_t(x1), as_t(x2)
-    obs1_q8, obs2_q8, counts, level1, level2, mask = (as_t(obs1_q8), as_t(obs2_q8), as_t(counts), as_t(level1),
-                                                       as_t(level2), as_t(mask))
-    if sim_in.dtype != torch.float32 or sim_in.dim() != 2 or int(sim_in.shape[1]) != 13:
-        raise ValueError("sim_in must be a float32 tensor [batch][13]")
-    batch = int(sim_in.shape[0])
+    sim_in, cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts, level1, level2, mask = map(
+        _on_device, (sim_in, cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts, level1, level2, mask))
+    batch, = _tensor(sim_in, torch.float32, (None, 13), "sim_in must be a float32 tensor [batch][13]")
     for c in (cam1, cam2):
-        if c.dtype != torch.float32 or tuple(c.shape) != (batch, 5):
-            raise ValueError("cam1 and cam2 must be float32 tensors [batch][5]")
-    if x1.dtype != torch.float32 or x1.dim() != 3 or int(x1.shape[0]) != batch or int(x1.shape[2]) != 3:
-        raise ValueError("x1 must be a float32 tensor [batch][stride][3]")
-    stride = int(x1.shape[1])
-    if x2.dtype != torch.float32 or tuple(x2.shape) != (batch, stride, 3):
-        raise ValueError("x2 must be a float32 tensor of x1's shape")
+        _tensor(c, torch.float32, (batch, 5), "cam1 and cam2 must be float32 tensors [batch][5]")
+    stride, = _tensor(x1, torch.float32, (batch, None, 3), "x1 must be a float32 tensor [batch][stride][3]")
+    _tensor(x2, torch.float32, (batch, stride, 3), "x2 must be a float32 tensor of x1's shape")
     for o in (obs1_q8, obs2_q8):
-        if o.dtype != torch.int32 or tuple(o.shape) != (batch, stride, 3):
-            raise ValueError("obs1_q8 and obs2_q8 must be int32 tensors [batch][stride][3]")
+        _tensor(o, torch.int32, (batch, stride, 3), "obs1_q8 and obs2_q8 must be int32 tensors [batch][stride][3]")
     if stride > POSE_MAX_STRIDE:
         raise ValueError(f"at most {POSE_MAX_STRIDE} matches per pair")
-    if counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(counts.shape) != (batch,):
-        raise ValueError("counts must be a 32-bit integer tensor [batch]")
-    if (level1 is None) != (level2 is None) or (level1 is None) != (inv_sigma2 is None):
-        raise ValueError("level1, level2 and inv_sigma2 go together")
-    tab, ntab = None, 0
-    if level1 is not None:
-        for lv in (level1, level2):
-            if lv.dtype != torch.uint8 or tuple(lv.shape) != (batch, stride):
-                raise ValueError("level1 and level2 must be uint8 tensors [batch][stride]")
-        host = np.ascontiguousarray(np.asarray(inv_sigma2, dtype=np.float32).reshape(-1))
-        ntab = int(host.size)
-        if not 1 <= ntab <= 16:
-            raise ValueError("inv_sigma2 must have 1..16 entries")
-        tab = (ctypes.c_float * ntab)(*host.tolist())
-    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (batch, stride)):
-        raise ValueError("mask must be a uint8 tensor [batch][stride]")
-    for t in (sim_in, cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts) + tuple(v for v in (level1, level2, mask) if v is not None):
-        if not t.is_contiguous():
-            raise ValueError("inputs must be contiguous")
+    _counts("counts must be a 32-bit integer tensor [batch]", batch, counts)
+    tab, ntab = _level_table((level1, level2), inv_sigma2, batch, stride, "level1, level2 and inv_sigma2 go together",
+                             "level1 and level2 must be uint8 tensors [batch][stride]")
+    if mask is not None:
+        _tensor(mask, torch.uint8, (batch, stride), "mask must be a uint8 tensor [batch][stride]")
+    _contiguous(sim_in, cam1, cam2, x1, x2, obs1_q8, obs2_q8, counts, level1, level2, mask)
     dev = sim_in.device
     p = capi.Sim3RefineParams(int(rounds), int(iters), int(huber_rounds), int(min_obs), float(th2), int(bool(fixed_scale)),
                               float(eps))
@@ -1603,23 +1582,18 @@ def matchEpipolarBatch(qdesc, qgroup, qobs_q8, qlevel, qcounts, tdesc, tgroup, t
                                ("f12", f12, (batch, 9), torch.float32), ("epipole", epipole, (batch, 2), torch.float32)):
         if t is None and name in ("qmask", "tmask"):
             continue
-        if tuple(t.shape) != shape or (dt is not None and t.dtype != dt) or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous tensor of shape {shape}" + (f" and type {dt}" if dt else ""))
+        message = f"{name} must be a contiguous tensor of shape {shape}" + (f" and type {dt}" if dt else "")
+        _tensor(t, dt, shape, message)
+        _contiguous(t, message=message)
     if (level_sigma2 is None) != (level_scale is None):
         raise ValueError("level_sigma2 and level_scale go together")
     if level_sigma2 is None:
         level_scale, level_sigma2 = mapPointLevelTables(nlevels, scale)
-    sg = np.ascontiguousarray(np.asarray(level_sigma2, dtype=np.float32).reshape(-1))
-    ls = np.ascontiguousarray(np.asarray(level_scale, dtype=np.float32).reshape(-1))
-    ntab = int(sg.size)
-    if not 1 <= ntab <= 16 or int(ls.size) != ntab:
-        raise ValueError("level_sigma2 and level_scale must have the same 1..16 entries")
-    tab_sg, tab_ls = (ctypes.c_float * ntab)(*sg.tolist()), (ctypes.c_float * ntab)(*ls.tolist())
+    unequal = "level_sigma2 and level_scale must have the same 1..16 entries"
+    tab_sg, ntab = _float_table(level_sigma2, unequal)
+    tab_ls, _ = _float_table(level_scale, unequal, ntab)
     p = capi.EpipolarParams(float(np.float32(chi2)), float(np.float32(epipole_r2)))
-    dev = qdesc.device
-    idx = torch.empty((batch, qs), dtype=torch.int32, device=dev) if idx is None else idx
-    dist = torch.empty((batch, qs), dtype=torch.int32, device=dev) if dist is None else dist
-    dist2 = torch.empty((batch, qs), dtype=torch.int32, device=dev) if dist2 is None else dist2
+    idx, dist, dist2 = _match_outputs(qdesc, idx, dist, dist2)
     ctx.check(ctx.lib.pislam_match_hamming_epipolar_batch(
         ctx.h, words, int(ngroups), ctypes.byref(p), tab_sg, tab_ls, ntab, ptr(f12), ptr(epipole), ptr(qdesc), ptr(qgroup),
         ptr(qobs_q8), ptr(qlevel), ptr(qmask), ptr(qcounts), qs, ptr(tdesc), ptr(tgroup), ptr(tobs_q8), ptr(tlevel),
@@ -1695,39 +1669,25 @@ def triangulateBatch(pose1, pose2, cam1, cam2, obs1_q8, obs2_q8, level1, level2,
     workspace: capturable as it is."""
     import torch
     ctx = ctx or default_context()
-    if pose1.dtype != torch.float32 or pose1.dim() != 2 or int(pose1.shape[1]) != 12:
-        raise ValueError("pose1 must be a float32 tensor [batch][12]")
-    batch = int(pose1.shape[0])
-    if pose2.dtype != torch.float32 or tuple(pose2.shape) != (batch, 12):
-        raise ValueError("pose2 must be a float32 tensor [batch][12]")
+    batch, = _tensor(pose1, torch.float32, (None, 12), "pose1 must be a float32 tensor [batch][12]")
+    _tensor(pose2, torch.float32, (batch, 12), "pose2 must be a float32 tensor [batch][12]")
     for cam in (cam1, cam2):
-        if cam.dtype != torch.float32 or tuple(cam.shape) != (batch, 5):
-            raise ValueError("cam1 and cam2 must be float32 tensors [batch][5]")
-    if obs1_q8.dtype != torch.int32 or obs1_q8.dim() != 3 or int(obs1_q8.shape[0]) != batch or int(obs1_q8.shape[2]) != 3:
-        raise ValueError("obs1_q8 must be an int32 tensor [batch][stride][3]")
-    stride = int(obs1_q8.shape[1])
-    if obs2_q8.dtype != torch.int32 or tuple(obs2_q8.shape) != (batch, stride, 3):
-        raise ValueError("obs2_q8 must be an int32 tensor of obs1_q8's shape")
+        _tensor(cam, torch.float32, (batch, 5), "cam1 and cam2 must be float32 tensors [batch][5]")
+    stride, = _tensor(obs1_q8, torch.int32, (batch, None, 3), "obs1_q8 must be an int32 tensor [batch][stride][3]")
+    _tensor(obs2_q8, torch.int32, (batch, stride, 3), "obs2_q8 must be an int32 tensor of obs1_q8's shape")
     if stride > TRIANGULATE_MAX_STRIDE:
         raise ValueError(f"at most {TRIANGULATE_MAX_STRIDE} slots per pair")
     for level in (level1, level2):
-        if level.dtype != torch.uint8 or tuple(level.shape) != (batch, stride):
-            raise ValueError("level1 and level2 must be uint8 tensors [batch][stride]")
-    if counts.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(counts.shape) != (batch,):
-        raise ValueError("counts must be a 32-bit integer tensor [batch]")
-    for t in (pose1, pose2, cam1, cam2, obs1_q8, obs2_q8, level1, level2, counts):
-        if not t.is_contiguous():
-            raise ValueError("inputs must be contiguous")
+        _tensor(level, torch.uint8, (batch, stride), "level1 and level2 must be uint8 tensors [batch][stride]")
+    _counts("counts must be a 32-bit integer tensor [batch]", batch, counts)
+    _contiguous(pose1, pose2, cam1, cam2, obs1_q8, obs2_q8, level1, level2, counts)
     if (level_scale is None) != (level_sigma2 is None):
         raise ValueError("level_scale and level_sigma2 go together")
     if level_scale is None:
         level_scale, level_sigma2 = mapPointLevelTables(nlevels, scale)
-    ls = np.ascontiguousarray(np.asarray(level_scale, dtype=np.float32).reshape(-1))
-    sg = np.ascontiguousarray(np.asarray(level_sigma2, dtype=np.float32).reshape(-1))
-    ntab = int(ls.size)
-    if not 1 <= ntab <= 16 or int(sg.size) != ntab:
-        raise ValueError("level_scale and level_sigma2 must have the same 1..16 entries")
-    tab_ls, tab_sg = (ctypes.c_float * ntab)(*ls.tolist()), (ctypes.c_float * ntab)(*sg.tolist())
+    unequal = "level_scale and level_sigma2 must have the same 1..16 entries"
+    tab_ls, ntab = _float_table(level_scale, unequal)
+    tab_sg, _ = _float_table(level_sigma2, unequal, ntab)
     if ratio_factor is None:
         ratio_factor = np.float32(1.5) * np.float32(scale)
     p = capi.TriangulateParams(float(np.float32(cos_min_parallax)), float(np.float32(chi2_mono)),
@@ -1804,42 +1764,19 @@ def localBundleAdjustBatch(poses, cams, kf_counts, kf_free, xw, pt_counts, obs_q
     same outputs, bit for bit.  Asynchronous on the ctx stream; capturable after reserveLocalBundleAdjust."""
     import torch
     ctx = ctx or default_context()
-    if poses.dtype != torch.float32 or poses.dim() != 3 or int(poses.shape[2]) != 12:
-        raise ValueError("poses must be a float32 tensor [batch][kf_stride][12]")
-    batch, kfs = int(poses.shape[0]), int(poses.shape[1])
-    if cams.dtype != torch.float32 or tuple(cams.shape) != (batch, kfs, 5):
-        raise ValueError("cams must be a float32 tensor [batch][kf_stride][5]")
-    if xw.dtype != torch.float32 or xw.dim() != 3 or int(xw.shape[0]) != batch or int(xw.shape[2]) != 3:
-        raise ValueError("xw must be a float32 tensor [batch][pt_stride][3]")
-    pts = int(xw.shape[1])
-    if obs_q8.dtype != torch.int32 or obs_q8.dim() != 3 or int(obs_q8.shape[0]) != batch or int(obs_q8.shape[2]) != 3:
-        raise ValueError("obs_q8 must be an int32 tensor [batch][stride][3]")
-    stride = int(obs_q8.shape[1])
-    if obs_kf.dtype != torch.uint8 or tuple(obs_kf.shape) != (batch, stride):
-        raise ValueError("obs_kf must be a uint8 tensor [batch][stride]")
-    if obs_pt.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) or tuple(obs_pt.shape) != (batch, stride):
-        raise ValueError("obs_pt must be a 16-bit integer tensor [batch][stride]")
+    batch, kfs = _tensor(poses, torch.float32, (None, None, 12), "poses must be a float32 tensor [batch][kf_stride][12]")
+    _tensor(cams, torch.float32, (batch, kfs, 5), "cams must be a float32 tensor [batch][kf_stride][5]")
+    pts, = _tensor(xw, torch.float32, (batch, None, 3), "xw must be a float32 tensor [batch][pt_stride][3]")
+    stride, = _tensor(obs_q8, torch.int32, (batch, None, 3), "obs_q8 must be an int32 tensor [batch][stride][3]")
+    _tensor(obs_kf, torch.uint8, (batch, stride), "obs_kf must be a uint8 tensor [batch][stride]")
+    _tensor(obs_pt, _word16(), (batch, stride), "obs_pt must be a 16-bit integer tensor [batch][stride]")
     if kfs > BA_MAX_KF or pts > BA_MAX_POINTS or stride > POSE_MAX_STRIDE:
         raise ValueError(f"at most {BA_MAX_KF} key frames, {BA_MAX_POINTS} points and {POSE_MAX_STRIDE} observations per window")
-    words = (torch.int32, getattr(torch, "uint32", torch.int32))
-    for t in (kf_counts, kf_free, pt_counts, counts):
-        if t.dtype not in words or tuple(t.shape) != (batch,):
-            raise ValueError("kf_counts, kf_free, pt_counts and counts must be 32-bit integer tensors [batch]")
-    if (level is None) != (inv_sigma2 is None):
-        raise ValueError("level and inv_sigma2 go together")
-    tab, ntab = None, 0
-    if level is not None:
-        if level.dtype != torch.uint8 or tuple(level.shape) != (batch, stride):
-            raise ValueError("level must be a uint8 tensor [batch][stride]")
-        host = np.ascontiguousarray(np.asarray(inv_sigma2, dtype=np.float32).reshape(-1))
-        ntab = int(host.size)
-        if not 1 <= ntab <= 16:
-            raise ValueError("inv_sigma2 must have 1..16 entries")
-        tab = (ctypes.c_float * ntab)(*host.tolist())
-    for t in (poses, cams, kf_counts, kf_free, xw, pt_counts, obs_q8, obs_kf, obs_pt, counts) + (
-            () if level is None else (level,)):
-        if not t.is_contiguous():
-            raise ValueError("inputs must be contiguous")
+    _counts("kf_counts, kf_free, pt_counts and counts must be 32-bit integer tensors [batch]", batch,
+            kf_counts, kf_free, pt_counts, counts)
+    tab, ntab = _level_table((level,), inv_sigma2, batch, stride, "level and inv_sigma2 go together",
+                             "level must be a uint8 tensor [batch][stride]")
+    _contiguous(poses, cams, kf_counts, kf_free, xw, pt_counts, obs_q8, obs_kf, obs_pt, counts, level)
     its = [int(v) for v in (iters if hasattr(iters, "__len__") else [iters] * int(rounds))]
     if len(its) < int(rounds) or len(its) > 4:
         raise ValueError("iters needs an entry per round, at most 4")
@@ -1961,28 +1898,18 @@ def poseGraphBatch(sims, v_counts, fixed, edges, meas, weight, e_counts, inc_ptr
     poses afterwards: rigidFromSim3(sims_out[b])."""
     import torch
     ctx = ctx or default_context()
-    if sims.dtype != torch.float32 or sims.dim() != 3 or int(sims.shape[2]) != 13:
-        raise ValueError("sims must be a float32 tensor [batch][v_stride][13]")
-    batch, V = int(sims.shape[0]), int(sims.shape[1])
-    words = (torch.int32, getattr(torch, "uint32", torch.int32))
-    if edges.dtype not in words or edges.dim() != 3 or int(edges.shape[0]) != batch or int(edges.shape[2]) != 2:
-        raise ValueError("edges must be a 32-bit integer tensor [batch][e_stride][2]")
-    E = int(edges.shape[1])
+    batch, V = _tensor(sims, torch.float32, (None, None, 13), "sims must be a float32 tensor [batch][v_stride][13]")
+    E, = _tensor(edges, _word32(), (batch, None, 2), "edges must be a 32-bit integer tensor [batch][e_stride][2]")
     if V > POSE_GRAPH_MAX_VERTICES or E > POSE_GRAPH_MAX_EDGES:
         raise ValueError(f"at most {POSE_GRAPH_MAX_VERTICES} vertices and {POSE_GRAPH_MAX_EDGES} edges per graph")
-    if fixed.dtype != torch.uint8 or tuple(fixed.shape) != (batch, V):
-        raise ValueError("fixed must be a uint8 tensor [batch][v_stride]")
-    if meas.dtype != torch.float32 or tuple(meas.shape) != (batch, E, 13):
-        raise ValueError("meas must be a float32 tensor [batch][e_stride][13]")
-    if weight is not None and (weight.dtype != torch.float32 or tuple(weight.shape) != (batch, E)):
-        raise ValueError("weight must be a float32 tensor [batch][e_stride]")
+    _tensor(fixed, torch.uint8, (batch, V), "fixed must be a uint8 tensor [batch][v_stride]")
+    _tensor(meas, torch.float32, (batch, E, 13), "meas must be a float32 tensor [batch][e_stride][13]")
+    if weight is not None:
+        _tensor(weight, torch.float32, (batch, E), "weight must be a float32 tensor [batch][e_stride]")
     for t, shape in ((v_counts, (batch,)), (e_counts, (batch,)), (inc_ptr, (batch, V + 1)), (inc, (batch, 2 * E))):
-        if t.dtype not in words or tuple(t.shape) != shape:
-            raise ValueError("v_counts, e_counts [batch], inc_ptr [batch][v_stride + 1] and inc [batch][2 * e_stride] must "
-                             "be 32-bit integer tensors")
-    for t in (sims, v_counts, fixed, edges, meas, e_counts, inc_ptr, inc) + (() if weight is None else (weight,)):
-        if not t.is_contiguous():
-            raise ValueError("inputs must be contiguous")
+        _tensor(t, _word32(), shape, "v_counts, e_counts [batch], inc_ptr [batch][v_stride + 1] and inc [batch][2 * e_stride] "
+                                     "must be 32-bit integer tensors")
+    _contiguous(sims, v_counts, fixed, edges, meas, e_counts, inc_ptr, inc, weight)
     p = capi.PoseGraphParams(int(iters), int(cg_iters), float(cg_tol), float(eps))
     dev = sims.device
     sims_out = torch.empty_like(sims) if sims_out is None else sims_out
@@ -2004,26 +1931,16 @@ def correctMapPointsBatch(xw, ref, pt_counts, sims_old, sims_new, v_counts, *, x
     stays as it was).  xw_out may be `xw`.  Asynchronous on the ctx stream, no workspace: capturable as it is."""
     import torch
     ctx = ctx or default_context()
-    if xw.dtype != torch.float32 or xw.dim() != 3 or int(xw.shape[2]) != 3:
-        raise ValueError("xw must be a float32 tensor [batch][pt_stride][3]")
-    batch, pts = int(xw.shape[0]), int(xw.shape[1])
-    if ref.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) or tuple(ref.shape) != (batch, pts):
-        raise ValueError("ref must be a 16-bit integer tensor [batch][pt_stride]")
-    if sims_old.dtype != torch.float32 or sims_old.dim() != 3 or int(sims_old.shape[0]) != batch or int(sims_old.shape[2]) != 13:
-        raise ValueError("sims_old must be a float32 tensor [batch][v_stride][13]")
-    if sims_new.dtype != torch.float32 or tuple(sims_new.shape) != tuple(sims_old.shape):
-        raise ValueError("sims_new must be a float32 tensor of sims_old's shape")
-    words = (torch.int32, getattr(torch, "uint32", torch.int32))
-    for t in (pt_counts, v_counts):
-        if t.dtype not in words or tuple(t.shape) != (batch,):
-            raise ValueError("pt_counts and v_counts must be 32-bit integer tensors [batch]")
-    for t in (xw, ref, pt_counts, sims_old, sims_new, v_counts):
-        if not t.is_contiguous():
-            raise ValueError("inputs must be contiguous")
+    batch, pts = _tensor(xw, torch.float32, (None, None, 3), "xw must be a float32 tensor [batch][pt_stride][3]")
+    _tensor(ref, _word16(), (batch, pts), "ref must be a 16-bit integer tensor [batch][pt_stride]")
+    V, = _tensor(sims_old, torch.float32, (batch, None, 13), "sims_old must be a float32 tensor [batch][v_stride][13]")
+    _tensor(sims_new, torch.float32, (batch, V, 13), "sims_new must be a float32 tensor of sims_old's shape")
+    _counts("pt_counts and v_counts must be 32-bit integer tensors [batch]", batch, pt_counts, v_counts)
+    _contiguous(xw, ref, pt_counts, sims_old, sims_new, v_counts)
     xw_out = torch.empty_like(xw) if xw_out is None else xw_out
     status = torch.empty((batch, pts), dtype=torch.uint8, device=xw.device) if status is None else status
     ctx.check(ctx.lib.pislam_map_points_correct_batch(ctx.h, ptr(xw), ptr(ref), ptr(pt_counts), ptr(sims_old),
-                                                      ptr(sims_new), ptr(v_counts), pts, int(sims_old.shape[1]), batch,
+                                                      ptr(sims_new), ptr(v_counts), pts, V, batch,
                                                       ptr(xw_out), ptr(status)), "pislam_map_points_correct_batch")
     return xw_out, status
 
