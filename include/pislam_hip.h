@@ -2116,7 +2116,9 @@ int pislam_triangulate_batch(pislam_ctx *ctx, const pislam_triangulate_params *p
  * is walked by the same 1024 workgroups in passes.
  *
  * Not here: ORBmatcher::Fuse (pislam_match_fuse_batch, which runs before this call so that a landmark is optimised
- * once), global bundle adjustment and windows beyond the limits, marginalisation, IMU terms. */
+ * once), global bundle adjustment and windows beyond the limits, marginalisation, IMU terms.  Which key frames form a
+ * window (the key frame, its covisible neighbours, the key frames that see their points) is read off
+ * pislam_covisibility_batch, below. */
 typedef struct pislam_ba_params {
   int32_t rounds;        /* 1..4 (ORB-SLAM: 2) */
   int32_t iters[4];      /* 1..32 Levenberg iterations of round r, r < rounds (ORB-SLAM: 5, 10) */
@@ -2239,7 +2241,8 @@ int pislam_local_ba_batch(pislam_ctx *ctx, const pislam_ba_params *p, const floa
  * launch, so a single large graph uses one compute unit; a batch above 1024 graphs is walked by the same 1024
  * workgroups in passes.
  *
- * Not here: a robust kernel, a several-workgroup form for one large graph, global bundle adjustment afterwards. */
+ * Not here: a robust kernel, a several-workgroup form for one large graph, global bundle adjustment afterwards.  The
+ * spanning-tree and covisibility edges of the graph come from pislam_covisibility_batch, below. */
 typedef struct pislam_pose_graph_params {
   int32_t iters;     /* 1..64 Levenberg iterations (ORB-SLAM: 20) */
   int32_t cg_iters;  /* 1..1024 conjugate-gradient iterations of a solve at the most */
@@ -2267,6 +2270,82 @@ int pislam_pose_graph_batch(pislam_ctx *ctx, const pislam_pose_graph_params *p, 
 int pislam_map_points_correct_batch(pislam_ctx *ctx, const float *xw, const uint16_t *ref, const uint32_t *pt_counts,
                                     const float *sims_old, const float *sims_new, const uint32_t *v_counts,
                                     size_t pt_stride, size_t v_stride, int batch, float *xw_out, uint8_t *status);
+
+/* ---- the covisibility graph: weights, ordered neighbours, spanning tree, culling statistic ---- */
+
+/* What ORB-SLAM's KeyFrame::UpdateConnections computes for every key frame of a MAP at once,
+ * with the spanning tree that the first UpdateConnections of each key frame fixes and the statistic that
+ * LocalMapping::KeyFrameCulling decides on.  One batch item is one map: a local map of a few dozen key frames, or a
+ * whole map.  The reference ships nothing of the kind: the semantics are this library's own.  This comment is the
+ * contract.  Everything is integer counting: every output is exact for every valid input, and the same inputs give the
+ * same outputs bit for bit.  tests/test_covisibility.py restates it with dictionaries of sets; tools/probes/
+ * covis_host_check.cpp compiles the kernels' own rules (pislam_covis_math.h) for the host and runs a map serially.
+ *
+ * Inputs, all device, read only.  Map b has nk = kf_counts[b] key frames, indexed in creation order, and n = counts[b]
+ * observations; both are SIGNED words that are checked, not clamped.  Entries at and beyond n are never read.
+ *   obs_pt     int32 [batch][stride]: the map point of observation i, >= 0
+ *   obs_kf     uint16 [batch][stride]: its key frame, < nk
+ *              The first n entries are STRICTLY ASCENDING in (obs_pt, obs_kf): sorted by point and by key frame within
+ *              a point, and no pair occurs twice.
+ *   obs_level  uint8 [batch][stride] or NULL: the pyramid level of the observation's keypoint; NULL: all zero
+ *   cull_mask  uint8 [batch][stride] or NULL: zero takes the observation out of the culling statistic OF ITS OWN KEY
+ *              FRAME only (ORB-SLAM: far stereo points are not counted); it still is an observer of its point and counts
+ *              in every weight; NULL: all count
+ *
+ * Definitions.  The OBSERVERS of a point are the key frames of its observations.  w(i, j), i != j, is the number of
+ * points that both key frame i and key frame j observe.  Key frame j QUALIFIES for i iff w(i, j) >= min_weight.  If
+ * nobody qualifies for i and some w(i, j) > 0, the FALLBACK applies: the single j with the largest w(i, j) qualifies, the
+ * smallest such j on a tie (UpdateConnections' "if none, keep the best").
+ *
+ * Outputs, per map, all device.
+ *   nb_idx     uint16 [batch][kf_stride][nb_stride], nb_weight int32 of the same shape: row i holds the key frames that
+ *              qualify for i, ordered by weight descending and by index ascending on equal weight
+ *              (mvpOrderedConnectedKeyFrames with the tie made definite), with their weights.  The first min(nb_count,
+ *              nb_stride) entries are written; the entries behind them are not touched.
+ *   nb_count   int32 [batch][kf_stride]: the number that qualify; it may exceed nb_stride, which is how truncation shows
+ *   parent     uint16 [batch][kf_stride]: the spanning tree.  parent[k] is the j < k with the largest w(k, j) > 0, the
+ *              smallest such j on a tie, 0xFFFF if there is none: what ORB-SLAM fixes at key frame k's first
+ *              UpdateConnections, when only earlier key frames exist and the fallback makes the best one front().
+ *              parent[0] is always 0xFFFF and the tree has no cycle.
+ *   kf_points  int32 [batch][kf_stride]: the observations of the key frame whose cull_mask is nonzero (its SUBJECTS)
+ *   kf_redundant int32 [batch][kf_stride]: the subjects whose point has at least cull_min_observers OTHER observers o
+ *              with level(o) <= level(subject) + cull_level_slack.  KeyFrameCulling removes k when kf_redundant >
+ *              0.9 * kf_points: that comparison is the caller's.
+ *   status     int32 [batch]: 0 ok; 1 nothing to do (nk == 0 or n == 0); 3 malformed: n outside [0, stride], nk outside
+ *              [0, kf_stride], an obs_kf >= nk, a negative obs_pt, or a list that is not strictly ascending.
+ * For the codes 1 and 3 the map's nb_count, kf_points and kf_redundant rows are zero, its parent row is 0xFFFF, and its
+ * nb_idx and nb_weight are untouched.  A malformed map never indexes outside its own workspace and outputs and does not
+ * disturb the other maps of the batch.  The rows k >= nk of a good map read like rows of a key frame without
+ * observations (counts 0, parent 0xFFFF).  A weight can be as large as the number of observations of a key frame and
+ * is carried in 32 bits throughout.  The votes of Tracking::UpdateLocalKeyFrames for a frame are the row of that frame
+ * appended to the map as key frame nk, with min_weight = 1.
+ *
+ * Limits: the parameter ranges in the struct comments; 1 <= kf_stride <= 4096 (the vertex limit of
+ * pislam_pose_graph_batch: a map that fits this call fits that one), 1 <= stride < 2^31, 1 <= nb_stride <= kf_stride;
+ * batch >= 0 (batch == 0 is a no-op that returns PISLAM_OK after the checks of p and the shape); offsets use size_t
+ * arithmetic.  Any violation, or a NULL or host pointer where a device pointer is required (obs_level and cull_mask
+ * alone may be NULL), or an output that overlaps an input or another output: PISLAM_ERR_INVALID with a message, before
+ * anything is launched or written.  `p` is host memory, read during the call.  Asynchronous on the context stream: an
+ * asynchronous memset of the workspace, a pass with one thread per observation that adds into a dense uint32 matrix
+ * [kf_stride][kf_stride] per map with integer atomics (the order of arrival cannot change a word), and a pass with one
+ * workgroup per key frame that sorts its row.  The workspace, 4 * batch * (kf_stride^2 + 2 * kf_stride + 1) bytes (64
+ * MiB per map at kf_stride = 4096), belongs to the context and grows on demand, which synchronises; a size that the
+ * device refuses is PISLAM_ERR_NOMEM.  After pislam_covisibility_reserve of the same or a larger shape the call
+ * allocates nothing and never synchronises, so it can be captured into a hipGraph.
+ *
+ * Not here: the choice of a map point's descriptor, and building the windows of pislam_local_ba_batch from the
+ * graph. */
+typedef struct pislam_covis_params {
+  int32_t min_weight;          /* >= 1 (ORB-SLAM: 15) */
+  int32_t cull_min_observers;  /* >= 1 (ORB-SLAM: 3) */
+  int32_t cull_level_slack;    /* 0..255 (ORB-SLAM: 1) */
+} pislam_covis_params;
+int pislam_covisibility_reserve(pislam_ctx *ctx, size_t kf_stride, size_t stride, int batch);
+int pislam_covisibility_batch(pislam_ctx *ctx, const pislam_covis_params *p, const uint16_t *obs_kf, const int32_t *obs_pt,
+                              const int32_t *counts, const int32_t *kf_counts, const uint8_t *obs_level,
+                              const uint8_t *cull_mask, size_t kf_stride, size_t stride, size_t nb_stride, int batch,
+                              uint16_t *nb_idx, int32_t *nb_weight, int32_t *nb_count, uint16_t *parent,
+                              int32_t *kf_points, int32_t *kf_redundant, int32_t *status);
 
 /* ---- multi-GPU: one process per GPU, pyramids sharded, ONE collective ---- */
 

@@ -71,6 +71,10 @@ class PoseGraphParams(ctypes.Structure):
                 ("eps", ctypes.c_double)]
 
 
+class CovisParams(ctypes.Structure):
+    _fields_ = [("min_weight", ctypes.c_int32), ("cull_min_observers", ctypes.c_int32), ("cull_level_slack", ctypes.c_int32)]
+
+
 class PnpParams(ctypes.Structure):
     _fields_ = [("hypotheses", ctypes.c_int32), ("seed", ctypes.c_uint32), ("min_inliers", ctypes.c_int32)]
 
@@ -224,6 +228,9 @@ SYMBOLS = {
     "pislam_pose_graph_batch": (_i, [_vp, ctypes.POINTER(PoseGraphParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                      _sz, _i, _vp, _vp, _vp]),
     "pislam_map_points_correct_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i, _vp, _vp]),
+    "pislam_covisibility_reserve": (_i, [_vp, _sz, _sz, _i]),
+    "pislam_covisibility_batch": (_i, [_vp, ctypes.POINTER(CovisParams), _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _i, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _vp]),
     "pislam_pnp_ransac_batch": (_i, [_vp, ctypes.POINTER(PnpParams), _vp, _vp, _vp, _vp, _vp,
                                      ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pislam_sim3_ransac_batch": (_i, [_vp, ctypes.POINTER(Sim3Params), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -70,6 +70,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_mappoint_kernels.h"
 #include "pislam_ba_kernels.h"
 #include "pislam_graph_kernels.h"
+#include "pislam_covis_kernels.h"
 #include "pislam_warp_kernels.h"
 #include "pislam_clahe_kernels.h"
 
@@ -139,6 +140,7 @@ struct pislam_ctx {
   CellIndex w_epi;                   // epipolar matcher (pe::k_epi_index): group offsets, group-sorted entries with their geometry (meta), descriptors
   DevBuf w_ba;                       // local bundle adjustment (pbk::k_local_ba): a slice per workgroup (pbk::ws_bytes)
   DevBuf w_pg;                       // essential-graph optimisation (pgk::k_pose_graph): a slice per workgroup (pgr::ws_bytes)
+  DevBuf w_cv;                       // covisibility graph (pcvk::k_covis_count, k_covis_rows): matrices, counters, flags (pcv::ws_bytes)
   DevBuf w_db;                       // key-frame database query (pd::k_db_accumulate .. k_db_merge): accumulator planes, maxima, partial lists
   // Host-built plan tables the kernels read instead of walking the plan (the bucket selection pass's unit table): one
   // device buffer per distinct CONTENT, never rewritten in place — a captured graph keeps reading the table
@@ -519,6 +521,7 @@ PISLAM_EXPORT int pislam_ctx_destroy(pislam_ctx *c) {
   c->w_db.release();
   c->w_ba.release();
   c->w_pg.release();
+  c->w_cv.release();
   for (auto *t : c->plan_tables) {
     t->dev.release();
     delete t;
@@ -3209,6 +3212,84 @@ PISLAM_EXPORT int pislam_map_points_correct_batch(pislam_ctx *c, const float *xw
   hipLaunchKernelGGL(pgk::k_map_points_correct, dim3((unsigned)std::min<size_t>(groups, pgk::MC_GRID_CAP)),
                      dim3(pgk::MC_THREADS), 0, c->stream, a);
   return launch_ok(c, "k_map_points_correct");
+}
+
+// ---- the covisibility graph of a map -------------------------------------------------------------
+
+namespace {
+
+int covis_shape(pislam_ctx *c, size_t kf_stride, size_t stride, int batch) {
+  if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
+  if (kf_stride < 1 || kf_stride > (size_t)pcv::MAX_KF) return fail(c, PISLAM_ERR_INVALID, "kf_stride must be 1..4096");
+  if (stride < 1 || stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..2^31 - 1");
+  return PISLAM_OK;
+}
+
+int covis_workspace(pislam_ctx *c, size_t kf_stride, int batch) {
+  if (c->w_cv.ensure(pcv::ws_bytes(kf_stride, (size_t)batch)) != PISLAM_OK)
+    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(covisibility workspace)");
+  return PISLAM_OK;
+}
+
+}  // namespace
+
+PISLAM_EXPORT int pislam_covisibility_reserve(pislam_ctx *c, size_t kf_stride, size_t stride, int batch) {
+  if (!c) return PISLAM_ERR_INVALID;
+  PCHK(covis_shape(c, kf_stride, stride, batch));
+  if (batch == 0) return PISLAM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  return covis_workspace(c, kf_stride, batch);
+}
+
+PISLAM_EXPORT int pislam_covisibility_batch(pislam_ctx *c, const pislam_covis_params *p, const uint16_t *obs_kf,
+                                            const int32_t *obs_pt, const int32_t *counts, const int32_t *kf_counts,
+                                            const uint8_t *obs_level, const uint8_t *cull_mask, size_t kf_stride,
+                                            size_t stride, size_t nb_stride, int batch, uint16_t *nb_idx, int32_t *nb_weight,
+                                            int32_t *nb_count, uint16_t *parent, int32_t *kf_points, int32_t *kf_redundant,
+                                            int32_t *status) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
+  if (p->min_weight < 1) return fail(c, PISLAM_ERR_INVALID, "min_weight must be >= 1");
+  if (p->cull_min_observers < 1) return fail(c, PISLAM_ERR_INVALID, "cull_min_observers must be >= 1");
+  if (p->cull_level_slack < 0 || p->cull_level_slack > 255) return fail(c, PISLAM_ERR_INVALID, "cull_level_slack must be 0..255");
+  PCHK(covis_shape(c, kf_stride, stride, batch));
+  if (nb_stride < 1 || nb_stride > kf_stride) return fail(c, PISLAM_ERR_INVALID, "nb_stride must be 1..kf_stride");
+  if (batch == 0) return PISLAM_OK;
+  const char *what = "the covisibility call takes device pointers only";
+  PCHK(device_ptrs(c, {obs_kf, obs_pt, counts, kf_counts, nb_idx, nb_weight, nb_count, parent, kf_points, kf_redundant, status},
+                   what));
+  if ((obs_level && !is_device_ptr(obs_level)) || (cull_mask && !is_device_ptr(cull_mask)))
+    return fail(c, PISLAM_ERR_INVALID, what);
+  {
+    const size_t B = (size_t)batch, word = B * sizeof(int32_t), row = B * kf_stride;
+    const LkRange in[] = {{obs_kf, B * stride * sizeof(uint16_t)}, {obs_pt, B * stride * sizeof(int32_t)}, {counts, word},
+                          {kf_counts, word}, {obs_level, B * stride}, {cull_mask, B * stride}};
+    const LkRange out[] = {{nb_idx, row * nb_stride * sizeof(uint16_t)}, {nb_weight, row * nb_stride * sizeof(int32_t)},
+                           {nb_count, row * sizeof(int32_t)}, {parent, row * sizeof(uint16_t)},
+                           {kf_points, row * sizeof(int32_t)}, {kf_redundant, row * sizeof(int32_t)}, {status, word}};
+    if (const char *bad = ranges_overlap(in, out)) return fail(c, PISLAM_ERR_INVALID, bad);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  PCHK(covis_workspace(c, kf_stride, batch));
+  pcvk::CvArgs a{};
+  a.obs_pt = obs_pt, a.counts = counts, a.kf_counts = kf_counts, a.obs_kf = obs_kf, a.obs_level = obs_level, a.cull_mask = cull_mask;
+  a.kf_stride = kf_stride, a.stride = stride, a.nb_stride = nb_stride, a.batch = (size_t)batch;
+  a.p = pcv::Params{p->min_weight, p->cull_min_observers, p->cull_level_slack};
+  a.nb_idx = nb_idx, a.parent = parent, a.nb_weight = nb_weight, a.nb_count = nb_count, a.kf_points = kf_points;
+  a.kf_redundant = kf_redundant, a.status = status;
+  pcv::ws_carve(c->w_cv.p, kf_stride, a.batch, &a.ws);
+  // a second call on the same context starts from a clean matrix
+  HIPCHK(c, hipMemsetAsync(c->w_cv.p, 0, pcv::ws_bytes(kf_stride, a.batch), c->stream));
+  const size_t slots = a.batch * stride, count_groups = (slots + pcvk::CV_THREADS - 1) / pcvk::CV_THREADS;
+  hipLaunchKernelGGL(pcvk::k_covis_count, dim3((unsigned)std::min<size_t>(count_groups, pcvk::CV_GRID_CAP)),
+                     dim3(pcvk::CV_THREADS), 0, c->stream, a);
+  PCHK(launch_ok(c, "k_covis_count"));
+  // the row kernel: 64, 128 or 256 threads and 8 bytes of LDS per key, both by kf_stride rounded up to a power of two
+  size_t keys = 64;
+  while (keys < kf_stride) keys <<= 1;
+  hipLaunchKernelGGL(pcvk::k_covis_rows, dim3((unsigned)std::min<size_t>(a.batch * kf_stride, pcvk::CV_GRID_CAP)),
+                     dim3((unsigned)std::min<size_t>(keys, pcvk::CV_THREADS)), keys * sizeof(uint64_t), c->stream, a);
+  return launch_ok(c, "k_covis_rows");
 }
 
 // ---- bag of words: integer weights and the key-frame database -----------------------------

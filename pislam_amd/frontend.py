@@ -1945,6 +1945,153 @@ def correctMapPointsBatch(xw, ref, pt_counts, sims_old, sims_new, v_counts, *, x
     return xw_out, status
 
 
+# ---- the covisibility graph: weights, ordered neighbours, spanning tree, culling statistic ----------
+COVIS_MAX_KF = 4096         # == POSE_GRAPH_MAX_VERTICES: a map that fits covisibilityBatch fits poseGraphBatch
+
+
+def mapObservations(obs_kf, obs_pt, counts, *more):
+    """The observations of covisibilityBatch from per-observation lists in any order: obs_kf and obs_pt are integer
+    tensors [batch][stride] (key frame of the map, point of the map), counts [batch].  The first counts[b] entries of a row
+    are sorted by point and by key frame within a point (a stable sort of the key obs_pt * 65536 + obs_kf; the call
+    itself refuses a map in which a pair occurs twice, a negative point or a key frame beyond the map's); the entries
+    behind them stay behind.  Every further tensor [batch][stride] or [batch][stride][..] passed (obs_level, cull_mask,
+    keypoint words) is sorted alike and keeps its dtype.  Returns (obs_kf int16 [batch][stride] (the uint16 words of the
+    call: a key frame index is below 4096), obs_pt int32 [batch][stride], counts int32 [batch] clamped to [0, stride],
+    *more).  Torch ops on the current torch stream."""
+    import torch
+    if obs_kf.dim() != 2 or tuple(obs_pt.shape) != tuple(obs_kf.shape):
+        raise ValueError("obs_kf and obs_pt must be [batch][stride]")
+    batch, stride = (int(v) for v in obs_kf.shape)
+    if tuple(counts.shape) != (batch,):
+        raise ValueError("counts must be [batch]")
+    for t in more:
+        if t.dim() < 2 or tuple(t.shape[:2]) != (batch, stride):
+            raise ValueError("every further tensor must be [batch][stride] or [batch][stride][..]")
+    k, p = obs_kf.to(torch.int64) & 0xFFFF, obs_pt.to(torch.int64)
+    n = counts.to(torch.int64).clamp(0, stride)
+    live = torch.arange(stride, device=k.device)[None, :] < n[:, None]
+    key = torch.where(live, p * 65536 + k, torch.full_like(k, 1 << 62))
+    order = torch.argsort(key, dim=1, stable=True)
+
+    def g(t):
+        o = order.reshape(order.shape + (1,) * (t.dim() - 2)).expand(t.shape)
+        return torch.gather(t, 1, o).contiguous()
+    return (((g(k) ^ 0x8000) - 0x8000).to(torch.int16), g(p).to(torch.int32), n.to(torch.int32)) + tuple(g(t) for t in more)
+
+
+def reserveCovisibility(kf_stride: int, stride: int, batch: int, *, ctx: Context | None = None):
+    """Size the context's workspace for covisibilityBatch calls of up to this shape (pislam_covisibility_reserve; 4 *
+    batch * (kf_stride^2 + 2 * kf_stride + 1) bytes): afterwards such calls allocate nothing and never synchronise, so
+    they can be captured into a hipGraph."""
+    ctx = ctx or default_context()
+    ctx.check(ctx.lib.pislam_covisibility_reserve(ctx.h, int(kf_stride), int(stride), int(batch)), "pislam_covisibility_reserve")
+
+
+def covisibilityBatch(obs_kf, obs_pt, counts, kf_counts, *, obs_level=None, cull_mask=None, kf_stride=None, nb_stride=None,
+                      min_weight=15, cull_min_observers=3, cull_level_slack=1, nb_idx=None, nb_weight=None, nb_count=None,
+                      parent=None, kf_points=None, kf_redundant=None, status=None, ctx: Context | None = None):
+    """Batched covisibility graph (pislam_covisibility_batch; the contract is the comment in include/pislam_hip.h),
+    ORB-SLAM's KeyFrame::UpdateConnections for every key frame of a map at once, with the spanning tree and the statistic
+    of KeyFrameCulling.  Per map: obs_kf int16 or uint16 and obs_pt 32-bit integers [batch][stride], the first counts[b]
+    entries strictly ascending in (obs_pt, obs_kf) (mapObservations makes them); counts and kf_counts [batch]; obs_level
+    and cull_mask uint8 [batch][stride] or None (all levels zero; every observation counts in the statistic of its key
+    frame).  kf_stride (<= 4096) is the key-frame extent of the outputs: given, or that of nb_count when it is passed;
+    nb_stride (1..kf_stride) the neighbours kept per key frame: given, or that of nb_idx when it is passed, or kf_stride
+    (nothing is truncated; the two neighbour tensors then take 6 * kf_stride^2 bytes per map).  Key frame j qualifies for
+    i with at least min_weight shared points; if nobody does, the best one.  Returns (nb_idx int16 and nb_weight int32
+    [batch][kf_stride][nb_stride]: the neighbours by weight descending, index ascending on a tie, written up to
+    min(nb_count, nb_stride); nb_count int32 [batch][kf_stride]; parent int16 [batch][kf_stride] (the uint16 words of the
+    call: -1 is 0xFFFF, no parent); kf_points and kf_redundant int32 [batch][kf_stride] (a key frame is redundant by
+    ORB-SLAM's rule when kf_redundant > 0.9 * kf_points); status int32 [batch]: 0 ok, 1 nothing to do, 3 malformed).
+    Numpy inputs go to the current device.  Integer counting: exact, and the same inputs give the same outputs bit for
+    bit.  Asynchronous on the ctx stream; capturable after reserveCovisibility."""
+    import torch
+    ctx = ctx or default_context()
+    obs_kf, obs_pt, counts, kf_counts, obs_level, cull_mask = (_on_device(a) for a in (obs_kf, obs_pt, counts, kf_counts,
+                                                                                       obs_level, cull_mask))
+    batch, stride = _tensor(obs_pt, _word32(), (None, None), "obs_pt must be a 32-bit integer tensor [batch][stride]")
+    _tensor(obs_kf, _word16(), (batch, stride), "obs_kf must be a 16-bit integer tensor [batch][stride]")
+    _counts("counts and kf_counts must be 32-bit integer tensors [batch]", batch, counts, kf_counts)
+    for t, message in ((obs_level, "obs_level must be a uint8 tensor [batch][stride]"),
+                       (cull_mask, "cull_mask must be a uint8 tensor [batch][stride]")):
+        if t is not None:
+            _tensor(t, torch.uint8, (batch, stride), message)
+    if kf_stride is None:
+        if nb_count is None or nb_count.dim() != 2:
+            raise ValueError("kf_stride is needed, or the output nb_count [batch][kf_stride] to take it from")
+        kf_stride = int(nb_count.shape[1])
+    kf_stride = int(kf_stride)
+    if not 1 <= kf_stride <= COVIS_MAX_KF:
+        raise ValueError(f"kf_stride must be 1..{COVIS_MAX_KF}")
+    if nb_stride is None:
+        nb_stride = int(nb_idx.shape[2]) if nb_idx is not None and nb_idx.dim() == 3 else kf_stride
+    nb_stride = int(nb_stride)
+    if not 1 <= nb_stride <= kf_stride:
+        raise ValueError("nb_stride must be 1..kf_stride")
+    if int(min_weight) < 1 or int(cull_min_observers) < 1 or not 0 <= int(cull_level_slack) <= 255:
+        raise ValueError("min_weight and cull_min_observers must be >= 1 and cull_level_slack 0..255")
+    dev = obs_pt.device
+    new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)
+    nb_idx = new(torch.int16, batch, kf_stride, nb_stride) if nb_idx is None else nb_idx
+    nb_weight = new(torch.int32, batch, kf_stride, nb_stride) if nb_weight is None else nb_weight
+    nb_count = new(torch.int32, batch, kf_stride) if nb_count is None else nb_count
+    parent = new(torch.int16, batch, kf_stride) if parent is None else parent
+    kf_points = new(torch.int32, batch, kf_stride) if kf_points is None else kf_points
+    kf_redundant = new(torch.int32, batch, kf_stride) if kf_redundant is None else kf_redundant
+    status = new(torch.int32, batch) if status is None else status
+    _tensor(nb_idx, _word16(), (batch, kf_stride, nb_stride), "nb_idx must be a 16-bit integer tensor [batch][kf_stride][nb_stride]")
+    _tensor(nb_weight, _word32(), (batch, kf_stride, nb_stride),
+            "nb_weight must be a 32-bit integer tensor [batch][kf_stride][nb_stride]")
+    _tensor(parent, _word16(), (batch, kf_stride), "parent must be a 16-bit integer tensor [batch][kf_stride]")
+    for t in (nb_count, kf_points, kf_redundant):
+        _tensor(t, _word32(), (batch, kf_stride), "nb_count, kf_points and kf_redundant must be 32-bit integer tensors "
+                                                  "[batch][kf_stride]")
+    _counts("status must be a 32-bit integer tensor [batch]", batch, status)
+    _contiguous(obs_kf, obs_pt, counts, kf_counts, obs_level, cull_mask)
+    _contiguous(nb_idx, nb_weight, nb_count, parent, kf_points, kf_redundant, status, message="outputs must be contiguous")
+    p = capi.CovisParams(int(min_weight), int(cull_min_observers), int(cull_level_slack))
+    ctx.check(ctx.lib.pislam_covisibility_batch(ctx.h, ctypes.byref(p), ptr(obs_kf), ptr(obs_pt), ptr(counts), ptr(kf_counts),
+                                                ptr(obs_level), ptr(cull_mask), kf_stride, stride, nb_stride, batch,
+                                                ptr(nb_idx), ptr(nb_weight), ptr(nb_count), ptr(parent), ptr(kf_points),
+                                                ptr(kf_redundant), ptr(status)), "pislam_covisibility_batch")
+    return nb_idx, nb_weight, nb_count, parent, kf_points, kf_redundant, status
+
+
+def essentialPairs(nb_idx, nb_weight, nb_count, parent, kf_counts, min_weight=100):
+    """The `pairs` of essentialGraph from covisibilityBatch's outputs: a list with one integer tensor [ne][2] per map.
+    First the spanning-tree edges (parent[k], k) in ascending k; behind them the covisibility links with nb_weight >=
+    min_weight (ORB-SLAM: 100) as (i, j), i < j, in ascending order, each once, without those that are tree edges
+    already.  The caller appends the loop edges behind them and passes their measurements as essentialGraph's `meas`.
+    Only key frames below kf_counts[b] are looked at.  Raises ValueError if a row was truncated (nb_count > nb_stride)
+    and its last written weight still reaches min_weight: a strong link may then be missing (a row is ordered by weight,
+    so a truncated row whose last weight is below min_weight hides none).  Reads sizes on the host, as essentialGraph
+    does (this synchronises); torch ops on the current torch stream."""
+    import torch
+    if nb_idx.dim() != 3 or tuple(nb_weight.shape) != tuple(nb_idx.shape):
+        raise ValueError("nb_idx and nb_weight must be [batch][kf_stride][nb_stride]")
+    batch, ks, nbs = (int(v) for v in nb_idx.shape)
+    if tuple(nb_count.shape) != (batch, ks) or tuple(parent.shape) != (batch, ks) or tuple(kf_counts.shape) != (batch,):
+        raise ValueError("nb_count and parent must be [batch][kf_stride] and kf_counts [batch]")
+    out = []
+    for b, nk in enumerate(int(v) for v in kf_counts.tolist()):
+        nk = min(max(nk, 0), ks)
+        par = parent[b, :nk].to(torch.int64) & 0xFFFF
+        kid = torch.nonzero(par != 0xFFFF)[:, 0]
+        tree = torch.stack([par[kid], kid], dim=1)
+        cnt = nb_count[b, :nk].to(torch.int64)
+        idx, w = nb_idx[b, :nk].to(torch.int64) & 0xFFFF, nb_weight[b, :nk].to(torch.int64)
+        written = torch.arange(nbs, device=idx.device)[None, :] < cnt.clamp(0, nbs)[:, None]
+        if bool(((cnt > nbs) & (w[:, nbs - 1] >= int(min_weight))).any()):
+            raise ValueError("a neighbour row was truncated (nb_count > nb_stride) above min_weight: a strong link may be missing")
+        row, col = torch.nonzero(written & (w >= int(min_weight)), as_tuple=True)
+        other = idx[row, col]
+        code = torch.unique(torch.minimum(row, other) * 65536 + torch.maximum(row, other))    # (sorted ascending)
+        code = code[~torch.isin(code, tree[:, 0] * 65536 + tree[:, 1])]
+        links = torch.stack([code // 65536, code % 65536], dim=1)
+        out.append(torch.cat([tree, links]).to(torch.int32))
+    return out
+
+
 # ---- bag of words: integer weights and the key-frame database ----------
 BOW_MAX_STRIDE = 16384      # entries of a bag-of-words vector (pislam_bow_vector_batch)
 
