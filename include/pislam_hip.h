@@ -740,9 +740,10 @@ int pislam_match_projection_batch(pislam_ctx *ctx, int words, const pislam_level
  * there).
  *
  * Not here: what follows a match (add the observation, or replace the point
- * with fewer observations by the other: the map is the caller's), descriptor
- * and normal updates of fused points, and the stereo right-coordinate test of
- * the motion-model SearchByProjection. */
+ * with fewer observations by the other: the map is the caller's), and the
+ * stereo right-coordinate test of the motion-model SearchByProjection.  The
+ * descriptor and normal updates of the fused points are
+ * pislam_map_points_update_batch, below, on the map after the caller's edit. */
 typedef struct pislam_fuse_params {
   float chi2_mono;   /* > 0, +inf allowed (ORB-SLAM: 5.99f) */
   float chi2_stereo; /* > 0, +inf allowed (ORB-SLAM: 7.8f) */
@@ -2333,8 +2334,8 @@ int pislam_map_points_correct_batch(pislam_ctx *ctx, const float *xw, const uint
  * device refuses is PISLAM_ERR_NOMEM.  After pislam_covisibility_reserve of the same or a larger shape the call
  * allocates nothing and never synchronises, so it can be captured into a hipGraph.
  *
- * Not here: the choice of a map point's descriptor, and building the windows of pislam_local_ba_batch from the
- * graph. */
+ * Not here: building the windows of pislam_local_ba_batch from the graph.  The choice of a map point's descriptor is
+ * pislam_map_points_update_batch, below, on the same observation list. */
 typedef struct pislam_covis_params {
   int32_t min_weight;          /* >= 1 (ORB-SLAM: 15) */
   int32_t cull_min_observers;  /* >= 1 (ORB-SLAM: 3) */
@@ -2346,6 +2347,89 @@ int pislam_covisibility_batch(pislam_ctx *ctx, const pislam_covis_params *p, con
                               const uint8_t *cull_mask, size_t kf_stride, size_t stride, size_t nb_stride, int batch,
                               uint16_t *nb_idx, int32_t *nb_weight, int32_t *nb_count, uint16_t *parent,
                               int32_t *kf_points, int32_t *kf_redundant, int32_t *status);
+
+/* ---- the map points' summaries: mean viewing direction, distance range, representative descriptor ---- */
+
+/* What ORB-SLAM's MapPoint::UpdateNormalAndDepth and MapPoint::ComputeDistinctiveDescriptors compute, for every point of
+ * a MAP at once: the words that pislam_match_projection_batch and pislam_match_fuse_batch read
+ * of a map point (normal, drange, the query descriptor) and the nobs that frontend.fuseDecisions takes.  ORB-SLAM runs
+ * the two after CreateNewMapPoints, after Fuse, after local bundle adjustment and after a loop correction; this call runs
+ * after pislam_triangulate_batch, pislam_match_fuse_batch, pislam_local_ba_batch and pislam_map_points_correct_batch.
+ * One batch item is one map, as in pislam_covisibility_batch.  The reference ships nothing of the kind: the semantics
+ * are this library's own.  This comment is the contract.  Every +, -, *, / and sqrt below is ONE binary32 operation
+ * rounded to nearest even, NEVER fused into an FMA, evaluated left to right as written; the divisions and the square
+ * root are correctly rounded; a NaN fails every comparison.  tests/test_map_points_update.py restates it in numpy;
+ * tools/probes/mapupdate_host_check.cpp compiles the kernels' own rules (pislam_mapupdate_math.h) for the host and runs a
+ * map serially.
+ *
+ * Inputs, all device, read only.  Map b has nk = kf_counts[b] key frames, n = counts[b] observations (SIGNED words,
+ * checked, not clamped) and npt = pt_counts[b] points (checked against pt_stride).  Entries at and beyond a count are
+ * never read.
+ *   obs_pt, obs_kf, counts, kf_counts: pislam_covisibility_batch's observation list, as they are: the first n entries
+ *              STRICTLY ASCENDING in (obs_pt, obs_kf); here obs_pt < npt as well
+ *   obs_level  uint8 [batch][stride]: the pyramid level of the observation's keypoint
+ *   obs_desc   uint32 [batch][stride][8] or NULL: the 256-bit descriptor of the observation's keypoint, in the matchers'
+ *              word order; NULL: no descriptor is chosen, and desc must be NULL
+ *   poses      float [batch][kf_stride][12]: per key frame R row-major, then t (Xc = R Xw + t): the pose call's layout
+ *   xw         float [batch][pt_stride][3]: the points
+ *   ref        uint16 [batch][pt_stride] or NULL: each point's reference key frame, what
+ *              pislam_map_points_correct_batch takes
+ *   level_scale HOST float [nlevels], read during the call and carried by value (pislam_triangulate_batch's table)
+ *
+ * One point p.  Its OBSERVERS are the observations with obs_pt == p, in list order (ascending key frame), n_p of them,
+ * observer i in key frame k_i with pose (R, t) on level l_i.
+ *   Geometry:  O_j = -((R_j*t_0 + R_(3+j)*t_1) + R_(6+j)*t_2)   (the triangulation call's camera centre),  e = Xw - O,
+ *              d_i = sqrt((e_0*e_0 + e_1*e_1) + e_2*e_2),  u_i = e / d_i (three divisions);
+ *              w = u_0, then w = w + u_i for i = 1 .. n_p - 1, in list order;
+ *              wn = sqrt((w_0*w_0 + w_1*w_1) + w_2*w_2),  normal = w / wn.
+ *              The normal is a UNIT vector, as pislam_triangulate_batch writes it (ORB-SLAM divides the sum by n_p
+ *              instead; the matchers only compare its cosine).  The sum has this one order, so the words do not depend
+ *              on the launch shape.
+ *   Reference: the observer whose key frame equals ref[p]; the first observer if ref is NULL; also the first observer,
+ *              with status 2, if ref[p] is not among the observers (what MapPoint::EraseObservation does to mpRefKF).
+ *   Range:     with the reference observer r:  rr = d_r * level_scale[l_r],  drange = (rr / level_scale[nlevels - 1], rr).
+ *              For a point with two observers and the first as reference, normal and drange are
+ *              pislam_triangulate_batch's words exactly.
+ *   Descriptor: D(i, j) is the Hamming distance of the descriptors of observers i and j, D(i, i) = 0; med(i) is the
+ *              element with index floor((n_p - 1) / 2) of row i sorted ascending, the self-distance included (ORB-SLAM's
+ *              vDists[0.5*(N-1)]); desc[p] is the descriptor of the observer with the smallest med, the first in list
+ *              order on a tie.  An integer choice: exact.
+ *
+ * Outputs, device, each written for every p < min(npt, pt_stride) and for no other point:
+ *   normal     float [batch][pt_stride][3] or NULL;  drange float [batch][pt_stride][2] or NULL;
+ *   desc       uint32 [batch][pt_stride][8] or NULL
+ *   nobs       int32 [batch][pt_stride]: n_p
+ *   first      int32 [batch][pt_stride] or NULL: the list index of the point's first observation, -1 if it has none
+ *   pt_status  uint8 [batch][pt_stride]: 0 ok;  1 no observers (nobs 0; normal, drange and desc untouched);  2 the
+ *              reference was replaced (everything written);  3 geometry refused: a pose word of an observer or a word of
+ *              xw[p] is not finite, some d_i == 0, wn == 0, or a word of normal or drange is not finite (normal and
+ *              drange zeros, desc still chosen);  4 l_r >= nlevels (drange zeros, normal and desc written).  Of 3, 4 and
+ *              2 the first that applies.
+ *   status     int32 [batch]: 0 ok; 1 nothing to do (npt == 0 or n == 0); 3 malformed: n outside [0, stride], nk outside
+ *              [0, kf_stride], npt > pt_stride, an obs_kf >= nk, an obs_pt outside [0, npt), or a list that is not
+ *              strictly ascending.  For the codes 1 and 3 every point of the map gets pt_status 1, nobs 0 and first -1,
+ *              and its normal, drange and desc are untouched.  A malformed map never indexes outside its own rows and
+ *              does not disturb the other maps of the batch.
+ *
+ * Limits: level_scale 1..16 entries, finite, > 0, non-decreasing; 1 <= kf_stride <= 4096, 1 <= stride < 2^31, 1 <=
+ * pt_stride < 2^31; batch >= 0 (batch == 0 is a no-op that returns PISLAM_OK after the checks of the table and the
+ * shape); offsets use size_t arithmetic.  Any violation, or a NULL or host pointer where a device pointer is required
+ * (obs_desc, ref, normal, drange, desc and first alone may be NULL), desc without obs_desc, or an output that overlaps
+ * an input or another output: PISLAM_ERR_INVALID with a message, before anything is launched or written.  No workspace
+ * and no reserve call: status[b] carries the map's flag between the kernels (an asynchronous memset, then one thread per
+ * observation slot that checks it), a point's observers are found by binary search in the ascending list, one lane
+ * walks a point's observers for the geometry, one wave chooses the descriptors of as many tracks as fit its 64 lanes
+ * together, and a track of more than 64 observers takes a workgroup.  Asynchronous on the context stream, never
+ * synchronises: the call can be captured into a hipGraph as it is.
+ *
+ * Not here: adding and erasing observations and replacing a fused point (frontend.fuseDecisions lists them; the map is
+ * the caller's), and mnVisible / mnFound, which are counters of the tracking thread. */
+int pislam_map_points_update_batch(pislam_ctx *ctx, const uint16_t *obs_kf, const int32_t *obs_pt, const int32_t *counts,
+                                   const int32_t *kf_counts, const uint8_t *obs_level, const uint32_t *obs_desc,
+                                   const float *poses, const float *xw, const uint32_t *pt_counts, const uint16_t *ref,
+                                   const float *level_scale, int nlevels, size_t kf_stride, size_t stride,
+                                   size_t pt_stride, int batch, float *normal, float *drange, uint32_t *desc,
+                                   int32_t *nobs, int32_t *first, uint8_t *pt_status, int32_t *status);
 
 /* ---- multi-GPU: one process per GPU, pyramids sharded, ONE collective ---- */
 

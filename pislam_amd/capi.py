@@ -231,6 +231,9 @@ SYMBOLS = {
     "pislam_covisibility_reserve": (_i, [_vp, _sz, _sz, _i]),
     "pislam_covisibility_batch": (_i, [_vp, ctypes.POINTER(CovisParams), _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _i, _vp,
                                        _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pislam_map_points_update_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            ctypes.POINTER(ctypes.c_float), _i, _sz, _sz, _sz, _i, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _vp]),
     "pislam_pnp_ransac_batch": (_i, [_vp, ctypes.POINTER(PnpParams), _vp, _vp, _vp, _vp, _vp,
                                      ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pislam_sim3_ransac_batch": (_i, [_vp, ctypes.POINTER(Sim3Params), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

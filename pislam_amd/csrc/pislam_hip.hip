@@ -71,6 +71,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_ba_kernels.h"
 #include "pislam_graph_kernels.h"
 #include "pislam_covis_kernels.h"
+#include "pislam_mapupdate_kernels.h"
 #include "pislam_warp_kernels.h"
 #include "pislam_clahe_kernels.h"
 
@@ -3290,6 +3291,67 @@ PISLAM_EXPORT int pislam_covisibility_batch(pislam_ctx *c, const pislam_covis_pa
   hipLaunchKernelGGL(pcvk::k_covis_rows, dim3((unsigned)std::min<size_t>(a.batch * kf_stride, pcvk::CV_GRID_CAP)),
                      dim3((unsigned)std::min<size_t>(keys, pcvk::CV_THREADS)), keys * sizeof(uint64_t), c->stream, a);
   return launch_ok(c, "k_covis_rows");
+}
+
+// ---- the map points' summaries: normal, distance range, representative descriptor ----------
+
+PISLAM_EXPORT int pislam_map_points_update_batch(pislam_ctx *c, const uint16_t *obs_kf, const int32_t *obs_pt,
+                                                 const int32_t *counts, const int32_t *kf_counts, const uint8_t *obs_level,
+                                                 const uint32_t *obs_desc, const float *poses, const float *xw,
+                                                 const uint32_t *pt_counts, const uint16_t *ref, const float *level_scale,
+                                                 int nlevels, size_t kf_stride, size_t stride, size_t pt_stride, int batch,
+                                                 float *normal, float *drange, uint32_t *desc, int32_t *nobs, int32_t *first,
+                                                 uint8_t *pt_status, int32_t *status) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!level_scale || nlevels < 1 || nlevels > pmu::MAX_LEVELS)
+    return fail(c, PISLAM_ERR_INVALID, "level_scale needs 1..16 entries");
+  for (int l = 0; l < nlevels; l++) {
+    if (!(level_scale[l] > 0.0f) || !psm::finite_f(level_scale[l]))
+      return fail(c, PISLAM_ERR_INVALID, "level_scale must be finite and > 0");
+    if (l > 0 && level_scale[l] < level_scale[l - 1]) return fail(c, PISLAM_ERR_INVALID, "level_scale must not decrease");
+  }
+  PCHK(covis_shape(c, kf_stride, stride, batch));
+  if (pt_stride < 1 || pt_stride > 0x7fffffffu) return fail(c, PISLAM_ERR_INVALID, "pt_stride must be 1..2^31 - 1");
+  if (batch == 0) return PISLAM_OK;
+  const char *what = "the map-point update takes device pointers only";
+  PCHK(device_ptrs(c, {obs_kf, obs_pt, counts, kf_counts, obs_level, poses, xw, pt_counts, nobs, pt_status, status}, what));
+  for (const void *opt : {(const void *)obs_desc, (const void *)ref, (const void *)normal, (const void *)drange,
+                          (const void *)desc, (const void *)first})
+    if (opt && !is_device_ptr(opt)) return fail(c, PISLAM_ERR_INVALID, what);
+  if (desc && !obs_desc) return fail(c, PISLAM_ERR_INVALID, "desc needs obs_desc");
+  {
+    const size_t B = (size_t)batch, word = B * sizeof(int32_t), pts = B * pt_stride;
+    const size_t words = pmu::WORDS * sizeof(uint32_t);
+    const LkRange in[] = {{obs_kf, B * stride * sizeof(uint16_t)}, {obs_pt, B * stride * sizeof(int32_t)}, {counts, word},
+                          {kf_counts, word}, {obs_level, B * stride}, {obs_desc, B * stride * words},
+                          {poses, B * kf_stride * 12 * sizeof(float)}, {xw, pts * 3 * sizeof(float)}, {pt_counts, word},
+                          {ref, pts * sizeof(uint16_t)}};
+    const LkRange out[] = {{normal, pts * 3 * sizeof(float)}, {drange, pts * 2 * sizeof(float)}, {desc, pts * words},
+                           {nobs, pts * sizeof(int32_t)}, {first, pts * sizeof(int32_t)}, {pt_status, pts}, {status, word}};
+    if (const char *bad = ranges_overlap(in, out)) return fail(c, PISLAM_ERR_INVALID, bad);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  pmuk::MuArgs a{};
+  a.obs_pt = obs_pt, a.counts = counts, a.kf_counts = kf_counts, a.obs_kf = obs_kf, a.ref = ref, a.obs_level = obs_level;
+  a.obs_desc = obs_desc, a.pt_counts = pt_counts, a.poses = poses, a.xw = xw;
+  a.kf_stride = kf_stride, a.stride = stride, a.pt_stride = pt_stride, a.batch = (size_t)batch;
+  a.tab.nlevels = nlevels;
+  for (int l = 0; l < pmu::MAX_LEVELS; l++) a.tab.level_scale[l] = l < nlevels ? level_scale[l] : 0.0f;
+  a.normal = normal, a.drange = drange, a.desc = desc, a.nobs = nobs, a.first = first, a.status = status, a.pt_status = pt_status;
+  // status[b] is the map's flag between the kernels: zero, then 3 from whoever finds the map malformed
+  HIPCHK(c, hipMemsetAsync(status, 0, a.batch * sizeof(int32_t), c->stream));
+  const auto grid = [](size_t groups) { return dim3((unsigned)std::min<size_t>(groups, pmuk::MU_GRID_CAP)); };
+  hipLaunchKernelGGL(pmuk::k_mapupdate_check, grid((a.batch * stride + pmuk::MU_THREADS - 1) / pmuk::MU_THREADS),
+                     dim3(pmuk::MU_THREADS), 0, c->stream, a);
+  PCHK(launch_ok(c, "k_mapupdate_check"));
+  const size_t waves = a.batch * ((pt_stride + pmuk::MU_CHUNK - 1) / pmuk::MU_CHUNK);
+  hipLaunchKernelGGL(pmuk::k_mapupdate_points, grid((waves + pmuk::MU_WAVES - 1) / pmuk::MU_WAVES), dim3(pmuk::MU_THREADS), 0,
+                     c->stream, a);
+  PCHK(launch_ok(c, "k_mapupdate_points"));
+  if (!desc) return PISLAM_OK;
+  hipLaunchKernelGGL(pmuk::k_mapupdate_long, grid(a.batch * ((pt_stride + pmuk::MU_THREADS - 1) / pmuk::MU_THREADS)),
+                     dim3(pmuk::MU_THREADS), 0, c->stream, a);
+  return launch_ok(c, "k_mapupdate_long");
 }
 
 // ---- bag of words: integer weights and the key-frame database -----------------------------

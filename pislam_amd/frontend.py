@@ -528,7 +528,8 @@ def fuseDecisions(sel, qid, tpoint, nobs):
     slot as in sel.  Torch ops on the current torch stream.
     With the caller stay: applying the decisions to the map, in batch order (a point dropped in frame b may be the
     keep of a later frame: follow the chain of replacements across key frames, as ORB-SLAM's GetReplaced does), and
-    descriptor / normal updates of the kept points.  With unique=0 in the selection several queries may share one
+    descriptor / normal updates of the kept points (mapPointsUpdateBatch on the edited map; its nobs is this function's
+    nobs for the next round).  With unique=0 in the selection several queries may share one
     keypoint; each gets its decision against the state passed in, not against the others' outcome."""
     import torch
     sel_q, sel_t, nsel = sel
@@ -2090,6 +2091,111 @@ def essentialPairs(nb_idx, nb_weight, nb_count, parent, kf_counts, min_weight=10
         links = torch.stack([code // 65536, code % 65536], dim=1)
         out.append(torch.cat([tree, links]).to(torch.int32))
     return out
+
+
+# ---- the map points' summaries: normal, distance range, representative descriptor ----------
+MAP_POINT_STATUS = ("ok", "no observers", "reference replaced", "geometry", "no level")
+
+
+def observationDescriptors(desc, obs_kf, obs_kp, counts):
+    """The obs_desc of mapPointsUpdateBatch from the key frames' own descriptor tensors: desc 32-bit words
+    [batch][kf_stride][kp_stride][8] (the front end's descriptors of every key frame of the map), obs_kf integer
+    [batch][stride] (mapObservations' output: 16-bit words read unsigned) and obs_kp integer [batch][stride] (the index of
+    the observation's keypoint in its key frame; pass it to mapObservations as a further tensor so that it is sorted
+    alike), counts [batch].  Slot i < counts[b] gets desc[b][obs_kf[b][i]][obs_kp[b][i]]; the slots at and beyond
+    counts[b] may hold unwritten memory: they are masked before gathering and come out as zeros.  Returns a tensor
+    [batch][stride][8] of desc's dtype.  Torch ops on the current torch stream."""
+    import torch
+    if desc.dim() != 4 or int(desc.shape[3]) != 8 or desc.dtype not in _word32():
+        raise ValueError("desc must be a 32-bit integer tensor [batch][kf_stride][kp_stride][8]")
+    batch, ks, kps = (int(v) for v in desc.shape[:3])
+    if obs_kf.dim() != 2 or int(obs_kf.shape[0]) != batch or tuple(obs_kp.shape) != tuple(obs_kf.shape):
+        raise ValueError("obs_kf and obs_kp must be [batch][stride]")
+    if tuple(counts.shape) != (batch,):
+        raise ValueError("counts must be [batch]")
+    stride = int(obs_kf.shape[1])
+    live = torch.arange(stride, device=obs_kf.device)[None, :] < counts.to(torch.int64)[:, None]
+    zero = torch.zeros_like(live, dtype=torch.int64)
+    unsigned = 0xFFFF if obs_kf.dtype in _word16() else -1
+    kf = torch.where(live, obs_kf.to(torch.int64) & unsigned, zero).clamp(0, ks - 1)
+    kp = torch.where(live, obs_kp.to(torch.int64), zero).clamp(0, kps - 1)
+    rows = desc.reshape(batch, ks * kps, 8).view(torch.int32)
+    got = torch.gather(rows, 1, (kf * kps + kp)[..., None].expand(-1, -1, 8))
+    return torch.where(live[..., None], got, torch.zeros_like(got)).view(desc.dtype).contiguous()
+
+
+def mapPointsUpdateBatch(obs_kf, obs_pt, counts, kf_counts, obs_level, poses, xw, pt_counts, *, obs_desc=None, ref=None,
+                         level_scale=None, nlevels=8, scale=1.2, want_normal=True, want_drange=True, want_first=True,
+                         normal=None, drange=None, desc=None, nobs=None, first=None, pt_status=None, status=None,
+                         ctx: Context | None = None):
+    """Batched refresh of the map points' summaries (pislam_map_points_update_batch; the contract is the comment in
+    include/pislam_hip.h), ORB-SLAM's MapPoint::UpdateNormalAndDepth and ComputeDistinctiveDescriptors for every point of
+    a map at once: what matchProjectionBatch and matchFuseBatch read of a map point (normal, drange, qdesc) and the nobs
+    of fuseDecisions, after triangulateBatch, a fusion, localBundleAdjustBatch or correctMapPointsBatch changed the map.
+    Per map: obs_kf int16 or uint16 and obs_pt 32-bit integers [batch][stride], the first counts[b] entries strictly
+    ascending in (obs_pt, obs_kf), and obs_level uint8 [batch][stride] (mapObservations makes all three); counts and
+    kf_counts [batch]; poses float32 [batch][kf_stride][12] (R row-major, then t; Xc = R Xw + t); xw float32
+    [batch][pt_stride][3]; pt_counts [batch]; obs_desc 32-bit words [batch][stride][8] or None (observationDescriptors
+    makes it; None: no descriptor is chosen); ref int16 or uint16 [batch][pt_stride] or None (each point's reference key
+    frame, correctMapPointsBatch's; None: the first observer).  level_scale: a HOST sequence of 1..16 float32 (default:
+    mapPointLevelTables(nlevels, scale)[0]).  Returns (normal float32 [batch][pt_stride][3]: the unit mean viewing
+    direction; drange float32 [batch][pt_stride][2]; desc [batch][pt_stride][8] of obs_desc's dtype, None without
+    obs_desc: the observer's descriptor with the least median distance to the others; nobs int32 [batch][pt_stride];
+    first int32 [batch][pt_stride]: the list index of the point's first observation or -1; pt_status uint8
+    [batch][pt_stride] (MAP_POINT_STATUS names the codes); status int32 [batch]: 0 ok, 1 nothing to do, 3 malformed).
+    normal, drange and first are None when not wanted and not passed.  Points at and beyond pt_counts[b] are not
+    written; a point without observers keeps its normal, drange and desc.  Numpy inputs go to the current device.  The
+    same inputs give the same outputs, bit for bit.  Asynchronous on the ctx stream, no workspace: capturable as it
+    is."""
+    import torch
+    ctx = ctx or default_context()
+    obs_kf, obs_pt, counts, kf_counts, obs_level, poses, xw, pt_counts, obs_desc, ref = (
+        _on_device(a) for a in (obs_kf, obs_pt, counts, kf_counts, obs_level, poses, xw, pt_counts, obs_desc, ref))
+    batch, stride = _tensor(obs_pt, _word32(), (None, None), "obs_pt must be a 32-bit integer tensor [batch][stride]")
+    _tensor(obs_kf, _word16(), (batch, stride), "obs_kf must be a 16-bit integer tensor [batch][stride]")
+    _tensor(obs_level, torch.uint8, (batch, stride), "obs_level must be a uint8 tensor [batch][stride]")
+    kf_stride, = _tensor(poses, torch.float32, (batch, None, 12), "poses must be a float32 tensor [batch][kf_stride][12]")
+    if not 1 <= kf_stride <= COVIS_MAX_KF:
+        raise ValueError(f"kf_stride must be 1..{COVIS_MAX_KF}")
+    pts, = _tensor(xw, torch.float32, (batch, None, 3), "xw must be a float32 tensor [batch][pt_stride][3]")
+    _counts("counts, kf_counts and pt_counts must be 32-bit integer tensors [batch]", batch, counts, kf_counts, pt_counts)
+    if obs_desc is not None:
+        _tensor(obs_desc, _word32(), (batch, stride, 8), "obs_desc must be a 32-bit integer tensor [batch][stride][8]")
+    if ref is not None:
+        _tensor(ref, _word16(), (batch, pts), "ref must be a 16-bit integer tensor [batch][pt_stride]")
+    if desc is not None and obs_desc is None:
+        raise ValueError("desc needs obs_desc")
+    if level_scale is None:
+        level_scale = mapPointLevelTables(nlevels, scale)[0]
+    tab, ntab = _float_table(level_scale, "level_scale must have 1..16 entries")
+    dev = obs_pt.device
+    new = lambda dtype, *shape: torch.empty(shape, dtype=dtype, device=dev)
+    normal = new(torch.float32, batch, pts, 3) if normal is None and want_normal else normal
+    drange = new(torch.float32, batch, pts, 2) if drange is None and want_drange else drange
+    first = new(torch.int32, batch, pts) if first is None and want_first else first
+    desc = new(obs_desc.dtype, batch, pts, 8) if desc is None and obs_desc is not None else desc
+    nobs = new(torch.int32, batch, pts) if nobs is None else nobs
+    pt_status = new(torch.uint8, batch, pts) if pt_status is None else pt_status
+    status = new(torch.int32, batch) if status is None else status
+    if normal is not None:
+        _tensor(normal, torch.float32, (batch, pts, 3), "normal must be a float32 tensor [batch][pt_stride][3]")
+    if drange is not None:
+        _tensor(drange, torch.float32, (batch, pts, 2), "drange must be a float32 tensor [batch][pt_stride][2]")
+    if desc is not None:
+        _tensor(desc, _word32(), (batch, pts, 8), "desc must be a 32-bit integer tensor [batch][pt_stride][8]")
+    for t in (nobs, first):
+        if t is not None:
+            _tensor(t, _word32(), (batch, pts), "nobs and first must be 32-bit integer tensors [batch][pt_stride]")
+    _tensor(pt_status, torch.uint8, (batch, pts), "pt_status must be a uint8 tensor [batch][pt_stride]")
+    _counts("status must be a 32-bit integer tensor [batch]", batch, status)
+    _contiguous(obs_kf, obs_pt, counts, kf_counts, obs_level, poses, xw, pt_counts, obs_desc, ref)
+    _contiguous(normal, drange, desc, nobs, first, pt_status, status, message="outputs must be contiguous")
+    ctx.check(ctx.lib.pislam_map_points_update_batch(ctx.h, ptr(obs_kf), ptr(obs_pt), ptr(counts), ptr(kf_counts),
+                                                     ptr(obs_level), ptr(obs_desc), ptr(poses), ptr(xw), ptr(pt_counts),
+                                                     ptr(ref), tab, ntab, kf_stride, stride, pts, batch, ptr(normal),
+                                                     ptr(drange), ptr(desc), ptr(nobs), ptr(first), ptr(pt_status),
+                                                     ptr(status)), "pislam_map_points_update_batch")
+    return normal, drange, desc, nobs, first, pt_status, status
 
 
 # ---- bag of words: integer weights and the key-frame database ----------
