@@ -2117,7 +2117,7 @@ int pislam_triangulate_batch(pislam_ctx *ctx, const pislam_triangulate_params *p
  * is walked by the same 1024 workgroups in passes.
  *
  * Not here: ORBmatcher::Fuse (pislam_match_fuse_batch, which runs before this call so that a landmark is optimised
- * once), global bundle adjustment and windows beyond the limits, marginalisation, IMU terms.  Which key frames form a
+ * once), marginalisation, IMU terms; windows beyond the limits and whole maps are pislam_global_ba_batch's, below.  Which key frames form a
  * window (the key frame, its covisible neighbours, the key frames that see their points) is read off
  * pislam_covisibility_batch, below. */
 typedef struct pislam_ba_params {
@@ -2242,8 +2242,8 @@ int pislam_local_ba_batch(pislam_ctx *ctx, const pislam_ba_params *p, const floa
  * launch, so a single large graph uses one compute unit; a batch above 1024 graphs is walked by the same 1024
  * workgroups in passes.
  *
- * Not here: a robust kernel, a several-workgroup form for one large graph, global bundle adjustment afterwards.  The
- * spanning-tree and covisibility edges of the graph come from pislam_covisibility_batch, below. */
+ * Not here: a robust kernel, a several-workgroup form for one large graph.  The bundle adjustment of the whole map that
+ * follows the correction is pislam_global_ba_batch, below.  The spanning-tree and covisibility edges of the graph come from pislam_covisibility_batch, below. */
 typedef struct pislam_pose_graph_params {
   int32_t iters;     /* 1..64 Levenberg iterations (ORB-SLAM: 20) */
   int32_t cg_iters;  /* 1..1024 conjugate-gradient iterations of a solve at the most */
@@ -2430,6 +2430,122 @@ int pislam_map_points_update_batch(pislam_ctx *ctx, const uint16_t *obs_kf, cons
                                    const float *level_scale, int nlevels, size_t kf_stride, size_t stride,
                                    size_t pt_stride, int batch, float *normal, float *drange, uint32_t *desc,
                                    int32_t *nobs, int32_t *first, uint8_t *pt_status, int32_t *status);
+
+/* ---- global bundle adjustment: a whole map across workgroups ---- */
+
+/* What ORB-SLAM's Optimizer::GlobalBundleAdjustemnt does, per MAP of a batch: all free key-frame
+ * poses and all map points of the map are moved together so that the robust reprojection error of every observation
+ * becomes minimal.  Levenberg on the Schur complement; the reduced camera system is never formed: it is solved
+ * matrix-free by block-Jacobi preconditioned conjugate gradients (PCG).  Every phase of one map is spread over many
+ * workgroups, one launch per phase.  The reference ships nothing of the kind: the semantics are this library's own.
+ * This comment is the contract.  It is pislam_local_ba_batch's contract with the differences stated here and no others:
+ * every +, -, *, / and sqrt is ONE binary32 or binary64 operation (as marked there and here) rounded to nearest even, in
+ * the order the parentheses give, NEVER fused into an FMA; a NaN fails every comparison.  tests/test_global_ba.py restates
+ * it in numpy; tools/probes/gba_host_check.cpp compiles the kernels' own arithmetic header (pislam_gba_math.h) for the
+ * host and runs a map serially, phase by phase in the order of the launches.
+ *
+ * Inputs, all device, read only.  The map is indexed exactly as pislam_covisibility_batch and
+ * pislam_map_points_update_batch index it: one observation list serves the three calls.  Map b has nk = kf_counts[b] key
+ * frames and n = counts[b] observations (SIGNED words, checked, not clamped) and npt = min(pt_counts[b], pt_stride) points
+ * (PISLAM_COUNT_INVALID counts as 0); entries at and beyond a count are never read.
+ *   obs_pt     int32 [batch][stride], obs_kf uint16 [batch][stride]: the first n entries STRICTLY ASCENDING in (obs_pt,
+ *              obs_kf), 0 <= obs_pt < npt, obs_kf < nk
+ *   obs_q8     int32 [batch][stride][3], level uint8 [batch][stride] or NULL, inv_sigma2 HOST float [nlevels]: read
+ *              exactly as pislam_local_ba_batch reads them
+ *   poses      float [batch][kf_stride][12], cams float [batch][kf_stride][5], xw float [batch][pt_stride][3]: as there
+ *   fixed      uint8 [batch][kf_stride]: nonzero = the key frame is held FIXED (ORB-SLAM holds key frame 0); the others are
+ *              FREE.  It replaces the local call's "first kf_free", so that key-frame indices stay the map's own.
+ *   kf_ptr     uint32 [batch][kf_stride + 1], kf_obs uint32 [batch][stride]: the key-frame side of the list.  The ENTRIES of
+ *              key frame k are the observation indices kf_obs[kf_ptr[k] .. kf_ptr[k+1]).  The index is CONSISTENT iff
+ *              kf_ptr[0] == 0, kf_ptr[k] <= kf_ptr[k+1] <= n, kf_ptr[nk] == n, every entry of k is an index < n of an
+ *              observation whose obs_kf is k, and the entries of a key frame are strictly ascending.  Then every
+ *              observation is an entry of exactly one key frame.  (frontend.keyFrameObservationIndex builds it.)
+ *
+ * One observation, a PASS, the per-point sums V_p, g_p and (rho_p, n_p, c_p) over the point's contiguous observations in
+ * ascending index, the sums S = (F, S_1, S_2) over the points (256 partials by p mod 256, then halving), the point blocks
+ * at s = 1.0 + lambda with the HELD rule and Sol_p, the retraction, the Levenberg rule of a ROUND, the rounds and the
+ * CLASSIFYING passes: pislam_local_ba_batch's, word for word, with "free" read off `fixed`.  The terms W (6 x 3) and the
+ * 27 camera terms of a contributing observation of a free key frame are kept as binary32 words.
+ *
+ * Per-key-frame sums.  Every sum over a key frame's entries is a 64-PARTIAL SUM: partial q = 0..63 starts at +0.0 and
+ * takes the entries at the places q, q + 64, q + 128, .. of the key frame's list in ascending order, only those that
+ * qualify as stated with the sum; then the partials are combined by halving: p[q] = p[q] + p[q + h] for q < h, h = 32,
+ * 16, .. 1; the sum is p[0].  An entry o TAKES PART iff it contributes (pislam_local_ba_batch's term) and its point is
+ * not held.  Dot products of 6-vectors are ((((a0*b0 + a1*b1) + a2*b2) + a3*b3) + a4*b4) + a5*b5.  A sum over the
+ * KEY FRAMES: 256 partial sums from +0.0, partial k mod 256 takes its free key frames in ascending k, then halving
+ * (128, 64, .. 1) as for S.
+ *
+ * A SOLVE at lambda, binary64, s = 1.0 + lambda.
+ *   Point blocks, HELD, Sol_p: the local call's.
+ *   Per free key frame k (the SET-UP):
+ *     H_k (21, upper triangle row by row), g_k (6): 64-partial sums of double(term) over the contributing entries.
+ *     H'_k = H_k with each diagonal entry times s.
+ *     For an entry o that takes part, with its point p: Y_a = Sol_p(double(W_a0), double(W_a1), double(W_a2)), a = 0..5.
+ *     E_ab (a <= b) = the 64-partial sum over the entries that take part of ((Y_a0*w_b0 + Y_a1*w_b1) + Y_a2*w_b2), w =
+ *     double(W);  e_a = the 64-partial sum over the same entries of ((Y_a0*g0 + Y_a1*g1) + Y_a2*g2), g = g_p.
+ *     The preconditioner block S_kk = H'_k - E (entry by entry, one subtraction) is eliminated WITHOUT pivoting exactly
+ *     as the pose call's solve (f = A[r][c]/A[c][c]; A[r][j] = A[r][j] - f*A[c][j] for j > c); the solve FAILS unless
+ *     every pivot is > 0, which is what a free key frame without a contributing observation does.  Sol_k(b): b_r = b_r -
+ *     f_rc*b_c for c ascending, r > c ascending; x_r = (b_r - A_r,r+1*x_r+1 - .. - A_r5*x_5)/A_rr for r = 5 .. 0.
+ *     rhs_k,a = (-g_k,a) + e_a.   Start: x_k = 0, r_k = rhs_k, z_k = Sol_k(r_k), p_k = z_k.
+ *   rz = the key-frame sum of r_k . z_k;  thr = (cg_tol*cg_tol)*rz.
+ *   PCG iteration n = 0 .. cg_iters - 1: stop if rz <= thr.
+ *     Per point p (one owner): t_p,j starts at +0.0; over the point's contributing observations of free key frames k in
+ *     ascending index, with e = p_k:  t_j = t_j + (((((w_0j*e0 + w_1j*e1) + w_2j*e2) + w_3j*e3) + w_4j*e4) + w_5j*e5), w
+ *     = double(W);  q_p = Sol_p(t_p), and q_p = 0 if the point is held.
+ *     Per free key frame: (S p)_k,a = (the dot product of row a of H'_k with p_k) - the 64-partial sum over the entries
+ *     that take part of ((w_a0*q0 + w_a1*q1) + w_a2*q2), q = q_p of the entry's point.
+ *     pAp = the key-frame sum of p_k . (S p)_k; the solve FAILS unless pAp > 0.  alpha = rz/pAp; x_k = x_k + alpha*p_k;
+ *     r_k = r_k - alpha*(S p)_k; z_k = Sol_k(r_k); rz' = the key-frame sum of r_k . z_k; beta = rz'/rz; p_k = z_k +
+ *     beta*p_k; rz = rz'.   (The pose graph call's scalars in its order.)
+ *   d_k = x_k.  Points: the local call's dp with e = d_k.  The solve fails as well when a word of d or of a dp is not
+ *   finite.  dmax = the largest |word| of d and of all dp (a maximum: its order is free).  Trial state: as there.
+ *
+ * Per map.  Refused on the device, in this order: code 3 (structure): n outside [0, stride], nk outside [0, kf_stride],
+ * an obs_kf >= nk, an obs_pt outside [0, npt), a list that is not strictly ascending, or an inconsistent kf_obs index;
+ * code 2: a word of poses or cams below nk, or of xw below npt, is not finite; code 1: n < min_obs, or no free key
+ * frame.  Otherwise the rounds run as in the local call.
+ *
+ * Outputs, in-place rules (poses_out may be exactly poses, xw_out exactly xw), what a refused map writes and status =
+ * code | evaluations << 8: the local call's.  work uint32 [batch][2] or NULL: (the solves begun, the PCG iterations of
+ * all of them).  Entries at and beyond a count are never written.
+ *
+ * Limits: p->ba as in its struct comments, except min_obs 1..2^24; cg_iters 1..256, cg_tol in [0, 1); 1 <= kf_stride <=
+ * 4096 (the limit of pislam_pose_graph_batch and pislam_covisibility_batch), 1 <= pt_stride <= 2^22, 1 <= stride <= 2^24;
+ * batch >= 0 (batch == 0 is a no-op that returns PISLAM_OK after the checks of p, the table and the shape); offsets use
+ * size_t arithmetic.  Any violation, or a NULL or host pointer where a device pointer is required (level and work alone
+ * may be NULL), or a forbidden overlap: PISLAM_ERR_INVALID, before anything is launched or written.  `p` and inv_sigma2
+ * are host memory, read during the call.  The workspace belongs to the context: per map a control block of 256 bytes and
+ * 362 bytes per observation of stride, 317 per point of pt_stride and 992 per key frame of kf_stride (each array rounded
+ * up to 16 bytes, the slice to 256: 6.9 GiB for one map at the limits, which is what bounds them); it grows on demand,
+ * which synchronises; a size the device refuses is PISLAM_ERR_NOMEM.  After pislam_global_ba_reserve of the same or a
+ * larger shape the call allocates nothing and never synchronises, so it can be captured into a hipGraph.
+ *
+ * Launches.  Asynchronous on the context stream.  The host issues a FIXED sequence from the parameters alone and reads
+ * nothing back: one memset of the control blocks, then 7 + the sum over the rounds r of (iters[r] * (6 + 3 * cg_iters) +
+ * 2) launches (at most 99 087; ORB-SLAM's schedule, rounds 1, iters {10}, with cg_iters 50: 1569).  Per Levenberg
+ * iteration: the point factors, the key-frame set-up, the PCG start; per PCG iteration the points, the key frames, the
+ * scalars; then the step, the pass, the decision.  Launch order is the only synchronisation between workgroups: no
+ * cooperative launch, no grid-wide wait, no polling.  A workgroup whose map is refused, finished, converged (dmax <=
+ * eps ends the round; rz <= thr ends the solve) returns at once from the map's control block.  The number of workgroups
+ * of a launch follows the strides (points, observations or key frames of every map), not only the batch.
+ *
+ * Not here: propagating the result to key frames and points outside the map (the caller's, as in ORB-SLAM),
+ * marginalisation, IMU terms.  ORB-SLAM's schedule is rounds 1, iters {10} (20 at map initialisation), huber_rounds 1; the
+ * closing classification gives the inlier mask that ORB-SLAM does not compute. */
+typedef struct pislam_gba_params {
+  pislam_ba_params ba; /* as in pislam_local_ba_batch; min_obs 1..2^24 */
+  int32_t cg_iters;    /* 1..256 conjugate-gradient iterations of a solve at the most */
+  double cg_tol;       /* in [0, 1): a solve stops when r'z <= cg_tol^2 times its first value */
+} pislam_gba_params;
+int pislam_global_ba_reserve(pislam_ctx *ctx, size_t kf_stride, size_t pt_stride, size_t stride, int batch);
+int pislam_global_ba_batch(pislam_ctx *ctx, const pislam_gba_params *p, const float *poses, const float *cams,
+                           const uint8_t *fixed, const int32_t *kf_counts, const float *xw, const uint32_t *pt_counts,
+                           const int32_t *obs_q8, const uint16_t *obs_kf, const int32_t *obs_pt, const uint8_t *level,
+                           const int32_t *counts, const uint32_t *kf_ptr, const uint32_t *kf_obs, const float *inv_sigma2,
+                           int nlevels, size_t kf_stride, size_t pt_stride, size_t stride, int batch, float *poses_out,
+                           float *xw_out, uint8_t *inlier, uint32_t *ninliers, double *cost, uint32_t *status,
+                           uint32_t *work);
 
 /* ---- multi-GPU: one process per GPU, pyramids sharded, ONE collective ---- */
 

@@ -66,6 +66,10 @@ class BaParams(ctypes.Structure):
                 ("min_obs", ctypes.c_int32), ("eps", ctypes.c_double)]
 
 
+class GbaParams(ctypes.Structure):
+    _fields_ = [("ba", BaParams), ("cg_iters", ctypes.c_int32), ("cg_tol", ctypes.c_double)]
+
+
 class PoseGraphParams(ctypes.Structure):
     _fields_ = [("iters", ctypes.c_int32), ("cg_iters", ctypes.c_int32), ("cg_tol", ctypes.c_double),
                 ("eps", ctypes.c_double)]
@@ -234,6 +238,10 @@ SYMBOLS = {
     "pislam_map_points_update_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             ctypes.POINTER(ctypes.c_float), _i, _sz, _sz, _sz, _i, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp]),
+    "pislam_global_ba_reserve": (_i, [_vp, _sz, _sz, _sz, _i]),
+    "pislam_global_ba_batch": (_i, [_vp, ctypes.POINTER(GbaParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, ctypes.POINTER(ctypes.c_float), _i, _sz, _sz, _sz, _i, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp]),
     "pislam_pnp_ransac_batch": (_i, [_vp, ctypes.POINTER(PnpParams), _vp, _vp, _vp, _vp, _vp,
                                      ctypes.POINTER(ctypes.c_float), _i, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pislam_sim3_ransac_batch": (_i, [_vp, ctypes.POINTER(Sim3Params), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -70,6 +70,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_mappoint_kernels.h"
 #include "pislam_ba_kernels.h"
 #include "pislam_graph_kernels.h"
+#include "pislam_gba_kernels.h"
 #include "pislam_covis_kernels.h"
 #include "pislam_mapupdate_kernels.h"
 #include "pislam_warp_kernels.h"
@@ -141,6 +142,7 @@ struct pislam_ctx {
   CellIndex w_epi;                   // epipolar matcher (pe::k_epi_index): group offsets, group-sorted entries with their geometry (meta), descriptors
   DevBuf w_ba;                       // local bundle adjustment (pbk::k_local_ba): a slice per workgroup (pbk::ws_bytes)
   DevBuf w_pg;                       // essential-graph optimisation (pgk::k_pose_graph): a slice per workgroup (pgr::ws_bytes)
+  DevBuf w_gba;                      // global bundle adjustment (gbk::k_gba_*): a control block and a slice per map (gba::ws_bytes)
   DevBuf w_cv;                       // covisibility graph (pcvk::k_covis_count, k_covis_rows): matrices, counters, flags (pcv::ws_bytes)
   DevBuf w_db;                       // key-frame database query (pd::k_db_accumulate .. k_db_merge): accumulator planes, maxima, partial lists
   // Host-built plan tables the kernels read instead of walking the plan (the bucket selection pass's unit table): one
@@ -522,6 +524,7 @@ PISLAM_EXPORT int pislam_ctx_destroy(pislam_ctx *c) {
   c->w_db.release();
   c->w_ba.release();
   c->w_pg.release();
+  c->w_gba.release();
   c->w_cv.release();
   for (auto *t : c->plan_tables) {
     t->dev.release();
@@ -3352,6 +3355,130 @@ PISLAM_EXPORT int pislam_map_points_update_batch(pislam_ctx *c, const uint16_t *
   hipLaunchKernelGGL(pmuk::k_mapupdate_long, grid(a.batch * ((pt_stride + pmuk::MU_THREADS - 1) / pmuk::MU_THREADS)),
                      dim3(pmuk::MU_THREADS), 0, c->stream, a);
   return launch_ok(c, "k_mapupdate_long");
+}
+
+// ---- global bundle adjustment of whole maps across workgroups ---------------------------------
+
+namespace {
+
+int global_ba_shape(pislam_ctx *c, size_t kf_stride, size_t pt_stride, size_t stride, int batch) {
+  if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
+  if (kf_stride < 1 || kf_stride > (size_t)gba::MAX_KF) return fail(c, PISLAM_ERR_INVALID, "kf_stride must be 1..4096");
+  if (pt_stride < 1 || pt_stride > gba::MAX_PTS) return fail(c, PISLAM_ERR_INVALID, "pt_stride must be 1..2^22");
+  if (stride < 1 || stride > gba::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "stride must be 1..2^24");
+  return PISLAM_OK;
+}
+
+int global_ba_workspace(pislam_ctx *c, size_t kf_stride, size_t pt_stride, size_t stride, int batch, size_t *per_map) {
+  *per_map = gba::ws_bytes(kf_stride, pt_stride, stride);
+  if (*per_map + gba::CTL_BYTES > SIZE_MAX / (size_t)batch) return fail(c, PISLAM_ERR_NOMEM, "the global bundle adjustment workspace");
+  if (c->w_gba.ensure((*per_map + gba::CTL_BYTES) * (size_t)batch) != PISLAM_OK)
+    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(global bundle adjustment workspace)");
+  return PISLAM_OK;
+}
+
+}  // namespace
+
+PISLAM_EXPORT int pislam_global_ba_reserve(pislam_ctx *c, size_t kf_stride, size_t pt_stride, size_t stride, int batch) {
+  if (!c) return PISLAM_ERR_INVALID;
+  PCHK(global_ba_shape(c, kf_stride, pt_stride, stride, batch));
+  if (batch == 0) return PISLAM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  size_t per_map;
+  return global_ba_workspace(c, kf_stride, pt_stride, stride, batch, &per_map);
+}
+
+PISLAM_EXPORT int pislam_global_ba_batch(pislam_ctx *c, const pislam_gba_params *p, const float *poses, const float *cams,
+                                         const uint8_t *fixed, const int32_t *kf_counts, const float *xw,
+                                         const uint32_t *pt_counts, const int32_t *obs_q8, const uint16_t *obs_kf,
+                                         const int32_t *obs_pt, const uint8_t *level, const int32_t *counts,
+                                         const uint32_t *kf_ptr, const uint32_t *kf_obs, const float *inv_sigma2, int nlevels,
+                                         size_t kf_stride, size_t pt_stride, size_t stride, int batch, float *poses_out,
+                                         float *xw_out, uint8_t *inlier, uint32_t *ninliers, double *cost, uint32_t *status,
+                                         uint32_t *work) {
+  if (!c) return PISLAM_ERR_INVALID;
+  if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
+  const pislam_ba_params &q = p->ba;
+  if (q.rounds < 1 || q.rounds > gba::MAX_ROUNDS) return fail(c, PISLAM_ERR_INVALID, "rounds must be 1..4");
+  for (int r = 0; r < q.rounds; r++)
+    if (q.iters[r] < 1 || q.iters[r] > gba::MAX_ITERS) return fail(c, PISLAM_ERR_INVALID, "iters must be 1..32");
+  if (q.huber_rounds < 0 || q.huber_rounds > q.rounds) return fail(c, PISLAM_ERR_INVALID, "huber_rounds must be 0..rounds");
+  if (q.min_obs < 1 || (size_t)q.min_obs > gba::MAX_STRIDE) return fail(c, PISLAM_ERR_INVALID, "min_obs must be 1..2^24");
+  PCHK(check_refine_eps(c, q.eps));
+  if (p->cg_iters < 1 || p->cg_iters > gba::MAX_CG) return fail(c, PISLAM_ERR_INVALID, "cg_iters must be 1..256");
+  if (!(p->cg_tol >= 0.0 && p->cg_tol < 1.0)) return fail(c, PISLAM_ERR_INVALID, "cg_tol must be in [0, 1)");
+  if (level) PCHK(check_level_table(c, "level needs", inv_sigma2, nlevels));
+  PCHK(global_ba_shape(c, kf_stride, pt_stride, stride, batch));
+  if (batch == 0) return PISLAM_OK;
+  const char *what = "the global bundle adjustment takes device pointers only";
+  PCHK(device_ptrs(c, {poses, cams, fixed, kf_counts, xw, pt_counts, obs_q8, obs_kf, obs_pt, counts, kf_ptr, kf_obs, poses_out,
+                       xw_out, inlier, ninliers, cost, status}, what));
+  if ((level && !is_device_ptr(level)) || (work && !is_device_ptr(work))) return fail(c, PISLAM_ERR_INVALID, what);
+  {
+    const size_t B = (size_t)batch, word = B * sizeof(uint32_t), pose = B * kf_stride * 12 * sizeof(float);
+    const size_t pts = B * pt_stride * 3 * sizeof(float);
+    const LkRange in[] = {{poses, pose}, {xw, pts}, {cams, B * kf_stride * 5 * sizeof(float)}, {fixed, B * kf_stride},
+                          {kf_counts, word}, {pt_counts, word}, {obs_q8, B * stride * 3 * sizeof(int32_t)},
+                          {obs_kf, B * stride * sizeof(uint16_t)}, {obs_pt, B * stride * sizeof(int32_t)}, {level, B * stride},
+                          {counts, word}, {kf_ptr, B * (kf_stride + 1) * sizeof(uint32_t)}, {kf_obs, B * stride * sizeof(uint32_t)}};
+    const LkRange out[] = {{poses_out, pose}, {xw_out, pts}, {inlier, B * stride}, {ninliers, word},
+                           {cost, B * sizeof(double)}, {status, word}, {work, 2 * word}};
+    // poses_out == poses and xw_out == xw are allowed: the state is read into the workspace before anything is written
+    for (size_t o = 0; o < sizeof(out) / sizeof(out[0]); o++) {
+      for (size_t i = 0; i < sizeof(in) / sizeof(in[0]); i++) {
+        if (o < 2 && i == o && out[o].p == in[i].p) continue;
+        if (lk_overlap(out[o], in[i])) return fail(c, PISLAM_ERR_INVALID, "an output overlaps an input");
+      }
+      for (size_t k = 0; k < o; k++)
+        if (lk_overlap(out[o], out[k])) return fail(c, PISLAM_ERR_INVALID, "two outputs overlap");
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  gbk::GbaArgs a{};
+  PCHK(global_ba_workspace(c, kf_stride, pt_stride, stride, batch, &a.ws_map));
+  a.poses = poses, a.cams = cams, a.xw = xw, a.obs = obs_q8, a.obs_pt = obs_pt, a.counts = counts, a.kf_counts = kf_counts;
+  a.pt_counts = pt_counts, a.kf_ptr = kf_ptr, a.kf_obs = kf_obs, a.obs_kf = obs_kf, a.level = level, a.fixed = fixed;
+  a.kf_stride = kf_stride, a.pt_stride = pt_stride, a.stride = stride, a.batch = (size_t)batch;
+  copy_level_table(&a, inv_sigma2, level ? nlevels : 0);
+  a.p.ba = pba::Params{q.rounds, {q.iters[0], q.iters[1], q.iters[2], q.iters[3]}, q.huber_rounds, q.min_obs, q.eps};
+  a.p.cg_iters = p->cg_iters, a.p.cg_tol = p->cg_tol;
+  a.poses_out = poses_out, a.xw_out = xw_out, a.inlier = inlier, a.ninliers = ninliers, a.status = status, a.work = work;
+  a.cost = cost, a.ws = c->w_gba.as<char>();
+  // the control blocks start from zero: the checks only raise flags
+  HIPCHK(c, hipMemsetAsync(a.ws, 0, a.batch * gba::CTL_BYTES, c->stream));
+  const size_t K = kf_stride, P = pt_stride, N = stride, T = gbk::THREADS, W = gbk::WAVES;
+  int rc = PISLAM_OK;
+  auto run = [&](auto kernel, size_t per_map, size_t group, const char *name, auto... more) {
+    if (rc != PISLAM_OK) return;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)gbk::groups_of(a, per_map, group)), dim3(gbk::THREADS), 0, c->stream, a, more...);
+    rc = launch_ok(c, name);
+  };
+  // the fixed sequence of gba::launch_count(): nothing is read back, a map's control block gates every launch
+  run(gbk::k_gba_check_items, N + P, T, "k_gba_check_items");
+  run(gbk::k_gba_check_kf, K, W, "k_gba_check_kf");
+  run(gbk::k_gba_begin, 1, 1, "k_gba_begin");
+  run(gbk::k_gba_load, K + P + 1 + N, T, "k_gba_load");
+  run(gbk::k_gba_pass, P, T, "k_gba_pass", (int)gbk::FIRST, (int)(0 < q.huber_rounds));
+  run(gbk::k_gba_decide, 1, 1, "k_gba_decide", (int)gbk::FIRST, 0);
+  for (int r = 0; r < q.rounds; r++) {
+    for (int it = 0; it < q.iters[r]; it++) {
+      run(gbk::k_gba_factor, P, T, "k_gba_factor");
+      run(gbk::k_gba_kf_setup, K, W, "k_gba_kf_setup");
+      run(gbk::k_gba_cg_begin, 1, 1, "k_gba_cg_begin");
+      for (int n = 0; n < p->cg_iters; n++) {
+        run(gbk::k_gba_cg_point, P, T, "k_gba_cg_point");
+        run(gbk::k_gba_cg_kf, K, W, "k_gba_cg_kf");
+        run(gbk::k_gba_cg_scalar, 1, 1, "k_gba_cg_scalar");
+      }
+      run(gbk::k_gba_step, P + K, T, "k_gba_step");
+      run(gbk::k_gba_pass, P, T, "k_gba_pass", (int)gbk::TRIAL, (int)(r < q.huber_rounds));
+      run(gbk::k_gba_decide, 1, 1, "k_gba_decide", (int)gbk::TRIAL, r);
+    }
+    run(gbk::k_gba_pass, P, T, "k_gba_pass", (int)gbk::CLASSIFY, (int)(r + 1 < q.huber_rounds));
+    run(gbk::k_gba_decide, 1, 1, "k_gba_decide", (int)gbk::CLASSIFY, r);
+  }
+  run(gbk::k_gba_out, std::max(std::max(12 * K, 3 * P), N), T, "k_gba_out");
+  return rc;
 }
 
 // ---- bag of words: integer weights and the key-frame database -----------------------------

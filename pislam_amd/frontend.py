@@ -2198,6 +2198,104 @@ def mapPointsUpdateBatch(obs_kf, obs_pt, counts, kf_counts, obs_level, poses, xw
     return normal, drange, desc, nobs, first, pt_status, status
 
 
+# ---- global bundle adjustment of whole maps ---------------------------------
+GBA_MAX_KF, GBA_MAX_POINTS, GBA_MAX_STRIDE, GBA_MAX_CG = COVIS_MAX_KF, 1 << 22, 1 << 24, 256
+
+
+def keyFrameObservationIndex(obs_kf, counts, kf_stride: int):
+    """The key-frame side of a map's observation list, as globalBundleAdjustBatch reads it: obs_kf integer [batch][stride]
+    (mapObservations' words), counts [batch], kf_stride the key-frame extent of the map's tensors.  Returns (kf_ptr int32
+    [batch][kf_stride + 1], kf_obs int32 [batch][stride]): the observations of key frame k are kf_obs[kf_ptr[k] ..
+    kf_ptr[k + 1]), in ascending order (a stable sort by key frame); the key frames from the map's count on have empty
+    ranges, so kf_ptr[nk] is counts[b] for every nk beyond the last key frame observed.  An observation whose key frame is
+    not below kf_stride is left out (the call refuses such a map by itself).  Torch ops on the current torch stream."""
+    import torch
+    if obs_kf.dim() != 2 or tuple(counts.shape) != (obs_kf.shape[0],):
+        raise ValueError("obs_kf must be [batch][stride] and counts [batch]")
+    batch, stride = (int(v) for v in obs_kf.shape)
+    kf_stride = int(kf_stride)
+    if not 1 <= kf_stride <= GBA_MAX_KF:
+        raise ValueError(f"kf_stride must be 1..{GBA_MAX_KF}")
+    k = obs_kf.to(torch.int64) & 0xFFFF
+    n = counts.to(torch.int64).clamp(0, stride)
+    live = (torch.arange(stride, device=k.device)[None, :] < n[:, None]) & (k < kf_stride)
+    key = torch.where(live, k, torch.full_like(k, kf_stride))
+    kf_obs = torch.argsort(key, dim=1, stable=True).to(torch.int32).contiguous()
+    hist = torch.zeros((batch, kf_stride + 1), dtype=torch.int64, device=k.device)
+    hist.scatter_add_(1, key, torch.ones_like(key))
+    kf_ptr = torch.zeros((batch, kf_stride + 1), dtype=torch.int64, device=k.device)
+    kf_ptr[:, 1:] = torch.cumsum(hist[:, :kf_stride], dim=1)
+    return kf_ptr.to(torch.int32).contiguous(), kf_obs
+
+
+def reserveGlobalBundleAdjust(kf_stride: int, pt_stride: int, stride: int, batch: int, *, ctx: Context | None = None):
+    """Size the context's workspace for globalBundleAdjustBatch calls of up to this shape (pislam_global_ba_reserve; per
+    map 362 bytes per observation, 317 per point and 992 per key frame): afterwards such calls allocate nothing and never
+    synchronise, so they can be captured into a hipGraph."""
+    ctx = ctx or default_context()
+    ctx.check(ctx.lib.pislam_global_ba_reserve(ctx.h, int(kf_stride), int(pt_stride), int(stride), int(batch)),
+              "pislam_global_ba_reserve")
+
+
+def globalBundleAdjustBatch(poses, cams, fixed, kf_counts, xw, pt_counts, obs_q8, obs_kf, obs_pt, counts, kf_ptr, kf_obs, *,
+                            level=None, inv_sigma2=None, rounds=1, iters=(10,), huber_rounds=1, min_obs=10, eps=1e-6,
+                            cg_iters=50, cg_tol=1e-4, poses_out=None, xw_out=None, inlier=None, ninliers=None, cost=None,
+                            status=None, work=None, ctx: Context | None = None):
+    """Batched global bundle adjustment (pislam_global_ba_batch; the contract is the comment in include/pislam_hip.h):
+    per map, the poses of all key frames whose `fixed` byte is zero and all map points are moved together to minimise the
+    robust reprojection error of the observations.  Levenberg on the Schur complement, solved matrix-free by block-Jacobi
+    preconditioned conjugate gradients (at most cg_iters iterations of a solve, stopped at cg_tol); every phase of a map
+    runs across many workgroups.  poses float32 [batch][kf_stride][12] (kf_stride <= 4096), cams float32
+    [batch][kf_stride][5], fixed uint8 [batch][kf_stride], xw float32 [batch][pt_stride][3], obs_q8 int32
+    [batch][stride][3]; obs_kf (16-bit words), obs_pt (32-bit words), counts and kf_counts are covisibilityBatch's and
+    mapPointsUpdateBatch's observation list as it is (mapObservations makes it); kf_ptr [batch][kf_stride + 1] and kf_obs
+    [batch][stride] are keyFrameObservationIndex's; pt_counts [batch]; level and inv_sigma2 as in poseRefineBatch.  The
+    defaults are ORB-SLAM's schedule (one round of 10 iterations, robust; 20 at map initialisation).  Returns (poses_out,
+    xw_out, inlier uint8 [batch][stride], ninliers int32 [batch], cost float64 [batch], status int32 [batch] = code |
+    evaluations << 8; code 0 ok, 1 stopped for min_obs or no free key frame, 2 an input is not finite, 3 the map is
+    malformed, work int32 [batch][2] = (solves begun, conjugate-gradient iterations)).  poses_out may be `poses` and
+    xw_out may be `xw`.  The same inputs give the same outputs, bit for bit.  Asynchronous on the ctx stream; capturable
+    after reserveGlobalBundleAdjust."""
+    import torch
+    ctx = ctx or default_context()
+    batch, kfs = _tensor(poses, torch.float32, (None, None, 12), "poses must be a float32 tensor [batch][kf_stride][12]")
+    _tensor(cams, torch.float32, (batch, kfs, 5), "cams must be a float32 tensor [batch][kf_stride][5]")
+    _tensor(fixed, torch.uint8, (batch, kfs), "fixed must be a uint8 tensor [batch][kf_stride]")
+    pts, = _tensor(xw, torch.float32, (batch, None, 3), "xw must be a float32 tensor [batch][pt_stride][3]")
+    stride, = _tensor(obs_q8, torch.int32, (batch, None, 3), "obs_q8 must be an int32 tensor [batch][stride][3]")
+    _tensor(obs_kf, _word16(), (batch, stride), "obs_kf must be a 16-bit integer tensor [batch][stride]")
+    _tensor(obs_pt, _word32(), (batch, stride), "obs_pt must be a 32-bit integer tensor [batch][stride]")
+    _tensor(kf_ptr, _word32(), (batch, kfs + 1), "kf_ptr must be a 32-bit integer tensor [batch][kf_stride + 1]")
+    _tensor(kf_obs, _word32(), (batch, stride), "kf_obs must be a 32-bit integer tensor [batch][stride]")
+    if kfs > GBA_MAX_KF or pts > GBA_MAX_POINTS or stride > GBA_MAX_STRIDE:
+        raise ValueError(f"at most {GBA_MAX_KF} key frames, {GBA_MAX_POINTS} points and {GBA_MAX_STRIDE} observations per map")
+    _counts("kf_counts, pt_counts and counts must be 32-bit integer tensors [batch]", batch, kf_counts, pt_counts, counts)
+    tab, ntab = _level_table((level,), inv_sigma2, batch, stride, "level and inv_sigma2 go together",
+                             "level must be a uint8 tensor [batch][stride]")
+    _contiguous(poses, cams, fixed, kf_counts, xw, pt_counts, obs_q8, obs_kf, obs_pt, counts, kf_ptr, kf_obs, level)
+    its = [int(v) for v in (iters if hasattr(iters, "__len__") else [iters] * int(rounds))]
+    if len(its) < int(rounds) or len(its) > 4:
+        raise ValueError("iters needs an entry per round, at most 4")
+    if not 1 <= int(cg_iters) <= GBA_MAX_CG or not 0.0 <= float(cg_tol) < 1.0:
+        raise ValueError(f"cg_iters must be 1..{GBA_MAX_CG} and cg_tol in [0, 1)")
+    p = capi.GbaParams(capi.BaParams(int(rounds), (ctypes.c_int32 * 4)(*(its + [1] * (4 - len(its)))), int(huber_rounds),
+                                     int(min_obs), float(eps)), int(cg_iters), float(cg_tol))
+    dev = poses.device
+    poses_out = torch.empty_like(poses) if poses_out is None else poses_out
+    xw_out = torch.empty_like(xw) if xw_out is None else xw_out
+    inlier = torch.empty((batch, stride), dtype=torch.uint8, device=dev) if inlier is None else inlier
+    ninliers = torch.empty((batch,), dtype=torch.int32, device=dev) if ninliers is None else ninliers
+    cost = torch.empty((batch,), dtype=torch.float64, device=dev) if cost is None else cost
+    status = torch.empty((batch,), dtype=torch.int32, device=dev) if status is None else status
+    work = torch.empty((batch, 2), dtype=torch.int32, device=dev) if work is None else work
+    ctx.check(ctx.lib.pislam_global_ba_batch(ctx.h, ctypes.byref(p), ptr(poses), ptr(cams), ptr(fixed), ptr(kf_counts),
+                                             ptr(xw), ptr(pt_counts), ptr(obs_q8), ptr(obs_kf), ptr(obs_pt), ptr(level),
+                                             ptr(counts), ptr(kf_ptr), ptr(kf_obs), tab, ntab, kfs, pts, stride, batch,
+                                             ptr(poses_out), ptr(xw_out), ptr(inlier), ptr(ninliers), ptr(cost),
+                                             ptr(status), ptr(work)), "pislam_global_ba_batch")
+    return poses_out, xw_out, inlier, ninliers, cost, status, work
+
+
 # ---- bag of words: integer weights and the key-frame database ----------
 BOW_MAX_STRIDE = 16384      # entries of a bag-of-words vector (pislam_bow_vector_batch)
 
