@@ -2242,8 +2242,8 @@ int pislam_local_ba_batch(pislam_ctx *ctx, const pislam_ba_params *p, const floa
  * launch, so a single large graph uses one compute unit; a batch above 1024 graphs is walked by the same 1024
  * workgroups in passes.
  *
- * Not here: a robust kernel, a several-workgroup form for one large graph.  The bundle adjustment of the whole map that
- * follows the correction is pislam_global_ba_batch, below.  The spanning-tree and covisibility edges of the graph come from pislam_covisibility_batch, below. */
+ * Not here: a robust kernel, a several-workgroup form for one large graph.  That form is a call of its own,
+ * pislam_pose_graph_wide_batch, below.  The bundle adjustment of the whole map that follows the correction is pislam_global_ba_batch, below.  The spanning-tree and covisibility edges of the graph come from pislam_covisibility_batch, below. */
 typedef struct pislam_pose_graph_params {
   int32_t iters;     /* 1..64 Levenberg iterations (ORB-SLAM: 20) */
   int32_t cg_iters;  /* 1..1024 conjugate-gradient iterations of a solve at the most */
@@ -2255,6 +2255,43 @@ int pislam_pose_graph_batch(pislam_ctx *ctx, const pislam_pose_graph_params *p, 
                             const uint32_t *v_counts, const uint8_t *fixed, const uint32_t *edges, const float *meas,
                             const float *weight, const uint32_t *e_counts, const uint32_t *inc_ptr, const uint32_t *inc,
                             size_t v_stride, size_t e_stride, int batch, float *sims_out, double *cost, uint32_t *status);
+
+/* pislam_pose_graph_batch for large graphs: every phase of the call is one launch over all graphs of the batch and all
+ * of their edges or vertices, so one large graph uses the whole device.  The contract is the comment of
+ * pislam_pose_graph_batch, word for word: the residual, the Jacobians, the solve, every order of summation, the
+ * Levenberg rule, the refusals with their codes and their order, the outputs and the in-place rule (sims_out may be
+ * exactly sims: the state is read into the workspace before anything is written).  On the same inputs sims_out, cost
+ * and status are that call's, bit for bit.  tools/probes/graph_wide_host_check.cpp runs pgr::host_graph with these
+ * limits.  What differs:
+ *   work       uint32 [batch][2] or NULL, device: the solves attempted and the conjugate-gradient iterations made over
+ *              all of them; both 0 for the codes 1 to 3.  No overlap with an input or another output.
+ *   Limits     1 <= v_stride <= 65536 (what pislam_map_points_correct_batch accepts), 1 <= e_stride <= 2^20, so an
+ *              entry edge << 1 | side fits 32 bits; batch >= 0; p as in pislam_pose_graph_params.
+ *   Workspace  per GRAPH of the batch, not per workgroup: a control block of 256 bytes, then 944 bytes per vertex of
+ *              v_stride and 336 per edge of e_stride (pislam_pose_graph_batch's slice plus one binary64 term of the sums
+ *              per vertex and per edge; each array rounded up to 16 bytes, the slice to 256: 395 MiB for one graph at
+ *              the limits).  It is a buffer of its own in the context and grows on demand, which synchronises; after
+ *              pislam_pose_graph_wide_reserve of the same or a larger shape and batch the call allocates nothing, never
+ *              synchronises and can be captured into a hipGraph (one memset node and a single chain of kernel nodes).
+ *   Launches   the host issues a fixed sequence from p alone and reads nothing back:
+ *                5 + iters * (5 + 6 * cg_iters)
+ *              launches (the checks, the load, the first evaluation and its rule; per Levenberg iteration the set-up
+ *              and the start of the solve, six launches per conjugate-gradient iteration, the retraction, the evaluation
+ *              and the rule; the outputs).  A graph that is refused, has converged, or whose solve has met its
+ *              stopping rule skips the remaining launches from its control block, but the launches are still issued:
+ *              iters * cg_iters is paid in launches (a few microseconds each), not only in work.  At the parameter
+ *              limits that is 393 541 launches; choose cg_iters for the graph at hand.  The grid of a launch follows
+ *              the strides: (graph, group of 256 items) pairs, at most 65536 workgroups, more are walked in passes.
+ * Which call: this one for a graph of more than a few hundred vertices or beyond the other's limits;
+ * pislam_pose_graph_batch for batches of many small graphs (INTEGRATION.md has the measured crossover).
+ * Any violation of the limits, or a NULL or host pointer where a device pointer is required (weight and work alone may
+ * be NULL): PISLAM_ERR_INVALID, before anything is launched or written. */
+int pislam_pose_graph_wide_reserve(pislam_ctx *ctx, size_t v_stride, size_t e_stride, int batch);
+int pislam_pose_graph_wide_batch(pislam_ctx *ctx, const pislam_pose_graph_params *p, const float *sims,
+                                 const uint32_t *v_counts, const uint8_t *fixed, const uint32_t *edges, const float *meas,
+                                 const float *weight, const uint32_t *e_counts, const uint32_t *inc_ptr,
+                                 const uint32_t *inc, size_t v_stride, size_t e_stride, int batch, float *sims_out,
+                                 double *cost, uint32_t *status, uint32_t *work);
 
 /* The last step of LoopClosing::CorrectLoop: every map point moves with its reference key frame.  Point p < npt =
  * min(pt_counts[b], pt_stride) of element b with k = ref[p]: in binary64, one rounded operation at a time, with O =

@@ -231,6 +231,9 @@ SYMBOLS = {
     "pislam_pose_graph_reserve": (_i, [_vp, _sz, _sz, _i]),
     "pislam_pose_graph_batch": (_i, [_vp, ctypes.POINTER(PoseGraphParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                      _sz, _i, _vp, _vp, _vp]),
+    "pislam_pose_graph_wide_reserve": (_i, [_vp, _sz, _sz, _i]),
+    "pislam_pose_graph_wide_batch": (_i, [_vp, ctypes.POINTER(PoseGraphParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                          _sz, _i, _vp, _vp, _vp, _vp]),
     "pislam_map_points_correct_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i, _vp, _vp]),
     "pislam_covisibility_reserve": (_i, [_vp, _sz, _sz, _i]),
     "pislam_covisibility_batch": (_i, [_vp, ctypes.POINTER(CovisParams), _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _i, _vp,

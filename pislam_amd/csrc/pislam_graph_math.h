@@ -1,6 +1,7 @@
 // pislam_graph_math.h — the arithmetic of pislam_pose_graph_batch and pislam_map_points_correct_batch (include/
-// pislam_hip.h: those comments are the contract), stated ONCE for the device kernels (pislam_graph_kernels.h) and for a
-// plain C++ compiler (tools/probes/graph_host_check.cpp): composition and error of an edge, the rational residual, the
+// pislam_hip.h: those comments are the contract), stated ONCE for the device kernels (pislam_graph_kernels.h, and
+// pislam_graph_wide_kernels.h for pislam_pose_graph_wide_batch) and for a plain C++ compiler (tools/probes/
+// graph_host_check.cpp, graph_wide_host_check.cpp): composition and error of an edge, the rational residual, the
 // structured Jacobians applied to a 7-vector and as a diagonal block, the pivot-free 7 x 7 factorisation, the steps of
 // the block-Jacobi preconditioned conjugate gradients as the owner of an edge or of a vertex takes them, the workspace
 // slice of a graph and, for the host only, the whole call for one graph run serially.  The retraction is
@@ -14,7 +15,7 @@ namespace pgr {
 using psm::finite_d;
 using psm::finite_f;
 
-constexpr int MAX_V = 4096, MAX_E = 16384;
+constexpr int MAX_V = 4096, MAX_E = 16384;      // of pislam_pose_graph_batch (the wide call: pgw::MAX_V, pgw::MAX_E)
 constexpr int STATE = 13, DIM = 7, TRI = 28, FAC = 49;
 constexpr double ROT_MIN = 0x1p-10;            // an edge is admissible while 1 + tr R_E exceeds this
 

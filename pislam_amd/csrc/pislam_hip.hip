@@ -71,6 +71,7 @@ __device__ const BriefOfsTab g_brief_ofs = make_brief_ofs();
 #include "pislam_ba_kernels.h"
 #include "pislam_graph_kernels.h"
 #include "pislam_gba_kernels.h"
+#include "pislam_graph_wide_kernels.h"
 #include "pislam_covis_kernels.h"
 #include "pislam_mapupdate_kernels.h"
 #include "pislam_warp_kernels.h"
@@ -142,6 +143,7 @@ struct pislam_ctx {
   CellIndex w_epi;                   // epipolar matcher (pe::k_epi_index): group offsets, group-sorted entries with their geometry (meta), descriptors
   DevBuf w_ba;                       // local bundle adjustment (pbk::k_local_ba): a slice per workgroup (pbk::ws_bytes)
   DevBuf w_pg;                       // essential-graph optimisation (pgk::k_pose_graph): a slice per workgroup (pgr::ws_bytes)
+  DevBuf w_pgw;                      // essential graphs across workgroups (pgw::k_pgw_*): a control block and a slice per graph
   DevBuf w_gba;                      // global bundle adjustment (gbk::k_gba_*): a control block and a slice per map (gba::ws_bytes)
   DevBuf w_cv;                       // covisibility graph (pcvk::k_covis_count, k_covis_rows): matrices, counters, flags (pcv::ws_bytes)
   DevBuf w_db;                       // key-frame database query (pd::k_db_accumulate .. k_db_merge): accumulator planes, maxima, partial lists
@@ -525,6 +527,7 @@ PISLAM_EXPORT int pislam_ctx_destroy(pislam_ctx *c) {
   c->w_ba.release();
   c->w_pg.release();
   c->w_gba.release();
+  c->w_pgw.release();
   c->w_cv.release();
   for (auto *t : c->plan_tables) {
     t->dev.release();
@@ -3135,6 +3138,14 @@ int pose_graph_shape(pislam_ctx *c, size_t v_stride, size_t e_stride, int batch)
   return PISLAM_OK;
 }
 
+int pose_graph_params_ok(pislam_ctx *c, const pislam_pose_graph_params *p) {
+  if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
+  if (p->iters < 1 || p->iters > 64) return fail(c, PISLAM_ERR_INVALID, "iters must be 1..64");
+  if (p->cg_iters < 1 || p->cg_iters > 1024) return fail(c, PISLAM_ERR_INVALID, "cg_iters must be 1..1024");
+  if (!(p->cg_tol >= 0.0 && p->cg_tol < 1.0)) return fail(c, PISLAM_ERR_INVALID, "cg_tol must be in [0, 1)");
+  return check_refine_eps(c, p->eps);
+}
+
 int pose_graph_workspace(pislam_ctx *c, size_t v_stride, size_t e_stride, int batch) {
   const size_t groups = (size_t)std::min(batch, prf::GRID_CAP);
   if (c->w_pg.ensure(pgr::ws_bytes(v_stride, e_stride) * groups) != PISLAM_OK)
@@ -3158,11 +3169,7 @@ PISLAM_EXPORT int pislam_pose_graph_batch(pislam_ctx *c, const pislam_pose_graph
                                           const uint32_t *inc_ptr, const uint32_t *inc, size_t v_stride, size_t e_stride,
                                           int batch, float *sims_out, double *cost, uint32_t *status) {
   if (!c) return PISLAM_ERR_INVALID;
-  if (!p) return fail(c, PISLAM_ERR_INVALID, "null parameters");
-  if (p->iters < 1 || p->iters > 64) return fail(c, PISLAM_ERR_INVALID, "iters must be 1..64");
-  if (p->cg_iters < 1 || p->cg_iters > 1024) return fail(c, PISLAM_ERR_INVALID, "cg_iters must be 1..1024");
-  if (!(p->cg_tol >= 0.0 && p->cg_tol < 1.0)) return fail(c, PISLAM_ERR_INVALID, "cg_tol must be in [0, 1)");
-  PCHK(check_refine_eps(c, p->eps));
+  PCHK(pose_graph_params_ok(c, p));
   PCHK(pose_graph_shape(c, v_stride, e_stride, batch));
   if (batch == 0) return PISLAM_OK;
   const char *what = "the pose graph call takes device pointers only";
@@ -3216,6 +3223,98 @@ PISLAM_EXPORT int pislam_map_points_correct_batch(pislam_ctx *c, const float *xw
   hipLaunchKernelGGL(pgk::k_map_points_correct, dim3((unsigned)std::min<size_t>(groups, pgk::MC_GRID_CAP)),
                      dim3(pgk::MC_THREADS), 0, c->stream, a);
   return launch_ok(c, "k_map_points_correct");
+}
+
+// ---- essential-graph optimisation of large graphs across workgroups -------------------------
+
+namespace {
+
+int pose_graph_wide_shape(pislam_ctx *c, size_t v_stride, size_t e_stride, int batch) {
+  if (batch < 0) return fail(c, PISLAM_ERR_INVALID, "negative batch");
+  if (v_stride < 1 || v_stride > pgw::MAX_V) return fail(c, PISLAM_ERR_INVALID, "v_stride must be 1..65536");
+  if (e_stride < 1 || e_stride > pgw::MAX_E) return fail(c, PISLAM_ERR_INVALID, "e_stride must be 1..2^20");
+  return PISLAM_OK;
+}
+
+int pose_graph_wide_workspace(pislam_ctx *c, size_t v_stride, size_t e_stride, int batch, size_t *per_graph) {
+  *per_graph = pgw::ws_graph_bytes(v_stride, e_stride);
+  if (*per_graph + pgw::CTL_BYTES > SIZE_MAX / (size_t)batch) return fail(c, PISLAM_ERR_NOMEM, "the wide pose graph workspace");
+  if (c->w_pgw.ensure((*per_graph + pgw::CTL_BYTES) * (size_t)batch) != PISLAM_OK)
+    return fail(c, PISLAM_ERR_NOMEM, "hipMalloc(wide pose graph workspace)");
+  return PISLAM_OK;
+}
+
+}  // namespace
+
+PISLAM_EXPORT int pislam_pose_graph_wide_reserve(pislam_ctx *c, size_t v_stride, size_t e_stride, int batch) {
+  if (!c) return PISLAM_ERR_INVALID;
+  PCHK(pose_graph_wide_shape(c, v_stride, e_stride, batch));
+  if (batch == 0) return PISLAM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  size_t per_graph;
+  return pose_graph_wide_workspace(c, v_stride, e_stride, batch, &per_graph);
+}
+
+PISLAM_EXPORT int pislam_pose_graph_wide_batch(pislam_ctx *c, const pislam_pose_graph_params *p, const float *sims,
+                                               const uint32_t *v_counts, const uint8_t *fixed, const uint32_t *edges,
+                                               const float *meas, const float *weight, const uint32_t *e_counts,
+                                               const uint32_t *inc_ptr, const uint32_t *inc, size_t v_stride,
+                                               size_t e_stride, int batch, float *sims_out, double *cost, uint32_t *status,
+                                               uint32_t *work) {
+  if (!c) return PISLAM_ERR_INVALID;
+  PCHK(pose_graph_params_ok(c, p));
+  PCHK(pose_graph_wide_shape(c, v_stride, e_stride, batch));
+  if (batch == 0) return PISLAM_OK;
+  const char *what = "the wide pose graph call takes device pointers only";
+  PCHK(device_ptrs(c, {sims, v_counts, fixed, edges, meas, e_counts, inc_ptr, inc, sims_out, cost, status}, what));
+  if ((weight && !is_device_ptr(weight)) || (work && !is_device_ptr(work))) return fail(c, PISLAM_ERR_INVALID, what);
+  {
+    const size_t B = (size_t)batch, word = B * sizeof(uint32_t), sim = B * v_stride * 13 * sizeof(float);
+    const LkRange in[] = {{sims, sim}, {v_counts, word}, {fixed, B * v_stride}, {edges, B * e_stride * 2 * sizeof(uint32_t)},
+                          {meas, B * e_stride * 13 * sizeof(float)}, {weight, B * e_stride * sizeof(float)}, {e_counts, word},
+                          {inc_ptr, B * (v_stride + 1) * sizeof(uint32_t)}, {inc, B * e_stride * 2 * sizeof(uint32_t)}};
+    const LkRange out[] = {{sims_out, sim}, {cost, B * sizeof(double)}, {status, word}, {work, 2 * word}};
+    // sims_out == sims is allowed: the state is read into the workspace before anything is written
+    if (const char *bad = ranges_overlap(in, out, 0)) return fail(c, PISLAM_ERR_INVALID, bad);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  pgw::WideArgs a{};
+  PCHK(pose_graph_wide_workspace(c, v_stride, e_stride, batch, &a.ws_graph));
+  a.sims = sims, a.meas = meas, a.weight = weight, a.fixed = fixed, a.v_counts = v_counts, a.e_counts = e_counts;
+  a.edges = edges, a.inc_ptr = inc_ptr, a.inc = inc, a.v_stride = v_stride, a.e_stride = e_stride, a.batch = (size_t)batch;
+  a.p = pgr::Params{p->iters, p->cg_iters, p->cg_tol, p->eps};
+  a.sims_out = sims_out, a.cost = cost, a.status = status, a.work = work, a.ws = c->w_pgw.as<char>();
+  // the control blocks start from zero: the checks only raise flags
+  HIPCHK(c, hipMemsetAsync(a.ws, 0, a.batch * pgw::CTL_BYTES, c->stream));
+  const size_t V = v_stride, E = e_stride, T = pgw::THREADS;
+  int rc = PISLAM_OK;
+  auto run = [&](auto kernel, size_t per_graph, size_t group, const char *name, auto... more) {
+    if (rc != PISLAM_OK) return;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)pgw::groups_of(a, per_graph, group)), dim3(pgw::THREADS), 0, c->stream, a, more...);
+    rc = launch_ok(c, name);
+  };
+  // the fixed sequence of pgw::launch_count(): nothing is read back, a graph's control block gates every launch
+  run(pgw::k_pgw_check, E + V, T, "k_pgw_check");
+  run(pgw::k_pgw_load, V + E, T, "k_pgw_load");
+  run(pgw::k_pgw_eval, E, T, "k_pgw_eval", (int)pgw::FIRST);
+  run(pgw::k_pgw_decide, 1, 1, "k_pgw_decide", (int)pgw::FIRST);
+  for (int it = 0; it < p->iters; it++) {
+    run(pgw::k_pgw_setup, V, T, "k_pgw_setup");
+    run(pgw::k_pgw_cg_scalar, 1, 1, "k_pgw_cg_scalar", (int)pgw::BEGIN, 0);
+    for (int n = 0; n < p->cg_iters; n++) {
+      run(pgw::k_pgw_edge_v, E, T, "k_pgw_edge_v");
+      run(pgw::k_pgw_cg_vertex, V, T, "k_pgw_cg_vertex", (int)pgw::AP);
+      run(pgw::k_pgw_cg_scalar, 1, 1, "k_pgw_cg_scalar", (int)pgw::ALPHA, n);
+      run(pgw::k_pgw_cg_vertex, V, T, "k_pgw_cg_vertex", (int)pgw::UPDATE);
+      run(pgw::k_pgw_cg_scalar, 1, 1, "k_pgw_cg_scalar", (int)pgw::BETA, n);
+      run(pgw::k_pgw_cg_vertex, V, T, "k_pgw_cg_vertex", (int)pgw::P);
+    }
+    run(pgw::k_pgw_retract, V, T, "k_pgw_retract");
+    run(pgw::k_pgw_eval, E, T, "k_pgw_eval", (int)pgw::TRIAL);
+    run(pgw::k_pgw_decide, 1, 1, "k_pgw_decide", (int)pgw::TRIAL);
+  }
+  run(pgw::k_pgw_out, pgr::STATE * V, T, "k_pgw_out");
+  return rc;
 }
 
 // ---- the covisibility graph of a map -------------------------------------------------------------

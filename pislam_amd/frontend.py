@@ -1800,6 +1800,7 @@ def localBundleAdjustBatch(poses, cams, kf_counts, kf_free, xw, pt_counts, obs_q
 
 # ---- after a loop is accepted: essential-graph optimisation, map points moved ----------
 POSE_GRAPH_MAX_VERTICES, POSE_GRAPH_MAX_EDGES = 4096, 16384
+POSE_GRAPH_WIDE_MAX_VERTICES, POSE_GRAPH_WIDE_MAX_EDGES = 65536, 1 << 20     # poseGraphWideBatch
 
 
 def relativeSim3(sim_i, sim_j):
@@ -1814,7 +1815,7 @@ def relativeSim3(sim_i, sim_j):
     return torch.cat([R.reshape(*a.shape[:-1], 9), t, s], dim=-1).to(torch.float32)
 
 
-def essentialGraph(sims, fixed, pairs, meas=None, weight=None):
+def essentialGraph(sims, fixed, pairs, meas=None, weight=None, *, wide=False):
     """The padded batch arrays and the incidence index of poseGraphBatch from per-graph lists.  One graph: sims float32
     [nv][13] (world to camera, the sim_out layout), fixed a boolean or integer tensor [nv] (nonzero: held), pairs an
     integer tensor [ne][2] = (i, j); a batch: lists of such tensors, one entry per graph.  meas: None, or float32
@@ -1825,6 +1826,7 @@ def essentialGraph(sims, fixed, pairs, meas=None, weight=None):
     [batch][e_stride][13], weight float32 [batch][e_stride] or None, e_counts int32, inc_ptr int32
     [batch][v_stride + 1], inc int32 [batch][2 * e_stride]) with the strides of the largest graph (at least 1).  A vertex's
     entries edge << 1 | side are ascending.  The pairs are not checked: the call refuses a malformed graph with code 3.
+    wide=True: the graph is for poseGraphWideBatch and is held to its limits (65536 vertices, 2^20 edges) instead.
     Torch ops on the current torch stream."""
     import torch
     one = not isinstance(sims, (list, tuple))
@@ -1839,8 +1841,10 @@ def essentialGraph(sims, fixed, pairs, meas=None, weight=None):
     dev = sims[0].device
     V = max(max(int(s.shape[0]) for s in sims), 1)
     E = max(max(int(p.shape[0]) for p in pairs), 1)
-    if V > POSE_GRAPH_MAX_VERTICES or E > POSE_GRAPH_MAX_EDGES:
-        raise ValueError(f"at most {POSE_GRAPH_MAX_VERTICES} vertices and {POSE_GRAPH_MAX_EDGES} edges per graph")
+    max_v, max_e = ((POSE_GRAPH_WIDE_MAX_VERTICES, POSE_GRAPH_WIDE_MAX_EDGES) if wide else
+                    (POSE_GRAPH_MAX_VERTICES, POSE_GRAPH_MAX_EDGES))
+    if V > max_v or E > max_e:
+        raise ValueError(f"at most {max_v} vertices and {max_e} edges per graph")
     o_s = torch.zeros((B, V, 13), dtype=torch.float32, device=dev)
     o_f = torch.zeros((B, V), dtype=torch.uint8, device=dev)
     o_e = torch.zeros((B, E, 2), dtype=torch.int32, device=dev)
@@ -1884,6 +1888,27 @@ def reservePoseGraph(v_stride: int, e_stride: int, batch: int, *, ctx: Context |
     ctx.check(ctx.lib.pislam_pose_graph_reserve(ctx.h, int(v_stride), int(e_stride), int(batch)), "pislam_pose_graph_reserve")
 
 
+def _pose_graph_shape(sims, edges):
+    """The first tensor checks of poseGraphBatch and poseGraphWideBatch: (batch, v_stride, e_stride)."""
+    import torch
+    batch, V = _tensor(sims, torch.float32, (None, None, 13), "sims must be a float32 tensor [batch][v_stride][13]")
+    E, = _tensor(edges, _word32(), (batch, None, 2), "edges must be a 32-bit integer tensor [batch][e_stride][2]")
+    return batch, V, E
+
+
+def _pose_graph_rest(batch, V, E, sims, v_counts, fixed, edges, meas, weight, e_counts, inc_ptr, inc):
+    """The tensor checks that follow the limits, in their order."""
+    import torch
+    _tensor(fixed, torch.uint8, (batch, V), "fixed must be a uint8 tensor [batch][v_stride]")
+    _tensor(meas, torch.float32, (batch, E, 13), "meas must be a float32 tensor [batch][e_stride][13]")
+    if weight is not None:
+        _tensor(weight, torch.float32, (batch, E), "weight must be a float32 tensor [batch][e_stride]")
+    for t, shape in ((v_counts, (batch,)), (e_counts, (batch,)), (inc_ptr, (batch, V + 1)), (inc, (batch, 2 * E))):
+        _tensor(t, _word32(), shape, "v_counts, e_counts [batch], inc_ptr [batch][v_stride + 1] and inc [batch][2 * e_stride] "
+                                     "must be 32-bit integer tensors")
+    _contiguous(sims, v_counts, fixed, edges, meas, e_counts, inc_ptr, inc, weight)
+
+
 def poseGraphBatch(sims, v_counts, fixed, edges, meas, weight, e_counts, inc_ptr, inc, *, iters=20, cg_iters=256,
                    cg_tol=1e-6, eps=1e-9, sims_out=None, cost=None, status=None, ctx: Context | None = None):
     """Batched essential-graph optimisation (pislam_pose_graph_batch; the contract is the comment in include/
@@ -1896,21 +1921,14 @@ def poseGraphBatch(sims, v_counts, fixed, edges, meas, weight, e_counts, inc_ptr
     Returns (sims_out, cost float64 [batch], status int32 [batch] = code | evaluations << 8; code 0 ok, 1 nothing to do,
     2 a bad value or an inadmissible input state, 3 the graph is malformed).  sims_out may be `sims`.  The same inputs
     give the same outputs, bit for bit.  Asynchronous on the ctx stream; capturable after reservePoseGraph.  Key-frame
-    poses afterwards: rigidFromSim3(sims_out[b])."""
+    poses afterwards: rigidFromSim3(sims_out[b]).  One workgroup runs a graph: for a large graph, or one beyond 4096
+    vertices or 16384 edges, use poseGraphWideBatch."""
     import torch
     ctx = ctx or default_context()
-    batch, V = _tensor(sims, torch.float32, (None, None, 13), "sims must be a float32 tensor [batch][v_stride][13]")
-    E, = _tensor(edges, _word32(), (batch, None, 2), "edges must be a 32-bit integer tensor [batch][e_stride][2]")
+    batch, V, E = _pose_graph_shape(sims, edges)
     if V > POSE_GRAPH_MAX_VERTICES or E > POSE_GRAPH_MAX_EDGES:
         raise ValueError(f"at most {POSE_GRAPH_MAX_VERTICES} vertices and {POSE_GRAPH_MAX_EDGES} edges per graph")
-    _tensor(fixed, torch.uint8, (batch, V), "fixed must be a uint8 tensor [batch][v_stride]")
-    _tensor(meas, torch.float32, (batch, E, 13), "meas must be a float32 tensor [batch][e_stride][13]")
-    if weight is not None:
-        _tensor(weight, torch.float32, (batch, E), "weight must be a float32 tensor [batch][e_stride]")
-    for t, shape in ((v_counts, (batch,)), (e_counts, (batch,)), (inc_ptr, (batch, V + 1)), (inc, (batch, 2 * E))):
-        _tensor(t, _word32(), shape, "v_counts, e_counts [batch], inc_ptr [batch][v_stride + 1] and inc [batch][2 * e_stride] "
-                                     "must be 32-bit integer tensors")
-    _contiguous(sims, v_counts, fixed, edges, meas, e_counts, inc_ptr, inc, weight)
+    _pose_graph_rest(batch, V, E, sims, v_counts, fixed, edges, meas, weight, e_counts, inc_ptr, inc)
     p = capi.PoseGraphParams(int(iters), int(cg_iters), float(cg_tol), float(eps))
     dev = sims.device
     sims_out = torch.empty_like(sims) if sims_out is None else sims_out
@@ -1920,6 +1938,44 @@ def poseGraphBatch(sims, v_counts, fixed, edges, meas, weight, e_counts, inc_ptr
                                               ptr(meas), ptr(weight), ptr(e_counts), ptr(inc_ptr), ptr(inc), V, E, batch,
                                               ptr(sims_out), ptr(cost), ptr(status)), "pislam_pose_graph_batch")
     return sims_out, cost, status
+
+
+def reservePoseGraphWide(v_stride: int, e_stride: int, batch: int, *, ctx: Context | None = None):
+    """Size the context's workspace for poseGraphWideBatch calls of up to this shape and batch
+    (pislam_pose_graph_wide_reserve): afterwards such calls allocate nothing and never synchronise, so they can be
+    captured into a hipGraph.  The workspace is per graph: 944 bytes per vertex and 336 per edge of the strides."""
+    ctx = ctx or default_context()
+    ctx.check(ctx.lib.pislam_pose_graph_wide_reserve(ctx.h, int(v_stride), int(e_stride), int(batch)),
+              "pislam_pose_graph_wide_reserve")
+
+
+def poseGraphWideBatch(sims, v_counts, fixed, edges, meas, weight, e_counts, inc_ptr, inc, *, iters=20, cg_iters=256,
+                       cg_tol=1e-6, eps=1e-9, sims_out=None, cost=None, status=None, work=None,
+                       ctx: Context | None = None):
+    """poseGraphBatch for large graphs (pislam_pose_graph_wide_batch): the same arguments, keywords, defaults and
+    checks, the same outputs bit for bit, but every phase of the optimisation is one launch over all edges or vertices of
+    all graphs, so one large graph uses the whole device, and the limits are 65536 vertices and 2^20 edges per graph
+    (essentialGraph(..., wide=True)).  Returns (sims_out, cost, status, work); work int32 [batch][2] = the solves
+    attempted and the conjugate-gradient iterations made.  The call issues 5 + iters * (5 + 6 * cg_iters) launches
+    whatever the graphs need, so iters * cg_iters is paid in launches: prefer poseGraphBatch for batches of many small
+    graphs.  Asynchronous on the ctx stream; capturable after reservePoseGraphWide."""
+    import torch
+    ctx = ctx or default_context()
+    batch, V, E = _pose_graph_shape(sims, edges)
+    if V > POSE_GRAPH_WIDE_MAX_VERTICES or E > POSE_GRAPH_WIDE_MAX_EDGES:
+        raise ValueError(f"at most {POSE_GRAPH_WIDE_MAX_VERTICES} vertices and {POSE_GRAPH_WIDE_MAX_EDGES} edges per graph")
+    _pose_graph_rest(batch, V, E, sims, v_counts, fixed, edges, meas, weight, e_counts, inc_ptr, inc)
+    p = capi.PoseGraphParams(int(iters), int(cg_iters), float(cg_tol), float(eps))
+    dev = sims.device
+    sims_out = torch.empty_like(sims) if sims_out is None else sims_out
+    cost = torch.empty((batch,), dtype=torch.float64, device=dev) if cost is None else cost
+    status = torch.empty((batch,), dtype=torch.int32, device=dev) if status is None else status
+    work = torch.empty((batch, 2), dtype=torch.int32, device=dev) if work is None else work
+    ctx.check(ctx.lib.pislam_pose_graph_wide_batch(ctx.h, ctypes.byref(p), ptr(sims), ptr(v_counts), ptr(fixed), ptr(edges),
+                                                   ptr(meas), ptr(weight), ptr(e_counts), ptr(inc_ptr), ptr(inc), V, E,
+                                                   batch, ptr(sims_out), ptr(cost), ptr(status), ptr(work)),
+              "pislam_pose_graph_wide_batch")
+    return sims_out, cost, status, work
 
 
 def correctMapPointsBatch(xw, ref, pt_counts, sims_old, sims_new, v_counts, *, xw_out=None, status=None,
@@ -1947,7 +2003,8 @@ def correctMapPointsBatch(xw, ref, pt_counts, sims_old, sims_new, v_counts, *, x
 
 
 # ---- the covisibility graph: weights, ordered neighbours, spanning tree, culling statistic ----------
-COVIS_MAX_KF = 4096         # == POSE_GRAPH_MAX_VERTICES: a map that fits covisibilityBatch fits poseGraphBatch
+COVIS_MAX_KF = 4096         # == POSE_GRAPH_MAX_VERTICES: a map that fits covisibilityBatch fits poseGraphBatch in its
+                            # vertices; its essential graph may have more than 16384 edges: poseGraphWideBatch
 
 
 def mapObservations(obs_kf, obs_pt, counts, *more):

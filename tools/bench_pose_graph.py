@@ -1,5 +1,5 @@
-"""Batched essential-graph optimisation (pislam_pose_graph_batch) on synthetic loops, next to a device copy of its input
-bytes; prints one JSON line.
+"""Batched essential-graph optimisation (pislam_pose_graph_batch, and pislam_pose_graph_wide_batch on the same inputs) on
+synthetic loops, next to a device copy of its input bytes; prints one JSON line.
 
 Setup: a key-frame trajectory on a ring, world to camera, its odometry drifted (every relative motion off by about 0.003
 rad, 0.015 units and 0.3 % of scale), vertex 0 held; a chain edge between consecutive key frames and covisibility edges
@@ -11,7 +11,16 @@ median device-event time of single calls after a warm-up (the workspace is reser
 Levenberg iterations at the most, and a device-to-device copy of its input bytes.  `evaluations` is the mean number of
 evaluations of F (status >> 8); `cg_per_solve` the mean conjugate-gradient iterations of a solve, taken from the host
 probe (tools/probes/graph_host_check.cpp: the same arithmetic, word for word) on the same graphs, null without a host
-compiler; map-point correction of `points` points per graph is timed beside the small shape."""
+compiler; map-point correction of `points` points per graph is timed beside the small shape.
+
+The several-workgroup call runs on the same device buffers in the same run (`wide_ms`; `wide_equals_old`: its sims_out,
+cost and status are the other call's byte for byte; `wide_solves` and `wide_cg_per_solve` from its work output;
+`wide_launches` the launches it issues, which depend on the parameters alone), and once more with an eps that every
+first step meets (`wide_early_ms`): all graphs finish in the first Levenberg iteration, and what remains is the cost of
+the launches that find nothing to do.  A third shape, ONE graph of `wide_vertices` vertices and about `wide_edges`
+edges, is beyond pislam_pose_graph_batch's limits and is timed through the several-workgroup call alone.  The tool
+exits with an error if the two calls' bytes differ on a shape both take, or if the several-workgroup call is not the
+faster one on the one large graph."""
 from __future__ import annotations
 
 import argparse
@@ -48,8 +57,9 @@ def inv(A):
     return sims_of(Rt, -np.einsum("nij,nj->ni", Rt, A[:, 9:12]) / A[:, 12:13], 1.0 / A[:, 12])
 
 
-def loop_graph(rng, nv, ne):
-    """(sims float32 [nv][13], fixed, pairs [ne'][2], loop measurement [1][13])."""
+def loop_graph(rng, nv, ne, span=8):
+    """(sims float32 [nv][13], fixed, pairs [ne'][2], loop measurement [1][13]); covisibility edges reach below `span`
+    places on."""
     a = 2 * np.pi * np.arange(nv) / nv
     R = rotations(np.stack([np.zeros(nv), a, np.zeros(nv)], 1)) @ rotations(rng.normal(0, 0.05, (nv, 3)))
     c = np.stack([4 * np.cos(a), rng.normal(0, 0.1, nv), 4 * np.sin(a)], 1)
@@ -66,7 +76,7 @@ def loop_graph(rng, nv, ne):
     pairs = {(k, k + 1) for k in range(nv - 1)}
     while len(pairs) < ne - 1:
         i = int(rng.integers(0, nv - 2))
-        pairs.add((i, int(min(i + rng.integers(2, 8), nv - 1))))
+        pairs.add((i, int(min(i + rng.integers(2, span), nv - 1))))
     pairs = sorted(pairs) + [(nv - 1, 0)]
     fixed = np.zeros(nv, np.uint8)
     fixed[0] = 1
@@ -110,6 +120,8 @@ def main():
     ap.add_argument("--edges", type=int, default=300)
     ap.add_argument("--big-vertices", type=int, default=2048)
     ap.add_argument("--big-edges", type=int, default=10000)
+    ap.add_argument("--wide-vertices", type=int, default=4096)
+    ap.add_argument("--wide-edges", type=int, default=40000)
     ap.add_argument("--points", type=int, default=4096, help="map points per graph moved by the correction call")
     ap.add_argument("--lm-iters", type=int, default=20)
     ap.add_argument("--cg-iters", type=int, default=256)
@@ -123,7 +135,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_pose_graph needs a GPU (there is no CPU fallback)")
     from pislam_amd.capi import Context
-    from pislam_amd.frontend import correctMapPointsBatch, essentialGraph, poseGraphBatch, reservePoseGraph
+    from pislam_amd.frontend import (correctMapPointsBatch, essentialGraph, poseGraphBatch, poseGraphWideBatch, reservePoseGraph,
+                                     reservePoseGraphWide)
     rng = np.random.default_rng(args.seed)
     dev = torch.device("cuda:0")
     stream = torch.cuda.Stream(dev)
@@ -132,6 +145,26 @@ def main():
     prm = (args.lm_iters, args.cg_iters, args.cg_tol, args.eps)
     kw = dict(iters=prm[0], cg_iters=prm[1], cg_tol=prm[2], eps=prm[3])
     res = {}
+
+    def wide(G, B, old):
+        """The several-workgroup call on the arrays G: its entries of a result."""
+        reservePoseGraphWide(int(G[0].shape[1]), int(G[3].shape[1]), B, ctx=ctx)
+        names = ("sims_out", "cost", "status", "work")
+        keep = dict(zip(names, poseGraphWideBatch(*G, ctx=ctx, **kw)))
+        ms = timed(lambda: poseGraphWideBatch(*G, ctx=ctx, **kw, **keep), stream, torch, args.warmup, args.iters)
+        stream.synchronize()
+        work = keep["work"].cpu().numpy().astype(np.int64)
+        r = {"wide_ms": round(ms, 4), "wide_launches": 5 + prm[0] * (5 + 6 * prm[1]), "wide_solves": round(float(work[:, 0].mean()), 2),
+             "wide_cg_per_solve": round(float(work[:, 1].sum()) / max(int(work[:, 0].sum()), 1), 2)}
+        if old is not None:
+            r["wide_equals_old"] = all(keep[k].cpu().numpy().tobytes() == old[k].cpu().numpy().tobytes() for k in names[:3])
+        early = dict(zip(names, poseGraphWideBatch(*G, ctx=ctx, **dict(kw, eps=1e30))))
+        r["wide_early_ms"] = round(timed(lambda: poseGraphWideBatch(*G, ctx=ctx, **dict(kw, eps=1e30), **early), stream, torch,
+                                         args.warmup, args.iters), 4)
+        stream.synchronize()
+        r["wide_early_evaluations"] = round(float((early["status"].cpu().numpy() >> 8).mean()), 2)
+        return r, keep
+
     with torch.cuda.stream(stream):
         for tag, B, nv, ne in (("batch", args.graphs, args.vertices, args.edges), ("big", 1, args.big_vertices, args.big_edges)):
             gs = [loop_graph(rng, nv, ne) for _ in range(B)]
@@ -161,9 +194,32 @@ def main():
                 r["correct_points_ms"] = round(timed(lambda: correctMapPointsBatch(xw, ref, cnt, G[0], keep["sims_out"], G[1], ctx=ctx,
                                                                                    **pk), stream, torch, args.warmup, args.iters), 4)
                 r["points"] = B * P
+            r.update(wide(G, B, keep)[0])
             res[tag] = r
+        nv, ne = args.wide_vertices, args.wide_edges
+        g = loop_graph(rng, nv, ne, span=max(8, 2 * ne // nv))
+        G = essentialGraph(T(g[0]), T(g[1]), T(g[2]), T(g[3]), wide=True)
+        r, keep = wide(G, 1, None)
+        ins = [x for x in G if x is not None]
+        dst = [torch.empty_like(a) for a in ins]
+
+        def copy_wide():
+            for d, s in zip(dst, ins):
+                d.copy_(s)
+        status = keep["status"].cpu().numpy()
+        res["wide"] = dict({"graphs": 1, "vertices": nv, "mean_edges": float(G[6].float().mean()),
+                            "copy_inputs_ms": round(timed(copy_wide, stream, torch, args.warmup, args.iters), 4),
+                            "input_bytes": int(sum(a.numel() * a.element_size() for a in ins)),
+                            "codes_ok": int((status & 255 == 0).sum()), "evaluations": round(float((status >> 8).mean()), 2),
+                            "mean_cost": float(keep["cost"].cpu().numpy().mean())}, **r)
         stream.synchronize()
     print(json.dumps({"tool": "bench_pose_graph", "iters": args.iters, "params": kw, "results": res}))
+    # what the several-workgroup call is for: the same bytes, and less time on the one large graph
+    for tag in ("batch", "big"):
+        if not res[tag]["wide_equals_old"]:
+            raise SystemExit(f"{tag}: pislam_pose_graph_wide_batch's outputs differ from pislam_pose_graph_batch's")
+    if not res["big"]["wide_ms"] < res["big"]["pose_graph_ms"]:
+        raise SystemExit("big: pislam_pose_graph_wide_batch is not faster than pislam_pose_graph_batch")
 
 
 if __name__ == "__main__":
